@@ -94,9 +94,16 @@ def parse():
                          "processes, the reference's own call (default; the opt-in route is then measured after the timed region as "
                          "`native_delaunay`), 'native' = optim_params['hip_delaunay'] = 'native' (same_amd/delaunay.py)")
     ap.add_argument("--dry-launch", action="store_true", help="ranks only rendezvous (no GPU): launcher / control-plane check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed loop, write what its last step computed (rank 0's outputs) as DIR/<name>.npy in float32 / "
+                         "float64, at most 64 MB in all (large outputs as a fixed, seeded sample): see dump_outputs")
     args = ap.parse_args()
     if args.workload is None:
         args.workload = "cfg4" if args.scaling == "strong" else "dense100k"
+    if args.dump_outputs is not None and args.workload == "cfg5":
+        ap.error("--dump-outputs covers the dense-build workloads, not --workload cfg5")
+    if args.dump_outputs is not None and args.steps < 1:
+        ap.error("--dump-outputs needs --steps >= 1: it writes what the last timed step computed")
     return args
 
 
@@ -167,6 +174,8 @@ def run_rank(args):
     note(group, f"warm-up ({args.warmup}) + timed loop ({args.steps} steps)")
     dt, dense_ms = prob.timed_loop(args.steps, args.warmup)
     note(group, f"{args.steps} steps in {dt:.3f} s")
+    if args.dump_outputs is not None and group.rank == 0:      # before anything after the timed loop reuses the buffers
+        note(group, f"outputs of the last timed step: {dump_outputs(prob, args.dump_outputs)} bytes written to {args.dump_outputs}")
 
     # ---- N > 1 (or the forced communicator): the line explains itself ------------------------------------------------
     gather = gather_hidden_ms = per_rank = parity_transport = strong_rec = None
@@ -269,6 +278,90 @@ def run_rank(args):
     if tctx is not ctx:
         tctx.close()
     group.close()
+
+
+# ======================================================================================================================
+# --dump-outputs: what the timed step hands its caller, so that two builds can be compared output for output
+# ======================================================================================================================
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_DENSE_ROWS = 8            # whole rows of the dense cost block
+DUMP_MAX_ROWS = 65536          # aligned rows of the candidate lists
+DUMP_MAX_TRIANGLES = 131072    # triangles of the per-triangle maps and sweep flags
+
+
+def dump_outputs(prob, outdir):
+    """Write the outputs of the LAST timed step of `prob` (this rank's) as outdir/<name>.npy; -> bytes written.
+
+    Called right after the timed loop, before anything else runs on the buffers.  The inputs are the same from run to run (seeded
+    synthetic sections, Qhull on them), and so are the samples: seed 0, whole rows / triangles, their positions written beside them
+    (`*_row_ids`, `tri_ids`).  Floating outputs stay float64; integer and flag outputs become float32 where every value is exact in it
+    (|v| < 2^24), else float64.  Every value written is finite: entries the step leaves undefined are not written (see knn_cost,
+    area_after), and any other non-finite value is an error.
+      dense_cost_rows      DUMP_DENSE_ROWS rows of the dense cost block (of the chunk it holds last, strong mode)
+      knn_idx / knn_count  pruned candidate lists (-1 padding) and their lengths, per sampled aligned row
+      knn_cost             the costs of the candidates that exist (knn_idx >= 0), row by row (the padding's cost is +inf)
+      tri_class / tri_perim / tri_maxcos / tri_sign / tri_weight   triangle maps, per sampled triangle
+      xy_edge_flags / xy_tri_flag / area_before / area_matched3 / area_flipped   sweep outputs, per sampled triangle
+      area_after           the signed area under the matching of the sampled triangles whose three cells are matched (area_matched3
+                           all 1; NaN for the others), in order
+      xy_point_flag, match     per aligned cell; xy_counts (the XY-order sweep's counters); orient_checked, orient_flipped
+    (the XY-order and area-flip arrays are absent when the sweeps ran sharded over ranks: they then live in the shards)."""
+    import numpy as np
+
+    rng = np.random.default_rng(0)
+
+    def sample(n, cap):
+        return np.arange(n) if n <= cap else np.sort(rng.choice(n, cap, replace=False))
+
+    def as_float(a):
+        a = np.asarray(a)
+        if a.dtype.kind == "f":
+            return a
+        exact32 = a.size == 0 or int(np.max(np.abs(a.astype(np.int64)))) < (1 << 24)
+        return a.astype(np.float32 if exact32 else np.float64)
+
+    out = {}
+    n_ref, k, rows, n_mov, Tr = prob.n_ref, prob.k, prob.rows, prob.n_mov, prob.Tr
+    if rows > 0:
+        c_last = prob.rb + (rows - 1) // prob.chunk_rows * prob.chunk_rows        # first row of the chunk the dense block holds
+        dr = c_last + sample(prob.re - c_last, DUMP_DENSE_ROWS)
+        out["dense_cost_rows"] = np.stack([prob.dD.download((n_ref,), np.float64, offset_bytes=int(r - c_last) * prob.ld * 8) for r in dr])
+        out["dense_cost_row_ids"] = dr
+        kr = sample(rows, DUMP_MAX_ROWS)
+        out["knn_idx"] = prob.didx.download((rows, k), np.int32)[kr]
+        out["knn_cost"] = prob.dcost.download((rows, k), np.float64)[kr][out["knn_idx"] >= 0]
+        out["knn_count"] = prob.dcnt.download((rows,), np.int32)[kr]
+        out["knn_row_ids"] = prob.rb + kr
+    tr = sample(Tr, DUMP_MAX_TRIANGLES)
+    out["tri_ids"] = tr
+    out["tri_class"] = prob.dcls.download((Tr,), np.uint8)[tr]
+    out["tri_perim"] = prob.dperim.download((Tr,), np.float64)[tr]
+    out["tri_maxcos"] = prob.dmaxcos.download((Tr,), np.float64)[tr]
+    out["tri_sign"] = prob.dsign.download((Tr,), np.int8)[tr]
+    out["tri_weight"] = prob.dweight.download((Tr,), np.float64)[tr]
+    if prob.sharded is None:
+        out["xy_edge_flags"] = prob.dedge.download((Tr, 3), np.uint8)[tr]
+        out["xy_tri_flag"] = prob.dtflag.download((Tr,), np.uint8)[tr]
+        out["xy_point_flag"] = prob.dpflag.download((n_mov,), np.uint8)
+        out["xy_counts"] = prob.dcounts.download((3,), np.uint64).astype(np.float64)
+        out["area_before"] = prob.dbefore.download((Tr,), np.float64)[tr]
+        out["area_matched3"] = prob.dm3.download((Tr, 3), np.uint8)[tr]
+        out["area_after"] = prob.dafter.download((Tr,), np.float64)[tr][out["area_matched3"].all(axis=1)]
+        out["area_flipped"] = prob.dflip.download((Tr,), np.uint8)[tr]
+    out["match"] = prob.dmatch.download((n_mov,), np.int32)
+    out["orient_checked"] = np.array([prob.last["checked"]], np.float64)
+    out["orient_flipped"] = np.array(prob.last["viol"])
+    out = {name: as_float(a) for name, a in out.items()}
+    bad = [name for name, a in out.items() if not np.isfinite(a).all()]
+    if bad:
+        raise SystemExit(f"--dump-outputs: non-finite values where the step defines every value: {bad}")
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_BUDGET_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes is over the {DUMP_BUDGET_BYTES}-byte budget")
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(outdir, f"{name}.npy"), a)
+    return total
 
 
 def run_cfg5_workload(args, group, json_fd, local_rank):

@@ -315,6 +315,58 @@ def test_bench_contract_line(force_comm):
         assert q["opt_in"] is True and q["max_rel_diff_vs_exact_on_16_rows"] <= 1e-6
 
 
+def test_bench_dump_outputs_are_the_last_steps_outputs(tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the timed step computed, in float32 / float64 within 64 MB: on the tiny workload (no
+    sampling there) every array equals the oracle's on the same seeded inputs."""
+    import os
+    import subprocess
+    import sys
+
+    from scipy.spatial import Delaunay
+
+    from oracle import same_oracle as orc
+    from same_amd import synth
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out_dir = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--workload", "tiny", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+           "--no-extras", "--embed-cfg5", "off", "--dump-outputs", str(out_dir)]
+    res = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-2000:]
+    assert len([ln for ln in res.stdout.splitlines() if ln.strip()]) == 1
+    got = {f[:-4]: np.load(out_dir / f, allow_pickle=False) for f in os.listdir(out_dir)}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in got.values())
+    assert sum(os.path.getsize(out_dir / f"{n}.npy") for n in got) <= 64 << 20
+    n, T, k, radius = 4000, 20, 32, 25.0                         # bench_problem.WORKLOADS["tiny"], its seeds
+    ref = synth.make_cells(n, T, seed=0)
+    mov = synth.make_cells(n, T, seed=1, side=ref["side"])
+    tris = np.ascontiguousarray(Delaunay(mov["xy"]).simplices, dtype=np.int32)
+    dr = got["dense_cost_row_ids"].astype(np.int64)
+    assert len(dr) == 8 and np.array_equal(got["dense_cost_rows"], np.stack(
+        [orc.dense_cost(mov["types"], ref["types"], mov["xy"], ref["xy"], 1.0, int(r), int(r) + 1)[0] for r in dr]))
+    idx, _, cnt = orc.knn_prune(mov["xy"], ref["xy"], radius, k)
+    assert np.array_equal(got["knn_row_ids"], np.arange(n)) and np.array_equal(got["knn_idx"], idx)
+    assert np.array_equal(got["knn_count"], cnt)
+    rr, cc = np.nonzero(idx >= 0)                                # the candidates that exist, row by row
+    want_cost = orc.pair_cost_arrays(mov["types"], ref["types"], mov["xy"], ref["xy"], np.column_stack((rr, idx[rr, cc])), 1.0)
+    assert np.array_equal(got["knn_cost"], want_cost)
+    assert np.array_equal(got["tri_ids"], np.arange(len(tris)))
+    cls, perim, maxcos = orc.tri_classify(mov["xy"], tris, radius, 15, mov["cell_type"])
+    sign, weight = orc.tri_sign_weight(mov["xy"], mov["size"], tris)
+    assert np.array_equal(got["tri_class"], cls) and np.array_equal(got["tri_perim"], perim) and np.array_equal(got["tri_maxcos"], maxcos)
+    assert np.array_equal(got["tri_sign"], sign) and np.array_equal(got["tri_weight"], weight)
+    match = idx[:, 0]                                            # nearest reference within the radius, else -1
+    assert np.array_equal(got["match"], match)
+    edge, tflag, pflag, counts = orc.xyorder_sweep(mov["xy"], ref["xy"], tris, match)
+    assert np.array_equal(got["xy_edge_flags"], np.asarray(edge).reshape(-1, 3)) and np.array_equal(got["xy_tri_flag"], tflag)
+    assert np.array_equal(got["xy_point_flag"], pflag) and np.array_equal(got["xy_counts"], np.asarray(counts)[:3])
+    before, after, m3, flipped = orc.area_flip(mov["xy"], ref["xy"], tris, match)
+    assert np.array_equal(got["area_before"], before) and np.array_equal(got["area_after"], after[m3.all(axis=1)])
+    assert np.array_equal(got["area_matched3"], m3) and np.array_equal(got["area_flipped"], flipped)
+    checked, viol, _ = orc.orient_sweep(tris, sign, ref["xy"], match)
+    assert got["orient_checked"].tolist() == [checked] and np.array_equal(got["orient_flipped"], viol) and checked > 0
+
+
 def _check_multi_rank_keys(out, world, kind):
     """What the N > 1 line must carry to explain itself."""
     r = out["rccl"]

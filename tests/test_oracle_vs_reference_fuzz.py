@@ -1,8 +1,13 @@
-"""The oracle against the REFERENCE ITSELF on seeded random inputs -- where the reference is mounted (the build container; never the
-GPU box).  The committed fixtures pin the oracle on 17 recorded cases; this walks the same functions over a few hundred small random
-ones (ragged sizes, empty results, every flag combination, NaN coordinates in the window loop), so that what every GPU parity test is
-checked against is itself checked against the code it restates, beyond the recorded cases.  Tie-free inputs where the reference's
-own order is unspecified (its unstable argsort over equal distances)."""
+"""The oracle against the REFERENCE ITSELF on seeded random inputs.  The committed fixtures pin the oracle on 17 recorded cases; this
+walks the same functions over a few hundred small random ones (ragged sizes, empty results, every flag combination, NaN coordinates in
+the window loop), so that what every GPU parity test is checked against is itself checked against the code it restates, beyond the
+recorded cases.  Tie-free inputs where the reference's own order is unspecified (its unstable argsort over equal distances, SURVEY
+appendix A).
+
+What the reference returned for these cases is stored in tests/golden/ref_fuzz.npz (tests/ref_replay.py: every call replays its
+recorded output after checking that its arguments are the recorded ones), so the suite needs nothing outside the repository.  Where
+the reference is mounted it can be run live instead: SAME_REF_FUZZ_LIVE=1, or SAME_REF_FUZZ_SEED=s for other cases, or
+SAME_REF_FUZZ_RECORD=<path.npz> to record the suite's own cases again (tools/README.md)."""
 import contextlib
 import io
 import os
@@ -13,22 +18,75 @@ import pandas as pd
 import pytest
 
 SEED = 1000 * int(os.environ.get("SAME_REF_FUZZ_SEED", "0"))      # other seeds for a longer run (0 = the suite's own cases)
+RECORD = os.environ.get("SAME_REF_FUZZ_RECORD")                   # a path: run the mounted reference and record its outputs there
+LIVE = bool(RECORD) or SEED != 0 or os.environ.get("SAME_REF_FUZZ_LIVE") == "1"
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-pytestmark = pytest.mark.skipif(not os.path.isdir("/root/reference/src"), reason="the reference is not mounted here")
+RECORDED = os.path.join(ROOT, "tests", "golden", "ref_fuzz.npz")
+# every reference call the tests below make (`window.run` and `metacell.collapse` are the adapters of _live_reference)
+CALLS = ("utils.find_knn_within_radius", "knn_utils.find_knn_with_cell_type_priority", "helpers.filter_triangles_by_radius",
+         "helpers.precompute_triangle_info", "violationhelper.verify_spatial_preservation", "init_helpers.compute_mip_start_pairs",
+         "window.run", "gg.ref_pair_costs", "gg.ref_weights_signs", "gg.ref_lazy_sweep", "gg.ref_area_flips", "metacell.collapse")
+
+
+def _live_reference():
+    """The reference's modules (tools/ref_loader.py), tools/gen_golden.py's drivers of run_same's inline loops as `gg`, and two adapters
+    that turn what the reference does into plain values: `window.run` (sliding_window_matching with run_same replaced by a recorder of
+    the cells every window receives) and `metacell.collapse` (greedy_triangle_collapse's result object as a tuple)."""
+    import types
+
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import fake_gurobipy
+    import ref_loader
+
+    if not os.path.isdir(ref_loader.REF_SRC):
+        pytest.skip(f"a live run needs the reference, which is not mounted at {ref_loader.REF_ROOT}")
+    fake_gurobipy.install()            # src/same.py imports gurobipy at module scope; the window loop below never reaches a solver
+    ns = ref_loader.load_reference(with_run_same=True)
+    import gen_golden
+
+    ns.gg = gen_golden
+
+    def window_run(r_df, m_df, op):
+        calls = []
+
+        def recorder(aligned_df, ref_df, commonCT, optim_params, gurobi_params, outprefix, aligned_delaunay, aligned_delaunay_vertex_col,
+                     ignore_precomputed_triangulation):
+            calls.append((aligned_df["Cell_Num_Old"].to_numpy().copy(), ref_df["Cell_Num_Old"].to_numpy().copy()))
+            return pd.DataFrame({"X": aligned_df["X"].to_numpy(), "Y": aligned_df["Y"].to_numpy(),
+                                 "Aligned_Cell_Num_Old": aligned_df["Cell_Num_Old"].to_numpy()}), {}
+
+        saved = ns.same.run_same
+        ns.same.run_same = recorder
+        try:
+            res = quiet(ns.same.sliding_window_matching, r_df.copy(), m_df.copy(), commonCT=["t0"], optim_params=dict(op))
+        finally:
+            ns.same.run_same = saved
+        return res, calls
+
+    def collapse(df, **kw):
+        want = quiet(ns.metacell_utils.greedy_triangle_collapse, df, use_alpha_shape=False, return_object=True, **kw)
+        return want.metacell_df, want.metacell_delaunay, want.original_delaunay
+
+    ns.window = types.SimpleNamespace(run=window_run)
+    ns.metacell = types.SimpleNamespace(collapse=collapse)
+    return ns
 
 
 @pytest.fixture(scope="module")
 def ref():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import ref_replay
+
+    if not LIVE:
+        yield ref_replay.Replayer(RECORDED)
+        return
+    assert not (RECORD and SEED), "only the suite's own cases (seed 0) are recorded"
     saved = sys.modules.get("gurobipy")
-    import fake_gurobipy
-
-    fake_gurobipy.install()            # src/same.py imports gurobipy at module scope; the window loop below never reaches a solver
-    from ref_loader import load_reference
-
-    ns = load_reference(with_run_same=True)
-    yield ns
+    ns = _live_reference()
+    rec = ref_replay.Recorder(ns, CALLS) if RECORD else None
+    yield rec.view if rec else ns
+    if rec:
+        rec.save(RECORD)
     if saved is None:
         sys.modules.pop("gurobipy", None)
     else:
@@ -147,49 +205,36 @@ def test_window_loop_with_rows_that_have_no_coordinates(ref, oracle):
     layouts in which some rows have NaN coordinates: pandas' min / max skip them (:481-482), no window receives them, and the job runs.
     The oracle's window_plan must name the same windows, hand each the same cells in the same order and keep the same central rows."""
     rng = np.random.default_rng(404 + SEED)
-    calls = []
-
-    def recorder(aligned_df, ref_df, commonCT, optim_params, gurobi_params, outprefix, aligned_delaunay, aligned_delaunay_vertex_col,
-                 ignore_precomputed_triangulation):
-        calls.append((aligned_df["Cell_Num_Old"].to_numpy().copy(), ref_df["Cell_Num_Old"].to_numpy().copy()))
-        return pd.DataFrame({"X": aligned_df["X"].to_numpy(), "Y": aligned_df["Y"].to_numpy(), "Aligned_Cell_Num_Old": aligned_df["Cell_Num_Old"].to_numpy()}), {}
-
-    saved = ref.same.run_same
-    ref.same.run_same = recorder
     windows = 0
-    try:
-        for case in range(12):
-            side = float(rng.choice([150.0, 333.3, 500.0]))
-            frames = []
-            for n in (int(rng.integers(300, 1500)), int(rng.integers(300, 1500))):
-                df = _cells(rng, n, side, T=1, with_size=False)
-                hole = (df["X"] < side * 0.3) & (df["Y"] < side * 0.4) & (rng.random(n) < 0.9)          # under-populated corner: merges
-                df = df[~hole].reset_index(drop=True)
-                df["Cell_Num_Old"] = np.arange(len(df))                                                    # id = row position
-                if case % 2:
-                    df.loc[rng.integers(0, len(df), 7), "X"] = np.nan
-                    df.loc[rng.integers(0, len(df), 4), "Y"] = np.nan
-                frames.append(df)
-            r_df, m_df = frames
-            ws = int(rng.choice([60, 100, 170]))
-            op = dict(window_size=ws, overlap=int(rng.choice([0, ws // 5, ws // 2])), min_cells_per_window=int(rng.choice([10, 40])))
-            res = quiet(ref.same.sliding_window_matching, r_df.copy(), m_df.copy(), commonCT=["t0"], optim_params=dict(op))
-            rxy, mxy = r_df[["X", "Y"]].to_numpy(dtype=np.float64), m_df[["X", "Y"]].to_numpy(dtype=np.float64)
-            plan = oracle.window_plan(rxy, mxy, ws, op["overlap"], op["min_cells_per_window"])
-            assert len(plan) == len(calls), (case, len(plan), len(calls))
-            want_rows = []
-            for w, (a_ids, r_ids) in zip(plan, calls):
-                ma, mr = oracle.window_mask(mxy, *w["box"]), oracle.window_mask(rxy, *w["box"])
-                assert np.array_equal(np.flatnonzero(ma), a_ids) and np.array_equal(np.flatnonzero(mr), r_ids), (case, w["window_id"])
-                tx0, tx1, ty0, ty1 = w["trim"]
-                c = np.flatnonzero(ma & (mxy[:, 0] >= tx0) & (mxy[:, 0] < tx1) & (mxy[:, 1] >= ty0) & (mxy[:, 1] < ty1))
-                want_rows.append(np.column_stack((c, np.full(len(c), w["window_id"]))))
-            got_rows = res[["Aligned_Cell_Num_Old", "window_id"]].to_numpy(dtype=np.int64) if len(res) else np.zeros((0, 2), np.int64)
-            assert np.array_equal(got_rows, np.concatenate(want_rows + [np.zeros((0, 2), np.int64)]).astype(np.int64)), case
-            windows += len(plan)
-            calls.clear()
-    finally:
-        ref.same.run_same = saved
+    for case in range(12):
+        side = float(rng.choice([150.0, 333.3, 500.0]))
+        frames = []
+        for n in (int(rng.integers(300, 1500)), int(rng.integers(300, 1500))):
+            df = _cells(rng, n, side, T=1, with_size=False)
+            hole = (df["X"] < side * 0.3) & (df["Y"] < side * 0.4) & (rng.random(n) < 0.9)          # under-populated corner: merges
+            df = df[~hole].reset_index(drop=True)
+            df["Cell_Num_Old"] = np.arange(len(df))                                                    # id = row position
+            if case % 2:
+                df.loc[rng.integers(0, len(df), 7), "X"] = np.nan
+                df.loc[rng.integers(0, len(df), 4), "Y"] = np.nan
+            frames.append(df)
+        r_df, m_df = frames
+        ws = int(rng.choice([60, 100, 170]))
+        op = dict(window_size=ws, overlap=int(rng.choice([0, ws // 5, ws // 2])), min_cells_per_window=int(rng.choice([10, 40])))
+        res, calls = ref.window.run(r_df, m_df, op)
+        rxy, mxy = r_df[["X", "Y"]].to_numpy(dtype=np.float64), m_df[["X", "Y"]].to_numpy(dtype=np.float64)
+        plan = oracle.window_plan(rxy, mxy, ws, op["overlap"], op["min_cells_per_window"])
+        assert len(plan) == len(calls), (case, len(plan), len(calls))
+        want_rows = []
+        for w, (a_ids, r_ids) in zip(plan, calls):
+            ma, mr = oracle.window_mask(mxy, *w["box"]), oracle.window_mask(rxy, *w["box"])
+            assert np.array_equal(np.flatnonzero(ma), a_ids) and np.array_equal(np.flatnonzero(mr), r_ids), (case, w["window_id"])
+            tx0, tx1, ty0, ty1 = w["trim"]
+            c = np.flatnonzero(ma & (mxy[:, 0] >= tx0) & (mxy[:, 0] < tx1) & (mxy[:, 1] >= ty0) & (mxy[:, 1] < ty1))
+            want_rows.append(np.column_stack((c, np.full(len(c), w["window_id"]))))
+        got_rows = res[["Aligned_Cell_Num_Old", "window_id"]].to_numpy(dtype=np.int64) if len(res) else np.zeros((0, 2), np.int64)
+        assert np.array_equal(got_rows, np.concatenate(want_rows + [np.zeros((0, 2), np.int64)]).astype(np.int64)), case
+        windows += len(plan)
     assert windows > 60
 
 
@@ -201,8 +246,7 @@ def test_inline_loops_of_run_same(ref, oracle):
     several pairs above 0.5 for one aligned row (the last one wins)."""
     from scipy.spatial import Delaunay
 
-    import gen_golden as gg          # tools/ (on sys.path through the `ref` fixture): loads the reference the same way
-
+    gg = ref.gg                      # tools/gen_golden.py's drivers (recorded)
     rng = np.random.default_rng(505 + SEED)
     flips = checked_total = 0
     for case in range(25):
@@ -258,15 +302,14 @@ def test_metacell_collapse(ref, oracle):
         df = _cells(rng, int(rng.integers(6, 140)), float(rng.choice([30.0, 60.0])), T=2, with_size=False)
         df["batch"] = np.where(np.arange(len(df)) % 3 == 0, "b0", "b1")
         kw = dict(max_metacell_size=int(rng.choice([1, 3, 4, 9])), r_max=[None, 8.0, 25.0][case % 3], min_angle_deg=[10, None, 25][case % 3])
-        want = quiet(ref.metacell_utils.greedy_triangle_collapse, df, use_alpha_shape=False, return_object=True, **kw)
+        wdf, want_tri, want_orig = ref.metacell.collapse(df, **kw)
         gdf, gtri, gorig = oracle.greedy_triangle_collapse(df, **kw)
-        wdf = want.metacell_df
         assert list(wdf.columns) == list(gdf.columns) and len(wdf) == len(gdf), case
         assert [list(map(int, m)) for m in wdf["members"]] == [list(map(int, m)) for m in gdf["members"]], case
         for c in wdf.columns:
             if c != "members":
                 assert np.array_equal(wdf[c].to_numpy(), gdf[c].to_numpy()), (case, c)
-        assert np.array_equal(np.asarray(want.metacell_delaunay, dtype=np.int64).reshape(-1, 3), np.asarray(gtri, dtype=np.int64).reshape(-1, 3)), case
-        assert np.array_equal(np.asarray(want.original_delaunay, dtype=np.int64).reshape(-1, 3), np.asarray(gorig, dtype=np.int64).reshape(-1, 3)), case
+        assert np.array_equal(np.asarray(want_tri, dtype=np.int64).reshape(-1, 3), np.asarray(gtri, dtype=np.int64).reshape(-1, 3)), case
+        assert np.array_equal(np.asarray(want_orig, dtype=np.int64).reshape(-1, 3), np.asarray(gorig, dtype=np.int64).reshape(-1, 3)), case
         collapsed += len(df) - len(wdf)
     assert collapsed > (100 if SEED == 0 else 40)        # coverage of the suite's own seed; other seeds (SAME_REF_FUZZ_SEED) collapse 90-130

@@ -59,7 +59,8 @@ typedef struct same_sweep same_sweep; /* resident state of one lazy-constraint s
  * part 2  DEVICE-RESIDENT forms (operands already in HBM; enqueue     same_dense_cost_*_dev, same_knn_prune_dev, same_knn_index_*,
  *         only unless noted)                                          same_knn_prune_indexed_dev, same_padded_cost_*_dev, same_tri_*_dev,
  *                                                                     same_area_flip_dev, same_xyorder_sweep_dev, same_orient_*_dev, same_first_candidate_dev
- * part 3  WINDOW path, sections resident (BASELINE cfg 5)             same_section_*, same_window_*, same_merge_acc_*, same_delaunay2d (host)
+ * part 3  WINDOW path, sections resident (BASELINE cfg 5)             same_section_*, same_window_*, same_merge_acc_*, same_delaunay2d (host),
+ *                                                                     same_delaunay_filtered
  * part 4  COMM: RCCL collectives between the ranks' contexts          same_comm_*, same_allgather_dev*, same_allreduce_dev
  * Every declaration cites the reference lines it replaces (file:line into the reference tree).
  * Measurement hooks and opt-in controls that are NOT the path -- runtime-call counters, timers, the spread allocator, the fixed-point
@@ -440,6 +441,37 @@ int same_window_filter_finish(same_window *const *windows, int n_windows, const 
  * SAME_ENOMEM. */
 int same_delaunay2d(const double *xy, int64_t n, int32_t *out_tris, int64_t cap, int64_t *out_n_tris, double guard,
                     double *out_margin /* may be NULL */);
+
+/* ---- a6 on the DEVICE for the window path (csrc/delaunay_dev.hip): replaces the scipy.spatial.Delaunay call of src/same.py:1016-1031
+ * where the filter of src/helpers.py:298-319 follows.  The filter drops every triangle with a side >= radius or an angle < min_angle and
+ * nothing downstream sees a dropped triangle (:321-325, :331-340, :357, :365-389), so only Delaunay triangles that pass a slack screen of
+ * it are needed: with points in general position those are exactly the screened triangles whose circumcircle is empty, and their
+ * circumradius is at most radius / (2 sin min_angle) -- a map over points that reads a bounded neighbourhood.  Every in-circle sign is
+ * measured as Qhull would see it (qhull_margin.h, the formula of same_delaunay2d); the answer is given only when every sign clears `guard`
+ * x Qhull's allowance and the hull is clear of collinear runs, so an answer is the SET of kept-candidate triangles Qhull's triangulation
+ * holds.  The candidates come counter-clockwise in this library's order (by owner = smallest vertex, then the other two ascending).
+ *   same_window_delaunay: for each staged window of the batch (up to eight per launch, nine launches per group, ONE wait for the batch),
+ *     the candidates over its kept aligned cells (SAME_WINDOW_ALIGNED_XY), left on the device.  out_status[i] = 0 (answered; out_n_tris[i]
+ *     candidates) or a mask of SAME_DD_* reasons (refused: the caller asks Qhull, as the reference does).  A window's candidates stay valid
+ *     until it is staged again.  cos_thr / angle_enabled as for same_window_filter_finish.
+ *   same_window_filter_finish_device: same_window_filter_finish (prefiltered = 0) over every window's device-made candidates -- no host
+ *     array, no upload: the classes, the keep list and the same-type re-add are decided by the filter's own kernels, with the reference's
+ *     arithmetic, and out_counts' near and ORDER TIES are what they mean there (a caller re-finishes a window whose count is not zero with
+ *     Qhull's simplices).  Every window must have been answered by same_window_delaunay since it was staged.
+ *   same_delaunay_filtered: the same triangulation for a caller's host array of n points (xy interleaved): *out_status as above;
+ *     answered: *out_n_tris triangles in out_tris (room for `cap`; 2 n always suffices).  SAME_EINVAL if cap is too small. */
+#define SAME_DD_FEW_POINTS 1   /* fewer than 3 points */
+#define SAME_DD_NO_ANGLE 2     /* no angle threshold (min_angle_deg None or ~0) or no finite radius: no circumradius bound */
+#define SAME_DD_NONFINITE 4    /* a coordinate is not finite */
+#define SAME_DD_IN_DOUBT 8     /* a sign within guard x Qhull's allowance: duplicates, cocircular quads, collinear runs, hull corners */
+#define SAME_DD_OVERFLOW 16    /* a neighbour, candidate, hull or grid list longer than its buffer */
+int same_window_delaunay(same_window *const *windows, int n_windows, double radius, int angle_enabled, double cos_thr, double guard,
+                         int32_t *out_status, int64_t *out_n_tris);
+int same_window_filter_finish_device(same_window *const *windows, int n_windows, double radius, int angle_enabled, double cos_thr,
+                                     double near_tol, int ignore_same_type, int ensure_min_triangle_per_node, double no_match_penalty,
+                                     int32_t *out_match_row, uint8_t *out_point_flag, int64_t *out_stats, int64_t *out_counts);
+int same_delaunay_filtered(same_ctx *ctx, const double *xy, int64_t n, double radius, int angle_enabled, double cos_thr, double guard,
+                           int32_t *out_tris, int64_t cap, int64_t *out_n_tris, int32_t *out_status);
 
 /* ---- f3 on the window path: the window merge where the windows' matches are ------------------------------------------------
  * The reference trims every window's match table to the window's central region (src/same.py:565-582), concatenates the tables and

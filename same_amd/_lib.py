@@ -105,6 +105,9 @@ _PROTOTYPES = {
     "same_window_filter_finish": [c_vp, c_int, c_vp, c_vp, c_int, c_dbl, c_int, c_dbl, c_dbl, c_int, c_int, c_dbl, c_vp, c_vp, c_vp, c_vp],
     "same_merge_dedup": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, ctypes.POINTER(c_i64)],
     "same_delaunay2d": [c_vp, c_i64, c_vp, c_i64, ctypes.POINTER(c_i64), c_dbl, ctypes.POINTER(c_dbl)],
+    "same_window_delaunay": [c_vp, c_int, c_dbl, c_int, c_dbl, c_dbl, c_vp, c_vp],
+    "same_window_filter_finish_device": [c_vp, c_int, c_dbl, c_int, c_dbl, c_dbl, c_int, c_int, c_dbl, c_vp, c_vp, c_vp, c_vp],
+    "same_delaunay_filtered": [c_vp, c_vp, c_i64, c_dbl, c_int, c_dbl, c_dbl, c_vp, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(c_int)],
     "same_section_set_codes": [c_vp, c_vp, c_i64],
     "same_merge_acc_create": [c_vp, ctypes.POINTER(c_vp)],
     "same_merge_acc_destroy": [c_vp],
@@ -135,6 +138,8 @@ EXPORTS = tuple(_PROTOTYPES)
 
 
 SAME_EINVAL, SAME_ENOMEM, SAME_EIO, SAME_ENODEV, SAME_ERANGE, SAME_EUNSURE = -22, -12, -5, -19, -34, -11   # include/same_hip.h
+# why the device's triangulator refused a set (a mask; include/same_hip.h, same_window_delaunay)
+SAME_DD_FEW_POINTS, SAME_DD_NO_ANGLE, SAME_DD_NONFINITE, SAME_DD_IN_DOUBT, SAME_DD_OVERFLOW = 1, 2, 4, 8, 16
 
 
 class SameHipError(RuntimeError):

@@ -12,6 +12,7 @@
 // this file's order, counter-clockwise; Qhull's order and orientation are its own (same_amd/delaunay.py says what that touches).
 // Host code only: no device, no context.
 #include "same_hip.h"
+#include "qhull_margin.h"
 
 #include <algorithm>
 #include <cmath>
@@ -24,7 +25,6 @@ namespace {
 
 constexpr double SIGN_MARGIN = 1e-12;   // a sign is trusted when |det| > SIGN_MARGIN x (sum of the |products| it was made of); the
                                         // proven bounds (Shewchuk, 3.4e-16 and 1.2e-15) are three orders below
-constexpr double EPS = 2.220446049250313e-16;
 
 struct Unsure {};
 
@@ -271,9 +271,8 @@ struct Tri {
         }
     }
 
-    // The finished triangulation as Qhull would judge it.  Qhull lifts (x, y) to z = x*x + y*y WITHOUT centring, scales z to the range
-    // [0, m], m = the largest |x| or |y| ('Qbb'), and takes a point for coplanar with a facet when its distance from the facet's plane
-    // is within a few DISTround = eps * (3 * sqrt(3) * 1.01 + 1) * m; z itself carries eps * z of rounding before the scaling.
+    // The finished triangulation as Qhull would judge it (qhull_margin.h: the lifted coordinates, Qhull's allowance, the factor per
+    // triangle -- shared with the device's triangulator, delaunay_dev.hip).
     // worst = the smallest (distance / allowance) over interior edges (the neighbour's far corner against the triangle's plane) and
     // hull corners (the corner's distance from the chord of its neighbours, and every hull triangle's height over its hull edge).
     double worst_margin() {
@@ -283,22 +282,13 @@ struct Tri {
             m = std::max(m, std::max(std::fabs(x), std::fabs(y)));
             zmin = std::min(zmin, z); zmax = std::max(zmax, z);
         }
-        const double s = zmax > zmin ? m / (zmax - zmin) : 1.0;                      // Qbb's scale of the lifted coordinate
-        const double allow = EPS * (6.25 * m + zmax * s);                            // plane distance Qhull cannot tell from zero
+        const qm::Scale sc = qm::scale(m, zmin, zmax);
         double worst = std::numeric_limits<double>::infinity();
-        // per triangle (p0, p1, p2): the plane of the lifted triangle is z = 2 c . x + const, c its circumcentre -- slope 2 |c| before the
-        // scaling; a thin triangle's plane is known that much worse (longest side over height); the distance of a point with in-circle
-        // determinant det is s * det / (2 area) / sqrt(1 + slope^2)
         const int64_t n_tri = len / 3;
         judge.resize((size_t)n_tri);
         for (int64_t t = 0; t < n_tri; ++t) {
             const int32_t p0 = tri[3 * t], p1 = tri[3 * t + 1], p2 = tri[3 * t + 2];
-            const double dx = X(p1) - X(p0), dy = Y(p1) - Y(p0), ex = X(p2) - X(p0), ey = Y(p2) - Y(p0);
-            const double bl = dx * dx + dy * dy, cl = ex * ex + ey * ey, d = dx * ey - dy * ex, area2 = std::fabs(d);
-            const double ccx = X(p0) + (ey * bl - dy * cl) * 0.5 / d, ccy = Y(p0) + (dx * cl - ex * bl) * 0.5 / d;
-            const double slope2 = 4 * s * s * (ccx * ccx + ccy * ccy);
-            const double l2 = std::max(bl, std::max(cl, (ex - dx) * (ex - dx) + (ey - dy) * (ey - dy)));
-            judge[(size_t)t] = s / (area2 * std::sqrt(1 + slope2) * allow * std::max(1.0, l2 / area2));
+            judge[(size_t)t] = qm::judge(X(p0), Y(p0), X(p1) - X(p0), Y(p1) - Y(p0), X(p2) - X(p0), Y(p2) - Y(p0), sc);
         }
         for (int32_t a = 0; a < (int32_t)len; ++a) {
             const int32_t b = half[a];
@@ -309,7 +299,7 @@ struct Tri {
                 // is vertical: it holds the point at infinity of 'Qz')
                 const double area2 = std::fabs((X(pr) - X(p0)) * (Y(pl) - Y(p0)) - (Y(pr) - Y(p0)) * (X(pl) - X(p0)));
                 const double edge = std::hypot(X(pl) - X(pr), Y(pl) - Y(pr));
-                worst = std::min(worst, area2 / edge / allow);
+                worst = std::min(worst, qm::plain_ratio(area2, edge, sc));
                 continue;
             }
             if (b < a) continue;
@@ -322,7 +312,7 @@ struct Tri {
         do {
             const int32_t p = hprev[e], q = hnext[e];
             const double area2 = std::fabs((X(e) - X(p)) * (Y(q) - Y(p)) - (Y(e) - Y(p)) * (X(q) - X(p)));
-            worst = std::min(worst, area2 / std::hypot(X(q) - X(p), Y(q) - Y(p)) / allow);
+            worst = std::min(worst, qm::plain_ratio(area2, std::hypot(X(q) - X(p), Y(q) - Y(p)), sc));
             e = q;
         } while (e != hull_start);
         return worst;

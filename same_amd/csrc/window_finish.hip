@@ -527,14 +527,12 @@ int read_finish(same_window *w, FinishPlan *p, int32_t *out_match_row, uint8_t *
     return SAME_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int same_window_filter_finish(same_window *const *windows, int n_windows, const int32_t *simplices, const int64_t *simplex_offsets, int prefiltered,
-                              double radius, int angle_enabled, double cos_thr, double near_tol, int ignore_same_type,
-                              int ensure_min_triangle_per_node, double no_match_penalty, int32_t *out_match_row, uint8_t *out_point_flag,
-                              int64_t *out_stats, int64_t *out_counts) {
+// same_window_filter_finish's body; on_device: every window's simplices are the ones same_window_delaunay left on the device for it
+// (simplex_offsets are then the offsets of those counts, there is no host array)
+int filter_finish(same_window *const *windows, int n_windows, const int32_t *simplices, const int64_t *simplex_offsets, int prefiltered,
+                  bool on_device, double radius, int angle_enabled, double cos_thr, double near_tol, int ignore_same_type,
+                  int ensure_min_triangle_per_node, double no_match_penalty, int32_t *out_match_row, uint8_t *out_point_flag,
+                  int64_t *out_stats, int64_t *out_counts) {
     same_ctx *ctx = nullptr;
     SAME_TRY(check_batch(windows, n_windows, &ctx));
     REQUIRE(ctx, simplex_offsets && out_counts && out_stats && simplex_offsets[0] == 0);
@@ -544,13 +542,14 @@ int same_window_filter_finish(same_window *const *windows, int n_windows, const 
         REQUIRE(ctx, windows[i]->staged == 2 && Tr >= 0 && Tr < ((int64_t)1 << 31) - 512);
         n_cells += windows[i]->n_ua;
     }
-    REQUIRE(ctx, (simplex_offsets[n_windows] == 0 || simplices) && (n_cells == 0 || (out_match_row && out_point_flag)));
+    REQUIRE(ctx, (simplex_offsets[n_windows] == 0 || simplices || on_device) && (n_cells == 0 || (out_match_row && out_point_flag)));
     for (int q = 0; q < 4 * n_windows; ++q) out_counts[q] = 0;
     for (int q = 0; q < 8 * n_windows; ++q) out_stats[q] = 0;
     SAME_TRY(same_use(ctx));
-    for (int i = 0; i < n_windows; ++i)
-        SAME_TRY(check_index_range(ctx, simplices + 3 * simplex_offsets[i], (simplex_offsets[i + 1] - simplex_offsets[i]) * 3, 0, windows[i]->n_ua,
-                                   "triangles"));
+    if (!on_device)     // (the device's own triangles index the window's kept cells by construction)
+        for (int i = 0; i < n_windows; ++i)
+            SAME_TRY(check_index_range(ctx, simplices + 3 * simplex_offsets[i], (simplex_offsets[i + 1] - simplex_offsets[i]) * 3, 0,
+                                       windows[i]->n_ua, "triangles"));
     struct Item {
         FilterPlan fplan;
         FinishPlan plan;
@@ -561,7 +560,7 @@ int same_window_filter_finish(same_window *const *windows, int n_windows, const 
     // only); per window its filter and finish buffers are laid out; then per GROUP of SAME_LAUNCH_WINDOWS windows the zeroing of the
     // buffers' heads, the filter's and the finish's kernels (one launch each for the whole group); then every window's copies back
     const int32_t *d_simplices = nullptr;
-    if (!prefiltered && simplex_offsets[n_windows] > 0) {
+    if (!on_device && !prefiltered && simplex_offsets[n_windows] > 0) {
         int32_t *d = nullptr;
         SAME_TRY(slot_as(ctx, SL_TRIS, (size_t)simplex_offsets[n_windows] * 3, &d));
         SAME_COPY(ctx, d, simplices, (size_t)simplex_offsets[n_windows] * 12, hipMemcpyHostToDevice);
@@ -574,13 +573,14 @@ int same_window_filter_finish(same_window *const *windows, int n_windows, const 
     for (int i = 0; i < n_windows && rc == SAME_OK; ++i) {
         same_window *w = windows[i];
         Item &it = items[(size_t)i];
-        const int32_t *tri = simplices + 3 * simplex_offsets[i];
+        const int32_t *tri = on_device ? nullptr : simplices + 3 * simplex_offsets[i];
         const int64_t Tr = simplex_offsets[i + 1] - simplex_offsets[i];
         w->filtered = w->finished = 0;
         w->Tr = 0;
         if (w->n_ua == 0) continue;
         if (Tr && !prefiltered) {
-            rc = prepare_filter(w, d_simplices + 3 * simplex_offsets[i], Tr, ignore_same_type, ensure_min_triangle_per_node, &it.fplan);
+            const int32_t *raw = on_device ? static_cast<const int32_t *>(w->dd_tris.p) : d_simplices + 3 * simplex_offsets[i];
+            rc = prepare_filter(w, raw, Tr, ignore_same_type, ensure_min_triangle_per_node, &it.fplan);
             if (rc == SAME_OK) rc = prepare_finish(w, nullptr, Tr, it.fplan.counters + FC_TR, &it.plan);
             if (rc == SAME_OK) {
                 fplans.push_back(&it.fplan);
@@ -686,6 +686,32 @@ int same_window_filter_finish(same_window *const *windows, int n_windows, const 
         w->filtered = w->finished = 1;
     }
     return SAME_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int same_window_filter_finish(same_window *const *windows, int n_windows, const int32_t *simplices, const int64_t *simplex_offsets, int prefiltered,
+                              double radius, int angle_enabled, double cos_thr, double near_tol, int ignore_same_type,
+                              int ensure_min_triangle_per_node, double no_match_penalty, int32_t *out_match_row, uint8_t *out_point_flag,
+                              int64_t *out_stats, int64_t *out_counts) {
+    return filter_finish(windows, n_windows, simplices, simplex_offsets, prefiltered, false, radius, angle_enabled, cos_thr, near_tol,
+                         ignore_same_type, ensure_min_triangle_per_node, no_match_penalty, out_match_row, out_point_flag, out_stats, out_counts);
+}
+
+int same_window_filter_finish_device(same_window *const *windows, int n_windows, double radius, int angle_enabled, double cos_thr, double near_tol,
+                                     int ignore_same_type, int ensure_min_triangle_per_node, double no_match_penalty, int32_t *out_match_row,
+                                     uint8_t *out_point_flag, int64_t *out_stats, int64_t *out_counts) {
+    same_ctx *ctx = nullptr;
+    SAME_TRY(check_batch(windows, n_windows, &ctx));
+    std::vector<int64_t> offsets((size_t)n_windows + 1, 0);
+    for (int i = 0; i < n_windows; ++i) {
+        REQUIRE(ctx, windows[i]->dd_ok && windows[i]->staged == 2);
+        offsets[(size_t)i + 1] = offsets[(size_t)i] + windows[i]->n_dd;
+    }
+    return filter_finish(windows, n_windows, nullptr, offsets.data(), 0, true, radius, angle_enabled, cos_thr, near_tol, ignore_same_type,
+                         ensure_min_triangle_per_node, no_match_penalty, out_match_row, out_point_flag, out_stats, out_counts);
 }
 
 }  // extern "C"

@@ -174,6 +174,9 @@ struct same_window {
     int64_t cap_m = 0, cap_r = 0;                   // candidates of the covered cells: what the lists are sized for
     int64_t n_m = 0, n_r = 0, n_ua = 0, P = 0, Tr = 0;
     win::DevBuf stage, filter, finish, tris, big_mask, full_m, full_r;
+    win::DevBuf dd_work, dd_tris;                   // the device's triangulation (delaunay_dev.hip): work buffer, candidate triangles
+    int64_t n_dd = 0;                               // candidate triangles in dd_tris ...
+    int dd_ok = 0;                                  // ... valid for the window as staged (same_window_delaunay answered it)
     // stage block
     unsigned long long *counts = nullptr;           // [8], first words of the block the stage call copies back
     int32_t *rows_m = nullptr, *rows_r = nullptr, *idx = nullptr, *cnt = nullptr, *ua = nullptr, *rows_ua = nullptr, *type_c = nullptr,

@@ -362,7 +362,7 @@ void same_window_destroy(same_window *w) {
     if (!w) return;
     (void)hipSetDevice(w->ctx->device);
     (void)hipStreamSynchronize(w->ctx->stream);
-    for (DevBuf *b : {&w->stage, &w->filter, &w->finish, &w->tris, &w->big_mask, &w->full_m, &w->full_r}) release(*b);
+    for (DevBuf *b : {&w->stage, &w->filter, &w->finish, &w->tris, &w->big_mask, &w->full_m, &w->full_r, &w->dd_work, &w->dd_tris}) release(*b);
     if (w->host) (void)hipHostFree(w->host);
     delete w;
 }
@@ -616,7 +616,7 @@ int same_window_stage(same_window *const *windows, int n_windows, const same_sec
     REQUIRE(ctx, mov->T == ref->T && mov->cost_f32 == ref->cost_f32 && k >= 1 && k <= SAME_MAX_KNN && radius >= 0.0);
     SAME_TRY(same_use(ctx));
     for (int i = 0; i < 4 * n_windows; ++i) out_counts[i] = 0;
-    for (int i = 0; i < n_windows; ++i) windows[i]->staged = windows[i]->finished = windows[i]->filtered = 0;
+    for (int i = 0; i < n_windows; ++i) windows[i]->staged = windows[i]->finished = windows[i]->filtered = windows[i]->dd_ok = 0;
     std::shared_ptr<same_knn_index> ix;           // held until this call's kernels have finished (both returns below wait first)
     SAME_TRY(knn_index_for(ctx, ref, radius, &ix));
     // both sections' grids stay as they are until this call's kernels are enqueued (same_section_bin waits for this, then for the device)

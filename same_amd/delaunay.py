@@ -14,7 +14,14 @@ either way; what does differ is the order of a window's kept TRIANGLES on the de
 why `run_same` / `sliding_window_matching` -- they hand the triangle list to the solver, index = constraint id -- keep scipy.
 
 Use: optim_params["hip_delaunay"] = "native" (or $SAME_DELAUNAY=native) with `sliding_window_incumbent` on resident frames; the
-default is "qhull".  tests/test_delaunay_cpu.py (sets of triangles against scipy, fallbacks), tests/test_gpu_delaunay.py (tables of
+default is "qhull".  "device" triangulates on the GPU instead (csrc/delaunay_dev.hip, same_window_delaunay): the filter's kept
+triangles are the Delaunay triangles that pass it, and those are the triangles with an empty circumcircle among the ones that pass a
+slack screen of it -- a local rule, one thread per point.  The device answers for the same SET as the host's triangulator does (every
+sign clear of `GUARD` x Qhull's allowance, the same formula: csrc/qhull_margin.h), its candidates never leave the device
+(same_window_filter_finish_device), and a window it refuses goes to the Qhull helpers, started on the first refusal.  The ORDER rule
+above is the same rule: windows.iter_device_windows re-finishes a window with order ties or a cosine at the threshold with scipy's
+simplices.  `DeviceTriangulator.stats` (and `last_device_stats()` for the last pass of `sliding_window_incumbent`) count a pass's
+windows submitted, refused and re-finished, each window once.  tests/test_delaunay_cpu.py (sets of triangles against scipy, fallbacks), tests/test_gpu_delaunay.py (tables of
 both ways bit-identical; forced ties), tools/delaunay_margin.py (where Qhull itself stops being exact).
 """
 import os
@@ -31,12 +38,99 @@ GUARD = 16.0
 
 
 def mode(optim_params=None):
-    """'native' | 'qhull' from optim_params['hip_delaunay'], else $SAME_DELAUNAY, else 'qhull'."""
+    """'native' | 'device' | 'qhull' from optim_params['hip_delaunay'], else $SAME_DELAUNAY, else 'qhull'."""
     m = (optim_params or {}).get("hip_delaunay") or os.environ.get("SAME_DELAUNAY") or "qhull"
     m = str(m).lower()
-    if m not in ("native", "qhull"):
-        raise ValueError(f"hip_delaunay / SAME_DELAUNAY must be 'native' or 'qhull', not {m!r}")
+    if m not in ("native", "device", "qhull"):
+        raise ValueError(f"hip_delaunay / SAME_DELAUNAY must be 'native', 'device' or 'qhull', not {m!r}")
     return m
+
+
+def device_filtered_triangles(points, radius, min_angle_deg, ctx=None, guard=GUARD, with_status=False):
+    """(k, 3) int32 counter-clockwise triangles: the Delaunay triangles of `points` ((n, 2) float64) that pass a slack screen of the
+    reference's side / angle filter -- a superset of what filter_triangles_by_radius(points, Delaunay(points).simplices, radius, ...)
+    keeps, and exactly the triangles of scipy's triangulation that pass the screen -- made on the GPU (same_delaunay_filtered), or None
+    when the device refuses the set (duplicates, cocircular or collinear points, no angle threshold, a list longer than its buffer: ask
+    scipy).  with_status: (that, the status: 0 or a mask of _lib.SAME_DD_* reasons)."""
+    import ctypes
+
+    from . import ops
+    from .triangles import cos_threshold
+
+    ctx = ops._ctx(ctx)
+    pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 2)
+    n = len(pts)
+    angle_enabled, cos_thr = cos_threshold(min_angle_deg)
+    out = np.empty((max(2 * n, 1), 3), np.int32)
+    n_tris, status = ctypes.c_int64(0), ctypes.c_int(0)
+    with ctx.lock:
+        ctx.check(ctx.lib.same_delaunay_filtered(ctx.handle, pts.ctypes.data, n, float(abs(radius)), int(angle_enabled), float(cos_thr),
+                                                 float(guard), out.ctypes.data, len(out), ctypes.byref(n_tris), ctypes.byref(status)),
+                  "same_delaunay_filtered")
+    tris = None if status.value else out[:n_tris.value].copy()
+    return (tris, status.value) if with_status else tris
+
+
+class DeviceTriangulator:
+    """What `iter_device_windows` is handed for optim_params["hip_delaunay"] = "device": the windows are triangulated on the device
+    (same_window_delaunay) right before their filter + finish call, and a window the device refuses is handed to a Qhull helper (the
+    pool is started on the first refusal).  `stats`: windows submitted to the device, refused by it, and re-finished with scipy's
+    simplices after an answer (order ties, a cosine at the angle threshold) -- each window counted once, whichever threads walk them."""
+
+    on_device = True
+    threads = 0          # no triangulator threads: nothing is triangulated ahead of the finish call
+
+    def __init__(self, guard=GUARD):
+        self.guard = float(guard)
+        self._lock = threading.Lock()
+        self.stats = {"submitted": 0, "refused": 0, "refinished": 0}
+
+    def ticket(self, points, answered):
+        """the window's ticket after same_window_delaunay: answered -> its candidates are on the device (`.result()` is None, `.native`
+        is true, `.qhull()` asks a helper for scipy's simplices and counts the window as re-finished); refused -> a helper has it now"""
+        return _DeviceTicket(self, points, answered)
+
+    def note(self, submitted=0, refused=0, refinished=0):
+        with self._lock:
+            self.stats["submitted"] += submitted
+            self.stats["refused"] += refused
+            self.stats["refinished"] += refinished
+
+    def reset(self):
+        with self._lock:
+            self.stats = {"submitted": 0, "refused": 0, "refinished": 0}
+
+
+class _DeviceTicket:
+    def __init__(self, owner, points, answered):
+        from . import qhull_pool
+
+        self.owner, self.points, self.native, self._qhull = owner, points, bool(answered), None
+        self._asked = None if answered else qhull_pool.pool().submit(points)
+
+    def result(self):
+        if self.native:
+            return None
+        if self._qhull is None:
+            self._qhull = self._asked.result()
+        return self._qhull
+
+    def qhull(self):
+        if self._qhull is None:
+            from . import qhull_pool
+
+            self._qhull = qhull_pool.pool().submit(self.points).result()
+            self.owner.note(refinished=1)
+        self.native = False
+        return self._qhull
+
+
+_last_device = None
+
+
+def last_device_stats():
+    """The counts of the last pass `sliding_window_incumbent` made with hip_delaunay = "device" in this process (None before one)."""
+    return None if _last_device is None else dict(_last_device.stats)
 
 
 def native_simplices(points, guard=GUARD, with_margin=False):

@@ -731,16 +731,51 @@ def filter_finish_windows(states, simplices, radius, angle_enabled, cos_thr, nea
     offsets = np.zeros(n + 1, np.int64)
     np.cumsum([len(t) for t in tris], out=offsets[1:])
     flat = tris[0] if n == 1 else np.concatenate(tris)
+
+    def call(match_row, flag, stats, counts):
+        return ctx.lib.same_window_filter_finish(_handles(states), n, flat.ctypes.data, offsets.ctypes.data, int(bool(prefiltered)),
+                                                 float(radius),
+                                                 int(angle_enabled), float(cos_thr), float(near_tol), int(bool(ignore_same_type)),
+                                                 int(bool(ensure_min_triangle_per_node)), float(no_match_penalty), match_row.ctypes.data,
+                                                 flag.ctypes.data, stats.ctypes.data, counts.ctypes.data)
+
+    return _filter_finish_results(states, call, "same_window_filter_finish")
+
+
+def filter_finish_device_windows(states, radius, angle_enabled, cos_thr, near_tol, ignore_same_type, no_match_penalty,
+                                 ensure_min_triangle_per_node=True):
+    """same_window_filter_finish_device: `filter_finish_windows` over the candidates `triangulate_windows` left on the device for each
+    window (every state must have been answered since it was staged); the same results, no simplices from the host."""
+    ctx, n = states[0].ctx, len(states)
+
+    def call(match_row, flag, stats, counts):
+        return ctx.lib.same_window_filter_finish_device(_handles(states), n, float(radius), int(angle_enabled), float(cos_thr),
+                                                        float(near_tol), int(bool(ignore_same_type)), int(bool(ensure_min_triangle_per_node)),
+                                                        float(no_match_penalty), match_row.ctypes.data, flag.ctypes.data, stats.ctypes.data,
+                                                        counts.ctypes.data)
+
+    return _filter_finish_results(states, call, "same_window_filter_finish_device")
+
+
+def triangulate_windows(states, radius, angle_enabled, cos_thr, guard):
+    """same_window_delaunay for a batch of staged windows (one wait): -> (status per window: 0 answered, else a mask of
+    _lib.SAME_DD_* reasons; candidate triangles per window); the candidates stay on the device for filter_finish_device_windows"""
+    ctx, n = states[0].ctx, len(states)
+    status, n_tris = np.zeros(n, np.int32), np.zeros(n, np.int64)
+    with ctx.lock:
+        ctx.check(ctx.lib.same_window_delaunay(_handles(states), n, float(abs(radius)), int(angle_enabled), float(cos_thr), float(guard),
+                                               status.ctypes.data, n_tris.ctypes.data), "same_window_delaunay")
+    return status, n_tris
+
+
+def _filter_finish_results(states, call, what):
+    ctx, n = states[0].ctx, len(states)
     kept_cells = [s.counts[2] for s in states]
     cell_off = np.concatenate(([0], np.cumsum(kept_cells))).astype(np.int64)
     match_row, flag = np.empty(int(cell_off[-1]), np.int32), np.empty(int(cell_off[-1]), np.uint8)
     stats, counts = np.zeros((n, 8), np.int64), np.zeros((n, 4), np.int64)
     with ctx.lock:
-        ctx.check(ctx.lib.same_window_filter_finish(_handles(states), n, flat.ctypes.data, offsets.ctypes.data, int(bool(prefiltered)),
-                                                    float(radius),
-                                                    int(angle_enabled), float(cos_thr), float(near_tol), int(bool(ignore_same_type)),
-                                                    int(bool(ensure_min_triangle_per_node)), float(no_match_penalty), match_row.ctypes.data,
-                                                    flag.ctypes.data, stats.ctypes.data, counts.ctypes.data), "same_window_filter_finish")
+        ctx.check(call(match_row, flag, stats, counts), what)
     out = []
     for i, s in enumerate(states):
         kept, added, near, s.order_ties = (int(c) for c in counts[i])
@@ -839,6 +874,7 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
     ctx = ops._ctx(ctx)
     angle_enabled, cos_thr = cos_threshold(min_angle_deg)
     near_tol = float(8 * np.spacing(abs(cos_thr))) if (angle_enabled and np.isfinite(cos_thr)) else 0.0
+    on_device = getattr(triangulator, "on_device", False)      # delaunay.DeviceTriangulator: the device triangulates at finish time
     own_threads = getattr(triangulator, "threads", None)        # a triangulator with threads of its own (delaunay.NativeTriangulator)
     depth = qhull_pool.lookahead() if own_threads is None else int(own_threads)
     if own_threads is None:
@@ -887,7 +923,7 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
             ticket = None
             try:
                 out.rows_m, out.axy = state.fetch(_W_ALIGNED_ROWS), state.fetch(_W_ALIGNED_XY)
-                if triangulate:
+                if triangulate and not on_device:
                     with marked("triangulate (hand-over; waits for a free helper)"):
                         ticket = (qhull_pool.pool().submit(out.axy) if triangulator is None
                                   else triangulator.submit(out.axy, key=out.window.get("window_id")))
@@ -906,12 +942,24 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
             out.state, out.n_triangles = state, 0
         if not triangulate or not todo:
             return
+        if on_device:
+            with marked("triangulate (device)"):
+                status, _n = triangulate_windows([st for _o, st, _t in todo], radius, angle_enabled, cos_thr, triangulator.guard)
+                todo = [(out, state, triangulator.ticket(out.axy, status[q] == 0)) for q, (out, state, _t) in enumerate(todo)]
+                triangulator.note(submitted=len(todo), refused=int(np.count_nonzero(status)))
         with marked("triangulate (wait for helper)"):
             tris = [ticket.result() for _o, _s, ticket in todo]
         with marked("filter + signs + incumbent + sweeps (device)"):
-            res = filter_finish_windows([st for _o, st, _t in todo], tris, radius, angle_enabled, cos_thr, near_tol,
-                                        ignore_same_type_triangles,
-                                        no_match_penalty)
+            res = [None] * len(todo)
+            # candidates the device made stay there (same_window_filter_finish_device); every other window brings its simplices
+            mine = [q for q, t in enumerate(tris) if t is None]
+            theirs = [q for q, t in enumerate(tris) if t is not None]
+            for qs, r in ((mine, filter_finish_device_windows([todo[q][1] for q in mine], radius, angle_enabled, cos_thr, near_tol,
+                                                              ignore_same_type_triangles, no_match_penalty) if mine else []),
+                          (theirs, filter_finish_windows([todo[q][1] for q in theirs], [tris[q] for q in theirs], radius, angle_enabled,
+                                                         cos_thr, near_tol, ignore_same_type_triangles, no_match_penalty) if theirs else [])):
+                for q, rq in zip(qs, r):
+                    res[q] = rq
         # simplices that are not Qhull's own (delaunay.py: the same triangles in another order): where the window's numbers hang on that
         # order -- the device counted such places, or a cosine sits at the threshold and the host is about to re-decide the filter --
         # the window is finished again with scipy's

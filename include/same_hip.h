@@ -473,6 +473,33 @@ int same_window_filter_finish_device(same_window *const *windows, int n_windows,
 int same_delaunay_filtered(same_ctx *ctx, const double *xy, int64_t n, double radius, int angle_enabled, double cos_thr, double guard,
                            int32_t *out_tris, int64_t cap, int64_t *out_n_tris, int32_t *out_status);
 
+/* ---- the optimal-assignment incumbent (csrc/assign.hip): the reference's init_method="hungarian" MIP start (src/init_helpers.py:135-175)
+ * on its SPARSE form, without the size cap of :136-142.  Rows are the aligned cells, columns the reference cells plus one private
+ * no-match column per row; the edges are the pairs at their costs and each row's edge to its own no-match column; every row is
+ * assigned at minimum total cost, and a row on its no-match column is unmatched (:163-175).  With every no-match cost below big_m / 2
+ * this is the reference's dense big-M problem (same_assign_matrix); the caller checks that and max_matches == 1 (:97-98).  Solved by
+ * successive shortest paths with Jonker-Volgenant potentials, one wave per problem, the searches in row order inside the kernel; a
+ * certificate kernel checks every reduced cost (>= -delta, delta an fp64 rounding bound) and v = 0 on free reference columns.  The
+ * answer depends on the input alone.  A problem the certificate refuses (or that needs more steps than a cap) is FLAGGED: its caller
+ * solves it elsewhere.
+ *   same_sparse_assign: host buffers.  pairs[P][2] = (row < n_m, column < n_r), each (row, column) at most once; unmatched[n_m] the
+ *     no-match costs.  out_match_pair[i] = index of row i's pair, -1 = unmatched.  out_stats[4] = {searches, columns finalized, flags
+ *     (!= 0: not certified, the matching must not be used), objective as the bits of a double}.  One wait.
+ *   same_window_set_incumbent: what same_window_filter_finish / _device match a window by from its next call on:
+ *     SAME_INCUMBENT_GREEDY (the default: src/init_helpers.py:104-133) or SAME_INCUMBENT_ASSIGNMENT (no_match cost = no_match_penalty *
+ *     size, the fp64 product of the greedy rule; stats slot 6 then counts the searches, not greedy rounds).
+ *   same_window_incumbent_result: after a finish call in assignment mode, its searches, flags and objective (0 otherwise).
+ *   same_window_refinish: a finished window's tail again (matched rows, the three sweeps, stats) under the caller's match_pair[n kept]
+ *     (pair index per kept cell, -1 = none): how the caller replaces a flagged window's assignment.  One wait. */
+#define SAME_INCUMBENT_GREEDY 0
+#define SAME_INCUMBENT_ASSIGNMENT 1
+int same_sparse_assign(same_ctx *ctx, const int32_t *pairs, const double *costs, int64_t P, const double *unmatched, int64_t n_m,
+                       int64_t n_r, int32_t *out_match_pair, int64_t *out_stats);
+int same_window_set_incumbent(same_window *window, int mode);
+int same_window_incumbent_result(same_window *window, int64_t *out_rounds, int64_t *out_flags, double *out_objective);
+int same_window_refinish(same_window *window, const int32_t *match_pair, int32_t *out_match_row, uint8_t *out_point_flag,
+                         int64_t *out_stats);
+
 /* ---- f3 on the window path: the window merge where the windows' matches are ------------------------------------------------
  * The reference trims every window's match table to the window's central region (src/same.py:565-582), concatenates the tables and
  * merges them (helpers.merge_window_matches_unique_ref, src/helpers.py:692-815: one row per (aligned, ref) pair -- not violating

@@ -1,0 +1,34 @@
+// assign.h -- the optimal-assignment incumbent (assign.hip) as the window path (window_finish.hip) and the host-buffer entry point
+// (same_sparse_assign) launch it.
+#pragma once
+#include "window_internal.h"
+
+namespace asg {
+
+// one problem: rows 0..n-1 with their pairs a contiguous run prow[i] .. prow[i+1] of the pair list (column = pairs[2 p + 1] in
+// 0..n_r-1, each column at most once per row), the row's no-match column n_r + i
+struct AssignArgs {
+    const int32_t *prow = nullptr, *pairs = nullptr;
+    const double *cost = nullptr;
+    const double *unm = nullptr;          // no-match cost per row, or null: penalty * size[i]
+    const double *size = nullptr;
+    double penalty = 0.0;
+    int64_t n = 0, n_r = 0, max_pops = 0;
+    uint8_t *alive = nullptr;             // or null: the greedy rule's pair flags, cleared (match_rows_kernel reads them)
+    int32_t *match_pair = nullptr;        // [n] out: the pair of each row, -1 = its no-match column
+    unsigned long long *res = nullptr;    // [4] out: searches, columns finalized, flags (!= 0: not certified), objective (fp64 bits)
+    // the work arrays (carve): per column (n_r + n) ...
+    int32_t *col_row = nullptr, *pred = nullptr, *mark = nullptr, *list = nullptr, *done = nullptr, *ppair = nullptr;
+    double *v = nullptr, *d = nullptr, *ec = nullptr;
+    // ... per row
+    int32_t *row_col = nullptr;
+    double *rc = nullptr;
+};
+
+size_t work_bytes(int64_t n, int64_t n_r);
+void carve(AssignArgs *a, char *work);           // the work arrays of `a` (n, n_r set) in `work` (work_bytes, 256-byte aligned)
+int64_t default_max_pops(int64_t n, int64_t n_r, int64_t P);
+// the solve and its certificate for up to SAME_LAUNCH_WINDOWS problems: two launches, no wait
+int launch(same_ctx *ctx, const AssignArgs *jobs, int n_w);
+
+}  // namespace asg

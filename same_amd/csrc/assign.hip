@@ -1,0 +1,400 @@
+// assign.hip -- the optimal-assignment incumbent: the reference's init_method="hungarian" MIP start (src/init_helpers.py:135-175)
+// solved on its sparse form, with no size cap (the reference's dense n_aligned x (n_ref + n_aligned) matrix gives up above
+// init_hungarian_max_n, :136-142).
+//
+// Rows are the window's kept aligned cells, columns its reference cells plus one PRIVATE no-match column per row (column n_r + i, cost
+// no_match_penalty * size[i] -- the fp64 product row_prefer_kernel forms -- or the caller's `unmatched[i]`).  Every row is assigned; a
+// row on its no-match column is unmatched (:163-175).  With every no-match cost below big_m / 2 this is the reference's dense big-M
+// problem (the caller checks that).
+//
+// The method: successive shortest augmenting paths with Jonker-Volgenant potentials, one WAVE per window.
+//   * dual start: v = 0; every row takes the argmin of its row (a pair beats the no-match column only when strictly cheaper; among pairs
+//     the first in pair order).  A reference column wanted by several rows goes to the lowest row; the others start free.  Every
+//     matched edge then has reduced cost 0 and every edge a reduced cost >= 0: the state is optimal for the rows it matches.
+//   * each free row, in row order, is one Dijkstra search on reduced costs c_rk - v_k - (c_r,m(r) - v_m(r)).  Its own no-match column is
+//     always free, so the search is bounded by that edge and stays local.  Columns are finalized by (distance, column index); a free
+//     column ends the search (early: a free column reached at the distance just finalized, the lowest such).  The path is flipped and
+//     every finalized column's potential moves by d_k - d_sink (<= 0; free columns keep v = 0).
+//   * searches run one after another inside the kernel (no host round trip), so the answer depends on nothing but the input.
+// A window's work arrays live in global memory (sized by its own counts: no list can outgrow them).  A cap on the columns finalized
+// (`max_pops`), an empty frontier (NaN costs) or a failed certificate flags the window; the caller then solves it on the host.
+//
+// certificate_kernel checks the answer edge by edge, no-match edges included: each row holds a column that holds it back, the row's
+// recorded cost is its edge's, every reduced cost is >= -delta and free reference columns have v = 0, where
+//   delta = 2^-40 (|c_rk| + |v_k| + |c_r,m(r)| + |v_m(r)|)
+// bounds the fp64 rounding the potentials gather over a window's searches (each update is one rounded difference of path sums).
+#include "assign.h"
+
+namespace {
+
+constexpr int WAVE = 64;
+constexpr int32_t NO_OWNER = 0x7fffffff;
+
+__device__ __forceinline__ double wave_min(double x) {
+    for (int o = WAVE / 2; o > 0; o >>= 1) x = fmin(x, __shfl_xor(x, o));
+    return x;
+}
+__device__ __forceinline__ double wave_sum(double x) {
+    for (int o = WAVE / 2; o > 0; o >>= 1) x += __shfl_xor(x, o);
+    return x;
+}
+__device__ __forceinline__ double no_match_cost(const asg::AssignArgs &a, int64_t i) {
+    return a.unm ? a.unm[i] : a.penalty * a.size[i];
+}
+
+__global__ __launch_bounds__(WAVE) void assign_kernel(win::Batch<asg::AssignArgs> b) {
+    const asg::AssignArgs &a = b.w[blockIdx.y];
+    const int lane = threadIdx.x;
+    const int64_t n = a.n, n_r = a.n_r, C = n_r + n;
+    if (n == 0) {
+        if (lane == 0) a.res[0] = a.res[1] = a.res[2] = a.res[3] = 0;
+        return;
+    }
+    const int64_t P = a.prow[n];
+    for (int64_t k = lane; k < C; k += WAVE) {
+        a.col_row[k] = -1;
+        a.v[k] = 0.0;
+        a.mark[k] = 0;
+        a.pred[k] = NO_OWNER;
+    }
+    if (a.alive)
+        for (int64_t p = lane; p < P; p += WAVE) a.alive[p] = 0;
+    __syncthreads();
+    // dual start: every row on its row minimum
+    for (int64_t i = lane; i < n; i += WAVE) {
+        double best = no_match_cost(a, i);
+        int64_t bj = n_r + i;
+        int32_t bp = -1;
+        for (int32_t p = a.prow[i]; p < a.prow[i + 1]; ++p) {
+            const double c = a.cost[p];
+            if (c < best) {
+                best = c;
+                bj = a.pairs[2 * (int64_t)p + 1];
+                bp = p;
+            }
+        }
+        a.row_col[i] = (int32_t)bj;
+        a.rc[i] = best;
+        a.match_pair[i] = bp;
+        if (bj < n_r) atomicMin(&a.pred[bj], (int32_t)i);
+        else a.col_row[bj] = (int32_t)i;
+    }
+    __syncthreads();
+    for (int64_t i = lane; i < n; i += WAVE) {
+        const int32_t j = a.row_col[i];
+        if (j < n_r) {
+            if (a.pred[j] == (int32_t)i) {
+                a.col_row[j] = (int32_t)i;
+            } else {
+                a.row_col[i] = -1;
+                a.match_pair[i] = -1;
+            }
+        }
+    }
+    __syncthreads();
+
+    unsigned long long searches = 0, pops = 0, flags = 0;
+    int32_t stamp = 0;
+    const unsigned long long lt_mask = (1ull << lane) - 1;   // lanes below this one
+    for (int64_t base = 0; base < n && !flags; base += WAVE) {
+        const int64_t i = base + lane;
+        unsigned long long todo = __ballot(i < n && a.row_col[i] < 0);
+        while (todo && !flags) {
+            const int32_t i0 = (int32_t)(base + __builtin_ctzll(todo));
+            todo &= todo - 1;
+            ++searches;
+            ++stamp;
+            const int32_t s_front = 2 * stamp, s_done = 2 * stamp + 1;
+            int64_t L = 0, F = 0;      // frontier length, columns finalized
+            double ub = __builtin_inf(), d_sink = 0.0;
+            int32_t sink = -1;
+            // relax row r's edges (pairs, then its no-match column) from distance `off`; a free column reached at distance <= `early`
+            // (the distance just finalized: nothing can come closer) ends the search at once -- the lowest such column
+            auto relax = [&](int32_t r, double off, double early) {
+                const int32_t lo = a.prow[r], cnt = a.prow[r + 1] - lo + 1;
+                int32_t early_k = NO_OWNER;
+                for (int32_t e0 = 0; e0 < cnt; e0 += WAVE) {
+                    const int32_t e = e0 + lane;
+                    bool fresh = false, upd = false;
+                    int32_t k = -1;
+                    double nd = __builtin_inf();
+                    if (e < cnt) {
+                        int32_t pp = -1;
+                        double c;
+                        if (e < cnt - 1) {
+                            pp = lo + e;
+                            k = a.pairs[2 * (int64_t)pp + 1];
+                            c = a.cost[pp];
+                        } else {
+                            k = (int32_t)(n_r + r);
+                            c = no_match_cost(a, r);
+                        }
+                        const int32_t mk = a.mark[k];
+                        nd = off + (c - a.v[k]);
+                        if (mk != s_done && nd <= ub) {
+                            fresh = mk != s_front;
+                            upd = fresh || nd < a.d[k];
+                            if (upd) {
+                                a.d[k] = nd;
+                                a.pred[k] = r;
+                                a.ec[k] = c;
+                                a.ppair[k] = pp;
+                                a.mark[k] = s_front;
+                            }
+                        }
+                    }
+                    const bool free_col = upd && a.col_row[k] < 0;
+                    const unsigned long long nb = __ballot(fresh);
+                    if (fresh) a.list[L + __builtin_popcountll(nb & lt_mask)] = k;
+                    L += __builtin_popcountll(nb);
+                    ub = fmin(ub, wave_min(free_col ? nd : __builtin_inf()));
+                    int32_t ek = free_col && nd <= early ? k : NO_OWNER;
+                    for (int o = WAVE / 2; o > 0; o >>= 1) ek = min(ek, __shfl_xor(ek, o));
+                    early_k = min(early_k, ek);
+                }
+                __syncthreads();
+                return early_k;
+            };
+            relax(i0, 0.0, -__builtin_inf());
+            for (;;) {
+                if (L == 0 || ++pops > (unsigned long long)a.max_pops) {   // no free column reachable (NaN costs), or the cap
+                    flags |= L == 0 ? 1 : 2;
+                    break;
+                }
+                double bd = __builtin_inf();
+                int32_t bk = NO_OWNER;
+                int64_t bpos = -1;
+                for (int64_t x = lane; x < L; x += WAVE) {
+                    const int32_t k = a.list[x];
+                    const double dk = a.d[k];
+                    if (dk < bd || (dk == bd && k < bk)) {
+                        bd = dk;
+                        bk = k;
+                        bpos = x;
+                    }
+                }
+                for (int o = WAVE / 2; o > 0; o >>= 1) {
+                    const double od = __shfl_xor(bd, o);
+                    const int32_t ok = __shfl_xor(bk, o);
+                    const int64_t op = __shfl_xor(bpos, o);
+                    if (od < bd || (od == bd && ok < bk)) {
+                        bd = od;
+                        bk = ok;
+                        bpos = op;
+                    }
+                }
+                if (bk == NO_OWNER) {              // only NaN distances left
+                    flags |= 1;
+                    break;
+                }
+                --L;
+                if (lane == 0) {
+                    a.list[bpos] = a.list[L];
+                    a.mark[bk] = s_done;
+                    a.done[F] = bk;
+                }
+                ++F;
+                __syncthreads();
+                const int32_t r = a.col_row[bk];
+                if (r < 0) {
+                    sink = bk;
+                    d_sink = bd;
+                    break;
+                }
+                const int32_t ek = relax(r, bd - (a.rc[r] - a.v[bk]), bd);
+                if (ek != NO_OWNER) {
+                    sink = ek;
+                    d_sink = a.d[ek];
+                    if (lane == 0) {
+                        a.mark[ek] = s_done;
+                        a.done[F] = ek;
+                    }
+                    ++F;
+                    __syncthreads();
+                    break;
+                }
+            }
+            if (flags) break;
+            // flip the path, then move the finalized columns' potentials
+            if (lane == 0) {
+                int32_t j = sink;
+                for (int64_t steps = 0;; ++steps) {
+                    if (steps > F) {
+                        flags |= 1;
+                        break;
+                    }
+                    const int32_t r = a.pred[j], prev = a.row_col[r];
+                    a.row_col[r] = j;
+                    a.col_row[j] = r;
+                    a.rc[r] = a.ec[j];
+                    a.match_pair[r] = a.ppair[j];
+                    if (r == i0) break;
+                    j = prev;
+                }
+            }
+            for (int64_t f = lane; f < F; f += WAVE) {
+                const int32_t k = a.done[f];
+                a.v[k] += a.d[k] - d_sink;
+            }
+            flags = __shfl(flags, 0);
+            __syncthreads();
+        }
+    }
+    double obj = 0.0;
+    for (int64_t i = lane; i < n; i += WAVE) obj += a.rc[i];
+    obj = wave_sum(obj);
+    if (lane == 0) {
+        a.res[0] = searches;
+        a.res[1] = pops;
+        a.res[2] = flags;
+        a.res[3] = (unsigned long long)__double_as_longlong(obj);
+    }
+}
+
+// the certificate: rows (blockIdx.x < row blocks) and reference columns (the blocks after them); any failure sets bit 2 of res[2]
+__global__ __launch_bounds__(256) void certificate_kernel(win::Batch<asg::AssignArgs> b, unsigned row_blocks) {
+    const asg::AssignArgs &a = b.w[blockIdx.y];
+    const int64_t n = a.n, n_r = a.n_r, C = n_r + n;
+    bool bad = false;
+    if (blockIdx.x < row_blocks) {
+        const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        if (i >= n) return;
+        const int32_t m = a.row_col[i], mp = a.match_pair[i];
+        if (m < 0 || m >= C || a.col_row[m] != (int32_t)i) {
+            bad = true;
+        } else {
+            const double cm = a.rc[i], vm = a.v[m], h = cm - vm;
+            const double cnm = no_match_cost(a, i);
+            if (mp >= 0) bad = mp < a.prow[i] || mp >= a.prow[i + 1] || a.pairs[2 * (int64_t)mp + 1] != m || !(a.cost[mp] == cm);
+            else bad = m != n_r + i || !(cnm == cm);
+            for (int32_t p = a.prow[i]; p <= a.prow[i + 1] && !bad; ++p) {
+                const bool nm = p == a.prow[i + 1];
+                const int64_t k = nm ? n_r + i : a.pairs[2 * (int64_t)p + 1];
+                const double c = nm ? cnm : a.cost[p], vk = a.v[k];
+                const double red = (c - vk) - h;
+                const double tol = 0x1p-40 * (fabs(c) + fabs(vk) + fabs(cm) + fabs(vm));
+                bad = !(red >= -tol);
+            }
+        }
+    } else {
+        const int64_t j = (int64_t)(blockIdx.x - row_blocks) * blockDim.x + threadIdx.x;
+        if (j >= n_r) return;
+        const int32_t r = a.col_row[j];
+        bad = r < 0 ? a.v[j] != 0.0 : (r >= n || a.row_col[r] != (int32_t)j);
+    }
+    if (bad) atomicOr(&a.res[2], 4ull);
+}
+
+}  // namespace
+
+namespace asg {
+
+size_t work_bytes(int64_t n, int64_t n_r) {
+    const size_t C = (size_t)(n + n_r);
+    win::Carver cv;
+    for (int q = 0; q < 6; ++q) cv.take(C * 4);     // col_row pred mark list done ppair
+    cv.take((size_t)n * 4);                           // row_col
+    for (int q = 0; q < 3; ++q) cv.take(C * 8);     // v d ec
+    cv.take((size_t)n * 8);                           // rc
+    return cv.off;
+}
+
+void carve(AssignArgs *a, char *work) {
+    const size_t C = (size_t)(a->n + a->n_r);
+    win::Carver cv;
+    int32_t **ints[6] = {&a->col_row, &a->pred, &a->mark, &a->list, &a->done, &a->ppair};
+    for (auto p : ints) *p = reinterpret_cast<int32_t *>(work + cv.take(C * 4));
+    a->row_col = reinterpret_cast<int32_t *>(work + cv.take((size_t)a->n * 4));
+    double **dbls[3] = {&a->v, &a->d, &a->ec};
+    for (auto p : dbls) *p = reinterpret_cast<double *>(work + cv.take(C * 8));
+    a->rc = reinterpret_cast<double *>(work + cv.take((size_t)a->n * 8));
+}
+
+int64_t default_max_pops(int64_t n, int64_t n_r, int64_t P) {
+    // every search finalizes at most n_r + n columns; a window that needs more than this many in all is left to the host
+    return 64 * (n + n_r + P) + 4096;
+}
+
+int launch(same_ctx *ctx, const AssignArgs *jobs, int n_w) {
+    if (n_w <= 0) return SAME_OK;
+    win::Batch<AssignArgs> bt{};
+    int64_t max_n = 0, max_r = 0;
+    for (int q = 0; q < n_w; ++q) {
+        bt.w[q] = jobs[q];
+        max_n = std::max(max_n, jobs[q].n);
+        max_r = std::max(max_r, jobs[q].n_r);
+    }
+    SAME_LAUNCH(ctx, assign_kernel, dim3(1, (unsigned)n_w), dim3(WAVE), 0, bt);
+    const unsigned rb = win::grid_for(max_n);
+    SAME_LAUNCH(ctx, certificate_kernel, dim3(rb + win::grid_for(max_r), (unsigned)n_w), dim3(256), 0, bt, rb);
+    HIP_TRY(ctx, hipGetLastError());
+    return SAME_OK;
+}
+
+}  // namespace asg
+
+extern "C" int same_sparse_assign(same_ctx *ctx, const int32_t *pairs, const double *costs, int64_t P, const double *unmatched, int64_t n_m,
+                                  int64_t n_r, int32_t *out_match_pair, int64_t *out_stats) {
+    REQUIRE(ctx, ctx != nullptr);
+    REQUIRE(ctx, P >= 0 && n_m >= 0 && n_r >= 0 && n_m + n_r < ((int64_t)1 << 30) && P < ((int64_t)1 << 31) - 1);
+    REQUIRE(ctx, (P == 0 || (pairs && costs)) && (n_m == 0 || (unmatched && out_match_pair)) && out_stats);
+    // the pairs by row (stable), each (row, column) once
+    std::vector<int32_t> prow((size_t)n_m + 1, 0), order((size_t)P), csr((size_t)P * 2);
+    std::vector<double> ccsr((size_t)P);
+    for (int64_t p = 0; p < P; ++p) {
+        const int32_t i = pairs[2 * p], j = pairs[2 * p + 1];
+        REQUIRE(ctx, i >= 0 && i < n_m && j >= 0 && j < n_r);
+        ++prow[(size_t)i + 1];
+    }
+    for (int64_t i = 0; i < n_m; ++i) prow[(size_t)i + 1] += prow[(size_t)i];
+    {
+        std::vector<int32_t> at(prow.begin(), prow.end() - 1);
+        for (int64_t p = 0; p < P; ++p) order[(size_t)at[(size_t)pairs[2 * p]]++] = (int32_t)p;
+    }
+    std::vector<int64_t> seen((size_t)n_r, -1);
+    for (int64_t i = 0; i < n_m; ++i)
+        for (int32_t q = prow[(size_t)i]; q < prow[(size_t)i + 1]; ++q) {
+            const int32_t p = order[(size_t)q], j = pairs[2 * (int64_t)p + 1];
+            if (seen[(size_t)j] == i) {
+                ctx->err = "invalid argument: a (row, column) pair given twice";
+                return SAME_EINVAL;
+            }
+            seen[(size_t)j] = i;
+            csr[2 * (size_t)q] = (int32_t)i;
+            csr[2 * (size_t)q + 1] = j;
+            ccsr[(size_t)q] = costs[p];
+        }
+    SAME_TRY(same_use(ctx));
+    win::Carver cv;
+    const size_t o_prow = cv.take(((size_t)n_m + 1) * 4), o_pairs = cv.take((size_t)P * 8 + 8), o_cost = cv.take((size_t)P * 8 + 8),
+                 o_unm = cv.take((size_t)n_m * 8 + 8), o_match = cv.take((size_t)n_m * 4 + 4), o_res = cv.take(4 * 8),
+                 o_work = cv.take(asg::work_bytes(n_m, n_r));
+    char *d = nullptr;
+    SAME_TRY(slot_as(ctx, SL_OUT0, cv.off, &d));
+    asg::AssignArgs a{};
+    a.prow = reinterpret_cast<const int32_t *>(d + o_prow);
+    a.pairs = reinterpret_cast<const int32_t *>(d + o_pairs);
+    a.cost = reinterpret_cast<const double *>(d + o_cost);
+    a.unm = reinterpret_cast<const double *>(d + o_unm);
+    a.n = n_m;
+    a.n_r = n_r;
+    a.match_pair = reinterpret_cast<int32_t *>(d + o_match);
+    a.res = reinterpret_cast<unsigned long long *>(d + o_res);
+    a.max_pops = asg::default_max_pops(n_m, n_r, P);
+    asg::carve(&a, d + o_work);
+    SAME_COPY(ctx, d + o_prow, prow.data(), prow.size() * 4, hipMemcpyHostToDevice);
+    if (P) {
+        SAME_COPY(ctx, d + o_pairs, csr.data(), (size_t)P * 8, hipMemcpyHostToDevice);
+        SAME_COPY(ctx, d + o_cost, ccsr.data(), (size_t)P * 8, hipMemcpyHostToDevice);
+    }
+    if (n_m) SAME_COPY(ctx, d + o_unm, unmatched, (size_t)n_m * 8, hipMemcpyHostToDevice);
+    SAME_TRY(asg::launch(ctx, &a, 1));
+    std::vector<int32_t> mp((size_t)n_m);
+    unsigned long long res[4] = {};
+    if (n_m) SAME_COPY(ctx, mp.data(), a.match_pair, (size_t)n_m * 4, hipMemcpyDeviceToHost);
+    SAME_COPY(ctx, res, a.res, sizeof res, hipMemcpyDeviceToHost);
+    SAME_WAIT(ctx);
+    for (int64_t i = 0; i < n_m; ++i) out_match_pair[i] = mp[(size_t)i] >= 0 ? order[(size_t)mp[(size_t)i]] : -1;
+    for (int q = 0; q < 4; ++q) out_stats[q] = (int64_t)res[q];
+    return SAME_OK;
+}

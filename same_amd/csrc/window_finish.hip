@@ -5,7 +5,7 @@
 // (src/same.py:1128-1146), per-row minimum and the greedy MIP start (src/init_helpers.py:104-133), the lazy-constraint body under
 // that incumbent (src/same.py:645-669), XY-order sweep (src/violationhelper.py:53-117), signed-area flips (src/same.py:1362-1402).
 // Back to the host: the matched reference row per kept aligned cell, the per-cell violation flags and eight counters.
-#include "window_internal.h"
+#include "assign.h"
 
 namespace {
 
@@ -372,6 +372,7 @@ struct FinishPlan {
     unsigned long long *counters = nullptr;
     int64_t cap_tr = 0;
     const unsigned long long *dTr = nullptr;
+    char *assign_work = nullptr;              // the optimal assignment's work arrays (SAME_INCUMBENT_ASSIGNMENT), else null
 };
 
 // match rows + the one pass over the triangles, for a group of windows (<= SAME_LAUNCH_WINDOWS) in one launch each
@@ -417,6 +418,7 @@ int prepare_finish(same_window *w, const int32_t *host_tris, int64_t cap_tr, con
     const size_t tt = (size_t)std::max<int64_t>(cap_tr, 1);
     const size_t o_alive = cv.take((size_t)std::max<int64_t>(P, 1)), o_match_pair = cv.take((size_t)n * 4), o_match_loc = cv.take((size_t)n * 4),
                  o_sign = cv.take(tt), o_weight = cv.take(tt * 8);
+    const size_t o_assign = w->incumbent == SAME_INCUMBENT_ASSIGNMENT ? cv.take(asg::work_bytes(n, w->n_r)) : 0;
     SAME_TRY(ensure(ctx, w->finish, cv.off));
     SAME_TRY(ensure(ctx, w->tris, tt * 12));
     char *base = static_cast<char *>(w->finish.p);
@@ -445,6 +447,7 @@ int prepare_finish(same_window *w, const int32_t *host_tris, int64_t cap_tr, con
     w->pflag = p->pflag;
     w->sign = reinterpret_cast<int8_t *>(at(o_sign));
     w->weight = reinterpret_cast<double *>(at(o_weight));
+    p->assign_work = o_assign ? at(o_assign) : nullptr;
     p->cap_tr = cap_tr;
     p->dTr = dTr;
     REQUIRE(ctx, w->host_finish_off + p->back_bytes <= w->host_filter_off);   // sized by the stage call
@@ -455,6 +458,31 @@ int prepare_finish(same_window *w, const int32_t *host_tris, int64_t cap_tr, con
 // greedy MIP start of a group of prepared windows -- per-row minimum, rows that beat their penalty, the scan's matching (one pair per
 // aligned row) -- and the tail: one launch per kernel for the whole group (windows of one batch call share the cost type)
 int launch_finish(same_ctx *ctx, same_window *const *ws, FinishPlan *const *ps, int n_w, double no_match_penalty) {
+    if (ws[0]->incumbent == SAME_INCUMBENT_ASSIGNMENT) {
+        // the optimal assignment instead (assign.hip): it writes match_pair, clears the pairs' greedy flags, and leaves searches, flags
+        // and objective in the head of `sel` (the greedy rounds' words, unused here), which comes back with the finish block
+        asg::AssignArgs jobs[SAME_LAUNCH_WINDOWS];
+        for (int q = 0; q < n_w; ++q) {
+            same_window *w = ws[q];
+            FinishPlan *p = ps[q];
+            asg::AssignArgs &a = jobs[q];
+            a = asg::AssignArgs{};
+            a.prow = w->prow;
+            a.pairs = w->pairs;
+            a.cost = w->cost64;
+            a.size = w->size_c;
+            a.penalty = no_match_penalty;
+            a.n = w->n_ua;
+            a.n_r = w->n_r;
+            a.max_pops = asg::default_max_pops(w->n_ua, w->n_r, w->P);
+            a.alive = p->gs.alive;
+            a.match_pair = p->match_pair;
+            a.res = p->gs.sel;
+            asg::carve(&a, p->assign_work);
+        }
+        SAME_TRY(asg::launch(ctx, jobs, n_w));
+        return enqueue_tail(ctx, ws, ps, n_w);
+    }
     Batch<PreferArgs> pb{};
     same_greedy_job jobs[SAME_LAUNCH_WINDOWS];
     int64_t max_n = 0;
@@ -492,7 +520,12 @@ int read_finish(same_window *w, FinishPlan *p, int32_t *out_match_row, uint8_t *
     const unsigned long long *sel = reinterpret_cast<const unsigned long long *>(h);
     const unsigned long long *cnt = reinterpret_cast<const unsigned long long *>(h + p->o_counters);
     int rounds = 0;
-    if (P) {
+    if (w->incumbent == SAME_INCUMBENT_ASSIGNMENT) {     // no greedy rounds to add: the assignment settled in its one launch
+        rounds = (int)sel[0];
+        w->as_rounds = (int64_t)sel[0];
+        w->as_flags = (int64_t)sel[2];
+        memcpy(&w->as_objective, &sel[3], sizeof(double));
+    } else if (P) {
         int q = 0;
         while (q < WINDOW_GREEDY_ROUNDS && sel[q] != 0) ++q;
         rounds = q;
@@ -577,6 +610,8 @@ int filter_finish(same_window *const *windows, int n_windows, const int32_t *sim
         const int64_t Tr = simplex_offsets[i + 1] - simplex_offsets[i];
         w->filtered = w->finished = 0;
         w->Tr = 0;
+        w->as_rounds = w->as_flags = 0;
+        w->as_objective = 0.0;
         if (w->n_ua == 0) continue;
         if (Tr && !prefiltered) {
             const int32_t *raw = on_device ? static_cast<const int32_t *>(w->dd_tris.p) : d_simplices + 3 * simplex_offsets[i];
@@ -612,7 +647,8 @@ int filter_finish(same_window *const *windows, int n_windows, const int32_t *sim
         rc = launch_filter(ctx, fplans.data() + g, (int)(e - g), radius, angle_enabled, cos_thr, near_tol);
     }
     for (size_t g = 0, e; g < live.size() && rc == SAME_OK; g = e) {
-        for (e = g + 1; e < live.size() && e - g < SAME_LAUNCH_WINDOWS && live[e]->cost_f32 == live[g]->cost_f32; ++e) {}
+        for (e = g + 1; e < live.size() && e - g < SAME_LAUNCH_WINDOWS && live[e]->cost_f32 == live[g]->cost_f32 &&
+                        live[e]->incumbent == live[g]->incumbent; ++e) {}
         rc = launch_finish(ctx, live.data() + g, plans.data() + g, (int)(e - g), no_match_penalty);
     }
     // the finish block of every window and, beside it, the filter's counters: one launch per group straight into the pinned blocks (or
@@ -712,6 +748,48 @@ int same_window_filter_finish_device(same_window *const *windows, int n_windows,
     }
     return filter_finish(windows, n_windows, nullptr, offsets.data(), 0, true, radius, angle_enabled, cos_thr, near_tol, ignore_same_type,
                          ensure_min_triangle_per_node, no_match_penalty, out_match_row, out_point_flag, out_stats, out_counts);
+}
+
+int same_window_set_incumbent(same_window *window, int mode) {
+    if (!window) return SAME_EINVAL;
+    REQUIRE(window->ctx, mode == SAME_INCUMBENT_GREEDY || mode == SAME_INCUMBENT_ASSIGNMENT);
+    window->incumbent = mode;
+    return SAME_OK;
+}
+
+int same_window_incumbent_result(same_window *window, int64_t *out_rounds, int64_t *out_flags, double *out_objective) {
+    if (!window) return SAME_EINVAL;
+    REQUIRE(window->ctx, out_rounds && out_flags && out_objective && window->finished);
+    *out_rounds = window->as_rounds;
+    *out_flags = window->as_flags;
+    *out_objective = window->as_objective;
+    return SAME_OK;
+}
+
+int same_window_refinish(same_window *window, const int32_t *match_pair, int32_t *out_match_row, uint8_t *out_point_flag, int64_t *out_stats) {
+    if (!window) return SAME_EINVAL;
+    same_window *w = window;
+    same_ctx *ctx = w->ctx;
+    REQUIRE(ctx, w->finished && w->staged == 2 && w->n_ua > 0 && match_pair && out_match_row && out_point_flag && out_stats);
+    for (int64_t i = 0; i < w->n_ua; ++i) REQUIRE(ctx, match_pair[i] >= -1 && match_pair[i] < w->P);
+    SAME_TRY(same_use(ctx));
+    // the window's kept triangles are still the first w->Tr of its triangle buffer: lay the finish block out for exactly those
+    FinishPlan p;
+    SAME_TRY(prepare_finish(w, nullptr, w->Tr, nullptr, &p));
+    SAME_FILL(ctx, p.zero, 0, p.zero_bytes);
+    if (w->P) SAME_FILL(ctx, p.gs.alive, 0, (size_t)w->P);
+    SAME_COPY(ctx, p.match_pair, match_pair, (size_t)w->n_ua * 4, hipMemcpyHostToDevice);
+    FinishPlan *pp = &p;
+    SAME_TRY(enqueue_tail(ctx, &w, &pp, 1));
+    char *h = static_cast<char *>(w->host) + w->host_finish_off;
+    SAME_COPY(ctx, h, reinterpret_cast<const char *>(p.gs.sel), p.back_bytes, hipMemcpyDeviceToHost);
+    SAME_WAIT(ctx);
+    const unsigned long long *cnt = reinterpret_cast<const unsigned long long *>(h + p.o_counters);
+    for (int q = 0; q < 8; ++q) out_stats[q] = (int64_t)cnt[q];
+    out_stats[SC_ROUNDS] = w->as_rounds;
+    memcpy(out_match_row, h + p.o_match_row, (size_t)w->n_ua * sizeof(int32_t));
+    memcpy(out_point_flag, h + p.o_pflag, (size_t)w->n_ua);
+    return SAME_OK;
 }
 
 }  // extern "C"

@@ -16,6 +16,11 @@ Same arguments as `sliding_window_matching`; the result has its columns wherever
 * `ref_idx` (index in the window's compacted reference frame) needs the window's pair list on the host and is only made on request
   (`window_local_indices=True`); `aligned_idx` is free.  `run_time` is 0.0, `time_limit_reached` False.
 
+optim_params["hip_incumbent"] = "assignment" (opt-in; "greedy" is the default) takes each window's OPTIMAL one-to-one assignment
+instead: the reference's Hungarian start (src/init_helpers.py:135-175) on its sparse form, without `init_hungarian_max_n`, solved on the
+GPU (csrc/assign.hip).  It needs max_matches == 1 and every no-match cost below init_big_m / 2 (`incumbent_mode`).  With
+return_stats each window's stats then carry its `objective` and `fallback` (the device's certificate refused it; scipy answered).
+
 Two routes produce the same table (tests/test_gpu_run_same.py::test_incumbent_table_routes_agree):
   device   both frames resident on the GPU, two library calls per window, the incumbent and the sweeps computed where the pairs are
            (csrc/window.hip); the host triangulates, receives (match, flags) per window and gathers the table's columns ONCE at the
@@ -36,6 +41,36 @@ from .api import _stage_prune, prepare_same_inputs
 from .window_api import _WindowJob, _WindowSubsetter, _prepared_from_device, _staged_from_device, _window_error
 
 STAT_KEYS = ("pairs", "triangles", "checked", "flipped", "xy_violations", "area_flips", "matched")
+INCUMBENTS = ("greedy", "assignment")          # optim_params["hip_incumbent"]; "greedy" without the key
+
+
+def incumbent_mode(optim_params, gurobi_params=None, moving=None):
+    """optim_params["hip_incumbent"] checked before anything reaches a device -> "greedy" | "assignment".  The assignment is the
+    reference's Hungarian start (src/init_helpers.py:135-175) without its size cap: it needs max_matches == 1 (:97-98, the reference's own
+    message), and it equals the reference's dense big-M problem only while every no-match cost no_match_penalty * size is below
+    init_big_m / 2 (gurobi_params), which is checked over every aligned cell of `moving`."""
+    from .params import init_gurobi_params, init_optim_params
+    from .window_api import ResidentFrames
+
+    op = dict(optim_params or {})
+    mode = op.get("hip_incumbent", "greedy")
+    if not isinstance(mode, str) or mode not in INCUMBENTS:
+        raise ValueError(f"optim_params['hip_incumbent'] must be one of {INCUMBENTS}, not {mode!r}")
+    if mode == "greedy":
+        return mode
+    op = init_optim_params(**op)
+    if op["max_matches"] != 1:
+        raise ValueError("init_method='hungarian' requires max_matches == 1.")
+    big_m = float(init_gurobi_params(**dict(gurobi_params or {}))["init_big_m"])
+    frame = moving.moving_arg if isinstance(moving, ResidentFrames) else moving
+    frame = getattr(frame, "metacell_df", frame)
+    if frame is not None and len(frame):
+        size = frame["size"].to_numpy(dtype=np.float64) if "size" in frame.columns else np.ones(1)
+        worst = float(op["no_match_penalty"]) * size
+        if not np.all(worst < big_m / 2):
+            raise ValueError(f"hip_incumbent='assignment': a no-match cost no_match_penalty * size ({np.nanmax(worst):g}) is not below "
+                             f"init_big_m / 2 ({big_m / 2:g}); the sparse problem would differ from the reference's big-M one")
+    return mode
 
 
 def _default_workers():
@@ -239,11 +274,13 @@ class _TableBuilder:
         return pd.DataFrame(out, copy=False)
 
 
-def incumbent_of_prepared(prep, commonCT, with_ref_idx=True, ctx=None, use_device=True):
+def incumbent_of_prepared(prep, commonCT, with_ref_idx=True, ctx=None, use_device=True, incumbent="greedy"):
     """(match table of ONE window as run_same's post-solve builds it, stats) from its pre-MIP artefacts, through the host-buffer entry
     points: greedy start -> matching -> lazy-constraint body, XY-order sweep, area flips.  The general route of this module.
     use_device: a PreparedInputs made by the device-resident window path with its pair list untouched carries the incumbent and the
-    sweeps already (computed where the pairs are, by same_window_filter_finish): take them instead of computing them again."""
+    sweeps already (computed where the pairs are, by same_window_filter_finish): take them instead of computing them again.
+    incumbent="assignment": the optimal one-to-one assignment (ops.sparse_assign) instead of the greedy start; the stats then carry the
+    window's "objective" and whether it fell back to the host solver ("fallback")."""
     op = prep.optim_params
     dw = getattr(prep, "device", None)
     if use_device and dw is not None and dw.match_row is not None and isinstance(prep.valid_pairs, np.ndarray):
@@ -252,8 +289,13 @@ def incumbent_of_prepared(prep, commonCT, with_ref_idx=True, ctx=None, use_devic
     costs, n_a, n_r = prep.costs_array, prep.n_aligned, prep.n_ref
     a_df, r_df, tris = prep.aligned_df, prep.ref_df, prep.triangles_array
     size = a_df["size"].to_numpy(dtype=np.float64)
-    wants = ops.pair_rowmin(pairs, costs, n_a, ctx=ctx) < float(op["no_match_penalty"]) * size       # src/init_helpers.py:104,118-122
-    pair_of_row, _rounds = ops.greedy_match(pairs, costs, n_a, n_r, wants, ctx=ctx)
+    extra = {}
+    if incumbent == "assignment":
+        pair_of_row, st = ops.sparse_assign(pairs, costs, float(op["no_match_penalty"]) * size, n_a, n_r, ctx=ctx)
+        extra = {"objective": st["objective"], "fallback": st["fallback"]}
+    else:
+        wants = ops.pair_rowmin(pairs, costs, n_a, ctx=ctx) < float(op["no_match_penalty"]) * size     # src/init_helpers.py:104,118-122
+        pair_of_row, _rounds = ops.greedy_match(pairs, costs, n_a, n_r, wants, ctx=ctx)
     ai = np.flatnonzero(pair_of_row >= 0)
     ri = pairs[pair_of_row[ai], 1].astype(np.int64)
     match = np.full(n_a, -1, np.int32)
@@ -271,7 +313,7 @@ def incumbent_of_prepared(prep, commonCT, with_ref_idx=True, ctx=None, use_devic
     if len(t32):
         flip_node[t32[flipped.astype(bool)].reshape(-1)] = True
     stats = {"pairs": len(pairs), "triangles": len(t32), "checked": int(checked), "flipped": len(viol), "xy_violations": int(counts[1]),
-             "area_flips": int(np.count_nonzero(flipped)), "matched": len(ai)}
+             "area_flips": int(np.count_nonzero(flipped)), "matched": len(ai), **extra}
     return _window_table(prep, commonCT, ai, ri, flip_node, pflag, with_ref_idx), stats
 
 
@@ -322,8 +364,11 @@ def _table_of_device_window(prep, dw, commonCT, with_ref_idx):
 def _device_stats(dw):
     """a window's stats record (STAT_KEYS) from what the device counted"""
     st = dw.stats
-    return {"pairs": dw.counts[3], "triangles": dw.n_triangles, "checked": st["checked"], "flipped": st["flipped"],
-            "xy_violations": st["xy_violations"], "area_flips": st["area_flips"], "matched": st["matched"]}
+    rec = {"pairs": dw.counts[3], "triangles": dw.n_triangles, "checked": st["checked"], "flipped": st["flipped"],
+           "xy_violations": st["xy_violations"], "area_flips": st["area_flips"], "matched": st["matched"]}
+    if dw.assignment is not None:
+        rec["objective"], rec["fallback"] = dw.assignment["objective"], dw.assignment["fallback"]
+    return rec
 
 
 def _device_ref_idx(dw):
@@ -353,8 +398,10 @@ def sliding_window_incumbent(ref, moving, commonCT=None, outprefix=None, moving_
     aligned ids ascending -- without the pre-merge table ever being laid out: the merge reads the rows' keys, and only the rows it keeps
     get their columns.  With `_shard` and a `_merge_channel` (dist.MergeChannel) the result is this rank's PART of the merged table
     (dist.sharded_merged_window_incumbent)."""
+    mode = incumbent_mode(optim_params, gurobi_params, moving)
     job = _WindowJob(ref, moving, commonCT, outprefix, moving_delaunay, moving_delaunay_vertex_col, optim_params, gurobi_params,
                      ignore_precomputed_triangulation, _shard)
+    job.incumbent = mode
     frames, own = job.device_frames(_pipeline, ctx=ctx)
     fast = frames is not None and not job.caller_triangulation and not job.optim_params["ignore_knn_if_matched"]
     if _route is not None:
@@ -447,7 +494,7 @@ def _device_route(job, frames, workers, with_ref_idx, triangulator, stats, merge
             collector = lambda states, windows: accs[q].collect(states, [w["trim"] for w in windows], [w["window_id"] for w in windows],
                                                                 [pos_of[id(w)] for w in windows])
         for (pos, w), dw in zip(mine, frames.windows([w for _p, w in mine], ctx=contexts[q], triangulator=triangulator,
-                                                     collector=collector, batch=batch)):
+                                                     collector=collector, batch=batch, incumbent=job.incumbent)):
             if dw.error is not None:
                 raise dw.error
             with stage("table rows (central trim)"):
@@ -634,7 +681,8 @@ def _general_route(job, frames, with_ref_idx, stats, ctx):
             if len(prep.valid_pairs) == 0:               # every node unconstrained under the caller's triangulation: nothing to match
                 continue
             with stage("incumbent + sweeps + table (general route)"):
-                window_matches, stats[pos] = incumbent_of_prepared(prep, commonCT, with_ref_idx, ctx=ctx, use_device=False)
+                window_matches, stats[pos] = incumbent_of_prepared(prep, commonCT, with_ref_idx, ctx=ctx, use_device=False,
+                                                                         incumbent=job.incumbent)
             job.collect(pos, w, window_matches)
     finally:
         job.outprefix = keep_csv

@@ -308,6 +308,61 @@ def greedy_match(pairs, costs, n_aligned, n_ref, prefer, ctx=None):
     return out, rounds.value
 
 
+def sparse_assign(pairs, costs, unmatched, n_aligned, n_ref, ctx=None):
+    """The optimal-assignment incumbent (src/init_helpers.py:135-175 on its sparse form, no size cap): every aligned row assigned to
+    one of its pairs or to its own no-match column at `unmatched[i]`, minimum total cost, on the device (same_sparse_assign).
+    -> (match_pair (n_aligned,) int32: pair index per row, -1 = unmatched; stats {"rounds", "objective", "fallback"}).  A problem the
+    device's certificate refuses is solved again by scipy's sparse solver (`sparse_assign_host`) and counted as a fallback."""
+    ctx = _ctx(ctx)
+    pairs, costs, unmatched = as_c(pairs, I32).reshape(-1, 2), as_c(costs, F64), as_c(unmatched, F64)
+    n_aligned, n_ref = int(n_aligned), int(n_ref)
+    assert len(costs) == len(pairs) and len(unmatched) == n_aligned
+    out = np.empty(n_aligned, I32)
+    st = np.zeros(4, I64)
+    with ctx.lock:
+        ctx.check(ctx.lib.same_sparse_assign(ctx.handle, pairs.ctypes.data, costs.ctypes.data, len(pairs), unmatched.ctypes.data,
+                                             n_aligned, n_ref, out.ctypes.data, st.ctypes.data), "same_sparse_assign")
+    stats = {"rounds": int(st[0]), "objective": float(st[3:4].view(F64)[0]), "fallback": 0}
+    if st[2] != 0:
+        out = sparse_assign_host(pairs, costs, unmatched, n_aligned, n_ref)
+        stats["objective"], stats["fallback"] = assign_objective(out, costs, unmatched), 1
+    return out, stats
+
+
+def sparse_assign_host(pairs, costs, unmatched, n_aligned, n_ref):
+    """The same problem by scipy.sparse.csgraph.min_weight_full_bipartite_matching (the fallback of `sparse_assign` and of the window
+    path).  Sparse matrices drop explicit zeros, so every edge is shifted to be >= 1 first: each row is assigned exactly once, and the
+    shift leaves the optimum where it was.  -> match_pair as `sparse_assign`."""
+    from scipy.sparse import csr_matrix
+    from scipy.sparse.csgraph import min_weight_full_bipartite_matching
+
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    costs, unmatched = np.asarray(costs, F64), np.asarray(unmatched, F64)
+    n_aligned, n_ref = int(n_aligned), int(n_ref)
+    out = np.full(n_aligned, -1, I32)
+    if n_aligned == 0:
+        return out
+    rows = np.concatenate((pairs[:, 0], np.arange(n_aligned)))
+    cols = np.concatenate((pairs[:, 1], n_ref + np.arange(n_aligned)))
+    w = np.concatenate((costs, unmatched))
+    w = w - w.min() + 1.0
+    g = csr_matrix((w, (rows, cols)), shape=(n_aligned, n_ref + n_aligned))
+    row_ind, row_col = min_weight_full_bipartite_matching(g)
+    assert np.array_equal(row_ind, np.arange(n_aligned))
+    lookup = {(int(i), int(j)): p for p, (i, j) in enumerate(pairs.tolist())}
+    for i, j in enumerate(row_col.tolist()):
+        if j < n_ref:
+            out[i] = lookup[(i, j)]
+    return out
+
+
+def assign_objective(match_pair, costs, unmatched):
+    """sum of the assigned edges' costs (pairs, no-match columns) of a `sparse_assign` answer"""
+    match_pair, costs, unmatched = np.asarray(match_pair), np.asarray(costs, F64), np.asarray(unmatched, F64)
+    m = match_pair >= 0
+    return float(np.sum(costs[match_pair[m]]) + np.sum(unmatched[~m]))
+
+
 def tri_flip_stats(axy, mapped_xy, matched, triangles, type_id=None, ctx=None):
     """-> (tri_flag (Tr,) uint8 [bit0 matched, bit1 same type, bit2 flipped], node_tri, node_flip (n,) uint32)."""
     ctx = _ctx(ctx)

@@ -463,6 +463,36 @@ class DeviceWindow:
         stats dict)."""
         return filter_finish_windows([self], [triangles], 0.0, 0, 0.0, 0.0, False, no_match_penalty, True, prefiltered=True)[0][3:]
 
+    INCUMBENTS = {"greedy": 0, "assignment": 1}       # SAME_INCUMBENT_*
+
+    def set_incumbent(self, mode):
+        """what the finish calls match this window by from now on: "greedy" (src/init_helpers.py:104-133) or "assignment" (the optimal
+        one-to-one assignment, csrc/assign.hip)"""
+        with self.ctx.lock:
+            self.ctx.check(self.ctx.lib.same_window_set_incumbent(self.handle, self.INCUMBENTS[mode]), "same_window_set_incumbent")
+
+    def incumbent_result(self):
+        """after a finish call in assignment mode -> (searches, flags: != 0 the device's answer is not certified, objective)"""
+        import ctypes
+
+        rounds, flags, obj = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0.0)
+        with self.ctx.lock:
+            self.ctx.check(self.ctx.lib.same_window_incumbent_result(self.handle, ctypes.byref(rounds), ctypes.byref(flags),
+                                                                     ctypes.byref(obj)), "same_window_incumbent_result")
+        return rounds.value, flags.value, obj.value
+
+    def refinish(self, match_pair):
+        """the finished window's matched rows and sweeps again under `match_pair` (pair index per kept cell, -1 = none) -> (match_row,
+        flag byte, stats dict) as `finish`"""
+        n = self.counts[2]
+        match_pair = np.ascontiguousarray(match_pair, dtype=np.int32)
+        assert len(match_pair) == n
+        match_row, flag, stats = np.empty(n, np.int32), np.empty(n, np.uint8), np.zeros(8, np.int64)
+        with self.ctx.lock:
+            self.ctx.check(self.ctx.lib.same_window_refinish(self.handle, match_pair.ctypes.data, match_row.ctypes.data, flag.ctypes.data,
+                                                             stats.ctypes.data), "same_window_refinish")
+        return match_row, flag, dict(zip(self.STAT_NAMES, stats.tolist()))
+
     def close(self):
         if getattr(self, "handle", None) and self.ctx.handle:
             with self.ctx.lock:
@@ -788,16 +818,33 @@ def _filter_finish_results(states, call, what):
     return out
 
 
+def _assignment_result(state, out, moving, no_match_penalty, match_row, cell_flags, stats):
+    """a finished window in assignment mode: its searches and objective; a window the device's certificate refused is solved by scipy's
+    sparse solver and finished again under that matching (counted as a fallback)"""
+    from ._trace import stage as marked
+
+    rounds, flags, objective = state.incumbent_result()
+    fallback = 0
+    if flags:
+        with marked("assignment fallback (host)"):
+            pairs, costs = state.fetch(_W_PAIRS), state.fetch(_W_COSTS)
+            unmatched = float(no_match_penalty) * moving.size[out.rows_m].astype(np.float64)
+            mp = ops.sparse_assign_host(pairs, costs, unmatched, len(unmatched), out.counts[1])
+            match_row, cell_flags, stats = state.refinish(mp)
+            objective, fallback = ops.assign_objective(mp, costs, unmatched), 1
+    return match_row, cell_flags, stats, {"objective": objective, "fallback": fallback, "rounds": rounds}
+
+
 class DeviceWindowResult:
     """What one window of `iter_device_windows` leaves on the host: `rows_m` section rows of the kept aligned cells, `axy` their XY,
     `triangles` the kept Delaunay triangles over them (None unless asked for or filtered on the host; `n_triangles` always),
     `match_row` the section row of each cell's matched reference cell (-1 = none), `point_flag` the XY-order sweep's per-cell flag,
     `flip_flag` 1 for the vertices of triangles whose signed area flips, `stats` the sweeps' counters, `counts` (aligned in box, refs in
     box, kept, pairs); `state` is the live DeviceWindow until the generator is asked for the first window of the next batch (pairs,
-    costs, signs ... through `state.fetch`)."""
+    costs, signs ... through `state.fetch`).  `assignment` (incumbent="assignment" only): {"objective", "fallback", "rounds"}."""
 
     __slots__ = ("window", "error", "rows_m", "axy", "triangles", "n_triangles", "match_row", "point_flag", "flip_flag", "stats",
-                 "counts", "state")
+                 "counts", "state", "assignment")
 
     def __init__(self, window):
         self.window = window
@@ -848,7 +895,7 @@ class TriangulationCache:
 
 def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dist_ct_coeff=1.0, min_angle_deg=15,
                         ignore_same_type_triangles=True, no_match_penalty=100.0, ctx=None, fetch_triangles=False, triangulator=None,
-                        triangulate=True, batch=None, collector=None):
+                        triangulate=True, batch=None, collector=None, incumbent="greedy"):
     """The window path of `iter_window_arrays` + the greedy incumbent and the three sweeps, with both sections resident on the
     device (`dref`, `dmoving`: DeviceSections of `ref`, `moving`): per window the host only triangulates (Qhull helpers, windows
     ahead as before) and receives the match; the triangle filter runs on the device too, unless a cosine sits within 8 ulp of the
@@ -863,7 +910,10 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
     `triangulate=False` stops after the stage call (rows, prune, costs, compaction): the caller brings its own triangles
     (api.sliding_window_matching with a caller's triangulation) and reads pairs / costs through `state.fetch`.
     `collector(states, windows)` is called once per finished batch with its windows' live states (the window merge's accumulator:
-    MergeAccumulator.collect)."""
+    MergeAccumulator.collect).
+    `incumbent`: "greedy" (src/init_helpers.py:104-133) or "assignment" -- the optimal one-to-one assignment of the window's kept cells
+    under the pair costs with a no-match column per cell (csrc/assign.hip); a window whose answer the device does not certify is solved
+    again on the host (ops.sparse_assign_host) and finished again under that matching."""
     import os
     from collections import deque
 
@@ -942,6 +992,8 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
             out.state, out.n_triangles = state, 0
         if not triangulate or not todo:
             return
+        for _o, state, _t in todo:
+            state.set_incumbent(incumbent)
         if on_device:
             with marked("triangulate (device)"):
                 status, _n = triangulate_windows([st for _o, st, _t in todo], radius, angle_enabled, cos_thr, triangulator.guard)
@@ -979,6 +1031,9 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
                                                                _type_id=tid)
                 with marked("signs + incumbent + sweeps (device)"):
                     match_row, cell_flags, stats = state.finish(out.triangles, no_match_penalty)
+            if incumbent == "assignment":
+                match_row, cell_flags, stats, out.assignment = _assignment_result(state, out, moving, no_match_penalty, match_row,
+                                                                                  cell_flags, stats)
             out.match_row, out.stats = match_row, stats
             # the library packs both per-cell flags into one byte
             out.point_flag, out.flip_flag = cell_flags & 1, (cell_flags >> 1) & 1

@@ -1,5 +1,6 @@
-"""The window path's own triangulator (opt-in): `same_delaunay2d` of libsame_hip instead of scipy.spatial.Delaunay, where that is
-provably the same thing.
+"""How the window path triangulates: the Qhull helper pool (the default), and two opt-in routes that give the same tables --
+libsame_hip's own triangulator (`same_delaunay2d`) instead of scipy.spatial.Delaunay where that is provably the same thing, and the
+device's (`same_window_delaunay`).
 
 The reference triangulates every window's kept aligned cells with Qhull through scipy (src/same.py:1023); at ~1.6 us per point
 that is three quarters of a cfg 5 pass, on the host, with the GPU waiting (`qhull_wait_share` 0.8).  libsame_hip's triangulator is
@@ -21,8 +22,13 @@ sign clear of `GUARD` x Qhull's allowance, the same formula: csrc/qhull_margin.h
 (same_window_filter_finish_device), and a window it refuses goes to the Qhull helpers, started on the first refusal.  The ORDER rule
 above is the same rule: windows.iter_device_windows re-finishes a window with order ties or a cosine at the threshold with scipy's
 simplices.  `DeviceTriangulator.stats` (and `last_device_stats()` for the last pass of `sliding_window_incumbent`) count a pass's
-windows submitted, refused and re-finished, each window once.  tests/test_delaunay_cpu.py (sets of triangles against scipy, fallbacks), tests/test_gpu_delaunay.py (tables of
-both ways bit-identical; forced ties), tools/delaunay_margin.py (where Qhull itself stops being exact).
+windows submitted, refused and re-finished, each window once.
+
+Every route is a `Triangulator` -- `QHULL` (the helper pool), windows.TriangulationCache, `NativeTriangulator`, `DeviceTriangulator`
+-- and hands out `Ticket`s; that protocol is all windows.iter_device_windows knows of them.  `triangulator_for(optim_params)` picks the
+route of a pass.  tests/test_delaunay_cpu.py (sets of triangles against scipy, fallbacks, tickets), tests/test_gpu_delaunay.py and
+tests/test_gpu_device_delaunay.py (tables of every route bit-identical; forced ties), tools/delaunay_margin.py (where Qhull itself
+stops being exact).
 """
 import os
 import threading
@@ -30,11 +36,12 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from . import _lib
+from . import _lib, qhull_pool
 
 # x Qhull's round-off allowance: 60 x the largest ratio (0.27) at which Qhull's triangles differed from the exact ones in 6 000
+# calibration sets (an edge's property, not a set's: larger sets have smaller margins only because they have more edges) -- calibrated,
+# not proven
 GUARD = 16.0
-               # calibration sets (an edge's property, not a set's: larger sets have smaller margins only because they have more edges)
 
 
 def mode(optim_params=None):
@@ -71,68 +78,6 @@ def device_filtered_triangles(points, radius, min_angle_deg, ctx=None, guard=GUA
     return (tris, status.value) if with_status else tris
 
 
-class DeviceTriangulator:
-    """What `iter_device_windows` is handed for optim_params["hip_delaunay"] = "device": the windows are triangulated on the device
-    (same_window_delaunay) right before their filter + finish call, and a window the device refuses is handed to a Qhull helper (the
-    pool is started on the first refusal).  `stats`: windows submitted to the device, refused by it, and re-finished with scipy's
-    simplices after an answer (order ties, a cosine at the angle threshold) -- each window counted once, whichever threads walk them."""
-
-    on_device = True
-    threads = 0          # no triangulator threads: nothing is triangulated ahead of the finish call
-
-    def __init__(self, guard=GUARD):
-        self.guard = float(guard)
-        self._lock = threading.Lock()
-        self.stats = {"submitted": 0, "refused": 0, "refinished": 0}
-
-    def ticket(self, points, answered):
-        """the window's ticket after same_window_delaunay: answered -> its candidates are on the device (`.result()` is None, `.native`
-        is true, `.qhull()` asks a helper for scipy's simplices and counts the window as re-finished); refused -> a helper has it now"""
-        return _DeviceTicket(self, points, answered)
-
-    def note(self, submitted=0, refused=0, refinished=0):
-        with self._lock:
-            self.stats["submitted"] += submitted
-            self.stats["refused"] += refused
-            self.stats["refinished"] += refinished
-
-    def reset(self):
-        with self._lock:
-            self.stats = {"submitted": 0, "refused": 0, "refinished": 0}
-
-
-class _DeviceTicket:
-    def __init__(self, owner, points, answered):
-        from . import qhull_pool
-
-        self.owner, self.points, self.native, self._qhull = owner, points, bool(answered), None
-        self._asked = None if answered else qhull_pool.pool().submit(points)
-
-    def result(self):
-        if self.native:
-            return None
-        if self._qhull is None:
-            self._qhull = self._asked.result()
-        return self._qhull
-
-    def qhull(self):
-        if self._qhull is None:
-            from . import qhull_pool
-
-            self._qhull = qhull_pool.pool().submit(self.points).result()
-            self.owner.note(refinished=1)
-        self.native = False
-        return self._qhull
-
-
-_last_device = None
-
-
-def last_device_stats():
-    """The counts of the last pass `sliding_window_incumbent` made with hip_delaunay = "device" in this process (None before one)."""
-    return None if _last_device is None else dict(_last_device.stats)
-
-
 def native_simplices(points, guard=GUARD, with_margin=False):
     """(Tr, 3) int32 counter-clockwise triangles of the Delaunay triangulation of `points` ((n, 2) float64), or None when the library
     would not answer for Qhull (SAME_EUNSURE).  Raises when libsame_hip is missing: there is no second implementation."""
@@ -152,48 +97,70 @@ def native_simplices(points, guard=GUARD, with_margin=False):
     return (tris, margin.value) if with_margin else tris
 
 
-class _Ticket:
-    """`.result()` = the simplices; `.native` (after result) = they are this library's, not Qhull's; `.qhull()` = scipy's."""
+class Ticket:
+    """One window's triangulation, whichever route makes it: a known answer, a pending one (a Qhull helper's ticket, or a native thread's
+    future) or the candidates same_window_delaunay left on the device.  `.result()` = the simplices (None: the candidates on the device);
+    `.native` (after `.result()`) = they are not Qhull's own, and `.qhull()` = scipy's, asked for now.  What the owner counts, it is told:
+    `owner._answered` once when a pending answer arrives, `owner._refinished` when scipy's simplices replace a native answer."""
 
-    def __init__(self, owner, points, future):
-        self.owner, self.points, self.future, self.native, self._qhull = owner, points, future, False, None
+    def __init__(self, owner, points, pending=None, simplices=None, native=False, key=None):
+        self.owner, self.points, self.key = owner, points, key
+        self._pending, self._simplices, self.native = pending, simplices, native
 
     def result(self):
-        tris, asked = self.future.result()
-        if tris is None:                        # left to Qhull by the library: a helper has been at it since
-            if self._qhull is None:
-                self._qhull = asked.result()
-                self.owner._note(True)
-            return self._qhull
-        self.native = True
-        self.owner._note(False)
-        return tris
+        if self._pending is not None:
+            self._simplices, self.native = self.owner._answered(self, self._pending.result())
+            self._pending = None
+        return self._simplices
 
     def qhull(self):
         """scipy's simplices for a window whose numbers hang on Qhull's order (asked for now: nobody could know before)"""
-        if self._qhull is None:
-            from . import qhull_pool
-
-            self._qhull = qhull_pool.pool().submit(self.points).result()
-            self.owner._note(True)
-        self.native = False
-        return self._qhull
+        if self.native:
+            self._simplices, self.native = qhull_pool.pool().submit(self.points).result(), False
+            self.owner._refinished()
+        return self.result()
 
 
-class _QhullTicket:
-    """a ticket of the Qhull helper pool behind the same face (`native` stays false)"""
-    native = False
+class Triangulator:
+    """What windows.iter_device_windows asks of a triangulation route -- every route is one of these:
+      lookahead()       how many windows to stage ahead of the batch being finished
+      warm              whether to start the Qhull helpers before the first window (only where they are what answers: a route that asks
+                        them only for the windows it refuses starts them on the first refusal)
+      submit(points, key=None) -> Ticket        at stage time; `key` is the window's id
+      before_finish(states, tickets, radius, angle_enabled, cos_thr)   once per batch, right before its filter + finish call
+    and, for its tickets: `_answered(ticket, what the pending answer brought) -> (simplices, native)`, `_refinished()`."""
 
-    def __init__(self, ticket):
-        self.ticket = ticket
+    warm = False
 
-    def result(self):
-        return self.ticket.result()
+    def lookahead(self):
+        return 0
 
-    qhull = result
+    def before_finish(self, states, tickets, radius, angle_enabled, cos_thr):
+        pass
+
+    def _answered(self, ticket, simplices):
+        return simplices, False
+
+    def _refinished(self):
+        pass
 
 
-class NativeTriangulator:
+class QhullTriangulator(Triangulator):
+    """The default route: scipy's simplices from the Qhull helper pool (qhull_pool), one window ahead per helper."""
+
+    warm = True
+
+    def lookahead(self):
+        return qhull_pool.lookahead()
+
+    def submit(self, points, key=None):
+        return Ticket(self, points, pending=qhull_pool.pool().submit(points))
+
+
+QHULL = QhullTriangulator()           # (it holds nothing: the pool is the process's)
+
+
+class NativeTriangulator(Triangulator):
     """`submit(points, key=None) -> ticket` like the Qhull helper pool's, answered by same_delaunay2d on a thread of this process
     (ctypes drops the GIL for the call).  `threads`: default one and a half per CPU of this process's share ($SAME_DELAUNAY_THREADS).
     A set the library leaves to Qhull goes to a Qhull helper from the triangulator's thread, windows ahead of its use.  Where most
@@ -204,8 +171,6 @@ class NativeTriangulator:
 
     def __init__(self, threads=None, guard=GUARD):
         from collections import deque
-
-        from . import qhull_pool
 
         if threads is None:
             # one and a half threads per CPU of this process's share (as the Qhull helpers have it): the worker threads and the runtime's
@@ -220,6 +185,9 @@ class NativeTriangulator:
         self._recent, self._bypass, self._lock = deque(maxlen=self.WINDOW), 0, threading.Lock()
         _lib.load()
 
+    def lookahead(self):
+        return self.threads          # its own threads triangulate the windows ahead; the helpers only answer what it refuses
+
     def _note(self, sent_back):
         with self._lock:
             self.asked_qhull += bool(sent_back)
@@ -232,9 +200,19 @@ class NativeTriangulator:
         tris = native_simplices(pts, self.guard)
         if tris is not None:
             return tris, None
-        from . import qhull_pool
-
         return None, qhull_pool.pool().submit(pts)
+
+    def _answered(self, ticket, answer):
+        tris, asked = answer
+        if tris is None:                        # left to Qhull by the library: a helper has been at it since
+            tris = asked.result()
+            self._note(True)
+            return tris, False
+        self._note(False)
+        return tris, True
+
+    def _refinished(self):
+        self._note(True)
 
     def submit(self, points, key=None):
         pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 2)
@@ -245,10 +223,8 @@ class NativeTriangulator:
                 self._bypass -= 1
                 self.bypassed += 1
         if bypass:
-            from . import qhull_pool
-
-            return _QhullTicket(qhull_pool.pool().submit(pts))
-        return _Ticket(self, pts, self.pool.submit(self._work, pts))
+            return QHULL.submit(pts)
+        return Ticket(self, pts, pending=self.pool.submit(self._work, pts))
 
     def reset(self):
         """forget what the recent windows did (a new job may be nothing like the last)"""
@@ -270,3 +246,62 @@ def shared():
         if _shared is None:
             _shared = NativeTriangulator()
         return _shared
+
+
+class DeviceTriangulator(Triangulator):
+    """The route of optim_params["hip_delaunay"] = "device": the windows are triangulated on the device (same_window_delaunay) right
+    before their filter + finish call, and a window the device refuses is handed to a Qhull helper (the pool is started on the first
+    refusal).  `stats`: windows submitted to the device, refused by it, and re-finished with scipy's simplices after an answer (order
+    ties, a cosine at the angle threshold) -- each window counted once, whichever threads walk them."""
+
+    def __init__(self, guard=GUARD):
+        self.guard = float(guard)
+        self._lock = threading.Lock()
+        self.stats = {"submitted": 0, "refused": 0, "refinished": 0}
+
+    def submit(self, points, key=None):
+        return Ticket(self, points, native=True)        # the device's candidates, unless before_finish finds it refused
+
+    def before_finish(self, states, tickets, radius, angle_enabled, cos_thr):
+        from ._trace import stage
+        from .windows import triangulate_windows
+
+        with stage("triangulate (device)"):
+            status, _n = triangulate_windows(states, radius, angle_enabled, cos_thr, self.guard)
+            for ticket, refused in zip(tickets, status.tolist()):
+                if refused:                                  # a helper has it now
+                    ticket.native, ticket._pending = False, qhull_pool.pool().submit(ticket.points)
+            self.note(submitted=len(tickets), refused=int(np.count_nonzero(status)))
+
+    def _refinished(self):
+        self.note(refinished=1)
+
+    def note(self, submitted=0, refused=0, refinished=0):
+        with self._lock:
+            self.stats["submitted"] += submitted
+            self.stats["refused"] += refused
+            self.stats["refinished"] += refinished
+
+
+_last_device = None
+
+
+def last_device_stats():
+    """The counts of the last pass `sliding_window_incumbent` made with hip_delaunay = "device" in this process (None before one)."""
+    return None if _last_device is None else dict(_last_device.stats)
+
+
+def triangulator_for(optim_params=None):
+    """The route of a pass of `sliding_window_incumbent` for mode(optim_params): "qhull" -> the helper pool (QHULL); "native" -> the
+    process's NativeTriangulator (shared()), its recent history forgotten; "device" -> a fresh DeviceTriangulator, whose counts
+    last_device_stats() reports."""
+    global _last_device
+    m = mode(optim_params)
+    if m == "native":
+        tr = shared()
+        tr.reset()
+        return tr
+    if m == "device":
+        _last_device = DeviceTriangulator()
+        return _last_device
+    return QHULL

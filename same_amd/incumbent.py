@@ -23,8 +23,8 @@ return_stats each window's stats then carry its `objective` and `fallback` (the 
 
 Two routes produce the same table (tests/test_gpu_run_same.py::test_incumbent_table_routes_agree):
   device   both frames resident on the GPU, two library calls per window, the incumbent and the sweeps computed where the pairs are
-           (csrc/window.hip); the host triangulates, receives (match, flags) per window and gathers the table's columns ONCE at the
-           end.  Windows are walked by `workers` threads with a context each.
+           (csrc/window_stage.hip, csrc/window_finish.hip); the host triangulates, receives (match, flags) per window and gathers
+           the table's columns ONCE at the end.  Windows are walked by `workers` threads with a context each.
   general  every window becomes a `PreparedInputs` (either pipeline of same_amd.api) and the incumbent + sweeps run through the
            host-buffer entry points: caller-supplied triangulations (MetaCell inputs), the cell-type-priority filter, inputs the
            sections cannot hold.
@@ -37,8 +37,8 @@ import pandas as pd
 
 from . import ops
 from ._trace import stage
-from .api import _stage_prune, prepare_same_inputs
-from .window_api import _WindowJob, _WindowSubsetter, _prepared_from_device, _staged_from_device, _window_error
+from .api import _Staged, prepare_same_inputs
+from .window_api import _WindowJob, _walk_windows
 
 STAT_KEYS = ("pairs", "triangles", "checked", "flipped", "xy_violations", "area_flips", "matched")
 INCUMBENTS = ("greedy", "assignment")          # optim_params["hip_incumbent"]; "greedy" without the key
@@ -416,12 +416,7 @@ def sliding_window_incumbent(ref, moving, commonCT=None, outprefix=None, moving_
             if triangulator is None:
                 from . import delaunay
 
-                m = delaunay.mode(job.optim_params)                  # optim_params["hip_delaunay"] / $SAME_DELAUNAY (delaunay.py)
-                if m == "native":
-                    triangulator = delaunay.shared()
-                    triangulator.reset()
-                elif m == "device":                                   # this pass's counts: delaunay.last_device_stats()
-                    triangulator = delaunay._last_device = delaunay.DeviceTriangulator()
+                triangulator = delaunay.triangulator_for(job.optim_params)   # optim_params["hip_delaunay"] / $SAME_DELAUNAY
             table = _device_route(job, frames, workers, window_local_indices, triangulator, stats, merge, _merge_channel, batch)
         else:
             table = _general_route(job, frames, window_local_indices, stats, ctx)
@@ -645,39 +640,16 @@ def _seam_step_on_device(frames, ctx, parts, rank):
 
 
 def _general_route(job, frames, with_ref_idx, stats, ctx):
-    commonCT, op, gp = job.commonCT, job.optim_params, job.gurobi_params
-
-    def prepared():
-        if frames is not None:
-            plan = [w for _pos, w in job.todo]
-            for (pos, w), dw in zip(job.todo, frames.windows(plan, triangulate=not job.caller_triangulation, ctx=ctx,
-                                                             fetch_triangles=True)):
-                if dw.error is not None:
-                    raise _window_error(dw, op)
-                if job.caller_triangulation:
-                    st = _staged_from_device(dw, frames, commonCT, op, gp, job.moving_delaunay, job.vertex_col, verbose=False)
-                    yield pos, w, prepare_same_inputs(None, None, commonCT, verbose=False, ctx=ctx, _staged=st)
-                else:
-                    yield pos, w, _prepared_from_device(dw, frames, op, gp, verbose=False, vertex_col=job.vertex_col)
-            return
-        from . import qhull_pool
-
-        ref_rows, moving_rows = _WindowSubsetter(job.ref), _WindowSubsetter(job.moving)
-        depth = qhull_pool.lookahead()               # windows cut, pruned and handed to the Qhull helpers ahead of the one being finished
-        qhull_pool.warm(min(depth, len(job.todo)))
-        ahead = {}
-        for q, (pos, w) in enumerate(job.todo):
-            for nxt in range(q, min(q + 1 + depth, len(job.todo))):
-                if nxt not in ahead:
-                    box = job.todo[nxt][1]["box"]
-                    ahead[nxt] = _stage_prune(ref_rows.subset(*box), moving_rows.subset(*box), commonCT, job.moving_delaunay,
-                                              job.vertex_col, op, gp,
-                                              job.ignore_pre, False, ctx, prefetch=True, fresh_frames=True)
-            yield pos, w, prepare_same_inputs(None, None, commonCT, verbose=False, ctx=ctx, _staged=ahead.pop(q))
-
+    commonCT = job.commonCT
     keep_csv, job.outprefix = job.outprefix, None        # the table is written once, by the caller of this route
     try:
-        for pos, w, prep in prepared():
+        for pos, w, prep in _walk_windows(job.todo, frames, job.ref, job.moving, commonCT, job.optim_params, job.gurobi_params,
+                                          moving_delaunay=job.moving_delaunay, vertex_col=job.vertex_col, ignore_pre=job.ignore_pre,
+                                          verbose=False, ctx=ctx, fetch_triangles=True):
+            if isinstance(prep, Exception):
+                raise prep
+            if isinstance(prep, _Staged):
+                prep = prepare_same_inputs(None, None, commonCT, verbose=False, ctx=ctx, _staged=prep)
             if len(prep.valid_pairs) == 0:               # every node unconstrained under the caller's triangulation: nothing to match
                 continue
             with stage("incumbent + sweeps + table (general route)"):

@@ -20,9 +20,9 @@ from .params import init_gurobi_params, init_optim_params
 # signature here:
 #   "device" (default)  both frames are uploaded ONCE as sections binned on the window grid (windows.DeviceSection); per window the
 #                       rows of the box, the prune, the pair costs, the compaction, the triangle filter, weights and signs come from
-#                       two library calls on the resident sections (csrc/window.hip); the host only triangulates (Qhull helpers,
-#                       windows ahead) and hands `PreparedInputs` -- whose frames are made from the section rows when somebody reads
-#                       them -- to the unchanged run_same body.
+#                       two library calls on the resident sections (csrc/window_stage.hip, csrc/window_finish.hip); the host only
+#                       triangulates (Qhull helpers, windows ahead) and hands `PreparedInputs` -- whose frames are made from the
+#                       section rows when somebody reads them -- to the unchanged run_same body.
 #   "frames"            every window's frames are cut on the host and go through the host-buffer entry points (`_stage_prune`): the
 #                       pipeline of rounds 1-4, kept as the fallback for inputs the sections cannot hold and as the comparison
 #                       the tests and `bench.py --cfg5-pipeline frames` run.
@@ -507,44 +507,63 @@ class _WindowJob:
         return pd.concat(self.all_matches, ignore_index=True) if self.all_matches else pd.DataFrame()
 
 
+def _walk_windows(todo, frames, ref, moving, commonCT, optim_params, gurobi_params, *, verbose, ctx, moving_delaunay=None, vertex_col=None,
+                  ignore_pre=False, fetch_triangles=False):
+    """The one loop that turns windows into run_same's inputs: yields (pos, window, what) for every (pos, window) of `todo`, in order;
+    `what` is a PreparedInputs, a _Staged (the caller's triangulation, or the frames pipeline: run_same's second half still to run) or
+    the window's error (device pipeline; the frames pipeline's is inside its _Staged).  frames: _DeviceFrames -> the device pipeline on
+    `ctx` (None: the frames' own); None -> the frames pipeline, windows n+1..n+k cut, pruned and handed to the Qhull helpers ahead."""
+    caller_triangulation = moving_delaunay is not None and not ignore_pre
+    if frames is not None:
+        windows = frames.windows([w for _pos, w in todo], triangulate=not caller_triangulation, ctx=ctx, fetch_triangles=fetch_triangles)
+        for (pos, w), dw in zip(todo, windows):
+            if dw.error is not None:
+                yield pos, w, _window_error(dw, optim_params)
+            elif caller_triangulation:
+                yield pos, w, _staged_from_device(dw, frames, commonCT, optim_params, gurobi_params, moving_delaunay, vertex_col,
+                                                  verbose=verbose)
+            else:
+                yield pos, w, _prepared_from_device(dw, frames, optim_params, gurobi_params, verbose=verbose, vertex_col=vertex_col)
+        return
+    from . import qhull_pool
+
+    depth = qhull_pool.lookahead()
+    qhull_pool.warm(min(depth, len(todo)))      # helpers start (import scipy) while the first window is being pruned
+    ref_rows, moving_rows = _WindowSubsetter(ref), _WindowSubsetter(moving)
+    ahead = {}
+    for q, (pos, w) in enumerate(todo):
+        for nxt in range(q, min(q + 1 + depth, len(todo))):
+            if nxt not in ahead:
+                box = todo[nxt][1]["box"]
+                ahead[nxt] = _stage_prune(ref_rows.subset(*box), moving_rows.subset(*box), commonCT, moving_delaunay, vertex_col,
+                                          optim_params, gurobi_params, ignore_pre, verbose, ctx, prefetch=True, fresh_frames=True)
+        yield pos, w, ahead.pop(q)
+
+
 def iter_prepared_windows(ref, moving, commonCT, plan, optim_params=None, gurobi_params=None, verbose=False, ctx=None, pipeline=None):
     """Pre-MIP artefacts of every window of `plan` (windows.window_plan), in plan order: yields (window, PreparedInputs).
     Window n+1..n+k are staged ahead and triangulated by the Qhull helpers while the consumer works on window n (the same
     pipelining sliding_window_matching uses); a window whose prune leaves no pairs yields (window, the ValueError).
     pipeline: 'device' (default; both frames resident on the GPU, frames of a PreparedInputs made when read) or 'frames'."""
     op, gp = init_optim_params(**dict(optim_params or {})), init_gurobi_params(**dict(gurobi_params or {}))
+    frames = None
     if window_pipeline(pipeline) == "device" and len(plan) and _DeviceFrames.refusal(ref, moving, commonCT, op) is None:
         frames = _DeviceFrames(ref, moving, commonCT, op, None, ctx=ctx)
-        try:
-            for w, dw in zip(plan, frames.windows(plan, ctx=ctx)):
-                if dw.error is not None:
-                    err = _window_error(dw, op)
-                    # only run_same's own ValueError is a window's answer; anything else ends the walk
-                    if not isinstance(err, ValueError):
-                        raise err
-                    yield w, err
-                else:
-                    yield w, _prepared_from_device(dw, frames, op, gp, verbose=verbose)
-        finally:
+    try:
+        # (the frames pipeline's prune takes the parameters as given and completes them itself: op and gp are the same to it)
+        for _pos, w, what in _walk_windows(list(enumerate(plan)), frames, ref, moving, commonCT, op, gp, verbose=verbose, ctx=ctx):
+            if isinstance(what, _Staged):
+                try:
+                    what = prepare_same_inputs(None, None, commonCT, verbose=verbose, ctx=ctx, _staged=what)
+                except ValueError as e:
+                    what = e
+            # only run_same's own ValueError is a window's answer; anything else ends the walk
+            elif isinstance(what, Exception) and not isinstance(what, ValueError):
+                raise what
+            yield w, what
+    finally:
+        if frames is not None:
             frames.close()
-        return
-    from . import qhull_pool
-
-    depth = qhull_pool.lookahead()
-    qhull_pool.warm(min(depth, len(plan)))
-    ref_rows, moving_rows = _WindowSubsetter(ref), _WindowSubsetter(moving)
-    ahead = {}
-    for q, w in enumerate(plan):
-        for nxt in range(q, min(q + 1 + depth, len(plan))):
-            if nxt not in ahead:
-                box = plan[nxt]["box"]
-                ahead[nxt] = _stage_prune(ref_rows.subset(*box), moving_rows.subset(*box), commonCT, None, None,
-                                          optim_params, gurobi_params, False, verbose, ctx, prefetch=True, fresh_frames=True)
-        st = ahead.pop(q)
-        try:
-            yield w, prepare_same_inputs(None, None, commonCT, verbose=verbose, ctx=ctx, _staged=st)
-        except ValueError as e:
-            yield w, e
 
 
 def sliding_window_matching(ref, moving, commonCT=None, outprefix=None, moving_delaunay=None,
@@ -563,33 +582,42 @@ def sliding_window_matching(ref, moving, commonCT=None, outprefix=None, moving_d
                                                    gurobi_params, ignore_precomputed_triangulation, _shard)
     frames, own = job.device_frames(_pipeline)
     try:
-        if frames is not None:
-            _solver_windows_on_device(job, frames, _run_window, _solve)
+        if _run_window is not None:
+            _run_windows(job, frames, _run_window)
         else:
-            _solver_windows_on_frames(job, _run_window, _solve)
+            _solver_windows(job, frames, _solve)
     finally:
         if own:
             frames.close()
     return job.result()
 
 
-def _solve_window(solve, commonCT, outprefix, job, staged, prepared):
-    """The solver half of one window: run_same's own body, or the caller's stand-in on the finished PreparedInputs."""
-    op, gp = job.optim_params, job.gurobi_params
-    if solve is None:
-        return _run_same(None, None, commonCT, outprefix, job.moving_delaunay, job.vertex_col, op, gp, job.ignore_pre, staged, prepared)
-    if isinstance(prepared, Exception):
-        raise prepared
-    prep = prepared if prepared is not None else prepare_same_inputs(None, None, commonCT, verbose=False, _staged=staged)
-    return solve(prep, outprefix)
-
-
-def _solver_windows_on_device(job, frames, run_window, solve=None):
-    """The window loop with both frames resident on the device: per window two library calls + the triangulation; the frames a window's
-    run_same body reads are made from the device's row lists."""
+def _solver_windows(job, frames, solve=None):
+    """The window loop: per window the pre-MIP half on either pipeline (`_walk_windows`; frames None: the frames pipeline), then the
+    solver half -- run_same's own body, or the caller's stand-in (`_solve`) on the finished PreparedInputs.  A window whose prune finds
+    no pair hands its error to the run_same body, which raises it where the reference does."""
     commonCT, op, gp = job.commonCT, job.optim_params, job.gurobi_params
-    # a stand-in for run_same takes the window's frames: subset_data of both, from the device's row lists
-    if run_window is not None:
+    # the frames pipeline's prune always speaks; the device pipeline's only ahead of run_same's own body
+    verbose = solve is None or frames is None
+    for pos, w, what in _walk_windows(job.todo, frames, job.ref, job.moving, commonCT, op, gp, moving_delaunay=job.moving_delaunay,
+                                      vertex_col=job.vertex_col, ignore_pre=job.ignore_pre, verbose=verbose, ctx=None):
+        staged, prepared = (what, None) if isinstance(what, _Staged) else (None, what)
+        if solve is None:
+            window_matches, _ = _run_same(None, None, commonCT, job.window_outprefix(w), job.moving_delaunay, job.vertex_col, op, gp,
+                                          job.ignore_pre, staged, prepared)
+        elif isinstance(prepared, Exception):
+            raise prepared
+        else:
+            prep = prepared if prepared is not None else prepare_same_inputs(None, None, commonCT, verbose=False, _staged=staged)
+            window_matches, _ = solve(prep, job.window_outprefix(w))
+        job.collect(pos, w, window_matches)
+
+
+def _run_windows(job, frames, run_window):
+    """The window loop with a stand-in for run_same (`_run_window`, testing): it takes the window's frames, subset_data of both -- from
+    the device's row lists when the frames are resident, else cut on the host."""
+    commonCT, op, gp = job.commonCT, job.optim_params, job.gurobi_params
+    if frames is not None:
         from .windows import DeviceWindow
 
         state = DeviceWindow(frames.ctx)
@@ -604,53 +632,10 @@ def _solver_windows_on_device(job, frames, run_window, solve=None):
         finally:
             state.close()
         return
-    plan = [w for _pos, w in job.todo]
-    for (pos, w), dw in zip(job.todo, frames.windows(plan, triangulate=not job.caller_triangulation)):
-        staged = prepared = None
-        if dw.error is not None:
-            prepared = _window_error(dw, op)                         # raised by the run_same body, where the reference raises it
-        elif job.caller_triangulation:
-            staged = _staged_from_device(dw, frames, commonCT, op, gp, job.moving_delaunay, job.vertex_col, verbose=solve is None)
-        else:
-            prepared = _prepared_from_device(dw, frames, op, gp, verbose=solve is None, vertex_col=job.vertex_col)
-        window_matches, _ = _solve_window(solve, commonCT, job.window_outprefix(w), job, staged, prepared)
-        job.collect(pos, w, window_matches)
-
-
-def _solver_windows_on_frames(job, run_window, solve=None):
-    """The window loop on host frames (the pipeline of rounds 1-4): window n+1..n+k are cut, pruned and compacted while window n is
-    still to run, and their triangulations are computed by helper processes meanwhile (qhull_pool); window n then finds its simplices
-    ready.  Outputs are unchanged: the same frames reach the same run_same body in the same order."""
-    commonCT, op, gp, todo = job.commonCT, job.optim_params, job.gurobi_params, job.todo
     ref_rows, moving_rows = _WindowSubsetter(job.ref), _WindowSubsetter(job.moving)
-
-    def subsets(w):
-        return ref_rows.subset(*w["box"]), moving_rows.subset(*w["box"])
-
-    ahead = {}
-    depth = 0
-    if run_window is None:
-        from . import qhull_pool
-        depth = qhull_pool.lookahead()
-        qhull_pool.warm(min(depth, len(todo)))      # helpers start (import scipy) while the first window is being pruned
-
-    def stage_window(q):
-        _pos_q, w_q = todo[q]
-        rs, ms = subsets(w_q)
-        ahead[q] = (rs, ms, _stage_prune(rs, ms, commonCT, job.moving_delaunay, job.vertex_col, op, gp, job.ignore_pre, True, None,
-                                         prefetch=True, fresh_frames=True))
-
-    for q, (pos, w) in enumerate(todo):
-        window_outprefix = job.window_outprefix(w)
-        if run_window is not None:
-            ref_subset, moving_subset = subsets(w)
-            window_matches, _ = run_window(aligned_df=moving_subset, ref_df=ref_subset, commonCT=commonCT, optim_params=op,
-                                           gurobi_params=gp, outprefix=window_outprefix, aligned_delaunay=job.moving_delaunay,
-                                           aligned_delaunay_vertex_col=job.vertex_col, ignore_precomputed_triangulation=job.ignore_pre)
-        else:
-            for nxt in range(q, min(q + 1 + depth, len(todo))):
-                if nxt not in ahead:
-                    stage_window(nxt)
-            _ref_subset, _moving_subset, staged = ahead.pop(q)
-            window_matches, _ = _solve_window(solve, commonCT, window_outprefix, job, staged, None)
+    for pos, w in job.todo:
+        ref_subset, moving_subset = ref_rows.subset(*w["box"]), moving_rows.subset(*w["box"])
+        window_matches, _ = run_window(aligned_df=moving_subset, ref_df=ref_subset, commonCT=commonCT, optim_params=op, gurobi_params=gp,
+                                       outprefix=job.window_outprefix(w), aligned_delaunay=job.moving_delaunay,
+                                       aligned_delaunay_vertex_col=job.vertex_col, ignore_precomputed_triangulation=job.ignore_pre)
         job.collect(pos, w, window_matches)

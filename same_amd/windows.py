@@ -10,6 +10,7 @@ import os
 import numpy as np
 
 from . import ops
+from .delaunay import QHULL, QhullTriangulator, Ticket
 
 
 def window_grid(ref_xy, mov_xy, window_size, overlap):
@@ -335,7 +336,7 @@ def iter_window_arrays(ref, moving, plan, radius=250, knn=8, dist_ct_coeff=1.0, 
         yield out if out.error is not None else finish(out, staged)
 
 
-# ---- the window path with the sections resident on the device (csrc/window.hip) -------------------------------------------
+# ---- the window path with the sections resident on the device (csrc/window_stage.hip, csrc/window_finish.hip) -------------
 
 _W_ALIGNED_XY, _W_ALIGNED_ROWS, _W_ROWS_M, _W_ROWS_R, _W_PAIRS, _W_COSTS, _W_KEPT, _W_SIGNS, _W_WEIGHTS, _W_MATCH, _W_TRIANGLES = range(11)
 
@@ -852,25 +853,10 @@ class DeviceWindowResult:
             setattr(self, name, None)
 
 
-class TriangulationCache:
+class TriangulationCache(QhullTriangulator):
     """Delaunay simplices remembered per window (a DIAGNOSTIC: bench.py's "what would a pass cost if the triangulations were free").
     `submit(points, key)` hands back the simplices of `key` when it has seen the window before, else asks the helper pool and keeps
     the answer; the simplices are the pool's, i.e. scipy's, either way."""
-
-    class _Ready:
-        def __init__(self, value):
-            self._value = value
-
-        def result(self):
-            return self._value
-
-    class _Pending:
-        def __init__(self, cache, key, ticket):
-            self.cache, self.key, self.ticket = cache, key, ticket
-
-        def result(self):
-            v = self.cache.known[self.key] = self.ticket.result()
-            return v
 
     def __init__(self):
         self.known = {}
@@ -885,12 +871,15 @@ class TriangulationCache:
     def submit(self, points, key=None):
         from . import qhull_pool
 
-        if key is None:                                   # a window without an id cannot be remembered
-            return qhull_pool.pool().submit(points)
-        tag = self._tag(points, key)
+        tag = None if key is None else self._tag(points, key)       # a window without an id cannot be remembered
         if tag in self.known:
-            return self._Ready(self.known[tag])
-        return self._Pending(self, tag, qhull_pool.pool().submit(points))
+            return Ticket(self, points, simplices=self.known[tag])
+        return Ticket(self, points, pending=qhull_pool.pool().submit(points), key=tag)
+
+    def _answered(self, ticket, simplices):
+        if ticket.key is not None:
+            self.known[ticket.key] = simplices
+        return simplices, False
 
 
 def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dist_ct_coeff=1.0, min_angle_deg=15,
@@ -905,7 +894,9 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
     Windows go to the library in BATCHES of `batch` (default $SAME_WINDOW_BATCH, else 8): one stage call, and later one filter + finish
     call, for up to that many windows -- one wait per call instead of one per window, and the device works on one window while the host
     enqueues the next.  The states of a batch stay live (`result.state`) until the generator is asked for the first window of the next.
-    `triangulator` (default: the Qhull helper pool) is anything with `submit(points, key=...) -> ticket with .result()`; a ticket
+    `triangulator`: the route, a delaunay.Triangulator (default: delaunay.QHULL, the Qhull helper pool).  It says how many windows to
+    stage ahead and whether to start the helpers first; each window is submitted when it is staged, and the route's per-batch hook runs
+    right before the batch's filter + finish call.  A ticket's `.result()` is the simplices, or None for candidates the device made; one
     whose `.native` is true after `.result()` brought simplices that are not scipy's own and has `.qhull()` for those (delaunay.py).
     `triangulate=False` stops after the stage call (rows, prune, costs, compaction): the caller brings its own triangles
     (api.sliding_window_matching with a caller's triangulation) and reads pairs / costs through `state.fetch`.
@@ -924,10 +915,9 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
     ctx = ops._ctx(ctx)
     angle_enabled, cos_thr = cos_threshold(min_angle_deg)
     near_tol = float(8 * np.spacing(abs(cos_thr))) if (angle_enabled and np.isfinite(cos_thr)) else 0.0
-    on_device = getattr(triangulator, "on_device", False)      # delaunay.DeviceTriangulator: the device triangulates at finish time
-    own_threads = getattr(triangulator, "threads", None)        # a triangulator with threads of its own (delaunay.NativeTriangulator)
-    depth = qhull_pool.lookahead() if own_threads is None else int(own_threads)
-    if own_threads is None:
+    tri = QHULL if triangulator is None else triangulator
+    depth = int(tri.lookahead())
+    if tri.warm:
         qhull_pool.warm(min(depth, len(plan)))
     B = max(1, min(int(batch if batch is not None else os.environ.get("SAME_WINDOW_BATCH", "8")), WINDOW_BATCH_MAX, max(len(plan), 1)))
     if batch is None and depth > 0:
@@ -973,10 +963,9 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
             ticket = None
             try:
                 out.rows_m, out.axy = state.fetch(_W_ALIGNED_ROWS), state.fetch(_W_ALIGNED_XY)
-                if triangulate and not on_device:
+                if triangulate:
                     with marked("triangulate (hand-over; waits for a free helper)"):
-                        ticket = (qhull_pool.pool().submit(out.axy) if triangulator is None
-                                  else triangulator.submit(out.axy, key=out.window.get("window_id")))
+                        ticket = tri.submit(out.axy, key=out.window.get("window_id"))
             except BaseException:
                 free.extend(st for st in states[q:])
                 free.extend(st for _o, st, _t in staged if st is not None)
@@ -992,40 +981,33 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
             out.state, out.n_triangles = state, 0
         if not triangulate or not todo:
             return
-        for _o, state, _t in todo:
+        states, tickets = [st for _o, st, _t in todo], [t for _o, _s, t in todo]
+        for state in states:
             state.set_incumbent(incumbent)
-        if on_device:
-            with marked("triangulate (device)"):
-                status, _n = triangulate_windows([st for _o, st, _t in todo], radius, angle_enabled, cos_thr, triangulator.guard)
-                todo = [(out, state, triangulator.ticket(out.axy, status[q] == 0)) for q, (out, state, _t) in enumerate(todo)]
-                triangulator.note(submitted=len(todo), refused=int(np.count_nonzero(status)))
+        tri.before_finish(states, tickets, radius, angle_enabled, cos_thr)
         with marked("triangulate (wait for helper)"):
-            tris = [ticket.result() for _o, _s, ticket in todo]
+            tris = [ticket.result() for ticket in tickets]
+        args = (radius, angle_enabled, cos_thr, near_tol, ignore_same_type_triangles, no_match_penalty)
         with marked("filter + signs + incumbent + sweeps (device)"):
-            res = [None] * len(todo)
             # candidates the device made stay there (same_window_filter_finish_device); every other window brings its simplices
             mine = [q for q, t in enumerate(tris) if t is None]
             theirs = [q for q, t in enumerate(tris) if t is not None]
-            for qs, r in ((mine, filter_finish_device_windows([todo[q][1] for q in mine], radius, angle_enabled, cos_thr, near_tol,
-                                                              ignore_same_type_triangles, no_match_penalty) if mine else []),
-                          (theirs, filter_finish_windows([todo[q][1] for q in theirs], [tris[q] for q in theirs], radius, angle_enabled,
-                                                         cos_thr, near_tol, ignore_same_type_triangles, no_match_penalty) if theirs else [])):
-                for q, rq in zip(qs, r):
-                    res[q] = rq
+            res = dict(zip(mine, filter_finish_device_windows([states[q] for q in mine], *args) if mine else []))
+            res.update(zip(theirs, filter_finish_windows([states[q] for q in theirs], [tris[q] for q in theirs], *args) if theirs else []))
         # simplices that are not Qhull's own (delaunay.py: the same triangles in another order): where the window's numbers hang on that
         # order -- the device counted such places, or a cosine sits at the threshold and the host is about to re-decide the filter --
         # the window is finished again with scipy's
-        for q, ((_o, state, ticket), r) in enumerate(zip(todo, res)):
-            if getattr(ticket, "native", False) and (state.order_ties or r[2]):
+        for q, (state, ticket) in enumerate(zip(states, tickets)):
+            if ticket.native and (state.order_ties or res[q][2]):
                 with marked("order ties: the window again with Qhull's simplices"):
                     tris[q] = ticket.qhull()
-                    res[q] = filter_finish_windows([state], [tris[q]], radius, angle_enabled, cos_thr, near_tol,
-                                                   ignore_same_type_triangles, no_match_penalty)[0]
-        for (out, state, _t), simplices, (_kept, _added, near, match_row, cell_flags, stats) in zip(todo, tris, res):
+                    res[q] = filter_finish_windows([state], [tris[q]], *args)[0]
+        for q, (out, state, _t) in enumerate(todo):
+            _kept, _added, near, match_row, cell_flags, stats = res[q]
             if near:
                 with marked("triangle filter (host: a cosine at the threshold)"):
                     tid = moving.type_id[out.rows_m] if (ignore_same_type_triangles and moving.type_id is not None) else None
-                    out.triangles = filter_triangles_by_radius(out.axy, simplices, radius,
+                    out.triangles = filter_triangles_by_radius(out.axy, tris[q], radius,
                                                                ignore_same_type_triangles=ignore_same_type_triangles,
                                                                min_angle_deg=min_angle_deg, verbose=False, ctx=ctx, _rows_as_array=True,
                                                                _type_id=tid)
@@ -1042,7 +1024,7 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
                 out.triangles = state.fetch(_W_TRIANGLES)
         if collector is not None:
             with marked("central rows to the merge accumulator (device, enqueue only)"):
-                collector([st for _o, st, _t in todo], [o.window for o, _s, _t in todo])
+                collector(states, [o.window for o, _s, _t in todo])
 
     pending, live, nxt = deque(), [], 0
     try:

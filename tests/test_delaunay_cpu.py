@@ -137,6 +137,32 @@ def test_triangulator_steps_aside_where_most_windows_go_back(monkeypatch):
         tr.close()
 
 
+def test_device_route_counts_each_window_once(monkeypatch):
+    """The device route's tickets without a device: same_window_delaunay's verdicts are stood in for (windows.triangulate_windows).  An
+    answered window's ticket gives None -- its candidates are on the device -- until scipy's simplices replace them; a refused one gives
+    scipy's.  The pass's counts (last_device_stats) take every window once: submitted, refused, re-finished."""
+    from same_amd import qhull_pool, windows
+
+    monkeypatch.setenv("SAME_QHULL_WORKERS", "0")      # a refused window asks scipy in this process
+    monkeypatch.setattr(qhull_pool, "_pool", None)
+    monkeypatch.setattr(delaunay, "_last_device", None)
+    monkeypatch.setattr(windows, "triangulate_windows", lambda states, *args: (np.array([0, 3, 0], np.int32), np.zeros(3, np.int64)))
+    tr = delaunay.triangulator_for({"hip_delaunay": "device"})
+    rng = np.random.default_rng(4)
+    sets = [rng.uniform(0, 100, (n, 2)) for n in (50, 80, 120)]
+    tickets = [tr.submit(p, key=q) for q, p in enumerate(sets)]
+    assert tr.lookahead() == 0 and not tr.warm and qhull_pool._pool is None      # nothing is asked of the helpers at stage time
+    tr.before_finish([None] * 3, tickets, 25.0, True, 0.9)
+    assert delaunay.last_device_stats() == {"submitted": 3, "refused": 1, "refinished": 0}
+    got = [t.result() for t in tickets]
+    assert got[0] is None and got[2] is None and tickets[0].native and tickets[2].native
+    assert np.array_equal(got[1], Delaunay(sets[1]).simplices) and not tickets[1].native
+    assert np.array_equal(tickets[1].qhull(), Delaunay(sets[1]).simplices)          # scipy's already: not a re-finish
+    for _ in range(2):
+        assert np.array_equal(tickets[0].qhull(), Delaunay(sets[0]).simplices) and not tickets[0].native
+    assert delaunay.last_device_stats() == {"submitted": 3, "refused": 1, "refinished": 1}
+
+
 def test_triangulator_under_the_sanitizers(tmp_path):
     """csrc/delaunay.cpp built with -fsanitize=address,undefined and driven from C++ (tests/native/delaunay_test.cpp): random and
     degenerate sets, bad arguments, eight threads at once; every answer checked for the local Delaunay property."""

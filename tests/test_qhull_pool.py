@@ -281,7 +281,7 @@ def test_threads_share_the_pool_without_waiting_on_each_other():
     pool.close()
 
 
-def test_triangulation_cache_remembers_windows_by_id(monkeypatch):
+def test_triangulation_cache_answers_remembered_windows_without_a_helper(monkeypatch):
     """windows.TriangulationCache (bench.py's diagnostic pass): the first request of a window goes to the helper pool and its answer is
     kept under (id, number of points, checksum of their coordinates); the second is answered from memory; other points under the same id
     ask the pool again; a window without an id is never remembered.  The simplices are scipy's either way."""
@@ -296,12 +296,14 @@ def test_triangulation_cache_remembers_windows_by_id(monkeypatch):
         cache = TriangulationCache()
         first = cache.submit(a, key=7)
         assert not cache.known and np.array_equal(first.result(), Delaunay(a).simplices) and len(cache.known) == 1
+        asked = qhull_pool.pool().seq
         again = cache.submit(a.copy(), key=7)           # the same window again: answered from memory, no helper asked
-        assert isinstance(again, TriangulationCache._Ready) and np.array_equal(again.result(), Delaunay(a).simplices)
+        assert qhull_pool.pool().seq == asked and np.array_equal(again.result(), Delaunay(a).simplices)
         # the id alone does not decide: a cache reused with another plan / section whose windows reuse ids must not answer with stale simplices
         other = cache.submit(b, key=7)
-        assert not isinstance(other, TriangulationCache._Ready) and np.array_equal(other.result(), Delaunay(b).simplices) and len(cache.known) == 2
+        assert qhull_pool.pool().seq == asked + 1 and np.array_equal(other.result(), Delaunay(b).simplices) and len(cache.known) == 2
         assert np.array_equal(cache.submit(b, key=None).result(), Delaunay(b).simplices) and len(cache.known) == 2
+        assert qhull_pool.pool().seq == asked + 2                # a window without an id asks a helper every time
     finally:
         if qhull_pool._pool is not None:
             qhull_pool._pool.close()

@@ -500,6 +500,29 @@ int same_window_incumbent_result(same_window *window, int64_t *out_rounds, int64
 int same_window_refinish(same_window *window, const int32_t *match_pair, int32_t *out_match_row, uint8_t *out_point_flag,
                          int64_t *out_stats);
 
+/* ---- the local search on the lazy model's objective (csrc/refine.hip): from a window's one-to-one incumbent, moves that lower
+ *   sum_p c_p x_p + no_match_penalty sum_i size_i n_i + delaunay_penalty sum_t w_t q_t        (src/same.py:1191-1196; p_j = 0)
+ * over the window's kept aligned cells, their pairs and the kept triangles; w_t = the corners' size sum (:1128-1134), q_t = 1 when the
+ * lazy body (:645-669) sees t flip.  Moves: a matched cell to a free candidate reference, an unmatched cell to a free candidate, a cell to
+ * unmatched, two matched cells swapping references (both crossed pairs candidates).  Rounds: every cell proposes its best improving
+ * move (delta < -2^-40 scale); moves whose footprints (closed 1-rings of the moved cells + the references taken) do not meet apply
+ * together, by a minimum key; a round without a move settles the search.  The result depends on the triangle SET only, not on its order.
+ *   same_window_set_refine: what the finish calls (and same_window_refinish) do after the incumbent from the next call on: rounds_cap
+ *     rounds at most (0 = no search, the default), delaunay_penalty finite and >= 0.  The sweeps, matched rows and flags then describe
+ *     the search's result; the incumbent's own statistics (same_window_incumbent_result) keep describing the incumbent.
+ *   same_window_refine_result: after a finish call with the search on: productive rounds, moves applied, settled (1: a round found no
+ *     improving move; 0: stopped at the cap), the objective of the incumbent and of the result (0 when the search is off).
+ *   same_refine_matching: host buffers.  pairs[P][2] = (cell < n_m, reference < n_r), each once; unmatched[n_m] the no-match costs;
+ *     tris[Tr][3] the kept triangles; axy[n_m][2], ref_xy[n_r][2], size[n_m]; match_pair_inout[n_m] = pair index per cell (-1 = none),
+ *     one-to-one, replaced by the result.  out_stats[5] = {rounds, moves, settled, objective at the start, objective (both as the bits
+ *     of a double)}.  One wait unless the search still moves after its first chunk of rounds. */
+int same_window_set_refine(same_window *window, int64_t rounds_cap, double delaunay_penalty);
+int same_window_refine_result(same_window *window, int64_t *out_rounds, int64_t *out_moves, int64_t *out_settled, double *out_objective_start,
+                              double *out_objective);
+int same_refine_matching(same_ctx *ctx, const int32_t *pairs, const double *costs, int64_t P, const double *unmatched, int64_t n_m,
+                         int64_t n_r, const int32_t *tris, int64_t Tr, const double *axy, const double *ref_xy, const double *size,
+                         double delaunay_penalty, int64_t rounds_cap, int32_t *match_pair_inout, int64_t *out_stats);
+
 /* ---- f3 on the window path: the window merge where the windows' matches are ------------------------------------------------
  * The reference trims every window's match table to the window's central region (src/same.py:565-582), concatenates the tables and
  * merges them (helpers.merge_window_matches_unique_ref, src/helpers.py:692-815: one row per (aligned, ref) pair -- not violating

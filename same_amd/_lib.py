@@ -110,6 +110,9 @@ _PROTOTYPES = {
     "same_window_set_incumbent": [c_vp, c_int],
     "same_window_incumbent_result": [c_vp, c_vp, c_vp, c_vp],
     "same_window_refinish": [c_vp, c_vp, c_vp, c_vp, c_vp],
+    "same_window_set_refine": [c_vp, c_i64, c_dbl],
+    "same_window_refine_result": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "same_refine_matching": [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_dbl, c_i64, c_vp, c_vp],
     "same_window_filter_finish_device": [c_vp, c_int, c_dbl, c_int, c_dbl, c_dbl, c_int, c_int, c_dbl, c_vp, c_vp, c_vp, c_vp],
     "same_delaunay_filtered": [c_vp, c_vp, c_i64, c_dbl, c_int, c_dbl, c_dbl, c_vp, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(c_int)],
     "same_section_set_codes": [c_vp, c_vp, c_i64],

@@ -1,0 +1,545 @@
+// refine.hip -- a local search that lowers a window's full lazy-model objective (src/same.py:1191-1196) from its incumbent:
+//
+//   sum_p c_p x_p  +  penalty_coeff sum_j p_j  +  no_match_penalty sum_i size_i n_i  +  delaunay_penalty sum_t w_t q_t
+//
+// over the window's kept aligned cells, their pairs and the kept triangles.  w_t is the size sum of the triangle's corners (:1128-1134);
+// q_t = 1 when the lazy body (:645-669) sees t flip: all three corners matched, neither the source nor the reference sign zero, the
+// signs different.  The matching stays one-to-one like both starts, so p_j = 0 (a feasible point of the model for any max_matches).
+//
+// Moves of one cell i, each evaluated exactly against the current state: to a free candidate reference, from unmatched to a free
+// candidate, to unmatched, and the swap of the references of two matched cells i < k when both crossed pairs are candidates (the swap
+// belongs to the lower cell).  A move's delta only involves the triangles incident to the cells it moves:
+//   delta = delaunay_penalty * F + (new cost terms - old cost terms),  F = sum over those triangles of +-w_t where q_t changes
+// (F first, in the canonical incidence order, exact for integer sizes; one product; then the cost terms).  It improves when
+// delta < -2^-40 * scale, scale = delaunay_penalty * (sum of the w_t looked at) + |new terms| + |old terms|: rounding never counts as
+// an improvement, so the search cannot cycle.
+//
+// A ROUND: every cell proposes its best improving move (ties: the first in pair order, unmatching before every pair).  Its key is
+// (the delta rounded to float, ordered | cell), and it is written by atomicMin to every slot of its FOOTPRINT: the closed 1-ring of every
+// cell it moves in the kept-triangle graph, and the references it takes.  A move whose key is the minimum on all of them WINS.  Winners
+// share no triangle and no reference, so their deltas add up exactly and the objective never goes up; the smallest key always wins, so a
+// round without a winner is a round without an improving move (SETTLED).  The result depends on the input alone -- not on scheduling or
+// block shape -- and only on the SET of triangles: each cell's incident triangles are listed by their sorted corner rows and every sign
+// and weight is taken over sorted corners.
+//
+// Kernels over Batch<RefineArgs> (blockIdx.y = window): setup (init, triangles, incidence scan / fill / sort, objective), then per round
+// q_t of every triangle, propose, apply; apply's last block closes the round (rounds, moves, settled).  Rounds of a settled window, or one at its cap, return
+// at once, so rounds can be enqueued ahead of any look at the device.
+#include "refine.h"
+
+namespace {
+
+using namespace devmath;
+using namespace win;
+using rfn::Prop;
+using rfn::RefineArgs;
+
+constexpr unsigned long long NONE = ~0ull;
+
+__device__ __forceinline__ int32_t col_of(const RefineArgs &w, int32_t p) { return w.pairs[2 * (int64_t)p + 1]; }
+__device__ __forceinline__ double2_t ref_of(const RefineArgs &w, int32_t p) { return ld2(w.ref_xy, w.ref_row ? w.ref_row[p] : col_of(w, p)); }
+__device__ __forceinline__ double unm_of(const RefineArgs &w, int64_t i) { return w.unm ? w.unm[i] : w.penalty * w.size[i]; }
+__device__ __forceinline__ unsigned long long ld_ctrl(const RefineArgs &w, int q) {
+    return __hip_atomic_load(w.ctrl + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ bool active(const RefineArgs &w) {
+    return w.cap > 0 && !ld_ctrl(w, rfn::RC_SETTLED) && (int64_t)ld_ctrl(w, rfn::RC_ROUNDS) < w.cap;
+}
+__device__ __forceinline__ int64_t n_tris(const RefineArgs &w) { return w.dTr ? (int64_t)*w.dTr : w.cap_tr; }
+
+// q_t under the current matching with cell ci on pair pi and cell ck on pair pk (ci, ck = -1: unchanged)
+__device__ __forceinline__ bool flips(const RefineArgs &w, int32_t t, int32_t ci, int32_t pi, int32_t ck, int32_t pk) {
+    const int8_t s = w.tsign[t];
+    if (s == 0) return false;
+    double2_t r[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const int32_t v = w.tsort[3 * (int64_t)t + q];
+        const int32_t p = v == ci ? pi : (v == ck ? pk : w.match[v]);
+        if (p < 0) return false;
+        r[q] = ref_of(w, p);
+    }
+    const int8_t rs = orient_sign(r[0], r[1], r[2]);
+    return rs != 0 && rs != s;
+}
+__device__ __forceinline__ bool has_corner(const RefineArgs &w, int32_t t, int32_t v) {
+    const int32_t *c = w.tsort + 3 * (int64_t)t;
+    return c[0] == v || c[1] == v || c[2] == v;
+}
+// the flip part over the triangles of cell c (skipping those with corner `skip`), with ci -> pi and ck -> pk
+__device__ __forceinline__ void flip_part(const RefineArgs &w, int32_t c, int32_t skip, int32_t ci, int32_t pi, int32_t ck, int32_t pk,
+                                          double &F, double &W) {
+    for (int32_t q = w.off[c]; q < w.off[c + 1]; ++q) {
+        const int32_t t = w.inc[q];
+        if (skip >= 0 && has_corner(w, t, skip)) continue;
+        const double wt = w.tw[t];
+        W += wt;
+        const bool o = w.q[t] != 0, nw = flips(w, t, ci, pi, ck, pk);
+        if (o != nw) F += nw ? wt : -wt;
+    }
+}
+struct Delta {
+    double d, scale;
+};
+// cell i from its pair to pair pn (-1 = unmatched)
+__device__ __forceinline__ Delta delta_single(const RefineArgs &w, int32_t i, int32_t pn) {
+    double F = 0.0, W = 0.0;
+    flip_part(w, i, -1, i, pn, -1, 0, F, W);
+    const int32_t po = w.match[i];
+    const double nw = pn >= 0 ? w.cost[pn] : unm_of(w, i), old = po >= 0 ? w.cost[po] : unm_of(w, i);
+    return Delta{w.dp * F + (nw - old), w.dp * W + (fabs(nw) + fabs(old))};
+}
+// cells i < k exchange their references: i to pair pi, k to pair pk
+__device__ __forceinline__ Delta delta_swap(const RefineArgs &w, int32_t i, int32_t pi, int32_t k, int32_t pk) {
+    double F = 0.0, W = 0.0;
+    flip_part(w, i, -1, i, pi, k, pk, F, W);
+    flip_part(w, k, i, i, pi, k, pk, F, W);
+    const double nw = w.cost[pi] + w.cost[pk], old = w.cost[w.match[i]] + w.cost[w.match[k]];
+    return Delta{w.dp * F + (nw - old), w.dp * W + (fabs(nw) + fabs(old))};
+}
+__device__ __forceinline__ bool improves(Delta x) { return x.d < -rfn::EPS * x.scale; }
+// (delta rounded to float, as an ordered 32-bit word | cell): round-to-nearest is monotone, the cell makes every key distinct
+__device__ __forceinline__ unsigned long long key_of(double d, int32_t i) {
+    const unsigned u = __float_as_uint((float)d);
+    const unsigned o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((unsigned long long)o << 32) | (unsigned)i;
+}
+
+// every slot of a proposal's footprint: f(slot index) for cells (closed 1-rings of the moved cells) and references (n + column)
+template <class Fn>
+__device__ __forceinline__ bool each_slot(const RefineArgs &w, int32_t i, const Prop &pr, Fn f) {
+    bool all = f((int64_t)i);
+    for (int32_t q = w.off[i]; q < w.off[i + 1]; ++q) {
+        const int32_t *c = w.tsort + 3 * (int64_t)w.inc[q];
+        all &= f(c[0]);
+        all &= f(c[1]);
+        all &= f(c[2]);
+    }
+    if (pr.k >= 0) {
+        all &= f((int64_t)pr.k);
+        for (int32_t q = w.off[pr.k]; q < w.off[pr.k + 1]; ++q) {
+            const int32_t *c = w.tsort + 3 * (int64_t)w.inc[q];
+            all &= f(c[0]);
+            all &= f(c[1]);
+            all &= f(c[2]);
+        }
+        all &= f(w.n + col_of(w, pr.p_k));
+    }
+    if (pr.p_i >= 0) all &= f(w.n + col_of(w, pr.p_i));
+    return all;
+}
+
+// ---- setup ---------------------------------------------------------------------------------------------------------------------
+// the matching from the start, counters and claim slots cleared, no reference held
+__global__ __launch_bounds__(256) void refine_init_kernel(Batch<RefineArgs> b) {
+    const RefineArgs &w = b.w[blockIdx.y];
+    const int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (x < w.n) {
+        w.match[x] = w.start[x];
+        w.deg[x] = 0;
+        w.cur[x] = 0;
+    }
+    if (x < w.n_r) w.owner[x] = -1;
+    if (x < w.n + w.n_r) w.slot[0][x] = w.slot[1][x] = NONE;
+    if (x < (int64_t)scan::blocks_for(w.n)) w.st[x] = 0;
+    if (x < rfn::RC_COUNT) w.ctrl[x] = 0;
+}
+// per triangle: corners sorted, sign and weight over them, degrees; per cell: the reference it holds
+__global__ __launch_bounds__(256) void refine_tri_kernel(Batch<RefineArgs> b) {
+    const RefineArgs &w = b.w[blockIdx.y];
+    const int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (x < w.n && w.match[x] >= 0) w.owner[col_of(w, w.match[x])] = (int32_t)x;
+    if (x >= n_tris(w)) return;
+    int32_t a = w.tris[3 * x], c1 = w.tris[3 * x + 1], c2 = w.tris[3 * x + 2], t;
+    if (a > c1) { t = a; a = c1; c1 = t; }
+    if (c1 > c2) { t = c1; c1 = c2; c2 = t; }
+    if (a > c1) { t = a; a = c1; c1 = t; }
+    w.tsort[3 * x] = a;
+    w.tsort[3 * x + 1] = c1;
+    w.tsort[3 * x + 2] = c2;
+    w.tsign[x] = orient_sign(ld2(w.axy, a), ld2(w.axy, c1), ld2(w.axy, c2));
+    w.tw[x] = w.size[a] + w.size[c1] + w.size[c2];
+    atomicAdd(&w.deg[a], 1u);
+    atomicAdd(&w.deg[c1], 1u);
+    atomicAdd(&w.deg[c2], 1u);
+}
+__global__ __launch_bounds__(scan::NT) void refine_scan_kernel(Batch<RefineArgs> b) {
+    __shared__ scan::Shared sh;
+    const RefineArgs &w = b.w[blockIdx.y];
+    const int nb = (int)scan::blocks_for(w.n);
+    if ((int)blockIdx.x >= nb) return;
+    const int64_t n = w.n;
+    auto val = [&](int64_t i) { return scan::Pair{i < n ? w.deg[i] : 0u, 0u}; };
+    scan::Pair through;
+    const scan::Pair off = scan::exclusive(w.st, (int)blockIdx.x, val, sh, &through);
+    const int64_t i = (int64_t)blockIdx.x * scan::NT + threadIdx.x;
+    if (i < n) w.off[i] = (int32_t)off.a;
+    if ((int)blockIdx.x == nb - 1 && threadIdx.x == 0) w.off[n] = (int32_t)through.a;
+}
+__global__ __launch_bounds__(256) void refine_fill_kernel(Batch<RefineArgs> b) {
+    const RefineArgs &w = b.w[blockIdx.y];
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_tris(w)) return;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const int32_t v = w.tsort[3 * t + q];
+        w.inc[w.off[v] + (int32_t)atomicAdd(&w.cur[v], 1u)] = (int32_t)t;
+    }
+}
+// each cell's incident triangles in the order of their sorted corner rows (distinct triangles: distinct keys)
+__device__ __forceinline__ bool tri_less(const RefineArgs &w, int32_t s, int32_t t) {
+    const int32_t *a = w.tsort + 3 * (int64_t)s, *c = w.tsort + 3 * (int64_t)t;
+    if (a[0] != c[0]) return a[0] < c[0];
+    if (a[1] != c[1]) return a[1] < c[1];
+    if (a[2] != c[2]) return a[2] < c[2];
+    return s < t;
+}
+__global__ __launch_bounds__(256) void refine_sort_kernel(Batch<RefineArgs> b) {
+    const RefineArgs &w = b.w[blockIdx.y];
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= w.n) return;
+    int32_t *l = w.inc + w.off[i];
+    const int32_t d = w.off[i + 1] - w.off[i];
+    for (int32_t q = 1; q < d; ++q) {
+        const int32_t t = l[q];
+        int32_t r = q - 1;
+        while (r >= 0 && tri_less(w, t, l[r])) {
+            l[r + 1] = l[r];
+            --r;
+        }
+        l[r + 1] = t;
+    }
+}
+// the objective of the current matching: one block of OBJ_NT per window, a fixed reduction order
+constexpr int OBJ_NT = 1024;
+__global__ __launch_bounds__(OBJ_NT) void refine_objective_kernel(Batch<RefineArgs> b, int which) {
+    const RefineArgs &w = b.w[blockIdx.y];
+    double c = 0.0, f = 0.0;
+    for (int64_t i = threadIdx.x; i < w.n; i += OBJ_NT) c += w.match[i] >= 0 ? w.cost[w.match[i]] : unm_of(w, i);
+    const int64_t Tr = n_tris(w);
+    for (int64_t t = threadIdx.x; t < Tr; t += OBJ_NT)
+        if (flips(w, (int32_t)t, -1, 0, -1, 0)) f += w.tw[t];
+    for (int o = 32; o > 0; o >>= 1) {
+        c += __shfl_down(c, o, 64);
+        f += __shfl_down(f, o, 64);
+    }
+    __shared__ double pc[OBJ_NT / 64], pf[OBJ_NT / 64];
+    if ((threadIdx.x & 63) == 0) {
+        pc[threadIdx.x >> 6] = c;
+        pf[threadIdx.x >> 6] = f;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double cs = 0.0, fs = 0.0;
+        for (int q = 0; q < OBJ_NT / 64; ++q) {
+            cs += pc[q];
+            fs += pf[q];
+        }
+        const double obj = cs + w.dp * fs;
+        w.ctrl[which] = (unsigned long long)__double_as_longlong(obj);
+    }
+}
+
+// ---- rounds ---------------------------------------------------------------------------------------------------------------------
+// q_t of every triangle under the matching the round starts from
+__global__ __launch_bounds__(256) void refine_flag_kernel(Batch<RefineArgs> b) {
+    const RefineArgs &w = b.w[blockIdx.y];
+    if ((int64_t)blockIdx.x * blockDim.x >= n_tris(w) || !active(w)) return;
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < n_tris(w)) w.q[t] = flips(w, (int32_t)t, -1, 0, -1, 0);
+}
+__global__ __launch_bounds__(256) void refine_propose_kernel(Batch<RefineArgs> b) {
+    const RefineArgs &w = b.w[blockIdx.y];
+    if ((int64_t)blockIdx.x * blockDim.x >= w.n || !active(w)) return;
+    const int32_t i = (int32_t)((int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= w.n) return;
+    Prop best{NONE, -1, -1, -1, 0};
+    double bd = 0.0;
+    bool found = false;
+    const int32_t po = w.match[i];
+    auto consider = [&](Delta x, int32_t pn, int32_t k, int32_t pk) {
+        if (!improves(x) || (found && !(x.d < bd))) return;
+        found = true;
+        bd = x.d;
+        best.p_i = pn;
+        best.k = k;
+        best.p_k = pk;
+    };
+    if (po >= 0) consider(delta_single(w, i, -1), -1, -1, -1);
+    const int32_t jo = po >= 0 ? col_of(w, po) : -1;
+    for (int32_t p = w.prow[i]; p < w.prow[i + 1]; ++p) {
+        if (p == po) continue;
+        const int32_t o = w.owner[col_of(w, p)];
+        if (o < 0) {
+            consider(delta_single(w, i, p), p, -1, -1);
+        } else if (po >= 0 && o > i) {
+            for (int32_t q = w.prow[o]; q < w.prow[o + 1]; ++q)
+                if (col_of(w, q) == jo) {
+                    consider(delta_swap(w, i, p, o, q), p, o, q);
+                    break;
+                }
+        }
+    }
+    if (found) {
+        best.key = key_of(bd, i);
+        unsigned long long *s = w.slot[ld_ctrl(w, rfn::RC_ROUNDS) & 1];
+        each_slot(w, i, best, [&](int64_t x) { atomicMin(&s[x], best.key); return true; });
+    }
+    w.best[i] = best;
+}
+// winners (their key is the minimum on every slot of their footprint) applied; the other parity's slots cleared for the next round;
+// the last block of the window closes the round
+__global__ __launch_bounds__(256) void refine_apply_kernel(Batch<RefineArgs> b) {
+    const RefineArgs &w = b.w[blockIdx.y];
+    const int64_t ns = w.n + w.n_r;
+    const unsigned nb = (unsigned)((ns + 255) / 256);        // the window's own blocks (launch: grid_for of the largest)
+    if (blockIdx.x >= nb || !active(w)) return;
+    const unsigned long long par = ld_ctrl(w, rfn::RC_ROUNDS) & 1;
+    const int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool won = false;
+    if (x < w.n) {
+        const int32_t i = (int32_t)x;
+        const Prop pr = w.best[i];
+        if (pr.key != NONE) {
+            const unsigned long long *s = w.slot[par];
+            won = each_slot(w, i, pr, [&](int64_t y) { return s[y] == pr.key; });
+            if (won) {
+                const int32_t po = w.match[i];
+                if (pr.k >= 0) {
+                    w.match[i] = pr.p_i;
+                    w.match[pr.k] = pr.p_k;
+                    w.owner[col_of(w, pr.p_i)] = i;
+                    w.owner[col_of(w, pr.p_k)] = pr.k;
+                } else {
+                    if (po >= 0) w.owner[col_of(w, po)] = -1;
+                    if (pr.p_i >= 0) w.owner[col_of(w, pr.p_i)] = i;
+                    w.match[i] = pr.p_i;
+                }
+            }
+        }
+    }
+    if (x < ns) w.slot[par ^ 1][x] = NONE;
+    const unsigned long long bal = __ballot(won);
+    if ((threadIdx.x & 63) == 0 && bal) atomicAdd(&w.ctrl[rfn::RC_WIN], (unsigned long long)__builtin_popcountll(bal));
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __threadfence();
+        if (atomicAdd(&w.ctrl[rfn::RC_DONE], 1ull) == nb - 1) {
+            __threadfence();
+            const unsigned long long win = atomicAdd(&w.ctrl[rfn::RC_WIN], 0ull);
+            if (win) {
+                w.ctrl[rfn::RC_ROUNDS] += 1;
+                w.ctrl[rfn::RC_MOVES] += win;
+            } else {
+                w.ctrl[rfn::RC_SETTLED] = 1;
+            }
+            w.ctrl[rfn::RC_WIN] = 0;
+            w.ctrl[rfn::RC_DONE] = 0;
+        }
+    }
+}
+
+}  // namespace
+
+namespace rfn {
+
+size_t work_bytes(int64_t n, int64_t n_r, int64_t cap_tr) {
+    const size_t N = (size_t)std::max<int64_t>(n, 1), R = (size_t)std::max<int64_t>(n_r, 1), T = (size_t)std::max<int64_t>(cap_tr, 1);
+    Carver cv;
+    cv.take(N * 4);                 // match
+    cv.take(R * 4);                 // owner
+    cv.take(T * 12);                // tsort
+    cv.take(T);                     // tsign
+    cv.take(T * 8);                 // tw
+    cv.take(T);                     // q
+    cv.take(N * 4);                 // deg
+    cv.take(N * 4);                 // cur
+    cv.take((N + 1) * 4);           // off
+    cv.take(T * 12);                // inc
+    cv.take(scan::status_bytes(n)); // st
+    cv.take((N + R) * 8);           // slot[0]
+    cv.take((N + R) * 8);           // slot[1]
+    cv.take(N * sizeof(Prop));      // best
+    return cv.off;
+}
+
+void carve(RefineArgs *a, char *work) {
+    const size_t N = (size_t)std::max<int64_t>(a->n, 1), R = (size_t)std::max<int64_t>(a->n_r, 1), T = (size_t)std::max<int64_t>(a->cap_tr, 1);
+    Carver cv;
+    a->match = reinterpret_cast<int32_t *>(work + cv.take(N * 4));
+    a->owner = reinterpret_cast<int32_t *>(work + cv.take(R * 4));
+    a->tsort = reinterpret_cast<int32_t *>(work + cv.take(T * 12));
+    a->tsign = reinterpret_cast<int8_t *>(work + cv.take(T));
+    a->tw = reinterpret_cast<double *>(work + cv.take(T * 8));
+    a->q = reinterpret_cast<uint8_t *>(work + cv.take(T));
+    a->deg = reinterpret_cast<unsigned *>(work + cv.take(N * 4));
+    a->cur = reinterpret_cast<unsigned *>(work + cv.take(N * 4));
+    a->off = reinterpret_cast<int32_t *>(work + cv.take((N + 1) * 4));
+    a->inc = reinterpret_cast<int32_t *>(work + cv.take(T * 12));
+    a->st = reinterpret_cast<unsigned long long *>(work + cv.take(scan::status_bytes(a->n)));
+    a->slot[0] = reinterpret_cast<unsigned long long *>(work + cv.take((N + R) * 8));
+    a->slot[1] = reinterpret_cast<unsigned long long *>(work + cv.take((N + R) * 8));
+    a->best = reinterpret_cast<Prop *>(work + cv.take(N * sizeof(Prop)));
+}
+
+static Batch<RefineArgs> batch_of(const RefineArgs *jobs, int n_w, int64_t *max_n, int64_t *max_s, int64_t *max_t) {
+    Batch<RefineArgs> bt{};
+    *max_n = *max_s = *max_t = 0;
+    for (int q = 0; q < n_w; ++q) {
+        bt.w[q] = jobs[q];
+        *max_n = std::max(*max_n, jobs[q].n);
+        *max_s = std::max(*max_s, jobs[q].n + jobs[q].n_r);
+        *max_t = std::max(*max_t, jobs[q].cap_tr);
+    }
+    return bt;
+}
+
+int launch_setup(same_ctx *ctx, const RefineArgs *jobs, int n_w) {
+    if (n_w <= 0) return SAME_OK;
+    int64_t max_n, max_s, max_t;
+    const Batch<RefineArgs> bt = batch_of(jobs, n_w, &max_n, &max_s, &max_t);
+    const unsigned nw = (unsigned)n_w;
+    SAME_LAUNCH(ctx, refine_init_kernel, dim3(grid_for(std::max<int64_t>(max_s, 64)), nw), dim3(256), 0, bt);
+    SAME_LAUNCH(ctx, refine_tri_kernel, dim3(grid_for(std::max(max_t, max_n)), nw), dim3(256), 0, bt);
+    SAME_LAUNCH(ctx, refine_scan_kernel, dim3(scan::blocks_for(max_n), nw), dim3(scan::NT), 0, bt);
+    SAME_LAUNCH(ctx, refine_fill_kernel, dim3(grid_for(max_t), nw), dim3(256), 0, bt);
+    SAME_LAUNCH(ctx, refine_sort_kernel, dim3(grid_for(max_n), nw), dim3(256), 0, bt);
+    SAME_LAUNCH(ctx, refine_objective_kernel, dim3(1, nw), dim3(OBJ_NT), 0, bt, (int)RC_OBJ0);
+    HIP_TRY(ctx, hipGetLastError());
+    return SAME_OK;
+}
+
+int launch_rounds(same_ctx *ctx, const RefineArgs *jobs, int n_w, int rounds) {
+    if (n_w <= 0) return SAME_OK;
+    int64_t max_n, max_s, max_t;
+    const Batch<RefineArgs> bt = batch_of(jobs, n_w, &max_n, &max_s, &max_t);
+    const unsigned nw = (unsigned)n_w;
+    for (int r = 0; r < rounds; ++r) {
+        SAME_LAUNCH(ctx, refine_flag_kernel, dim3(grid_for(max_t), nw), dim3(256), 0, bt);
+        SAME_LAUNCH(ctx, refine_propose_kernel, dim3(grid_for(max_n), nw), dim3(256), 0, bt);
+        SAME_LAUNCH(ctx, refine_apply_kernel, dim3(grid_for(max_s), nw), dim3(256), 0, bt);
+    }
+    SAME_LAUNCH(ctx, refine_objective_kernel, dim3(1, nw), dim3(OBJ_NT), 0, bt, (int)RC_OBJ);
+    HIP_TRY(ctx, hipGetLastError());
+    return SAME_OK;
+}
+
+}  // namespace rfn
+
+// ---- the host-buffer form ------------------------------------------------------------------------------------------------------
+extern "C" int same_refine_matching(same_ctx *ctx, const int32_t *pairs, const double *costs, int64_t P, const double *unmatched, int64_t n_m,
+                                    int64_t n_r, const int32_t *tris, int64_t Tr, const double *axy, const double *ref_xy, const double *size,
+                                    double delaunay_penalty, int64_t rounds_cap, int32_t *match_pair_inout, int64_t *out_stats) {
+    REQUIRE(ctx, ctx != nullptr);
+    REQUIRE(ctx, P >= 0 && n_m >= 0 && n_r >= 0 && Tr >= 0 && n_m + n_r < ((int64_t)1 << 30) && P < ((int64_t)1 << 31) - 1 &&
+                     Tr < ((int64_t)1 << 29));
+    REQUIRE(ctx, (P == 0 || (pairs && costs)) && (n_m == 0 || (unmatched && match_pair_inout && axy && size)) && (n_r == 0 || ref_xy) &&
+                     (Tr == 0 || tris) && out_stats);
+    REQUIRE(ctx, rounds_cap >= 1 && delaunay_penalty >= 0.0 && delaunay_penalty - delaunay_penalty == 0.0);
+    // the pairs by row (stable: the caller's order inside a row), each (row, column) once; the start one-to-one
+    std::vector<int32_t> prow((size_t)n_m + 1, 0), order((size_t)P), where((size_t)P), csr((size_t)P * 2), start((size_t)n_m);
+    std::vector<double> ccsr((size_t)P);
+    for (int64_t p = 0; p < P; ++p) {
+        const int32_t i = pairs[2 * p], j = pairs[2 * p + 1];
+        REQUIRE(ctx, i >= 0 && i < n_m && j >= 0 && j < n_r);
+        ++prow[(size_t)i + 1];
+    }
+    for (int64_t i = 0; i < n_m; ++i) prow[(size_t)i + 1] += prow[(size_t)i];
+    {
+        std::vector<int32_t> at(prow.begin(), prow.end() - 1);
+        for (int64_t p = 0; p < P; ++p) {
+            const int32_t q = at[(size_t)pairs[2 * p]]++;
+            order[(size_t)q] = (int32_t)p;
+            where[(size_t)p] = q;
+        }
+    }
+    std::vector<int64_t> seen((size_t)n_r, -1);
+    for (int64_t i = 0; i < n_m; ++i)
+        for (int32_t q = prow[(size_t)i]; q < prow[(size_t)i + 1]; ++q) {
+            const int32_t p = order[(size_t)q], j = pairs[2 * (int64_t)p + 1];
+            if (seen[(size_t)j] == i) {
+                ctx->err = "invalid argument: a (row, column) pair given twice";
+                return SAME_EINVAL;
+            }
+            seen[(size_t)j] = i;
+            csr[2 * (size_t)q] = (int32_t)i;
+            csr[2 * (size_t)q + 1] = j;
+            ccsr[(size_t)q] = costs[p];
+        }
+    std::vector<uint8_t> held((size_t)n_r, 0);
+    for (int64_t i = 0; i < n_m; ++i) {
+        const int32_t p = match_pair_inout[i];
+        REQUIRE(ctx, p >= -1 && p < P && (p < 0 || pairs[2 * (int64_t)p] == i));
+        if (p >= 0) {
+            const int32_t j = pairs[2 * (int64_t)p + 1];
+            if (held[(size_t)j]) {
+                ctx->err = "invalid argument: the start matching takes a reference twice";
+                return SAME_EINVAL;
+            }
+            held[(size_t)j] = 1;
+        }
+        start[(size_t)i] = p >= 0 ? where[(size_t)p] : -1;
+    }
+    SAME_TRY(check_index_range(ctx, tris, Tr * 3, 0, n_m, "triangles"));
+    SAME_TRY(same_use(ctx));
+    Carver cv;
+    const size_t o_prow = cv.take(((size_t)n_m + 1) * 4), o_pairs = cv.take((size_t)P * 8 + 8), o_cost = cv.take((size_t)P * 8 + 8),
+                 o_unm = cv.take((size_t)n_m * 8 + 8), o_size = cv.take((size_t)n_m * 8 + 8), o_axy = cv.take((size_t)n_m * 16 + 16),
+                 o_rxy = cv.take((size_t)n_r * 16 + 16), o_tris = cv.take((size_t)Tr * 12 + 12), o_start = cv.take((size_t)n_m * 4 + 4),
+                 o_ctrl = cv.take(rfn::RC_COUNT * 8), o_work = cv.take(rfn::work_bytes(n_m, n_r, Tr));
+    char *d = nullptr;
+    SAME_TRY(slot_as(ctx, SL_OUT0, cv.off, &d));
+    rfn::RefineArgs a{};
+    a.prow = reinterpret_cast<const int32_t *>(d + o_prow);
+    a.pairs = reinterpret_cast<const int32_t *>(d + o_pairs);
+    a.cost = reinterpret_cast<const double *>(d + o_cost);
+    a.unm = reinterpret_cast<const double *>(d + o_unm);
+    a.size = reinterpret_cast<const double *>(d + o_size);
+    a.dp = delaunay_penalty;
+    a.axy = reinterpret_cast<const double *>(d + o_axy);
+    a.ref_xy = reinterpret_cast<const double *>(d + o_rxy);
+    a.tris = reinterpret_cast<const int32_t *>(d + o_tris);
+    a.n = n_m;
+    a.n_r = n_r;
+    a.cap_tr = Tr;
+    a.cap = rounds_cap;
+    a.start = reinterpret_cast<const int32_t *>(d + o_start);
+    a.ctrl = reinterpret_cast<unsigned long long *>(d + o_ctrl);
+    rfn::carve(&a, d + o_work);
+    SAME_COPY(ctx, d + o_prow, prow.data(), prow.size() * 4, hipMemcpyHostToDevice);
+    if (P) {
+        SAME_COPY(ctx, d + o_pairs, csr.data(), (size_t)P * 8, hipMemcpyHostToDevice);
+        SAME_COPY(ctx, d + o_cost, ccsr.data(), (size_t)P * 8, hipMemcpyHostToDevice);
+    }
+    if (n_m) {
+        SAME_COPY(ctx, d + o_unm, unmatched, (size_t)n_m * 8, hipMemcpyHostToDevice);
+        SAME_COPY(ctx, d + o_size, size, (size_t)n_m * 8, hipMemcpyHostToDevice);
+        SAME_COPY(ctx, d + o_axy, axy, (size_t)n_m * 16, hipMemcpyHostToDevice);
+        SAME_COPY(ctx, d + o_start, start.data(), (size_t)n_m * 4, hipMemcpyHostToDevice);
+    }
+    if (n_r) SAME_COPY(ctx, d + o_rxy, ref_xy, (size_t)n_r * 16, hipMemcpyHostToDevice);
+    if (Tr) SAME_COPY(ctx, d + o_tris, tris, (size_t)Tr * 12, hipMemcpyHostToDevice);
+    std::vector<int32_t> mp((size_t)n_m);
+    unsigned long long ctrl[rfn::RC_COUNT] = {};
+    if (n_m) {
+        SAME_TRY(rfn::launch_setup(ctx, &a, 1));
+        // rounds in growing chunks up to the cap (every enqueued round of a live search either applies moves or settles it); one wait
+        // unless the search is still moving after the first chunk
+        int64_t chunk = std::min<int64_t>(rfn::FIRST_ROUNDS * 4, rounds_cap);
+        for (;;) {
+            SAME_TRY(rfn::launch_rounds(ctx, &a, 1, (int)chunk));
+            SAME_COPY(ctx, ctrl, a.ctrl, sizeof ctrl, hipMemcpyDeviceToHost);
+            SAME_COPY(ctx, mp.data(), a.match, (size_t)n_m * 4, hipMemcpyDeviceToHost);
+            SAME_WAIT(ctx);
+            if (ctrl[rfn::RC_SETTLED] || (int64_t)ctrl[rfn::RC_ROUNDS] >= rounds_cap) break;
+            chunk = std::min<int64_t>(chunk * 2, rounds_cap - (int64_t)ctrl[rfn::RC_ROUNDS]);
+        }
+    }
+    for (int64_t i = 0; i < n_m; ++i) match_pair_inout[i] = mp[(size_t)i] >= 0 ? order[(size_t)mp[(size_t)i]] : -1;
+    out_stats[0] = (int64_t)ctrl[rfn::RC_ROUNDS];
+    out_stats[1] = (int64_t)ctrl[rfn::RC_MOVES];
+    out_stats[2] = (int64_t)ctrl[rfn::RC_SETTLED];
+    out_stats[3] = (int64_t)ctrl[rfn::RC_OBJ0];
+    out_stats[4] = (int64_t)ctrl[rfn::RC_OBJ];
+    return SAME_OK;
+}

@@ -3,9 +3,11 @@
 // device, in the reference's order (a cosine within 8 ulp of the angle threshold is left to the host, which re-decides it with the
 // reference's literal arccos and calls again with prefiltered = 1: the kept triangles in, no filter); source signs / weights
 // (src/same.py:1128-1146), per-row minimum and the greedy MIP start (src/init_helpers.py:104-133), the lazy-constraint body under
-// that incumbent (src/same.py:645-669), XY-order sweep (src/violationhelper.py:53-117), signed-area flips (src/same.py:1362-1402).
+// that incumbent, optionally refined against the model's flip penalty (refine.hip), the lazy-constraint body under the result
+// (src/same.py:645-669), XY-order sweep (src/violationhelper.py:53-117), signed-area flips (src/same.py:1362-1402).
 // Back to the host: the matched reference row per kept aligned cell, the per-cell violation flags and eight counters.
 #include "assign.h"
+#include "refine.h"
 
 namespace {
 
@@ -169,9 +171,10 @@ __global__ __launch_bounds__(256) void row_prefer_kernel(Batch<PreferArgs> b, do
     w.match_pair[a] = -1;
 }
 // pair per row -> matched reference cell: its number in the window (handed out), its section row (the sweeps and the caller); and
-// whether the greedy rule is finished: a pair still alive whose end points are both free would be taken by a further round
+// whether the greedy rule is finished: a pair still alive whose end points are both free would be taken by a further round.  The
+// rows' pairs are `final_pair` (the local search's result, or the incumbent itself); the greedy rule's state is the incumbent's
 struct MatchRowsArgs {
-    const int32_t *match_pair, *pairs, *jsec, *prow;
+    const int32_t *match_pair, *final_pair, *pairs, *jsec, *prow;
     const uint8_t *alive, *used;
     int64_t n_rows;
     const unsigned long long *dn;
@@ -186,12 +189,12 @@ __global__ __launch_bounds__(256) void match_rows_kernel(Batch<MatchRowsArgs> b)
     bool m = false;
     int open = 0;
     if (i < (int64_t)*w.dn) {
-        const int32_t p = w.match_pair[i];
+        const int32_t p = w.final_pair[i];
         w.match_loc[i] = p >= 0 ? w.pairs[2 * (int64_t)p + 1] : -1;
         w.match_row[i] = p >= 0 ? w.jsec[p] : -1;
         w.pflag[i] = 0;
         m = p >= 0;
-        if (!m && !w.used[i])
+        if (w.match_pair[i] < 0 && !w.used[i])
             for (int32_t q = w.prow[i]; q < w.prow[i + 1]; ++q) open += w.alive[q] && !w.used[w.n_rows + w.pairs[2 * (int64_t)q + 1]];
     }
     const unsigned long long bal = __ballot(m), ob = __ballot(open != 0);
@@ -373,6 +376,8 @@ struct FinishPlan {
     int64_t cap_tr = 0;
     const unsigned long long *dTr = nullptr;
     char *assign_work = nullptr;              // the optimal assignment's work arrays (SAME_INCUMBENT_ASSIGNMENT), else null
+    bool refine = false;                      // the local search runs on the incumbent (same_window_set_refine) ...
+    rfn::RefineArgs rargs{};                  // ... over these arrays; its control words are counters + SC_REFINE
 };
 
 // match rows + the one pass over the triangles, for a group of windows (<= SAME_LAUNCH_WINDOWS) in one launch each
@@ -384,7 +389,7 @@ int enqueue_tail(same_ctx *ctx, same_window *const *ws, FinishPlan *const *ps, i
         same_window *w = ws[q];
         FinishPlan *p = ps[q];
         const int64_t n = w->n_ua;
-        mb.w[q] = MatchRowsArgs{p->match_pair, w->pairs, w->jsec, w->prow, p->gs.alive, p->gs.used, n, w->counts + 2, w->match_loc, p->match_row, p->pflag,
+        mb.w[q] = MatchRowsArgs{p->match_pair, p->refine ? p->rargs.match : p->match_pair, w->pairs, w->jsec, w->prow, p->gs.alive, p->gs.used, n, w->counts + 2, w->match_loc, p->match_row, p->pflag,
                                 p->counters};
         sb.w[q] = SweepArgs{static_cast<const int32_t *>(w->tris.p), p->cap_tr, p->dTr, w->axy_c, w->size_c, w->ref->xy, p->match_row, w->sign, w->weight,
                             p->pflag, p->counters};
@@ -419,6 +424,7 @@ int prepare_finish(same_window *w, const int32_t *host_tris, int64_t cap_tr, con
     const size_t o_alive = cv.take((size_t)std::max<int64_t>(P, 1)), o_match_pair = cv.take((size_t)n * 4), o_match_loc = cv.take((size_t)n * 4),
                  o_sign = cv.take(tt), o_weight = cv.take(tt * 8);
     const size_t o_assign = w->incumbent == SAME_INCUMBENT_ASSIGNMENT ? cv.take(asg::work_bytes(n, w->n_r)) : 0;
+    const size_t o_refine = w->rf_cap > 0 ? cv.take(rfn::work_bytes(n, w->n_r, cap_tr)) : 0;
     SAME_TRY(ensure(ctx, w->finish, cv.off));
     SAME_TRY(ensure(ctx, w->tris, tt * 12));
     char *base = static_cast<char *>(w->finish.p);
@@ -450,9 +456,43 @@ int prepare_finish(same_window *w, const int32_t *host_tris, int64_t cap_tr, con
     p->assign_work = o_assign ? at(o_assign) : nullptr;
     p->cap_tr = cap_tr;
     p->dTr = dTr;
+    p->refine = o_refine != 0;
+    if (p->refine) {
+        rfn::RefineArgs &r = p->rargs;
+        r = rfn::RefineArgs{};
+        r.prow = w->prow;
+        r.pairs = w->pairs;
+        r.cost = w->cost64;
+        r.size = w->size_c;
+        r.dp = w->rf_dp;
+        r.axy = w->axy_c;
+        r.ref_xy = w->ref->xy;
+        r.ref_row = w->jsec;
+        r.tris = static_cast<const int32_t *>(w->tris.p);
+        r.dTr = dTr;
+        r.n = n;
+        r.n_r = w->n_r;
+        r.cap_tr = cap_tr;
+        r.cap = w->rf_cap;
+        r.penalty = w->rf_nm;
+        r.start = p->match_pair;
+        r.ctrl = p->counters + SC_REFINE;
+        rfn::carve(&r, at(o_refine));
+    }
     REQUIRE(ctx, w->host_finish_off + p->back_bytes <= w->host_filter_off);   // sized by the stage call
     if (host_tris && cap_tr) SAME_COPY(ctx, w->tris.p, host_tris, (size_t)cap_tr * 12, hipMemcpyHostToDevice);
     return SAME_OK;
+}
+
+// the local search from the incumbent, for the windows of a group that ask for it: setup and the first rounds (refine.hip)
+int enqueue_refine(same_ctx *ctx, FinishPlan *const *ps, int n_w) {
+    rfn::RefineArgs jobs[SAME_LAUNCH_WINDOWS];
+    int k = 0;
+    for (int q = 0; q < n_w; ++q)
+        if (ps[q]->refine) jobs[k++] = ps[q]->rargs;
+    if (k == 0) return SAME_OK;
+    SAME_TRY(rfn::launch_setup(ctx, jobs, k));
+    return rfn::launch_rounds(ctx, jobs, k, rfn::FIRST_ROUNDS);
 }
 
 // greedy MIP start of a group of prepared windows -- per-row minimum, rows that beat their penalty, the scan's matching (one pair per
@@ -481,6 +521,7 @@ int launch_finish(same_ctx *ctx, same_window *const *ws, FinishPlan *const *ps, 
             asg::carve(&a, p->assign_work);
         }
         SAME_TRY(asg::launch(ctx, jobs, n_w));
+        SAME_TRY(enqueue_refine(ctx, ps, n_w));
         return enqueue_tail(ctx, ws, ps, n_w);
     }
     Batch<PreferArgs> pb{};
@@ -501,6 +542,7 @@ int launch_finish(same_ctx *ctx, same_window *const *ws, FinishPlan *const *ps, 
     }
     if (max_n) SAME_LAUNCH(ctx, row_prefer_kernel, dim3(grid_for(max_n), (unsigned)n_w), dim3(256), 0, pb, no_match_penalty);
     SAME_TRY(same_greedy_rounds_batch_core(ctx, jobs, n_w, 0, WINDOW_GREEDY_ROUNDS));
+    SAME_TRY(enqueue_refine(ctx, ps, n_w));
     return enqueue_tail(ctx, ws, ps, n_w);
 }
 
@@ -512,6 +554,46 @@ int enqueue_finish_copy(same_window *w, FinishPlan *p) {
     return SAME_OK;
 }
 
+// After a look at the finish block (in the pinned block): when the incumbent changed since (`fresh`: greedy rounds added), the local
+// search again from it; more rounds while the search is live and under its cap, in growing chunks, one wait each; then, if any of that
+// happened, the tail again and the finish block back.  The search's result goes to the window (same_window_refine_result).
+int settle(same_window *w, FinishPlan *p, bool fresh) {
+    same_ctx *ctx = w->ctx;
+    char *h = static_cast<char *>(w->host) + w->host_finish_off;
+    const unsigned long long *rc = reinterpret_cast<const unsigned long long *>(h + p->o_counters) + SC_REFINE;
+    bool redo = fresh;
+    if (p->refine) {
+        int chunk = rfn::FIRST_ROUNDS;
+        if (fresh) {
+            SAME_TRY(enqueue_refine(ctx, &p, 1));
+            SAME_COPY(ctx, const_cast<unsigned long long *>(rc), p->rargs.ctrl, rfn::RC_COUNT * 8, hipMemcpyDeviceToHost);
+            SAME_WAIT(ctx);
+        }
+        while (!rc[rfn::RC_SETTLED] && (int64_t)rc[rfn::RC_ROUNDS] < w->rf_cap) {
+            chunk = (int)std::min<int64_t>(std::min(2 * chunk, 256), w->rf_cap - (int64_t)rc[rfn::RC_ROUNDS]);
+            SAME_TRY(rfn::launch_rounds(ctx, &p->rargs, 1, chunk));
+            SAME_COPY(ctx, const_cast<unsigned long long *>(rc), p->rargs.ctrl, rfn::RC_COUNT * 8, hipMemcpyDeviceToHost);
+            SAME_WAIT(ctx);
+            ++ctx->stats[SAME_STAT_GREEDY_READBACKS];
+            redo = true;
+        }
+    }
+    if (redo) {
+        SAME_FILL(ctx, p->counters, 0, SC_REFINE * 8);
+        SAME_TRY(enqueue_tail(ctx, &w, &p, 1));
+        SAME_COPY(ctx, h, reinterpret_cast<const char *>(p->gs.sel), p->back_bytes, hipMemcpyDeviceToHost);
+        SAME_WAIT(ctx);
+    }
+    if (p->refine) {
+        w->rf_rounds = (int64_t)rc[rfn::RC_ROUNDS];
+        w->rf_moves = (int64_t)rc[rfn::RC_MOVES];
+        w->rf_settled = (int64_t)rc[rfn::RC_SETTLED];
+        memcpy(&w->rf_obj0, &rc[rfn::RC_OBJ0], sizeof(double));
+        memcpy(&w->rf_obj, &rc[rfn::RC_OBJ], sizeof(double));
+    }
+    return SAME_OK;
+}
+
 int read_finish(same_window *w, FinishPlan *p, int32_t *out_match_row, uint8_t *out_point_flag, int64_t *out_stats, int64_t *out_ties) {
     same_ctx *ctx = w->ctx;
     const int64_t n = w->n_ua, P = w->P;
@@ -520,6 +602,7 @@ int read_finish(same_window *w, FinishPlan *p, int32_t *out_match_row, uint8_t *
     const unsigned long long *sel = reinterpret_cast<const unsigned long long *>(h);
     const unsigned long long *cnt = reinterpret_cast<const unsigned long long *>(h + p->o_counters);
     int rounds = 0;
+    bool again = false;      // the incumbent changed after the first look
     if (w->incumbent == SAME_INCUMBENT_ASSIGNMENT) {     // no greedy rounds to add: the assignment settled in its one launch
         rounds = (int)sel[0];
         w->as_rounds = (int64_t)sel[0];
@@ -546,12 +629,10 @@ int read_finish(same_window *w, FinishPlan *p, int32_t *out_match_row, uint8_t *
                 if (q < batch) break;
                 if (batch < SAME_GREEDY_BATCH_MAX) batch *= 2;
             }
-            SAME_FILL(ctx, p->counters, 0, SC_COUNT * 8);
-            SAME_TRY(enqueue_tail(ctx, &w, &p, 1));
-            SAME_COPY(ctx, h, dsel, p->back_bytes, hipMemcpyDeviceToHost);
-            SAME_WAIT(ctx);
+            again = true;
         }
     }
+    SAME_TRY(settle(w, p, again));
     for (int q = 0; q < 8; ++q) out_stats[q] = (int64_t)cnt[q];
     out_stats[SC_ROUNDS] = rounds;
     *out_ties += (int64_t)cnt[SC_TIES];
@@ -612,6 +693,9 @@ int filter_finish(same_window *const *windows, int n_windows, const int32_t *sim
         w->Tr = 0;
         w->as_rounds = w->as_flags = 0;
         w->as_objective = 0.0;
+        w->rf_rounds = w->rf_moves = w->rf_settled = 0;
+        w->rf_obj0 = w->rf_obj = 0.0;
+        w->rf_nm = no_match_penalty;
         if (w->n_ua == 0) continue;
         if (Tr && !prefiltered) {
             const int32_t *raw = on_device ? static_cast<const int32_t *>(w->dd_tris.p) : d_simplices + 3 * simplex_offsets[i];
@@ -766,6 +850,26 @@ int same_window_incumbent_result(same_window *window, int64_t *out_rounds, int64
     return SAME_OK;
 }
 
+int same_window_set_refine(same_window *window, int64_t rounds_cap, double delaunay_penalty) {
+    if (!window) return SAME_EINVAL;
+    REQUIRE(window->ctx, rounds_cap >= 0 && delaunay_penalty >= 0.0 && delaunay_penalty - delaunay_penalty == 0.0);
+    window->rf_cap = rounds_cap;
+    window->rf_dp = rounds_cap > 0 ? delaunay_penalty : 0.0;
+    return SAME_OK;
+}
+
+int same_window_refine_result(same_window *window, int64_t *out_rounds, int64_t *out_moves, int64_t *out_settled, double *out_objective_start,
+                              double *out_objective) {
+    if (!window) return SAME_EINVAL;
+    REQUIRE(window->ctx, out_rounds && out_moves && out_settled && out_objective_start && out_objective && window->finished);
+    *out_rounds = window->rf_rounds;
+    *out_moves = window->rf_moves;
+    *out_settled = window->rf_settled;
+    *out_objective_start = window->rf_obj0;
+    *out_objective = window->rf_obj;
+    return SAME_OK;
+}
+
 int same_window_refinish(same_window *window, const int32_t *match_pair, int32_t *out_match_row, uint8_t *out_point_flag, int64_t *out_stats) {
     if (!window) return SAME_EINVAL;
     same_window *w = window;
@@ -780,10 +884,12 @@ int same_window_refinish(same_window *window, const int32_t *match_pair, int32_t
     if (w->P) SAME_FILL(ctx, p.gs.alive, 0, (size_t)w->P);
     SAME_COPY(ctx, p.match_pair, match_pair, (size_t)w->n_ua * 4, hipMemcpyHostToDevice);
     FinishPlan *pp = &p;
+    SAME_TRY(enqueue_refine(ctx, &pp, 1));          // the local search again, from the caller's matching
     SAME_TRY(enqueue_tail(ctx, &w, &pp, 1));
     char *h = static_cast<char *>(w->host) + w->host_finish_off;
     SAME_COPY(ctx, h, reinterpret_cast<const char *>(p.gs.sel), p.back_bytes, hipMemcpyDeviceToHost);
     SAME_WAIT(ctx);
+    SAME_TRY(settle(w, &p, false));
     const unsigned long long *cnt = reinterpret_cast<const unsigned long long *>(h + p.o_counters);
     for (int q = 0; q < 8; ++q) out_stats[q] = (int64_t)cnt[q];
     out_stats[SC_ROUNDS] = w->as_rounds;

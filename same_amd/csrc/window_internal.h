@@ -132,8 +132,10 @@ struct Cover {
 // counters of the filter: [0] kept (class 0), [1] added back, [2] cosines within `tol` of the threshold, [3] triangles left
 enum { FC_KEEP = 0, FC_ADD = 1, FC_NEAR = 2, FC_TR = 3, FC_TIES = 4, FC_COPIED = 5 };
 // counters of the finish call: [0] orientation checked, [1] flipped, [2] XY comparisons, [3] XY violations, [4] triangles with
-// one, [5] area flips, [6] (host) greedy rounds, [7] matched aligned cells, [8] pairs the greedy rule could still take
-enum { SC_CHECKED = 0, SC_FLIPPED = 1, SC_CMP = 2, SC_VIOL = 3, SC_TVIOL = 4, SC_AFLIP = 5, SC_ROUNDS = 6, SC_MATCHED = 7, SC_REMAINING = 8, SC_TIES = 9, SC_COUNT = 16 };
+// one, [5] area flips, [6] (host) greedy rounds, [7] matched aligned cells, [8] pairs the greedy rule could still take; from
+// SC_REFINE on the local search's control words (refine.h RC_*), which a second pass of the tail leaves as they are
+enum { SC_CHECKED = 0, SC_FLIPPED = 1, SC_CMP = 2, SC_VIOL = 3, SC_TVIOL = 4, SC_AFLIP = 5, SC_ROUNDS = 6, SC_MATCHED = 7, SC_REMAINING = 8, SC_TIES = 9,
+       SC_REFINE = 16, SC_COUNT = 32 };
 
 }  // namespace win
 
@@ -180,6 +182,11 @@ struct same_window {
     int incumbent = 0;                              // SAME_INCUMBENT_* (same_window_set_incumbent): what the finish call matches by
     int64_t as_rounds = 0, as_flags = 0;            // the last finish's optimal assignment: searches, flags (!= 0: not certified) ...
     double as_objective = 0.0;                      // ... and its objective
+    int64_t rf_cap = 0;                             // the local search (same_window_set_refine): round cap, 0 = off ...
+    double rf_dp = 0.0;                             // ... delaunay_penalty, and the last finish call's no-match penalty
+    double rf_nm = 0.0;
+    int64_t rf_rounds = 0, rf_moves = 0, rf_settled = 0;   // the last finish's search: productive rounds, moves, settled ...
+    double rf_obj0 = 0.0, rf_obj = 0.0;             // ... objective of its start and of its result
     // stage block
     unsigned long long *counts = nullptr;           // [8], first words of the block the stage call copies back
     int32_t *rows_m = nullptr, *rows_r = nullptr, *idx = nullptr, *cnt = nullptr, *ua = nullptr, *rows_ua = nullptr, *type_c = nullptr,

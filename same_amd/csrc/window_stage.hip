@@ -470,7 +470,7 @@ int prepare_stage(same_window *w, const same_section *mov, const same_section *r
     SAME_TRY(ensure(ctx, w->stage, cv.off));
     // everything the three calls of this window copy back fits the pinned block from now on (it must not move between them)
     w->host_finish_off = (back_bytes + 255) & ~size_t(255);
-    w->host_filter_off = w->host_finish_off + ((SAME_GREEDY_BATCH_MAX * 8 + 128 + (size_t)cap_m * 5 + 64 + 255) & ~size_t(255));
+    w->host_filter_off = w->host_finish_off + ((SAME_GREEDY_BATCH_MAX * 8 + SC_COUNT * 8 + (size_t)cap_m * 5 + 64 + 255) & ~size_t(255));
     SAME_TRY(ensure_host(w, w->host_filter_off + 256));
     char *base = static_cast<char *>(w->stage.p);
     auto at = [&](size_t off) { return base + off; };

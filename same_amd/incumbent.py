@@ -21,6 +21,16 @@ instead: the reference's Hungarian start (src/init_helpers.py:135-175) on its sp
 GPU (csrc/assign.hip).  It needs max_matches == 1 and every no-match cost below init_big_m / 2 (`incumbent_mode`).  With
 return_stats each window's stats then carry its `objective` and `fallback` (the device's certificate refused it; scipy answered).
 
+optim_params["hip_refine"] = "local" (opt-in; without the key or with None nothing changes) runs a local search on the GPU after
+either incumbent and before the sweeps (csrc/refine.hip).  It lowers each window's full lazy-model objective
+(src/same.py:1191-1196): pair costs + no_match_penalty * size per unmatched cell + delaunay_penalty * the size sum of every kept triangle
+the lazy body (:645-669) sees flip.  Moves: a cell to a free candidate reference, to or from unmatched, two cells swapping references;
+rounds of non-overlapping best moves until a round has none or optim_params["hip_refine_rounds"] (default 32) is reached.  The matching
+stays one-to-one like both starts, so penalty_coeff's p_j stay 0: with max_matches > 1 the result is still a feasible solution of the
+model, one that leaves reference capacity unused.  The table, `flipped` and the flag columns describe the refined matching; with
+return_stats each window's stats gain `mip_objective_start`, `mip_objective` (the model's objective before and after), `refine_rounds`,
+`refine_moves` and `refine_settled` (0: stopped at the round cap); `objective` stays the assignment's.
+
 Two routes produce the same table (tests/test_gpu_run_same.py::test_incumbent_table_routes_agree):
   device   both frames resident on the GPU, two library calls per window, the incumbent and the sweeps computed where the pairs are
            (csrc/window_stage.hip, csrc/window_finish.hip); the host triangulates, receives (match, flags) per window and gathers
@@ -71,6 +81,32 @@ def incumbent_mode(optim_params, gurobi_params=None, moving=None):
             raise ValueError(f"hip_incumbent='assignment': a no-match cost no_match_penalty * size ({np.nanmax(worst):g}) is not below "
                              f"init_big_m / 2 ({big_m / 2:g}); the sparse problem would differ from the reference's big-M one")
     return mode
+
+
+REFINES = ("local",)                           # optim_params["hip_refine"]; None without the key
+REFINE_ROUNDS = 32                             # optim_params["hip_refine_rounds"] without the key
+
+
+def refine_mode(optim_params):
+    """optim_params["hip_refine"] / ["hip_refine_rounds"] / ["delaunay_penalty"] checked before anything reaches a device -> None (no
+    search) or (rounds_cap, delaunay_penalty)"""
+    import numbers
+
+    from .params import init_optim_params
+
+    op = dict(optim_params or {})
+    mode = op.get("hip_refine")
+    if mode is None:
+        return None
+    if not isinstance(mode, str) or mode not in REFINES:
+        raise ValueError(f"optim_params['hip_refine'] must be None or one of {REFINES}, not {mode!r}")
+    cap = op.get("hip_refine_rounds", REFINE_ROUNDS)
+    if isinstance(cap, bool) or not isinstance(cap, numbers.Integral) or cap < 1:
+        raise ValueError(f"optim_params['hip_refine_rounds'] must be a positive int, not {cap!r}")
+    dp = init_optim_params(**op)["delaunay_penalty"]
+    if isinstance(dp, bool) or not isinstance(dp, numbers.Real) or not np.isfinite(float(dp)) or float(dp) < 0:
+        raise ValueError(f"optim_params['delaunay_penalty'] must be finite and >= 0 for hip_refine, not {dp!r}")
+    return int(cap), float(dp)
 
 
 def _default_workers():
@@ -274,13 +310,15 @@ class _TableBuilder:
         return pd.DataFrame(out, copy=False)
 
 
-def incumbent_of_prepared(prep, commonCT, with_ref_idx=True, ctx=None, use_device=True, incumbent="greedy"):
+def incumbent_of_prepared(prep, commonCT, with_ref_idx=True, ctx=None, use_device=True, incumbent="greedy", refine=None):
     """(match table of ONE window as run_same's post-solve builds it, stats) from its pre-MIP artefacts, through the host-buffer entry
     points: greedy start -> matching -> lazy-constraint body, XY-order sweep, area flips.  The general route of this module.
     use_device: a PreparedInputs made by the device-resident window path with its pair list untouched carries the incumbent and the
     sweeps already (computed where the pairs are, by same_window_filter_finish): take them instead of computing them again.
     incumbent="assignment": the optimal one-to-one assignment (ops.sparse_assign) instead of the greedy start; the stats then carry the
-    window's "objective" and whether it fell back to the host solver ("fallback")."""
+    window's "objective" and whether it fell back to the host solver ("fallback").
+    refine=(rounds_cap, delaunay_penalty): the local search on the lazy model's objective (ops.refine_matching) from the incumbent
+    before the sweeps; the stats then carry mip_objective_start, mip_objective, refine_rounds, refine_moves, refine_settled."""
     op = prep.optim_params
     dw = getattr(prep, "device", None)
     if use_device and dw is not None and dw.match_row is not None and isinstance(prep.valid_pairs, np.ndarray):
@@ -296,12 +334,16 @@ def incumbent_of_prepared(prep, commonCT, with_ref_idx=True, ctx=None, use_devic
     else:
         wants = ops.pair_rowmin(pairs, costs, n_a, ctx=ctx) < float(op["no_match_penalty"]) * size     # src/init_helpers.py:104,118-122
         pair_of_row, _rounds = ops.greedy_match(pairs, costs, n_a, n_r, wants, ctx=ctx)
+    axy, rxy = a_df[["X", "Y"]].to_numpy(dtype=np.float64), r_df[["X", "Y"]].to_numpy(dtype=np.float64)
+    t32 = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
+    if refine is not None:
+        pair_of_row, rst = ops.refine_matching(pairs, costs, float(op["no_match_penalty"]) * size, n_a, n_r, t32, axy, rxy, size,
+                                               refine[1], refine[0], pair_of_row, ctx=ctx)
+        extra.update(_refine_stats(rst))
     ai = np.flatnonzero(pair_of_row >= 0)
     ri = pairs[pair_of_row[ai], 1].astype(np.int64)
     match = np.full(n_a, -1, np.int32)
     match[ai] = ri
-    axy, rxy = a_df[["X", "Y"]].to_numpy(dtype=np.float64), r_df[["X", "Y"]].to_numpy(dtype=np.float64)
-    t32 = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
     sw = ops.BoundSweep(t32, prep.signs_array.astype(np.int8), rxy, n_a, ctx=ctx)
     try:
         checked, viol = sw.sweep_match(match)
@@ -361,6 +403,12 @@ def _table_of_device_window(prep, dw, commonCT, with_ref_idx):
                         dw.flip_flag[ai], dw.point_flag[ai]), stats
 
 
+def _refine_stats(rst):
+    """the local search's keys of a window's stats record"""
+    return {"mip_objective_start": rst["objective_start"], "mip_objective": rst["objective"], "refine_rounds": rst["rounds"],
+            "refine_moves": rst["moves"], "refine_settled": rst["settled"]}
+
+
 def _device_stats(dw):
     """a window's stats record (STAT_KEYS) from what the device counted"""
     st = dw.stats
@@ -368,6 +416,8 @@ def _device_stats(dw):
            "xy_violations": st["xy_violations"], "area_flips": st["area_flips"], "matched": st["matched"]}
     if dw.assignment is not None:
         rec["objective"], rec["fallback"] = dw.assignment["objective"], dw.assignment["fallback"]
+    if dw.refine is not None:
+        rec.update(_refine_stats(dw.refine))
     return rec
 
 
@@ -399,9 +449,11 @@ def sliding_window_incumbent(ref, moving, commonCT=None, outprefix=None, moving_
     get their columns.  With `_shard` and a `_merge_channel` (dist.MergeChannel) the result is this rank's PART of the merged table
     (dist.sharded_merged_window_incumbent)."""
     mode = incumbent_mode(optim_params, gurobi_params, moving)
+    refine = refine_mode(optim_params)
     job = _WindowJob(ref, moving, commonCT, outprefix, moving_delaunay, moving_delaunay_vertex_col, optim_params, gurobi_params,
                      ignore_precomputed_triangulation, _shard)
     job.incumbent = mode
+    job.refine = refine
     frames, own = job.device_frames(_pipeline, ctx=ctx)
     fast = frames is not None and not job.caller_triangulation and not job.optim_params["ignore_knn_if_matched"]
     if _route is not None:
@@ -489,7 +541,8 @@ def _device_route(job, frames, workers, with_ref_idx, triangulator, stats, merge
             collector = lambda states, windows: accs[q].collect(states, [w["trim"] for w in windows], [w["window_id"] for w in windows],
                                                                 [pos_of[id(w)] for w in windows])
         for (pos, w), dw in zip(mine, frames.windows([w for _p, w in mine], ctx=contexts[q], triangulator=triangulator,
-                                                     collector=collector, batch=batch, incumbent=job.incumbent)):
+                                                     collector=collector, batch=batch, incumbent=job.incumbent,
+                                                     refine=job.refine)):
             if dw.error is not None:
                 raise dw.error
             with stage("table rows (central trim)"):
@@ -654,7 +707,7 @@ def _general_route(job, frames, with_ref_idx, stats, ctx):
                 continue
             with stage("incumbent + sweeps + table (general route)"):
                 window_matches, stats[pos] = incumbent_of_prepared(prep, commonCT, with_ref_idx, ctx=ctx, use_device=False,
-                                                                         incumbent=job.incumbent)
+                                                                         incumbent=job.incumbent, refine=job.refine)
             job.collect(pos, w, window_matches)
     finally:
         job.outprefix = keep_csv

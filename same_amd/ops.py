@@ -363,6 +363,31 @@ def assign_objective(match_pair, costs, unmatched):
     return float(np.sum(costs[match_pair[m]]) + np.sum(unmatched[~m]))
 
 
+def refine_matching(pairs, costs, unmatched, n_aligned, n_ref, triangles, axy, ref_xy, size, delaunay_penalty, rounds_cap, match_pair,
+                    ctx=None):
+    """The local search of csrc/refine.hip on host buffers (same_refine_matching): from the one-to-one `match_pair` (pair index per
+    aligned cell, -1 = none), moves that lower the lazy model's objective (src/same.py:1191-1196) -- pair costs + unmatched[i] per
+    unmatched cell + delaunay_penalty * the size sum of every kept triangle the lazy body (:645-669) sees flip -- for at most
+    `rounds_cap` rounds.  -> (match_pair (n_aligned,) int32, stats {"rounds", "moves", "settled", "objective_start", "objective"}).
+    tests/refine_check.py states the same rule on the host."""
+    ctx = _ctx(ctx)
+    pairs, costs, unmatched = as_c(pairs, I32).reshape(-1, 2), as_c(costs, F64), as_c(unmatched, F64)
+    tris, axy, ref_xy, size = _tris(triangles), as_c(axy, F64).reshape(-1, 2), as_c(ref_xy, F64).reshape(-1, 2), as_c(size, F64)
+    n_aligned, n_ref = int(n_aligned), int(n_ref)
+    assert len(costs) == len(pairs) and len(unmatched) == n_aligned == len(axy) == len(size) and len(ref_xy) == n_ref
+    out = np.array(match_pair, dtype=I32, copy=True).reshape(-1)
+    assert len(out) == n_aligned
+    st = np.zeros(5, I64)
+    with ctx.lock:
+        ctx.check(ctx.lib.same_refine_matching(ctx.handle, pairs.ctypes.data, costs.ctypes.data, len(pairs), unmatched.ctypes.data,
+                                               n_aligned, n_ref, tris.ctypes.data, len(tris), axy.ctypes.data, ref_xy.ctypes.data,
+                                               size.ctypes.data, float(delaunay_penalty), int(rounds_cap), out.ctypes.data,
+                                               st.ctypes.data), "same_refine_matching")
+    obj = st[3:5].view(F64)
+    return out, {"rounds": int(st[0]), "moves": int(st[1]), "settled": int(st[2]), "objective_start": float(obj[0]),
+                 "objective": float(obj[1])}
+
+
 def tri_flip_stats(axy, mapped_xy, matched, triangles, type_id=None, ctx=None):
     """-> (tri_flag (Tr,) uint8 [bit0 matched, bit1 same type, bit2 flipped], node_tri, node_flip (n,) uint32)."""
     ctx = _ctx(ctx)

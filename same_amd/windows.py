@@ -482,6 +482,24 @@ class DeviceWindow:
                                                                      ctypes.byref(obj)), "same_window_incumbent_result")
         return rounds.value, flags.value, obj.value
 
+    def set_refine(self, refine):
+        """what the finish calls do after the incumbent from now on: `refine` = (rounds_cap, delaunay_penalty) runs the local search on
+        the lazy model's objective (csrc/refine.hip) for at most rounds_cap rounds; None runs none"""
+        cap, dp = (0, 0.0) if refine is None else (int(refine[0]), float(refine[1]))
+        with self.ctx.lock:
+            self.ctx.check(self.ctx.lib.same_window_set_refine(self.handle, cap, dp), "same_window_set_refine")
+
+    def refine_result(self):
+        """after a finish call with the local search on -> {"rounds", "moves", "settled", "objective_start", "objective"}"""
+        import ctypes
+
+        r, m, s = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        o0, o = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        with self.ctx.lock:
+            self.ctx.check(self.ctx.lib.same_window_refine_result(self.handle, ctypes.byref(r), ctypes.byref(m), ctypes.byref(s),
+                                                                  ctypes.byref(o0), ctypes.byref(o)), "same_window_refine_result")
+        return {"rounds": r.value, "moves": m.value, "settled": s.value, "objective_start": o0.value, "objective": o.value}
+
     def refinish(self, match_pair):
         """the finished window's matched rows and sweeps again under `match_pair` (pair index per kept cell, -1 = none) -> (match_row,
         flag byte, stats dict) as `finish`"""
@@ -842,10 +860,11 @@ class DeviceWindowResult:
     `match_row` the section row of each cell's matched reference cell (-1 = none), `point_flag` the XY-order sweep's per-cell flag,
     `flip_flag` 1 for the vertices of triangles whose signed area flips, `stats` the sweeps' counters, `counts` (aligned in box, refs in
     box, kept, pairs); `state` is the live DeviceWindow until the generator is asked for the first window of the next batch (pairs,
-    costs, signs ... through `state.fetch`).  `assignment` (incumbent="assignment" only): {"objective", "fallback", "rounds"}."""
+    costs, signs ... through `state.fetch`).  `assignment` (incumbent="assignment" only): {"objective", "fallback", "rounds"}.
+    `refine` (refine given only): DeviceWindow.refine_result() of the window's final finish."""
 
     __slots__ = ("window", "error", "rows_m", "axy", "triangles", "n_triangles", "match_row", "point_flag", "flip_flag", "stats",
-                 "counts", "state", "assignment")
+                 "counts", "state", "assignment", "refine")
 
     def __init__(self, window):
         self.window = window
@@ -884,7 +903,7 @@ class TriangulationCache(QhullTriangulator):
 
 def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dist_ct_coeff=1.0, min_angle_deg=15,
                         ignore_same_type_triangles=True, no_match_penalty=100.0, ctx=None, fetch_triangles=False, triangulator=None,
-                        triangulate=True, batch=None, collector=None, incumbent="greedy"):
+                        triangulate=True, batch=None, collector=None, incumbent="greedy", refine=None):
     """The window path of `iter_window_arrays` + the greedy incumbent and the three sweeps, with both sections resident on the
     device (`dref`, `dmoving`: DeviceSections of `ref`, `moving`): per window the host only triangulates (Qhull helpers, windows
     ahead as before) and receives the match; the triangle filter runs on the device too, unless a cosine sits within 8 ulp of the
@@ -904,7 +923,10 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
     MergeAccumulator.collect).
     `incumbent`: "greedy" (src/init_helpers.py:104-133) or "assignment" -- the optimal one-to-one assignment of the window's kept cells
     under the pair costs with a no-match column per cell (csrc/assign.hip); a window whose answer the device does not certify is solved
-    again on the host (ops.sparse_assign_host) and finished again under that matching."""
+    again on the host (ops.sparse_assign_host) and finished again under that matching.
+    `refine` = (rounds_cap, delaunay_penalty): the local search on the lazy model's objective runs on every window's incumbent before the
+    sweeps (csrc/refine.hip; every later finish of the window -- greedy rounds added, the assignment's fallback, a re-finish with scipy's
+    simplices -- runs it again); the match, flags and stats are then the search's, and `result.refine` holds its counts."""
     import os
     from collections import deque
 
@@ -984,6 +1006,7 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
         states, tickets = [st for _o, st, _t in todo], [t for _o, _s, t in todo]
         for state in states:
             state.set_incumbent(incumbent)
+            state.set_refine(refine)
         tri.before_finish(states, tickets, radius, angle_enabled, cos_thr)
         with marked("triangulate (wait for helper)"):
             tris = [ticket.result() for ticket in tickets]
@@ -1016,6 +1039,8 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
             if incumbent == "assignment":
                 match_row, cell_flags, stats, out.assignment = _assignment_result(state, out, moving, no_match_penalty, match_row,
                                                                                   cell_flags, stats)
+            if refine is not None:
+                out.refine = state.refine_result()
             out.match_row, out.stats = match_row, stats
             # the library packs both per-cell flags into one byte
             out.point_flag, out.flip_flag = cell_flags & 1, (cell_flags >> 1) & 1

@@ -90,7 +90,8 @@ int main(void) {
     if (mkept != 4 || mrows[0] != 3 || mrows[1] != 2 || mrows[2] != 1 || mrows[3] != 4) return 4;
     /* the same instance as ONE window with both sections resident on the device (src/same.py:507-593 per window): subsetting, prune,
      * costs and compaction in same_window_stage; the four triangles above play the Delaunay simplices of the kept aligned cells for
-     * same_window_filter_finish (radius 30, no angle rule, no type rule; then the greedy MIP start and the three sweeps).  Both calls
+     * same_window_filter_finish (SAME_TRIS_SIMPLICES, radius 30, no angle rule, no type rule; then the greedy MIP start, no local
+     * search, and the three sweeps).  Both calls
      * take a BATCH of windows: here a batch of one */
     double size[NM > NR ? NM : NR];
     for (int i = 0; i < (NM > NR ? NM : NR); ++i) size[i] = 1.0;
@@ -102,7 +103,7 @@ int main(void) {
     CHECK(same_window_create(ctx, &win_b));
     const double box[4] = {-100.0, 100.0, -100.0, 100.0};
     const int64_t one_window[2] = {0, 4};          /* simplex offsets: window 0 owns triangles [0, 4) */
-    int64_t wc[4], fc[4], st[8];
+    int64_t wc[4], fc[4], st[SAME_WINDOW_STATS];
     CHECK(same_window_stage(&win, 1, smov, sref, box, 12.0, K, 1.0, wc));
     double wcost[NM * K];
     CHECK(same_window_fetch(win, SAME_WINDOW_COSTS, wcost, wc[3] * (int64_t)sizeof(double)));
@@ -110,7 +111,8 @@ int main(void) {
     for (int p = 0; same_costs && p < P; ++p) same_costs = wcost[p] == cost[p];
     int32_t mrow[NM];
     uint8_t pflag[NM];
-    CHECK(same_window_filter_finish(&win, 1, tris, one_window, 0, 30.0, 0, 0.0, 0.0, 0, 1, 100.0, mrow, pflag, st, fc));
+    CHECK(same_window_filter_finish(&win, 1, SAME_TRIS_SIMPLICES, tris, one_window, 30.0, 0, 0.0, 0.0, 0, 1, 100.0, SAME_INCUMBENT_GREEDY, 0,
+                                    0.0, mrow, pflag, st, fc));
     printf("window: %lld aligned, %lld ref, %lld kept, %lld pairs (costs %s the pair list's); %lld of 4 triangles kept; matched ref rows:",
            (long long)wc[0], (long long)wc[1], (long long)wc[2], (long long)wc[3], same_costs ? "equal" : "DIFFER FROM", (long long)fc[0]);
     for (int i = 0; i < wc[2]; ++i) printf(" %d", mrow[i]);
@@ -139,18 +141,19 @@ int main(void) {
     const int64_t two_windows[3] = {0, 4, 8};
     int32_t tris2[24];
     for (int q = 0; q < 24; ++q) tris2[q] = tris[q % 12];
-    int64_t c0[4], c1[4], wc2[8], fc2[8], st2[16];
+    int64_t c0[4], c1[4], wc2[8], fc2[8], st2[2 * SAME_WINDOW_STATS];
     int32_t mrow2[2 * NM];
     uint8_t pflag2[2 * NM];
     for (int q = 0; q < 4; ++q) CHECK(same_ctx_stat(ctx, q, &c0[q]));
     CHECK(same_window_stage(pair, 2, smov, sref, boxes2, 12.0, K, 1.0, wc2));
-    CHECK(same_window_filter_finish(pair, 2, tris2, two_windows, 0, 30.0, 0, 0.0, 0.0, 0, 1, 100.0, mrow2, pflag2, st2, fc2));
+    CHECK(same_window_filter_finish(pair, 2, SAME_TRIS_SIMPLICES, tris2, two_windows, 30.0, 0, 0.0, 0.0, 0, 1, 100.0, SAME_INCUMBENT_GREEDY,
+                                    0, 0.0, mrow2, pflag2, st2, fc2));
     for (int q = 0; q < 4; ++q) CHECK(same_ctx_stat(ctx, q, &c1[q]));
     int same_window = 1;
     for (int b = 0; b < 2; ++b) {
         same_window = same_window && fc2[4 * b] == fc[0] && fc2[4 * b + 1] == fc[1];
         for (int q = 0; q < 4; ++q) same_window = same_window && wc2[4 * b + q] == wc[q];
-        for (int q = 0; q < 8; ++q) same_window = same_window && st2[8 * b + q] == st[q];
+        for (int q = 0; q < SAME_WINDOW_STATS; ++q) same_window = same_window && st2[SAME_WINDOW_STATS * b + q] == st[q];
         for (int i = 0; i < wc[2]; ++i) same_window = same_window && mrow2[b * wc[2] + i] == mrow[i] && pflag2[b * wc[2] + i] == pflag[i];
     }
     printf("the window twice in one batch (binned sections): %s; %lld launches, %lld fills, %lld copies, %lld waits for the two\n",

@@ -43,7 +43,7 @@ extern "C" {
 #define SAME_ERANGE (-34)   /* an index in pairs/triangles/match is out of range */
 #define SAME_EUNSURE (-11)  /* same_delaunay2d only: not an error -- the points are too close to degenerate to answer for Qhull */
 
-#define SAME_ABI_VERSION 8
+#define SAME_ABI_VERSION 9
 #define SAME_MAX_KNN 448     /* largest k supported by the prune kernel (k <= 64 runs the 8-rows-per-wave form) */
 #define SAME_MAX_TYPES 4096  /* largest T (type columns) */
 
@@ -364,25 +364,37 @@ int same_first_candidate_dev(same_ctx *ctx, const int32_t *didx, int64_t rows, i
  *     per group of eight one zeroing launch, at most five kernels and one launch that writes what comes back into the windows' pinned
  *     blocks, reading O(rows of the covered cells); ONE wait for the whole batch.  The windows of a batch belong to one context and
  *     are distinct; n_windows <= SAME_WINDOW_BATCH_MAX.  If any window is refused nothing of the batch counts.
- *   same_window_filter_finish: for each window of the batch, the Delaunay simplices of its kept aligned cells (window i:
- *     simplices[3 simplex_offsets[i] .. 3 simplex_offsets[i+1]), offsets[0] = 0) ->
+ *   same_window_filter_finish: for each window of the batch, the Delaunay simplices of its kept aligned cells, from `source`:
+ *     SAME_TRIS_SIMPLICES the caller's host array (window i: simplices[3 simplex_offsets[i] .. 3 simplex_offsets[i+1]), offsets[0] = 0);
+ *     SAME_TRIS_KEPT the same array holding the KEPT triangles in the reference's order (a caller's own triangulation; the knife-edge
+ *     fallback below): no filter, the filter arguments are ignored; SAME_TRIS_DEVICE the candidates same_window_delaunay left on the
+ *     device for each window (every window must have been answered by it since it was staged): no host array, no upload -- the classes,
+ *     the keep list and the same-type re-add are decided by the filter's own kernels, with the reference's arithmetic, and out_counts'
+ *     near and ORDER TIES mean what they mean there.  NULL simplices and simplex_offsets go with SAME_TRIS_DEVICE and only with it ->
  *     - filter_triangles_by_radius on the device (src/helpers.py:233-395: classes :300-330, the keep list, the same-type triangles
  *       added back so that every node keeps one :331-340 / :365-389, in the reference's order); the section's type_id codes play
  *       aligned_df["cell_type"].  Simplices must be distinct as vertex rows (Qhull's are): the re-add pass de-duplicates by triangle,
- *       the reference by vertex row.  prefiltered != 0 skips this step: the rows passed ARE the kept triangles, in the reference's
- *       order (a caller's own triangulation; the knife-edge fallback below), and the filter arguments are ignored;
- *     - source signs / weights (src/same.py:1128-1146), greedy MIP start with prefer = rowmin < no_match_penalty * size
- *       (src/init_helpers.py:104-133), lazy-constraint body (src/same.py:645-669), XY-order sweep (src/violationhelper.py:53-117),
- *       area flips (src/same.py:1362-1402).
+ *       the reference by vertex row;
+ *     - source signs / weights (src/same.py:1128-1146); the incumbent: SAME_INCUMBENT_GREEDY the greedy MIP start with prefer = rowmin
+ *       < no_match_penalty * size (src/init_helpers.py:104-133), SAME_INCUMBENT_ASSIGNMENT the optimal assignment (same_sparse_assign
+ *       below; no_match cost = no_match_penalty * size, the fp64 product of the greedy rule);
+ *     - refine_rounds_cap > 0: the local search on the lazy model's objective from the incumbent (same_refine_matching below), at most
+ *       that many rounds, with delaunay_penalty (finite, >= 0); the matched rows, flags and sweeps then describe the search's result,
+ *       the assignment's words keep describing the assignment.  0: no search;
+ *     - lazy-constraint body (src/same.py:645-669), XY-order sweep (src/violationhelper.py:53-117), area flips (src/same.py:1362-1402).
+ *     A bad source, mode, cap or penalty is SAME_EINVAL before any device work.
  *     Outputs are laid end to end in window order: out_match_row / out_point_flag hold kept[0] + kept[1] + ... entries (kept = the
  *     stage call's out_counts[4 i + 2]); out_match_row = SECTION row of the matched reference cell or -1; out_point_flag = per-cell
  *     flag byte: bit 0 the XY-order sweep flags the cell (src/violationhelper.py:100-104), bit 1 the cell is a vertex of a triangle
- *     whose signed area flips (src/same.py:1464-1469); out_stats[8 i ..] = {orientation checked, flipped, XY comparisons, XY
- *     violations, triangles with a violation, area flips, greedy rounds, matched cells}; out_counts[4 i ..] = {kept, added back,
- *     cosines within near_tol of cos_thr, order ties} (prefiltered: {n, 0, 0, order ties}).  When a window's third count is not zero
+ *     whose signed area flips (src/same.py:1464-1469); out_stats[SAME_WINDOW_STATS i ..] = {orientation checked, flipped, XY
+ *     comparisons, XY violations, triangles with a violation, area flips, greedy rounds (assignment: its searches), matched cells; the
+ *     assignment's flags (!= 0: not certified, the matching must not be used) and objective; the search's productive rounds, moves
+ *     applied, settled (1: a round found no improving move; 0: stopped at the cap), objective of its start and of its result}, the
+ *     objectives as the bits of a double, the words of a mode that is off 0; out_counts[4 i ..] = {kept, added back, cosines within
+ *     near_tol of cos_thr, order ties} (SAME_TRIS_KEPT: {n, 0, 0, order ties}).  When a window's third count is not zero
  *     nothing of that window counts (its slices of the outputs mean nothing, no triangles are left on the device): the caller
  *     re-decides its triangles with the reference's literal arccos (same_amd/triangles.py) and calls again for that window with
- *     prefiltered = 1.  ORDER TIES (ABI 8) count the places where the reference's answer depends on the order in which the
+ *     SAME_TRIS_KEPT.  ORDER TIES (ABI 8) count the places where the reference's answer depends on the order in which the
  *     triangulation lists its triangles or their corners, beyond which triangles there are: an edge of the XY-order sweep whose
  *     ends share an x or a y (`<` is not symmetric, src/violationhelper.py:68-75), a signed area or orientation within rounding of
  *     zero (src/same.py:1401, :658), two same-type triangles of one node whose perimeters agree to the rounding of a three-term
@@ -390,10 +402,17 @@ int same_first_candidate_dev(same_ctx *ctx, const int32_t *didx, int64_t rows, i
  *     triangulates otherwise (same_delaunay2d: same triangles, another order) asks Qhull for a window whose count is not zero.  The call's
  *     simplices go up in ONE copy; per group of eight windows one zeroing launch, 14 kernels (17 with fp64 costs) and one launch
  *     that writes the answers into the pinned blocks; ONE wait for the batch (more greedy rounds, in batches with a wait each, only
- *     for a window in which a pair could still be taken after the rounds enqueued up front).
+ *     for a window in which a pair could still be taken after the rounds enqueued up front; the search, when it still moves after its
+ *     first rounds, in growing chunks with a wait each).
+ *   same_window_refinish: a finished window's tail again (matched rows, the three sweeps, stats) under the caller's match_pair[n kept]
+ *     (pair index per kept cell, -1 = none), the search from it when refine_rounds_cap > 0: how the caller replaces a flagged window's
+ *     assignment.  It reads the window's staged arrays and kept triangles, no earlier call's options.  out_stats[SAME_WINDOW_STATS] as
+ *     above (greedy rounds and the assignment's words 0).  One wait unless the search still moves.
  * same_window_fetch copies one array of the window's state to the host; bytes must be the array's exact size.
  * (Since ABI 6 same_window_stage / same_window_filter_finish take batches; same_window_filter and same_window_finish of ABI 5 are gone --
- * the former is the latter's first half, the latter is prefiltered = 1.) */
+ * the former is the latter's first half, the latter is prefiltered = 1.  Since ABI 9 the finish call takes its source, incumbent and
+ * search as arguments and answers with their records in the wider stats; gone with ABI 8, replaced by the source, the arguments and the
+ * stats words: same_window_filter_finish_device, same_window_set_incumbent / _incumbent_result / _set_refine / _refine_result.) */
 #define SAME_WINDOW_BATCH_MAX 64
 typedef struct same_section same_section;
 typedef struct same_window same_window;
@@ -419,10 +438,19 @@ void same_window_destroy(same_window *window);
 int same_window_stage(same_window *const *windows, int n_windows, const same_section *moving, const same_section *ref,
                       const double *boxes, double radius, int k, double dist_ct_coeff, int64_t *out_counts);
 int same_window_fetch(same_window *window, int what, void *out, int64_t bytes);
-int same_window_filter_finish(same_window *const *windows, int n_windows, const int32_t *simplices, const int64_t *simplex_offsets,
-                              int prefiltered, double radius, int angle_enabled, double cos_thr, double near_tol, int ignore_same_type,
-                              int ensure_min_triangle_per_node, double no_match_penalty, int32_t *out_match_row,
-                              uint8_t *out_point_flag, int64_t *out_stats, int64_t *out_counts);
+#define SAME_TRIS_SIMPLICES 0   /* host simplices, filtered on the device */
+#define SAME_TRIS_KEPT 1        /* host kept triangles in the reference's order */
+#define SAME_TRIS_DEVICE 2      /* the candidates same_window_delaunay left; simplices and simplex_offsets must be NULL */
+#define SAME_INCUMBENT_GREEDY 0
+#define SAME_INCUMBENT_ASSIGNMENT 1
+#define SAME_WINDOW_STATS 15    /* int64 words per window in out_stats */
+int same_window_filter_finish(same_window *const *windows, int n_windows, int source, const int32_t *simplices,
+                              const int64_t *simplex_offsets, double radius, int angle_enabled, double cos_thr, double near_tol,
+                              int ignore_same_type, int ensure_min_triangle_per_node, double no_match_penalty,
+                              int incumbent /* SAME_INCUMBENT_* */, int64_t refine_rounds_cap /* 0 = no search */, double delaunay_penalty,
+                              int32_t *out_match_row, uint8_t *out_point_flag, int64_t *out_stats, int64_t *out_counts);
+int same_window_refinish(same_window *window, const int32_t *match_pair, double no_match_penalty, int64_t refine_rounds_cap,
+                         double delaunay_penalty, int32_t *out_match_row, uint8_t *out_point_flag, int64_t *out_stats);
 
 /* ---- a6 on the window path without the library call --------------------------------------------------------------------------
  * The reference triangulates every window's kept aligned cells with scipy.spatial.Delaunay (Qhull; src/same.py:1023), on the host
@@ -453,11 +481,8 @@ int same_delaunay2d(const double *xy, int64_t n, int32_t *out_tris, int64_t cap,
  *   same_window_delaunay: for each staged window of the batch (up to eight per launch, nine launches per group, ONE wait for the batch),
  *     the candidates over its kept aligned cells (SAME_WINDOW_ALIGNED_XY), left on the device.  out_status[i] = 0 (answered; out_n_tris[i]
  *     candidates) or a mask of SAME_DD_* reasons (refused: the caller asks Qhull, as the reference does).  A window's candidates stay valid
- *     until it is staged again.  cos_thr / angle_enabled as for same_window_filter_finish.
- *   same_window_filter_finish_device: same_window_filter_finish (prefiltered = 0) over every window's device-made candidates -- no host
- *     array, no upload: the classes, the keep list and the same-type re-add are decided by the filter's own kernels, with the reference's
- *     arithmetic, and out_counts' near and ORDER TIES are what they mean there (a caller re-finishes a window whose count is not zero with
- *     Qhull's simplices).  Every window must have been answered by same_window_delaunay since it was staged.
+ *     until it is staged again; same_window_filter_finish takes them as SAME_TRIS_DEVICE (a caller re-finishes a window whose ORDER TIES
+ *     count is not zero with Qhull's simplices).  cos_thr / angle_enabled as for same_window_filter_finish.
  *   same_delaunay_filtered: the same triangulation for a caller's host array of n points (xy interleaved): *out_status as above;
  *     answered: *out_n_tris triangles in out_tris (room for `cap`; 2 n always suffices).  SAME_EINVAL if cap is too small. */
 #define SAME_DD_FEW_POINTS 1   /* fewer than 3 points */
@@ -467,9 +492,6 @@ int same_delaunay2d(const double *xy, int64_t n, int32_t *out_tris, int64_t cap,
 #define SAME_DD_OVERFLOW 16    /* a neighbour, candidate, hull or grid list longer than its buffer */
 int same_window_delaunay(same_window *const *windows, int n_windows, double radius, int angle_enabled, double cos_thr, double guard,
                          int32_t *out_status, int64_t *out_n_tris);
-int same_window_filter_finish_device(same_window *const *windows, int n_windows, double radius, int angle_enabled, double cos_thr,
-                                     double near_tol, int ignore_same_type, int ensure_min_triangle_per_node, double no_match_penalty,
-                                     int32_t *out_match_row, uint8_t *out_point_flag, int64_t *out_stats, int64_t *out_counts);
 int same_delaunay_filtered(same_ctx *ctx, const double *xy, int64_t n, double radius, int angle_enabled, double cos_thr, double guard,
                            int32_t *out_tris, int64_t cap, int64_t *out_n_tris, int32_t *out_status);
 
@@ -485,20 +507,9 @@ int same_delaunay_filtered(same_ctx *ctx, const double *xy, int64_t n, double ra
  *   same_sparse_assign: host buffers.  pairs[P][2] = (row < n_m, column < n_r), each (row, column) at most once; unmatched[n_m] the
  *     no-match costs.  out_match_pair[i] = index of row i's pair, -1 = unmatched.  out_stats[4] = {searches, columns finalized, flags
  *     (!= 0: not certified, the matching must not be used), objective as the bits of a double}.  One wait.
- *   same_window_set_incumbent: what same_window_filter_finish / _device match a window by from its next call on:
- *     SAME_INCUMBENT_GREEDY (the default: src/init_helpers.py:104-133) or SAME_INCUMBENT_ASSIGNMENT (no_match cost = no_match_penalty *
- *     size, the fp64 product of the greedy rule; stats slot 6 then counts the searches, not greedy rounds).
- *   same_window_incumbent_result: after a finish call in assignment mode, its searches, flags and objective (0 otherwise).
- *   same_window_refinish: a finished window's tail again (matched rows, the three sweeps, stats) under the caller's match_pair[n kept]
- *     (pair index per kept cell, -1 = none): how the caller replaces a flagged window's assignment.  One wait. */
-#define SAME_INCUMBENT_GREEDY 0
-#define SAME_INCUMBENT_ASSIGNMENT 1
+ *   On the window path: same_window_filter_finish with SAME_INCUMBENT_ASSIGNMENT; same_window_refinish replaces a flagged window's. */
 int same_sparse_assign(same_ctx *ctx, const int32_t *pairs, const double *costs, int64_t P, const double *unmatched, int64_t n_m,
                        int64_t n_r, int32_t *out_match_pair, int64_t *out_stats);
-int same_window_set_incumbent(same_window *window, int mode);
-int same_window_incumbent_result(same_window *window, int64_t *out_rounds, int64_t *out_flags, double *out_objective);
-int same_window_refinish(same_window *window, const int32_t *match_pair, int32_t *out_match_row, uint8_t *out_point_flag,
-                         int64_t *out_stats);
 
 /* ---- the local search on the lazy model's objective (csrc/refine.hip): from a window's one-to-one incumbent, moves that lower
  *   sum_p c_p x_p + no_match_penalty sum_i size_i n_i + delaunay_penalty sum_t w_t q_t        (src/same.py:1191-1196; p_j = 0)
@@ -507,18 +518,11 @@ int same_window_refinish(same_window *window, const int32_t *match_pair, int32_t
  * unmatched, two matched cells swapping references (both crossed pairs candidates).  Rounds: every cell proposes its best improving
  * move (delta < -2^-40 scale); moves whose footprints (closed 1-rings of the moved cells + the references taken) do not meet apply
  * together, by a minimum key; a round without a move settles the search.  The result depends on the triangle SET only, not on its order.
- *   same_window_set_refine: what the finish calls (and same_window_refinish) do after the incumbent from the next call on: rounds_cap
- *     rounds at most (0 = no search, the default), delaunay_penalty finite and >= 0.  The sweeps, matched rows and flags then describe
- *     the search's result; the incumbent's own statistics (same_window_incumbent_result) keep describing the incumbent.
- *   same_window_refine_result: after a finish call with the search on: productive rounds, moves applied, settled (1: a round found no
- *     improving move; 0: stopped at the cap), the objective of the incumbent and of the result (0 when the search is off).
+ *   On the window path: same_window_filter_finish / same_window_refinish with refine_rounds_cap > 0.
  *   same_refine_matching: host buffers.  pairs[P][2] = (cell < n_m, reference < n_r), each once; unmatched[n_m] the no-match costs;
  *     tris[Tr][3] the kept triangles; axy[n_m][2], ref_xy[n_r][2], size[n_m]; match_pair_inout[n_m] = pair index per cell (-1 = none),
  *     one-to-one, replaced by the result.  out_stats[5] = {rounds, moves, settled, objective at the start, objective (both as the bits
  *     of a double)}.  One wait unless the search still moves after its first chunk of rounds. */
-int same_window_set_refine(same_window *window, int64_t rounds_cap, double delaunay_penalty);
-int same_window_refine_result(same_window *window, int64_t *out_rounds, int64_t *out_moves, int64_t *out_settled, double *out_objective_start,
-                              double *out_objective);
 int same_refine_matching(same_ctx *ctx, const int32_t *pairs, const double *costs, int64_t P, const double *unmatched, int64_t n_m,
                          int64_t n_r, const int32_t *tris, int64_t Tr, const double *axy, const double *ref_xy, const double *size,
                          double delaunay_penalty, int64_t rounds_cap, int32_t *match_pair_inout, int64_t *out_stats);

@@ -23,7 +23,7 @@ c_vp = ctypes.c_void_p
 c_sz = ctypes.c_size_t
 
 UNIQUE_ID_BYTES = 128
-ABI_VERSION = 8
+ABI_VERSION = 9
 DT_U8, DT_I32, DT_U64, DT_F64 = 0, 1, 2, 3     # SAME_DT_*
 OP_SUM, OP_MAX, OP_MIN = 0, 1, 2               # SAME_OP_*
 SPREAD_INFO_LEN = 14                           # SAME_SPREAD_INFO_LEN
@@ -102,18 +102,14 @@ _PROTOTYPES = {
     "same_window_destroy": [c_vp],
     "same_window_stage": [c_vp, c_int, c_vp, c_vp, c_vp, c_dbl, c_int, c_dbl, c_vp],
     "same_window_fetch": [c_vp, c_int, c_vp, c_i64],
-    "same_window_filter_finish": [c_vp, c_int, c_vp, c_vp, c_int, c_dbl, c_int, c_dbl, c_dbl, c_int, c_int, c_dbl, c_vp, c_vp, c_vp, c_vp],
+    "same_window_filter_finish": [c_vp, c_int, c_int, c_vp, c_vp, c_dbl, c_int, c_dbl, c_dbl, c_int, c_int, c_dbl, c_int, c_i64, c_dbl, c_vp, c_vp,
+                                  c_vp, c_vp],
+    "same_window_refinish": [c_vp, c_vp, c_dbl, c_i64, c_dbl, c_vp, c_vp, c_vp],
     "same_merge_dedup": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, ctypes.POINTER(c_i64)],
     "same_delaunay2d": [c_vp, c_i64, c_vp, c_i64, ctypes.POINTER(c_i64), c_dbl, ctypes.POINTER(c_dbl)],
     "same_window_delaunay": [c_vp, c_int, c_dbl, c_int, c_dbl, c_dbl, c_vp, c_vp],
     "same_sparse_assign": [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp],
-    "same_window_set_incumbent": [c_vp, c_int],
-    "same_window_incumbent_result": [c_vp, c_vp, c_vp, c_vp],
-    "same_window_refinish": [c_vp, c_vp, c_vp, c_vp, c_vp],
-    "same_window_set_refine": [c_vp, c_i64, c_dbl],
-    "same_window_refine_result": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "same_refine_matching": [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_dbl, c_i64, c_vp, c_vp],
-    "same_window_filter_finish_device": [c_vp, c_int, c_dbl, c_int, c_dbl, c_dbl, c_int, c_int, c_dbl, c_vp, c_vp, c_vp, c_vp],
     "same_delaunay_filtered": [c_vp, c_vp, c_i64, c_dbl, c_int, c_dbl, c_dbl, c_vp, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(c_int)],
     "same_section_set_codes": [c_vp, c_vp, c_i64],
     "same_merge_acc_create": [c_vp, ctypes.POINTER(c_vp)],
@@ -147,6 +143,10 @@ EXPORTS = tuple(_PROTOTYPES)
 SAME_EINVAL, SAME_ENOMEM, SAME_EIO, SAME_ENODEV, SAME_ERANGE, SAME_EUNSURE = -22, -12, -5, -19, -34, -11   # include/same_hip.h
 # why the device's triangulator refused a set (a mask; include/same_hip.h, same_window_delaunay)
 SAME_DD_FEW_POINTS, SAME_DD_NO_ANGLE, SAME_DD_NONFINITE, SAME_DD_IN_DOUBT, SAME_DD_OVERFLOW = 1, 2, 4, 8, 16
+# what same_window_filter_finish reads its triangles from, what it matches by, the int64 words of its stats record per window
+SAME_TRIS_SIMPLICES, SAME_TRIS_KEPT, SAME_TRIS_DEVICE = 0, 1, 2
+SAME_INCUMBENT_GREEDY, SAME_INCUMBENT_ASSIGNMENT = 0, 1
+SAME_WINDOW_STATS = 15
 
 
 class SameHipError(RuntimeError):

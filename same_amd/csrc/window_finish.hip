@@ -1,11 +1,11 @@
 // window_finish.hip -- same_window_filter_finish: per window the Delaunay simplices in; triangle classes (src/helpers.py:300-330),
 // the keep list and the same-type triangles added back so that every node keeps one (src/helpers.py:331-340, :365-389) -- all on the
 // device, in the reference's order (a cosine within 8 ulp of the angle threshold is left to the host, which re-decides it with the
-// reference's literal arccos and calls again with prefiltered = 1: the kept triangles in, no filter); source signs / weights
-// (src/same.py:1128-1146), per-row minimum and the greedy MIP start (src/init_helpers.py:104-133), the lazy-constraint body under
-// that incumbent, optionally refined against the model's flip penalty (refine.hip), the lazy-constraint body under the result
-// (src/same.py:645-669), XY-order sweep (src/violationhelper.py:53-117), signed-area flips (src/same.py:1362-1402).
-// Back to the host: the matched reference row per kept aligned cell, the per-cell violation flags and eight counters.
+// reference's literal arccos and calls again with SAME_TRIS_KEPT: the kept triangles in, no filter); source signs / weights
+// (src/same.py:1128-1146), per-row minimum and the greedy MIP start (src/init_helpers.py:104-133) or the optimal assignment (assign.hip),
+// optionally refined against the model's flip penalty (refine.hip), the lazy-constraint body under the result (src/same.py:645-669),
+// XY-order sweep (src/violationhelper.py:53-117), signed-area flips (src/same.py:1362-1402).  The mode is the call's arguments.
+// Back to the host: the matched reference row per kept aligned cell, the per-cell violation flags and a stats record per window.
 #include "assign.h"
 #include "refine.h"
 
@@ -364,7 +364,23 @@ int launch_filter(same_ctx *ctx, FilterPlan *const *plans, int n_w, double radiu
     return SAME_OK;
 }
 
+// what a finish call matches by and does after the incumbent: the call's arguments, the same for every window of it
+struct FinishMode {
+    int incumbent = SAME_INCUMBENT_GREEDY;
+    double no_match_penalty = 0.0;
+    int64_t refine_cap = 0;                   // local search rounds at most (refine.hip), 0 = no search
+    double delaunay_penalty = 0.0;
+};
+int check_mode(same_ctx *ctx, const FinishMode &m) {
+    REQUIRE(ctx, m.incumbent == SAME_INCUMBENT_GREEDY || m.incumbent == SAME_INCUMBENT_ASSIGNMENT);
+    REQUIRE(ctx, m.refine_cap >= 0 && m.delaunay_penalty >= 0.0 && m.delaunay_penalty - m.delaunay_penalty == 0.0);
+    return SAME_OK;
+}
+// words of a window's out_stats record after the eight counters: the assignment's flags and objective, the search's record
+enum { WS_AS_FLAGS = 8, WS_AS_OBJ = 9, WS_REFINE = 10 };
+
 struct FinishPlan {
+    FinishMode mode;
     unsigned long long *zero = nullptr;       // head of the finish buffer: [sel | counters | point flags (padded) | matched rows]
     void *filter_zero = nullptr;              // head of the window's filter buffer when this call filters it (zeroed in the same launch)
     size_t filter_zero_bytes = 0;
@@ -376,7 +392,7 @@ struct FinishPlan {
     int64_t cap_tr = 0;
     const unsigned long long *dTr = nullptr;
     char *assign_work = nullptr;              // the optimal assignment's work arrays (SAME_INCUMBENT_ASSIGNMENT), else null
-    bool refine = false;                      // the local search runs on the incumbent (same_window_set_refine) ...
+    bool refine = false;                      // the local search runs on the incumbent (mode.refine_cap > 0) ...
     rfn::RefineArgs rargs{};                  // ... over these arrays; its control words are counters + SC_REFINE
 };
 
@@ -404,7 +420,8 @@ int enqueue_tail(same_ctx *ctx, same_window *const *ws, FinishPlan *const *ps, i
 
 // A window's finish buffer laid out, its triangles uploaded (prefiltered form); no launch, no fill -- those come per GROUP of windows
 // (launch_finish; p->zero / p->zero_bytes name the head to zero).  cap_tr: the number of triangles, or (dTr != null) the bound the launch is sized by with the number itself on the device
-int prepare_finish(same_window *w, const int32_t *host_tris, int64_t cap_tr, const unsigned long long *dTr, FinishPlan *p) {
+int prepare_finish(same_window *w, const int32_t *host_tris, int64_t cap_tr, const unsigned long long *dTr, const FinishMode &mode,
+                   FinishPlan *p) {
     same_ctx *ctx = w->ctx;
     const int64_t n = w->n_ua, P = w->P, n_ends = n + w->n_r;
     Carver cv;
@@ -423,12 +440,13 @@ int prepare_finish(same_window *w, const int32_t *host_tris, int64_t cap_tr, con
     const size_t tt = (size_t)std::max<int64_t>(cap_tr, 1);
     const size_t o_alive = cv.take((size_t)std::max<int64_t>(P, 1)), o_match_pair = cv.take((size_t)n * 4), o_match_loc = cv.take((size_t)n * 4),
                  o_sign = cv.take(tt), o_weight = cv.take(tt * 8);
-    const size_t o_assign = w->incumbent == SAME_INCUMBENT_ASSIGNMENT ? cv.take(asg::work_bytes(n, w->n_r)) : 0;
-    const size_t o_refine = w->rf_cap > 0 ? cv.take(rfn::work_bytes(n, w->n_r, cap_tr)) : 0;
+    const size_t o_assign = mode.incumbent == SAME_INCUMBENT_ASSIGNMENT ? cv.take(asg::work_bytes(n, w->n_r)) : 0;
+    const size_t o_refine = mode.refine_cap > 0 ? cv.take(rfn::work_bytes(n, w->n_r, cap_tr)) : 0;
     SAME_TRY(ensure(ctx, w->finish, cv.off));
     SAME_TRY(ensure(ctx, w->tris, tt * 12));
     char *base = static_cast<char *>(w->finish.p);
     auto at = [&](size_t off) { return base + off; };
+    p->mode = mode;
     p->zero = reinterpret_cast<unsigned long long *>(base);
     p->zero_bytes = zero_bytes;
     p->back_off = o_sel;
@@ -464,7 +482,7 @@ int prepare_finish(same_window *w, const int32_t *host_tris, int64_t cap_tr, con
         r.pairs = w->pairs;
         r.cost = w->cost64;
         r.size = w->size_c;
-        r.dp = w->rf_dp;
+        r.dp = mode.delaunay_penalty;
         r.axy = w->axy_c;
         r.ref_xy = w->ref->xy;
         r.ref_row = w->jsec;
@@ -473,8 +491,8 @@ int prepare_finish(same_window *w, const int32_t *host_tris, int64_t cap_tr, con
         r.n = n;
         r.n_r = w->n_r;
         r.cap_tr = cap_tr;
-        r.cap = w->rf_cap;
-        r.penalty = w->rf_nm;
+        r.cap = mode.refine_cap;
+        r.penalty = mode.no_match_penalty;
         r.start = p->match_pair;
         r.ctrl = p->counters + SC_REFINE;
         rfn::carve(&r, at(o_refine));
@@ -496,9 +514,10 @@ int enqueue_refine(same_ctx *ctx, FinishPlan *const *ps, int n_w) {
 }
 
 // greedy MIP start of a group of prepared windows -- per-row minimum, rows that beat their penalty, the scan's matching (one pair per
-// aligned row) -- and the tail: one launch per kernel for the whole group (windows of one batch call share the cost type)
-int launch_finish(same_ctx *ctx, same_window *const *ws, FinishPlan *const *ps, int n_w, double no_match_penalty) {
-    if (ws[0]->incumbent == SAME_INCUMBENT_ASSIGNMENT) {
+// aligned row) -- and the tail: one launch per kernel for the whole group (windows of one batch call share the cost type and the mode)
+int launch_finish(same_ctx *ctx, same_window *const *ws, FinishPlan *const *ps, int n_w) {
+    const double no_match_penalty = ps[0]->mode.no_match_penalty;
+    if (ps[0]->mode.incumbent == SAME_INCUMBENT_ASSIGNMENT) {
         // the optimal assignment instead (assign.hip): it writes match_pair, clears the pairs' greedy flags, and leaves searches, flags
         // and objective in the head of `sel` (the greedy rounds' words, unused here), which comes back with the finish block
         asg::AssignArgs jobs[SAME_LAUNCH_WINDOWS];
@@ -556,8 +575,8 @@ int enqueue_finish_copy(same_window *w, FinishPlan *p) {
 
 // After a look at the finish block (in the pinned block): when the incumbent changed since (`fresh`: greedy rounds added), the local
 // search again from it; more rounds while the search is live and under its cap, in growing chunks, one wait each; then, if any of that
-// happened, the tail again and the finish block back.  The search's result goes to the window (same_window_refine_result).
-int settle(same_window *w, FinishPlan *p, bool fresh) {
+// happened, the tail again and the finish block back.  The search's record goes to out_stats[WS_REFINE ..].
+int settle(same_window *w, FinishPlan *p, bool fresh, int64_t *out_stats) {
     same_ctx *ctx = w->ctx;
     char *h = static_cast<char *>(w->host) + w->host_finish_off;
     const unsigned long long *rc = reinterpret_cast<const unsigned long long *>(h + p->o_counters) + SC_REFINE;
@@ -569,8 +588,9 @@ int settle(same_window *w, FinishPlan *p, bool fresh) {
             SAME_COPY(ctx, const_cast<unsigned long long *>(rc), p->rargs.ctrl, rfn::RC_COUNT * 8, hipMemcpyDeviceToHost);
             SAME_WAIT(ctx);
         }
-        while (!rc[rfn::RC_SETTLED] && (int64_t)rc[rfn::RC_ROUNDS] < w->rf_cap) {
-            chunk = (int)std::min<int64_t>(std::min(2 * chunk, 256), w->rf_cap - (int64_t)rc[rfn::RC_ROUNDS]);
+        const int64_t cap = p->mode.refine_cap;
+        while (!rc[rfn::RC_SETTLED] && (int64_t)rc[rfn::RC_ROUNDS] < cap) {
+            chunk = (int)std::min<int64_t>(std::min(2 * chunk, 256), cap - (int64_t)rc[rfn::RC_ROUNDS]);
             SAME_TRY(rfn::launch_rounds(ctx, &p->rargs, 1, chunk));
             SAME_COPY(ctx, const_cast<unsigned long long *>(rc), p->rargs.ctrl, rfn::RC_COUNT * 8, hipMemcpyDeviceToHost);
             SAME_WAIT(ctx);
@@ -585,11 +605,12 @@ int settle(same_window *w, FinishPlan *p, bool fresh) {
         SAME_WAIT(ctx);
     }
     if (p->refine) {
-        w->rf_rounds = (int64_t)rc[rfn::RC_ROUNDS];
-        w->rf_moves = (int64_t)rc[rfn::RC_MOVES];
-        w->rf_settled = (int64_t)rc[rfn::RC_SETTLED];
-        memcpy(&w->rf_obj0, &rc[rfn::RC_OBJ0], sizeof(double));
-        memcpy(&w->rf_obj, &rc[rfn::RC_OBJ], sizeof(double));
+        int64_t *rf = out_stats + WS_REFINE;
+        rf[0] = (int64_t)rc[rfn::RC_ROUNDS];
+        rf[1] = (int64_t)rc[rfn::RC_MOVES];
+        rf[2] = (int64_t)rc[rfn::RC_SETTLED];
+        rf[3] = (int64_t)rc[rfn::RC_OBJ0];          // the objectives as the bits of a double
+        rf[4] = (int64_t)rc[rfn::RC_OBJ];
     }
     return SAME_OK;
 }
@@ -603,11 +624,10 @@ int read_finish(same_window *w, FinishPlan *p, int32_t *out_match_row, uint8_t *
     const unsigned long long *cnt = reinterpret_cast<const unsigned long long *>(h + p->o_counters);
     int rounds = 0;
     bool again = false;      // the incumbent changed after the first look
-    if (w->incumbent == SAME_INCUMBENT_ASSIGNMENT) {     // no greedy rounds to add: the assignment settled in its one launch
+    if (p->mode.incumbent == SAME_INCUMBENT_ASSIGNMENT) {     // no greedy rounds to add: the assignment settled in its one launch
         rounds = (int)sel[0];
-        w->as_rounds = (int64_t)sel[0];
-        w->as_flags = (int64_t)sel[2];
-        memcpy(&w->as_objective, &sel[3], sizeof(double));
+        out_stats[WS_AS_FLAGS] = (int64_t)sel[2];
+        out_stats[WS_AS_OBJ] = (int64_t)sel[3];             // the bits of a double
     } else if (P) {
         int q = 0;
         while (q < WINDOW_GREEDY_ROUNDS && sel[q] != 0) ++q;
@@ -632,7 +652,7 @@ int read_finish(same_window *w, FinishPlan *p, int32_t *out_match_row, uint8_t *
             again = true;
         }
     }
-    SAME_TRY(settle(w, p, again));
+    SAME_TRY(settle(w, p, again, out_stats));
     for (int q = 0; q < 8; ++q) out_stats[q] = (int64_t)cnt[q];
     out_stats[SC_ROUNDS] = rounds;
     *out_ties += (int64_t)cnt[SC_TIES];
@@ -641,24 +661,43 @@ int read_finish(same_window *w, FinishPlan *p, int32_t *out_match_row, uint8_t *
     return SAME_OK;
 }
 
-// same_window_filter_finish's body; on_device: every window's simplices are the ones same_window_delaunay left on the device for it
-// (simplex_offsets are then the offsets of those counts, there is no host array)
-int filter_finish(same_window *const *windows, int n_windows, const int32_t *simplices, const int64_t *simplex_offsets, int prefiltered,
-                  bool on_device, double radius, int angle_enabled, double cos_thr, double near_tol, int ignore_same_type,
-                  int ensure_min_triangle_per_node, double no_match_penalty, int32_t *out_match_row, uint8_t *out_point_flag,
-                  int64_t *out_stats, int64_t *out_counts) {
+}  // namespace
+
+extern "C" {
+
+int same_window_filter_finish(same_window *const *windows, int n_windows, int source, const int32_t *simplices, const int64_t *simplex_offsets,
+                              double radius, int angle_enabled, double cos_thr, double near_tol, int ignore_same_type,
+                              int ensure_min_triangle_per_node, double no_match_penalty, int incumbent, int64_t refine_rounds_cap,
+                              double delaunay_penalty, int32_t *out_match_row, uint8_t *out_point_flag, int64_t *out_stats,
+                              int64_t *out_counts) {
     same_ctx *ctx = nullptr;
     SAME_TRY(check_batch(windows, n_windows, &ctx));
-    REQUIRE(ctx, simplex_offsets && out_counts && out_stats && simplex_offsets[0] == 0);
+    const FinishMode mode{incumbent, no_match_penalty, refine_rounds_cap, delaunay_penalty};
+    SAME_TRY(check_mode(ctx, mode));
+    REQUIRE(ctx, source == SAME_TRIS_SIMPLICES || source == SAME_TRIS_KEPT || source == SAME_TRIS_DEVICE);
+    // SAME_TRIS_DEVICE: every window's simplices are the ones same_window_delaunay left on the device for it (no host array; the offsets
+    // are those of its counts)
+    const bool on_device = source == SAME_TRIS_DEVICE;
+    REQUIRE(ctx, on_device == !simplices && on_device == !simplex_offsets);
+    std::vector<int64_t> dd_offsets;
+    if (on_device) {
+        dd_offsets.assign((size_t)n_windows + 1, 0);
+        for (int i = 0; i < n_windows; ++i) {
+            REQUIRE(ctx, windows[i]->dd_ok && windows[i]->staged == 2);
+            dd_offsets[(size_t)i + 1] = dd_offsets[(size_t)i] + windows[i]->n_dd;
+        }
+        simplex_offsets = dd_offsets.data();
+    }
+    REQUIRE(ctx, out_counts && out_stats && simplex_offsets[0] == 0);
     int64_t n_cells = 0;
     for (int i = 0; i < n_windows; ++i) {
         const int64_t Tr = simplex_offsets[i + 1] - simplex_offsets[i];
         REQUIRE(ctx, windows[i]->staged == 2 && Tr >= 0 && Tr < ((int64_t)1 << 31) - 512);
         n_cells += windows[i]->n_ua;
     }
-    REQUIRE(ctx, (simplex_offsets[n_windows] == 0 || simplices || on_device) && (n_cells == 0 || (out_match_row && out_point_flag)));
+    REQUIRE(ctx, n_cells == 0 || (out_match_row && out_point_flag));
     for (int q = 0; q < 4 * n_windows; ++q) out_counts[q] = 0;
-    for (int q = 0; q < 8 * n_windows; ++q) out_stats[q] = 0;
+    for (int q = 0; q < SAME_WINDOW_STATS * n_windows; ++q) out_stats[q] = 0;
     SAME_TRY(same_use(ctx));
     if (!on_device)     // (the device's own triangles index the window's kept cells by construction)
         for (int i = 0; i < n_windows; ++i)
@@ -674,7 +713,7 @@ int filter_finish(same_window *const *windows, int n_windows, const int32_t *sim
     // only); per window its filter and finish buffers are laid out; then per GROUP of SAME_LAUNCH_WINDOWS windows the zeroing of the
     // buffers' heads, the filter's and the finish's kernels (one launch each for the whole group); then every window's copies back
     const int32_t *d_simplices = nullptr;
-    if (!on_device && !prefiltered && simplex_offsets[n_windows] > 0) {
+    if (source == SAME_TRIS_SIMPLICES && simplex_offsets[n_windows] > 0) {
         int32_t *d = nullptr;
         SAME_TRY(slot_as(ctx, SL_TRIS, (size_t)simplex_offsets[n_windows] * 3, &d));
         SAME_COPY(ctx, d, simplices, (size_t)simplex_offsets[n_windows] * 12, hipMemcpyHostToDevice);
@@ -691,16 +730,11 @@ int filter_finish(same_window *const *windows, int n_windows, const int32_t *sim
         const int64_t Tr = simplex_offsets[i + 1] - simplex_offsets[i];
         w->filtered = w->finished = 0;
         w->Tr = 0;
-        w->as_rounds = w->as_flags = 0;
-        w->as_objective = 0.0;
-        w->rf_rounds = w->rf_moves = w->rf_settled = 0;
-        w->rf_obj0 = w->rf_obj = 0.0;
-        w->rf_nm = no_match_penalty;
         if (w->n_ua == 0) continue;
-        if (Tr && !prefiltered) {
+        if (Tr && source != SAME_TRIS_KEPT) {
             const int32_t *raw = on_device ? static_cast<const int32_t *>(w->dd_tris.p) : d_simplices + 3 * simplex_offsets[i];
             rc = prepare_filter(w, raw, Tr, ignore_same_type, ensure_min_triangle_per_node, &it.fplan);
-            if (rc == SAME_OK) rc = prepare_finish(w, nullptr, Tr, it.fplan.counters + FC_TR, &it.plan);
+            if (rc == SAME_OK) rc = prepare_finish(w, nullptr, Tr, it.fplan.counters + FC_TR, mode, &it.plan);
             if (rc == SAME_OK) {
                 fplans.push_back(&it.fplan);
                 it.plan.filter_zero = it.fplan.zero;
@@ -708,7 +742,7 @@ int filter_finish(same_window *const *windows, int n_windows, const int32_t *sim
             }
             it.filtered = true;
         } else {
-            rc = prepare_finish(w, Tr ? tri : nullptr, Tr, nullptr, &it.plan);     // the caller's kept triangles (or none)
+            rc = prepare_finish(w, Tr ? tri : nullptr, Tr, nullptr, mode, &it.plan);     // the caller's kept triangles (or none)
         }
         if (rc == SAME_OK) {
             live.push_back(w);
@@ -725,15 +759,14 @@ int filter_finish(same_window *const *windows, int n_windows, const int32_t *sim
         rc = launch_zero(ctx, zr, n_g);
     }
     // groups of at most SAME_LAUNCH_WINDOWS consecutive windows that agree on what a launch fixes for all of them (windows of one call
-    // usually come from one pair of sections: whether same-type triangles come back, the cost type)
+    // usually come from one pair of sections: whether same-type triangles come back, the cost type; the mode is the call's)
     for (size_t g = 0, e; g < fplans.size() && rc == SAME_OK; g = e) {
         for (e = g + 1; e < fplans.size() && e - g < SAME_LAUNCH_WINDOWS && fplans[e]->readd == fplans[g]->readd; ++e) {}
         rc = launch_filter(ctx, fplans.data() + g, (int)(e - g), radius, angle_enabled, cos_thr, near_tol);
     }
     for (size_t g = 0, e; g < live.size() && rc == SAME_OK; g = e) {
-        for (e = g + 1; e < live.size() && e - g < SAME_LAUNCH_WINDOWS && live[e]->cost_f32 == live[g]->cost_f32 &&
-                        live[e]->incumbent == live[g]->incumbent; ++e) {}
-        rc = launch_finish(ctx, live.data() + g, plans.data() + g, (int)(e - g), no_match_penalty);
+        for (e = g + 1; e < live.size() && e - g < SAME_LAUNCH_WINDOWS && live[e]->cost_f32 == live[g]->cost_f32; ++e) {}
+        rc = launch_finish(ctx, live.data() + g, plans.data() + g, (int)(e - g));
     }
     // the finish block of every window and, beside it, the filter's counters: one launch per group straight into the pinned blocks (or
     // one copy from each buffer where a block is not device-addressable)
@@ -775,7 +808,7 @@ int filter_finish(same_window *const *windows, int n_windows, const int32_t *sim
         same_window *w = windows[i];
         Item &it = items[(size_t)i];
         const int64_t Tr = simplex_offsets[i + 1] - simplex_offsets[i];
-        int64_t *counts = out_counts + 4 * i, *stats = out_stats + 8 * i;
+        int64_t *counts = out_counts + 4 * i, *stats = out_stats + SAME_WINDOW_STATS * i;
         if (!it.enqueued) {                 // no kept aligned cell: nothing to match, nothing to sweep
             w->filtered = w->finished = 1;
             continue;
@@ -785,7 +818,7 @@ int filter_finish(same_window *const *windows, int n_windows, const int32_t *sim
         cell0 += w->n_ua;
         if (it.filtered) {
             // the filter's counters first (they are on the host since the batch's one wait): a window with a cosine at the threshold is
-            // redone by the caller with prefiltered = 1, so nothing of it is read back here -- in particular no further greedy rounds
+            // redone by the caller with SAME_TRIS_KEPT, so nothing of it is read back here (its stats stay 0) -- in particular no further greedy rounds
             // (fills, launches and a wait per batch of rounds) are spent on a matching that is thrown away
             const unsigned long long *hf = reinterpret_cast<const unsigned long long *>(static_cast<const char *>(w->host) + w->host_filter_off);
             const int64_t n_keep = (int64_t)hf[FC_KEEP], n_near = (int64_t)hf[FC_NEAR], n_add = it.fplan.readd ? (int64_t)hf[FC_ADD] : 0;
@@ -793,10 +826,7 @@ int filter_finish(same_window *const *windows, int n_windows, const int32_t *sim
             counts[1] = n_add;
             counts[2] = n_near;
             counts[3] = (int64_t)hf[FC_TIES];
-            if (n_near) {
-                for (int q = 0; q < 8; ++q) stats[q] = 0;
-                continue;
-            }
+            if (n_near) continue;
             w->Tr = n_keep + n_add;
         } else {
             counts[0] = Tr;
@@ -808,78 +838,19 @@ int filter_finish(same_window *const *windows, int n_windows, const int32_t *sim
     return SAME_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int same_window_filter_finish(same_window *const *windows, int n_windows, const int32_t *simplices, const int64_t *simplex_offsets, int prefiltered,
-                              double radius, int angle_enabled, double cos_thr, double near_tol, int ignore_same_type,
-                              int ensure_min_triangle_per_node, double no_match_penalty, int32_t *out_match_row, uint8_t *out_point_flag,
-                              int64_t *out_stats, int64_t *out_counts) {
-    return filter_finish(windows, n_windows, simplices, simplex_offsets, prefiltered, false, radius, angle_enabled, cos_thr, near_tol,
-                         ignore_same_type, ensure_min_triangle_per_node, no_match_penalty, out_match_row, out_point_flag, out_stats, out_counts);
-}
-
-int same_window_filter_finish_device(same_window *const *windows, int n_windows, double radius, int angle_enabled, double cos_thr, double near_tol,
-                                     int ignore_same_type, int ensure_min_triangle_per_node, double no_match_penalty, int32_t *out_match_row,
-                                     uint8_t *out_point_flag, int64_t *out_stats, int64_t *out_counts) {
-    same_ctx *ctx = nullptr;
-    SAME_TRY(check_batch(windows, n_windows, &ctx));
-    std::vector<int64_t> offsets((size_t)n_windows + 1, 0);
-    for (int i = 0; i < n_windows; ++i) {
-        REQUIRE(ctx, windows[i]->dd_ok && windows[i]->staged == 2);
-        offsets[(size_t)i + 1] = offsets[(size_t)i] + windows[i]->n_dd;
-    }
-    return filter_finish(windows, n_windows, nullptr, offsets.data(), 0, true, radius, angle_enabled, cos_thr, near_tol, ignore_same_type,
-                         ensure_min_triangle_per_node, no_match_penalty, out_match_row, out_point_flag, out_stats, out_counts);
-}
-
-int same_window_set_incumbent(same_window *window, int mode) {
-    if (!window) return SAME_EINVAL;
-    REQUIRE(window->ctx, mode == SAME_INCUMBENT_GREEDY || mode == SAME_INCUMBENT_ASSIGNMENT);
-    window->incumbent = mode;
-    return SAME_OK;
-}
-
-int same_window_incumbent_result(same_window *window, int64_t *out_rounds, int64_t *out_flags, double *out_objective) {
-    if (!window) return SAME_EINVAL;
-    REQUIRE(window->ctx, out_rounds && out_flags && out_objective && window->finished);
-    *out_rounds = window->as_rounds;
-    *out_flags = window->as_flags;
-    *out_objective = window->as_objective;
-    return SAME_OK;
-}
-
-int same_window_set_refine(same_window *window, int64_t rounds_cap, double delaunay_penalty) {
-    if (!window) return SAME_EINVAL;
-    REQUIRE(window->ctx, rounds_cap >= 0 && delaunay_penalty >= 0.0 && delaunay_penalty - delaunay_penalty == 0.0);
-    window->rf_cap = rounds_cap;
-    window->rf_dp = rounds_cap > 0 ? delaunay_penalty : 0.0;
-    return SAME_OK;
-}
-
-int same_window_refine_result(same_window *window, int64_t *out_rounds, int64_t *out_moves, int64_t *out_settled, double *out_objective_start,
-                              double *out_objective) {
-    if (!window) return SAME_EINVAL;
-    REQUIRE(window->ctx, out_rounds && out_moves && out_settled && out_objective_start && out_objective && window->finished);
-    *out_rounds = window->rf_rounds;
-    *out_moves = window->rf_moves;
-    *out_settled = window->rf_settled;
-    *out_objective_start = window->rf_obj0;
-    *out_objective = window->rf_obj;
-    return SAME_OK;
-}
-
-int same_window_refinish(same_window *window, const int32_t *match_pair, int32_t *out_match_row, uint8_t *out_point_flag, int64_t *out_stats) {
+int same_window_refinish(same_window *window, const int32_t *match_pair, double no_match_penalty, int64_t refine_rounds_cap,
+                         double delaunay_penalty, int32_t *out_match_row, uint8_t *out_point_flag, int64_t *out_stats) {
     if (!window) return SAME_EINVAL;
     same_window *w = window;
     same_ctx *ctx = w->ctx;
+    const FinishMode mode{SAME_INCUMBENT_GREEDY, no_match_penalty, refine_rounds_cap, delaunay_penalty};   // (no incumbent is searched for)
+    SAME_TRY(check_mode(ctx, mode));
     REQUIRE(ctx, w->finished && w->staged == 2 && w->n_ua > 0 && match_pair && out_match_row && out_point_flag && out_stats);
     for (int64_t i = 0; i < w->n_ua; ++i) REQUIRE(ctx, match_pair[i] >= -1 && match_pair[i] < w->P);
     SAME_TRY(same_use(ctx));
     // the window's kept triangles are still the first w->Tr of its triangle buffer: lay the finish block out for exactly those
     FinishPlan p;
-    SAME_TRY(prepare_finish(w, nullptr, w->Tr, nullptr, &p));
+    SAME_TRY(prepare_finish(w, nullptr, w->Tr, nullptr, mode, &p));
     SAME_FILL(ctx, p.zero, 0, p.zero_bytes);
     if (w->P) SAME_FILL(ctx, p.gs.alive, 0, (size_t)w->P);
     SAME_COPY(ctx, p.match_pair, match_pair, (size_t)w->n_ua * 4, hipMemcpyHostToDevice);
@@ -889,10 +860,10 @@ int same_window_refinish(same_window *window, const int32_t *match_pair, int32_t
     char *h = static_cast<char *>(w->host) + w->host_finish_off;
     SAME_COPY(ctx, h, reinterpret_cast<const char *>(p.gs.sel), p.back_bytes, hipMemcpyDeviceToHost);
     SAME_WAIT(ctx);
-    SAME_TRY(settle(w, &p, false));
+    for (int q = 0; q < SAME_WINDOW_STATS; ++q) out_stats[q] = 0;
+    SAME_TRY(settle(w, &p, false, out_stats));
     const unsigned long long *cnt = reinterpret_cast<const unsigned long long *>(h + p.o_counters);
     for (int q = 0; q < 8; ++q) out_stats[q] = (int64_t)cnt[q];
-    out_stats[SC_ROUNDS] = w->as_rounds;
     memcpy(out_match_row, h + p.o_match_row, (size_t)w->n_ua * sizeof(int32_t));
     memcpy(out_point_flag, h + p.o_pflag, (size_t)w->n_ua);
     return SAME_OK;

@@ -179,14 +179,6 @@ struct same_window {
     win::DevBuf dd_work, dd_tris;                   // the device's triangulation (delaunay_dev.hip): work buffer, candidate triangles
     int64_t n_dd = 0;                               // candidate triangles in dd_tris ...
     int dd_ok = 0;                                  // ... valid for the window as staged (same_window_delaunay answered it)
-    int incumbent = 0;                              // SAME_INCUMBENT_* (same_window_set_incumbent): what the finish call matches by
-    int64_t as_rounds = 0, as_flags = 0;            // the last finish's optimal assignment: searches, flags (!= 0: not certified) ...
-    double as_objective = 0.0;                      // ... and its objective
-    int64_t rf_cap = 0;                             // the local search (same_window_set_refine): round cap, 0 = off ...
-    double rf_dp = 0.0;                             // ... delaunay_penalty, and the last finish call's no-match penalty
-    double rf_nm = 0.0;
-    int64_t rf_rounds = 0, rf_moves = 0, rf_settled = 0;   // the last finish's search: productive rounds, moves, settled ...
-    double rf_obj0 = 0.0, rf_obj = 0.0;             // ... objective of its start and of its result
     // stage block
     unsigned long long *counts = nullptr;           // [8], first words of the block the stage call copies back
     int32_t *rows_m = nullptr, *rows_r = nullptr, *idx = nullptr, *cnt = nullptr, *ua = nullptr, *rows_ua = nullptr, *type_c = nullptr,

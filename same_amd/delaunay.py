@@ -19,7 +19,7 @@ default is "qhull".  "device" triangulates on the GPU instead (csrc/delaunay_dev
 triangles are the Delaunay triangles that pass it, and those are the triangles with an empty circumcircle among the ones that pass a
 slack screen of it -- a local rule, one thread per point.  The device answers for the same SET as the host's triangulator does (every
 sign clear of `GUARD` x Qhull's allowance, the same formula: csrc/qhull_margin.h), its candidates never leave the device
-(same_window_filter_finish_device), and a window it refuses goes to the Qhull helpers, started on the first refusal.  The ORDER rule
+(same_window_filter_finish, SAME_TRIS_DEVICE), and a window it refuses goes to the Qhull helpers, started on the first refusal.  The ORDER rule
 above is the same rule: windows.iter_device_windows re-finishes a window with order ties or a cosine at the threshold with scipy's
 simplices.  `DeviceTriangulator.stats` (and `last_device_stats()` for the last pass of `sliding_window_incumbent`) count a pass's
 windows submitted, refused and re-finished, each window once.

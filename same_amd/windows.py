@@ -9,7 +9,7 @@ import os
 
 import numpy as np
 
-from . import ops
+from . import _lib, ops
 from .delaunay import QHULL, QhullTriangulator, Ticket
 
 
@@ -429,6 +429,7 @@ class DeviceWindow:
         self.handle = h
         self.counts = (0, 0, 0, 0)
         self.n_triangles = 0
+        self.assignment = self.refine = None
 
     def stage(self, moving, ref, box, radius, knn, dist_ct_coeff):
         """-> (aligned rows in the box, reference rows in the box, aligned rows kept, pairs)"""
@@ -451,66 +452,36 @@ class DeviceWindow:
     STAT_NAMES = ("checked", "flipped", "xy_comparisons", "xy_violations", "xy_triangles", "area_flips", "greedy_rounds", "matched")
 
     def filter_finish(self, simplices, radius, angle_enabled, cos_thr, near_tol, ignore_same_type, no_match_penalty,
-                      ensure_min_triangle_per_node=True):
-        """filter_triangles_by_radius of the kept aligned cells' Delaunay simplices, then signs, weights, the greedy incumbent and the three
+                      ensure_min_triangle_per_node=True, incumbent="greedy", refine=None):
+        """filter_triangles_by_radius of the kept aligned cells' Delaunay simplices, then signs, weights, the incumbent and the three
         sweeps, in one call.  -> (kept, added back, near, match_row, flag, stats); with near != 0 (cosines within near_tol of the
-        threshold) the last three are None and the caller filters on the host and calls finish() with its triangles."""
+        threshold) the last three are None and the caller filters on the host and calls finish() with its triangles.  `incumbent`,
+        `refine`: as for filter_finish_windows."""
         return filter_finish_windows([self], [simplices], radius, angle_enabled, cos_thr, near_tol, ignore_same_type, no_match_penalty,
-                                     ensure_min_triangle_per_node)[0]
+                                     ensure_min_triangle_per_node, incumbent=incumbent, refine=refine)[0]
 
-    def finish(self, triangles, no_match_penalty):
+    def finish(self, triangles, no_match_penalty, incumbent="greedy", refine=None):
         """The same with triangles the CALLER filtered (kept ones, in the reference's order).  -> (section row of the matched reference
         cell per kept aligned cell or -1, flag byte per kept cell: bit 0 = XY-order sweep, bit 1 = vertex of an area-flipped triangle;
         stats dict)."""
-        return filter_finish_windows([self], [triangles], 0.0, 0, 0.0, 0.0, False, no_match_penalty, True, prefiltered=True)[0][3:]
+        return filter_finish_windows([self], [triangles], 0.0, 0, 0.0, 0.0, False, no_match_penalty, True, prefiltered=True,
+                                     incumbent=incumbent, refine=refine)[0][3:]
 
-    INCUMBENTS = {"greedy": 0, "assignment": 1}       # SAME_INCUMBENT_*
-
-    def set_incumbent(self, mode):
-        """what the finish calls match this window by from now on: "greedy" (src/init_helpers.py:104-133) or "assignment" (the optimal
-        one-to-one assignment, csrc/assign.hip)"""
-        with self.ctx.lock:
-            self.ctx.check(self.ctx.lib.same_window_set_incumbent(self.handle, self.INCUMBENTS[mode]), "same_window_set_incumbent")
-
-    def incumbent_result(self):
-        """after a finish call in assignment mode -> (searches, flags: != 0 the device's answer is not certified, objective)"""
-        import ctypes
-
-        rounds, flags, obj = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_double(0.0)
-        with self.ctx.lock:
-            self.ctx.check(self.ctx.lib.same_window_incumbent_result(self.handle, ctypes.byref(rounds), ctypes.byref(flags),
-                                                                     ctypes.byref(obj)), "same_window_incumbent_result")
-        return rounds.value, flags.value, obj.value
-
-    def set_refine(self, refine):
-        """what the finish calls do after the incumbent from now on: `refine` = (rounds_cap, delaunay_penalty) runs the local search on
-        the lazy model's objective (csrc/refine.hip) for at most rounds_cap rounds; None runs none"""
-        cap, dp = (0, 0.0) if refine is None else (int(refine[0]), float(refine[1]))
-        with self.ctx.lock:
-            self.ctx.check(self.ctx.lib.same_window_set_refine(self.handle, cap, dp), "same_window_set_refine")
-
-    def refine_result(self):
-        """after a finish call with the local search on -> {"rounds", "moves", "settled", "objective_start", "objective"}"""
-        import ctypes
-
-        r, m, s = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
-        o0, o = ctypes.c_double(0.0), ctypes.c_double(0.0)
-        with self.ctx.lock:
-            self.ctx.check(self.ctx.lib.same_window_refine_result(self.handle, ctypes.byref(r), ctypes.byref(m), ctypes.byref(s),
-                                                                  ctypes.byref(o0), ctypes.byref(o)), "same_window_refine_result")
-        return {"rounds": r.value, "moves": m.value, "settled": s.value, "objective_start": o0.value, "objective": o.value}
-
-    def refinish(self, match_pair):
-        """the finished window's matched rows and sweeps again under `match_pair` (pair index per kept cell, -1 = none) -> (match_row,
-        flag byte, stats dict) as `finish`"""
+    def refinish(self, match_pair, no_match_penalty, refine=None):
+        """the finished window's matched rows and sweeps again under `match_pair` (pair index per kept cell, -1 = none), the local search
+        from it first when `refine` is given -> (match_row, flag byte, stats dict) as `finish` (greedy_rounds 0); `refine` is set to the
+        search's record"""
         n = self.counts[2]
         match_pair = np.ascontiguousarray(match_pair, dtype=np.int32)
         assert len(match_pair) == n
-        match_row, flag, stats = np.empty(n, np.int32), np.empty(n, np.uint8), np.zeros(8, np.int64)
+        cap, dp = _refine_args(refine)
+        match_row, flag, stats = np.empty(n, np.int32), np.empty(n, np.uint8), np.zeros(_lib.SAME_WINDOW_STATS, np.int64)
         with self.ctx.lock:
-            self.ctx.check(self.ctx.lib.same_window_refinish(self.handle, match_pair.ctypes.data, match_row.ctypes.data, flag.ctypes.data,
-                                                             stats.ctypes.data), "same_window_refinish")
-        return match_row, flag, dict(zip(self.STAT_NAMES, stats.tolist()))
+            self.ctx.check(self.ctx.lib.same_window_refinish(self.handle, match_pair.ctypes.data, float(no_match_penalty), cap, dp,
+                                                             match_row.ctypes.data, flag.ctypes.data, stats.ctypes.data),
+                           "same_window_refinish")
+        self.refine = _window_records(stats, "greedy", refine)[1]
+        return match_row, flag, dict(zip(self.STAT_NAMES, stats[:8].tolist()))
 
     def close(self):
         if getattr(self, "handle", None) and self.ctx.handle:
@@ -769,46 +740,71 @@ def stage_windows(states, moving, ref, boxes, radius, knn, dist_ct_coeff):
     return [s.counts for s in states]
 
 
+_INCUMBENTS = {"greedy": _lib.SAME_INCUMBENT_GREEDY, "assignment": _lib.SAME_INCUMBENT_ASSIGNMENT}
+
+
+def _refine_args(refine):
+    """`refine` = (rounds_cap, delaunay_penalty) or None -> the library's (rounds_cap, delaunay_penalty), rounds_cap 0 = no search"""
+    return (0, 0.0) if refine is None else (int(refine[0]), float(refine[1]))
+
+
+def _window_records(s, incumbent, refine):
+    """a window's stats words (SAME_WINDOW_STATS) -> (the assignment's record {"rounds", "flags", "objective"}, the search's record
+    {"rounds", "moves", "settled", "objective_start", "objective"}), each None when its mode was off"""
+    f = s.view(np.float64)
+    asg = {"rounds": int(s[6]), "flags": int(s[8]), "objective": float(f[9])} if incumbent == "assignment" else None
+    rfn = None if refine is None else {"rounds": int(s[10]), "moves": int(s[11]), "settled": int(s[12]), "objective_start": float(f[13]),
+                                       "objective": float(f[14])}
+    return asg, rfn
+
+
 def filter_finish_windows(states, simplices, radius, angle_enabled, cos_thr, near_tol, ignore_same_type, no_match_penalty,
-                          ensure_min_triangle_per_node=True, prefiltered=False):
+                          ensure_min_triangle_per_node=True, prefiltered=False, incumbent="greedy", refine=None):
     """same_window_filter_finish for a batch (one wait for all of them): `simplices[i]` are window i's Delaunay simplices, or with
-    `prefiltered` its kept triangles.  -> [(kept, added back, near, match_row, flag byte, stats dict) per window]; a window with near != 0
-    has None for the last three.  Every state's `order_ties` is set to the call's count of places where the answer hangs on the ORDER
-    of the triangles or of their corners (include/same_hip.h; of consequence only when the simplices are not Qhull's own)."""
+    `prefiltered` its kept triangles; `simplices=None` takes the candidates `triangulate_windows` left on the device for every window
+    (each state must have been answered since it was staged).  `incumbent`: "greedy" (src/init_helpers.py:104-133) or "assignment" (the
+    optimal one-to-one assignment, csrc/assign.hip); `refine` = (rounds_cap, delaunay_penalty) runs the local search on the lazy model's
+    objective from the incumbent (csrc/refine.hip) for at most rounds_cap rounds, None none.
+    -> [(kept, added back, near, match_row, flag byte, stats dict) per window]; a window with near != 0 has None for the last three.
+    Every state's `order_ties` is set to the call's count of places where the answer hangs on the ORDER of the triangles or of their
+    corners (include/same_hip.h; of consequence only when the simplices are not Qhull's own), its `assignment` and `refine` to the
+    call's records of the two (_window_records; None when off)."""
     ctx, n = states[0].ctx, len(states)
-    tris = [ops._tris(t) for t in simplices]
-    offsets = np.zeros(n + 1, np.int64)
-    np.cumsum([len(t) for t in tris], out=offsets[1:])
-    flat = tris[0] if n == 1 else np.concatenate(tris)
-
-    def call(match_row, flag, stats, counts):
-        return ctx.lib.same_window_filter_finish(_handles(states), n, flat.ctypes.data, offsets.ctypes.data, int(bool(prefiltered)),
-                                                 float(radius),
-                                                 int(angle_enabled), float(cos_thr), float(near_tol), int(bool(ignore_same_type)),
-                                                 int(bool(ensure_min_triangle_per_node)), float(no_match_penalty), match_row.ctypes.data,
-                                                 flag.ctypes.data, stats.ctypes.data, counts.ctypes.data)
-
-    return _filter_finish_results(states, call, "same_window_filter_finish")
-
-
-def filter_finish_device_windows(states, radius, angle_enabled, cos_thr, near_tol, ignore_same_type, no_match_penalty,
-                                 ensure_min_triangle_per_node=True):
-    """same_window_filter_finish_device: `filter_finish_windows` over the candidates `triangulate_windows` left on the device for each
-    window (every state must have been answered since it was staged); the same results, no simplices from the host."""
-    ctx, n = states[0].ctx, len(states)
-
-    def call(match_row, flag, stats, counts):
-        return ctx.lib.same_window_filter_finish_device(_handles(states), n, float(radius), int(angle_enabled), float(cos_thr),
-                                                        float(near_tol), int(bool(ignore_same_type)), int(bool(ensure_min_triangle_per_node)),
-                                                        float(no_match_penalty), match_row.ctypes.data, flag.ctypes.data, stats.ctypes.data,
-                                                        counts.ctypes.data)
-
-    return _filter_finish_results(states, call, "same_window_filter_finish_device")
+    if simplices is None:
+        source, flat, offsets = _lib.SAME_TRIS_DEVICE, None, None
+    else:
+        source = _lib.SAME_TRIS_KEPT if prefiltered else _lib.SAME_TRIS_SIMPLICES
+        tris = [ops._tris(t) for t in simplices]
+        offsets = np.zeros(n + 1, np.int64)
+        np.cumsum([len(t) for t in tris], out=offsets[1:])
+        flat = tris[0] if n == 1 else np.concatenate(tris)
+    cap, dp = _refine_args(refine)
+    kept_cells = [s.counts[2] for s in states]
+    cell_off = np.concatenate(([0], np.cumsum(kept_cells))).astype(np.int64)
+    match_row, flag = np.empty(int(cell_off[-1]), np.int32), np.empty(int(cell_off[-1]), np.uint8)
+    stats, counts = np.zeros((n, _lib.SAME_WINDOW_STATS), np.int64), np.zeros((n, 4), np.int64)
+    with ctx.lock:
+        ctx.check(ctx.lib.same_window_filter_finish(_handles(states), n, source, _lib._ptr(flat), _lib._ptr(offsets), float(radius),
+                                                    int(angle_enabled), float(cos_thr), float(near_tol), int(bool(ignore_same_type)),
+                                                    int(bool(ensure_min_triangle_per_node)), float(no_match_penalty), _INCUMBENTS[incumbent],
+                                                    cap, dp, match_row.ctypes.data, flag.ctypes.data, stats.ctypes.data,
+                                                    counts.ctypes.data), "same_window_filter_finish")
+    out = []
+    for i, s in enumerate(states):
+        kept, added, near, s.order_ties = (int(c) for c in counts[i])
+        s.n_triangles = 0 if near else kept + added
+        s.assignment, s.refine = _window_records(stats[i], incumbent, refine)
+        if near:
+            out.append((kept, added, near, None, None, None))
+        else:
+            a, b = int(cell_off[i]), int(cell_off[i + 1])
+            out.append((kept, added, near, match_row[a:b], flag[a:b], dict(zip(DeviceWindow.STAT_NAMES, stats[i, :8].tolist()))))
+    return out
 
 
 def triangulate_windows(states, radius, angle_enabled, cos_thr, guard):
     """same_window_delaunay for a batch of staged windows (one wait): -> (status per window: 0 answered, else a mask of
-    _lib.SAME_DD_* reasons; candidate triangles per window); the candidates stay on the device for filter_finish_device_windows"""
+    _lib.SAME_DD_* reasons; candidate triangles per window); the candidates stay on the device for filter_finish_windows(states, None, ...)"""
     ctx, n = states[0].ctx, len(states)
     status, n_tris = np.zeros(n, np.int32), np.zeros(n, np.int64)
     with ctx.lock:
@@ -817,41 +813,19 @@ def triangulate_windows(states, radius, angle_enabled, cos_thr, guard):
     return status, n_tris
 
 
-def _filter_finish_results(states, call, what):
-    ctx, n = states[0].ctx, len(states)
-    kept_cells = [s.counts[2] for s in states]
-    cell_off = np.concatenate(([0], np.cumsum(kept_cells))).astype(np.int64)
-    match_row, flag = np.empty(int(cell_off[-1]), np.int32), np.empty(int(cell_off[-1]), np.uint8)
-    stats, counts = np.zeros((n, 8), np.int64), np.zeros((n, 4), np.int64)
-    with ctx.lock:
-        ctx.check(call(match_row, flag, stats, counts), what)
-    out = []
-    for i, s in enumerate(states):
-        kept, added, near, s.order_ties = (int(c) for c in counts[i])
-        s.n_triangles = 0 if near else kept + added
-        if near:
-            out.append((kept, added, near, None, None, None))
-        else:
-            a, b = int(cell_off[i]), int(cell_off[i + 1])
-            out.append((kept, added, near, match_row[a:b], flag[a:b], dict(zip(DeviceWindow.STAT_NAMES, stats[i].tolist()))))
-    return out
-
-
-def _assignment_result(state, out, moving, no_match_penalty, match_row, cell_flags, stats):
-    """a finished window in assignment mode: its searches and objective; a window the device's certificate refused is solved by scipy's
-    sparse solver and finished again under that matching (counted as a fallback)"""
+def _assignment_fallback(state, out, moving, no_match_penalty, refine):
+    """a window whose assignment the device's certificate refused: solved by scipy's sparse solver and finished again under that
+    matching (counted as a fallback) -> (match_row, flag byte, stats dict); greedy_rounds stays the device's searches"""
     from ._trace import stage as marked
 
-    rounds, flags, objective = state.incumbent_result()
-    fallback = 0
-    if flags:
-        with marked("assignment fallback (host)"):
-            pairs, costs = state.fetch(_W_PAIRS), state.fetch(_W_COSTS)
-            unmatched = float(no_match_penalty) * moving.size[out.rows_m].astype(np.float64)
-            mp = ops.sparse_assign_host(pairs, costs, unmatched, len(unmatched), out.counts[1])
-            match_row, cell_flags, stats = state.refinish(mp)
-            objective, fallback = ops.assign_objective(mp, costs, unmatched), 1
-    return match_row, cell_flags, stats, {"objective": objective, "fallback": fallback, "rounds": rounds}
+    with marked("assignment fallback (host)"):
+        pairs, costs = state.fetch(_W_PAIRS), state.fetch(_W_COSTS)
+        unmatched = float(no_match_penalty) * moving.size[out.rows_m].astype(np.float64)
+        mp = ops.sparse_assign_host(pairs, costs, unmatched, len(unmatched), out.counts[1])
+        match_row, cell_flags, stats = state.refinish(mp, no_match_penalty, refine)
+        stats["greedy_rounds"] = out.assignment["rounds"]
+        out.assignment.update(objective=ops.assign_objective(mp, costs, unmatched), fallback=1)
+    return match_row, cell_flags, stats
 
 
 class DeviceWindowResult:
@@ -861,7 +835,8 @@ class DeviceWindowResult:
     `flip_flag` 1 for the vertices of triangles whose signed area flips, `stats` the sweeps' counters, `counts` (aligned in box, refs in
     box, kept, pairs); `state` is the live DeviceWindow until the generator is asked for the first window of the next batch (pairs,
     costs, signs ... through `state.fetch`).  `assignment` (incumbent="assignment" only): {"objective", "fallback", "rounds"}.
-    `refine` (refine given only): DeviceWindow.refine_result() of the window's final finish."""
+    `refine` (refine given only): the search's record of the window's final finish ({"rounds", "moves", "settled", "objective_start",
+    "objective"})."""
 
     __slots__ = ("window", "error", "rows_m", "axy", "triangles", "n_triangles", "match_row", "point_flag", "flip_flag", "stats",
                  "counts", "state", "assignment", "refine")
@@ -1004,19 +979,18 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
         if not triangulate or not todo:
             return
         states, tickets = [st for _o, st, _t in todo], [t for _o, _s, t in todo]
-        for state in states:
-            state.set_incumbent(incumbent)
-            state.set_refine(refine)
         tri.before_finish(states, tickets, radius, angle_enabled, cos_thr)
         with marked("triangulate (wait for helper)"):
             tris = [ticket.result() for ticket in tickets]
         args = (radius, angle_enabled, cos_thr, near_tol, ignore_same_type_triangles, no_match_penalty)
+        mode = dict(incumbent=incumbent, refine=refine)
         with marked("filter + signs + incumbent + sweeps (device)"):
-            # candidates the device made stay there (same_window_filter_finish_device); every other window brings its simplices
+            # candidates the device made stay there (simplices None); every other window brings its simplices
             mine = [q for q, t in enumerate(tris) if t is None]
             theirs = [q for q, t in enumerate(tris) if t is not None]
-            res = dict(zip(mine, filter_finish_device_windows([states[q] for q in mine], *args) if mine else []))
-            res.update(zip(theirs, filter_finish_windows([states[q] for q in theirs], [tris[q] for q in theirs], *args) if theirs else []))
+            res = dict(zip(mine, filter_finish_windows([states[q] for q in mine], None, *args, **mode) if mine else []))
+            res.update(zip(theirs, filter_finish_windows([states[q] for q in theirs], [tris[q] for q in theirs], *args, **mode)
+                           if theirs else []))
         # simplices that are not Qhull's own (delaunay.py: the same triangles in another order): where the window's numbers hang on that
         # order -- the device counted such places, or a cosine sits at the threshold and the host is about to re-decide the filter --
         # the window is finished again with scipy's
@@ -1024,7 +998,7 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
             if ticket.native and (state.order_ties or res[q][2]):
                 with marked("order ties: the window again with Qhull's simplices"):
                     tris[q] = ticket.qhull()
-                    res[q] = filter_finish_windows([state], [tris[q]], *args)[0]
+                    res[q] = filter_finish_windows([state], [tris[q]], *args, **mode)[0]
         for q, (out, state, _t) in enumerate(todo):
             _kept, _added, near, match_row, cell_flags, stats = res[q]
             if near:
@@ -1035,12 +1009,12 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
                                                                min_angle_deg=min_angle_deg, verbose=False, ctx=ctx, _rows_as_array=True,
                                                                _type_id=tid)
                 with marked("signs + incumbent + sweeps (device)"):
-                    match_row, cell_flags, stats = state.finish(out.triangles, no_match_penalty)
+                    match_row, cell_flags, stats = state.finish(out.triangles, no_match_penalty, **mode)
             if incumbent == "assignment":
-                match_row, cell_flags, stats, out.assignment = _assignment_result(state, out, moving, no_match_penalty, match_row,
-                                                                                  cell_flags, stats)
-            if refine is not None:
-                out.refine = state.refine_result()
+                out.assignment = {"objective": state.assignment["objective"], "fallback": 0, "rounds": state.assignment["rounds"]}
+                if state.assignment["flags"]:
+                    match_row, cell_flags, stats = _assignment_fallback(state, out, moving, no_match_penalty, refine)
+            out.refine = state.refine
             out.match_row, out.stats = match_row, stats
             # the library packs both per-cell flags into one byte
             out.point_flag, out.flip_flag = cell_flags & 1, (cell_flags >> 1) & 1

@@ -9,20 +9,25 @@ import numpy as np
 import pytest
 from scipy.optimize import linear_sum_assignment
 
-NEW = ("same_sparse_assign", "same_window_set_incumbent", "same_window_incumbent_result", "same_window_refinish")
+NEW = ("same_sparse_assign", "same_window_filter_finish", "same_window_refinish")
+GONE = ("same_window_filter_finish_device", "same_window_set_incumbent", "same_window_incumbent_result", "same_window_set_refine",
+        "same_window_refine_result")     # folded into same_window_filter_finish (ABI 9)
 
 
-def test_entry_points_declared_exported_and_built():
+def test_abi9_entry_points_declared_exported_and_built():
     from same_amd import _lib
 
     header = open(os.path.join(os.path.dirname(__file__), "..", "include", "same_hip.h")).read()
-    assert "#define SAME_ABI_VERSION 8" in header and _lib.ABI_VERSION == 8
+    assert "#define SAME_ABI_VERSION 9" in header and _lib.ABI_VERSION == 9
     assert "#define SAME_INCUMBENT_GREEDY 0" in header and "#define SAME_INCUMBENT_ASSIGNMENT 1" in header
+    assert (_lib.SAME_INCUMBENT_GREEDY, _lib.SAME_INCUMBENT_ASSIGNMENT) == (0, 1)
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in NEW:
         assert f"int {name}(" in header
         assert name in _lib.EXPORTS
         assert hasattr(lib, name)
+    for name in GONE:
+        assert name not in _lib.EXPORTS and not hasattr(lib, name)
 
 
 def _frames(n=400, seed=0):

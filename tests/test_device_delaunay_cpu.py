@@ -1,6 +1,7 @@
 """The device triangulation route (optim_params["hip_delaunay"] = "device", csrc/delaunay_dev.hip) on the CPU: the mode switch, the
 ABI surface, and the premise the route is built on -- the filter's kept triangles are exactly the triangles that pass the filter and
 have an empty circumcircle -- stated in numpy and held against the reference's filter over scipy's triangulation."""
+import ctypes
 import os
 import zlib
 
@@ -26,14 +27,20 @@ def test_mode_accepts_device_from_params_and_environment(monkeypatch):
             delaunay.mode({"hip_delaunay": bad})
 
 
-def test_new_entry_points_are_exported_and_declared():
+def test_abi9_entry_points_are_exported_and_declared():
     from same_amd import _lib
 
     header = open(os.path.join(os.path.dirname(__file__), "..", "include", "same_hip.h")).read()
-    for name in ("same_window_delaunay", "same_window_filter_finish_device", "same_delaunay_filtered"):
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    for name in ("same_window_delaunay", "same_window_filter_finish", "same_delaunay_filtered"):
         assert name in _lib.EXPORTS
         assert f"int {name}(" in header
-    for name in ("SAME_DD_FEW_POINTS", "SAME_DD_NO_ANGLE", "SAME_DD_NONFINITE", "SAME_DD_IN_DOUBT", "SAME_DD_OVERFLOW"):
+        assert hasattr(lib, name)
+    for name in ("same_window_filter_finish_device", "same_window_set_incumbent", "same_window_incumbent_result", "same_window_set_refine",
+                 "same_window_refine_result"):       # folded into same_window_filter_finish (ABI 9)
+        assert name not in _lib.EXPORTS and not hasattr(lib, name)
+    for name in ("SAME_DD_FEW_POINTS", "SAME_DD_NO_ANGLE", "SAME_DD_NONFINITE", "SAME_DD_IN_DOUBT", "SAME_DD_OVERFLOW",
+                 "SAME_TRIS_SIMPLICES", "SAME_TRIS_KEPT", "SAME_TRIS_DEVICE", "SAME_WINDOW_STATS"):
         assert f"#define {name} {getattr(_lib, name)}" in " ".join(header.split())
 
 

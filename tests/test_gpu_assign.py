@@ -202,3 +202,181 @@ def test_cfg5_1m_cells_merged_table_is_stable_without_fallbacks():
     assert len(first) > 900_000 and first.equals(second) and st1 == st2
     assert len(st1) > 100 and sum(s["fallback"] for s in st1) == 0
     assert all(np.isfinite(s["objective"]) for s in st1)
+
+
+@pytest.fixture
+def staged():
+    """one window staged over a whole 4 000-cell section, with scipy's simplices of its kept cells"""
+    from scipy.spatial import Delaunay
+
+    from same_amd import _lib, synth
+    from same_amd import windows as W
+
+    ctx = _lib.default_context(0)
+    ref = synth.make_cells(4000, 4, seed=3)
+    mov = synth.make_jittered(ref, seed=4)
+    tid = np.unique(mov["cell_type"], return_inverse=True)[1].astype(np.int32)
+    size = np.where(np.arange(len(mov["xy"])) % 3 == 0, 2, 1)
+    rs, ms = W.Section(ref["xy"], ref["types"], None, None), W.Section(mov["xy"], mov["types"], tid, size)
+    dref, dmov = W.DeviceSection(rs, np.float64, ctx), W.DeviceSection(ms, np.float64, ctx)
+    st = W.DeviceWindow(ctx)
+    try:
+        W.stage_windows([st], dmov, dref, [(-1e9, 1e9, -1e9, 1e9)], 25.0, 8, 1.0)
+        yield st, rs, ms, Delaunay(st.fetch(W._W_ALIGNED_XY)).simplices
+    finally:
+        st.close()
+        dref.close()
+        dmov.close()
+
+
+PENALTY = 6.0
+REFINE = (256, 4.0)
+
+
+def _finish(st, simplices, **mode):
+    from same_amd.triangles import cos_threshold
+
+    en, thr = cos_threshold(15)
+    _k0, _k1, near, row, flag, stats = st.filter_finish(simplices, 25.0, en, thr, 0.0, True, PENALTY, **mode)
+    assert near == 0
+    return row, flag, stats
+
+
+@pytest.mark.parametrize("refine", [None, REFINE])
+def test_refinish_under_its_own_matching_repeats_the_finish(staged, refine):
+    """same_window_refinish with the window's own matching (pair per kept cell from its match and pairs) gives back what the finish
+    call gave: matched rows, flag bytes, every counter but the incumbent's rounds; with the search on, a settled search moves no more"""
+    from same_amd import windows as W
+
+    st, _rs, _ms, simplices = staged
+    for incumbent in ("greedy", "assignment"):
+        row, flag, stats = _finish(st, simplices, incumbent=incumbent, refine=refine)
+        first = st.refine
+        if refine is not None:
+            assert first["settled"] == 1 and first["rounds"] < refine[0], first
+        pair_of = {tuple(p): q for q, p in enumerate(st.fetch(W._W_PAIRS).tolist())}
+        mp = np.array([pair_of[(i, m)] if m >= 0 else -1 for i, m in enumerate(st.fetch(W._W_MATCH).tolist())], np.int32)
+        row2, flag2, stats2 = st.refinish(mp, PENALTY, refine)
+        assert np.array_equal(row2, row) and np.array_equal(flag2, flag), incumbent
+        assert stats2["greedy_rounds"] == 0 and stats["matched"] > 0 and (stats["greedy_rounds"] > 0 or incumbent == "assignment")
+        assert {k: v for k, v in stats2.items() if k != "greedy_rounds"} == {k: v for k, v in stats.items() if k != "greedy_rounds"}
+        if refine is None:
+            assert st.refine is None
+        else:
+            assert st.refine["moves"] == 0 and st.refine["settled"] == 1, st.refine
+            assert st.refine["objective"] == pytest.approx(first["objective"], rel=1e-12)
+
+
+@pytest.mark.parametrize("other", ["scipy", "unmatched"])
+def test_refinish_under_another_matching_equals_the_host_sweeps(staged, other):
+    """same_window_refinish under a matching the device did not make (scipy's optimum, or no cell matched): the matched rows, flag bytes
+    and counters are those of the host-buffer sweeps for that matching, as incumbent.incumbent_of_prepared computes them"""
+    from same_amd import ops
+    from same_amd import windows as W
+
+    st, rs, ms, simplices = staged
+    _finish(st, simplices, incumbent="assignment")
+    pairs, costs, rows_r = st.fetch(W._W_PAIRS), st.fetch(W._W_COSTS), st.fetch(W._W_ROWS_R)
+    axy, rows_m, tris, signs = st.fetch(W._W_ALIGNED_XY), st.fetch(W._W_ALIGNED_ROWS), st.fetch(W._W_TRIANGLES), st.fetch(W._W_SIGNS)
+    n_a, rxy = len(axy), rs.xy[rows_r]
+    unmatched = PENALTY * ms.size[rows_m].astype(np.float64)
+    if other == "scipy":
+        mp = ops.sparse_assign_host(pairs, costs, unmatched, n_a, len(rows_r))
+    else:
+        mp = np.full(n_a, -1, np.int32)
+    row, flag, stats = st.refinish(mp, PENALTY)
+    match = np.where(mp >= 0, pairs[np.maximum(mp, 0), 1], -1).astype(np.int32)
+    sw = ops.BoundSweep(tris, signs, rxy, n_a)
+    try:
+        checked, viol = sw.sweep_match(match)
+    finally:
+        sw.close()
+    _edge, _tflag, pflag, counts = ops.xyorder_sweep(axy, rxy, tris, match)
+    _before, _after, _m3, flipped = ops.area_flip(axy, rxy, tris, match)
+    flip_node = np.zeros(n_a, np.uint8)
+    flip_node[tris[flipped.astype(bool)].reshape(-1)] = 1
+    assert np.array_equal(row, np.where(match >= 0, rows_r[np.maximum(match, 0)], -1))
+    assert np.array_equal(flag & 1, pflag) and np.array_equal(flag >> 1, flip_node)
+    assert stats == {"checked": checked, "flipped": len(viol), "xy_comparisons": int(counts[0]), "xy_violations": int(counts[1]),
+                     "xy_triangles": int(counts[2]), "area_flips": int(np.count_nonzero(flipped)), "greedy_rounds": 0,
+                     "matched": int(np.count_nonzero(mp >= 0))}
+    assert (stats["matched"] > 0 and stats["xy_comparisons"] > 0) == (other == "scipy")
+
+
+@pytest.mark.parametrize("refine", [None, "local"])
+def test_device_route_fallback_equals_the_general_route(monkeypatch, refine):
+    """a window whose certificate flag is up (forced here, in the decoded record of its finish call) is solved by scipy and finished
+    again under that matching (same_window_refinish): its table rows and stats are the general route's, with fallback == 1"""
+    import same_amd
+    from same_amd import windows as W
+
+    r_df, m_df, cols, op = _section()
+    A = dict(op, hip_incumbent="assignment", **({} if refine is None else {"hip_refine": refine}))
+    run = lambda **k: same_amd.sliding_window_incumbent(r_df, m_df, commonCT=cols, optim_params=dict(A), return_stats=True, **k)
+    want, wst = run(_route="general")
+    inner, forced = W._window_records, []
+
+    def flagged(s, incumbent, refine_):
+        asg, rfn = inner(s, incumbent, refine_)
+        if asg is not None and s[7] > 0 and not forced:        # (word 7: matched cells)
+            forced.append(asg)
+            asg = dict(asg, flags=1)
+        return asg, rfn
+
+    monkeypatch.setattr(W, "_window_records", flagged)
+    got, gst = run(_route="device")
+    assert len(forced) == 1 and len(gst) == len(wst) > 10
+    assert [s["fallback"] for s in gst].count(1) == 1 and all(s["fallback"] == 0 for s in wst)
+    assert list(got.columns) == list(want.columns) and len(got) == len(want)
+    for c in want.columns:
+        assert np.array_equal(got[c].to_numpy(), want[c].to_numpy()), c
+    for a, b in zip(gst, wst):
+        assert set(a) == set(b)
+        for k in a:
+            if k in ("objective", "mip_objective_start", "mip_objective"):
+                assert a[k] == pytest.approx(b[k], rel=1e-9), k
+            elif k != "fallback":
+                assert a[k] == b[k], k
+
+
+def test_finish_arguments_are_checked_before_any_device_work(staged):
+    """a bad incumbent mode, a negative round cap, a NaN penalty, NULL simplices with a host source (and host simplices with the
+    device's): SAME_EINVAL, and not one launch, fill, copy or wait"""
+    from same_amd import _lib
+    from same_amd import windows as W
+
+    st, _rs, _ms, simplices = staged
+    _finish(st, simplices)                              # (a finished window: same_window_refinish would take it)
+    ctx = st.ctx
+    n = st.counts[2]
+    tris = np.ascontiguousarray(simplices, dtype=np.int32)
+    offsets = np.array([0, len(tris)], np.int64)
+    row, flag = np.empty(n, np.int32), np.empty(n, np.uint8)
+    stats, counts = np.zeros(_lib.SAME_WINDOW_STATS, np.int64), np.zeros(4, np.int64)
+    good = dict(source=_lib.SAME_TRIS_SIMPLICES, tris=tris.ctypes.data, offsets=offsets.ctypes.data, incumbent=_lib.SAME_INCUMBENT_GREEDY,
+                cap=0, dp=0.0)
+
+    def call(**kw):
+        a = dict(good, **kw)
+        return ctx.lib.same_window_filter_finish(W._handles([st]), 1, a["source"], a["tris"], a["offsets"], 25.0, 0, 0.0, 0.0, 1, 1,
+                                                 PENALTY, a["incumbent"], a["cap"], a["dp"], row.ctypes.data, flag.ctypes.data,
+                                                 stats.ctypes.data, counts.ctypes.data)
+
+    mp = np.full(n, -1, np.int32)
+    before = ctx.stats()
+    assert call(incumbent=2) == _lib.SAME_EINVAL
+    assert call(incumbent=-1) == _lib.SAME_EINVAL
+    assert call(cap=-1) == _lib.SAME_EINVAL
+    assert call(cap=8, dp=float("nan")) == _lib.SAME_EINVAL
+    assert call(cap=8, dp=-1.0) == _lib.SAME_EINVAL
+    assert call(source=3) == _lib.SAME_EINVAL
+    for source in (_lib.SAME_TRIS_SIMPLICES, _lib.SAME_TRIS_KEPT):
+        assert call(source=source, tris=None, offsets=None) == _lib.SAME_EINVAL
+        assert call(source=source, tris=None) == _lib.SAME_EINVAL
+    assert call(source=_lib.SAME_TRIS_DEVICE) == _lib.SAME_EINVAL
+    for cap, dp in ((-1, 0.0), (8, float("nan"))):
+        assert ctx.lib.same_window_refinish(st.handle, mp.ctypes.data, PENALTY, cap, dp, row.ctypes.data, flag.ctypes.data,
+                                            stats.ctypes.data) == _lib.SAME_EINVAL
+    after = ctx.stats()
+    assert {k: after[k] for k in ("launches", "fills", "copies", "waits")} == {k: before[k] for k in ("launches", "fills", "copies", "waits")}
+    assert call() == 0                                   # the same call with good arguments runs

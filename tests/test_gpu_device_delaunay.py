@@ -152,7 +152,7 @@ def test_fuzz_tables_device_route():
                 assert got[0].equals(want[0]) and got[1] == want[1], (seed, merge)
 
 
-def test_answered_batch_uploads_no_simplices():
+def test_answered_batch_from_the_device_source_uploads_no_simplices():
     """the device's candidates never cross the bus: the device finish call makes one copy fewer than the same finish with the
     simplices from the host (their upload), and the match it computes is the same"""
     from same_amd import _lib, synth
@@ -173,7 +173,7 @@ def test_answered_batch_uploads_no_simplices():
         status, n_tris = W.triangulate_windows([st], 25.0, en, thr, 16.0)
         assert status[0] == 0 and n_tris[0] > 0
         before = ctx.stats()
-        dev = W.filter_finish_device_windows([st], 25.0, en, thr, 0.0, True, 100.0)[0]
+        dev = W.filter_finish_windows([st], None, 25.0, en, thr, 0.0, True, 100.0)[0]
         dev_copies = ctx.stats()["copies"] - before["copies"]
         host_tris = Delaunay(st.fetch(W._W_ALIGNED_XY)).simplices
         W.stage_windows([st], dmov, dref, box, 25.0, 8, 1.0)

@@ -16,26 +16,31 @@ Workload `dense100k`, weak scaling (the configuration BASELINE.json's metric is 
     5. orientation sweep (lazy-constraint body), XY-order sweep, signed-area flips under a nearest-reference matching
   Inputs are resident in HBM before the timed region (the Delaunay triangulation itself is an input: scipy/Qhull on the
   host, as in the reference).  Every rank owns its own block of 100 000 aligned rows against the replicated refs.
-At N > 1 the same run then measures BASELINE cfg 4 as a second, embedded record (`strong_cfg4`): ONE 200k x 200k problem;
-  ranks own aligned-row blocks of it (dense build in 25k-row chunks through the resident buffer), all-gather the candidate
-  lists, derive the common matching, and sweep disjoint triangle blocks of the one triangulation (flag all-gather + counter
-  all-reduce).  `--scaling strong --workload cfg4` runs that configuration as the main record instead.
-`--workload cfg5` (BASELINE cfg 5) is a different step -- whole sliding windows dealt to the ranks in runs of the plan, fp32 costs,
-  the window merge per rank with one exchange of the seam rows -- see same_amd/bench_cfg5.py; every line of the default workload -- at
-  1 rank or N -- carries it as the sub-record `cfg5`, measured in the same job after the timed region (on its ranks, contexts and
-  communicator; `--embed-cfg5 off` skips it).
 value = aligned-ref cell pairs covered per second by the whole job.
 
-`roofline` is for the dense kernel: algorithmic bytes s*N_r*rows + s*(T+2)*(N_r+rows) over its mean launch
-time, HIP events on the stream it runs on.  Ceilings (same kernel at T=0, memset, device copy) are measured AFTER the timed
-loop on the warm chip, `telemetry` is board power / shader clock sampled from sysfs while the dense kernel loops,
-`valu_floor_ms_at_held_clock` / `valu_busy_frac` price the kernel's 2T+5 fp64 instructions per output at that clock,
-`sweep` repeats the measurement at the type counts of the reference's real datasets.
-At N > 1 the line explains itself: `rccl` is what the communicator reports (ncclCommCount, not the launcher's word),
-`gather` times the all-gather on its own stream and against a second loop without it, `per_rank_dense_ms` shows slow dies.
-`cpu_baseline` times the CPU oracle (scalar C port of the reference's arithmetic, 1 thread) on a bounded row sample of
-the same workload, rank 0, N=1 only (section bench_oracle_legs at the end of this file; the line itself is put together by
-same_amd/bench_report.py).
+A plain run does what the headline needs and nothing more: set up, warm up, time the steps, write `--dump-outputs`, print the line.
+Its `roofline` is the dense kernel's own: algorithmic bytes s*N_r*rows + s*(T+2)*(N_r+rows) over its mean launch time,
+HIP events on the stream it runs on, from the timed steps.  At N > 1 the line also carries what the timed loop saw of the ranks:
+`rccl` is what the communicator reports (ncclCommCount, not the launcher's word), `gather` times the all-gather on its own stream,
+`per_rank_dense_ms` shows slow dies.
+
+`--full` adds, after the timed region, everything that takes runs of its own or checks the run (the line is put together by
+same_amd/bench_report.py either way):
+  * N = 1: ceilings (same kernel at T=0, memset, device copy) on the warm chip, `telemetry` (board power / shader clock sampled from
+    sysfs while the dense kernel loops; `valu_floor_ms_at_held_clock` / `valu_busy_frac` price the kernel's 2T+5 fp64 instructions per
+    output at that clock), the `sweep` of the measurement over the type counts of the reference's real datasets (see
+    same_amd/bench_extras.py), and `cpu_baseline`: the CPU oracle (scalar C port of the reference's arithmetic, 1 thread) timed on a
+    bounded row sample of the same workload, whose outputs double as the parity check of this run (section bench_oracle_legs at the
+    end of this file).
+  * N > 1: a second loop without the candidate-list gather (what the gather costs the step), the transport check of the gathered lists,
+    and BASELINE cfg 4 as a second, embedded record (`strong_cfg4`): ONE 200k x 200k problem; ranks own aligned-row blocks of it
+    (dense build in 25k-row chunks through the resident buffer), all-gather the candidate lists, derive the common matching, and
+    sweep disjoint triangle blocks of the one triangulation (flag all-gather + counter all-reduce).
+  * the sub-record `cfg5` (any N, the default workload): BASELINE cfg 5 measured in the same job (its ranks, contexts and
+    communicator; `--embed-cfg5 off` skips it, `--embed-cfg5 on` asks for it without `--full`).
+`--scaling strong --workload cfg4` runs cfg 4 as the main record instead.  `--workload cfg5` (BASELINE cfg 5) is a different step --
+whole sliding windows dealt to the ranks in runs of the plan, fp32 costs, the window merge per rank with one exchange of the seam
+rows -- and a line of its own with its diagnostic passes (see same_amd/bench_cfg5.py); `--full` does not change it.
 """
 import argparse
 import json
@@ -60,9 +65,16 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS))
     ap.add_argument("--scaling", default="weak", choices=("weak", "strong"))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip ceilings / telemetry leg / T sweep (profiling runs)")
-    ap.add_argument("--no-strong-record", action="store_true", help="N > 1: skip the embedded ONE-problem (cfg 4) record")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed loop, also measure and check what the headline does not need: ceilings, telemetry, T sweep "
+                         "and cpu_baseline with its parity check (N = 1), the loop without the gather, the transport check and the "
+                         "embedded cfg 4 record (N > 1), the embedded cfg5 record (any N)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="skip the cpu_baseline leg and its parity check (of a --full run, and of --workload cfg5)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="skip ceilings / telemetry leg / T sweep of a --full run, and the native_delaunay, api_path and amdahl passes "
+                         "of a cfg5 line or record (profiling runs)")
+    ap.add_argument("--no-strong-record", action="store_true", help="with --full, N > 1: skip the embedded ONE-problem (cfg 4) record")
     ap.add_argument("--cpu-sample-rows", type=int, default=20000)  # 10-20 s of single-thread oracle work at dense100k
     ap.add_argument("--tail-stream", default="own", choices=("own", "shared"),
                     help="own: prune / costs / triangle maps / sweeps run on a second context (stream) beside the dense build; "
@@ -77,7 +89,8 @@ def parse():
     ap.add_argument("--cfg5-cells", type=int, default=1_000_000, help="--workload cfg5: cells per section")
     ap.add_argument("--embed-cfg5", choices=("auto", "on", "off"), default="auto",
                     help="after the timed loop, run BASELINE cfg 5 (the step of `--workload cfg5`) on this job's ranks and embed its "
-                         "numbers as `cfg5` (auto: with the default workload at any rank count, and with cfg2 / cfg4 at N > 1)")
+                         "numbers as `cfg5` (auto: with --full, for the default workload at any rank count and for cfg2 / cfg4 at "
+                         "N > 1; on: also without --full)")
     ap.add_argument("--cfg5-pipeline", choices=("device", "frames"), default="device",
                     help="--workload cfg5: both run the product function same_amd.sliding_window_incumbent; 'device' on frames resident "
                          "on the GPU (two library calls per window), 'frames' through its general route on host frames (every window's "
@@ -136,7 +149,7 @@ def run_rank(args):
         mx = group.max(float(group.rank + 1))
         ranks = group.allgather_object({"rank": group.rank, "pid": os.getpid(), "id_ok": uid == bytes(range(128)),
                                         "local_world": qhull_pool.local_world()[0], "qhull_helpers": qhull_pool.default_workers()})
-        if group.rank == 0:
+        if group.rank == 0:   # the keys are those of an N > 1 line run with --full; a plain one carries no strong_cfg4 and no cfg5
             os.write(json_fd, (json.dumps({"dry_launch": True, "world": group.world, "max_of_rank_plus_1": mx, "ranks": ranks,
                                            "line_keys_at_n_gt_1": list(N_GT1_KEYS) + ["strong_cfg4"],
                                            "strong_record_keys": list(N_GT1_STRONG_KEYS)}) + "\n").encode())
@@ -181,10 +194,12 @@ def run_rank(args):
     gather = gather_hidden_ms = per_rank = parity_transport = strong_rec = None
     if comm is not None:
         gather_steps = list(prob.gather_ms)
-        steps_ng = max(1, min(args.steps, 5))
-        note(group, "second loop without the candidate-list gather")
-        dt_ng, _ = prob.timed_loop(steps_ng, 1, gather=False)       # the same step without the candidate-list gather
-        prob.gather_ms = gather_steps
+        dt_ng = steps_ng = None
+        if args.full:
+            steps_ng = max(1, min(args.steps, 5))
+            note(group, "second loop without the candidate-list gather")
+            dt_ng, _ = prob.timed_loop(steps_ng, 1, gather=False)   # the same step without the candidate-list gather
+            prob.gather_ms = gather_steps
         gather, gather_hidden_ms = gather_report(prob, dt, args.steps, dt_ng, steps_ng)
         mine = {"rank": group.rank, "device": ctx.device, "pci": ctx.pci_bus_id(), "dense_ms": stats3([m for m, _ in dense_ms]),
                 "gather_ms": stats3(gather_steps)}
@@ -193,32 +208,35 @@ def run_rank(args):
                     "dense_ms_by_rank": [r["dense_ms"][1] for r in every],
                     "gather_ms_by_rank": [(r["gather_ms"] or [None, None])[1] for r in every],
                     "device_by_rank": [r["device"] for r in every], "pci_by_rank": [r["pci"] for r in every]}
-        prob.step()                                                    # one more step WITH the gather: the lists the check reads
-        if group.rank == 0:
-            parity_transport = prob.transport_check()
-        note(group, f"gather {gather['ms']} ms per step on its stream; step {gather['step_ms_with_gather']:.3f} ms with it, "
-                    f"{gather['step_ms_without_gather']:.3f} ms without")
+        if args.full:
+            prob.step()                                                # one more step WITH the gather: the lists the check reads
+            if group.rank == 0:
+                parity_transport = prob.transport_check()
+            note(group, f"gather {gather['ms']} ms per step on its stream; step {gather['step_ms_with_gather']:.3f} ms with it, "
+                        f"{gather['step_ms_without_gather']:.3f} ms without")
+        else:
+            note(group, f"gather {gather['ms']} ms per step on its stream; step {gather['step_ms_with_gather']:.3f} ms with it")
 
-    # ---- after the timed region, rank 0 at N=1: ceilings, operating point, T sweep (all on the warm chip) ------------
-    match = prob.dmatch.download((n_mov,), np.int32)
+    # ---- --full, after the timed region, rank 0 at N=1: ceilings, operating point, T sweep (all on the warm chip) ------
+    match = prob.dmatch.download((n_mov,), np.int32) if args.full else None   # the matching the cpu_baseline leg sweeps under
     extras = {}
-    if group.rank == 0 and group.world == 1 and not args.no_extras and not strong:
+    if args.full and group.rank == 0 and group.world == 1 and not args.no_extras and not strong:
         from same_amd.bench_extras import measure_extras
 
         extras = measure_extras(args, env, prob, headline_buffer)      # may re-take the cost block spread over the HBM regions
         dD = prob.dD
 
-    # ---- CPU baseline leg (rank 0, N=1, untimed region): see bench_oracle_legs below ------------------------------------
+    # ---- --full, CPU baseline leg (rank 0, N=1, untimed region): see bench_oracle_legs below ------------------------------
     cpu = None
-    parity = parity_transport or ("not checked in this run (the oracle only runs in the cpu_baseline leg: N=1 without "
-                                  "--no-cpu-baseline)")
-    if group.rank == 0 and group.world == 1 and not args.no_cpu_baseline:
+    parity = parity_transport or ("not checked in this run (the checks run with --full: the oracle in the cpu_baseline leg at N=1 "
+                                  "without --no-cpu-baseline, the transport check at N > 1)")
+    if args.full and group.rank == 0 and group.world == 1 and not args.no_cpu_baseline:
         cpu, parity = dense_oracle_leg(args, group, ctx, prob, match, rebuild_first_chunk=bool(strong or extras))
         if parity_transport:
             parity += "; " + parity_transport
 
-    # ---- N > 1, weak run: BASELINE cfg 4 as an embedded record (ONE problem over the ranks; the resident block is reused) ----
-    if comm is not None and not strong and not args.no_strong_record:
+    # ---- --full, N > 1, weak run: BASELINE cfg 4 as an embedded record (ONE problem over the ranks; the resident block is reused) ----
+    if args.full and comm is not None and not strong and not args.no_strong_record:
         sname = STRONG_OF.get(args.workload, args.workload)
         note(group, f"embedded strong record: {sname} as ONE problem over {group.world} rank(s)")
         prob.close(keep_dense=True)
@@ -240,8 +258,9 @@ def run_rank(args):
 
     # ---- BASELINE cfg 5 as an embedded record, IN THIS JOB (its ranks, their contexts, the communicator): the same at 1 rank or 8 ----
     cfg5_rec = None
-    # auto: the default workload at any rank count, and every full-size workload at N > 1 (`tiny` is the test suite's: it asks with "on")
-    want_cfg5 = args.embed_cfg5 == "on" or (args.embed_cfg5 == "auto" and not strong and not args.no_extras
+    # auto, with --full: the default workload at any rank count, and every full-size workload at N > 1 (`tiny` is the test suite's: it
+    # asks with "on")
+    want_cfg5 = args.embed_cfg5 == "on" or (args.embed_cfg5 == "auto" and args.full and not strong and not args.no_extras
                                             and (args.workload == "dense100k" or (group.world > 1 and args.workload != "tiny")))
     if want_cfg5:
         from same_amd import bench_cfg5

@@ -260,7 +260,7 @@ def test_run_same_eager_mode_matches_reference_model(gp, tmp_path):
 
 @pytest.mark.parametrize("force_comm", [False, True])
 def test_bench_contract_line(force_comm):
-    """bench.py prints ONE JSON line carrying the driver's keys plus roofline and cpu_baseline (tiny workload; with the
+    """bench.py --full prints ONE JSON line carrying the driver's keys plus roofline and cpu_baseline (tiny workload; with the
     RCCL branch forced through a size-1 communicator in the second case)."""
     import json
     import os
@@ -271,7 +271,7 @@ def test_bench_contract_line(force_comm):
     env = dict(os.environ)
     if force_comm:
         env["SAME_BENCH_FORCE_COMM"] = "1"
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--workload", "tiny", "--steps", "2", "--warmup", "1"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--workload", "tiny", "--steps", "2", "--warmup", "1", "--full"]
     if force_comm:
         cmd.append("--no-cpu-baseline")
     res = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
@@ -313,6 +313,42 @@ def test_bench_contract_line(force_comm):
         assert ("f64", 3) in kinds and ("f32", 20) in kinds and ("q32->f64", 20) in kinds
         q = [e for e in rf["sweep"] if e["dtype"] == "q32->f64"][0]
         assert q["opt_in"] is True and q["max_rel_diff_vs_exact_on_16_rows"] <= 1e-6
+
+
+@pytest.mark.parametrize("force_comm", [False, True])
+def test_bench_plain_line_is_the_headline_alone(force_comm):
+    """bench.py without --full: the same headline keys, the roofline of the timed launches, and nothing measured or checked after the
+    timed region -- no ceilings, telemetry, T sweep, cpu_baseline, embedded records or loop without the gather."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    if force_comm:
+        env["SAME_BENCH_FORCE_COMM"] = "1"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--workload", "tiny", "--steps", "2", "--warmup", "1"]
+    res = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["metric"] == json.load(open(os.path.join(root, "BASELINE.json"), encoding="utf-8"))["metric"]
+    assert out["value"] > 0 and out["unit"] == "cell-pairs/s" and out["higher_is_better"] is True and out["dtype"] == "f64"
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0
+    rf = out["roofline"]
+    assert rf["bound"] == "hbm" and rf["launches_timed"] == 2 and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-12
+    assert not {"measured_ceilings", "telemetry", "sweep", "pruned_path", "realistic_matching"} & set(rf)
+    assert out["cpu_baseline"] is None and out["parity_spot_check"].startswith("not checked in this run")
+    assert "cfg5" not in out and "strong_record" not in out and "ceilings, telemetry" not in res.stderr
+    if force_comm:
+        g = out["gather"]
+        assert out["rccl"]["nranks"] == 1 and g["ms"] is not None and g["step_ms_with_gather"] > 0
+        assert g["step_ms_without_gather"] is None and g["steps_without_gather"] == 0 and out["gather_hidden_ms"] is None
+        assert "second loop" not in res.stderr
+    else:
+        assert "rccl" not in out and "gather" not in out
 
 
 def test_bench_dump_outputs_are_the_last_steps_outputs(tmp_path):
@@ -389,7 +425,7 @@ def _check_multi_rank_keys(out, world, kind):
 
 
 def test_bench_two_ranks_on_one_gpu_carry_the_diagnosis():
-    """`bench.py --gpus 2` on this one GPU (RCCL refuses two ranks on one device, so the exchanges go through the host
+    """`bench.py --gpus 2 --full` on this one GPU (RCCL refuses two ranks on one device, so the exchanges go through the host
     transport): the line carries every key the 8-GPU run needs to explain itself, and the embedded ONE-problem record."""
     import json
     import os
@@ -400,7 +436,7 @@ def test_bench_two_ranks_on_one_gpu_carry_the_diagnosis():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "SAME_RDV_DIR")}
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--workload", "tiny", "--steps", "3", "--warmup",
                           "1",
-                          "--no-cpu-baseline"], env=env, cwd=root, capture_output=True, text=True, timeout=900)
+                          "--no-cpu-baseline", "--full"], env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1
@@ -662,7 +698,7 @@ def test_bench_line_embeds_a_cfg5_record(world):
 
 
 def test_bench_step_with_the_fixed_point_dense_build():
-    """`bench.py --dense q32`: the step's dense build is the opt-in fixed-point kernel; the line says so (dtype, kernel name, note)
+    """`bench.py --dense q32 --full`: the step's dense build is the opt-in fixed-point kernel; the line says so (dtype, kernel name, note)
     and its own check -- twin-equal and within 1e-6 relative of the exact costs on every sampled pair -- passed."""
     import json
     import os
@@ -672,7 +708,7 @@ def test_bench_step_with_the_fixed_point_dense_build():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "tiny", "--steps", "2", "--warmup", "1",
                           "--dense", "q32",
-                          "--no-extras"], cwd=root, capture_output=True, text=True, timeout=600)
+                          "--no-extras", "--full"], cwd=root, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     out = json.loads([ln for ln in res.stdout.splitlines() if ln.strip()][0])
     assert out["dtype"] == "u32+f64" and "dense_cost_q32_kernel" in out["roofline"]["kernel"] and "--dense q32" in out["roofline"]["note"]

@@ -7,7 +7,7 @@ out=gpurun_out/$tag; mkdir -p $out
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 run() { name=$1; shift; echo "== $name" && timeout -k 10 500 "$@" > $out/$name.json 2> $out/$name.err || { tail -20 $out/$name.err; exit 1; }; }
 run cfg5_2ranks_one_gpu python3 bench.py --gpus 2 --workload cfg5 --steps 3 --warmup 1
-run torchrun_2ranks_with_cfg5_record python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 5 --warmup 2
+run torchrun_2ranks_with_cfg5_record python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 5 --warmup 2 --full
 run cfg5_frames python3 bench.py --workload cfg5 --cfg5-pipeline frames --steps 2 --warmup 1
 run cfg5_4m_cells python3 bench.py --workload cfg5 --cfg5-cells 4000000 --steps 2 --warmup 1
 run cfg5_20_steps python3 bench.py --workload cfg5 --steps 20 --warmup 1 --no-extras

@@ -6,9 +6,9 @@ tag=${1:-visit_q32}
 root=$PWD
 out=$root/gpurun_out/$tag
 mkdir -p $out
-echo "== bench --dense q32" && timeout -k 10 600 python3 bench.py --steps 20 --warmup 5 --dense q32 > $out/bench_q32.json 2> $out/bench_q32.err || { tail -20 $out/bench_q32.err; exit 1; }
+echo "== bench --dense q32" && timeout -k 10 600 python3 bench.py --steps 20 --warmup 5 --dense q32 --full > $out/bench_q32.json 2> $out/bench_q32.err || { tail -20 $out/bench_q32.err; exit 1; }
 tail -2 $out/bench_q32.err
-echo "== bench default (same box)" && timeout -k 10 600 python3 bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
+echo "== bench default (same box)" && timeout -k 10 600 python3 bench.py --steps 20 --warmup 5 --full > $out/bench.json 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
 echo "== dense probes" && timeout -k 10 300 python3 tools/dense_probe.py 100000 0,3,8,12,16,20,24,32 > $out/dense_probe_f64.log 2>&1 && timeout -k 10 300 python3 tools/dense_probe.py 100000 0,8,20,32 q32 > $out/dense_probe_q32.log 2>&1 && timeout -k 10 300 python3 tools/dense_probe.py 100000 0,8,20 f32 > $out/dense_probe_f32.log 2>&1 || { tail -5 $out/dense_probe_*.log; exit 1; }
 tail -n 4 $out/dense_probe_f64.log $out/dense_probe_q32.log $out/dense_probe_f32.log
 echo "== energy table" && timeout -k 10 400 python3 tools/energy_table.py > $out/energy_table.md 2> $out/energy_table.err || { tail -5 $out/energy_table.err; exit 1; }

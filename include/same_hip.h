@@ -451,6 +451,27 @@ int same_window_filter_finish(same_window *const *windows, int n_windows, int so
                               int32_t *out_match_row, uint8_t *out_point_flag, int64_t *out_stats, int64_t *out_counts);
 int same_window_refinish(same_window *window, const int32_t *match_pair, double no_match_penalty, int64_t refine_rounds_cap,
                          double delaunay_penalty, int32_t *out_match_row, uint8_t *out_point_flag, int64_t *out_stats);
+/* The same two calls with the model's reference capacities in the search (csrc/refine.hip): reference j of a window may take up to
+ * limit_j of its kept cells, each match after the first priced penalty_coeff (src/helpers.py:102-161, src/same.py:1191-1196).  limit_j
+ * = max_matches * M when the window's frame of the references its pairs name holds a cell of size > 1 and j's size is > 1, else
+ * max_matches; M = multiplier, or int(the frame's largest size) when multiplier is 0 (None); at most 1001 (p_j <= 1000).  The sizes are
+ * the reference section's.  capacity NULL, or refine_rounds_cap 0: exactly the calls above.  out_stats holds SAME_WINDOW_STATS_CAP words
+ * per window: the 15 above, then sum_j max(0, count_j - 1) of the search's result.  max_matches >= 1, multiplier >= 0, penalty_coeff
+ * finite and >= 0, else SAME_EINVAL before any device work.  With every limit 1 the search is hip_refine="local" bit for bit. */
+typedef struct same_window_capacity {
+    int64_t max_matches;
+    int64_t multiplier;       /* 0 = None */
+    double penalty_coeff;
+} same_window_capacity;
+#define SAME_WINDOW_STATS_CAP 16
+int same_window_filter_finish_cap(same_window *const *windows, int n_windows, int source, const int32_t *simplices,
+                                  const int64_t *simplex_offsets, double radius, int angle_enabled, double cos_thr, double near_tol,
+                                  int ignore_same_type, int ensure_min_triangle_per_node, double no_match_penalty, int incumbent,
+                                  int64_t refine_rounds_cap, double delaunay_penalty, const same_window_capacity *capacity,
+                                  int32_t *out_match_row, uint8_t *out_point_flag, int64_t *out_stats, int64_t *out_counts);
+int same_window_refinish_cap(same_window *window, const int32_t *match_pair, double no_match_penalty, int64_t refine_rounds_cap,
+                             double delaunay_penalty, const same_window_capacity *capacity, int32_t *out_match_row,
+                             uint8_t *out_point_flag, int64_t *out_stats);
 
 /* ---- a6 on the window path without the library call --------------------------------------------------------------------------
  * The reference triangulates every window's kept aligned cells with scipy.spatial.Delaunay (Qhull; src/same.py:1023), on the host
@@ -512,7 +533,8 @@ int same_sparse_assign(same_ctx *ctx, const int32_t *pairs, const double *costs,
                        int64_t n_r, int32_t *out_match_pair, int64_t *out_stats);
 
 /* ---- the local search on the lazy model's objective (csrc/refine.hip): from a window's one-to-one incumbent, moves that lower
- *   sum_p c_p x_p + no_match_penalty sum_i size_i n_i + delaunay_penalty sum_t w_t q_t        (src/same.py:1191-1196; p_j = 0)
+ *   sum_p c_p x_p + no_match_penalty sum_i size_i n_i + delaunay_penalty sum_t w_t q_t        (src/same.py:1191-1196; p_j = 0;
+ *   the _cap entry points below add penalty_coeff sum_j p_j with the model's reference capacities)
  * over the window's kept aligned cells, their pairs and the kept triangles; w_t = the corners' size sum (:1128-1134), q_t = 1 when the
  * lazy body (:645-669) sees t flip.  Moves: a matched cell to a free candidate reference, an unmatched cell to a free candidate, a cell to
  * unmatched, two matched cells swapping references (both crossed pairs candidates).  Rounds: every cell proposes its best improving
@@ -526,6 +548,15 @@ int same_sparse_assign(same_ctx *ctx, const int32_t *pairs, const double *costs,
 int same_refine_matching(same_ctx *ctx, const int32_t *pairs, const double *costs, int64_t P, const double *unmatched, int64_t n_m,
                          int64_t n_r, const int32_t *tris, int64_t Tr, const double *axy, const double *ref_xy, const double *size,
                          double delaunay_penalty, int64_t rounds_cap, int32_t *match_pair_inout, int64_t *out_stats);
+/*   same_refine_matching_cap: the same search with reference capacities: ref_limit[n_r] (1 .. 1001) matches per reference, each after
+ *     the first priced penalty_coeff (finite, >= 0) -- the objective gains penalty_coeff sum_j max(0, count_j - 1).  Moves go to
+ *     references with room (count < limit); a swap partner is a reference's only holder.  match_pair_inout may hold a reference up to
+ *     its limit.  out_stats[6] = the five words above, then sum_j max(0, count_j - 1) of the result.  All limits 1 and penalty_coeff
+ *     anything: same_refine_matching bit for bit. */
+int same_refine_matching_cap(same_ctx *ctx, const int32_t *pairs, const double *costs, int64_t P, const double *unmatched, int64_t n_m,
+                             int64_t n_r, const int32_t *tris, int64_t Tr, const double *axy, const double *ref_xy, const double *size,
+                             double delaunay_penalty, const int32_t *ref_limit, double penalty_coeff, int64_t rounds_cap,
+                             int32_t *match_pair_inout, int64_t *out_stats);
 
 /* ---- f3 on the window path: the window merge where the windows' matches are ------------------------------------------------
  * The reference trims every window's match table to the window's central region (src/same.py:565-582), concatenates the tables and

@@ -105,11 +105,16 @@ _PROTOTYPES = {
     "same_window_filter_finish": [c_vp, c_int, c_int, c_vp, c_vp, c_dbl, c_int, c_dbl, c_dbl, c_int, c_int, c_dbl, c_int, c_i64, c_dbl, c_vp, c_vp,
                                   c_vp, c_vp],
     "same_window_refinish": [c_vp, c_vp, c_dbl, c_i64, c_dbl, c_vp, c_vp, c_vp],
+    "same_window_filter_finish_cap": [c_vp, c_int, c_int, c_vp, c_vp, c_dbl, c_int, c_dbl, c_dbl, c_int, c_int, c_dbl, c_int, c_i64, c_dbl,
+                                      c_vp, c_vp, c_vp, c_vp, c_vp],
+    "same_window_refinish_cap": [c_vp, c_vp, c_dbl, c_i64, c_dbl, c_vp, c_vp, c_vp, c_vp],
     "same_merge_dedup": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, ctypes.POINTER(c_i64)],
     "same_delaunay2d": [c_vp, c_i64, c_vp, c_i64, ctypes.POINTER(c_i64), c_dbl, ctypes.POINTER(c_dbl)],
     "same_window_delaunay": [c_vp, c_int, c_dbl, c_int, c_dbl, c_dbl, c_vp, c_vp],
     "same_sparse_assign": [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp],
     "same_refine_matching": [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_dbl, c_i64, c_vp, c_vp],
+    "same_refine_matching_cap": [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_dbl, c_vp, c_dbl, c_i64,
+                                 c_vp, c_vp],
     "same_delaunay_filtered": [c_vp, c_vp, c_i64, c_dbl, c_int, c_dbl, c_dbl, c_vp, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(c_int)],
     "same_section_set_codes": [c_vp, c_vp, c_i64],
     "same_merge_acc_create": [c_vp, ctypes.POINTER(c_vp)],
@@ -147,6 +152,12 @@ SAME_DD_FEW_POINTS, SAME_DD_NO_ANGLE, SAME_DD_NONFINITE, SAME_DD_IN_DOUBT, SAME_
 SAME_TRIS_SIMPLICES, SAME_TRIS_KEPT, SAME_TRIS_DEVICE = 0, 1, 2
 SAME_INCUMBENT_GREEDY, SAME_INCUMBENT_ASSIGNMENT = 0, 1
 SAME_WINDOW_STATS = 15
+SAME_WINDOW_STATS_CAP = 16       # the _cap calls: the 15 words, then sum_j max(0, count_j - 1) of the search's result
+
+
+class WindowCapacity(ctypes.Structure):
+    """same_window_capacity (include/same_hip.h)"""
+    _fields_ = [("max_matches", ctypes.c_int64), ("multiplier", ctypes.c_int64), ("penalty_coeff", ctypes.c_double)]
 
 
 class SameHipError(RuntimeError):

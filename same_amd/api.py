@@ -470,6 +470,17 @@ def _run_same(ref_df, aligned_df, commonCT, outprefix, aligned_delaunay, aligned
             pass
 
 
+def ref_match_limits(ref_df, max_matches, multiplier):
+    """-> the right-hand side of every `max_matches_{j}` constraint (src/helpers.py:102-161), one per row of `ref_df` (the model's
+    post-KNN reference frame): multiplier * max_matches for a row of size > 1 when the frame holds one, else max_matches; a None
+    multiplier is int(the frame's largest size).  A list of the reference's own values (Python ints where its inputs are)."""
+    rsize = ref_df["size"].to_numpy() if "size" in ref_df.columns else None
+    has_meta = rsize is not None and bool((rsize > 1).any())
+    if has_meta and multiplier is None:
+        multiplier = int(rsize.max())
+    return [multiplier * max_matches if (has_meta and rsize[j] > 1) else max_matches for j in range(len(ref_df))]
+
+
 def _add_basic_constraints(model, quicksum, valid_pairs, max_matches, x, penalty_vars, no_match_vars, ref_df, multiplier):
     """Assignment constraints in the order and with the names of src/helpers.py:102-161."""
     pairs = np.asarray(valid_pairs, dtype=np.int64).reshape(-1, 2)
@@ -477,13 +488,9 @@ def _add_basic_constraints(model, quicksum, valid_pairs, max_matches, x, penalty
     for idx, (ip, jp) in enumerate(pairs.tolist()):
         by_ref.setdefault(jp, []).append(idx)
         by_aligned.setdefault(ip, []).append(idx)
-    rsize = ref_df["size"].to_numpy() if "size" in ref_df.columns else None
-    has_meta = rsize is not None and bool((rsize > 1).any())
-    if has_meta and multiplier is None:
-        multiplier = int(rsize.max())
+    limits = ref_match_limits(ref_df, max_matches, multiplier)
     for j, idxs in by_ref.items():
-        limit = multiplier * max_matches if (has_meta and rsize[j] > 1) else max_matches
-        model.addConstr(quicksum(x[i] for i in idxs) <= limit, name=f"max_matches_{j}")
+        model.addConstr(quicksum(x[i] for i in idxs) <= limits[j], name=f"max_matches_{j}")
     model.update()
     for i, idxs in by_aligned.items():
         model.addConstr(quicksum(x[q] for q in idxs) <= 1, name=f"one_match_{i}")

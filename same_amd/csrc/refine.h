@@ -7,20 +7,24 @@ namespace rfn {
 
 // the search's control words (on the device; the window path keeps them in its finish block, so they come back with it):
 // productive rounds, moves applied, settled (a round found no winner), winners of the round in progress, blocks of the apply launch
-// done, objective at the start and now (fp64 bits)
-enum { RC_ROUNDS = 0, RC_MOVES = 1, RC_SETTLED = 2, RC_WIN = 3, RC_DONE = 4, RC_OBJ0 = 5, RC_OBJ = 6, RC_COUNT = 8 };
+// done, objective at the start and now (fp64 bits), sum_j max(0, count_j - 1) of the matching the objective was last taken of
+enum { RC_ROUNDS = 0, RC_MOVES = 1, RC_SETTLED = 2, RC_WIN = 3, RC_DONE = 4, RC_OBJ0 = 5, RC_OBJ = 6, RC_EXTRA = 7, RC_COUNT = 8 };
+constexpr int32_t MAX_LIMIT = 1001;       // count_j <= 1 + the upper bound 1000 of p_j (src/same.py:1117)
 
 constexpr int FIRST_ROUNDS = 4;          // rounds enqueued before the first look (cfg 5: at most 2 productive + the settling one)
 constexpr double EPS = 0x1p-40;          // a move improves when delta < -EPS * scale (the assignment certificate's bound)
 
-// a cell's proposal: key (~0 = none), its new pair (-1 = unmatched), the swap partner (-1 = none) and the partner's new pair
+// a cell's proposal: key (~0 = none), its new pair (-1 = unmatched), the swap partner (-1 = none), the partner's new pair and the
+// cell's pair when it proposed (-1 = unmatched)
 struct Prop {
     unsigned long long key;
-    int32_t p_i, k, p_k, pad;
+    int32_t p_i, k, p_k, p_o;
 };
 
 // one problem: cells 0..n-1 with their pairs a contiguous run prow[i] .. prow[i+1] (reference = pairs[2 p + 1] in 0..n_r-1, each
-// reference at most once per cell); the kept triangles over the cells; the start matching (pair per cell, -1 = none, one-to-one)
+// reference at most once per cell); the kept triangles over the cells; the start matching (pair per cell, -1 = none), which holds
+// every reference at most its limit times.  Limits: limit_in[n_r] (host form), or from the reference section's sizes (the window
+// path: rsize non-null, the model's rule src/helpers.py:102-161 over the references the pairs name), or 1 each (one-to-one).
 struct RefineArgs {
     const int32_t *prow = nullptr, *pairs = nullptr;
     const double *cost = nullptr;         // per pair
@@ -35,9 +39,16 @@ struct RefineArgs {
     int64_t n = 0, n_r = 0, cap_tr = 0, cap = 0;
     const int32_t *start = nullptr;       // [n]
     unsigned long long *ctrl = nullptr;   // [RC_COUNT], zeroed by the setup
+    double pc = 0.0;                      // penalty_coeff: the price of every match of a reference after its first
+    const int32_t *limit_in = nullptr;    // [n_r] matches each reference may take (1 .. MAX_LIMIT), or null: see above
+    const double *rsize = nullptr;        // the window path's capacity: reference section sizes, at ref_rows[j] for reference j and
+    const int32_t *ref_rows = nullptr;    // at ref_row[p] for pair p's; P pairs
+    int64_t P = 0, max_matches = 1, multiplier = 0;   // multiplier 0 = None (the frame's largest size)
     // the work arrays (carve)
     int32_t *match = nullptr;             // [n] the search's matching (its result)
-    int32_t *owner = nullptr;             // [n_r] cell holding each reference, -1 = free
+    int32_t *count = nullptr;             // [n_r] cells holding each reference
+    long long *hsum = nullptr;            // [n_r] sum of their ids: THE holder where count is 1 (the only swap partners)
+    int32_t *limit = nullptr;             // [n_r]
     int32_t *tsort = nullptr;             // [cap_tr][3] corners sorted ascending
     int8_t *tsign = nullptr;              // [cap_tr] source sign over the sorted corners
     double *tw = nullptr;                 // [cap_tr] weight: size sum over the sorted corners

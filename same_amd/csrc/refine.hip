@@ -4,20 +4,28 @@
 //
 // over the window's kept aligned cells, their pairs and the kept triangles.  w_t is the size sum of the triangle's corners (:1128-1134);
 // q_t = 1 when the lazy body (:645-669) sees t flip: all three corners matched, neither the source nor the reference sign zero, the
-// signs different.  The matching stays one-to-one like both starts, so p_j = 0 (a feasible point of the model for any max_matches).
+// signs different.  Reference j may hold up to limit_j cells (max_matches, or max_matches * the metacell multiplier; at most 1001, the
+// bound of p_j); p_j = max(0, count_j - 1).  With every limit 1 (hip_refine="local") the matching stays one-to-one like both starts and
+// p_j = 0.  Each reference keeps its count and the sum of its holders' ids, which names THE holder where the count is 1: only such
+// references offer a swap partner.
 //
-// Moves of one cell i, each evaluated exactly against the current state: to a free candidate reference, from unmatched to a free
-// candidate, to unmatched, and the swap of the references of two matched cells i < k when both crossed pairs are candidates (the swap
-// belongs to the lower cell).  A move's delta only involves the triangles incident to the cells it moves:
-//   delta = delaunay_penalty * F + (new cost terms - old cost terms),  F = sum over those triangles of +-w_t where q_t changes
-// (F first, in the canonical incidence order, exact for integer sizes; one product; then the cost terms).  It improves when
-// delta < -2^-40 * scale, scale = delaunay_penalty * (sum of the w_t looked at) + |new terms| + |old terms|: rounding never counts as
-// an improvement, so the search cannot cycle.
+// Moves of one cell i, each evaluated exactly against the current state: to a candidate reference with room (count < limit), from
+// unmatched to one, to unmatched, and the swap of the references of two matched cells i < k when both crossed pairs are candidates and
+// k holds its reference alone, with room or not (the swap belongs to the lower cell; two cells on one reference never swap).  Per
+// candidate the move comes before the swap.  A move's delta only
+// involves the triangles incident to the cells it moves and the counts of the references it leaves and takes:
+//   delta = delaunay_penalty * F + (new cost terms - old cost terms) + penalty_coeff * (dn - do),  F = sum over those triangles of
+// +-w_t where q_t changes, dn = 1 when the new reference is held already, do = 1 when the old one is held twice or more (swaps keep
+// every count: dn = do = 0) (F first, in the canonical incidence order, exact for integer sizes; one product; then the cost terms; then
+// the penalty).  It improves when delta < -2^-40 * scale, scale = delaunay_penalty * (sum of the w_t looked at) + |new terms| +
+// |old terms| + penalty_coeff * (dn + do): rounding never counts as an improvement, so the search cannot cycle.
 //
 // A ROUND: every cell proposes its best improving move (ties: the first in pair order, unmatching before every pair).  Its key is
 // (the delta rounded to float, ordered | cell), and it is written by atomicMin to every slot of its FOOTPRINT: the closed 1-ring of every
-// cell it moves in the kept-triangle graph, and the references it takes.  A move whose key is the minimum on all of them WINS.  Winners
-// share no triangle and no reference, so their deltas add up exactly and the objective never goes up; the smallest key always wins, so a
+// cell it moves in the kept-triangle graph, the references it takes and the one it leaves.  A move whose key is the minimum on all of
+// them WINS.  Winners share no triangle and no reference, so their deltas add up exactly (each reference's count changes by one move at
+// most) and the objective never goes up -- and the apply kernel updates counts with plain stores.  Under limit 1 no other proposal
+// claims a held reference but its holder's, so the old slot changes no round's winners.  The smallest key always wins, so a
 // round without a winner is a round without an improving move (SETTLED).  The result depends on the input alone -- not on scheduling or
 // block shape -- and only on the SET of triangles: each cell's incident triangles are listed by their sorted corner rows and every sign
 // and weight is taken over sorted corners.
@@ -39,6 +47,7 @@ constexpr unsigned long long NONE = ~0ull;
 __device__ __forceinline__ int32_t col_of(const RefineArgs &w, int32_t p) { return w.pairs[2 * (int64_t)p + 1]; }
 __device__ __forceinline__ double2_t ref_of(const RefineArgs &w, int32_t p) { return ld2(w.ref_xy, w.ref_row ? w.ref_row[p] : col_of(w, p)); }
 __device__ __forceinline__ double unm_of(const RefineArgs &w, int64_t i) { return w.unm ? w.unm[i] : w.penalty * w.size[i]; }
+__device__ __forceinline__ bool room(const RefineArgs &w, int32_t j) { return w.count[j] < w.limit[j]; }
 __device__ __forceinline__ unsigned long long ld_ctrl(const RefineArgs &w, int q) {
     return __hip_atomic_load(w.ctrl + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -81,13 +90,14 @@ __device__ __forceinline__ void flip_part(const RefineArgs &w, int32_t c, int32_
 struct Delta {
     double d, scale;
 };
-// cell i from its pair to pair pn (-1 = unmatched)
+// cell i from its pair to pair pn (-1 = unmatched); the penalty terms are 0.0 under limit 1, and adding them keeps every bit
 __device__ __forceinline__ Delta delta_single(const RefineArgs &w, int32_t i, int32_t pn) {
     double F = 0.0, W = 0.0;
     flip_part(w, i, -1, i, pn, -1, 0, F, W);
     const int32_t po = w.match[i];
     const double nw = pn >= 0 ? w.cost[pn] : unm_of(w, i), old = po >= 0 ? w.cost[po] : unm_of(w, i);
-    return Delta{w.dp * F + (nw - old), w.dp * W + (fabs(nw) + fabs(old))};
+    const int dn = pn >= 0 && w.count[col_of(w, pn)] >= 1, dold = po >= 0 && w.count[col_of(w, po)] >= 2;
+    return Delta{w.dp * F + (nw - old) + w.pc * (double)(dn - dold), w.dp * W + (fabs(nw) + fabs(old)) + w.pc * (double)(dn + dold)};
 }
 // cells i < k exchange their references: i to pair pi, k to pair pk
 __device__ __forceinline__ Delta delta_swap(const RefineArgs &w, int32_t i, int32_t pi, int32_t k, int32_t pk) {
@@ -126,11 +136,41 @@ __device__ __forceinline__ bool each_slot(const RefineArgs &w, int32_t i, const 
         all &= f(w.n + col_of(w, pr.p_k));
     }
     if (pr.p_i >= 0) all &= f(w.n + col_of(w, pr.p_i));
+    if (pr.k < 0 && pr.p_o >= 0) all &= f(w.n + col_of(w, pr.p_o));
     return all;
 }
 
 // ---- setup ---------------------------------------------------------------------------------------------------------------------
-// the matching from the start, counters and claim slots cleared, no reference held
+// the window path's limits (src/helpers.py:102-161) over the frame of the references its pairs name: one block per window
+constexpr int LIM_NT = 1024;
+__global__ __launch_bounds__(LIM_NT) void refine_limit_kernel(Batch<RefineArgs> b) {
+    const RefineArgs &w = b.w[blockIdx.y];
+    if (!w.rsize) return;
+    double mx = 0.0;
+    bool meta = false;
+    for (int64_t p = threadIdx.x; p < w.P; p += LIM_NT) {
+        const double s = w.rsize[w.ref_row[p]];
+        meta = meta || s > 1.0;
+        mx = fmax(mx, s);
+    }
+    for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_down(mx, o, 64));
+    const bool any_meta = __syncthreads_or(meta);
+    __shared__ double pm[LIM_NT / 64];
+    if ((threadIdx.x & 63) == 0) pm[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    double mult = (double)w.multiplier;
+    if (w.multiplier <= 0) {          // None: int(max size) over the frame
+        mult = 0.0;
+        for (int q = 0; q < LIM_NT / 64; ++q) mult = fmax(mult, pm[q]);
+        mult = trunc(mult);
+    }
+    // every product is of integers; it is compared with MAX_LIMIT, so fp64 is exact wherever it matters
+    const double big = fmin(mult * (double)w.max_matches, (double)rfn::MAX_LIMIT);
+    const int32_t plain = (int32_t)std::min<int64_t>(w.max_matches, rfn::MAX_LIMIT);
+    for (int64_t j = threadIdx.x; j < w.n_r; j += LIM_NT)
+        w.limit[j] = any_meta && w.rsize[w.ref_rows[j]] > 1.0 ? (int32_t)big : plain;
+}
+// the matching from the start, counters and claim slots cleared, no reference held (the limits: given or 1, unless the window's)
 __global__ __launch_bounds__(256) void refine_init_kernel(Batch<RefineArgs> b) {
     const RefineArgs &w = b.w[blockIdx.y];
     const int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -139,7 +179,11 @@ __global__ __launch_bounds__(256) void refine_init_kernel(Batch<RefineArgs> b) {
         w.deg[x] = 0;
         w.cur[x] = 0;
     }
-    if (x < w.n_r) w.owner[x] = -1;
+    if (x < w.n_r) {
+        w.count[x] = 0;
+        w.hsum[x] = 0;
+        if (!w.rsize) w.limit[x] = w.limit_in ? w.limit_in[x] : 1;
+    }
     if (x < w.n + w.n_r) w.slot[0][x] = w.slot[1][x] = NONE;
     if (x < (int64_t)scan::blocks_for(w.n)) w.st[x] = 0;
     if (x < rfn::RC_COUNT) w.ctrl[x] = 0;
@@ -148,7 +192,11 @@ __global__ __launch_bounds__(256) void refine_init_kernel(Batch<RefineArgs> b) {
 __global__ __launch_bounds__(256) void refine_tri_kernel(Batch<RefineArgs> b) {
     const RefineArgs &w = b.w[blockIdx.y];
     const int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (x < w.n && w.match[x] >= 0) w.owner[col_of(w, w.match[x])] = (int32_t)x;
+    if (x < w.n && w.match[x] >= 0) {
+        const int32_t j = col_of(w, w.match[x]);
+        atomicAdd(&w.count[j], 1);
+        atomicAdd(reinterpret_cast<unsigned long long *>(&w.hsum[j]), (unsigned long long)x);
+    }
     if (x >= n_tris(w)) return;
     int32_t a = w.tris[3 * x], c1 = w.tris[3 * x + 1], c2 = w.tris[3 * x + 2], t;
     if (a > c1) { t = a; a = c1; c1 = t; }
@@ -215,28 +263,38 @@ constexpr int OBJ_NT = 1024;
 __global__ __launch_bounds__(OBJ_NT) void refine_objective_kernel(Batch<RefineArgs> b, int which) {
     const RefineArgs &w = b.w[blockIdx.y];
     double c = 0.0, f = 0.0;
+    unsigned long long e = 0;
     for (int64_t i = threadIdx.x; i < w.n; i += OBJ_NT) c += w.match[i] >= 0 ? w.cost[w.match[i]] : unm_of(w, i);
     const int64_t Tr = n_tris(w);
     for (int64_t t = threadIdx.x; t < Tr; t += OBJ_NT)
         if (flips(w, (int32_t)t, -1, 0, -1, 0)) f += w.tw[t];
+    for (int64_t j = threadIdx.x; j < w.n_r; j += OBJ_NT)
+        if (w.count[j] > 1) e += (unsigned long long)(w.count[j] - 1);
     for (int o = 32; o > 0; o >>= 1) {
         c += __shfl_down(c, o, 64);
         f += __shfl_down(f, o, 64);
+        e += __shfl_down(e, o, 64);
     }
     __shared__ double pc[OBJ_NT / 64], pf[OBJ_NT / 64];
+    __shared__ unsigned long long pe[OBJ_NT / 64];
     if ((threadIdx.x & 63) == 0) {
         pc[threadIdx.x >> 6] = c;
         pf[threadIdx.x >> 6] = f;
+        pe[threadIdx.x >> 6] = e;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
         double cs = 0.0, fs = 0.0;
+        unsigned long long es = 0;
         for (int q = 0; q < OBJ_NT / 64; ++q) {
             cs += pc[q];
             fs += pf[q];
+            es += pe[q];
         }
-        const double obj = cs + w.dp * fs;
+        double obj = cs + w.dp * fs;
+        if (es) obj += w.pc * (double)es;      // last: a one-to-one matching's objective keeps its bits
         w.ctrl[which] = (unsigned long long)__double_as_longlong(obj);
+        w.ctrl[rfn::RC_EXTRA] = es;
     }
 }
 
@@ -253,7 +311,7 @@ __global__ __launch_bounds__(256) void refine_propose_kernel(Batch<RefineArgs> b
     if ((int64_t)blockIdx.x * blockDim.x >= w.n || !active(w)) return;
     const int32_t i = (int32_t)((int64_t)blockIdx.x * blockDim.x + threadIdx.x);
     if (i >= w.n) return;
-    Prop best{NONE, -1, -1, -1, 0};
+    Prop best{NONE, -1, -1, -1, -1};
     double bd = 0.0;
     bool found = false;
     const int32_t po = w.match[i];
@@ -269,10 +327,10 @@ __global__ __launch_bounds__(256) void refine_propose_kernel(Batch<RefineArgs> b
     const int32_t jo = po >= 0 ? col_of(w, po) : -1;
     for (int32_t p = w.prow[i]; p < w.prow[i + 1]; ++p) {
         if (p == po) continue;
-        const int32_t o = w.owner[col_of(w, p)];
-        if (o < 0) {
-            consider(delta_single(w, i, p), p, -1, -1);
-        } else if (po >= 0 && o > i) {
+        const int32_t j = col_of(w, p);
+        if (room(w, j)) consider(delta_single(w, i, p), p, -1, -1);
+        if (po >= 0 && w.count[j] == 1 && w.hsum[j] > i && j != jo) {      // (limit 1: only where there is no room)
+            const int32_t o = (int32_t)w.hsum[j];
             for (int32_t q = w.prow[o]; q < w.prow[o + 1]; ++q)
                 if (col_of(w, q) == jo) {
                     consider(delta_swap(w, i, p, o, q), p, o, q);
@@ -282,6 +340,7 @@ __global__ __launch_bounds__(256) void refine_propose_kernel(Batch<RefineArgs> b
     }
     if (found) {
         best.key = key_of(bd, i);
+        best.p_o = po;
         unsigned long long *s = w.slot[ld_ctrl(w, rfn::RC_ROUNDS) & 1];
         each_slot(w, i, best, [&](int64_t x) { atomicMin(&s[x], best.key); return true; });
     }
@@ -303,16 +362,24 @@ __global__ __launch_bounds__(256) void refine_apply_kernel(Batch<RefineArgs> b) 
         if (pr.key != NONE) {
             const unsigned long long *s = w.slot[par];
             won = each_slot(w, i, pr, [&](int64_t y) { return s[y] == pr.key; });
-            if (won) {
-                const int32_t po = w.match[i];
+            if (won) {         // winners share no reference: plain stores
                 if (pr.k >= 0) {
+                    const int32_t ji = col_of(w, pr.p_i), jk = col_of(w, pr.p_k);
                     w.match[i] = pr.p_i;
                     w.match[pr.k] = pr.p_k;
-                    w.owner[col_of(w, pr.p_i)] = i;
-                    w.owner[col_of(w, pr.p_k)] = pr.k;
+                    w.hsum[ji] += (long long)i - pr.k;
+                    w.hsum[jk] += (long long)pr.k - i;
                 } else {
-                    if (po >= 0) w.owner[col_of(w, po)] = -1;
-                    if (pr.p_i >= 0) w.owner[col_of(w, pr.p_i)] = i;
+                    if (pr.p_o >= 0) {
+                        const int32_t jo = col_of(w, pr.p_o);
+                        w.count[jo] -= 1;
+                        w.hsum[jo] -= i;
+                    }
+                    if (pr.p_i >= 0) {
+                        const int32_t jn = col_of(w, pr.p_i);
+                        w.count[jn] += 1;
+                        w.hsum[jn] += i;
+                    }
                     w.match[i] = pr.p_i;
                 }
             }
@@ -347,7 +414,9 @@ size_t work_bytes(int64_t n, int64_t n_r, int64_t cap_tr) {
     const size_t N = (size_t)std::max<int64_t>(n, 1), R = (size_t)std::max<int64_t>(n_r, 1), T = (size_t)std::max<int64_t>(cap_tr, 1);
     Carver cv;
     cv.take(N * 4);                 // match
-    cv.take(R * 4);                 // owner
+    cv.take(R * 4);                 // count
+    cv.take(R * 8);                 // hsum
+    cv.take(R * 4);                 // limit
     cv.take(T * 12);                // tsort
     cv.take(T);                     // tsign
     cv.take(T * 8);                 // tw
@@ -367,7 +436,9 @@ void carve(RefineArgs *a, char *work) {
     const size_t N = (size_t)std::max<int64_t>(a->n, 1), R = (size_t)std::max<int64_t>(a->n_r, 1), T = (size_t)std::max<int64_t>(a->cap_tr, 1);
     Carver cv;
     a->match = reinterpret_cast<int32_t *>(work + cv.take(N * 4));
-    a->owner = reinterpret_cast<int32_t *>(work + cv.take(R * 4));
+    a->count = reinterpret_cast<int32_t *>(work + cv.take(R * 4));
+    a->hsum = reinterpret_cast<long long *>(work + cv.take(R * 8));
+    a->limit = reinterpret_cast<int32_t *>(work + cv.take(R * 4));
     a->tsort = reinterpret_cast<int32_t *>(work + cv.take(T * 12));
     a->tsign = reinterpret_cast<int8_t *>(work + cv.take(T));
     a->tw = reinterpret_cast<double *>(work + cv.take(T * 8));
@@ -399,6 +470,9 @@ int launch_setup(same_ctx *ctx, const RefineArgs *jobs, int n_w) {
     int64_t max_n, max_s, max_t;
     const Batch<RefineArgs> bt = batch_of(jobs, n_w, &max_n, &max_s, &max_t);
     const unsigned nw = (unsigned)n_w;
+    bool by_frame = false;
+    for (int q = 0; q < n_w; ++q) by_frame = by_frame || jobs[q].rsize;
+    if (by_frame) SAME_LAUNCH(ctx, refine_limit_kernel, dim3(1, nw), dim3(LIM_NT), 0, bt);
     SAME_LAUNCH(ctx, refine_init_kernel, dim3(grid_for(std::max<int64_t>(max_s, 64)), nw), dim3(256), 0, bt);
     SAME_LAUNCH(ctx, refine_tri_kernel, dim3(grid_for(std::max(max_t, max_n)), nw), dim3(256), 0, bt);
     SAME_LAUNCH(ctx, refine_scan_kernel, dim3(scan::blocks_for(max_n), nw), dim3(scan::NT), 0, bt);
@@ -427,15 +501,20 @@ int launch_rounds(same_ctx *ctx, const RefineArgs *jobs, int n_w, int rounds) {
 }  // namespace rfn
 
 // ---- the host-buffer form ------------------------------------------------------------------------------------------------------
-extern "C" int same_refine_matching(same_ctx *ctx, const int32_t *pairs, const double *costs, int64_t P, const double *unmatched, int64_t n_m,
-                                    int64_t n_r, const int32_t *tris, int64_t Tr, const double *axy, const double *ref_xy, const double *size,
-                                    double delaunay_penalty, int64_t rounds_cap, int32_t *match_pair_inout, int64_t *out_stats) {
+// ref_limit null: every limit 1 (same_refine_matching); out_stats gets Σ p_j as a sixth word when `extra`
+static int refine_host(same_ctx *ctx, const int32_t *pairs, const double *costs, int64_t P, const double *unmatched, int64_t n_m, int64_t n_r,
+                       const int32_t *tris, int64_t Tr, const double *axy, const double *ref_xy, const double *size, double delaunay_penalty,
+                       const int32_t *ref_limit, double penalty_coeff, int64_t rounds_cap, int32_t *match_pair_inout, int64_t *out_stats,
+                       bool extra) {
     REQUIRE(ctx, ctx != nullptr);
     REQUIRE(ctx, P >= 0 && n_m >= 0 && n_r >= 0 && Tr >= 0 && n_m + n_r < ((int64_t)1 << 30) && P < ((int64_t)1 << 31) - 1 &&
                      Tr < ((int64_t)1 << 29));
     REQUIRE(ctx, (P == 0 || (pairs && costs)) && (n_m == 0 || (unmatched && match_pair_inout && axy && size)) && (n_r == 0 || ref_xy) &&
                      (Tr == 0 || tris) && out_stats);
     REQUIRE(ctx, rounds_cap >= 1 && delaunay_penalty >= 0.0 && delaunay_penalty - delaunay_penalty == 0.0);
+    REQUIRE(ctx, penalty_coeff >= 0.0 && penalty_coeff - penalty_coeff == 0.0);
+    if (ref_limit)
+        for (int64_t j = 0; j < n_r; ++j) REQUIRE(ctx, ref_limit[j] >= 1 && ref_limit[j] <= rfn::MAX_LIMIT);
     // the pairs by row (stable: the caller's order inside a row), each (row, column) once; the start one-to-one
     std::vector<int32_t> prow((size_t)n_m + 1, 0), order((size_t)P), where((size_t)P), csr((size_t)P * 2), start((size_t)n_m);
     std::vector<double> ccsr((size_t)P);
@@ -466,17 +545,17 @@ extern "C" int same_refine_matching(same_ctx *ctx, const int32_t *pairs, const d
             csr[2 * (size_t)q + 1] = j;
             ccsr[(size_t)q] = costs[p];
         }
-    std::vector<uint8_t> held((size_t)n_r, 0);
+    std::vector<int32_t> held((size_t)n_r, 0);
     for (int64_t i = 0; i < n_m; ++i) {
         const int32_t p = match_pair_inout[i];
         REQUIRE(ctx, p >= -1 && p < P && (p < 0 || pairs[2 * (int64_t)p] == i));
         if (p >= 0) {
             const int32_t j = pairs[2 * (int64_t)p + 1];
-            if (held[(size_t)j]) {
-                ctx->err = "invalid argument: the start matching takes a reference twice";
+            if (++held[(size_t)j] > (ref_limit ? ref_limit[j] : 1)) {
+                ctx->err = ref_limit ? "invalid argument: the start matching takes a reference more often than its limit"
+                                     : "invalid argument: the start matching takes a reference twice";
                 return SAME_EINVAL;
             }
-            held[(size_t)j] = 1;
         }
         start[(size_t)i] = p >= 0 ? where[(size_t)p] : -1;
     }
@@ -486,7 +565,7 @@ extern "C" int same_refine_matching(same_ctx *ctx, const int32_t *pairs, const d
     const size_t o_prow = cv.take(((size_t)n_m + 1) * 4), o_pairs = cv.take((size_t)P * 8 + 8), o_cost = cv.take((size_t)P * 8 + 8),
                  o_unm = cv.take((size_t)n_m * 8 + 8), o_size = cv.take((size_t)n_m * 8 + 8), o_axy = cv.take((size_t)n_m * 16 + 16),
                  o_rxy = cv.take((size_t)n_r * 16 + 16), o_tris = cv.take((size_t)Tr * 12 + 12), o_start = cv.take((size_t)n_m * 4 + 4),
-                 o_ctrl = cv.take(rfn::RC_COUNT * 8), o_work = cv.take(rfn::work_bytes(n_m, n_r, Tr));
+                 o_ctrl = cv.take(rfn::RC_COUNT * 8), o_lim = cv.take((size_t)n_r * 4 + 4), o_work = cv.take(rfn::work_bytes(n_m, n_r, Tr));
     char *d = nullptr;
     SAME_TRY(slot_as(ctx, SL_OUT0, cv.off, &d));
     rfn::RefineArgs a{};
@@ -505,6 +584,8 @@ extern "C" int same_refine_matching(same_ctx *ctx, const int32_t *pairs, const d
     a.cap = rounds_cap;
     a.start = reinterpret_cast<const int32_t *>(d + o_start);
     a.ctrl = reinterpret_cast<unsigned long long *>(d + o_ctrl);
+    a.pc = penalty_coeff;
+    a.limit_in = ref_limit ? reinterpret_cast<const int32_t *>(d + o_lim) : nullptr;
     rfn::carve(&a, d + o_work);
     SAME_COPY(ctx, d + o_prow, prow.data(), prow.size() * 4, hipMemcpyHostToDevice);
     if (P) {
@@ -518,6 +599,7 @@ extern "C" int same_refine_matching(same_ctx *ctx, const int32_t *pairs, const d
         SAME_COPY(ctx, d + o_start, start.data(), (size_t)n_m * 4, hipMemcpyHostToDevice);
     }
     if (n_r) SAME_COPY(ctx, d + o_rxy, ref_xy, (size_t)n_r * 16, hipMemcpyHostToDevice);
+    if (n_r && ref_limit) SAME_COPY(ctx, d + o_lim, ref_limit, (size_t)n_r * 4, hipMemcpyHostToDevice);
     if (Tr) SAME_COPY(ctx, d + o_tris, tris, (size_t)Tr * 12, hipMemcpyHostToDevice);
     std::vector<int32_t> mp((size_t)n_m);
     unsigned long long ctrl[rfn::RC_COUNT] = {};
@@ -541,5 +623,22 @@ extern "C" int same_refine_matching(same_ctx *ctx, const int32_t *pairs, const d
     out_stats[2] = (int64_t)ctrl[rfn::RC_SETTLED];
     out_stats[3] = (int64_t)ctrl[rfn::RC_OBJ0];
     out_stats[4] = (int64_t)ctrl[rfn::RC_OBJ];
+    if (extra) out_stats[5] = (int64_t)ctrl[rfn::RC_EXTRA];
     return SAME_OK;
+}
+
+extern "C" int same_refine_matching(same_ctx *ctx, const int32_t *pairs, const double *costs, int64_t P, const double *unmatched, int64_t n_m,
+                                    int64_t n_r, const int32_t *tris, int64_t Tr, const double *axy, const double *ref_xy, const double *size,
+                                    double delaunay_penalty, int64_t rounds_cap, int32_t *match_pair_inout, int64_t *out_stats) {
+    return refine_host(ctx, pairs, costs, P, unmatched, n_m, n_r, tris, Tr, axy, ref_xy, size, delaunay_penalty, nullptr, 0.0, rounds_cap,
+                       match_pair_inout, out_stats, false);
+}
+
+extern "C" int same_refine_matching_cap(same_ctx *ctx, const int32_t *pairs, const double *costs, int64_t P, const double *unmatched,
+                                        int64_t n_m, int64_t n_r, const int32_t *tris, int64_t Tr, const double *axy, const double *ref_xy,
+                                        const double *size, double delaunay_penalty, const int32_t *ref_limit, double penalty_coeff,
+                                        int64_t rounds_cap, int32_t *match_pair_inout, int64_t *out_stats) {
+    REQUIRE(ctx, n_r == 0 || ref_limit);
+    return refine_host(ctx, pairs, costs, P, unmatched, n_m, n_r, tris, Tr, axy, ref_xy, size, delaunay_penalty, ref_limit, penalty_coeff,
+                       rounds_cap, match_pair_inout, out_stats, true);
 }

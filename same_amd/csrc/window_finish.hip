@@ -370,11 +370,24 @@ struct FinishMode {
     double no_match_penalty = 0.0;
     int64_t refine_cap = 0;                   // local search rounds at most (refine.hip), 0 = no search
     double delaunay_penalty = 0.0;
+    bool capacity = false;                    // the search with the model's reference capacities (the _cap calls) ...
+    same_window_capacity cap{1, 0, 0.0};      // ... these
+    int stride = SAME_WINDOW_STATS;           // int64 words per window in out_stats
 };
 int check_mode(same_ctx *ctx, const FinishMode &m) {
     REQUIRE(ctx, m.incumbent == SAME_INCUMBENT_GREEDY || m.incumbent == SAME_INCUMBENT_ASSIGNMENT);
     REQUIRE(ctx, m.refine_cap >= 0 && m.delaunay_penalty >= 0.0 && m.delaunay_penalty - m.delaunay_penalty == 0.0);
+    REQUIRE(ctx, m.cap.max_matches >= 1 && m.cap.multiplier >= 0 && m.cap.penalty_coeff >= 0.0 &&
+                     m.cap.penalty_coeff - m.cap.penalty_coeff == 0.0);
     return SAME_OK;
+}
+FinishMode mode_of(int incumbent, double no_match_penalty, int64_t refine_rounds_cap, double delaunay_penalty,
+                   const same_window_capacity *capacity, bool wide) {
+    FinishMode m{incumbent, no_match_penalty, refine_rounds_cap, delaunay_penalty};
+    m.capacity = capacity != nullptr && refine_rounds_cap > 0;
+    if (capacity) m.cap = *capacity;
+    m.stride = wide ? SAME_WINDOW_STATS_CAP : SAME_WINDOW_STATS;
+    return m;
 }
 // words of a window's out_stats record after the eight counters: the assignment's flags and objective, the search's record
 enum { WS_AS_FLAGS = 8, WS_AS_OBJ = 9, WS_REFINE = 10 };
@@ -493,6 +506,14 @@ int prepare_finish(same_window *w, const int32_t *host_tris, int64_t cap_tr, con
         r.cap_tr = cap_tr;
         r.cap = mode.refine_cap;
         r.penalty = mode.no_match_penalty;
+        if (mode.capacity) {            // the limits from the reference section's sizes (refine_limit_kernel), pricing the extra matches
+            r.pc = mode.cap.penalty_coeff;
+            r.rsize = w->ref->size;
+            r.ref_rows = w->rows_r;
+            r.P = P;
+            r.max_matches = mode.cap.max_matches;
+            r.multiplier = mode.cap.multiplier;
+        }
         r.start = p->match_pair;
         r.ctrl = p->counters + SC_REFINE;
         rfn::carve(&r, at(o_refine));
@@ -611,6 +632,7 @@ int settle(same_window *w, FinishPlan *p, bool fresh, int64_t *out_stats) {
         rf[2] = (int64_t)rc[rfn::RC_SETTLED];
         rf[3] = (int64_t)rc[rfn::RC_OBJ0];          // the objectives as the bits of a double
         rf[4] = (int64_t)rc[rfn::RC_OBJ];
+        if (p->mode.stride > SAME_WINDOW_STATS) rf[5] = (int64_t)rc[rfn::RC_EXTRA];   // sum_j max(0, count_j - 1)
     }
     return SAME_OK;
 }
@@ -663,16 +685,12 @@ int read_finish(same_window *w, FinishPlan *p, int32_t *out_match_row, uint8_t *
 
 }  // namespace
 
-extern "C" {
-
-int same_window_filter_finish(same_window *const *windows, int n_windows, int source, const int32_t *simplices, const int64_t *simplex_offsets,
-                              double radius, int angle_enabled, double cos_thr, double near_tol, int ignore_same_type,
-                              int ensure_min_triangle_per_node, double no_match_penalty, int incumbent, int64_t refine_rounds_cap,
-                              double delaunay_penalty, int32_t *out_match_row, uint8_t *out_point_flag, int64_t *out_stats,
-                              int64_t *out_counts) {
+static int filter_finish(same_window *const *windows, int n_windows, int source, const int32_t *simplices, const int64_t *simplex_offsets,
+                         double radius, int angle_enabled, double cos_thr, double near_tol, int ignore_same_type,
+                         int ensure_min_triangle_per_node, const FinishMode &mode, int32_t *out_match_row, uint8_t *out_point_flag,
+                         int64_t *out_stats, int64_t *out_counts) {
     same_ctx *ctx = nullptr;
     SAME_TRY(check_batch(windows, n_windows, &ctx));
-    const FinishMode mode{incumbent, no_match_penalty, refine_rounds_cap, delaunay_penalty};
     SAME_TRY(check_mode(ctx, mode));
     REQUIRE(ctx, source == SAME_TRIS_SIMPLICES || source == SAME_TRIS_KEPT || source == SAME_TRIS_DEVICE);
     // SAME_TRIS_DEVICE: every window's simplices are the ones same_window_delaunay left on the device for it (no host array; the offsets
@@ -697,7 +715,7 @@ int same_window_filter_finish(same_window *const *windows, int n_windows, int so
     }
     REQUIRE(ctx, n_cells == 0 || (out_match_row && out_point_flag));
     for (int q = 0; q < 4 * n_windows; ++q) out_counts[q] = 0;
-    for (int q = 0; q < SAME_WINDOW_STATS * n_windows; ++q) out_stats[q] = 0;
+    for (int q = 0; q < mode.stride * n_windows; ++q) out_stats[q] = 0;
     SAME_TRY(same_use(ctx));
     if (!on_device)     // (the device's own triangles index the window's kept cells by construction)
         for (int i = 0; i < n_windows; ++i)
@@ -808,7 +826,7 @@ int same_window_filter_finish(same_window *const *windows, int n_windows, int so
         same_window *w = windows[i];
         Item &it = items[(size_t)i];
         const int64_t Tr = simplex_offsets[i + 1] - simplex_offsets[i];
-        int64_t *counts = out_counts + 4 * i, *stats = out_stats + SAME_WINDOW_STATS * i;
+        int64_t *counts = out_counts + 4 * i, *stats = out_stats + mode.stride * i;
         if (!it.enqueued) {                 // no kept aligned cell: nothing to match, nothing to sweep
             w->filtered = w->finished = 1;
             continue;
@@ -838,12 +856,11 @@ int same_window_filter_finish(same_window *const *windows, int n_windows, int so
     return SAME_OK;
 }
 
-int same_window_refinish(same_window *window, const int32_t *match_pair, double no_match_penalty, int64_t refine_rounds_cap,
-                         double delaunay_penalty, int32_t *out_match_row, uint8_t *out_point_flag, int64_t *out_stats) {
+static int refinish(same_window *window, const int32_t *match_pair, const FinishMode &mode, int32_t *out_match_row, uint8_t *out_point_flag,
+                    int64_t *out_stats) {
     if (!window) return SAME_EINVAL;
     same_window *w = window;
     same_ctx *ctx = w->ctx;
-    const FinishMode mode{SAME_INCUMBENT_GREEDY, no_match_penalty, refine_rounds_cap, delaunay_penalty};   // (no incumbent is searched for)
     SAME_TRY(check_mode(ctx, mode));
     REQUIRE(ctx, w->finished && w->staged == 2 && w->n_ua > 0 && match_pair && out_match_row && out_point_flag && out_stats);
     for (int64_t i = 0; i < w->n_ua; ++i) REQUIRE(ctx, match_pair[i] >= -1 && match_pair[i] < w->P);
@@ -860,13 +877,49 @@ int same_window_refinish(same_window *window, const int32_t *match_pair, double 
     char *h = static_cast<char *>(w->host) + w->host_finish_off;
     SAME_COPY(ctx, h, reinterpret_cast<const char *>(p.gs.sel), p.back_bytes, hipMemcpyDeviceToHost);
     SAME_WAIT(ctx);
-    for (int q = 0; q < SAME_WINDOW_STATS; ++q) out_stats[q] = 0;
+    for (int q = 0; q < mode.stride; ++q) out_stats[q] = 0;
     SAME_TRY(settle(w, &p, false, out_stats));
     const unsigned long long *cnt = reinterpret_cast<const unsigned long long *>(h + p.o_counters);
     for (int q = 0; q < 8; ++q) out_stats[q] = (int64_t)cnt[q];
     memcpy(out_match_row, h + p.o_match_row, (size_t)w->n_ua * sizeof(int32_t));
     memcpy(out_point_flag, h + p.o_pflag, (size_t)w->n_ua);
     return SAME_OK;
+}
+
+extern "C" {
+
+int same_window_filter_finish(same_window *const *windows, int n_windows, int source, const int32_t *simplices, const int64_t *simplex_offsets,
+                              double radius, int angle_enabled, double cos_thr, double near_tol, int ignore_same_type,
+                              int ensure_min_triangle_per_node, double no_match_penalty, int incumbent, int64_t refine_rounds_cap,
+                              double delaunay_penalty, int32_t *out_match_row, uint8_t *out_point_flag, int64_t *out_stats,
+                              int64_t *out_counts) {
+    return filter_finish(windows, n_windows, source, simplices, simplex_offsets, radius, angle_enabled, cos_thr, near_tol, ignore_same_type,
+                         ensure_min_triangle_per_node, mode_of(incumbent, no_match_penalty, refine_rounds_cap, delaunay_penalty, nullptr, false),
+                         out_match_row, out_point_flag, out_stats, out_counts);
+}
+
+int same_window_filter_finish_cap(same_window *const *windows, int n_windows, int source, const int32_t *simplices,
+                                  const int64_t *simplex_offsets, double radius, int angle_enabled, double cos_thr, double near_tol,
+                                  int ignore_same_type, int ensure_min_triangle_per_node, double no_match_penalty, int incumbent,
+                                  int64_t refine_rounds_cap, double delaunay_penalty, const same_window_capacity *capacity,
+                                  int32_t *out_match_row, uint8_t *out_point_flag, int64_t *out_stats, int64_t *out_counts) {
+    return filter_finish(windows, n_windows, source, simplices, simplex_offsets, radius, angle_enabled, cos_thr, near_tol, ignore_same_type,
+                         ensure_min_triangle_per_node, mode_of(incumbent, no_match_penalty, refine_rounds_cap, delaunay_penalty, capacity, true),
+                         out_match_row, out_point_flag, out_stats, out_counts);
+}
+
+int same_window_refinish(same_window *window, const int32_t *match_pair, double no_match_penalty, int64_t refine_rounds_cap,
+                         double delaunay_penalty, int32_t *out_match_row, uint8_t *out_point_flag, int64_t *out_stats) {
+    // (no incumbent is searched for)
+    return refinish(window, match_pair, mode_of(SAME_INCUMBENT_GREEDY, no_match_penalty, refine_rounds_cap, delaunay_penalty, nullptr, false),
+                    out_match_row, out_point_flag, out_stats);
+}
+
+int same_window_refinish_cap(same_window *window, const int32_t *match_pair, double no_match_penalty, int64_t refine_rounds_cap,
+                             double delaunay_penalty, const same_window_capacity *capacity, int32_t *out_match_row,
+                             uint8_t *out_point_flag, int64_t *out_stats) {
+    return refinish(window, match_pair, mode_of(SAME_INCUMBENT_GREEDY, no_match_penalty, refine_rounds_cap, delaunay_penalty, capacity, true),
+                    out_match_row, out_point_flag, out_stats);
 }
 
 }  // extern "C"

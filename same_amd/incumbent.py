@@ -31,6 +31,13 @@ model, one that leaves reference capacity unused.  The table, `flipped` and the 
 return_stats each window's stats gain `mip_objective_start`, `mip_objective` (the model's objective before and after), `refine_rounds`,
 `refine_moves` and `refine_settled` (0: stopped at the round cap); `objective` stays the assignment's.
 
+optim_params["hip_refine"] = "capacity" is the same search within the model's reference capacities (src/helpers.py:102-161,
+`api.ref_match_limits`): reference j of a window may take up to max_matches * ref_metacell_match_multiplier cells when the window's
+reference frame holds metacells and j is one (the multiplier None: the frame's largest size), else max_matches, at most 1001; every match
+after a reference's first costs penalty_coeff, so the objective gains penalty_coeff * sum_j max(0, count_j - 1).  Moves go to references
+with room.  With every limit 1 it is "local" bit for bit.  The stats also carry `ref_extra_matches` (sum_j max(0, count_j - 1) of the
+result), and both objectives include the penalty_coeff term.  The starts stay one-to-one.
+
 Two routes produce the same table (tests/test_gpu_run_same.py::test_incumbent_table_routes_agree):
   device   both frames resident on the GPU, two library calls per window, the incumbent and the sweeps computed where the pairs are
            (csrc/window_stage.hip, csrc/window_finish.hip); the host triangulates, receives (match, flags) per window and gathers
@@ -47,7 +54,7 @@ import pandas as pd
 
 from . import ops
 from ._trace import stage
-from .api import _Staged, prepare_same_inputs
+from .api import _Staged, prepare_same_inputs, ref_match_limits
 from .window_api import _WindowJob, _walk_windows
 
 STAT_KEYS = ("pairs", "triangles", "checked", "flipped", "xy_violations", "area_flips", "matched")
@@ -83,13 +90,15 @@ def incumbent_mode(optim_params, gurobi_params=None, moving=None):
     return mode
 
 
-REFINES = ("local",)                           # optim_params["hip_refine"]; None without the key
+REFINES = ("local", "capacity")               # optim_params["hip_refine"]; None without the key
 REFINE_ROUNDS = 32                             # optim_params["hip_refine_rounds"] without the key
+MAX_REF_LIMIT = 1001                           # "capacity": count_j <= 1 + the bound 1000 of p_j (src/same.py:1117)
 
 
 def refine_mode(optim_params):
-    """optim_params["hip_refine"] / ["hip_refine_rounds"] / ["delaunay_penalty"] checked before anything reaches a device -> None (no
-    search) or (rounds_cap, delaunay_penalty)"""
+    """optim_params["hip_refine"] / ["hip_refine_rounds"] / ["delaunay_penalty"] (and for "capacity" ["penalty_coeff"] /
+    ["max_matches"] / ["ref_metacell_match_multiplier"]) checked before anything reaches a device -> None (no search),
+    (rounds_cap, delaunay_penalty) ("local") or (rounds_cap, delaunay_penalty, (max_matches, multiplier or None, penalty_coeff))"""
     import numbers
 
     from .params import init_optim_params
@@ -103,10 +112,21 @@ def refine_mode(optim_params):
     cap = op.get("hip_refine_rounds", REFINE_ROUNDS)
     if isinstance(cap, bool) or not isinstance(cap, numbers.Integral) or cap < 1:
         raise ValueError(f"optim_params['hip_refine_rounds'] must be a positive int, not {cap!r}")
-    dp = init_optim_params(**op)["delaunay_penalty"]
+    full = init_optim_params(**op)
+    dp = full["delaunay_penalty"]
     if isinstance(dp, bool) or not isinstance(dp, numbers.Real) or not np.isfinite(float(dp)) or float(dp) < 0:
         raise ValueError(f"optim_params['delaunay_penalty'] must be finite and >= 0 for hip_refine, not {dp!r}")
-    return int(cap), float(dp)
+    if mode == "local":
+        return int(cap), float(dp)
+    pc, mm, mult = full["penalty_coeff"], full["max_matches"], full["ref_metacell_match_multiplier"]
+    if isinstance(pc, bool) or not isinstance(pc, numbers.Real) or not np.isfinite(float(pc)) or float(pc) < 0:
+        raise ValueError(f"optim_params['penalty_coeff'] must be finite and >= 0 for hip_refine='capacity', not {pc!r}")
+    if isinstance(mm, bool) or not isinstance(mm, numbers.Integral) or mm < 1:
+        raise ValueError(f"optim_params['max_matches'] must be an int >= 1 for hip_refine='capacity', not {mm!r}")
+    if mult is not None and (isinstance(mult, bool) or not isinstance(mult, numbers.Integral) or mult < 1):
+        raise ValueError(f"optim_params['ref_metacell_match_multiplier'] must be None or an int >= 1 for hip_refine='capacity', "
+                         f"not {mult!r}")
+    return int(cap), float(dp), (int(mm), None if mult is None else int(mult), float(pc))
 
 
 def _default_workers():
@@ -318,7 +338,9 @@ def incumbent_of_prepared(prep, commonCT, with_ref_idx=True, ctx=None, use_devic
     incumbent="assignment": the optimal one-to-one assignment (ops.sparse_assign) instead of the greedy start; the stats then carry the
     window's "objective" and whether it fell back to the host solver ("fallback").
     refine=(rounds_cap, delaunay_penalty): the local search on the lazy model's objective (ops.refine_matching) from the incumbent
-    before the sweeps; the stats then carry mip_objective_start, mip_objective, refine_rounds, refine_moves, refine_settled."""
+    before the sweeps; the stats then carry mip_objective_start, mip_objective, refine_rounds, refine_moves, refine_settled.
+    refine=(rounds_cap, delaunay_penalty, (max_matches, multiplier, penalty_coeff)): the same within the reference capacities of
+    prep.ref_df (api.ref_match_limits; ops.refine_matching_cap); the stats also carry ref_extra_matches."""
     op = prep.optim_params
     dw = getattr(prep, "device", None)
     if use_device and dw is not None and dw.match_row is not None and isinstance(prep.valid_pairs, np.ndarray):
@@ -336,7 +358,13 @@ def incumbent_of_prepared(prep, commonCT, with_ref_idx=True, ctx=None, use_devic
         pair_of_row, _rounds = ops.greedy_match(pairs, costs, n_a, n_r, wants, ctx=ctx)
     axy, rxy = a_df[["X", "Y"]].to_numpy(dtype=np.float64), r_df[["X", "Y"]].to_numpy(dtype=np.float64)
     t32 = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
-    if refine is not None:
+    if refine is not None and len(refine) > 2:
+        mm, mult, pc = refine[2]
+        limits = np.minimum(np.asarray(ref_match_limits(r_df, mm, mult), dtype=np.float64), MAX_REF_LIMIT).astype(np.int32)
+        pair_of_row, rst = ops.refine_matching_cap(pairs, costs, float(op["no_match_penalty"]) * size, n_a, n_r, t32, axy, rxy, size,
+                                                   refine[1], limits, pc, refine[0], pair_of_row, ctx=ctx)
+        extra.update(_refine_stats(rst))
+    elif refine is not None:
         pair_of_row, rst = ops.refine_matching(pairs, costs, float(op["no_match_penalty"]) * size, n_a, n_r, t32, axy, rxy, size,
                                                refine[1], refine[0], pair_of_row, ctx=ctx)
         extra.update(_refine_stats(rst))
@@ -405,8 +433,11 @@ def _table_of_device_window(prep, dw, commonCT, with_ref_idx):
 
 def _refine_stats(rst):
     """the local search's keys of a window's stats record"""
-    return {"mip_objective_start": rst["objective_start"], "mip_objective": rst["objective"], "refine_rounds": rst["rounds"],
-            "refine_moves": rst["moves"], "refine_settled": rst["settled"]}
+    out = {"mip_objective_start": rst["objective_start"], "mip_objective": rst["objective"], "refine_rounds": rst["rounds"],
+           "refine_moves": rst["moves"], "refine_settled": rst["settled"]}
+    if "ref_extra_matches" in rst:
+        out["ref_extra_matches"] = rst["ref_extra_matches"]
+    return out
 
 
 def _device_stats(dw):

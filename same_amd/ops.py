@@ -388,6 +388,31 @@ def refine_matching(pairs, costs, unmatched, n_aligned, n_ref, triangles, axy, r
                  "objective": float(obj[1])}
 
 
+def refine_matching_cap(pairs, costs, unmatched, n_aligned, n_ref, triangles, axy, ref_xy, size, delaunay_penalty, ref_limit, penalty_coeff,
+                        rounds_cap, match_pair, ctx=None):
+    """refine_matching with the model's reference capacities (same_refine_matching_cap): reference j may hold up to ref_limit[j] cells
+    (1 .. 1001), each after the first priced penalty_coeff, so the objective gains penalty_coeff * sum_j max(0, count_j - 1).
+    `match_pair` may hold a reference up to its limit.  -> (match_pair, stats as refine_matching's + "ref_extra_matches" (that sum)).
+    With every limit 1 it is refine_matching bit for bit.  tests/refine_capacity_check.py states the same rule on the host."""
+    ctx = _ctx(ctx)
+    pairs, costs, unmatched = as_c(pairs, I32).reshape(-1, 2), as_c(costs, F64), as_c(unmatched, F64)
+    tris, axy, ref_xy, size = _tris(triangles), as_c(axy, F64).reshape(-1, 2), as_c(ref_xy, F64).reshape(-1, 2), as_c(size, F64)
+    limit = as_c(ref_limit, I32)
+    n_aligned, n_ref = int(n_aligned), int(n_ref)
+    assert len(costs) == len(pairs) and len(unmatched) == n_aligned == len(axy) == len(size) and len(ref_xy) == n_ref == len(limit)
+    out = np.array(match_pair, dtype=I32, copy=True).reshape(-1)
+    assert len(out) == n_aligned
+    st = np.zeros(6, I64)
+    with ctx.lock:
+        ctx.check(ctx.lib.same_refine_matching_cap(ctx.handle, pairs.ctypes.data, costs.ctypes.data, len(pairs), unmatched.ctypes.data,
+                                                   n_aligned, n_ref, tris.ctypes.data, len(tris), axy.ctypes.data, ref_xy.ctypes.data,
+                                                   size.ctypes.data, float(delaunay_penalty), limit.ctypes.data, float(penalty_coeff),
+                                                   int(rounds_cap), out.ctypes.data, st.ctypes.data), "same_refine_matching_cap")
+    obj = st[3:5].view(F64)
+    return out, {"rounds": int(st[0]), "moves": int(st[1]), "settled": int(st[2]), "objective_start": float(obj[0]),
+                 "objective": float(obj[1]), "ref_extra_matches": int(st[5])}
+
+
 def tri_flip_stats(axy, mapped_xy, matched, triangles, type_id=None, ctx=None):
     """-> (tri_flag (Tr,) uint8 [bit0 matched, bit1 same type, bit2 flipped], node_tri, node_flip (n,) uint32)."""
     ctx = _ctx(ctx)

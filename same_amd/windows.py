@@ -5,6 +5,7 @@ Windows are the shard unit for very large sections (BASELINE config 5).  Cell co
 box the merge logic can ask about (base, right-merged, down-merged, both) come from one
 batched device pass (csrc/sweep.hip window_count_kernel) instead of one pandas boolean mask
 per window; the sequential walk that decides merges is then pure host lookups."""
+import ctypes
 import os
 
 import numpy as np
@@ -475,11 +476,18 @@ class DeviceWindow:
         match_pair = np.ascontiguousarray(match_pair, dtype=np.int32)
         assert len(match_pair) == n
         cap, dp = _refine_args(refine)
-        match_row, flag, stats = np.empty(n, np.int32), np.empty(n, np.uint8), np.zeros(_lib.SAME_WINDOW_STATS, np.int64)
+        capacity = _capacity_arg(refine)
+        width = _lib.SAME_WINDOW_STATS if capacity is None else _lib.SAME_WINDOW_STATS_CAP
+        match_row, flag, stats = np.empty(n, np.int32), np.empty(n, np.uint8), np.zeros(width, np.int64)
         with self.ctx.lock:
-            self.ctx.check(self.ctx.lib.same_window_refinish(self.handle, match_pair.ctypes.data, float(no_match_penalty), cap, dp,
-                                                             match_row.ctypes.data, flag.ctypes.data, stats.ctypes.data),
-                           "same_window_refinish")
+            if capacity is None:
+                self.ctx.check(self.ctx.lib.same_window_refinish(self.handle, match_pair.ctypes.data, float(no_match_penalty), cap, dp,
+                                                                 match_row.ctypes.data, flag.ctypes.data, stats.ctypes.data),
+                               "same_window_refinish")
+            else:
+                self.ctx.check(self.ctx.lib.same_window_refinish_cap(self.handle, match_pair.ctypes.data, float(no_match_penalty), cap, dp,
+                                                                     ctypes.byref(capacity), match_row.ctypes.data, flag.ctypes.data,
+                                                                     stats.ctypes.data), "same_window_refinish_cap")
         self.refine = _window_records(stats, "greedy", refine)[1]
         return match_row, flag, dict(zip(self.STAT_NAMES, stats[:8].tolist()))
 
@@ -744,17 +752,30 @@ _INCUMBENTS = {"greedy": _lib.SAME_INCUMBENT_GREEDY, "assignment": _lib.SAME_INC
 
 
 def _refine_args(refine):
-    """`refine` = (rounds_cap, delaunay_penalty) or None -> the library's (rounds_cap, delaunay_penalty), rounds_cap 0 = no search"""
+    """`refine` = (rounds_cap, delaunay_penalty[, capacity]) or None -> the library's (rounds_cap, delaunay_penalty), rounds_cap 0 = no
+    search"""
     return (0, 0.0) if refine is None else (int(refine[0]), float(refine[1]))
 
 
+def _capacity_arg(refine):
+    """the capacity of `refine` = (rounds_cap, delaunay_penalty, (max_matches, multiplier or None, penalty_coeff)) -> the library's
+    same_window_capacity; None without one (hip_refine="local")"""
+    if refine is None or len(refine) < 3 or refine[2] is None:
+        return None
+    mm, mult, pc = refine[2]
+    return _lib.WindowCapacity(int(mm), 0 if mult is None else int(mult), float(pc))
+
+
 def _window_records(s, incumbent, refine):
-    """a window's stats words (SAME_WINDOW_STATS) -> (the assignment's record {"rounds", "flags", "objective"}, the search's record
-    {"rounds", "moves", "settled", "objective_start", "objective"}), each None when its mode was off"""
+    """a window's stats words (SAME_WINDOW_STATS, or SAME_WINDOW_STATS_CAP with a capacity) -> (the assignment's record {"rounds",
+    "flags", "objective"}, the search's record {"rounds", "moves", "settled", "objective_start", "objective"[, "ref_extra_matches"]}),
+    each None when its mode was off"""
     f = s.view(np.float64)
     asg = {"rounds": int(s[6]), "flags": int(s[8]), "objective": float(f[9])} if incumbent == "assignment" else None
     rfn = None if refine is None else {"rounds": int(s[10]), "moves": int(s[11]), "settled": int(s[12]), "objective_start": float(f[13]),
                                        "objective": float(f[14])}
+    if rfn is not None and len(s) > _lib.SAME_WINDOW_STATS:
+        rfn["ref_extra_matches"] = int(s[15])
     return asg, rfn
 
 
@@ -764,7 +785,8 @@ def filter_finish_windows(states, simplices, radius, angle_enabled, cos_thr, nea
     `prefiltered` its kept triangles; `simplices=None` takes the candidates `triangulate_windows` left on the device for every window
     (each state must have been answered since it was staged).  `incumbent`: "greedy" (src/init_helpers.py:104-133) or "assignment" (the
     optimal one-to-one assignment, csrc/assign.hip); `refine` = (rounds_cap, delaunay_penalty) runs the local search on the lazy model's
-    objective from the incumbent (csrc/refine.hip) for at most rounds_cap rounds, None none.
+    objective from the incumbent (csrc/refine.hip) for at most rounds_cap rounds, None none; (rounds_cap, delaunay_penalty, (max_matches,
+    multiplier or None, penalty_coeff)) runs it with the model's reference capacities (same_window_filter_finish_cap).
     -> [(kept, added back, near, match_row, flag byte, stats dict) per window]; a window with near != 0 has None for the last three.
     Every state's `order_ties` is set to the call's count of places where the answer hangs on the ORDER of the triangles or of their
     corners (include/same_hip.h; of consequence only when the simplices are not Qhull's own), its `assignment` and `refine` to the
@@ -779,16 +801,21 @@ def filter_finish_windows(states, simplices, radius, angle_enabled, cos_thr, nea
         np.cumsum([len(t) for t in tris], out=offsets[1:])
         flat = tris[0] if n == 1 else np.concatenate(tris)
     cap, dp = _refine_args(refine)
+    capacity = _capacity_arg(refine)
     kept_cells = [s.counts[2] for s in states]
     cell_off = np.concatenate(([0], np.cumsum(kept_cells))).astype(np.int64)
     match_row, flag = np.empty(int(cell_off[-1]), np.int32), np.empty(int(cell_off[-1]), np.uint8)
-    stats, counts = np.zeros((n, _lib.SAME_WINDOW_STATS), np.int64), np.zeros((n, 4), np.int64)
+    width = _lib.SAME_WINDOW_STATS if capacity is None else _lib.SAME_WINDOW_STATS_CAP
+    stats, counts = np.zeros((n, width), np.int64), np.zeros((n, 4), np.int64)
+    args = (_handles(states), n, source, _lib._ptr(flat), _lib._ptr(offsets), float(radius), int(angle_enabled), float(cos_thr),
+            float(near_tol), int(bool(ignore_same_type)), int(bool(ensure_min_triangle_per_node)), float(no_match_penalty),
+            _INCUMBENTS[incumbent], cap, dp)
+    outs = (match_row.ctypes.data, flag.ctypes.data, stats.ctypes.data, counts.ctypes.data)
     with ctx.lock:
-        ctx.check(ctx.lib.same_window_filter_finish(_handles(states), n, source, _lib._ptr(flat), _lib._ptr(offsets), float(radius),
-                                                    int(angle_enabled), float(cos_thr), float(near_tol), int(bool(ignore_same_type)),
-                                                    int(bool(ensure_min_triangle_per_node)), float(no_match_penalty), _INCUMBENTS[incumbent],
-                                                    cap, dp, match_row.ctypes.data, flag.ctypes.data, stats.ctypes.data,
-                                                    counts.ctypes.data), "same_window_filter_finish")
+        if capacity is None:
+            ctx.check(ctx.lib.same_window_filter_finish(*args, *outs), "same_window_filter_finish")
+        else:
+            ctx.check(ctx.lib.same_window_filter_finish_cap(*args, ctypes.byref(capacity), *outs), "same_window_filter_finish_cap")
     out = []
     for i, s in enumerate(states):
         kept, added, near, s.order_ties = (int(c) for c in counts[i])

@@ -55,7 +55,8 @@ typedef struct same_sweep same_sweep; /* resident state of one lazy-constraint s
  * part 1  HOST-BUFFER entry points (caller's arrays in and out; one   same_pair_cost_*, same_dense_cost_f64 / f32, same_knn_prune, same_tri_*, same_sweep_* /
  *         call = upload, kernels, download, wait)                     same_orient_sweep*, same_xyorder_sweep, same_area_flip, same_pair_rowmin,
  *                                                                     same_assign_matrix, same_greedy_*, same_tri_flip_stats, same_collapse_candidates,
- *                                                                     same_batched_assign, same_eager_signs, same_window_count, same_merge_dedup
+ *                                                                     same_batched_assign, same_eager_signs, same_window_count, same_merge_dedup,
+ *                                                                     same_check_alignment
  * part 2  DEVICE-RESIDENT forms (operands already in HBM; enqueue     same_dense_cost_*_dev, same_knn_prune_dev, same_knn_index_*,
  *         only unless noted)                                          same_knn_prune_indexed_dev, same_padded_cost_*_dev, same_tri_*_dev,
  *                                                                     same_area_flip_dev, same_xyorder_sweep_dev, same_orient_*_dev, same_first_candidate_dev
@@ -212,6 +213,23 @@ int same_tri_flip_stats(same_ctx *ctx, const double *axy, const double *mapped_x
                         const uint8_t *matched, int64_t n, const int32_t *type_id,
                         const int32_t *tris, int64_t Tr, uint8_t *out_tri_flag,
                         uint32_t *out_node_tri, uint32_t *out_node_flip);
+
+/* ---- f2: k-nearest-template label check of eval_utils.check_alignment (src/eval_utils.py:6-53) ----------------------------
+ * For each query point: is its label code among the codes of its k nearest template points (cKDTree.query(k))?  Labels arrive
+ * as int32 codes made by the caller (equal codes = equal labels; a code no template point carries never matches).  Exact against
+ * scipy, whose order among (nearly) equidistant points follows its tree: with d_k the k-th smallest d2 = dx*dx + dy*dy (fp64,
+ * no contraction), B = {d2 within d_k * 1e-12 + 1e-300 of d_k}, S = {d2 below B}, a row is decided on the device only when the
+ * answer does not depend on which members of B scipy takes -- k > 1: label in S (match), in no member of B (no match),
+ * |S| + |B| <= k (match); k == 1: |S| = 0 and |B| = 1.  out_flag[i] = SAME_ALIGN_DECIDED | SAME_ALIGN_MATCH bits; the caller
+ * resolves the rows without SAME_ALIGN_DECIDED itself.  out_nearest (k == 1 only, else may be NULL) = the unique nearest
+ * template row of a decided query, -1 otherwise; neighbour lists for k > 1 never leave the device.
+ * 1 <= k <= SAME_ALIGN_MAX_KNN, k <= n_t when n_q > 0, n_q and n_t < 2^31, every coordinate finite (else SAME_EINVAL). */
+#define SAME_ALIGN_MAX_KNN 64
+#define SAME_ALIGN_MATCH 1
+#define SAME_ALIGN_DECIDED 2
+int same_check_alignment(same_ctx *ctx, const double *qxy, int64_t n_q, const int32_t *qcode,
+                         const double *txy, int64_t n_t, const int32_t *tcode, int k,
+                         uint8_t *out_flag, int32_t *out_nearest);
 
 /* ---- f2: metacell collapse (metacell_utils.greedy_triangle_collapse) -----------------------
  * same_collapse_candidates replaces the per-triangle work of one collapse iteration

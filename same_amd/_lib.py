@@ -28,6 +28,8 @@ DT_U8, DT_I32, DT_U64, DT_F64 = 0, 1, 2, 3     # SAME_DT_*
 OP_SUM, OP_MAX, OP_MIN = 0, 1, 2               # SAME_OP_*
 SPREAD_INFO_LEN = 14                           # SAME_SPREAD_INFO_LEN
 MAX_KNN = 448
+ALIGN_MAX_KNN = 64                             # SAME_ALIGN_MAX_KNN
+ALIGN_MATCH, ALIGN_DECIDED = 1, 2              # SAME_ALIGN_* bits of same_check_alignment's flags
 MAX_TYPES = 4096
 
 # name -> argtypes, exactly the declarations of include/same_hip.h and include/same_hip_diag.h (restype int unless noted)
@@ -90,6 +92,7 @@ _PROTOTYPES = {
     "same_assign_matrix": [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_dbl, c_vp],
     "same_greedy_match": [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, ctypes.POINTER(c_int)],
     "same_tri_flip_stats": [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp],
+    "same_check_alignment": [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_int, c_vp, c_vp],
     "same_collapse_candidates": [c_vp, c_vp, c_i64, c_vp, c_i64, c_int, c_dbl, c_int, c_dbl, c_vp, c_vp, c_dbl, c_vp, c_vp, c_vp],
     "same_greedy_disjoint": [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, ctypes.POINTER(c_int)],
     "same_batched_assign": [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp],

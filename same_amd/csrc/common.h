@@ -19,6 +19,8 @@ enum Slot {
     SL_SIGN, SL_SIZE, SL_TYPE, SL_FLAG0, SL_FLAG1, SL_FLAG2, SL_COUNTS, SL_X, SL_MASK,
     // uniform-grid index of the reference cells built per call by the un-indexed prune entry points (knn.hip)
     SL_K_HIST, SL_K_RANK, SL_K_SXY, SL_K_SIDX, SL_K_BBOX, SL_K_START,
+    // the queries of same_check_alignment counting-sorted by template cell (align.hip)
+    SL_Q_START, SL_Q_RANK, SL_Q_SXY, SL_Q_SIDX,
     SL_COUNT
 };
 

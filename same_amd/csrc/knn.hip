@@ -16,6 +16,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "grid.h"
 #include "scan.h"
 
 namespace {
@@ -170,11 +171,6 @@ __global__ __launch_bounds__(64 * KNN_WAVES) void knn_prune_kernel(
 // 64-lane step at the reference's typical density), with the same exact fp64 inclusion test and
 // the same (d2, original ref index) ranking as the brute-force kernel -- the grid only prunes
 // candidates that cannot pass, so outputs are bit-identical.
-struct GridDesc {
-    double x0, y0, inv_cell;
-    int gx, gy;
-};
-
 __device__ __forceinline__ unsigned long long f64_key(double v) {
     const unsigned long long u = (unsigned long long)__double_as_longlong(v);
     return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
@@ -198,11 +194,6 @@ __global__ __launch_bounds__(256) void bbox_kernel(const double *__restrict__ xy
     if ((threadIdx.x & 63) == 0) {
         atomicMin(&bbox[0], kx0); atomicMin(&bbox[1], ky0); atomicMax(&bbox[2], kx1); atomicMax(&bbox[3], ky1);
     }
-}
-
-__device__ __forceinline__ int cell_coord(double v, double v0, double inv_cell, int g) {
-    const double c = __builtin_floor((v - v0) * inv_cell);
-    return c < 0.0 ? 0 : (c >= (double)g ? g - 1 : (int)c);
 }
 
 __global__ __launch_bounds__(256) void grid_count_kernel(const double *__restrict__ rxy, int64_t n_r, GridDesc g,
@@ -330,36 +321,20 @@ static double key_to_f64(unsigned long long k) {
 int launch_knn_brute(same_ctx *ctx, const double *daxy, const double *drxy, int64_t n_r, int64_t rb, int64_t re,
                      double radius, int k, int32_t *didx, double *dd2, int32_t *dcnt);
 
-// Grid geometry for a reference set: bounding box by a device reduction and one 32-byte read-back (the only host
-// synchronisation of the grid path -- which is why an unchanged reference set should keep its index, same_knn_index_build).
-// *usable = false when the grid would not help or cannot be built (NaN/inf coordinates, radius spanning everything).
-int grid_geometry(same_ctx *ctx, const double *drxy, int64_t n_r, double radius, GridDesc *out, bool *usable) {
-    *usable = false;
+}  // namespace
+
+// ---- the grid build shared through grid.h (align.hip bins its template with it) --------------------------------------------
+int grid_bbox(same_ctx *ctx, const double *dxy, int64_t n, double box[4]) {
     unsigned long long *dbbox;
     SAME_TRY(slot_as(ctx, SL_K_BBOX, (size_t)4, &dbbox));
     unsigned long long *h = static_cast<unsigned long long *>(ctx->pinned);
     h[0] = h[1] = ~0ull; h[2] = h[3] = 0ull;
     HIP_TRY(ctx, hipMemcpyAsync(dbbox, h, 4 * sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(bbox_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(n_r, 256), 64)), dim3(256), 0, ctx->stream, drxy, n_r, dbbox);
+    hipLaunchKernelGGL(bbox_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(n, 256), 64)), dim3(256), 0, ctx->stream, dxy, n, dbbox);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(h + 8, dbbox, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    const double x0 = key_to_f64(h[8]), y0 = key_to_f64(h[9]), x1 = key_to_f64(h[10]), y1 = key_to_f64(h[11]);
-    if (!(x1 >= x0) || !(y1 >= y0) || !std::isfinite(x1 - x0) || !std::isfinite(y1 - y0)) return SAME_OK;  // NaN/inf coordinates
-    // cell edge: a hair above the radius (so |dx| <= r can never skip a cell, rounding included), and
-    // large enough to keep the grid below ~1M cells and ~1 ref per cell on sparse inputs
-    const double ext = std::max(x1 - x0, y1 - y0);
-    double cell = radius * (1.0 + 1e-9);
-    cell = std::max(cell, ext / 1024.0);
-    cell = std::max(cell, std::sqrt((x1 - x0) * (y1 - y0) / (double)std::max<int64_t>(n_r, 1)) * 0.5);
-    if (!(cell > 0.0)) cell = 1.0;  // all references coincide and radius == 0
-    GridDesc g;
-    g.x0 = x0; g.y0 = y0; g.inv_cell = 1.0 / cell;
-    g.gx = (int)std::min(1025.0, std::floor((x1 - x0) / cell) + 1.0);
-    g.gy = (int)std::min(1025.0, std::floor((y1 - y0) / cell) + 1.0);
-    *out = g;
-    // <= 9 cells: the radius spans the whole reference set, the 3 x 3 neighbourhood is everything -> brute force, 8 rows per wave
-    *usable = (int64_t)g.gx * g.gy > 9;
+    for (int q = 0; q < 4; ++q) box[q] = key_to_f64(h[8 + q]);
     return SAME_OK;
 }
 
@@ -379,6 +354,34 @@ int grid_fill(same_ctx *ctx, const double *drxy, int64_t n_r, const GridDesc &g,
     hipLaunchKernelGGL(grid_scatter_kernel, dim3((unsigned)ceil_div(n_r, 256)), dim3(256), 0, ctx->stream, drxy, n_r, g, dstart, drank,
                        dsxy, dsidx);
     HIP_TRY(ctx, hipGetLastError());
+    return SAME_OK;
+}
+
+namespace {
+
+// Grid geometry for a reference set: bounding box by a device reduction and one 32-byte read-back (the only host
+// synchronisation of the grid path -- which is why an unchanged reference set should keep its index, same_knn_index_build).
+// *usable = false when the grid would not help or cannot be built (NaN/inf coordinates, radius spanning everything).
+int grid_geometry(same_ctx *ctx, const double *drxy, int64_t n_r, double radius, GridDesc *out, bool *usable) {
+    *usable = false;
+    double box[4];
+    SAME_TRY(grid_bbox(ctx, drxy, n_r, box));
+    const double x0 = box[0], y0 = box[1], x1 = box[2], y1 = box[3];
+    if (!(x1 >= x0) || !(y1 >= y0) || !std::isfinite(x1 - x0) || !std::isfinite(y1 - y0)) return SAME_OK;  // NaN/inf coordinates
+    // cell edge: a hair above the radius (so |dx| <= r can never skip a cell, rounding included), and
+    // large enough to keep the grid below ~1M cells and ~1 ref per cell on sparse inputs
+    const double ext = std::max(x1 - x0, y1 - y0);
+    double cell = radius * (1.0 + 1e-9);
+    cell = std::max(cell, ext / 1024.0);
+    cell = std::max(cell, std::sqrt((x1 - x0) * (y1 - y0) / (double)std::max<int64_t>(n_r, 1)) * 0.5);
+    if (!(cell > 0.0)) cell = 1.0;  // all references coincide and radius == 0
+    GridDesc g;
+    g.x0 = x0; g.y0 = y0; g.inv_cell = 1.0 / cell;
+    g.gx = (int)std::min(1025.0, std::floor((x1 - x0) / cell) + 1.0);
+    g.gy = (int)std::min(1025.0, std::floor((y1 - y0) / cell) + 1.0);
+    *out = g;
+    // <= 9 cells: the radius spans the whole reference set, the 3 x 3 neighbourhood is everything -> brute force, 8 rows per wave
+    *usable = (int64_t)g.gx * g.gy > 9;
     return SAME_OK;
 }
 

@@ -1,11 +1,11 @@
-"""eval_utils.check_triangle_violations (src/eval_utils.py:66-223), same signature: triangle
-orientation flips after alignment, and which nodes sit in flipped triangles (optionally by a
-node-local majority rule).  The triangle loop runs in csrc/match.hip (tri_flip_stats_kernel);
-id bookkeeping and the per-node rule are host work on small arrays."""
+"""eval_utils of the reference, same signatures.  check_triangle_violations (src/eval_utils.py:66-223): triangle orientation flips
+after alignment, and which nodes sit in flipped triangles (optionally by a node-local majority rule); the triangle loop runs in
+csrc/match.hip (tri_flip_stats_kernel); id bookkeeping and the per-node rule are host work on small arrays.  check_alignment
+(src/eval_utils.py:6-53): the k-nearest-template label check, searched in csrc/align.hip."""
 import numpy as np
 import pandas as pd
 
-from . import ops
+from . import _lib, ops
 
 
 def check_triangle_violations(outputDF, mc_align, aligned_id_col="aligned_metacell_index",
@@ -88,22 +88,76 @@ def check_triangle_violations(outputDF, mc_align, aligned_id_col="aligned_metace
     return outputDF, stats
 
 
-def check_alignment(queryDF, templateDF, xcol, ycol, ctype_col="cell_type", kNN=1, ctx=None):
-    """eval_utils.check_alignment (src/eval_utils.py:6-55), same signature: is the query cell's type among the
-    types of its kNN nearest template cells?  cKDTree.query(k) = the k nearest by Euclidean distance; here the
-    radius-free form of the prune kernel (radius = +inf, ranking by (d2, template index))."""
+def _knn_count(kNN):
+    """the k that cKDTree.query(k=kNN) reads: an integral number >= 1"""
+    if isinstance(kNN, (bool, np.bool_, int, np.integer)) or (isinstance(kNN, (float, np.floating)) and float(kNN).is_integer()):
+        k = int(kNN)
+        if k >= 1:
+            return k
+    raise ValueError(f"kNN must be an integer >= 1, got {kNN!r}")
+
+
+def _label_codes(q_labels, t_labels):
+    """int32 codes of the query and template labels whose equality is Python `==` of the labels: pd.factorize merges values that
+    compare equal (1 == 1.0 == True, '1' != 1); None equals None; NaN and every other missing value equal nothing (-1 on the query
+    side, -2 on the template side)."""
+    both = pd.concat([pd.Series(q_labels).reset_index(drop=True), pd.Series(t_labels).reset_index(drop=True)], ignore_index=True)
+    codes, uniques = pd.factorize(both)
+    codes = codes.astype(np.int32)
+    missing = np.flatnonzero(codes < 0)
+    if len(missing):
+        is_none = np.asarray(both.to_numpy(dtype=object)[missing] == None, dtype=bool)  # noqa: E711 (elementwise)
+        codes[missing] = np.where(is_none, len(uniques), np.where(missing < len(q_labels), -1, -2))
+    return codes[:len(q_labels)], codes[len(q_labels):]
+
+
+def check_alignment(queryDF, templateDF, xcol, ycol, ctype_col="cell_type", kNN=1, *, ctx=None, return_stats=False):
+    """eval_utils.check_alignment (src/eval_utils.py:6-53), same signature and result: is the query cell's label among the labels of
+    its kNN nearest template cells (cKDTree.query(k=kNN))?  Returns (queryDF copy with `_{kNN}NN_match` -- and, for kNN == 1,
+    `_1NN_match_ctype`, the nearest template cell's label --, the column's mean); return_stats=True adds a dict of row counts.
+
+    The search runs in csrc/align.hip (same_check_alignment), which decides every row whose answer does not depend on how scipy
+    orders (nearly) equidistant template points; the rows in doubt are asked of cKDTree itself, built as the reference builds it."""
     queryDF = queryDF.copy()
     required = {xcol, ycol, ctype_col}
     if not required.issubset(queryDF.columns) or not required.issubset(templateDF.columns):
         raise ValueError(f"Both DataFrames must contain the columns: {required}")
-    q = queryDF[[xcol, ycol]].to_numpy(dtype=np.float64)
-    t = templateDF[[xcol, ycol]].to_numpy(dtype=np.float64)
-    idx, _, _ = ops.knn_prune(q, t, float("inf"), int(kNN), want_d2=False, ctx=ctx)
-    qt = queryDF[ctype_col].to_numpy()
-    tt = templateDF[ctype_col].to_numpy()
-    near_types = tt[np.maximum(idx, 0)]
+    txy = templateDF[[xcol, ycol]].to_numpy(dtype=np.float64)
+    if not np.isfinite(txy).all():
+        raise ValueError("data must be finite, check for nan or inf values")
+    qxy = queryDF[[xcol, ycol]].to_numpy(dtype=np.float64)
+    if not np.isfinite(qxy).all():
+        raise ValueError("'x' must be finite, check for nan or inf values")
+    k = _knn_count(kNN)
+    if k > _lib.ALIGN_MAX_KNN:
+        raise ValueError(f"kNN={kNN} exceeds the device cap SAME_ALIGN_MAX_KNN = {_lib.ALIGN_MAX_KNN}")
+    n_q, n_t = len(qxy), len(txy)
+    if n_q and k > n_t:   # the reference's .iloc of scipy's missing-neighbour index n_t
+        raise IndexError("single positional indexer is out-of-bounds" if k == 1 else "positional indexers are out-of-bounds")
+    ctx = ctx if ctx is not None else _lib.default_context()
+    qcode, tcode = _label_codes(queryDF[ctype_col].to_numpy(), templateDF[ctype_col].to_numpy())
     col = "_" + str(kNN) + "NN_match"
-    queryDF.loc[:, col] = ((near_types == qt[:, None]) & (idx >= 0)).any(axis=1)
+    n_doubt = 0
+    if n_q:
+        flag, nearest = ops.check_alignment(qxy, qcode, txy, tcode, k, ctx=ctx)
+        match = (flag & _lib.ALIGN_MATCH).astype(bool)
+        doubt = np.flatnonzero((flag & _lib.ALIGN_DECIDED) == 0)
+        n_doubt = len(doubt)
+        if n_doubt:
+            from scipy.spatial import cKDTree
+
+            _, idx = cKDTree(templateDF[[xcol, ycol]]).query(qxy[doubt], k=k)
+            if k == 1:
+                nearest[doubt] = idx
+                match[doubt] = tcode[idx] == qcode[doubt]
+            else:
+                match[doubt] = (tcode[idx] == qcode[doubt, None]).any(axis=1)
+    else:
+        match, nearest = [], np.zeros(0, np.intp)
+    queryDF.loc[:, col] = match
     if kNN == 1:
-        queryDF.loc[:, "_" + str(kNN) + "NN_match_ctype"] = near_types[:, 0]
-    return queryDF, queryDF[col].mean()
+        queryDF.loc[:, "_" + str(kNN) + "NN_match_ctype"] = templateDF[ctype_col].iloc[nearest].values
+    alignment_score = queryDF[col].mean()
+    if not return_stats:
+        return queryDF, alignment_score
+    return queryDF, alignment_score, {"rows": n_q, "rows_decided_on_device": n_q - n_doubt, "rows_resolved_on_host": n_doubt, "kNN": k}

@@ -430,6 +430,22 @@ def tri_flip_stats(axy, mapped_xy, matched, triangles, type_id=None, ctx=None):
     return flag, nt, nf
 
 
+def check_alignment(qxy, qcode, txy, tcode, knn, ctx=None):
+    """Label check of the knn nearest template points (same_check_alignment) -> (flag (n_q,) uint8 [bit0 match, bit1 decided on the
+    device], nearest (n_q,) int32 for knn == 1 (-1 where not decided), else None)."""
+    ctx = _ctx(ctx)
+    qxy, txy = as_c(qxy, F64).reshape(-1, 2), as_c(txy, F64).reshape(-1, 2)
+    qcode, tcode = as_c(qcode, I32), as_c(tcode, I32)
+    n_q, n_t, k = len(qxy), len(txy), int(knn)
+    assert len(qcode) == n_q and len(tcode) == n_t
+    flag = np.empty(n_q, U8)
+    nearest = np.empty(n_q, I32) if k == 1 else None
+    with ctx.lock:
+        ctx.check(ctx.lib.same_check_alignment(ctx.handle, qxy.ctypes.data, n_q, qcode.ctypes.data, txy.ctypes.data, n_t, tcode.ctypes.data,
+                                               k, flag.ctypes.data, _lib._ptr(nearest)), "same_check_alignment")
+    return flag, nearest
+
+
 def collapse_candidates(xy, triangles, r_max, angle_enabled, cos_thr, type_id, size, max_size, ctx=None):
     """One collapse iteration's per-triangle work -> (flag [bit0 valid, bit1 collapsible], perimeter, total size)."""
     ctx = _ctx(ctx)

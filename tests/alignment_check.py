@@ -3,7 +3,8 @@ fixture tests/golden/check_alignment.npz (tools/gen_golden_alignment.py).
 
 The rule, in numpy: d2 = dx*dx + dy*dy in fp64 against every template point; d_k = the k-th smallest; B = the points within
 d_k * REL + ABS of d_k, S = the points below B.  k > 1 is decided when the label is in S (match), in no member of B (no match) or
-|S| + |B| <= k (match); k == 1 only when |S| = 0 and |B| = 1, and then the nearest template row is that member of B."""
+|S| + |B| <= k (match); k == 1 only when |S| = 0 and |B| = 1, and then the nearest template row is that member of B.  A row whose
+d_k is not finite (d2 overflowed) is in doubt, as in the kernel."""
 import numpy as np
 
 REL, ABS = 1e-12, 1e-300   # ALIGN_REL, ALIGN_ABS of csrc/align.hip
@@ -22,10 +23,11 @@ def statement(qxy, qcode, txy, tcode, k, block=2048):
         q = qxy[b:b + block]
         dx = txy[None, :, 0] - q[:, None, 0]
         dy = txy[None, :, 1] - q[:, None, 1]
-        d2 = dx * dx + dy * dy
-        dk = np.partition(d2, k - 1, axis=1)[:, k - 1]
-        m = dk * REL + ABS
-        lo, hi = (dk - m)[:, None], (dk + m)[:, None]
+        with np.errstate(over="ignore", invalid="ignore"):
+            d2 = dx * dx + dy * dy
+            dk = np.partition(d2, k - 1, axis=1)[:, k - 1]
+            m = dk * REL + ABS
+            lo, hi = (dk - m)[:, None], (dk + m)[:, None]
         S, B = d2 < lo, (d2 >= lo) & (d2 <= hi)
         eq = tcode[None, :] == qcode[b:b + block, None]
         ms, mb = (S & eq).any(1), (B & eq).any(1)
@@ -33,10 +35,11 @@ def statement(qxy, qcode, txy, tcode, k, block=2048):
         if k == 1:
             dec = (ns == 0) & (nb == 1)
             match = mb
-            nearest[b:b + block] = np.where(dec, B.argmax(1), -1)
+            nearest[b:b + block] = np.where(dec & np.isfinite(dk), B.argmax(1), -1)
         else:
             dec = ms | ~mb | (ns + nb <= k)
             match = ms | (mb & (ns + nb <= k))
+        dec = dec & np.isfinite(dk)   # the kernel's isfinite(dk) guard
         flag[b:b + block] = np.where(dec, DECIDED | np.where(match, MATCH, 0), 0)
         n_s[b:b + block], n_b[b:b + block] = ns, nb
     return flag, nearest, n_s, n_b

@@ -17,7 +17,7 @@ struct AssignArgs {
     uint8_t *alive = nullptr;             // or null: the greedy rule's pair flags, cleared (match_rows_kernel reads them)
     int32_t *match_pair = nullptr;        // [n] out: the pair of each row, -1 = its no-match column
     unsigned long long *res = nullptr;    // [4] out: searches, columns finalized, flags (!= 0: not certified), objective (fp64 bits)
-    // the work arrays (carve): per column (n_r + n) ...
+    // the work arrays (lay): per column (n_r + n) ...
     int32_t *col_row = nullptr, *pred = nullptr, *mark = nullptr, *list = nullptr, *done = nullptr, *ppair = nullptr;
     double *v = nullptr, *d = nullptr, *ec = nullptr;
     // ... per row
@@ -25,8 +25,8 @@ struct AssignArgs {
     double *rc = nullptr;
 };
 
-size_t work_bytes(int64_t n, int64_t n_r);
-void carve(AssignArgs *a, char *work);           // the work arrays of `a` (n, n_r set) in `work` (work_bytes, 256-byte aligned)
+// the work arrays of `a` (n, n_r set) as the next takes of a buffer's layout (win::Carver: measured, then placed)
+void lay(AssignArgs &a, win::Carver &cv);
 int64_t default_max_pops(int64_t n, int64_t n_r, int64_t P);
 // the solve and its certificate for up to SAME_LAUNCH_WINDOWS problems: two launches, no wait
 int launch(same_ctx *ctx, const AssignArgs *jobs, int n_w);

@@ -289,25 +289,13 @@ __global__ __launch_bounds__(256) void certificate_kernel(win::Batch<asg::Assign
 
 namespace asg {
 
-size_t work_bytes(int64_t n, int64_t n_r) {
-    const size_t C = (size_t)(n + n_r);
-    win::Carver cv;
-    for (int q = 0; q < 6; ++q) cv.take(C * 4);     // col_row pred mark list done ppair
-    cv.take((size_t)n * 4);                           // row_col
-    for (int q = 0; q < 3; ++q) cv.take(C * 8);     // v d ec
-    cv.take((size_t)n * 8);                           // rc
-    return cv.off;
-}
-
-void carve(AssignArgs *a, char *work) {
-    const size_t C = (size_t)(a->n + a->n_r);
-    win::Carver cv;
-    int32_t **ints[6] = {&a->col_row, &a->pred, &a->mark, &a->list, &a->done, &a->ppair};
-    for (auto p : ints) *p = reinterpret_cast<int32_t *>(work + cv.take(C * 4));
-    a->row_col = reinterpret_cast<int32_t *>(work + cv.take((size_t)a->n * 4));
-    double **dbls[3] = {&a->v, &a->d, &a->ec};
-    for (auto p : dbls) *p = reinterpret_cast<double *>(work + cv.take(C * 8));
-    a->rc = reinterpret_cast<double *>(work + cv.take((size_t)a->n * 8));
+void lay(AssignArgs &a, win::Carver &cv) {
+    // sized by the counts themselves (rfn::lay gives every array one element at least)
+    const size_t C = (size_t)(a.n + a.n_r);
+    for (int32_t **p : {&a.col_row, &a.pred, &a.mark, &a.list, &a.done, &a.ppair}) *p = cv.take<int32_t>(C);
+    a.row_col = cv.take<int32_t>((size_t)a.n);
+    for (double **p : {&a.v, &a.d, &a.ec}) *p = cv.take<double>(C);
+    a.rc = cv.take<double>((size_t)a.n);
 }
 
 int64_t default_max_pops(int64_t n, int64_t n_r, int64_t P) {
@@ -339,55 +327,35 @@ extern "C" int same_sparse_assign(same_ctx *ctx, const int32_t *pairs, const dou
     REQUIRE(ctx, P >= 0 && n_m >= 0 && n_r >= 0 && n_m + n_r < ((int64_t)1 << 30) && P < ((int64_t)1 << 31) - 1);
     REQUIRE(ctx, (P == 0 || (pairs && costs)) && (n_m == 0 || (unmatched && out_match_pair)) && out_stats);
     // the pairs by row (stable), each (row, column) once
-    std::vector<int32_t> prow((size_t)n_m + 1, 0), order((size_t)P), csr((size_t)P * 2);
-    std::vector<double> ccsr((size_t)P);
-    for (int64_t p = 0; p < P; ++p) {
-        const int32_t i = pairs[2 * p], j = pairs[2 * p + 1];
-        REQUIRE(ctx, i >= 0 && i < n_m && j >= 0 && j < n_r);
-        ++prow[(size_t)i + 1];
-    }
-    for (int64_t i = 0; i < n_m; ++i) prow[(size_t)i + 1] += prow[(size_t)i];
-    {
-        std::vector<int32_t> at(prow.begin(), prow.end() - 1);
-        for (int64_t p = 0; p < P; ++p) order[(size_t)at[(size_t)pairs[2 * p]]++] = (int32_t)p;
-    }
-    std::vector<int64_t> seen((size_t)n_r, -1);
-    for (int64_t i = 0; i < n_m; ++i)
-        for (int32_t q = prow[(size_t)i]; q < prow[(size_t)i + 1]; ++q) {
-            const int32_t p = order[(size_t)q], j = pairs[2 * (int64_t)p + 1];
-            if (seen[(size_t)j] == i) {
-                ctx->err = "invalid argument: a (row, column) pair given twice";
-                return SAME_EINVAL;
-            }
-            seen[(size_t)j] = i;
-            csr[2 * (size_t)q] = (int32_t)i;
-            csr[2 * (size_t)q + 1] = j;
-            ccsr[(size_t)q] = costs[p];
-        }
+    same_pair_csr by_row;
+    SAME_TRY(same_pairs_by_row(ctx, pairs, costs, P, n_m, n_r, &by_row));
+    const std::vector<int32_t> &order = by_row.order;
     SAME_TRY(same_use(ctx));
-    win::Carver cv;
-    const size_t o_prow = cv.take(((size_t)n_m + 1) * 4), o_pairs = cv.take((size_t)P * 8 + 8), o_cost = cv.take((size_t)P * 8 + 8),
-                 o_unm = cv.take((size_t)n_m * 8 + 8), o_match = cv.take((size_t)n_m * 4 + 4), o_res = cv.take(4 * 8),
-                 o_work = cv.take(asg::work_bytes(n_m, n_r));
-    char *d = nullptr;
-    SAME_TRY(slot_as(ctx, SL_OUT0, cv.off, &d));
     asg::AssignArgs a{};
-    a.prow = reinterpret_cast<const int32_t *>(d + o_prow);
-    a.pairs = reinterpret_cast<const int32_t *>(d + o_pairs);
-    a.cost = reinterpret_cast<const double *>(d + o_cost);
-    a.unm = reinterpret_cast<const double *>(d + o_unm);
     a.n = n_m;
     a.n_r = n_r;
-    a.match_pair = reinterpret_cast<int32_t *>(d + o_match);
-    a.res = reinterpret_cast<unsigned long long *>(d + o_res);
     a.max_pops = asg::default_max_pops(n_m, n_r, P);
-    asg::carve(&a, d + o_work);
-    SAME_COPY(ctx, d + o_prow, prow.data(), prow.size() * 4, hipMemcpyHostToDevice);
+    int32_t *d_prow, *d_pairs;
+    double *d_cost, *d_unm;
+    auto lay = [&](win::Carver cv) {       // (one element more than each input: no array is empty)
+        a.prow = d_prow = cv.take<int32_t>((size_t)n_m + 1);
+        a.pairs = d_pairs = cv.take<int32_t>((size_t)P * 2 + 2);
+        a.cost = d_cost = cv.take<double>((size_t)P + 1);
+        a.unm = d_unm = cv.take<double>((size_t)n_m + 1);
+        a.match_pair = cv.take<int32_t>((size_t)n_m + 1);
+        a.res = cv.take<unsigned long long>(4);
+        asg::lay(a, cv);
+        return cv.off;
+    };
+    char *d = nullptr;
+    SAME_TRY(slot_as(ctx, SL_OUT0, lay(win::Carver()), &d));
+    lay(win::Carver(d));
+    SAME_COPY(ctx, d_prow, by_row.prow.data(), by_row.prow.size() * 4, hipMemcpyHostToDevice);
     if (P) {
-        SAME_COPY(ctx, d + o_pairs, csr.data(), (size_t)P * 8, hipMemcpyHostToDevice);
-        SAME_COPY(ctx, d + o_cost, ccsr.data(), (size_t)P * 8, hipMemcpyHostToDevice);
+        SAME_COPY(ctx, d_pairs, by_row.csr.data(), (size_t)P * 8, hipMemcpyHostToDevice);
+        SAME_COPY(ctx, d_cost, by_row.ccsr.data(), (size_t)P * 8, hipMemcpyHostToDevice);
     }
-    if (n_m) SAME_COPY(ctx, d + o_unm, unmatched, (size_t)n_m * 8, hipMemcpyHostToDevice);
+    if (n_m) SAME_COPY(ctx, d_unm, unmatched, (size_t)n_m * 8, hipMemcpyHostToDevice);
     SAME_TRY(asg::launch(ctx, &a, 1));
     std::vector<int32_t> mp((size_t)n_m);
     unsigned long long res[4] = {};

@@ -152,6 +152,50 @@ static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // Host-side index validation: a bad index must come back as SAME_ERANGE, never as a GPU fault.
 int check_index_range(same_ctx *ctx, const int32_t *idx, int64_t n, int64_t lo, int64_t hi, const char *what);
 
+// The caller's pairs of a sparse problem (same_sparse_assign, the same_refine_matching calls) by row: prow[n_m + 1]; order[q] = the caller's
+// number of the q-th pair, rows ascending and the caller's order inside a row; where[p] = the place of the caller's pair p; csr / ccsr =
+// the pairs and their costs in that order.  A (row, column) pair given twice is refused.
+struct same_pair_csr {
+    std::vector<int32_t> prow, order, where, csr;
+    std::vector<double> ccsr;
+};
+inline int same_pairs_by_row(same_ctx *ctx, const int32_t *pairs, const double *costs, int64_t P, int64_t n_m, int64_t n_r, same_pair_csr *out) {
+    std::vector<int32_t> &prow = out->prow, &order = out->order, &where = out->where, &csr = out->csr;
+    prow.assign((size_t)n_m + 1, 0);
+    order.resize((size_t)P);
+    where.resize((size_t)P);
+    csr.resize((size_t)P * 2);
+    out->ccsr.resize((size_t)P);
+    for (int64_t p = 0; p < P; ++p) {
+        const int32_t i = pairs[2 * p], j = pairs[2 * p + 1];
+        REQUIRE(ctx, i >= 0 && i < n_m && j >= 0 && j < n_r);
+        ++prow[(size_t)i + 1];
+    }
+    for (int64_t i = 0; i < n_m; ++i) prow[(size_t)i + 1] += prow[(size_t)i];
+    {
+        std::vector<int32_t> at(prow.begin(), prow.end() - 1);
+        for (int64_t p = 0; p < P; ++p) {
+            const int32_t q = at[(size_t)pairs[2 * p]]++;
+            order[(size_t)q] = (int32_t)p;
+            where[(size_t)p] = q;
+        }
+    }
+    std::vector<int64_t> seen((size_t)n_r, -1);
+    for (int64_t i = 0; i < n_m; ++i)
+        for (int32_t q = prow[(size_t)i]; q < prow[(size_t)i + 1]; ++q) {
+            const int32_t p = order[(size_t)q], j = pairs[2 * (int64_t)p + 1];
+            if (seen[(size_t)j] == i) {
+                ctx->err = "invalid argument: a (row, column) pair given twice";
+                return SAME_EINVAL;
+            }
+            seen[(size_t)j] = i;
+            csr[2 * (size_t)q] = (int32_t)i;
+            csr[2 * (size_t)q + 1] = j;
+            out->ccsr[(size_t)q] = costs[p];
+        }
+    return SAME_OK;
+}
+
 // Device cores shared between the host-buffer entry points and the window pipeline (window.hip): every pointer is a device
 // pointer, the calls enqueue on ctx->stream (same_greedy_core reads one counter back per round).
 int same_pair_rowmin_core(same_ctx *ctx, const int32_t *dpairs, const double *dcosts, int64_t P, int64_t n_m, double *dout);

@@ -446,48 +446,24 @@ __global__ __launch_bounds__(scan::NT) void dd_emit_kernel(Batch<Job> b) {
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 // the work buffer of a set of n points: [zeroed head: status words | cell scan words | cell counts | owner counts | owner scan words]
 // then parameters, cell offsets, per-point cell / slot / sorted order, per-owner triangles
-struct Layout {
-    size_t o_st, o_scan_cells, o_cell_cnt, o_own_cnt, o_scan_own, zero_bytes, o_par, o_cell_start, o_cell_of, o_slot, o_sorted, o_own, total;
-    int64_t ncell_cap;
-};
-Layout layout_for(int64_t n) {
-    Layout l{};
-    l.ncell_cap = 2 * n + 64;
-    Carver cv;
-    l.o_st = cv.take(ST_WORDS * 8);
-    l.o_scan_cells = cv.take(scan::status_bytes(l.ncell_cap));
-    l.o_cell_cnt = cv.take((size_t)l.ncell_cap * 4);
-    l.o_own_cnt = cv.take((size_t)n * 4);
-    l.o_scan_own = cv.take(scan::status_bytes(n));
-    l.zero_bytes = cv.off;
-    l.o_par = cv.take(sizeof(Par));
-    l.o_cell_start = cv.take((size_t)(l.ncell_cap + 1) * 4);
-    l.o_cell_of = cv.take((size_t)n * 4);
-    l.o_slot = cv.take((size_t)n * 4);
-    l.o_sorted = cv.take((size_t)n * 4);
-    l.o_own = cv.take((size_t)n * OWN_CAP * 12);
-    l.total = cv.off;
-    return l;
-}
-Job job_on(char *base, const Layout &l, const double *xy, int64_t n, int32_t *out, int64_t cap_out) {
-    Job j{};
-    j.xy = xy;
-    j.n = n;
-    j.ncell_cap = l.ncell_cap;
-    j.cap_out = cap_out;
-    j.st = reinterpret_cast<unsigned long long *>(base + l.o_st);
-    j.scan_cells = scan::arg(reinterpret_cast<unsigned long long *>(base + l.o_scan_cells));
-    j.cell_cnt = reinterpret_cast<unsigned *>(base + l.o_cell_cnt);
-    j.own_cnt = reinterpret_cast<unsigned *>(base + l.o_own_cnt);
-    j.scan_own = scan::arg(reinterpret_cast<unsigned long long *>(base + l.o_scan_own));
-    j.par = reinterpret_cast<Par *>(base + l.o_par);
-    j.cell_start = reinterpret_cast<unsigned *>(base + l.o_cell_start);
-    j.cell_of = reinterpret_cast<int32_t *>(base + l.o_cell_of);
-    j.slot = reinterpret_cast<unsigned *>(base + l.o_slot);
-    j.sorted = reinterpret_cast<int32_t *>(base + l.o_sorted);
-    j.own_tris = reinterpret_cast<int32_t *>(base + l.o_own);
-    j.out = out;
-    return j;
+// (measured without a base, placed with one; answers the length of the head to zero)
+size_t lay(Job &j, Carver cv, size_t *total) {
+    const int64_t n = j.n;
+    j.ncell_cap = 2 * n + 64;
+    j.st = cv.take<unsigned long long>(ST_WORDS);
+    j.scan_cells = scan::arg(cv.scan_words(j.ncell_cap));
+    j.cell_cnt = cv.take<unsigned>((size_t)j.ncell_cap);
+    j.own_cnt = cv.take<unsigned>((size_t)n);
+    j.scan_own = scan::arg(cv.scan_words(n));
+    const size_t zero_bytes = cv.off;
+    j.par = cv.take<Par>(1);
+    j.cell_start = cv.take<unsigned>((size_t)j.ncell_cap + 1);
+    j.cell_of = cv.take<int32_t>((size_t)n);
+    j.slot = cv.take<unsigned>((size_t)n);
+    j.sorted = cv.take<int32_t>((size_t)n);
+    j.own_tris = cv.take<int32_t>((size_t)n * OWN_CAP * 3);
+    *total = cv.off;
+    return zero_bytes;
 }
 
 // the kernels for up to SAME_LAUNCH_WINDOWS sets (heads already zeroed): nine launches
@@ -531,6 +507,7 @@ int same_window_delaunay(same_window *const *windows, int n_windows, double radi
     const bool ok = settings_answerable(radius, angle_enabled, cos_thr);
     const Settings set{radius, cos_thr, guard};
     std::vector<Job> jobs;
+    std::vector<size_t> zero_bytes;       // of each job's work buffer
     std::vector<int> at((size_t)n_windows, -1);
     for (int i = 0; i < n_windows; ++i) {
         same_window *w = windows[i];
@@ -540,22 +517,25 @@ int same_window_delaunay(same_window *const *windows, int n_windows, double radi
         out_n_tris[i] = 0;
         if (out_status[i]) continue;
         const int64_t n = w->n_ua, cap_out = 2 * n;
-        const Layout l = layout_for(n);
-        SAME_TRY(ensure(ctx, w->dd_work, l.total));
+        Job jb{};
+        jb.xy = w->axy_c;
+        jb.n = n;
+        jb.cap_out = cap_out;
+        size_t total = 0;
+        lay(jb, Carver(), &total);
+        SAME_TRY(ensure(ctx, w->dd_work, total));
         SAME_TRY(ensure(ctx, w->dd_tris, (size_t)cap_out * 12));
+        zero_bytes.push_back(lay(jb, Carver(w->dd_work.p), &total));
+        jb.out = static_cast<int32_t *>(w->dd_tris.p);
         at[(size_t)i] = (int)jobs.size();
-        jobs.push_back(job_on(static_cast<char *>(w->dd_work.p), l, w->axy_c, n, static_cast<int32_t *>(w->dd_tris.p), cap_out));
-        jobs.back().ncell_cap = l.ncell_cap;
+        jobs.push_back(jb);
     }
     if (jobs.empty()) return SAME_OK;
     int rc = SAME_OK;
     for (size_t g = 0; g < jobs.size() && rc == SAME_OK; g += SAME_LAUNCH_WINDOWS) {
         const int n_g = (int)std::min<size_t>(SAME_LAUNCH_WINDOWS, jobs.size() - g);
         ZeroArgs zr[SAME_LAUNCH_WINDOWS];
-        for (int q = 0; q < n_g; ++q) {
-            const Job &jb = jobs[g + (size_t)q];
-            zr[q] = ZeroArgs{{jb.st, nullptr}, {layout_for(jb.n).zero_bytes, 0}};
-        }
+        for (int q = 0; q < n_g; ++q) zr[q] = ZeroArgs{{jobs[g + (size_t)q].st, nullptr}, {zero_bytes[g + (size_t)q], 0}};
         rc = launch_zero(ctx, zr, n_g);
         if (rc == SAME_OK) rc = launch_group(ctx, jobs.data() + g, n_g, set);
     }
@@ -594,15 +574,21 @@ int same_delaunay_filtered(same_ctx *ctx, const double *xy, int64_t n, double ra
     *out_status = !settings_answerable(radius, angle_enabled, cos_thr) ? SAME_DD_NO_ANGLE : (n < 3 ? SAME_DD_FEW_POINTS : 0);
     if (*out_status) return SAME_OK;
     SAME_TRY(same_use(ctx));
-    const Layout l = layout_for(n);
     double *dxy = nullptr;
     char *work = nullptr;
     int32_t *dout = nullptr;
+    Job jb{};
+    jb.n = n;
+    jb.cap_out = 2 * n;
+    size_t total = 0;
+    lay(jb, Carver(), &total);
     SAME_TRY(up_as(ctx, SL_AXY, xy, (size_t)n * 2, &dxy));
-    SAME_TRY(slot_as(ctx, SL_X, l.total, &work));
+    SAME_TRY(slot_as(ctx, SL_X, total, &work));
     SAME_TRY(slot_as(ctx, SL_TRIS, (size_t)(2 * n) * 3, &dout));
-    Job jb = job_on(work, l, dxy, n, dout, 2 * n);
-    SAME_FILL(ctx, work, 0, l.zero_bytes);
+    const size_t zero_bytes = lay(jb, Carver(work), &total);
+    jb.xy = dxy;
+    jb.out = dout;
+    SAME_FILL(ctx, work, 0, zero_bytes);
     SAME_TRY(launch_group(ctx, &jb, 1, Settings{radius, cos_thr, guard}));
     unsigned long long *h = static_cast<unsigned long long *>(ctx->pinned);
     SAME_COPY(ctx, h, jb.st, 16, hipMemcpyDeviceToHost);

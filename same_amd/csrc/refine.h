@@ -44,7 +44,7 @@ struct RefineArgs {
     const double *rsize = nullptr;        // the window path's capacity: reference section sizes, at ref_rows[j] for reference j and
     const int32_t *ref_rows = nullptr;    // at ref_row[p] for pair p's; P pairs
     int64_t P = 0, max_matches = 1, multiplier = 0;   // multiplier 0 = None (the frame's largest size)
-    // the work arrays (carve)
+    // the work arrays (lay)
     int32_t *match = nullptr;             // [n] the search's matching (its result)
     int32_t *count = nullptr;             // [n_r] cells holding each reference
     long long *hsum = nullptr;            // [n_r] sum of their ids: THE holder where count is 1 (the only swap partners)
@@ -61,8 +61,8 @@ struct RefineArgs {
     Prop *best = nullptr;                 // [n]
 };
 
-size_t work_bytes(int64_t n, int64_t n_r, int64_t cap_tr);
-void carve(RefineArgs *a, char *work);    // the work arrays of `a` (n, n_r, cap_tr set) in `work` (work_bytes, 256-byte aligned)
+// the work arrays of `a` (n, n_r, cap_tr set) as the next takes of a buffer's layout (win::Carver: measured, then placed)
+void lay(RefineArgs &a, win::Carver &cv);
 // the search for up to SAME_LAUNCH_WINDOWS problems, enqueue only.  setup: the matching from `start`, the incidence lists, the
 // objective at the start; rounds: `rounds` more rounds (each returns at once once its window settled or reached its cap), then the
 // objective now

@@ -410,47 +410,25 @@ __global__ __launch_bounds__(256) void refine_apply_kernel(Batch<RefineArgs> b) 
 
 namespace rfn {
 
-size_t work_bytes(int64_t n, int64_t n_r, int64_t cap_tr) {
-    const size_t N = (size_t)std::max<int64_t>(n, 1), R = (size_t)std::max<int64_t>(n_r, 1), T = (size_t)std::max<int64_t>(cap_tr, 1);
-    Carver cv;
-    cv.take(N * 4);                 // match
-    cv.take(R * 4);                 // count
-    cv.take(R * 8);                 // hsum
-    cv.take(R * 4);                 // limit
-    cv.take(T * 12);                // tsort
-    cv.take(T);                     // tsign
-    cv.take(T * 8);                 // tw
-    cv.take(T);                     // q
-    cv.take(N * 4);                 // deg
-    cv.take(N * 4);                 // cur
-    cv.take((N + 1) * 4);           // off
-    cv.take(T * 12);                // inc
-    cv.take(scan::status_bytes(n)); // st
-    cv.take((N + R) * 8);           // slot[0]
-    cv.take((N + R) * 8);           // slot[1]
-    cv.take(N * sizeof(Prop));      // best
-    return cv.off;
-}
-
-void carve(RefineArgs *a, char *work) {
-    const size_t N = (size_t)std::max<int64_t>(a->n, 1), R = (size_t)std::max<int64_t>(a->n_r, 1), T = (size_t)std::max<int64_t>(a->cap_tr, 1);
-    Carver cv;
-    a->match = reinterpret_cast<int32_t *>(work + cv.take(N * 4));
-    a->count = reinterpret_cast<int32_t *>(work + cv.take(R * 4));
-    a->hsum = reinterpret_cast<long long *>(work + cv.take(R * 8));
-    a->limit = reinterpret_cast<int32_t *>(work + cv.take(R * 4));
-    a->tsort = reinterpret_cast<int32_t *>(work + cv.take(T * 12));
-    a->tsign = reinterpret_cast<int8_t *>(work + cv.take(T));
-    a->tw = reinterpret_cast<double *>(work + cv.take(T * 8));
-    a->q = reinterpret_cast<uint8_t *>(work + cv.take(T));
-    a->deg = reinterpret_cast<unsigned *>(work + cv.take(N * 4));
-    a->cur = reinterpret_cast<unsigned *>(work + cv.take(N * 4));
-    a->off = reinterpret_cast<int32_t *>(work + cv.take((N + 1) * 4));
-    a->inc = reinterpret_cast<int32_t *>(work + cv.take(T * 12));
-    a->st = reinterpret_cast<unsigned long long *>(work + cv.take(scan::status_bytes(a->n)));
-    a->slot[0] = reinterpret_cast<unsigned long long *>(work + cv.take((N + R) * 8));
-    a->slot[1] = reinterpret_cast<unsigned long long *>(work + cv.take((N + R) * 8));
-    a->best = reinterpret_cast<Prop *>(work + cv.take(N * sizeof(Prop)));
+void lay(RefineArgs &a, Carver &cv) {
+    // every array holds one element at least (asg::lay sizes by the counts themselves)
+    const size_t N = (size_t)std::max<int64_t>(a.n, 1), R = (size_t)std::max<int64_t>(a.n_r, 1), T = (size_t)std::max<int64_t>(a.cap_tr, 1);
+    a.match = cv.take<int32_t>(N);
+    a.count = cv.take<int32_t>(R);
+    a.hsum = cv.take<long long>(R);
+    a.limit = cv.take<int32_t>(R);
+    a.tsort = cv.take<int32_t>(T * 3);
+    a.tsign = cv.take<int8_t>(T);
+    a.tw = cv.take<double>(T);
+    a.q = cv.take<uint8_t>(T);
+    a.deg = cv.take<unsigned>(N);
+    a.cur = cv.take<unsigned>(N);
+    a.off = cv.take<int32_t>(N + 1);
+    a.inc = cv.take<int32_t>(T * 3);
+    a.st = cv.scan_words(a.n);
+    a.slot[0] = cv.take<unsigned long long>(N + R);
+    a.slot[1] = cv.take<unsigned long long>(N + R);
+    a.best = cv.take<Prop>(N);
 }
 
 static Batch<RefineArgs> batch_of(const RefineArgs *jobs, int n_w, int64_t *max_n, int64_t *max_s, int64_t *max_t) {
@@ -515,36 +493,11 @@ static int refine_host(same_ctx *ctx, const int32_t *pairs, const double *costs,
     REQUIRE(ctx, penalty_coeff >= 0.0 && penalty_coeff - penalty_coeff == 0.0);
     if (ref_limit)
         for (int64_t j = 0; j < n_r; ++j) REQUIRE(ctx, ref_limit[j] >= 1 && ref_limit[j] <= rfn::MAX_LIMIT);
-    // the pairs by row (stable: the caller's order inside a row), each (row, column) once; the start one-to-one
-    std::vector<int32_t> prow((size_t)n_m + 1, 0), order((size_t)P), where((size_t)P), csr((size_t)P * 2), start((size_t)n_m);
-    std::vector<double> ccsr((size_t)P);
-    for (int64_t p = 0; p < P; ++p) {
-        const int32_t i = pairs[2 * p], j = pairs[2 * p + 1];
-        REQUIRE(ctx, i >= 0 && i < n_m && j >= 0 && j < n_r);
-        ++prow[(size_t)i + 1];
-    }
-    for (int64_t i = 0; i < n_m; ++i) prow[(size_t)i + 1] += prow[(size_t)i];
-    {
-        std::vector<int32_t> at(prow.begin(), prow.end() - 1);
-        for (int64_t p = 0; p < P; ++p) {
-            const int32_t q = at[(size_t)pairs[2 * p]]++;
-            order[(size_t)q] = (int32_t)p;
-            where[(size_t)p] = q;
-        }
-    }
-    std::vector<int64_t> seen((size_t)n_r, -1);
-    for (int64_t i = 0; i < n_m; ++i)
-        for (int32_t q = prow[(size_t)i]; q < prow[(size_t)i + 1]; ++q) {
-            const int32_t p = order[(size_t)q], j = pairs[2 * (int64_t)p + 1];
-            if (seen[(size_t)j] == i) {
-                ctx->err = "invalid argument: a (row, column) pair given twice";
-                return SAME_EINVAL;
-            }
-            seen[(size_t)j] = i;
-            csr[2 * (size_t)q] = (int32_t)i;
-            csr[2 * (size_t)q + 1] = j;
-            ccsr[(size_t)q] = costs[p];
-        }
+    // the pairs by row (stable: the caller's order inside a row), each (row, column) once; the start within the limits
+    same_pair_csr by_row;
+    SAME_TRY(same_pairs_by_row(ctx, pairs, costs, P, n_m, n_r, &by_row));
+    const std::vector<int32_t> &order = by_row.order, &where = by_row.where;
+    std::vector<int32_t> start((size_t)n_m);
     std::vector<int32_t> held((size_t)n_r, 0);
     for (int64_t i = 0; i < n_m; ++i) {
         const int32_t p = match_pair_inout[i];
@@ -561,46 +514,48 @@ static int refine_host(same_ctx *ctx, const int32_t *pairs, const double *costs,
     }
     SAME_TRY(check_index_range(ctx, tris, Tr * 3, 0, n_m, "triangles"));
     SAME_TRY(same_use(ctx));
-    Carver cv;
-    const size_t o_prow = cv.take(((size_t)n_m + 1) * 4), o_pairs = cv.take((size_t)P * 8 + 8), o_cost = cv.take((size_t)P * 8 + 8),
-                 o_unm = cv.take((size_t)n_m * 8 + 8), o_size = cv.take((size_t)n_m * 8 + 8), o_axy = cv.take((size_t)n_m * 16 + 16),
-                 o_rxy = cv.take((size_t)n_r * 16 + 16), o_tris = cv.take((size_t)Tr * 12 + 12), o_start = cv.take((size_t)n_m * 4 + 4),
-                 o_ctrl = cv.take(rfn::RC_COUNT * 8), o_lim = cv.take((size_t)n_r * 4 + 4), o_work = cv.take(rfn::work_bytes(n_m, n_r, Tr));
-    char *d = nullptr;
-    SAME_TRY(slot_as(ctx, SL_OUT0, cv.off, &d));
     rfn::RefineArgs a{};
-    a.prow = reinterpret_cast<const int32_t *>(d + o_prow);
-    a.pairs = reinterpret_cast<const int32_t *>(d + o_pairs);
-    a.cost = reinterpret_cast<const double *>(d + o_cost);
-    a.unm = reinterpret_cast<const double *>(d + o_unm);
-    a.size = reinterpret_cast<const double *>(d + o_size);
     a.dp = delaunay_penalty;
-    a.axy = reinterpret_cast<const double *>(d + o_axy);
-    a.ref_xy = reinterpret_cast<const double *>(d + o_rxy);
-    a.tris = reinterpret_cast<const int32_t *>(d + o_tris);
     a.n = n_m;
     a.n_r = n_r;
     a.cap_tr = Tr;
     a.cap = rounds_cap;
-    a.start = reinterpret_cast<const int32_t *>(d + o_start);
-    a.ctrl = reinterpret_cast<unsigned long long *>(d + o_ctrl);
     a.pc = penalty_coeff;
-    a.limit_in = ref_limit ? reinterpret_cast<const int32_t *>(d + o_lim) : nullptr;
-    rfn::carve(&a, d + o_work);
-    SAME_COPY(ctx, d + o_prow, prow.data(), prow.size() * 4, hipMemcpyHostToDevice);
+    int32_t *d_prow, *d_pairs, *d_tris, *d_start, *d_lim;
+    double *d_cost, *d_unm, *d_size, *d_axy, *d_rxy;
+    auto lay = [&](Carver cv) {       // (one element more than each input: no array is empty)
+        a.prow = d_prow = cv.take<int32_t>((size_t)n_m + 1);
+        a.pairs = d_pairs = cv.take<int32_t>((size_t)P * 2 + 2);
+        a.cost = d_cost = cv.take<double>((size_t)P + 1);
+        a.unm = d_unm = cv.take<double>((size_t)n_m + 1);
+        a.size = d_size = cv.take<double>((size_t)n_m + 1);
+        a.axy = d_axy = cv.take<double>((size_t)n_m * 2 + 2);
+        a.ref_xy = d_rxy = cv.take<double>((size_t)n_r * 2 + 2);
+        a.tris = d_tris = cv.take<int32_t>((size_t)Tr * 3 + 3);
+        a.start = d_start = cv.take<int32_t>((size_t)n_m + 1);
+        a.ctrl = cv.take<unsigned long long>(rfn::RC_COUNT);
+        d_lim = cv.take<int32_t>((size_t)n_r + 1);
+        a.limit_in = ref_limit ? d_lim : nullptr;
+        rfn::lay(a, cv);
+        return cv.off;
+    };
+    char *d = nullptr;
+    SAME_TRY(slot_as(ctx, SL_OUT0, lay(Carver()), &d));
+    lay(Carver(d));
+    SAME_COPY(ctx, d_prow, by_row.prow.data(), by_row.prow.size() * 4, hipMemcpyHostToDevice);
     if (P) {
-        SAME_COPY(ctx, d + o_pairs, csr.data(), (size_t)P * 8, hipMemcpyHostToDevice);
-        SAME_COPY(ctx, d + o_cost, ccsr.data(), (size_t)P * 8, hipMemcpyHostToDevice);
+        SAME_COPY(ctx, d_pairs, by_row.csr.data(), (size_t)P * 8, hipMemcpyHostToDevice);
+        SAME_COPY(ctx, d_cost, by_row.ccsr.data(), (size_t)P * 8, hipMemcpyHostToDevice);
     }
     if (n_m) {
-        SAME_COPY(ctx, d + o_unm, unmatched, (size_t)n_m * 8, hipMemcpyHostToDevice);
-        SAME_COPY(ctx, d + o_size, size, (size_t)n_m * 8, hipMemcpyHostToDevice);
-        SAME_COPY(ctx, d + o_axy, axy, (size_t)n_m * 16, hipMemcpyHostToDevice);
-        SAME_COPY(ctx, d + o_start, start.data(), (size_t)n_m * 4, hipMemcpyHostToDevice);
+        SAME_COPY(ctx, d_unm, unmatched, (size_t)n_m * 8, hipMemcpyHostToDevice);
+        SAME_COPY(ctx, d_size, size, (size_t)n_m * 8, hipMemcpyHostToDevice);
+        SAME_COPY(ctx, d_axy, axy, (size_t)n_m * 16, hipMemcpyHostToDevice);
+        SAME_COPY(ctx, d_start, start.data(), (size_t)n_m * 4, hipMemcpyHostToDevice);
     }
-    if (n_r) SAME_COPY(ctx, d + o_rxy, ref_xy, (size_t)n_r * 16, hipMemcpyHostToDevice);
-    if (n_r && ref_limit) SAME_COPY(ctx, d + o_lim, ref_limit, (size_t)n_r * 4, hipMemcpyHostToDevice);
-    if (Tr) SAME_COPY(ctx, d + o_tris, tris, (size_t)Tr * 12, hipMemcpyHostToDevice);
+    if (n_r) SAME_COPY(ctx, d_rxy, ref_xy, (size_t)n_r * 16, hipMemcpyHostToDevice);
+    if (n_r && ref_limit) SAME_COPY(ctx, d_lim, ref_limit, (size_t)n_r * 4, hipMemcpyHostToDevice);
+    if (Tr) SAME_COPY(ctx, d_tris, tris, (size_t)Tr * 12, hipMemcpyHostToDevice);
     std::vector<int32_t> mp((size_t)n_m);
     unsigned long long ctrl[rfn::RC_COUNT] = {};
     if (n_m) {

@@ -304,40 +304,35 @@ int prepare_filter(same_window *w, const int32_t *d_simplices, int64_t Tr, int i
     const int64_t n = w->n_ua;
     const bool use_type = ignore_same_type && w->has_type;
     plan->readd = use_type && ensure_min_triangle_per_node;
-    Carver cv;   // zeroed head: scan words, counters, vertex marks, inverted minima
-    const size_t st_keep = scan::status_bytes(Tr), st_own = scan::status_bytes(n);
-    const size_t o_st_keep = cv.take(st_keep), o_st_own = cv.take(st_own), o_counters = cv.take(64), o_has_kept = cv.take((size_t)n),
-                 o_any_valid = cv.take((size_t)n), o_best_p = cv.take((size_t)n * 8), o_best_t = cv.take((size_t)n * 4),
-                 o_first_v = cv.take((size_t)Tr * 4);
-    const size_t zero_bytes = cv.off;
-    const size_t o_cls = cv.take((size_t)Tr), o_perim = cv.take((size_t)Tr * 8), o_klist = cv.take((size_t)Tr * 4), o_nlist = cv.take((size_t)n * 4);
-    SAME_TRY(ensure(ctx, w->filter, cv.off));
-    SAME_TRY(ensure(ctx, w->tris, (size_t)std::max<int64_t>(Tr, 1) * 12));
-    char *base = static_cast<char *>(w->filter.p);
-    auto at = [&](size_t off) { return base + off; };
-    unsigned long long *dc = reinterpret_cast<unsigned long long *>(at(o_counters));
-    plan->counters = dc;
     FilterArgs &a = plan->args;
     a.xy = w->axy_c;
     a.raw = d_simplices;
     a.Tr = Tr;
     a.n = n;
     a.type_id = use_type ? w->type_c : nullptr;
-    a.cls = reinterpret_cast<uint8_t *>(at(o_cls));
-    a.perim = reinterpret_cast<double *>(at(o_perim));
-    a.has_kept = reinterpret_cast<uint8_t *>(at(o_has_kept));
-    a.any_valid = reinterpret_cast<uint8_t *>(at(o_any_valid));
-    a.best_p = plan->readd ? reinterpret_cast<unsigned long long *>(at(o_best_p)) : nullptr;
-    a.best_t = reinterpret_cast<unsigned *>(at(o_best_t));
-    a.first_v = reinterpret_cast<unsigned *>(at(o_first_v));
-    a.st_keep = scan::arg(reinterpret_cast<unsigned long long *>(at(o_st_keep)));
-    a.st_own = scan::arg(reinterpret_cast<unsigned long long *>(at(o_st_own)));
-    a.counters = dc;
-    a.klist = reinterpret_cast<int32_t *>(at(o_klist));
-    a.nlist = reinterpret_cast<int32_t *>(at(o_nlist));
+    auto lay = [&](Carver cv) {
+        // zeroed head: scan words, counters, vertex marks, inverted minima
+        a.st_keep = scan::arg(cv.scan_words(Tr));
+        a.st_own = scan::arg(cv.scan_words(n));
+        a.counters = plan->counters = cv.take<unsigned long long>(8);
+        a.has_kept = cv.take<uint8_t>((size_t)n);
+        a.any_valid = cv.take<uint8_t>((size_t)n);
+        a.best_p = cv.take<unsigned long long>((size_t)n);
+        if (!plan->readd) a.best_p = nullptr;
+        a.best_t = cv.take<unsigned>((size_t)n);
+        a.first_v = cv.take<unsigned>((size_t)Tr);
+        plan->zero_bytes = cv.off;
+        a.cls = cv.take<uint8_t>((size_t)Tr);
+        a.perim = cv.take<double>((size_t)Tr);
+        a.klist = cv.take<int32_t>((size_t)Tr);
+        a.nlist = cv.take<int32_t>((size_t)n);
+        return cv.off;
+    };
+    SAME_TRY(ensure(ctx, w->filter, lay(Carver())));
+    SAME_TRY(ensure(ctx, w->tris, (size_t)std::max<int64_t>(Tr, 1) * 12));
+    lay(Carver(w->filter.p));
     a.out = static_cast<int32_t *>(w->tris.p);
-    plan->zero = base;
-    plan->zero_bytes = zero_bytes;
+    plan->zero = w->filter.p;
     return SAME_OK;
 }
 
@@ -392,19 +387,17 @@ FinishMode mode_of(int incumbent, double no_match_penalty, int64_t refine_rounds
 // words of a window's out_stats record after the eight counters: the assignment's flags and objective, the search's record
 enum { WS_AS_FLAGS = 8, WS_AS_OBJ = 9, WS_REFINE = 10 };
 
-struct FinishPlan {
+// (FinishBack: the head's zeroed length, the block that comes back and its parts -- window_internal.h)
+struct FinishPlan : FinishBack {
     FinishMode mode;
-    unsigned long long *zero = nullptr;       // head of the finish buffer: [sel | counters | point flags (padded) | matched rows]
+    unsigned long long *zero = nullptr;       // head of the finish buffer: [used | keys | sel | counters | point flags (padded)], then the matched rows
     void *filter_zero = nullptr;              // head of the window's filter buffer when this call filters it (zeroed in the same launch)
     size_t filter_zero_bytes = 0;
-    size_t zero_bytes = 0, back_off = 0, back_bytes = 0, o_counters = 0, o_pflag = 0, o_match_row = 0;
     same_greedy_state gs;
-    int32_t *match_pair = nullptr, *match_row = nullptr;
-    uint8_t *pflag = nullptr;
-    unsigned long long *counters = nullptr;
+    int32_t *match_pair = nullptr;
     int64_t cap_tr = 0;
     const unsigned long long *dTr = nullptr;
-    char *assign_work = nullptr;              // the optimal assignment's work arrays (SAME_INCUMBENT_ASSIGNMENT), else null
+    asg::AssignArgs aargs{};                  // the optimal assignment's work arrays (SAME_INCUMBENT_ASSIGNMENT), else unset
     bool refine = false;                      // the local search runs on the incumbent (mode.refine_cap > 0) ...
     rfn::RefineArgs rargs{};                  // ... over these arrays; its control words are counters + SC_REFINE
 };
@@ -437,60 +430,44 @@ int prepare_finish(same_window *w, const int32_t *host_tris, int64_t cap_tr, con
                    FinishPlan *p) {
     same_ctx *ctx = w->ctx;
     const int64_t n = w->n_ua, P = w->P, n_ends = n + w->n_r;
-    Carver cv;
-    const size_t o_used = cv.take((size_t)n_ends), o_key = cv.take((size_t)n_ends * 16), o_idx = cv.take((size_t)n_ends * 8);
-    const size_t o_sel = cv.take(SAME_GREEDY_BATCH_MAX * 8);
-    const size_t o_counters = cv.off;
-    cv.off += SC_COUNT * 8;
-    const size_t o_pflag = cv.off;
-    cv.off += ((size_t)n + 7) & ~size_t(7);
-    const size_t zero_bytes = (cv.off + 15) & ~size_t(15);
-    cv.off = zero_bytes;
-    const size_t o_match_row = cv.off;
-    cv.off += (size_t)n * 4;
-    const size_t back_end = cv.off;
-    cv.off = (cv.off + 255) & ~size_t(255);
     const size_t tt = (size_t)std::max<int64_t>(cap_tr, 1);
-    const size_t o_alive = cv.take((size_t)std::max<int64_t>(P, 1)), o_match_pair = cv.take((size_t)n * 4), o_match_loc = cv.take((size_t)n * 4),
-                 o_sign = cv.take(tt), o_weight = cv.take(tt * 8);
-    const size_t o_assign = mode.incumbent == SAME_INCUMBENT_ASSIGNMENT ? cv.take(asg::work_bytes(n, w->n_r)) : 0;
-    const size_t o_refine = mode.refine_cap > 0 ? cv.take(rfn::work_bytes(n, w->n_r, cap_tr)) : 0;
-    SAME_TRY(ensure(ctx, w->finish, cv.off));
-    SAME_TRY(ensure(ctx, w->tris, tt * 12));
-    char *base = static_cast<char *>(w->finish.p);
-    auto at = [&](size_t off) { return base + off; };
     p->mode = mode;
-    p->zero = reinterpret_cast<unsigned long long *>(base);
-    p->zero_bytes = zero_bytes;
-    p->back_off = o_sel;
-    p->back_bytes = back_end - o_sel;
-    p->o_counters = o_counters - o_sel;
-    p->o_pflag = o_pflag - o_sel;
-    p->o_match_row = o_match_row - o_sel;
-    p->gs.alive = reinterpret_cast<uint8_t *>(at(o_alive));
-    p->gs.used = reinterpret_cast<uint8_t *>(at(o_used));
-    p->gs.key[0] = reinterpret_cast<unsigned long long *>(at(o_key));
-    p->gs.key[1] = p->gs.key[0] + n_ends;
-    p->gs.idx[0] = reinterpret_cast<unsigned *>(at(o_idx));
-    p->gs.idx[1] = p->gs.idx[0] + n_ends;
-    p->gs.sel = reinterpret_cast<unsigned long long *>(at(o_sel));
-    p->gs.float_costs = w->cost_f32 != 0;          // cost64 = (double)float there: the two-launch rounds
-    p->counters = reinterpret_cast<unsigned long long *>(at(o_counters));
-    p->pflag = reinterpret_cast<uint8_t *>(at(o_pflag));
-    p->match_row = reinterpret_cast<int32_t *>(at(o_match_row));
-    p->match_pair = reinterpret_cast<int32_t *>(at(o_match_pair));
-    w->match_loc = reinterpret_cast<int32_t *>(at(o_match_loc));
-    w->match_row = p->match_row;
-    w->pflag = p->pflag;
-    w->sign = reinterpret_cast<int8_t *>(at(o_sign));
-    w->weight = reinterpret_cast<double *>(at(o_weight));
-    p->assign_work = o_assign ? at(o_assign) : nullptr;
     p->cap_tr = cap_tr;
     p->dTr = dTr;
-    p->refine = o_refine != 0;
+    p->gs.float_costs = w->cost_f32 != 0;          // cost64 = (double)float there: the two-launch rounds
+    p->aargs = asg::AssignArgs{};
+    p->aargs.n = n;
+    p->aargs.n_r = w->n_r;
+    p->refine = mode.refine_cap > 0;
+    rfn::RefineArgs &r = p->rargs;
+    r = rfn::RefineArgs{};
+    r.n = n;
+    r.n_r = w->n_r;
+    r.cap_tr = cap_tr;
+    auto lay = [&](Carver cv) {
+        p->gs.used = cv.take<uint8_t>((size_t)n_ends);
+        p->gs.key[0] = cv.take<unsigned long long>((size_t)n_ends * 2);
+        p->gs.idx[0] = cv.take<unsigned>((size_t)n_ends * 2);
+        win::lay(*p, cv, n);            // sel, counters, point flags, matched rows: contiguous, they come back in one copy
+        p->gs.sel = p->sel;
+        p->gs.alive = cv.take<uint8_t>((size_t)std::max<int64_t>(P, 1));
+        p->match_pair = cv.take<int32_t>((size_t)n);
+        w->match_loc = cv.take<int32_t>((size_t)n);
+        w->sign = cv.take<int8_t>(tt);
+        w->weight = cv.take<double>(tt);
+        if (mode.incumbent == SAME_INCUMBENT_ASSIGNMENT) asg::lay(p->aargs, cv);
+        if (p->refine) rfn::lay(r, cv);
+        return cv.off;
+    };
+    SAME_TRY(ensure(ctx, w->finish, lay(Carver())));
+    SAME_TRY(ensure(ctx, w->tris, tt * 12));
+    lay(Carver(w->finish.p));
+    p->zero = static_cast<unsigned long long *>(w->finish.p);
+    p->gs.key[1] = p->gs.key[0] + n_ends;
+    p->gs.idx[1] = p->gs.idx[0] + n_ends;
+    w->match_row = p->match_row;
+    w->pflag = p->pflag;
     if (p->refine) {
-        rfn::RefineArgs &r = p->rargs;
-        r = rfn::RefineArgs{};
         r.prow = w->prow;
         r.pairs = w->pairs;
         r.cost = w->cost64;
@@ -501,9 +478,6 @@ int prepare_finish(same_window *w, const int32_t *host_tris, int64_t cap_tr, con
         r.ref_row = w->jsec;
         r.tris = static_cast<const int32_t *>(w->tris.p);
         r.dTr = dTr;
-        r.n = n;
-        r.n_r = w->n_r;
-        r.cap_tr = cap_tr;
         r.cap = mode.refine_cap;
         r.penalty = mode.no_match_penalty;
         if (mode.capacity) {            // the limits from the reference section's sizes (refine_limit_kernel), pricing the extra matches
@@ -516,7 +490,6 @@ int prepare_finish(same_window *w, const int32_t *host_tris, int64_t cap_tr, con
         }
         r.start = p->match_pair;
         r.ctrl = p->counters + SC_REFINE;
-        rfn::carve(&r, at(o_refine));
     }
     REQUIRE(ctx, w->host_finish_off + p->back_bytes <= w->host_filter_off);   // sized by the stage call
     if (host_tris && cap_tr) SAME_COPY(ctx, w->tris.p, host_tris, (size_t)cap_tr * 12, hipMemcpyHostToDevice);
@@ -546,19 +519,16 @@ int launch_finish(same_ctx *ctx, same_window *const *ws, FinishPlan *const *ps, 
             same_window *w = ws[q];
             FinishPlan *p = ps[q];
             asg::AssignArgs &a = jobs[q];
-            a = asg::AssignArgs{};
+            a = p->aargs;                     // n, n_r and the work arrays (prepare_finish)
             a.prow = w->prow;
             a.pairs = w->pairs;
             a.cost = w->cost64;
             a.size = w->size_c;
             a.penalty = no_match_penalty;
-            a.n = w->n_ua;
-            a.n_r = w->n_r;
             a.max_pops = asg::default_max_pops(w->n_ua, w->n_r, w->P);
             a.alive = p->gs.alive;
             a.match_pair = p->match_pair;
             a.res = p->gs.sel;
-            asg::carve(&a, p->assign_work);
         }
         SAME_TRY(asg::launch(ctx, jobs, n_w));
         SAME_TRY(enqueue_refine(ctx, ps, n_w));

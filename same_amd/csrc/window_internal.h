@@ -81,14 +81,28 @@ inline void release(DevBuf &b) {
     b.bytes = 0;
 }
 
-// carve a buffer: offsets are multiples of 256 bytes
+// A buffer's layout is ONE sequence of typed takes, run twice: without a base it measures (every take answers null, `off` ends at the
+// size to ensure), on the allocation it places the pointers -- so a size and its pointers cannot disagree.  take: the array starts on a
+// 256-byte boundary and the buffer is padded to the next one; pack: the array starts on `align` bytes and nothing is padded behind it (runs
+// that are zeroed or copied back in one piece).  `off`, and what align() answers, are offsets where an offset itself is data.
 struct Carver {
+    char *base = nullptr;
     size_t off = 0;
-    size_t take(size_t bytes) {
-        const size_t at = off;
-        off += (bytes + 255) & ~size_t(255);
-        return at;
+    explicit Carver(void *b = nullptr) : base(static_cast<char *>(b)) {}
+    size_t align(size_t a) { return off = (off + a - 1) & ~(a - 1); }
+    template <class T>
+    T *pack(size_t count, size_t a = alignof(T)) {
+        const size_t at = align(a);
+        off = at + count * sizeof(T);
+        return base ? reinterpret_cast<T *>(base + at) : nullptr;
     }
+    template <class T>
+    T *take(size_t count) {
+        T *p = pack<T>(count, 256);
+        align(256);
+        return p;
+    }
+    unsigned long long *scan_words(int64_t n) { return take<unsigned long long>(scan::status_bytes(n) / 8); }   // status_bytes: 16-byte units
 };
 
 inline unsigned grid_for(int64_t n) { return (unsigned)ceil_div(n > 0 ? n : 1, 256); }
@@ -136,6 +150,34 @@ enum { FC_KEEP = 0, FC_ADD = 1, FC_NEAR = 2, FC_TR = 3, FC_TIES = 4, FC_COPIED =
 // SC_REFINE on the local search's control words (refine.h RC_*), which a second pass of the tail leaves as they are
 enum { SC_CHECKED = 0, SC_FLIPPED = 1, SC_CMP = 2, SC_VIOL = 3, SC_TVIOL = 4, SC_AFLIP = 5, SC_ROUNDS = 6, SC_MATCHED = 7, SC_REMAINING = 8, SC_TIES = 9,
        SC_REFINE = 16, SC_COUNT = 32 };
+
+// What the finish call copies back in one piece, [sel | counters | point flags | matched rows], and zeroes up to the matched rows:
+// laid out here because the stage call sizes the pinned block's share for it (finish_back_bytes) before the finish call places it
+struct FinishBack {
+    unsigned long long *sel = nullptr, *counters = nullptr;   // [SAME_GREEDY_BATCH_MAX] greedy rounds, [SC_COUNT]
+    uint8_t *pflag = nullptr;                                 // [n] padded to whole 16 bytes (its writers OR into 32-bit words)
+    int32_t *match_row = nullptr;                             // [n]
+    size_t back_off = 0, zero_bytes = 0, back_bytes = 0;      // the region's start, the end of the zeroed head; the region's size
+    size_t o_counters = 0, o_pflag = 0, o_match_row = 0;      // from the region's start: where the host finds them in its copy
+};
+inline void lay(FinishBack &b, Carver &cv, int64_t n) {
+    b.back_off = cv.align(256);
+    b.sel = cv.take<unsigned long long>(SAME_GREEDY_BATCH_MAX);
+    b.o_counters = cv.off - b.back_off;
+    b.counters = cv.pack<unsigned long long>(SC_COUNT);
+    b.o_pflag = cv.off - b.back_off;
+    b.pflag = cv.pack<uint8_t>((size_t)n);
+    b.zero_bytes = cv.align(16);
+    b.o_match_row = cv.off - b.back_off;
+    b.match_row = cv.pack<int32_t>((size_t)n);
+    b.back_bytes = cv.off - b.back_off;
+}
+inline size_t finish_back_bytes(int64_t n) {
+    FinishBack b;
+    Carver cv;
+    lay(b, cv, n);
+    return b.back_bytes;
+}
 
 }  // namespace win
 

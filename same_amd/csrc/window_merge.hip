@@ -532,22 +532,27 @@ int same_merge_acc_resolve(same_merge_acc *const *accs, int n_accs, const same_s
     const int32_t *codes_a = loaded ? nullptr : mov->id_codes, *codes_r = loaded ? nullptr : ref->id_codes;
     // layout of the work buffer: [scan words of the rest list | counters] zeroed; codes, survivors, classes, degree tables, the result table
     const int64_t nn = std::max<int64_t>(n, 1);
-    Carver cv;
-    const size_t o_status = cv.take(scan::status_bytes(nn)), o_counters = cv.take(64), o_deg_a = cv.take((size_t)n_codes_a * 4),
-                 o_deg_r = cv.take((size_t)n_codes_r * 4);
-    const size_t zero_bytes = cv.off;
-    const size_t o_row_of = cv.take((size_t)n_codes_a * 4), o_ac = cv.take((size_t)nn * 4), o_rc = cv.take((size_t)nn * 4),
-                 o_kept = cv.take((size_t)nn * 4), o_cls = cv.take((size_t)nn);
-    SAME_TRY(ensure(ctx, a->work, cv.off));
-    char *base = static_cast<char *>(a->work.p);
-    unsigned long long *status = reinterpret_cast<unsigned long long *>(base + o_status), *counters = reinterpret_cast<unsigned long long *>(base + o_counters);
-    unsigned *deg_a = reinterpret_cast<unsigned *>(base + o_deg_a), *deg_r = reinterpret_cast<unsigned *>(base + o_deg_r);
-    a->row_of = reinterpret_cast<int32_t *>(base + o_row_of);
-    a->ac = reinterpret_cast<int32_t *>(base + o_ac);
-    a->rc = reinterpret_cast<int32_t *>(base + o_rc);
-    int32_t *kept = reinterpret_cast<int32_t *>(base + o_kept);
-    uint8_t *cls = reinterpret_cast<uint8_t *>(base + o_cls);
-    SAME_FILL(ctx, base, 0, zero_bytes);
+    unsigned long long *status, *counters;
+    unsigned *deg_a, *deg_r;
+    int32_t *kept;
+    uint8_t *cls;
+    size_t zero_bytes = 0;
+    auto lay = [&](Carver cv) {
+        status = cv.scan_words(nn);
+        counters = cv.take<unsigned long long>(8);
+        deg_a = cv.take<unsigned>((size_t)n_codes_a);
+        deg_r = cv.take<unsigned>((size_t)n_codes_r);
+        zero_bytes = cv.off;
+        a->row_of = cv.take<int32_t>((size_t)n_codes_a);
+        a->ac = cv.take<int32_t>((size_t)nn);
+        a->rc = cv.take<int32_t>((size_t)nn);
+        kept = cv.take<int32_t>((size_t)nn);
+        cls = cv.take<uint8_t>((size_t)nn);
+        return cv.off;
+    };
+    SAME_TRY(ensure(ctx, a->work, lay(Carver())));
+    lay(Carver(a->work.p));
+    SAME_FILL(ctx, a->work.p, 0, zero_bytes);
     SAME_FILL(ctx, a->row_of, 0xFF, (size_t)n_codes_a * 4);
     a->counters = counters;
     SAME_TRY(ensure(ctx, a->out, (size_t)nn * sizeof(RestRec)));          // the rest list: at most n records

@@ -319,16 +319,19 @@ int subset_rows_full(same_window *w, const same_section *sec, const double *box,
     *out_n = 0;
     if (sec->n == 0) return SAME_OK;
     const int64_t n_words = (int64_t)grid_for(sec->n) * 4;
-    Carver cv;
-    const size_t o_status = cv.take(scan::status_bytes(n_words)), o_count = cv.take(16);
-    const size_t zero_bytes = cv.off;
-    const size_t o_mask = cv.take((size_t)n_words * 8);
-    SAME_TRY(ensure(ctx, w->big_mask, cv.off));
-    char *base = static_cast<char *>(w->big_mask.p);
-    unsigned long long *status = reinterpret_cast<unsigned long long *>(base + o_status), *dcount = reinterpret_cast<unsigned long long *>(base + o_count),
-                       *mask = reinterpret_cast<unsigned long long *>(base + o_mask);
+    unsigned long long *status, *dcount, *mask;
+    size_t zero_bytes = 0;
+    auto lay = [&](Carver cv) {
+        status = cv.scan_words(n_words);
+        dcount = cv.take<unsigned long long>(2);
+        zero_bytes = cv.off;
+        mask = cv.take<unsigned long long>((size_t)n_words);
+        return cv.off;
+    };
+    SAME_TRY(ensure(ctx, w->big_mask, lay(Carver())));
+    lay(Carver(w->big_mask.p));
     SAME_TRY(ensure(ctx, dst, (size_t)sec->n * sizeof(int32_t)));
-    SAME_FILL(ctx, base, 0, zero_bytes);
+    SAME_FILL(ctx, w->big_mask.p, 0, zero_bytes);
     SAME_LAUNCH(ctx, box_mask_kernel, dim3(grid_for(sec->n)), dim3(256), 0, sec->xy, sec->n, box[0], box[1], box[2], box[3], mask);
     SAME_LAUNCH(ctx, mask_compact_kernel, dim3(scan::blocks_for(n_words)), dim3(scan::NT), 0, mask, n_words, scan::arg(status),
                 static_cast<int32_t *>(dst.p), dcount);
@@ -451,49 +454,48 @@ int prepare_stage(same_window *w, const same_section *mov, const same_section *r
     const size_t slots = (size_t)cap_m * k, cm1 = (size_t)cap_m + 1;
     const bool compact_m = cm.use_runs && !cm.aligned && cap_m > 0, compact_r = cr.use_runs && !cr.aligned && cap_r > 0;
     // layout: [scan words | counts | kept XY | kept rows] (zeroed up to the counts; copied back from the counts on) | the rest
-    Carver cv;
-    const size_t st_scatter = scan::status_bytes(cap_m), st_cm = scan::status_bytes(cap_m), st_cr = scan::status_bytes(cap_r);
-    const size_t o_st_scatter = cv.take(st_scatter), o_st_cm = cv.take(st_cm), o_st_cr = cv.take(st_cr);
-    const size_t o_counts = cv.off;
-    cv.off += 64;
-    const size_t o_axy_c = cv.off;
-    cv.off += (size_t)cap_m * 2 * sizeof(double);
-    const size_t o_rows_ua = cv.off;
-    cv.off += (size_t)cap_m * sizeof(int32_t);
-    const size_t back_bytes = cv.off - o_counts;
-    cv.off = (cv.off + 255) & ~size_t(255);
-    const size_t o_merged_m = cv.take((size_t)cap_m * 4), o_merged_r = cv.take((size_t)cap_r * 4);
-    const size_t o_rows_m = cv.take((size_t)cap_m * 4), o_rows_r = cv.take((size_t)cap_r * 4);
-    const size_t o_idx = cv.take(slots * 4), o_cnt = cv.take((size_t)cap_m * 4), o_cost = cv.take(slots * cs);
-    const size_t o_ua = cv.take((size_t)cap_m * 4), o_type_c = cv.take((size_t)cap_m * 4), o_size_c = cv.take((size_t)cap_m * 8);
-    const size_t o_prow = cv.take(cm1 * 4), o_pairs = cv.take(slots * 8), o_jsec = cv.take(slots * 4), o_cost64 = cv.take(slots * 8);
-    SAME_TRY(ensure(ctx, w->stage, cv.off));
+    uint32_t *merged_m, *merged_r;
+    int32_t *rows_m, *rows_r;
+    unsigned long long *st_scatter, *st_cm, *st_cr;
+    void *cost;
+    size_t o_counts = 0, back_bytes = 0;
+    auto lay = [&](Carver cv) {
+        st_scatter = scan::arg(cv.scan_words(cap_m));
+        st_cm = scan::arg(cv.scan_words(cap_m));
+        st_cr = scan::arg(cv.scan_words(cap_r));
+        o_counts = cv.off;                  // counts, kept XY, kept rows: contiguous, they come back in one copy
+        w->counts = cv.pack<unsigned long long>(8);
+        w->axy_c = cv.pack<double>((size_t)cap_m * 2);
+        w->rows_ua = cv.pack<int32_t>((size_t)cap_m);
+        back_bytes = cv.off - o_counts;
+        merged_m = cv.take<uint32_t>((size_t)cap_m);
+        merged_r = cv.take<uint32_t>((size_t)cap_r);
+        rows_m = cv.take<int32_t>((size_t)cap_m);
+        rows_r = cv.take<int32_t>((size_t)cap_r);
+        w->idx = cv.take<int32_t>(slots);
+        w->cnt = cv.take<int32_t>((size_t)cap_m);
+        cost = cv.take<char>(slots * cs);
+        w->ua = cv.take<int32_t>((size_t)cap_m);
+        w->type_c = cv.take<int32_t>((size_t)cap_m);
+        w->size_c = cv.take<double>((size_t)cap_m);
+        w->prow = cv.take<int32_t>(cm1);
+        w->pairs = cv.take<int32_t>(slots * 2);
+        w->jsec = cv.take<int32_t>(slots);
+        w->cost64 = cv.take<double>(slots);
+        return cv.off;
+    };
+    SAME_TRY(ensure(ctx, w->stage, lay(Carver())));
     // everything the three calls of this window copy back fits the pinned block from now on (it must not move between them)
     w->host_finish_off = (back_bytes + 255) & ~size_t(255);
-    w->host_filter_off = w->host_finish_off + ((SAME_GREEDY_BATCH_MAX * 8 + SC_COUNT * 8 + (size_t)cap_m * 5 + 64 + 255) & ~size_t(255));
+    w->host_filter_off = w->host_finish_off + ((finish_back_bytes(cap_m) + 255) & ~size_t(255));     // (n_ua <= cap_m)
     SAME_TRY(ensure_host(w, w->host_filter_off + 256));
-    char *base = static_cast<char *>(w->stage.p);
-    auto at = [&](size_t off) { return base + off; };
-    w->counts = reinterpret_cast<unsigned long long *>(at(o_counts));
-    w->axy_c = reinterpret_cast<double *>(at(o_axy_c));
-    w->rows_ua = reinterpret_cast<int32_t *>(at(o_rows_ua));
-    uint32_t *merged_m = reinterpret_cast<uint32_t *>(at(o_merged_m)), *merged_r = reinterpret_cast<uint32_t *>(at(o_merged_r));
+    lay(Carver(w->stage.p));
     // aligned boxes: the merged list IS the row list; whole-section path: its own list is copied in
-    w->rows_m = reinterpret_cast<int32_t *>(compact_m || !cm.use_runs ? at(o_rows_m) : at(o_merged_m));
-    w->rows_r = reinterpret_cast<int32_t *>(compact_r || !cr.use_runs ? at(o_rows_r) : at(o_merged_r));
-    w->idx = reinterpret_cast<int32_t *>(at(o_idx));
-    w->cnt = reinterpret_cast<int32_t *>(at(o_cnt));
-    void *cost = at(o_cost);
-    w->ua = reinterpret_cast<int32_t *>(at(o_ua));
-    w->type_c = reinterpret_cast<int32_t *>(at(o_type_c));
-    w->size_c = reinterpret_cast<double *>(at(o_size_c));
-    w->prow = reinterpret_cast<int32_t *>(at(o_prow));
-    w->pairs = reinterpret_cast<int32_t *>(at(o_pairs));
-    w->jsec = reinterpret_cast<int32_t *>(at(o_jsec));
-    w->cost64 = reinterpret_cast<double *>(at(o_cost64));
+    w->rows_m = compact_m || !cm.use_runs ? rows_m : reinterpret_cast<int32_t *>(merged_m);
+    w->rows_r = compact_r || !cr.use_runs ? rows_r : reinterpret_cast<int32_t *>(merged_r);
     unsigned long long *dc = w->counts;
 
-    sp->zero = ZeroArgs{{base, nullptr}, {o_counts + 64, 0}};       // scan words + counts, zeroed with the group's (launch_stage)
+    sp->zero = ZeroArgs{{w->stage.p, nullptr}, {o_counts + 64, 0}};       // scan words + counts, zeroed with the group's (launch_stage)
     sp->full_m = !cm.use_runs ? cap_m : 0;        // the whole-section path's list and count take their places after that
     sp->full_r = !cr.use_runs ? cap_r : 0;
     RowsArgs &ra = sp->rows;
@@ -513,8 +515,8 @@ int prepare_stage(same_window *w, const same_section *mov, const same_section *r
     CompactArgs &ca = sp->compact;
     ca = CompactArgs{};
     if (compact_m || compact_r) {
-        ca.cm = RowsCompact{merged_m, compact_m ? (int)cap_m : 0, w->rows_m, scan::arg(reinterpret_cast<unsigned long long *>(at(o_st_cm))), dc};
-        ca.cr = RowsCompact{merged_r, compact_r ? (int)cap_r : 0, w->rows_r, scan::arg(reinterpret_cast<unsigned long long *>(at(o_st_cr))), dc + 1};
+        ca.cm = RowsCompact{merged_m, compact_m ? (int)cap_m : 0, w->rows_m, st_cm, dc};
+        ca.cr = RowsCompact{merged_r, compact_r ? (int)cap_r : 0, w->rows_r, st_cr, dc + 1};
         ca.blocks_m = compact_m ? scan::blocks_for(cap_m) : 0;
         ca.blocks = ca.blocks_m + (compact_r ? scan::blocks_for(cap_r) : 0);
     }
@@ -527,7 +529,7 @@ int prepare_stage(same_window *w, const same_section *mov, const same_section *r
         sp->knn.idx = w->idx; sp->knn.cnt = w->cnt;
         sp->cost.rows = w->rows_m; sp->cost.dn = dc; sp->cost.cap = cap_m; sp->cost.idx = w->idx; sp->cost.out = cost;
         sp->scatter = ScatterArgs{w->idx, cost, w->cnt, w->rows_m, w->rows_r, mov->xy, mov->size, mov->type_id,
-                                  scan::arg(reinterpret_cast<unsigned long long *>(at(o_st_scatter))), dc, w->ua, w->rows_ua, w->type_c, w->prow, w->pairs,
+                                  st_scatter, dc, w->ua, w->rows_ua, w->type_c, w->prow, w->pairs,
                                   w->jsec, w->axy_c, w->size_c, w->cost64, k, scan::blocks_for(cap_m)};
     } else {
         sp->knn.dn_m = dc; sp->knn.dn_r = dc + 1;     // a window without candidates still names its (zero) counts: its blocks read them and leave

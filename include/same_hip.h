@@ -482,6 +482,13 @@ typedef struct same_window_capacity {
     double penalty_coeff;
 } same_window_capacity;
 #define SAME_WINDOW_STATS_CAP 16
+/* SAME_INCUMBENT_TRANSPORT (same_window_filter_finish_cap only; `capacity` must not be NULL, with or without a search): the incumbent is
+ * the optimum of the model without its triangle term WITHIN those capacities (same_sparse_assign_cap below) -- the limits are worked
+ * out on the device before the start, by the kernel the search uses.  out_stats then holds SAME_WINDOW_STATS_TRANSPORT words per window:
+ * the 16 above (greedy rounds = the start's searches, the assignment's flags and objective = the transport's), then sum_j max(0,
+ * count_j - 1) of the START.  A flagged window's matching is replaced through same_window_refinish_cap like an assignment's. */
+#define SAME_INCUMBENT_TRANSPORT 2
+#define SAME_WINDOW_STATS_TRANSPORT 17
 int same_window_filter_finish_cap(same_window *const *windows, int n_windows, int source, const int32_t *simplices,
                                   const int64_t *simplex_offsets, double radius, int angle_enabled, double cos_thr, double near_tol,
                                   int ignore_same_type, int ensure_min_triangle_per_node, double no_match_penalty, int incumbent,
@@ -549,6 +556,18 @@ int same_delaunay_filtered(same_ctx *ctx, const double *xy, int64_t n, double ra
  *   On the window path: same_window_filter_finish with SAME_INCUMBENT_ASSIGNMENT; same_window_refinish replaces a flagged window's. */
 int same_sparse_assign(same_ctx *ctx, const int32_t *pairs, const double *costs, int64_t P, const double *unmatched, int64_t n_m,
                        int64_t n_r, int32_t *out_match_pair, int64_t *out_stats);
+/*   same_sparse_assign_cap: the TRANSPORT form -- the model without its triangle term (src/same.py:1191-1196 with delaunay_penalty 0):
+ *     every row takes one of its pairs or its no-match column, reference j at most ref_limit[j] (1 .. 1001) rows, each after its first
+ *     priced penalty_coeff (finite, >= 0): minimum of pair costs + no-match costs + penalty_coeff sum_j max(0, count_j - 1).  The
+ *     surcharge is convex, so reference j splits exactly into a slot column (capacity 1, cost c_ij) and a shared column behind the
+ *     no-match columns (capacity ref_limit[j] - 1, cost c_ij + penalty_coeff); the same searches, a column a sink while it has room, a
+ *     full column relaxing each of its holders; the certificate also checks the holder lists, count <= capacity, v = 0 on columns with
+ *     room and both tiers' reduced costs.  Its value is a lower bound on the full lazy model's optimum.  out_stats[5] = the four words
+ *     above, then sum_j max(0, count_j - 1).  With every limit 1: same_sparse_assign's match, searches and objective bit for bit.  Bad
+ *     limits or penalty_coeff: SAME_EINVAL before any device work.
+ *   On the window path: same_window_filter_finish_cap with SAME_INCUMBENT_TRANSPORT. */
+int same_sparse_assign_cap(same_ctx *ctx, const int32_t *pairs, const double *costs, int64_t P, const double *unmatched, int64_t n_m,
+                           int64_t n_r, const int32_t *ref_limit, double penalty_coeff, int32_t *out_match_pair, int64_t *out_stats);
 
 /* ---- the local search on the lazy model's objective (csrc/refine.hip): from a window's one-to-one incumbent, moves that lower
  *   sum_p c_p x_p + no_match_penalty sum_i size_i n_i + delaunay_penalty sum_t w_t q_t        (src/same.py:1191-1196; p_j = 0;

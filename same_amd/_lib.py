@@ -115,6 +115,7 @@ _PROTOTYPES = {
     "same_delaunay2d": [c_vp, c_i64, c_vp, c_i64, ctypes.POINTER(c_i64), c_dbl, ctypes.POINTER(c_dbl)],
     "same_window_delaunay": [c_vp, c_int, c_dbl, c_int, c_dbl, c_dbl, c_vp, c_vp],
     "same_sparse_assign": [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp],
+    "same_sparse_assign_cap": [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_dbl, c_vp, c_vp],
     "same_refine_matching": [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_dbl, c_i64, c_vp, c_vp],
     "same_refine_matching_cap": [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_dbl, c_vp, c_dbl, c_i64,
                                  c_vp, c_vp],
@@ -153,9 +154,10 @@ SAME_EINVAL, SAME_ENOMEM, SAME_EIO, SAME_ENODEV, SAME_ERANGE, SAME_EUNSURE = -22
 SAME_DD_FEW_POINTS, SAME_DD_NO_ANGLE, SAME_DD_NONFINITE, SAME_DD_IN_DOUBT, SAME_DD_OVERFLOW = 1, 2, 4, 8, 16
 # what same_window_filter_finish reads its triangles from, what it matches by, the int64 words of its stats record per window
 SAME_TRIS_SIMPLICES, SAME_TRIS_KEPT, SAME_TRIS_DEVICE = 0, 1, 2
-SAME_INCUMBENT_GREEDY, SAME_INCUMBENT_ASSIGNMENT = 0, 1
+SAME_INCUMBENT_GREEDY, SAME_INCUMBENT_ASSIGNMENT, SAME_INCUMBENT_TRANSPORT = 0, 1, 2
 SAME_WINDOW_STATS = 15
 SAME_WINDOW_STATS_CAP = 16       # the _cap calls: the 15 words, then sum_j max(0, count_j - 1) of the search's result
+SAME_WINDOW_STATS_TRANSPORT = 17  # SAME_INCUMBENT_TRANSPORT: the 16 words, then sum_j max(0, count_j - 1) of the start
 
 
 class WindowCapacity(ctypes.Structure):

@@ -67,6 +67,9 @@ void lay(RefineArgs &a, win::Carver &cv);
 // objective at the start; rounds: `rounds` more rounds (each returns at once once its window settled or reached its cap), then the
 // objective now
 int launch_setup(same_ctx *ctx, const RefineArgs *jobs, int n_w);
+// the window path's limits alone (rsize, ref_row, ref_rows, P, n_r, max_matches, multiplier -> limit[n_r]; nothing else of a job is
+// read): for the transport start, which runs before the search's setup (assign.hip)
+int launch_limits(same_ctx *ctx, const RefineArgs *jobs, int n_w);
 int launch_rounds(same_ctx *ctx, const RefineArgs *jobs, int n_w, int rounds);
 
 }  // namespace rfn

@@ -443,6 +443,15 @@ static Batch<RefineArgs> batch_of(const RefineArgs *jobs, int n_w, int64_t *max_
     return bt;
 }
 
+int launch_limits(same_ctx *ctx, const RefineArgs *jobs, int n_w) {
+    if (n_w <= 0) return SAME_OK;
+    Batch<RefineArgs> bt{};
+    for (int q = 0; q < n_w; ++q) bt.w[q] = jobs[q];
+    SAME_LAUNCH(ctx, refine_limit_kernel, dim3(1, (unsigned)n_w), dim3(LIM_NT), 0, bt);
+    HIP_TRY(ctx, hipGetLastError());
+    return SAME_OK;
+}
+
 int launch_setup(same_ctx *ctx, const RefineArgs *jobs, int n_w) {
     if (n_w <= 0) return SAME_OK;
     int64_t max_n, max_s, max_t;

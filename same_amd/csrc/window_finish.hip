@@ -366,11 +366,13 @@ struct FinishMode {
     int64_t refine_cap = 0;                   // local search rounds at most (refine.hip), 0 = no search
     double delaunay_penalty = 0.0;
     bool capacity = false;                    // the search with the model's reference capacities (the _cap calls) ...
-    same_window_capacity cap{1, 0, 0.0};      // ... these
+    same_window_capacity cap{1, 0, 0.0};      // ... these (the transport start's too)
+    bool has_cap = false;                     // the call brought a capacity (the transport start needs one)
     int stride = SAME_WINDOW_STATS;           // int64 words per window in out_stats
 };
 int check_mode(same_ctx *ctx, const FinishMode &m) {
-    REQUIRE(ctx, m.incumbent == SAME_INCUMBENT_GREEDY || m.incumbent == SAME_INCUMBENT_ASSIGNMENT);
+    REQUIRE(ctx, m.incumbent == SAME_INCUMBENT_GREEDY || m.incumbent == SAME_INCUMBENT_ASSIGNMENT ||
+                     (m.incumbent == SAME_INCUMBENT_TRANSPORT && m.has_cap));
     REQUIRE(ctx, m.refine_cap >= 0 && m.delaunay_penalty >= 0.0 && m.delaunay_penalty - m.delaunay_penalty == 0.0);
     REQUIRE(ctx, m.cap.max_matches >= 1 && m.cap.multiplier >= 0 && m.cap.penalty_coeff >= 0.0 &&
                      m.cap.penalty_coeff - m.cap.penalty_coeff == 0.0);
@@ -381,11 +383,13 @@ FinishMode mode_of(int incumbent, double no_match_penalty, int64_t refine_rounds
     FinishMode m{incumbent, no_match_penalty, refine_rounds_cap, delaunay_penalty};
     m.capacity = capacity != nullptr && refine_rounds_cap > 0;
     if (capacity) m.cap = *capacity;
-    m.stride = wide ? SAME_WINDOW_STATS_CAP : SAME_WINDOW_STATS;
+    m.has_cap = capacity != nullptr;
+    m.stride = !wide ? SAME_WINDOW_STATS : incumbent == SAME_INCUMBENT_TRANSPORT ? SAME_WINDOW_STATS_TRANSPORT : SAME_WINDOW_STATS_CAP;
     return m;
 }
-// words of a window's out_stats record after the eight counters: the assignment's flags and objective, the search's record
-enum { WS_AS_FLAGS = 8, WS_AS_OBJ = 9, WS_REFINE = 10 };
+// words of a window's out_stats record after the eight counters: the assignment's flags and objective, the search's record, the
+// transport start's sum_j max(0, count_j - 1)
+enum { WS_AS_FLAGS = 8, WS_AS_OBJ = 9, WS_REFINE = 10, WS_AS_EXTRA = 16 };
 
 // (FinishBack: the head's zeroed length, the block that comes back and its parts -- window_internal.h)
 struct FinishPlan : FinishBack {
@@ -438,6 +442,8 @@ int prepare_finish(same_window *w, const int32_t *host_tris, int64_t cap_tr, con
     p->aargs = asg::AssignArgs{};
     p->aargs.n = n;
     p->aargs.n_r = w->n_r;
+    p->aargs.transport = mode.incumbent == SAME_INCUMBENT_TRANSPORT;
+    p->aargs.pc = mode.cap.penalty_coeff;
     p->refine = mode.refine_cap > 0;
     rfn::RefineArgs &r = p->rargs;
     r = rfn::RefineArgs{};
@@ -455,7 +461,7 @@ int prepare_finish(same_window *w, const int32_t *host_tris, int64_t cap_tr, con
         w->match_loc = cv.take<int32_t>((size_t)n);
         w->sign = cv.take<int8_t>(tt);
         w->weight = cv.take<double>(tt);
-        if (mode.incumbent == SAME_INCUMBENT_ASSIGNMENT) asg::lay(p->aargs, cv);
+        if (mode.incumbent != SAME_INCUMBENT_GREEDY) asg::lay(p->aargs, cv);
         if (p->refine) rfn::lay(r, cv);
         return cv.off;
     };
@@ -511,10 +517,30 @@ int enqueue_refine(same_ctx *ctx, FinishPlan *const *ps, int n_w) {
 // aligned row) -- and the tail: one launch per kernel for the whole group (windows of one batch call share the cost type and the mode)
 int launch_finish(same_ctx *ctx, same_window *const *ws, FinishPlan *const *ps, int n_w) {
     const double no_match_penalty = ps[0]->mode.no_match_penalty;
-    if (ps[0]->mode.incumbent == SAME_INCUMBENT_ASSIGNMENT) {
+    if (ps[0]->mode.incumbent != SAME_INCUMBENT_GREEDY) {
         // the optimal assignment instead (assign.hip): it writes match_pair, clears the pairs' greedy flags, and leaves searches, flags
-        // and objective in the head of `sel` (the greedy rounds' words, unused here), which comes back with the finish block
+        // and objective in the head of `sel` (the greedy rounds' words, unused here), which comes back with the finish block.  The
+        // transport form: within the windows' reference limits, which the search's limits kernel works out first
+        const bool transport = ps[0]->mode.incumbent == SAME_INCUMBENT_TRANSPORT;
         asg::AssignArgs jobs[SAME_LAUNCH_WINDOWS];
+        if (transport) {
+            rfn::RefineArgs lim[SAME_LAUNCH_WINDOWS];
+            for (int q = 0; q < n_w; ++q) {
+                const same_window *w = ws[q];
+                const same_window_capacity &c = ps[q]->mode.cap;
+                rfn::RefineArgs &r = lim[q];
+                r = rfn::RefineArgs{};
+                r.rsize = w->ref->size;
+                r.ref_row = w->jsec;
+                r.ref_rows = w->rows_r;
+                r.P = w->P;
+                r.n_r = w->n_r;
+                r.max_matches = c.max_matches;
+                r.multiplier = c.multiplier;
+                r.limit = ps[q]->aargs.limit;
+            }
+            SAME_TRY(rfn::launch_limits(ctx, lim, n_w));
+        }
         for (int q = 0; q < n_w; ++q) {
             same_window *w = ws[q];
             FinishPlan *p = ps[q];
@@ -525,7 +551,7 @@ int launch_finish(same_ctx *ctx, same_window *const *ws, FinishPlan *const *ps, 
             a.cost = w->cost64;
             a.size = w->size_c;
             a.penalty = no_match_penalty;
-            a.max_pops = asg::default_max_pops(w->n_ua, w->n_r, w->P);
+            a.max_pops = asg::default_max_pops(w->n_ua, w->n_r, w->P, transport);
             a.alive = p->gs.alive;
             a.match_pair = p->match_pair;
             a.res = p->gs.sel;
@@ -616,10 +642,11 @@ int read_finish(same_window *w, FinishPlan *p, int32_t *out_match_row, uint8_t *
     const unsigned long long *cnt = reinterpret_cast<const unsigned long long *>(h + p->o_counters);
     int rounds = 0;
     bool again = false;      // the incumbent changed after the first look
-    if (p->mode.incumbent == SAME_INCUMBENT_ASSIGNMENT) {     // no greedy rounds to add: the assignment settled in its one launch
+    if (p->mode.incumbent != SAME_INCUMBENT_GREEDY) {     // no greedy rounds to add: the assignment settled in its one launch
         rounds = (int)sel[0];
         out_stats[WS_AS_FLAGS] = (int64_t)sel[2];
         out_stats[WS_AS_OBJ] = (int64_t)sel[3];             // the bits of a double
+        if (p->mode.incumbent == SAME_INCUMBENT_TRANSPORT) out_stats[WS_AS_EXTRA] = (int64_t)sel[4];
     } else if (P) {
         int q = 0;
         while (q < WINDOW_GREEDY_ROUNDS && sel[q] != 0) ++q;

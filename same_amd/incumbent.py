@@ -36,7 +36,15 @@ optim_params["hip_refine"] = "capacity" is the same search within the model's re
 reference frame holds metacells and j is one (the multiplier None: the frame's largest size), else max_matches, at most 1001; every match
 after a reference's first costs penalty_coeff, so the objective gains penalty_coeff * sum_j max(0, count_j - 1).  Moves go to references
 with room.  With every limit 1 it is "local" bit for bit.  The stats also carry `ref_extra_matches` (sum_j max(0, count_j - 1) of the
-result), and both objectives include the penalty_coeff term.  The starts stay one-to-one.
+result), and both objectives include the penalty_coeff term.  The "greedy" and "assignment" starts stay one-to-one.
+
+optim_params["hip_incumbent"] = "transport" (opt-in) is the start that uses those capacities: the model WITHOUT its triangle term,
+solved to its optimum on the GPU (csrc/assign.hip) -- every cell takes one of its pairs or stays unmatched, reference j takes
+at most limit_j cells, each after its first priced penalty_coeff.  Any max_matches >= 1; with every limit 1 it is "assignment" bit for
+bit.  Its `objective` is a lower bound on the window's full lazy model (delaunay_penalty * w_t * q_t >= 0), so with
+hip_refine="capacity" on top the stats carry `mip_gap` = (mip_objective - objective) / |mip_objective|: how far the refined window can be
+from optimal.  The stats also carry `ref_extra_matches_start`, `transport_searches` and `fallback` (the certificate refused; the host solved the expanded
+graph).  hip_refine="local" does not go with it (that search holds every reference to one match).
 
 Two routes produce the same table (tests/test_gpu_run_same.py::test_incumbent_table_routes_agree):
   device   both frames resident on the GPU, two library calls per window, the incumbent and the sweeps computed where the pairs are
@@ -58,14 +66,16 @@ from .api import _Staged, prepare_same_inputs, ref_match_limits
 from .window_api import _WindowJob, _walk_windows
 
 STAT_KEYS = ("pairs", "triangles", "checked", "flipped", "xy_violations", "area_flips", "matched")
-INCUMBENTS = ("greedy", "assignment")          # optim_params["hip_incumbent"]; "greedy" without the key
+INCUMBENTS = ("greedy", "assignment", "transport")          # optim_params["hip_incumbent"]; "greedy" without the key
 
 
 def incumbent_mode(optim_params, gurobi_params=None, moving=None):
-    """optim_params["hip_incumbent"] checked before anything reaches a device -> "greedy" | "assignment".  The assignment is the
-    reference's Hungarian start (src/init_helpers.py:135-175) without its size cap: it needs max_matches == 1 (:97-98, the reference's own
-    message), and it equals the reference's dense big-M problem only while every no-match cost no_match_penalty * size is below
-    init_big_m / 2 (gurobi_params), which is checked over every aligned cell of `moving`."""
+    """optim_params["hip_incumbent"] checked before anything reaches a device -> "greedy" | "assignment" | "transport".  The assignment
+    is the reference's Hungarian start (src/init_helpers.py:135-175) without its size cap: it needs max_matches == 1 (:97-98, the
+    reference's own message), and it equals the reference's dense big-M problem only while every no-match cost no_match_penalty * size is
+    below init_big_m / 2 (gurobi_params), which is checked over every aligned cell of `moving`.  The transport start takes any
+    max_matches >= 1; its penalty_coeff, max_matches and ref_metacell_match_multiplier pass the checks of hip_refine="capacity"
+    (`transport_capacity` gives the triple)."""
     from .params import init_gurobi_params, init_optim_params
     from .window_api import ResidentFrames
 
@@ -74,6 +84,9 @@ def incumbent_mode(optim_params, gurobi_params=None, moving=None):
     if not isinstance(mode, str) or mode not in INCUMBENTS:
         raise ValueError(f"optim_params['hip_incumbent'] must be one of {INCUMBENTS}, not {mode!r}")
     if mode == "greedy":
+        return mode
+    if mode == "transport":
+        _capacity_of(init_optim_params(**op), "hip_incumbent='transport'")
         return mode
     op = init_optim_params(**op)
     if op["max_matches"] != 1:
@@ -88,6 +101,32 @@ def incumbent_mode(optim_params, gurobi_params=None, moving=None):
             raise ValueError(f"hip_incumbent='assignment': a no-match cost no_match_penalty * size ({np.nanmax(worst):g}) is not below "
                              f"init_big_m / 2 ({big_m / 2:g}); the sparse problem would differ from the reference's big-M one")
     return mode
+
+
+def _capacity_of(full, what):
+    """(max_matches, ref_metacell_match_multiplier or None, penalty_coeff) of the completed optim_params `full`, checked for `what`
+    (hip_refine="capacity" and hip_incumbent="transport" read the model's reference capacities by the same rule)"""
+    import numbers
+
+    pc, mm, mult = full["penalty_coeff"], full["max_matches"], full["ref_metacell_match_multiplier"]
+    if isinstance(pc, bool) or not isinstance(pc, numbers.Real) or not np.isfinite(float(pc)) or float(pc) < 0:
+        raise ValueError(f"optim_params['penalty_coeff'] must be finite and >= 0 for {what}, not {pc!r}")
+    if isinstance(mm, bool) or not isinstance(mm, numbers.Integral) or mm < 1:
+        raise ValueError(f"optim_params['max_matches'] must be an int >= 1 for {what}, not {mm!r}")
+    if mult is not None and (isinstance(mult, bool) or not isinstance(mult, numbers.Integral) or mult < 1):
+        raise ValueError(f"optim_params['ref_metacell_match_multiplier'] must be None or an int >= 1 for {what}, "
+                         f"not {mult!r}")
+    return int(mm), None if mult is None else int(mult), float(pc)
+
+
+def transport_capacity(optim_params):
+    """the capacity triple of hip_incumbent="transport" (checked), None for the other starts"""
+    from .params import init_optim_params
+
+    op = dict(optim_params or {})
+    if op.get("hip_incumbent", "greedy") != "transport":
+        return None
+    return _capacity_of(init_optim_params(**op), "hip_incumbent='transport'")
 
 
 REFINES = ("local", "capacity")               # optim_params["hip_refine"]; None without the key
@@ -118,15 +157,7 @@ def refine_mode(optim_params):
         raise ValueError(f"optim_params['delaunay_penalty'] must be finite and >= 0 for hip_refine, not {dp!r}")
     if mode == "local":
         return int(cap), float(dp)
-    pc, mm, mult = full["penalty_coeff"], full["max_matches"], full["ref_metacell_match_multiplier"]
-    if isinstance(pc, bool) or not isinstance(pc, numbers.Real) or not np.isfinite(float(pc)) or float(pc) < 0:
-        raise ValueError(f"optim_params['penalty_coeff'] must be finite and >= 0 for hip_refine='capacity', not {pc!r}")
-    if isinstance(mm, bool) or not isinstance(mm, numbers.Integral) or mm < 1:
-        raise ValueError(f"optim_params['max_matches'] must be an int >= 1 for hip_refine='capacity', not {mm!r}")
-    if mult is not None and (isinstance(mult, bool) or not isinstance(mult, numbers.Integral) or mult < 1):
-        raise ValueError(f"optim_params['ref_metacell_match_multiplier'] must be None or an int >= 1 for hip_refine='capacity', "
-                         f"not {mult!r}")
-    return int(cap), float(dp), (int(mm), None if mult is None else int(mult), float(pc))
+    return int(cap), float(dp), _capacity_of(full, "hip_refine='capacity'")
 
 
 def _default_workers():
@@ -330,7 +361,7 @@ class _TableBuilder:
         return pd.DataFrame(out, copy=False)
 
 
-def incumbent_of_prepared(prep, commonCT, with_ref_idx=True, ctx=None, use_device=True, incumbent="greedy", refine=None):
+def incumbent_of_prepared(prep, commonCT, with_ref_idx=True, ctx=None, use_device=True, incumbent="greedy", refine=None, capacity=None):
     """(match table of ONE window as run_same's post-solve builds it, stats) from its pre-MIP artefacts, through the host-buffer entry
     points: greedy start -> matching -> lazy-constraint body, XY-order sweep, area flips.  The general route of this module.
     use_device: a PreparedInputs made by the device-resident window path with its pair list untouched carries the incumbent and the
@@ -340,7 +371,10 @@ def incumbent_of_prepared(prep, commonCT, with_ref_idx=True, ctx=None, use_devic
     refine=(rounds_cap, delaunay_penalty): the local search on the lazy model's objective (ops.refine_matching) from the incumbent
     before the sweeps; the stats then carry mip_objective_start, mip_objective, refine_rounds, refine_moves, refine_settled.
     refine=(rounds_cap, delaunay_penalty, (max_matches, multiplier, penalty_coeff)): the same within the reference capacities of
-    prep.ref_df (api.ref_match_limits; ops.refine_matching_cap); the stats also carry ref_extra_matches."""
+    prep.ref_df (api.ref_match_limits; ops.refine_matching_cap); the stats also carry ref_extra_matches.
+    incumbent="transport" with capacity=(max_matches, multiplier, penalty_coeff): the optimum of the model without its triangle term
+    within those capacities (ops.sparse_transport); the stats carry "objective", "fallback", "ref_extra_matches_start",
+    "transport_searches" (the device's augmenting searches) and, with a search on top, "mip_gap"."""
     op = prep.optim_params
     dw = getattr(prep, "device", None)
     if use_device and dw is not None and dw.match_row is not None and isinstance(prep.valid_pairs, np.ndarray):
@@ -353,21 +387,26 @@ def incumbent_of_prepared(prep, commonCT, with_ref_idx=True, ctx=None, use_devic
     if incumbent == "assignment":
         pair_of_row, st = ops.sparse_assign(pairs, costs, float(op["no_match_penalty"]) * size, n_a, n_r, ctx=ctx)
         extra = {"objective": st["objective"], "fallback": st["fallback"]}
+    elif incumbent == "transport":
+        pair_of_row, st = ops.sparse_transport(pairs, costs, float(op["no_match_penalty"]) * size, n_a, n_r,
+                                               _ref_limits(r_df, capacity), capacity[2], ctx=ctx)
+        extra = {"objective": st["objective"], "fallback": st["fallback"], "ref_extra_matches_start": st["ref_extra_matches"],
+                 "transport_searches": st["rounds"]}
     else:
         wants = ops.pair_rowmin(pairs, costs, n_a, ctx=ctx) < float(op["no_match_penalty"]) * size     # src/init_helpers.py:104,118-122
         pair_of_row, _rounds = ops.greedy_match(pairs, costs, n_a, n_r, wants, ctx=ctx)
     axy, rxy = a_df[["X", "Y"]].to_numpy(dtype=np.float64), r_df[["X", "Y"]].to_numpy(dtype=np.float64)
     t32 = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
     if refine is not None and len(refine) > 2:
-        mm, mult, pc = refine[2]
-        limits = np.minimum(np.asarray(ref_match_limits(r_df, mm, mult), dtype=np.float64), MAX_REF_LIMIT).astype(np.int32)
         pair_of_row, rst = ops.refine_matching_cap(pairs, costs, float(op["no_match_penalty"]) * size, n_a, n_r, t32, axy, rxy, size,
-                                                   refine[1], limits, pc, refine[0], pair_of_row, ctx=ctx)
+                                                   refine[1], _ref_limits(r_df, refine[2]), refine[2][2], refine[0], pair_of_row, ctx=ctx)
         extra.update(_refine_stats(rst))
     elif refine is not None:
         pair_of_row, rst = ops.refine_matching(pairs, costs, float(op["no_match_penalty"]) * size, n_a, n_r, t32, axy, rxy, size,
                                                refine[1], refine[0], pair_of_row, ctx=ctx)
         extra.update(_refine_stats(rst))
+    if incumbent == "transport" and refine is not None:
+        extra["mip_gap"] = mip_gap(extra["mip_objective"], extra["objective"])
     ai = np.flatnonzero(pair_of_row >= 0)
     ri = pairs[pair_of_row[ai], 1].astype(np.int64)
     match = np.full(n_a, -1, np.int32)
@@ -385,6 +424,18 @@ def incumbent_of_prepared(prep, commonCT, with_ref_idx=True, ctx=None, use_devic
     stats = {"pairs": len(pairs), "triangles": len(t32), "checked": int(checked), "flipped": len(viol), "xy_violations": int(counts[1]),
              "area_flips": int(np.count_nonzero(flipped)), "matched": len(ai), **extra}
     return _window_table(prep, commonCT, ai, ri, flip_node, pflag, with_ref_idx), stats
+
+
+def _ref_limits(r_df, capacity):
+    """the model's match limit of every reference of a window's frame (api.ref_match_limits), at most MAX_REF_LIMIT, int32"""
+    mm, mult, _pc = capacity
+    return np.minimum(np.asarray(ref_match_limits(r_df, mm, mult), dtype=np.float64), MAX_REF_LIMIT).astype(np.int32)
+
+
+def mip_gap(mip_objective, bound):
+    """(mip_objective - bound) / max(|mip_objective|, tiny): how far a refined window is from the transport optimum, which bounds the
+    full lazy model from below (the triangle term is >= 0 and the start solves the model's own capacities)"""
+    return (float(mip_objective) - float(bound)) / max(abs(float(mip_objective)), np.finfo(np.float64).tiny)
 
 
 def _match_table(a_df, r_df, ra, rr, commonCT, cid, aligned_idx, ref_idx, triangle_violation, filtered_violation):
@@ -447,8 +498,13 @@ def _device_stats(dw):
            "xy_violations": st["xy_violations"], "area_flips": st["area_flips"], "matched": st["matched"]}
     if dw.assignment is not None:
         rec["objective"], rec["fallback"] = dw.assignment["objective"], dw.assignment["fallback"]
+        if "ref_extra_matches_start" in dw.assignment:
+            rec["ref_extra_matches_start"] = dw.assignment["ref_extra_matches_start"]
+            rec["transport_searches"] = dw.assignment["rounds"]
     if dw.refine is not None:
         rec.update(_refine_stats(dw.refine))
+        if dw.assignment is not None and "ref_extra_matches_start" in dw.assignment:       # the transport start: a bound on the model
+            rec["mip_gap"] = mip_gap(rec["mip_objective"], rec["objective"])
     return rec
 
 
@@ -481,10 +537,14 @@ def sliding_window_incumbent(ref, moving, commonCT=None, outprefix=None, moving_
     (dist.sharded_merged_window_incumbent)."""
     mode = incumbent_mode(optim_params, gurobi_params, moving)
     refine = refine_mode(optim_params)
+    capacity = transport_capacity(optim_params)
+    if capacity is not None and refine is not None and len(refine) < 3:
+        raise ValueError("hip_refine='local' keeps every reference to one match; on hip_incumbent='transport' use hip_refine='capacity'")
     job = _WindowJob(ref, moving, commonCT, outprefix, moving_delaunay, moving_delaunay_vertex_col, optim_params, gurobi_params,
                      ignore_precomputed_triangulation, _shard)
     job.incumbent = mode
     job.refine = refine
+    job.capacity = capacity
     frames, own = job.device_frames(_pipeline, ctx=ctx)
     fast = frames is not None and not job.caller_triangulation and not job.optim_params["ignore_knn_if_matched"]
     if _route is not None:
@@ -573,7 +633,7 @@ def _device_route(job, frames, workers, with_ref_idx, triangulator, stats, merge
                                                                 [pos_of[id(w)] for w in windows])
         for (pos, w), dw in zip(mine, frames.windows([w for _p, w in mine], ctx=contexts[q], triangulator=triangulator,
                                                      collector=collector, batch=batch, incumbent=job.incumbent,
-                                                     refine=job.refine)):
+                                                     refine=job.refine, capacity=job.capacity)):
             if dw.error is not None:
                 raise dw.error
             with stage("table rows (central trim)"):
@@ -738,7 +798,8 @@ def _general_route(job, frames, with_ref_idx, stats, ctx):
                 continue
             with stage("incumbent + sweeps + table (general route)"):
                 window_matches, stats[pos] = incumbent_of_prepared(prep, commonCT, with_ref_idx, ctx=ctx, use_device=False,
-                                                                         incumbent=job.incumbent, refine=job.refine)
+                                                                         incumbent=job.incumbent, refine=job.refine,
+                                                                         capacity=job.capacity)
             job.collect(pos, w, window_matches)
     finally:
         job.outprefix = keep_csv

@@ -363,6 +363,100 @@ def assign_objective(match_pair, costs, unmatched):
     return float(np.sum(costs[match_pair[m]]) + np.sum(unmatched[~m]))
 
 
+MAX_REF_LIMIT = 1001        # count_j <= 1 + the bound 1000 of p_j (src/same.py:1117)
+
+
+def _transport_args(pairs, costs, unmatched, n_aligned, n_ref, ref_limit, penalty_coeff):
+    """the transport problem's arguments, checked (ValueError) before anything reaches a device or a solver"""
+    pairs = np.asarray(pairs).reshape(-1, 2)
+    costs, unmatched, limit = np.asarray(costs, F64), np.asarray(unmatched, F64), np.asarray(ref_limit)
+    n_aligned, n_ref = int(n_aligned), int(n_ref)
+    if len(costs) != len(pairs) or len(unmatched) != n_aligned or limit.shape != (n_ref,):
+        raise ValueError("transport: costs per pair, unmatched per aligned row and ref_limit per reference are needed")
+    if n_ref and (not np.issubdtype(limit.dtype, np.integer) or limit.min() < 1 or limit.max() > MAX_REF_LIMIT):
+        raise ValueError(f"transport: every ref_limit must be an int in 1..{MAX_REF_LIMIT}")
+    pc = float(penalty_coeff)
+    if not np.isfinite(pc) or pc < 0:
+        raise ValueError(f"transport: penalty_coeff must be finite and >= 0, not {penalty_coeff!r}")
+    if len(pairs) and (pairs.min() < 0 or pairs[:, 0].max() >= n_aligned or pairs[:, 1].max() >= n_ref):
+        raise ValueError("transport: a pair names a row or a reference that is not there")
+    return pairs, costs, unmatched, n_aligned, n_ref, limit.astype(I32), pc
+
+
+def sparse_transport(pairs, costs, unmatched, n_aligned, n_ref, ref_limit, penalty_coeff, ctx=None):
+    """The capacity-aware optimal start: the model without its triangle term (src/same.py:1191-1196 at delaunay_penalty 0) solved to
+    its optimum on the device (same_sparse_assign_cap; csrc/assign.hip).  Every aligned row takes one of its pairs or its no-match column
+    at `unmatched[i]`; reference j takes at most ref_limit[j] rows (1 .. 1001), each after its first priced `penalty_coeff`; minimum of
+    pair costs + no-match costs + penalty_coeff * sum_j max(0, count_j - 1).  The value is a lower bound on the full lazy model.
+    -> (match_pair (n_aligned,) int32: pair index per row, -1 = unmatched; stats {"rounds", "objective", "ref_extra_matches",
+    "fallback"}).  A problem the device's certificate refuses is solved again on the host (`sparse_transport_host`) and counted as a
+    fallback.  With every limit 1 it is `sparse_assign` bit for bit.  tests/transport_check.py states the problem on the host."""
+    pairs, costs, unmatched, n_aligned, n_ref, limit, pc = _transport_args(pairs, costs, unmatched, n_aligned, n_ref, ref_limit,
+                                                                           penalty_coeff)
+    ctx = _ctx(ctx)
+    pairs, costs, unmatched, limit = as_c(pairs, I32).reshape(-1, 2), as_c(costs, F64), as_c(unmatched, F64), as_c(limit, I32)
+    out = np.empty(n_aligned, I32)
+    st = np.zeros(5, I64)
+    with ctx.lock:
+        ctx.check(ctx.lib.same_sparse_assign_cap(ctx.handle, pairs.ctypes.data, costs.ctypes.data, len(pairs), unmatched.ctypes.data,
+                                                 n_aligned, n_ref, limit.ctypes.data, pc, out.ctypes.data, st.ctypes.data),
+                  "same_sparse_assign_cap")
+    stats = {"rounds": int(st[0]), "objective": float(st[3:4].view(F64)[0]), "ref_extra_matches": int(st[4]), "fallback": 0}
+    if st[2] != 0:
+        out = sparse_transport_host(pairs, costs, unmatched, n_aligned, n_ref, limit, pc)
+        stats["objective"], stats["ref_extra_matches"] = transport_objective(out, pairs, costs, unmatched, n_ref, pc, with_extra=True)
+        stats["fallback"] = 1
+    return out, stats
+
+
+def sparse_transport_host(pairs, costs, unmatched, n_aligned, n_ref, ref_limit, penalty_coeff):
+    """The same problem by scipy.sparse.csgraph.min_weight_full_bipartite_matching on the EXPANDED graph (the fallback of
+    `sparse_transport` and of the window path): reference j becomes min(ref_limit[j], degree_j) copies, the copies after the first
+    `penalty_coeff` dearer (the surcharge is convex: an optimum fills the cheap copy first, so this prices count_j rows on j at
+    penalty_coeff * max(0, count_j - 1)); a no-match column per row; every edge shifted to be >= 1 (sparse matrices drop explicit
+    zeros; every row is assigned once, so the shift leaves the optimum where it was).  -> match_pair as `sparse_transport`."""
+    from scipy.sparse import csr_matrix
+    from scipy.sparse.csgraph import min_weight_full_bipartite_matching
+
+    pairs, costs, unmatched, n_aligned, n_ref, limit, pc = _transport_args(pairs, costs, unmatched, n_aligned, n_ref, ref_limit,
+                                                                           penalty_coeff)
+    pairs = pairs.astype(np.int64)
+    out = np.full(n_aligned, -1, I32)
+    if n_aligned == 0:
+        return out
+    copies = np.minimum(limit.astype(np.int64), np.bincount(pairs[:, 1], minlength=n_ref))          # per reference
+    first = np.concatenate(([0], np.cumsum(copies)))                                                 # its first column
+    per_pair = copies[pairs[:, 1]]
+    edge_pair = np.repeat(np.arange(len(pairs)), per_pair)                                           # the pair of every expanded edge
+    tier = np.arange(len(edge_pair)) - np.repeat(np.cumsum(per_pair) - per_pair, per_pair)           # 0 = the first copy
+    n_cols = int(first[-1])
+    rows = np.concatenate((pairs[edge_pair, 0], np.arange(n_aligned)))
+    cols = np.concatenate((first[pairs[edge_pair, 1]] + tier, n_cols + np.arange(n_aligned)))
+    w = np.concatenate((costs[edge_pair] + np.where(tier > 0, pc, 0.0), unmatched))
+    w = w - w.min() + 1.0
+    g = csr_matrix((w, (rows, cols)), shape=(n_aligned, n_cols + n_aligned))
+    row_ind, row_col = min_weight_full_bipartite_matching(g)
+    assert np.array_equal(row_ind, np.arange(n_aligned))
+    col_ref = np.repeat(np.arange(n_ref), copies)
+    lookup = {(int(i), int(j)): p for p, (i, j) in enumerate(pairs.tolist())}
+    for i, c in enumerate(row_col.tolist()):
+        if c < n_cols:
+            out[i] = lookup[(i, int(col_ref[c]))]
+    return out
+
+
+def transport_objective(match_pair, pairs, costs, unmatched, n_ref, penalty_coeff, with_extra=False):
+    """pair costs + no-match costs + penalty_coeff * sum_j max(0, count_j - 1) of a `sparse_transport` answer (with_extra: and that
+    sum)"""
+    match_pair, costs, unmatched = np.asarray(match_pair), np.asarray(costs, F64), np.asarray(unmatched, F64)
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    m = match_pair >= 0
+    count = np.bincount(pairs[match_pair[m], 1], minlength=int(n_ref))
+    extra = int(np.maximum(count - 1, 0).sum())
+    obj = float(np.sum(costs[match_pair[m]]) + np.sum(unmatched[~m]) + float(penalty_coeff) * extra)
+    return (obj, extra) if with_extra else obj
+
+
 def refine_matching(pairs, costs, unmatched, n_aligned, n_ref, triangles, axy, ref_xy, size, delaunay_penalty, rounds_cap, match_pair,
                     ctx=None):
     """The local search of csrc/refine.hip on host buffers (same_refine_matching): from the one-to-one `match_pair` (pair index per

@@ -146,7 +146,7 @@ class _DeviceFrames:
         return None
 
     def windows(self, plan, triangulate=True, ctx=None, triangulator=None, fetch_triangles=False, collector=None, batch=None,
-                incumbent="greedy", refine=None):
+                incumbent="greedy", refine=None, capacity=None):
         from .windows import iter_device_windows
 
         op = self.op
@@ -155,7 +155,7 @@ class _DeviceFrames:
                                    ignore_same_type_triangles=op["ignore_same_type_triangles"], no_match_penalty=op["no_match_penalty"],
                                    ctx=self.ctx if ctx is None else ctx, triangulate=triangulate, triangulator=triangulator,
                                    fetch_triangles=fetch_triangles, collector=collector, batch=batch, incumbent=incumbent,
-                                   refine=refine)
+                                   refine=refine, capacity=capacity)
 
     def accumulators(self, contexts, cid):
         """One merge accumulator per worker context (kept with the frames: a pass re-uses the arrays of the last), and the sections' id

@@ -453,20 +453,20 @@ class DeviceWindow:
     STAT_NAMES = ("checked", "flipped", "xy_comparisons", "xy_violations", "xy_triangles", "area_flips", "greedy_rounds", "matched")
 
     def filter_finish(self, simplices, radius, angle_enabled, cos_thr, near_tol, ignore_same_type, no_match_penalty,
-                      ensure_min_triangle_per_node=True, incumbent="greedy", refine=None):
+                      ensure_min_triangle_per_node=True, incumbent="greedy", refine=None, capacity=None):
         """filter_triangles_by_radius of the kept aligned cells' Delaunay simplices, then signs, weights, the incumbent and the three
         sweeps, in one call.  -> (kept, added back, near, match_row, flag, stats); with near != 0 (cosines within near_tol of the
         threshold) the last three are None and the caller filters on the host and calls finish() with its triangles.  `incumbent`,
-        `refine`: as for filter_finish_windows."""
+        `refine`, `capacity`: as for filter_finish_windows."""
         return filter_finish_windows([self], [simplices], radius, angle_enabled, cos_thr, near_tol, ignore_same_type, no_match_penalty,
-                                     ensure_min_triangle_per_node, incumbent=incumbent, refine=refine)[0]
+                                     ensure_min_triangle_per_node, incumbent=incumbent, refine=refine, capacity=capacity)[0]
 
-    def finish(self, triangles, no_match_penalty, incumbent="greedy", refine=None):
+    def finish(self, triangles, no_match_penalty, incumbent="greedy", refine=None, capacity=None):
         """The same with triangles the CALLER filtered (kept ones, in the reference's order).  -> (section row of the matched reference
         cell per kept aligned cell or -1, flag byte per kept cell: bit 0 = XY-order sweep, bit 1 = vertex of an area-flipped triangle;
         stats dict)."""
         return filter_finish_windows([self], [triangles], 0.0, 0, 0.0, 0.0, False, no_match_penalty, True, prefiltered=True,
-                                     incumbent=incumbent, refine=refine)[0][3:]
+                                     incumbent=incumbent, refine=refine, capacity=capacity)[0][3:]
 
     def refinish(self, match_pair, no_match_penalty, refine=None):
         """the finished window's matched rows and sweeps again under `match_pair` (pair index per kept cell, -1 = none), the local search
@@ -748,7 +748,8 @@ def stage_windows(states, moving, ref, boxes, radius, knn, dist_ct_coeff):
     return [s.counts for s in states]
 
 
-_INCUMBENTS = {"greedy": _lib.SAME_INCUMBENT_GREEDY, "assignment": _lib.SAME_INCUMBENT_ASSIGNMENT}
+_INCUMBENTS = {"greedy": _lib.SAME_INCUMBENT_GREEDY, "assignment": _lib.SAME_INCUMBENT_ASSIGNMENT,
+               "transport": _lib.SAME_INCUMBENT_TRANSPORT}
 
 
 def _refine_args(refine):
@@ -757,12 +758,14 @@ def _refine_args(refine):
     return (0, 0.0) if refine is None else (int(refine[0]), float(refine[1]))
 
 
-def _capacity_arg(refine):
-    """the capacity of `refine` = (rounds_cap, delaunay_penalty, (max_matches, multiplier or None, penalty_coeff)) -> the library's
-    same_window_capacity; None without one (hip_refine="local")"""
-    if refine is None or len(refine) < 3 or refine[2] is None:
+def _capacity_arg(refine, capacity=None):
+    """the capacity of `refine` = (rounds_cap, delaunay_penalty, (max_matches, multiplier or None, penalty_coeff)), else the transport
+    start's `capacity` (the same triple) -> the library's same_window_capacity; None without one (hip_refine="local")"""
+    if refine is not None and len(refine) >= 3 and refine[2] is not None:
+        capacity = refine[2]
+    if capacity is None:
         return None
-    mm, mult, pc = refine[2]
+    mm, mult, pc = capacity
     return _lib.WindowCapacity(int(mm), 0 if mult is None else int(mult), float(pc))
 
 
@@ -771,7 +774,9 @@ def _window_records(s, incumbent, refine):
     "flags", "objective"}, the search's record {"rounds", "moves", "settled", "objective_start", "objective"[, "ref_extra_matches"]}),
     each None when its mode was off"""
     f = s.view(np.float64)
-    asg = {"rounds": int(s[6]), "flags": int(s[8]), "objective": float(f[9])} if incumbent == "assignment" else None
+    asg = {"rounds": int(s[6]), "flags": int(s[8]), "objective": float(f[9])} if incumbent in ("assignment", "transport") else None
+    if incumbent == "transport":        # (SAME_WINDOW_STATS_TRANSPORT words)
+        asg["ref_extra_matches_start"] = int(s[16])
     rfn = None if refine is None else {"rounds": int(s[10]), "moves": int(s[11]), "settled": int(s[12]), "objective_start": float(f[13]),
                                        "objective": float(f[14])}
     if rfn is not None and len(s) > _lib.SAME_WINDOW_STATS:
@@ -780,13 +785,15 @@ def _window_records(s, incumbent, refine):
 
 
 def filter_finish_windows(states, simplices, radius, angle_enabled, cos_thr, near_tol, ignore_same_type, no_match_penalty,
-                          ensure_min_triangle_per_node=True, prefiltered=False, incumbent="greedy", refine=None):
+                          ensure_min_triangle_per_node=True, prefiltered=False, incumbent="greedy", refine=None, capacity=None):
     """same_window_filter_finish for a batch (one wait for all of them): `simplices[i]` are window i's Delaunay simplices, or with
     `prefiltered` its kept triangles; `simplices=None` takes the candidates `triangulate_windows` left on the device for every window
     (each state must have been answered since it was staged).  `incumbent`: "greedy" (src/init_helpers.py:104-133) or "assignment" (the
     optimal one-to-one assignment, csrc/assign.hip); `refine` = (rounds_cap, delaunay_penalty) runs the local search on the lazy model's
     objective from the incumbent (csrc/refine.hip) for at most rounds_cap rounds, None none; (rounds_cap, delaunay_penalty, (max_matches,
-    multiplier or None, penalty_coeff)) runs it with the model's reference capacities (same_window_filter_finish_cap).
+    multiplier or None, penalty_coeff)) runs it with the model's reference capacities (same_window_filter_finish_cap).  "transport": the
+    optimum of the model without its triangle term within `capacity` = (max_matches, multiplier or None, penalty_coeff), required (a
+    `refine` on it carries the same triple).
     -> [(kept, added back, near, match_row, flag byte, stats dict) per window]; a window with near != 0 has None for the last three.
     Every state's `order_ties` is set to the call's count of places where the answer hangs on the ORDER of the triangles or of their
     corners (include/same_hip.h; of consequence only when the simplices are not Qhull's own), its `assignment` and `refine` to the
@@ -801,11 +808,17 @@ def filter_finish_windows(states, simplices, radius, angle_enabled, cos_thr, nea
         np.cumsum([len(t) for t in tris], out=offsets[1:])
         flat = tris[0] if n == 1 else np.concatenate(tris)
     cap, dp = _refine_args(refine)
-    capacity = _capacity_arg(refine)
+    if incumbent == "transport":
+        if capacity is None or (refine is not None and (len(refine) < 3 or tuple(refine[2]) != tuple(capacity))):
+            raise ValueError("incumbent='transport' needs its capacity, and a refine on it the same one")
+    elif capacity is not None:
+        raise ValueError("capacity goes with incumbent='transport'")
+    capacity = _capacity_arg(refine, capacity)
     kept_cells = [s.counts[2] for s in states]
     cell_off = np.concatenate(([0], np.cumsum(kept_cells))).astype(np.int64)
     match_row, flag = np.empty(int(cell_off[-1]), np.int32), np.empty(int(cell_off[-1]), np.uint8)
-    width = _lib.SAME_WINDOW_STATS if capacity is None else _lib.SAME_WINDOW_STATS_CAP
+    width = (_lib.SAME_WINDOW_STATS if capacity is None else
+             _lib.SAME_WINDOW_STATS_TRANSPORT if incumbent == "transport" else _lib.SAME_WINDOW_STATS_CAP)
     stats, counts = np.zeros((n, width), np.int64), np.zeros((n, 4), np.int64)
     args = (_handles(states), n, source, _lib._ptr(flat), _lib._ptr(offsets), float(radius), int(angle_enabled), float(cos_thr),
             float(near_tol), int(bool(ignore_same_type)), int(bool(ensure_min_triangle_per_node)), float(no_match_penalty),
@@ -840,18 +853,40 @@ def triangulate_windows(states, radius, angle_enabled, cos_thr, guard):
     return status, n_tris
 
 
-def _assignment_fallback(state, out, moving, no_match_penalty, refine):
+def window_ref_limits(ref_size, pairs, capacity):
+    """The model's match limit of every reference row of a window (src/helpers.py:102-161 as csrc/refine.hip's limits kernel reads it):
+    `ref_size` the sizes of the window's reference rows, the frame = the references its `pairs` name; (max_matches, multiplier or None,
+    penalty_coeff) -> int32 limits, at most 1001"""
+    mm, mult, _pc = capacity
+    ref_size = np.asarray(ref_size, dtype=np.float64)
+    frame = ref_size[np.unique(np.asarray(pairs).reshape(-1, 2)[:, 1])]
+    any_meta = bool((frame > 1).any())
+    if mult is None:
+        mult = int(frame.max()) if len(frame) else 0
+    big, plain = min(int(mult) * int(mm), ops.MAX_REF_LIMIT), min(int(mm), ops.MAX_REF_LIMIT)
+    return np.where(any_meta & (ref_size > 1), big, plain).astype(np.int32)
+
+
+def _assignment_fallback(state, out, moving, no_match_penalty, refine, ref=None, capacity=None):
     """a window whose assignment the device's certificate refused: solved by scipy's sparse solver and finished again under that
-    matching (counted as a fallback) -> (match_row, flag byte, stats dict); greedy_rounds stays the device's searches"""
+    matching (counted as a fallback) -> (match_row, flag byte, stats dict); greedy_rounds stays the device's searches.  With a
+    `capacity` (the transport start) the host solves the transport problem within the window's limits (sizes from the section `ref`)."""
     from ._trace import stage as marked
 
     with marked("assignment fallback (host)"):
         pairs, costs = state.fetch(_W_PAIRS), state.fetch(_W_COSTS)
         unmatched = float(no_match_penalty) * moving.size[out.rows_m].astype(np.float64)
-        mp = ops.sparse_assign_host(pairs, costs, unmatched, len(unmatched), out.counts[1])
+        if capacity is None:
+            mp = ops.sparse_assign_host(pairs, costs, unmatched, len(unmatched), out.counts[1])
+            record = dict(objective=ops.assign_objective(mp, costs, unmatched), fallback=1)
+        else:
+            limits = window_ref_limits(ref.size[state.fetch(_W_ROWS_R)], pairs, capacity)
+            mp = ops.sparse_transport_host(pairs, costs, unmatched, len(unmatched), out.counts[1], limits, capacity[2])
+            obj, extra = ops.transport_objective(mp, pairs, costs, unmatched, out.counts[1], capacity[2], with_extra=True)
+            record = dict(objective=obj, ref_extra_matches_start=extra, fallback=1)
         match_row, cell_flags, stats = state.refinish(mp, no_match_penalty, refine)
         stats["greedy_rounds"] = out.assignment["rounds"]
-        out.assignment.update(objective=ops.assign_objective(mp, costs, unmatched), fallback=1)
+        out.assignment.update(record)
     return match_row, cell_flags, stats
 
 
@@ -905,7 +940,7 @@ class TriangulationCache(QhullTriangulator):
 
 def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dist_ct_coeff=1.0, min_angle_deg=15,
                         ignore_same_type_triangles=True, no_match_penalty=100.0, ctx=None, fetch_triangles=False, triangulator=None,
-                        triangulate=True, batch=None, collector=None, incumbent="greedy", refine=None):
+                        triangulate=True, batch=None, collector=None, incumbent="greedy", refine=None, capacity=None):
     """The window path of `iter_window_arrays` + the greedy incumbent and the three sweeps, with both sections resident on the
     device (`dref`, `dmoving`: DeviceSections of `ref`, `moving`): per window the host only triangulates (Qhull helpers, windows
     ahead as before) and receives the match; the triangle filter runs on the device too, unless a cosine sits within 8 ulp of the
@@ -925,7 +960,9 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
     MergeAccumulator.collect).
     `incumbent`: "greedy" (src/init_helpers.py:104-133) or "assignment" -- the optimal one-to-one assignment of the window's kept cells
     under the pair costs with a no-match column per cell (csrc/assign.hip); a window whose answer the device does not certify is solved
-    again on the host (ops.sparse_assign_host) and finished again under that matching.
+    again on the host (ops.sparse_assign_host) and finished again under that matching.  "transport" with `capacity` = (max_matches,
+    multiplier or None, penalty_coeff): the optimum of the model without its triangle term within the reference capacities (the same
+    kernel's transport form; a refused window goes to ops.sparse_transport_host the same way).
     `refine` = (rounds_cap, delaunay_penalty): the local search on the lazy model's objective runs on every window's incumbent before the
     sweeps (csrc/refine.hip; every later finish of the window -- greedy rounds added, the assignment's fallback, a re-finish with scipy's
     simplices -- runs it again); the match, flags and stats are then the search's, and `result.refine` holds its counts."""
@@ -1010,7 +1047,7 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
         with marked("triangulate (wait for helper)"):
             tris = [ticket.result() for ticket in tickets]
         args = (radius, angle_enabled, cos_thr, near_tol, ignore_same_type_triangles, no_match_penalty)
-        mode = dict(incumbent=incumbent, refine=refine)
+        mode = dict(incumbent=incumbent, refine=refine, capacity=capacity)
         with marked("filter + signs + incumbent + sweeps (device)"):
             # candidates the device made stay there (simplices None); every other window brings its simplices
             mine = [q for q, t in enumerate(tris) if t is None]
@@ -1037,10 +1074,11 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
                                                                _type_id=tid)
                 with marked("signs + incumbent + sweeps (device)"):
                     match_row, cell_flags, stats = state.finish(out.triangles, no_match_penalty, **mode)
-            if incumbent == "assignment":
-                out.assignment = {"objective": state.assignment["objective"], "fallback": 0, "rounds": state.assignment["rounds"]}
+            if incumbent in ("assignment", "transport"):
+                out.assignment = {k: v for k, v in state.assignment.items() if k != "flags"}
+                out.assignment["fallback"] = 0
                 if state.assignment["flags"]:
-                    match_row, cell_flags, stats = _assignment_fallback(state, out, moving, no_match_penalty, refine)
+                    match_row, cell_flags, stats = _assignment_fallback(state, out, moving, no_match_penalty, refine, ref, capacity)
             out.refine = state.refine
             out.match_row, out.stats = match_row, stats
             # the library packs both per-cell flags into one byte

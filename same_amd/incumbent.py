@@ -63,101 +63,11 @@ import pandas as pd
 from . import ops
 from ._trace import stage
 from .api import _Staged, prepare_same_inputs, ref_match_limits
+from .ops import MAX_REF_LIMIT          # noqa: F401  (the bound of every reference's match limit, "capacity" and "transport")
 from .window_api import _WindowJob, _walk_windows
+from .window_mode import INCUMBENTS, REFINE_ROUNDS, REFINES, WindowMode, incumbent_mode, refine_mode, transport_capacity  # noqa: F401
 
 STAT_KEYS = ("pairs", "triangles", "checked", "flipped", "xy_violations", "area_flips", "matched")
-INCUMBENTS = ("greedy", "assignment", "transport")          # optim_params["hip_incumbent"]; "greedy" without the key
-
-
-def incumbent_mode(optim_params, gurobi_params=None, moving=None):
-    """optim_params["hip_incumbent"] checked before anything reaches a device -> "greedy" | "assignment" | "transport".  The assignment
-    is the reference's Hungarian start (src/init_helpers.py:135-175) without its size cap: it needs max_matches == 1 (:97-98, the
-    reference's own message), and it equals the reference's dense big-M problem only while every no-match cost no_match_penalty * size is
-    below init_big_m / 2 (gurobi_params), which is checked over every aligned cell of `moving`.  The transport start takes any
-    max_matches >= 1; its penalty_coeff, max_matches and ref_metacell_match_multiplier pass the checks of hip_refine="capacity"
-    (`transport_capacity` gives the triple)."""
-    from .params import init_gurobi_params, init_optim_params
-    from .window_api import ResidentFrames
-
-    op = dict(optim_params or {})
-    mode = op.get("hip_incumbent", "greedy")
-    if not isinstance(mode, str) or mode not in INCUMBENTS:
-        raise ValueError(f"optim_params['hip_incumbent'] must be one of {INCUMBENTS}, not {mode!r}")
-    if mode == "greedy":
-        return mode
-    if mode == "transport":
-        _capacity_of(init_optim_params(**op), "hip_incumbent='transport'")
-        return mode
-    op = init_optim_params(**op)
-    if op["max_matches"] != 1:
-        raise ValueError("init_method='hungarian' requires max_matches == 1.")
-    big_m = float(init_gurobi_params(**dict(gurobi_params or {}))["init_big_m"])
-    frame = moving.moving_arg if isinstance(moving, ResidentFrames) else moving
-    frame = getattr(frame, "metacell_df", frame)
-    if frame is not None and len(frame):
-        size = frame["size"].to_numpy(dtype=np.float64) if "size" in frame.columns else np.ones(1)
-        worst = float(op["no_match_penalty"]) * size
-        if not np.all(worst < big_m / 2):
-            raise ValueError(f"hip_incumbent='assignment': a no-match cost no_match_penalty * size ({np.nanmax(worst):g}) is not below "
-                             f"init_big_m / 2 ({big_m / 2:g}); the sparse problem would differ from the reference's big-M one")
-    return mode
-
-
-def _capacity_of(full, what):
-    """(max_matches, ref_metacell_match_multiplier or None, penalty_coeff) of the completed optim_params `full`, checked for `what`
-    (hip_refine="capacity" and hip_incumbent="transport" read the model's reference capacities by the same rule)"""
-    import numbers
-
-    pc, mm, mult = full["penalty_coeff"], full["max_matches"], full["ref_metacell_match_multiplier"]
-    if isinstance(pc, bool) or not isinstance(pc, numbers.Real) or not np.isfinite(float(pc)) or float(pc) < 0:
-        raise ValueError(f"optim_params['penalty_coeff'] must be finite and >= 0 for {what}, not {pc!r}")
-    if isinstance(mm, bool) or not isinstance(mm, numbers.Integral) or mm < 1:
-        raise ValueError(f"optim_params['max_matches'] must be an int >= 1 for {what}, not {mm!r}")
-    if mult is not None and (isinstance(mult, bool) or not isinstance(mult, numbers.Integral) or mult < 1):
-        raise ValueError(f"optim_params['ref_metacell_match_multiplier'] must be None or an int >= 1 for {what}, "
-                         f"not {mult!r}")
-    return int(mm), None if mult is None else int(mult), float(pc)
-
-
-def transport_capacity(optim_params):
-    """the capacity triple of hip_incumbent="transport" (checked), None for the other starts"""
-    from .params import init_optim_params
-
-    op = dict(optim_params or {})
-    if op.get("hip_incumbent", "greedy") != "transport":
-        return None
-    return _capacity_of(init_optim_params(**op), "hip_incumbent='transport'")
-
-
-REFINES = ("local", "capacity")               # optim_params["hip_refine"]; None without the key
-REFINE_ROUNDS = 32                             # optim_params["hip_refine_rounds"] without the key (DESIGN §5.8)
-MAX_REF_LIMIT = 1001                           # "capacity": count_j <= 1 + the bound 1000 of p_j (src/same.py:1117)
-
-
-def refine_mode(optim_params):
-    """optim_params["hip_refine"] / ["hip_refine_rounds"] / ["delaunay_penalty"] (and for "capacity" ["penalty_coeff"] /
-    ["max_matches"] / ["ref_metacell_match_multiplier"]) checked before anything reaches a device -> None (no search),
-    (rounds_cap, delaunay_penalty) ("local") or (rounds_cap, delaunay_penalty, (max_matches, multiplier or None, penalty_coeff))"""
-    import numbers
-
-    from .params import init_optim_params
-
-    op = dict(optim_params or {})
-    mode = op.get("hip_refine")
-    if mode is None:
-        return None
-    if not isinstance(mode, str) or mode not in REFINES:
-        raise ValueError(f"optim_params['hip_refine'] must be None or one of {REFINES}, not {mode!r}")
-    cap = op.get("hip_refine_rounds", REFINE_ROUNDS)
-    if isinstance(cap, bool) or not isinstance(cap, numbers.Integral) or cap < 1:
-        raise ValueError(f"optim_params['hip_refine_rounds'] must be a positive int, not {cap!r}")
-    full = init_optim_params(**op)
-    dp = full["delaunay_penalty"]
-    if isinstance(dp, bool) or not isinstance(dp, numbers.Real) or not np.isfinite(float(dp)) or float(dp) < 0:
-        raise ValueError(f"optim_params['delaunay_penalty'] must be finite and >= 0 for hip_refine, not {dp!r}")
-    if mode == "local":
-        return int(cap), float(dp)
-    return int(cap), float(dp), _capacity_of(full, "hip_refine='capacity'")
 
 
 def _default_workers():
@@ -361,20 +271,15 @@ class _TableBuilder:
         return pd.DataFrame(out, copy=False)
 
 
-def incumbent_of_prepared(prep, commonCT, with_ref_idx=True, ctx=None, use_device=True, incumbent="greedy", refine=None, capacity=None):
+def incumbent_of_prepared(prep, commonCT, with_ref_idx=True, ctx=None, use_device=True, mode=None):
     """(match table of ONE window as run_same's post-solve builds it, stats) from its pre-MIP artefacts, through the host-buffer entry
     points: greedy start -> matching -> lazy-constraint body, XY-order sweep, area flips.  The general route of this module.
     use_device: a PreparedInputs made by the device-resident window path with its pair list untouched carries the incumbent and the
     sweeps already (computed where the pairs are, by same_window_filter_finish): take them instead of computing them again.
-    incumbent="assignment": the optimal one-to-one assignment (ops.sparse_assign) instead of the greedy start; the stats then carry the
-    window's "objective" and whether it fell back to the host solver ("fallback").
-    refine=(rounds_cap, delaunay_penalty): the local search on the lazy model's objective (ops.refine_matching) from the incumbent
-    before the sweeps; the stats then carry mip_objective_start, mip_objective, refine_rounds, refine_moves, refine_settled.
-    refine=(rounds_cap, delaunay_penalty, (max_matches, multiplier, penalty_coeff)): the same within the reference capacities of
-    prep.ref_df (api.ref_match_limits; ops.refine_matching_cap); the stats also carry ref_extra_matches.
-    incumbent="transport" with capacity=(max_matches, multiplier, penalty_coeff): the optimum of the model without its triangle term
-    within those capacities (ops.sparse_transport); the stats carry "objective", "fallback", "ref_extra_matches_start",
-    "transport_searches" (the device's augmenting searches) and, with a search on top, "mip_gap"."""
+    `mode`: a WindowMode (None: the greedy start alone).  Its start through ops.sparse_assign / ops.sparse_transport, its search
+    through ops.refine_matching / ops.refine_matching_cap with the reference limits of prep.ref_df (api.ref_match_limits); the stats
+    carry the keys the module text lists for the start and the search."""
+    mode = WindowMode.default() if mode is None else mode
     op = prep.optim_params
     dw = getattr(prep, "device", None)
     if use_device and dw is not None and dw.match_row is not None and isinstance(prep.valid_pairs, np.ndarray):
@@ -383,30 +288,27 @@ def incumbent_of_prepared(prep, commonCT, with_ref_idx=True, ctx=None, use_devic
     costs, n_a, n_r = prep.costs_array, prep.n_aligned, prep.n_ref
     a_df, r_df, tris = prep.aligned_df, prep.ref_df, prep.triangles_array
     size = a_df["size"].to_numpy(dtype=np.float64)
-    extra = {}
-    if incumbent == "assignment":
-        pair_of_row, st = ops.sparse_assign(pairs, costs, float(op["no_match_penalty"]) * size, n_a, n_r, ctx=ctx)
-        extra = {"objective": st["objective"], "fallback": st["fallback"]}
-    elif incumbent == "transport":
-        pair_of_row, st = ops.sparse_transport(pairs, costs, float(op["no_match_penalty"]) * size, n_a, n_r,
-                                               _ref_limits(r_df, capacity), capacity[2], ctx=ctx)
-        extra = {"objective": st["objective"], "fallback": st["fallback"], "ref_extra_matches_start": st["ref_extra_matches"],
-                 "transport_searches": st["rounds"]}
+    unmatched = float(op["no_match_penalty"]) * size
+    start = search = None
+    if mode.incumbent == "assignment":
+        pair_of_row, start = ops.sparse_assign(pairs, costs, unmatched, n_a, n_r, ctx=ctx)
+    elif mode.incumbent == "transport":
+        pair_of_row, st = ops.sparse_transport(pairs, costs, unmatched, n_a, n_r, _ref_limits(r_df, mode.capacity), mode.capacity[2],
+                                               ctx=ctx)
+        start = {"objective": st["objective"], "fallback": st["fallback"], "rounds": st["rounds"],
+                 "ref_extra_matches_start": st["ref_extra_matches"]}       # (the device route's names: windows._assignment_fallback)
     else:
-        wants = ops.pair_rowmin(pairs, costs, n_a, ctx=ctx) < float(op["no_match_penalty"]) * size     # src/init_helpers.py:104,118-122
+        wants = ops.pair_rowmin(pairs, costs, n_a, ctx=ctx) < unmatched     # src/init_helpers.py:104,118-122
         pair_of_row, _rounds = ops.greedy_match(pairs, costs, n_a, n_r, wants, ctx=ctx)
     axy, rxy = a_df[["X", "Y"]].to_numpy(dtype=np.float64), r_df[["X", "Y"]].to_numpy(dtype=np.float64)
     t32 = np.ascontiguousarray(tris, dtype=np.int32).reshape(-1, 3)
-    if refine is not None and len(refine) > 2:
-        pair_of_row, rst = ops.refine_matching_cap(pairs, costs, float(op["no_match_penalty"]) * size, n_a, n_r, t32, axy, rxy, size,
-                                                   refine[1], _ref_limits(r_df, refine[2]), refine[2][2], refine[0], pair_of_row, ctx=ctx)
-        extra.update(_refine_stats(rst))
-    elif refine is not None:
-        pair_of_row, rst = ops.refine_matching(pairs, costs, float(op["no_match_penalty"]) * size, n_a, n_r, t32, axy, rxy, size,
-                                               refine[1], refine[0], pair_of_row, ctx=ctx)
-        extra.update(_refine_stats(rst))
-    if incumbent == "transport" and refine is not None:
-        extra["mip_gap"] = mip_gap(extra["mip_objective"], extra["objective"])
+    if mode.refine is not None:
+        problem, (rounds, dp) = (pairs, costs, unmatched, n_a, n_r, t32, axy, rxy, size), mode.search_args
+        if mode.refine == "capacity":
+            pair_of_row, search = ops.refine_matching_cap(*problem, dp, _ref_limits(r_df, mode.capacity), mode.capacity[2], rounds,
+                                                          pair_of_row, ctx=ctx)
+        else:
+            pair_of_row, search = ops.refine_matching(*problem, dp, rounds, pair_of_row, ctx=ctx)
     ai = np.flatnonzero(pair_of_row >= 0)
     ri = pairs[pair_of_row[ai], 1].astype(np.int64)
     match = np.full(n_a, -1, np.int32)
@@ -422,7 +324,7 @@ def incumbent_of_prepared(prep, commonCT, with_ref_idx=True, ctx=None, use_devic
     if len(t32):
         flip_node[t32[flipped.astype(bool)].reshape(-1)] = True
     stats = {"pairs": len(pairs), "triangles": len(t32), "checked": int(checked), "flipped": len(viol), "xy_violations": int(counts[1]),
-             "area_flips": int(np.count_nonzero(flipped)), "matched": len(ai), **extra}
+             "area_flips": int(np.count_nonzero(flipped)), "matched": len(ai), **_mode_stats(mode, start, search)}
     return _window_table(prep, commonCT, ai, ri, flip_node, pflag, with_ref_idx), stats
 
 
@@ -482,30 +384,30 @@ def _table_of_device_window(prep, dw, commonCT, with_ref_idx):
                         dw.flip_flag[ai], dw.point_flag[ai]), stats
 
 
-def _refine_stats(rst):
-    """the local search's keys of a window's stats record"""
-    out = {"mip_objective_start": rst["objective_start"], "mip_objective": rst["objective"], "refine_rounds": rst["rounds"],
-           "refine_moves": rst["moves"], "refine_settled": rst["settled"]}
-    if "ref_extra_matches" in rst:
-        out["ref_extra_matches"] = rst["ref_extra_matches"]
-    return out
+def _mode_stats(mode, start, search):
+    """what `mode` adds to a window's stats record, on either route: from the record of its start ({"objective", "fallback", "rounds",
+    "ref_extra_matches_start"}; None for greedy) and of its search (WindowMode.records; None without one)"""
+    rec = {}
+    if mode.incumbent != "greedy":
+        rec["objective"], rec["fallback"] = start["objective"], start["fallback"]
+    if mode.incumbent == "transport":
+        rec["ref_extra_matches_start"], rec["transport_searches"] = start["ref_extra_matches_start"], start["rounds"]
+    if mode.refine is not None:
+        rec.update(mip_objective_start=search["objective_start"], mip_objective=search["objective"], refine_rounds=search["rounds"],
+                   refine_moves=search["moves"], refine_settled=search["settled"])
+    if mode.refine == "capacity":
+        rec["ref_extra_matches"] = search["ref_extra_matches"]
+    if mode.incumbent == "transport" and mode.refine is not None:       # the transport start: a bound on the model
+        rec["mip_gap"] = mip_gap(rec["mip_objective"], rec["objective"])
+    return rec
 
 
 def _device_stats(dw):
     """a window's stats record (STAT_KEYS) from what the device counted"""
     st = dw.stats
-    rec = {"pairs": dw.counts[3], "triangles": dw.n_triangles, "checked": st["checked"], "flipped": st["flipped"],
-           "xy_violations": st["xy_violations"], "area_flips": st["area_flips"], "matched": st["matched"]}
-    if dw.assignment is not None:
-        rec["objective"], rec["fallback"] = dw.assignment["objective"], dw.assignment["fallback"]
-        if "ref_extra_matches_start" in dw.assignment:
-            rec["ref_extra_matches_start"] = dw.assignment["ref_extra_matches_start"]
-            rec["transport_searches"] = dw.assignment["rounds"]
-    if dw.refine is not None:
-        rec.update(_refine_stats(dw.refine))
-        if dw.assignment is not None and "ref_extra_matches_start" in dw.assignment:       # the transport start: a bound on the model
-            rec["mip_gap"] = mip_gap(rec["mip_objective"], rec["objective"])
-    return rec
+    return {"pairs": dw.counts[3], "triangles": dw.n_triangles, "checked": st["checked"], "flipped": st["flipped"],
+            "xy_violations": st["xy_violations"], "area_flips": st["area_flips"], "matched": st["matched"],
+            **_mode_stats(dw.mode, dw.assignment, dw.refine)}
 
 
 def _device_ref_idx(dw):
@@ -535,16 +437,9 @@ def sliding_window_incumbent(ref, moving, commonCT=None, outprefix=None, moving_
     aligned ids ascending -- without the pre-merge table ever being laid out: the merge reads the rows' keys, and only the rows it keeps
     get their columns.  With `_shard` and a `_merge_channel` (dist.MergeChannel) the result is this rank's PART of the merged table
     (dist.sharded_merged_window_incumbent)."""
-    mode = incumbent_mode(optim_params, gurobi_params, moving)
-    refine = refine_mode(optim_params)
-    capacity = transport_capacity(optim_params)
-    if capacity is not None and refine is not None and len(refine) < 3:
-        raise ValueError("hip_refine='local' keeps every reference to one match; on hip_incumbent='transport' use hip_refine='capacity'")
+    mode = WindowMode.from_params(optim_params, gurobi_params, moving)
     job = _WindowJob(ref, moving, commonCT, outprefix, moving_delaunay, moving_delaunay_vertex_col, optim_params, gurobi_params,
-                     ignore_precomputed_triangulation, _shard)
-    job.incumbent = mode
-    job.refine = refine
-    job.capacity = capacity
+                     ignore_precomputed_triangulation, _shard, mode=mode)
     frames, own = job.device_frames(_pipeline, ctx=ctx)
     fast = frames is not None and not job.caller_triangulation and not job.optim_params["ignore_knn_if_matched"]
     if _route is not None:
@@ -632,8 +527,7 @@ def _device_route(job, frames, workers, with_ref_idx, triangulator, stats, merge
             collector = lambda states, windows: accs[q].collect(states, [w["trim"] for w in windows], [w["window_id"] for w in windows],
                                                                 [pos_of[id(w)] for w in windows])
         for (pos, w), dw in zip(mine, frames.windows([w for _p, w in mine], ctx=contexts[q], triangulator=triangulator,
-                                                     collector=collector, batch=batch, incumbent=job.incumbent,
-                                                     refine=job.refine, capacity=job.capacity)):
+                                                     collector=collector, batch=batch, mode=job.mode)):
             if dw.error is not None:
                 raise dw.error
             with stage("table rows (central trim)"):
@@ -797,9 +691,7 @@ def _general_route(job, frames, with_ref_idx, stats, ctx):
             if len(prep.valid_pairs) == 0:               # every node unconstrained under the caller's triangulation: nothing to match
                 continue
             with stage("incumbent + sweeps + table (general route)"):
-                window_matches, stats[pos] = incumbent_of_prepared(prep, commonCT, with_ref_idx, ctx=ctx, use_device=False,
-                                                                         incumbent=job.incumbent, refine=job.refine,
-                                                                         capacity=job.capacity)
+                window_matches, stats[pos] = incumbent_of_prepared(prep, commonCT, with_ref_idx, ctx=ctx, use_device=False, mode=job.mode)
             job.collect(pos, w, window_matches)
     finally:
         job.outprefix = keep_csv

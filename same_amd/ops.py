@@ -464,22 +464,8 @@ def refine_matching(pairs, costs, unmatched, n_aligned, n_ref, triangles, axy, r
     unmatched cell + delaunay_penalty * the size sum of every kept triangle the lazy body (:645-669) sees flip -- for at most
     `rounds_cap` rounds.  -> (match_pair (n_aligned,) int32, stats {"rounds", "moves", "settled", "objective_start", "objective"}).
     tests/refine_check.py states the same rule on the host."""
-    ctx = _ctx(ctx)
-    pairs, costs, unmatched = as_c(pairs, I32).reshape(-1, 2), as_c(costs, F64), as_c(unmatched, F64)
-    tris, axy, ref_xy, size = _tris(triangles), as_c(axy, F64).reshape(-1, 2), as_c(ref_xy, F64).reshape(-1, 2), as_c(size, F64)
-    n_aligned, n_ref = int(n_aligned), int(n_ref)
-    assert len(costs) == len(pairs) and len(unmatched) == n_aligned == len(axy) == len(size) and len(ref_xy) == n_ref
-    out = np.array(match_pair, dtype=I32, copy=True).reshape(-1)
-    assert len(out) == n_aligned
-    st = np.zeros(5, I64)
-    with ctx.lock:
-        ctx.check(ctx.lib.same_refine_matching(ctx.handle, pairs.ctypes.data, costs.ctypes.data, len(pairs), unmatched.ctypes.data,
-                                               n_aligned, n_ref, tris.ctypes.data, len(tris), axy.ctypes.data, ref_xy.ctypes.data,
-                                               size.ctypes.data, float(delaunay_penalty), int(rounds_cap), out.ctypes.data,
-                                               st.ctypes.data), "same_refine_matching")
-    obj = st[3:5].view(F64)
-    return out, {"rounds": int(st[0]), "moves": int(st[1]), "settled": int(st[2]), "objective_start": float(obj[0]),
-                 "objective": float(obj[1])}
+    return _refine(pairs, costs, unmatched, n_aligned, n_ref, triangles, axy, ref_xy, size, delaunay_penalty, None, rounds_cap,
+                   match_pair, ctx)
 
 
 def refine_matching_cap(pairs, costs, unmatched, n_aligned, n_ref, triangles, axy, ref_xy, size, delaunay_penalty, ref_limit, penalty_coeff,
@@ -488,23 +474,35 @@ def refine_matching_cap(pairs, costs, unmatched, n_aligned, n_ref, triangles, ax
     (1 .. 1001), each after the first priced penalty_coeff, so the objective gains penalty_coeff * sum_j max(0, count_j - 1).
     `match_pair` may hold a reference up to its limit.  -> (match_pair, stats as refine_matching's + "ref_extra_matches" (that sum)).
     With every limit 1 it is refine_matching bit for bit.  tests/refine_capacity_check.py states the same rule on the host."""
+    return _refine(pairs, costs, unmatched, n_aligned, n_ref, triangles, axy, ref_xy, size, delaunay_penalty, (ref_limit, penalty_coeff),
+                   rounds_cap, match_pair, ctx)
+
+
+def _refine(pairs, costs, unmatched, n_aligned, n_ref, triangles, axy, ref_xy, size, delaunay_penalty, capacity, rounds_cap, match_pair,
+            ctx):
+    """both forms of the search: `capacity` = (ref_limit, penalty_coeff) takes the _cap entry point and its sixth stats word"""
     ctx = _ctx(ctx)
     pairs, costs, unmatched = as_c(pairs, I32).reshape(-1, 2), as_c(costs, F64), as_c(unmatched, F64)
     tris, axy, ref_xy, size = _tris(triangles), as_c(axy, F64).reshape(-1, 2), as_c(ref_xy, F64).reshape(-1, 2), as_c(size, F64)
-    limit = as_c(ref_limit, I32)
     n_aligned, n_ref = int(n_aligned), int(n_ref)
-    assert len(costs) == len(pairs) and len(unmatched) == n_aligned == len(axy) == len(size) and len(ref_xy) == n_ref == len(limit)
+    assert len(costs) == len(pairs) and len(unmatched) == n_aligned == len(axy) == len(size) and len(ref_xy) == n_ref
+    name, extra = "same_refine_matching", ()
+    if capacity is not None:
+        limit = as_c(capacity[0], I32)
+        assert len(limit) == n_ref
+        name, extra = "same_refine_matching_cap", (limit.ctypes.data, float(capacity[1]))
     out = np.array(match_pair, dtype=I32, copy=True).reshape(-1)
     assert len(out) == n_aligned
-    st = np.zeros(6, I64)
+    st = np.zeros(5 if capacity is None else 6, I64)
     with ctx.lock:
-        ctx.check(ctx.lib.same_refine_matching_cap(ctx.handle, pairs.ctypes.data, costs.ctypes.data, len(pairs), unmatched.ctypes.data,
-                                                   n_aligned, n_ref, tris.ctypes.data, len(tris), axy.ctypes.data, ref_xy.ctypes.data,
-                                                   size.ctypes.data, float(delaunay_penalty), limit.ctypes.data, float(penalty_coeff),
-                                                   int(rounds_cap), out.ctypes.data, st.ctypes.data), "same_refine_matching_cap")
+        ctx.check(getattr(ctx.lib, name)(ctx.handle, pairs.ctypes.data, costs.ctypes.data, len(pairs), unmatched.ctypes.data, n_aligned,
+                                         n_ref, tris.ctypes.data, len(tris), axy.ctypes.data, ref_xy.ctypes.data, size.ctypes.data,
+                                         float(delaunay_penalty), *extra, int(rounds_cap), out.ctypes.data, st.ctypes.data), name)
     obj = st[3:5].view(F64)
-    return out, {"rounds": int(st[0]), "moves": int(st[1]), "settled": int(st[2]), "objective_start": float(obj[0]),
-                 "objective": float(obj[1]), "ref_extra_matches": int(st[5])}
+    stats = {"rounds": int(st[0]), "moves": int(st[1]), "settled": int(st[2]), "objective_start": float(obj[0]), "objective": float(obj[1])}
+    if capacity is not None:
+        stats["ref_extra_matches"] = int(st[5])
+    return out, stats
 
 
 def tri_flip_stats(axy, mapped_xy, matched, triangles, type_id=None, ctx=None):

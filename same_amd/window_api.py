@@ -145,8 +145,7 @@ class _DeviceFrames:
             return "cell_type missing (priority filter)"
         return None
 
-    def windows(self, plan, triangulate=True, ctx=None, triangulator=None, fetch_triangles=False, collector=None, batch=None,
-                incumbent="greedy", refine=None, capacity=None):
+    def windows(self, plan, triangulate=True, ctx=None, triangulator=None, fetch_triangles=False, collector=None, batch=None, mode=None):
         from .windows import iter_device_windows
 
         op = self.op
@@ -154,8 +153,7 @@ class _DeviceFrames:
                                    dist_ct_coeff=op["dist_ct_coeff"], min_angle_deg=op.get("min_angle_deg", 15),
                                    ignore_same_type_triangles=op["ignore_same_type_triangles"], no_match_penalty=op["no_match_penalty"],
                                    ctx=self.ctx if ctx is None else ctx, triangulate=triangulate, triangulator=triangulator,
-                                   fetch_triangles=fetch_triangles, collector=collector, batch=batch, incumbent=incumbent,
-                                   refine=refine, capacity=capacity)
+                                   fetch_triangles=fetch_triangles, collector=collector, batch=batch, mode=mode)
 
     def accumulators(self, contexts, cid):
         """One merge accumulator per worker context (kept with the frames: a pass re-uses the arrays of the last), and the sections' id
@@ -373,8 +371,10 @@ class _WindowJob:
     commonCT, the plan, the resume state and this rank's share of the windows."""
 
     def __init__(self, ref, moving, commonCT, outprefix, moving_delaunay, moving_delaunay_vertex_col, optim_params, gurobi_params,
-                 ignore_precomputed_triangulation, shard, resident=None):
+                 ignore_precomputed_triangulation, shard, resident=None, mode=None):
         from .windows import window_grid, window_plan
+
+        self.mode = mode                # how sliding_window_incumbent matches the job's windows (a WindowMode)
 
         # the caller's frames are on the device already (resident_frames): both arguments may name it
         if isinstance(ref, ResidentFrames):

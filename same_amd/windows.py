@@ -12,6 +12,7 @@ import numpy as np
 
 from . import _lib, ops
 from .delaunay import QHULL, QhullTriangulator, Ticket
+from .window_mode import WindowMode
 
 
 def window_grid(ref_xy, mov_xy, window_size, overlap):
@@ -453,42 +454,39 @@ class DeviceWindow:
     STAT_NAMES = ("checked", "flipped", "xy_comparisons", "xy_violations", "xy_triangles", "area_flips", "greedy_rounds", "matched")
 
     def filter_finish(self, simplices, radius, angle_enabled, cos_thr, near_tol, ignore_same_type, no_match_penalty,
-                      ensure_min_triangle_per_node=True, incumbent="greedy", refine=None, capacity=None):
+                      ensure_min_triangle_per_node=True, mode=None):
         """filter_triangles_by_radius of the kept aligned cells' Delaunay simplices, then signs, weights, the incumbent and the three
         sweeps, in one call.  -> (kept, added back, near, match_row, flag, stats); with near != 0 (cosines within near_tol of the
-        threshold) the last three are None and the caller filters on the host and calls finish() with its triangles.  `incumbent`,
-        `refine`, `capacity`: as for filter_finish_windows."""
+        threshold) the last three are None and the caller filters on the host and calls finish() with its triangles.  `mode`: a
+        WindowMode."""
         return filter_finish_windows([self], [simplices], radius, angle_enabled, cos_thr, near_tol, ignore_same_type, no_match_penalty,
-                                     ensure_min_triangle_per_node, incumbent=incumbent, refine=refine, capacity=capacity)[0]
+                                     ensure_min_triangle_per_node, mode=mode)[0]
 
-    def finish(self, triangles, no_match_penalty, incumbent="greedy", refine=None, capacity=None):
+    def finish(self, triangles, no_match_penalty, mode=None):
         """The same with triangles the CALLER filtered (kept ones, in the reference's order).  -> (section row of the matched reference
         cell per kept aligned cell or -1, flag byte per kept cell: bit 0 = XY-order sweep, bit 1 = vertex of an area-flipped triangle;
         stats dict)."""
         return filter_finish_windows([self], [triangles], 0.0, 0, 0.0, 0.0, False, no_match_penalty, True, prefiltered=True,
-                                     incumbent=incumbent, refine=refine, capacity=capacity)[0][3:]
+                                     mode=mode)[0][3:]
 
-    def refinish(self, match_pair, no_match_penalty, refine=None):
-        """the finished window's matched rows and sweeps again under `match_pair` (pair index per kept cell, -1 = none), the local search
-        from it first when `refine` is given -> (match_row, flag byte, stats dict) as `finish` (greedy_rounds 0); `refine` is set to the
-        search's record"""
+    def refinish(self, match_pair, no_match_penalty, mode=None):
+        """the finished window's matched rows and sweeps again under `match_pair` (pair index per kept cell, -1 = none), the search of
+        `mode` (a WindowMode; its start is not run again) from it first -> (match_row, flag byte, stats dict) as `finish`
+        (greedy_rounds 0); `refine` is set to the search's record (decoded with start=False: these stats hold no start's words)"""
+        mode = WindowMode.default() if mode is None else mode
         n = self.counts[2]
         match_pair = np.ascontiguousarray(match_pair, dtype=np.int32)
         assert len(match_pair) == n
-        cap, dp = _refine_args(refine)
-        capacity = _capacity_arg(refine)
-        width = _lib.SAME_WINDOW_STATS if capacity is None else _lib.SAME_WINDOW_STATS_CAP
-        match_row, flag, stats = np.empty(n, np.int32), np.empty(n, np.uint8), np.zeros(width, np.int64)
+        match_row, flag, stats = np.empty(n, np.int32), np.empty(n, np.uint8), np.zeros(mode.refinish_width, np.int64)
+        args = (self.handle, match_pair.ctypes.data, float(no_match_penalty), *mode.search_args)
+        outs = (match_row.ctypes.data, flag.ctypes.data, stats.ctypes.data)
         with self.ctx.lock:
-            if capacity is None:
-                self.ctx.check(self.ctx.lib.same_window_refinish(self.handle, match_pair.ctypes.data, float(no_match_penalty), cap, dp,
-                                                                 match_row.ctypes.data, flag.ctypes.data, stats.ctypes.data),
-                               "same_window_refinish")
+            if mode.refine != "capacity":
+                self.ctx.check(self.ctx.lib.same_window_refinish(*args, *outs), "same_window_refinish")
             else:
-                self.ctx.check(self.ctx.lib.same_window_refinish_cap(self.handle, match_pair.ctypes.data, float(no_match_penalty), cap, dp,
-                                                                     ctypes.byref(capacity), match_row.ctypes.data, flag.ctypes.data,
-                                                                     stats.ctypes.data), "same_window_refinish_cap")
-        self.refine = _window_records(stats, "greedy", refine)[1]
+                capacity = mode.c_capacity()
+                self.ctx.check(self.ctx.lib.same_window_refinish_cap(*args, ctypes.byref(capacity), *outs), "same_window_refinish_cap")
+        self.refine = mode.records(stats, start=False)[1]
         return match_row, flag, dict(zip(self.STAT_NAMES, stats[:8].tolist()))
 
     def close(self):
@@ -748,56 +746,22 @@ def stage_windows(states, moving, ref, boxes, radius, knn, dist_ct_coeff):
     return [s.counts for s in states]
 
 
-_INCUMBENTS = {"greedy": _lib.SAME_INCUMBENT_GREEDY, "assignment": _lib.SAME_INCUMBENT_ASSIGNMENT,
-               "transport": _lib.SAME_INCUMBENT_TRANSPORT}
-
-
-def _refine_args(refine):
-    """`refine` = (rounds_cap, delaunay_penalty[, capacity]) or None -> the library's (rounds_cap, delaunay_penalty), rounds_cap 0 = no
-    search"""
-    return (0, 0.0) if refine is None else (int(refine[0]), float(refine[1]))
-
-
-def _capacity_arg(refine, capacity=None):
-    """the capacity of `refine` = (rounds_cap, delaunay_penalty, (max_matches, multiplier or None, penalty_coeff)), else the transport
-    start's `capacity` (the same triple) -> the library's same_window_capacity; None without one (hip_refine="local")"""
-    if refine is not None and len(refine) >= 3 and refine[2] is not None:
-        capacity = refine[2]
-    if capacity is None:
-        return None
-    mm, mult, pc = capacity
-    return _lib.WindowCapacity(int(mm), 0 if mult is None else int(mult), float(pc))
-
-
-def _window_records(s, incumbent, refine):
-    """a window's stats words (SAME_WINDOW_STATS, or SAME_WINDOW_STATS_CAP with a capacity) -> (the assignment's record {"rounds",
-    "flags", "objective"}, the search's record {"rounds", "moves", "settled", "objective_start", "objective"[, "ref_extra_matches"]}),
-    each None when its mode was off"""
-    f = s.view(np.float64)
-    asg = {"rounds": int(s[6]), "flags": int(s[8]), "objective": float(f[9])} if incumbent in ("assignment", "transport") else None
-    if incumbent == "transport":        # (SAME_WINDOW_STATS_TRANSPORT words)
-        asg["ref_extra_matches_start"] = int(s[16])
-    rfn = None if refine is None else {"rounds": int(s[10]), "moves": int(s[11]), "settled": int(s[12]), "objective_start": float(f[13]),
-                                       "objective": float(f[14])}
-    if rfn is not None and len(s) > _lib.SAME_WINDOW_STATS:
-        rfn["ref_extra_matches"] = int(s[15])
-    return asg, rfn
+def _window_records(stats_words, mode):
+    """WindowMode.records of a FINISH call's stats words (a re-finish's are narrower: `mode.records(s, start=False)`)"""
+    return mode.records(stats_words)
 
 
 def filter_finish_windows(states, simplices, radius, angle_enabled, cos_thr, near_tol, ignore_same_type, no_match_penalty,
-                          ensure_min_triangle_per_node=True, prefiltered=False, incumbent="greedy", refine=None, capacity=None):
+                          ensure_min_triangle_per_node=True, prefiltered=False, mode=None):
     """same_window_filter_finish for a batch (one wait for all of them): `simplices[i]` are window i's Delaunay simplices, or with
     `prefiltered` its kept triangles; `simplices=None` takes the candidates `triangulate_windows` left on the device for every window
-    (each state must have been answered since it was staged).  `incumbent`: "greedy" (src/init_helpers.py:104-133) or "assignment" (the
-    optimal one-to-one assignment, csrc/assign.hip); `refine` = (rounds_cap, delaunay_penalty) runs the local search on the lazy model's
-    objective from the incumbent (csrc/refine.hip) for at most rounds_cap rounds, None none; (rounds_cap, delaunay_penalty, (max_matches,
-    multiplier or None, penalty_coeff)) runs it with the model's reference capacities (same_window_filter_finish_cap).  "transport": the
-    optimum of the model without its triangle term within `capacity` = (max_matches, multiplier or None, penalty_coeff), required (a
-    `refine` on it carries the same triple).
+    (each state must have been answered since it was staged).  `mode`: a WindowMode -- the start, the search on it and the model's
+    reference capacities (None: the greedy start alone); one with a capacity goes through same_window_filter_finish_cap.
     -> [(kept, added back, near, match_row, flag byte, stats dict) per window]; a window with near != 0 has None for the last three.
     Every state's `order_ties` is set to the call's count of places where the answer hangs on the ORDER of the triangles or of their
     corners (include/same_hip.h; of consequence only when the simplices are not Qhull's own), its `assignment` and `refine` to the
     call's records of the two (_window_records; None when off)."""
+    mode = WindowMode.default() if mode is None else mode
     ctx, n = states[0].ctx, len(states)
     if simplices is None:
         source, flat, offsets = _lib.SAME_TRIS_DEVICE, None, None
@@ -807,22 +771,14 @@ def filter_finish_windows(states, simplices, radius, angle_enabled, cos_thr, nea
         offsets = np.zeros(n + 1, np.int64)
         np.cumsum([len(t) for t in tris], out=offsets[1:])
         flat = tris[0] if n == 1 else np.concatenate(tris)
-    cap, dp = _refine_args(refine)
-    if incumbent == "transport":
-        if capacity is None or (refine is not None and (len(refine) < 3 or tuple(refine[2]) != tuple(capacity))):
-            raise ValueError("incumbent='transport' needs its capacity, and a refine on it the same one")
-    elif capacity is not None:
-        raise ValueError("capacity goes with incumbent='transport'")
-    capacity = _capacity_arg(refine, capacity)
+    capacity = mode.c_capacity()
     kept_cells = [s.counts[2] for s in states]
     cell_off = np.concatenate(([0], np.cumsum(kept_cells))).astype(np.int64)
     match_row, flag = np.empty(int(cell_off[-1]), np.int32), np.empty(int(cell_off[-1]), np.uint8)
-    width = (_lib.SAME_WINDOW_STATS if capacity is None else
-             _lib.SAME_WINDOW_STATS_TRANSPORT if incumbent == "transport" else _lib.SAME_WINDOW_STATS_CAP)
-    stats, counts = np.zeros((n, width), np.int64), np.zeros((n, 4), np.int64)
+    stats, counts = np.zeros((n, mode.finish_width), np.int64), np.zeros((n, 4), np.int64)
     args = (_handles(states), n, source, _lib._ptr(flat), _lib._ptr(offsets), float(radius), int(angle_enabled), float(cos_thr),
             float(near_tol), int(bool(ignore_same_type)), int(bool(ensure_min_triangle_per_node)), float(no_match_penalty),
-            _INCUMBENTS[incumbent], cap, dp)
+            mode.incumbent_code, *mode.search_args)
     outs = (match_row.ctypes.data, flag.ctypes.data, stats.ctypes.data, counts.ctypes.data)
     with ctx.lock:
         if capacity is None:
@@ -833,7 +789,7 @@ def filter_finish_windows(states, simplices, radius, angle_enabled, cos_thr, nea
     for i, s in enumerate(states):
         kept, added, near, s.order_ties = (int(c) for c in counts[i])
         s.n_triangles = 0 if near else kept + added
-        s.assignment, s.refine = _window_records(stats[i], incumbent, refine)
+        s.assignment, s.refine = _window_records(stats[i], mode)
         if near:
             out.append((kept, added, near, None, None, None))
         else:
@@ -867,24 +823,24 @@ def window_ref_limits(ref_size, pairs, capacity):
     return np.where(any_meta & (ref_size > 1), big, plain).astype(np.int32)
 
 
-def _assignment_fallback(state, out, moving, no_match_penalty, refine, ref=None, capacity=None):
+def _assignment_fallback(state, out, moving, no_match_penalty, mode, ref=None):
     """a window whose assignment the device's certificate refused: solved by scipy's sparse solver and finished again under that
-    matching (counted as a fallback) -> (match_row, flag byte, stats dict); greedy_rounds stays the device's searches.  With a
-    `capacity` (the transport start) the host solves the transport problem within the window's limits (sizes from the section `ref`)."""
+    matching (counted as a fallback) -> (match_row, flag byte, stats dict); greedy_rounds stays the device's searches.  The transport
+    start of `mode`: the host solves the transport problem within the window's limits (sizes from the section `ref`)."""
     from ._trace import stage as marked
 
     with marked("assignment fallback (host)"):
         pairs, costs = state.fetch(_W_PAIRS), state.fetch(_W_COSTS)
         unmatched = float(no_match_penalty) * moving.size[out.rows_m].astype(np.float64)
-        if capacity is None:
+        if mode.incumbent != "transport":
             mp = ops.sparse_assign_host(pairs, costs, unmatched, len(unmatched), out.counts[1])
             record = dict(objective=ops.assign_objective(mp, costs, unmatched), fallback=1)
         else:
-            limits = window_ref_limits(ref.size[state.fetch(_W_ROWS_R)], pairs, capacity)
-            mp = ops.sparse_transport_host(pairs, costs, unmatched, len(unmatched), out.counts[1], limits, capacity[2])
-            obj, extra = ops.transport_objective(mp, pairs, costs, unmatched, out.counts[1], capacity[2], with_extra=True)
+            limits = window_ref_limits(ref.size[state.fetch(_W_ROWS_R)], pairs, mode.capacity)
+            mp = ops.sparse_transport_host(pairs, costs, unmatched, len(unmatched), out.counts[1], limits, mode.capacity[2])
+            obj, extra = ops.transport_objective(mp, pairs, costs, unmatched, out.counts[1], mode.capacity[2], with_extra=True)
             record = dict(objective=obj, ref_extra_matches_start=extra, fallback=1)
-        match_row, cell_flags, stats = state.refinish(mp, no_match_penalty, refine)
+        match_row, cell_flags, stats = state.refinish(mp, no_match_penalty, mode)
         stats["greedy_rounds"] = out.assignment["rounds"]
         out.assignment.update(record)
     return match_row, cell_flags, stats
@@ -896,17 +852,18 @@ class DeviceWindowResult:
     `match_row` the section row of each cell's matched reference cell (-1 = none), `point_flag` the XY-order sweep's per-cell flag,
     `flip_flag` 1 for the vertices of triangles whose signed area flips, `stats` the sweeps' counters, `counts` (aligned in box, refs in
     box, kept, pairs); `state` is the live DeviceWindow until the generator is asked for the first window of the next batch (pairs,
-    costs, signs ... through `state.fetch`).  `assignment` (incumbent="assignment" only): {"objective", "fallback", "rounds"}.
-    `refine` (refine given only): the search's record of the window's final finish ({"rounds", "moves", "settled", "objective_start",
-    "objective"})."""
+    costs, signs ... through `state.fetch`).  `mode`: the WindowMode the window was finished under.  `assignment` (a start other than
+    greedy only): {"objective", "fallback", "rounds"[, "ref_extra_matches_start"]}.  `refine` (with a search only): the search's record
+    of the window's final finish ({"rounds", "moves", "settled", "objective_start", "objective"[, "ref_extra_matches"]})."""
 
     __slots__ = ("window", "error", "rows_m", "axy", "triangles", "n_triangles", "match_row", "point_flag", "flip_flag", "stats",
-                 "counts", "state", "assignment", "refine")
+                 "counts", "state", "assignment", "refine", "mode")
 
-    def __init__(self, window):
+    def __init__(self, window, mode=None):
         self.window = window
         for name in self.__slots__[1:]:
             setattr(self, name, None)
+        self.mode = mode
 
 
 class TriangulationCache(QhullTriangulator):
@@ -940,7 +897,7 @@ class TriangulationCache(QhullTriangulator):
 
 def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dist_ct_coeff=1.0, min_angle_deg=15,
                         ignore_same_type_triangles=True, no_match_penalty=100.0, ctx=None, fetch_triangles=False, triangulator=None,
-                        triangulate=True, batch=None, collector=None, incumbent="greedy", refine=None, capacity=None):
+                        triangulate=True, batch=None, collector=None, mode=None):
     """The window path of `iter_window_arrays` + the greedy incumbent and the three sweeps, with both sections resident on the
     device (`dref`, `dmoving`: DeviceSections of `ref`, `moving`): per window the host only triangulates (Qhull helpers, windows
     ahead as before) and receives the match; the triangle filter runs on the device too, unless a cosine sits within 8 ulp of the
@@ -958,14 +915,9 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
     (api.sliding_window_matching with a caller's triangulation) and reads pairs / costs through `state.fetch`.
     `collector(states, windows)` is called once per finished batch with its windows' live states (the window merge's accumulator:
     MergeAccumulator.collect).
-    `incumbent`: "greedy" (src/init_helpers.py:104-133) or "assignment" -- the optimal one-to-one assignment of the window's kept cells
-    under the pair costs with a no-match column per cell (csrc/assign.hip); a window whose answer the device does not certify is solved
-    again on the host (ops.sparse_assign_host) and finished again under that matching.  "transport" with `capacity` = (max_matches,
-    multiplier or None, penalty_coeff): the optimum of the model without its triangle term within the reference capacities (the same
-    kernel's transport form; a refused window goes to ops.sparse_transport_host the same way).
-    `refine` = (rounds_cap, delaunay_penalty): the local search on the lazy model's objective runs on every window's incumbent before the
-    sweeps (csrc/refine.hip; every later finish of the window -- greedy rounds added, the assignment's fallback, a re-finish with scipy's
-    simplices -- runs it again); the match, flags and stats are then the search's, and `result.refine` holds its counts."""
+    `mode`: a WindowMode (None: the greedy start alone).  A window whose optimal start the device does not certify is solved again on
+    the host (ops.sparse_assign_host, ops.sparse_transport_host) and finished again under that matching; every later finish of a window
+    (that fallback, a re-finish with scipy's simplices) runs the mode's search again: `result.refine` holds the last one's counts."""
     import os
     from collections import deque
 
@@ -974,6 +926,7 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
     from .triangles import cos_threshold, filter_triangles_by_radius
 
     ctx = ops._ctx(ctx)
+    mode = WindowMode.default() if mode is None else mode
     angle_enabled, cos_thr = cos_threshold(min_angle_deg)
     near_tol = float(8 * np.spacing(abs(cos_thr))) if (angle_enabled and np.isfinite(cos_thr)) else 0.0
     tri = QHULL if triangulator is None else triangulator
@@ -1001,7 +954,7 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
 
     def stage_batch(windows):
         """-> [(result, state or None, ticket or None)] for `windows`, staged by ONE library call"""
-        outs = [DeviceWindowResult(w) for w in windows]
+        outs = [DeviceWindowResult(w, mode) for w in windows]
         if not prune_possible:
             for out in outs:
                 out.error = ValueError("No valid_pairs after KNN filtering. Increase radius and/or knn.")
@@ -1047,13 +1000,12 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
         with marked("triangulate (wait for helper)"):
             tris = [ticket.result() for ticket in tickets]
         args = (radius, angle_enabled, cos_thr, near_tol, ignore_same_type_triangles, no_match_penalty)
-        mode = dict(incumbent=incumbent, refine=refine, capacity=capacity)
         with marked("filter + signs + incumbent + sweeps (device)"):
             # candidates the device made stay there (simplices None); every other window brings its simplices
             mine = [q for q, t in enumerate(tris) if t is None]
             theirs = [q for q, t in enumerate(tris) if t is not None]
-            res = dict(zip(mine, filter_finish_windows([states[q] for q in mine], None, *args, **mode) if mine else []))
-            res.update(zip(theirs, filter_finish_windows([states[q] for q in theirs], [tris[q] for q in theirs], *args, **mode)
+            res = dict(zip(mine, filter_finish_windows([states[q] for q in mine], None, *args, mode=mode) if mine else []))
+            res.update(zip(theirs, filter_finish_windows([states[q] for q in theirs], [tris[q] for q in theirs], *args, mode=mode)
                            if theirs else []))
         # simplices that are not Qhull's own (delaunay.py: the same triangles in another order): where the window's numbers hang on that
         # order -- the device counted such places, or a cosine sits at the threshold and the host is about to re-decide the filter --
@@ -1062,7 +1014,7 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
             if ticket.native and (state.order_ties or res[q][2]):
                 with marked("order ties: the window again with Qhull's simplices"):
                     tris[q] = ticket.qhull()
-                    res[q] = filter_finish_windows([state], [tris[q]], *args, **mode)[0]
+                    res[q] = filter_finish_windows([state], [tris[q]], *args, mode=mode)[0]
         for q, (out, state, _t) in enumerate(todo):
             _kept, _added, near, match_row, cell_flags, stats = res[q]
             if near:
@@ -1073,12 +1025,12 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
                                                                min_angle_deg=min_angle_deg, verbose=False, ctx=ctx, _rows_as_array=True,
                                                                _type_id=tid)
                 with marked("signs + incumbent + sweeps (device)"):
-                    match_row, cell_flags, stats = state.finish(out.triangles, no_match_penalty, **mode)
-            if incumbent in ("assignment", "transport"):
+                    match_row, cell_flags, stats = state.finish(out.triangles, no_match_penalty, mode)
+            if mode.incumbent != "greedy":
                 out.assignment = {k: v for k, v in state.assignment.items() if k != "flags"}
                 out.assignment["fallback"] = 0
                 if state.assignment["flags"]:
-                    match_row, cell_flags, stats = _assignment_fallback(state, out, moving, no_match_penalty, refine, ref, capacity)
+                    match_row, cell_flags, stats = _assignment_fallback(state, out, moving, no_match_penalty, mode, ref)
             out.refine = state.refine
             out.match_row, out.stats = match_row, stats
             # the library packs both per-cell flags into one byte

@@ -233,11 +233,11 @@ PENALTY = 6.0
 REFINE = (256, 4.0)
 
 
-def _finish(st, simplices, **mode):
+def _finish(st, simplices, mode=None):
     from same_amd.triangles import cos_threshold
 
     en, thr = cos_threshold(15)
-    _k0, _k1, near, row, flag, stats = st.filter_finish(simplices, 25.0, en, thr, 0.0, True, PENALTY, **mode)
+    _k0, _k1, near, row, flag, stats = st.filter_finish(simplices, 25.0, en, thr, 0.0, True, PENALTY, mode=mode)
     assert near == 0
     return row, flag, stats
 
@@ -247,16 +247,18 @@ def test_refinish_under_its_own_matching_repeats_the_finish(staged, refine):
     """same_window_refinish with the window's own matching (pair per kept cell from its match and pairs) gives back what the finish
     call gave: matched rows, flag bytes, every counter but the incumbent's rounds; with the search on, a settled search moves no more"""
     from same_amd import windows as W
+    from same_amd.window_mode import WindowMode
 
     st, _rs, _ms, simplices = staged
     for incumbent in ("greedy", "assignment"):
-        row, flag, stats = _finish(st, simplices, incumbent=incumbent, refine=refine)
+        mode = WindowMode(incumbent) if refine is None else WindowMode(incumbent, "local", *refine)
+        row, flag, stats = _finish(st, simplices, mode)
         first = st.refine
         if refine is not None:
             assert first["settled"] == 1 and first["rounds"] < refine[0], first
         pair_of = {tuple(p): q for q, p in enumerate(st.fetch(W._W_PAIRS).tolist())}
         mp = np.array([pair_of[(i, m)] if m >= 0 else -1 for i, m in enumerate(st.fetch(W._W_MATCH).tolist())], np.int32)
-        row2, flag2, stats2 = st.refinish(mp, PENALTY, refine)
+        row2, flag2, stats2 = st.refinish(mp, PENALTY, mode)
         assert np.array_equal(row2, row) and np.array_equal(flag2, flag), incumbent
         assert stats2["greedy_rounds"] == 0 and stats["matched"] > 0 and (stats["greedy_rounds"] > 0 or incumbent == "assignment")
         assert {k: v for k, v in stats2.items() if k != "greedy_rounds"} == {k: v for k, v in stats.items() if k != "greedy_rounds"}
@@ -273,9 +275,10 @@ def test_refinish_under_another_matching_equals_the_host_sweeps(staged, other):
     and counters are those of the host-buffer sweeps for that matching, as incumbent.incumbent_of_prepared computes them"""
     from same_amd import ops
     from same_amd import windows as W
+    from same_amd.window_mode import WindowMode
 
     st, rs, ms, simplices = staged
-    _finish(st, simplices, incumbent="assignment")
+    _finish(st, simplices, WindowMode("assignment"))
     pairs, costs, rows_r = st.fetch(W._W_PAIRS), st.fetch(W._W_COSTS), st.fetch(W._W_ROWS_R)
     axy, rows_m, tris, signs = st.fetch(W._W_ALIGNED_XY), st.fetch(W._W_ALIGNED_ROWS), st.fetch(W._W_TRIANGLES), st.fetch(W._W_SIGNS)
     n_a, rxy = len(axy), rs.xy[rows_r]
@@ -316,8 +319,8 @@ def test_device_route_fallback_equals_the_general_route(monkeypatch, refine):
     want, wst = run(_route="general")
     inner, forced = W._window_records, []
 
-    def flagged(s, incumbent, refine_):
-        asg, rfn = inner(s, incumbent, refine_)
+    def flagged(s, mode):
+        asg, rfn = inner(s, mode)
         if asg is not None and s[7] > 0 and not forced:        # (word 7: matched cells)
             forced.append(asg)
             asg = dict(asg, flags=1)

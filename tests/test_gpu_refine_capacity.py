@@ -110,12 +110,12 @@ def _window_checks(r_df, m_df, cols, op):
     more than once"""
     from same_amd import windows as W
     from same_amd.api import ref_match_limits
-    from same_amd.incumbent import refine_mode
     from same_amd.window_api import _WindowJob
+    from same_amd.window_mode import WindowMode
 
     import pandas as pd
 
-    refine = refine_mode(op)
+    mode = WindowMode.from_params(op)
     job = _WindowJob(r_df, m_df, cols, None, None, None, op, None, False, None)
     frames, own = job.device_frames(None)
     plan = [w for _p, w in job.todo]
@@ -126,7 +126,7 @@ def _window_checks(r_df, m_df, cols, op):
                 starts[id(w)] = dw.state.fetch(W._W_MATCH).copy()
         multi = 0
         n_win = 0
-        for w, dw in zip(plan, frames.windows(plan, batch=1, refine=refine)):
+        for w, dw in zip(plan, frames.windows(plan, batch=1, mode=mode)):
             if dw.error is not None:
                 continue
             st = dw.state
@@ -157,7 +157,7 @@ def _window_checks(r_df, m_df, cols, op):
             start = np.array([pair_of[(i, int(s0[i]))] if s0[i] >= 0 else -1 for i in range(n)], np.int32)
             prob = rcc.CapProblem(pairs, costs, op["no_match_penalty"] * size, n, n_r, tris, axy, rxy, size, op["delaunay_penalty"],
                                   limit=lim, penalty_coeff=op["penalty_coeff"])
-            want, wst = rcc.refine(prob, start, refine[0])
+            want, wst = rcc.refine(prob, start, mode.rounds)
             assert np.array_equal(want, mp), w
             assert (wst["rounds"], wst["moves"], wst["settled"]) == (rec["rounds"], rec["moves"], rec["settled"])
             multi += int(cnt.max(initial=0) > 1)
@@ -206,8 +206,8 @@ def test_capacity_routes_agree_and_merge():
 def test_assignment_start_with_capacity_and_refinish():
     import same_amd
     from same_amd import windows as W
-    from same_amd.incumbent import refine_mode
     from same_amd.window_api import _WindowJob
+    from same_amd.window_mode import WindowMode
 
     r_df, m_df, cols, op = _section(seed=100, meta=True)
     op = dict(op, ref_metacell_match_multiplier=3, hip_refine="capacity", hip_incumbent="assignment")
@@ -216,12 +216,12 @@ def test_assignment_start_with_capacity_and_refinish():
     assert all(s["mip_objective"] <= s["mip_objective_start"] for s in st)
     assert sum(s["ref_extra_matches"] for s in st) > 0
     # a window sent through same_window_refinish_cap from its assignment gives what the finish call gave
-    refine = refine_mode(op)
+    mode = WindowMode.from_params(op)
     job = _WindowJob(r_df, m_df, cols, None, None, None, op, None, False, None)
     frames, own = job.device_frames(None)
     try:
         plan = [w for _p, w in job.todo]
-        for w, dw in zip(plan, frames.windows(plan, batch=1, incumbent="assignment", refine=refine)):
+        for w, dw in zip(plan, frames.windows(plan, batch=1, mode=mode)):
             if dw.error is not None:
                 continue
             first = dw.state.fetch(W._W_MATCH).copy()
@@ -230,7 +230,7 @@ def test_assignment_start_with_capacity_and_refinish():
             # the search's own result as the start: nothing left to improve, the same matching and record
             pair_of = {(int(i), int(j)): p for p, (i, j) in enumerate(pairs)}
             mp = np.array([pair_of[(i, int(first[i]))] if first[i] >= 0 else -1 for i in range(len(first))], np.int32)
-            match_row, _flag, _stats = dw.state.refinish(mp, op["no_match_penalty"], refine)
+            match_row, _flag, _stats = dw.state.refinish(mp, op["no_match_penalty"], mode)
             again = dw.state.refine
             assert np.array_equal(match_row, dw.match_row)
             assert again["moves"] == 0 and again["settled"] == 1

@@ -260,8 +260,8 @@ def test_device_route_fallback_equals_the_general_route(monkeypatch, refine):
     want, wst = _run(r_df, m_df, cols, A, _route="general")
     inner, forced = W._window_records, []
 
-    def flagged(s, incumbent, refine_):
-        asg, rfn = inner(s, incumbent, refine_)
+    def flagged(s, mode):
+        asg, rfn = inner(s, mode)
         if asg is not None and s[7] > 0 and not forced:        # (word 7: matched cells)
             forced.append(asg)
             asg = dict(asg, flags=1)
@@ -284,11 +284,14 @@ def test_device_route_fallback_equals_the_general_route(monkeypatch, refine):
 
 
 def test_finish_call_refuses_transport_without_a_capacity(monkeypatch):
-    """SAME_INCUMBENT_TRANSPORT through the call that carries no capacity, or with a bad one: SAME_EINVAL and no device work"""
+    """SAME_INCUMBENT_TRANSPORT through the library call that carries no capacity, or with a bad one: SAME_EINVAL and no device work.
+    On the Python side no such call can be made: the VALUE refuses (a transport WindowMode without a capacity raises when it is built,
+    before DeviceWindow.filter_finish is entered)."""
     import ctypes
 
     from same_amd import _lib, synth
     from same_amd import windows as W
+    from same_amd.window_mode import WindowMode
     from scipy.spatial import Delaunay
 
     ctx = _lib.default_context(0)
@@ -315,7 +318,7 @@ def test_finish_call_refuses_transport_without_a_capacity(monkeypatch):
             assert ctx.lib.same_window_filter_finish_cap(*head, ctypes.byref(bad), *outs) == _lib.SAME_EINVAL
         assert ctx.stats() == before
         with pytest.raises(ValueError):
-            st.filter_finish(tris, 25.0, 0, 0.0, 0.0, True, 6.0, incumbent="transport")
+            st.filter_finish(tris, 25.0, 0, 0.0, 0.0, True, 6.0, mode=WindowMode("transport"))
         assert ctx.stats() == before
         good = _lib.WindowCapacity(2, 0, 1.0)
         assert ctx.lib.same_window_filter_finish_cap(*head, ctypes.byref(good), *outs) == 0

@@ -48,8 +48,8 @@ graph).  hip_refine="local" does not go with it (that search holds every referen
 
 Two routes produce the same table (tests/test_gpu_run_same.py::test_incumbent_table_routes_agree):
   device   both frames resident on the GPU, two library calls per window, the incumbent and the sweeps computed where the pairs are
-           (csrc/window_stage.hip, csrc/window_finish.hip); the host triangulates, receives (match, flags) per window and gathers
-           the table's columns ONCE at the end.  Windows are walked by `workers` threads with a context each.
+           (csrc/window_stage.hip, csrc/window_finish.hip); the host triangulates, receives (match, flags) per window, keeps its matched
+           central cells as `windows.FINAL_RECORD`s (what the device's accumulator holds of them) and gathers the table's columns ONCE at the end.  Windows are walked by `workers` threads with a context each.
   general  every window becomes a `PreparedInputs` (either pipeline of same_amd.api) and the incumbent + sweeps run through the
            host-buffer entry points: caller-supplied triangulations (MetaCell inputs), the cell-type-priority filter, inputs the
            sections cannot hold.
@@ -66,6 +66,7 @@ from .api import _Staged, prepare_same_inputs, ref_match_limits
 from .ops import MAX_REF_LIMIT          # noqa: F401  (the bound of every reference's match limit, "capacity" and "transport")
 from .window_api import _WindowJob, _walk_windows
 from .window_mode import INCUMBENTS, REFINE_ROUNDS, REFINES, WindowMode, incumbent_mode, refine_mode, transport_capacity  # noqa: F401
+from .windows import FINAL_RECORD
 
 STAT_KEYS = ("pairs", "triangles", "checked", "flipped", "xy_violations", "area_flips", "matched")
 
@@ -78,8 +79,9 @@ def _default_workers():
 
 
 class _TableBuilder:
-    """The device route's result table.  As the windows come a builder keeps, per window, the section rows of the matched cells inside the
-    central trim (a few small index arrays); the columns are gathered from the caller's frames ONCE, when the pass is over, by `table()`:
+    """The device route's result table.  As the windows come a builder keeps, per window, one `windows.FINAL_RECORD` per matched cell inside
+    the central trim -- the form in which the device's accumulator hands the same rows back; the columns are gathered from the caller's
+    frames ONCE, when the pass is over, by `gather()`:
     the final columns are allocated at their full length and filled slice by slice on `GATHER_THREADS` threads (numpy copies without the
     interpreter lock; the Qhull helpers are idle by then) -- no per-window frames, no concatenation.  Where the frame's own columns are
     float64 (the usual case) the type columns and the coordinates come from the sections' row-major copies: a slice's rows are fetched as
@@ -104,124 +106,94 @@ class _TableBuilder:
         self.mov_size = col(mov, "size") if "size" in mov.columns else None
         self.ref_size = col(ref, "size") if "size" in ref.columns else None
         self.ref_id, self.mov_id = col(ref, self.cid), col(mov, self.cid)
-        self.parts = []
+        self.parts, self.ref_idx = [], []        # per window: its records; with_ref_idx: the rows' indices in its compacted reference frame
 
     def add(self, pos, w, dw, ref_idx=None):
         x, y = dw.axy[:, 0], dw.axy[:, 1]
         tx0, tx1, ty0, ty1 = w["trim"]                                  # central region (src/same.py:565-582), matched cells only
         c = np.flatnonzero((dw.match_row >= 0) & (x >= tx0) & (x < tx1) & (y >= ty0) & (y < ty1))
-        self.parts.append((pos, w["window_id"], dw.rows_m[c], dw.match_row[c], c, None if ref_idx is None else ref_idx[c],
-                           dw.point_flag[c], dw.flip_flag[c]))
+        rec = np.empty(len(c), FINAL_RECORD)
+        rec["a_row"], rec["r_row"], rec["cidx"], rec["wid"], rec["pos"] = dw.rows_m[c], dw.match_row[c], c, w["window_id"], pos
+        rec["flags"] = dw.point_flag[c] | dw.flip_flag[c] << 1          # the accumulator's bits: 1 the XY-order flag, 2 the area flip
+        self.parts.append(rec)
+        if self.with_ref_idx:
+            self.ref_idx.append(ref_idx[c])
 
     @staticmethod
-    def keys(builders):
-        """What the window merge reads of the rows, without their columns: (aligned section row, reference section row, XY-order flag,
-        window id, plan position) per row, the builders' windows laid end to end."""
-        parts = [p for b in builders for p in b.parts]
-        lens = [len(p[2]) for p in parts]
-        cat = lambda q, dt: (np.concatenate([p[q] for p in parts]) if parts else np.zeros(0)).astype(dt, copy=False)
-        return (cat(2, np.int64), cat(3, np.int64), cat(6, bool), np.repeat(np.array([p[1] for p in parts], np.int64), lens),
-                np.repeat(np.array([p[0] for p in parts], np.int64), lens))
+    def rows(builders):
+        """The builders' windows laid end to end (each builder walked a contiguous run of the plan, so this is plan order) -> (their
+        FINAL_RECORDs, with_ref_idx: the rows' `ref_idx`, else None)."""
+        cat = lambda parts, dt: np.concatenate(parts).astype(dt, copy=False) if parts else np.zeros(0, dt)
+        return (cat([p for b in builders for p in b.parts], FINAL_RECORD),
+                cat([r for b in builders for r in b.ref_idx], np.int64) if builders[0].with_ref_idx else None)
 
     @staticmethod
     def table(builders, select=None, plan_pos=None):
-        """The builders' windows laid end to end (each builder walked a contiguous run of the plan, so this is plan order); `select`:
-        these rows of that table only, in this order (the rows the window merge keeps: the other rows' columns are never gathered)."""
-        parts = [p for b in builders for p in b.parts]
-        lens = [len(p[2]) for p in parts]
-        if (int(sum(lens)) if select is None else len(select)) == 0:
-            return pd.DataFrame()
+        """The table of `rows(builders)`; `select`: of these rows only, in this order (the rows the window merge keeps: the other rows'
+        columns are never gathered)."""
         me = builders[0]                 # the sources are the job's: the same for every builder
-        pick = (lambda v: v) if select is None else (lambda v: v[select])
-        cat = lambda q, dt: pick(np.concatenate([p[q] for p in parts])).astype(dt, copy=False)
-        spread = lambda values: pick(np.repeat(np.array(values, np.int64), lens))
-        with_pos = me.job.mine is not None if plan_pos is None else plan_pos
-        return me.gather(cat(2, np.int64), cat(3, np.int64), cat(4, np.int64), cat(5, np.int64) if me.with_ref_idx else None, cat(7, bool),
-                         cat(6, bool), spread([p[1] for p in parts]), spread([p[0] for p in parts]) if with_pos else None)
+        rows, ref_idx = _TableBuilder.rows(builders)
+        if select is not None:
+            rows, ref_idx = rows[select], ref_idx if ref_idx is None else ref_idx[select]
+        return me.gather(rows, ref_idx, me.job.mine is not None if plan_pos is None else plan_pos)
 
-    def gather(self, ra, rr, aligned_idx, ref_idx, triangle_violation, filtered_violation, window_id, plan_pos=None, only=None):
-        """The result table of matched cells (moving section rows `ra` -> reference section rows `rr`): the columns of
-        src/same.py:1264-1278, :1464-1470, gathered from the caller's frames slice by slice on the gather threads.
+    def gather(self, rows, ref_idx=None, with_pos=False, only=None):
+        """The result table of the matched cells `rows` (FINAL_RECORDs: moving section row -> reference section row, the cell's index in its
+        window, window id, plan position, flag bits): the columns of src/same.py:1264-1278, :1464-1470, gathered from the caller's frames
+        slice by slice on the gather threads.  No rows: the empty frame.
         only: gather just these table columns (-> dict of arrays): the ones the device-side gather of `table_from_device` does not cover."""
         from concurrent.futures import ThreadPoolExecutor
 
         from .merge import GATHER_THREADS
 
-        me, n = self, len(ra)
+        me, n = self, len(rows)
+        if n == 0 and only is None:
+            return pd.DataFrame()
+        ra, rr = rows["a_row"].astype(np.int64), rows["r_row"].astype(np.int64)      # contiguous index arrays, made once
         want = (lambda name: True) if only is None else (lambda name: name in only)
-        out = {"aligned_idx": aligned_idx}
-        if ref_idx is not None:
-            out["ref_idx"] = ref_idx
-        new = lambda like: np.empty(n, like.dtype)
-        types_wanted = any(want(ct) for ct in me.cts)
-        xy_wanted = any(want(k) for k in ("X", "Y", "ref_X", "ref_Y"))
-        for ct, src in zip(me.cts, me.type_cols if me.type_block is None else [me.type_block] * len(me.cts)):
-            out[ct] = new(src) if types_wanted else None
-        if not xy_wanted:
-            for k in ("X", "Y", "ref_X", "ref_Y"):
-                out[k] = None
-        elif me.mov_xy is not None:
-            for k in ("X", "Y", "ref_X", "ref_Y"):
-                out[k] = np.empty(n, np.float64)
-        else:
-            (mx, my), (rx, ry) = me.xy_cols
-            out["X"], out["Y"], out["ref_X"], out["ref_Y"] = new(mx), new(my), new(rx), new(ry)
-        cid_r, cid_a = f"Ref_{me.cid}", f"Aligned_{me.cid}"
-        out["size"] = (new(me.mov_size) if me.mov_size is not None else np.ones(n, np.int64)) if want("size") else None
-        out["ref_size"] = (new(me.ref_size) if me.ref_size is not None else np.ones(n, np.int64)) if want("ref_size") else None
-        out[cid_r], out[cid_a] = new(me.ref_id) if want(cid_r) else None, new(me.mov_id) if want(cid_a) else None
-        out["time_limit_reached"] = np.zeros(n, bool)
-        out["triangle_violation"] = triangle_violation
-        out["filtered_violation"] = filtered_violation
-        out["run_time"] = np.zeros(n)
-        out["window_id"] = window_id
-        if plan_pos is not None:
-            out["__plan_pos"] = plan_pos
+        xy_names = ("X", "Y", "ref_X", "ref_Y")
+        # from the sections' row-major blocks: the type columns, the coordinates; column by column (column, its source, the rows to take
+        # of it) whatever has no block.  A frame without `size` is no source: `_result_frame` says what the column holds then.
+        block_types = me.type_block is not None and any(want(ct) for ct in me.cts)
+        block_xy = me.mov_xy is not None and any(want(k) for k in xy_names)
+        singles = [("size", me.mov_size, ra), ("ref_size", me.ref_size, rr), (f"Ref_{me.cid}", me.ref_id, rr),
+                   (f"Aligned_{me.cid}", me.mov_id, ra)]
+        if me.type_block is None:
+            singles += [(ct, col, ra) for ct, col in zip(me.cts, me.type_cols)]
+        if me.mov_xy is None:
+            singles += zip(xy_names, me.xy_cols[0] + me.xy_cols[1], (ra, ra, rr, rr))
+        singles = [(k, src, rows_of) for k, src, rows_of in singles if want(k) and src is not None]
+        out = {k: np.empty(n, src.dtype) for k, src, _rows_of in singles}
+        out.update({k: np.empty(n, np.float64) for k in (me.cts if block_types else []) + (list(xy_names) if block_xy else [])})
 
         def fill(lo):
             hi = min(n, lo + _TableBuilder.SLICE)
             a, r = ra[lo:hi], rr[lo:hi]
             # np.take(src, rows, axis=0) copies whole rows: 3-6x the speed of src[rows] on the (n, 8) / (n, 2) blocks
             take = np.take
-            if not types_wanted:
-                pass
-            elif me.type_block is not None:
+            if block_types:
                 block = take(me.type_block, a, axis=0)       # (rows, T): the commonCT columns in commonCT order
                 for q, ct in enumerate(me.cts):
                     out[ct][lo:hi] = block[:, q]
-            else:
-                for ct, col in zip(me.cts, me.type_cols):
-                    take(col, a, out=out[ct][lo:hi], mode="clip")       # (rows are valid: "clip" only spares numpy its bounce buffer)
-            if not xy_wanted:
-                pass
-            elif me.mov_xy is not None:
+            if block_xy:
                 axy, rxy = take(me.mov_xy, a, axis=0), take(me.ref_xy, r, axis=0)
                 out["X"][lo:hi], out["Y"][lo:hi], out["ref_X"][lo:hi], out["ref_Y"][lo:hi] = axy[:, 0], axy[:, 1], rxy[:, 0], rxy[:, 1]
-            else:
-                (mx, my), (rx, ry) = me.xy_cols
-                for k, col, rows in (("X", mx, a), ("Y", my, a), ("ref_X", rx, r), ("ref_Y", ry, r)):
-                    take(col, rows, out=out[k][lo:hi], mode="clip")
-            if me.mov_size is not None and want("size"):
-                take(me.mov_size, a, out=out["size"][lo:hi], mode="clip")
-            if me.ref_size is not None and want("ref_size"):
-                take(me.ref_size, r, out=out["ref_size"][lo:hi], mode="clip")
-            if want(cid_r):
-                take(me.ref_id, r, out=out[cid_r][lo:hi], mode="clip")
-            if want(cid_a):
-                take(me.mov_id, a, out=out[cid_a][lo:hi], mode="clip")
+            for k, src, rows_of in singles:
+                take(src, rows_of[lo:hi], out=out[k][lo:hi], mode="clip")       # (valid rows: "clip" only spares numpy its bounce buffer)
 
-        gathers_any = types_wanted or xy_wanted or any(want(k) and src is not None for k, src in
-                                                        (("size", me.mov_size), ("ref_size", me.ref_size), (cid_r, me.ref_id),
-                                                         (cid_a, me.mov_id)))
         starts = range(0, n, _TableBuilder.SLICE)
-        if not gathers_any:
-            pass
-        elif len(starts) == 1:
+        if len(starts) == 1 or not out:
             fill(0)
         else:
             with ThreadPoolExecutor(max_workers=GATHER_THREADS) as pool:
                 list(pool.map(fill, starts))
-        return pd.DataFrame(out, copy=False) if only is None else out
+        if only is not None:
+            return out
+        flags = rows["flags"]
+        out.update({"aligned_idx": rows["cidx"].astype(np.int64), "ref_idx": ref_idx, "triangle_violation": (flags & 2) != 0,
+                    "filtered_violation": (flags & 1) != 0, "window_id": rows["wid"].astype(np.int64),
+                    "__plan_pos": rows["pos"].astype(np.int64)})
+        return _result_frame(out, n, me.cts, me.cid, ref_idx is not None, with_pos)
 
     def device_columns_possible(self):
         """the frame's type columns and coordinates are float64 and the type columns distinct: the sections hold exactly their values"""
@@ -243,32 +215,15 @@ class _TableBuilder:
         names = (list(self.cts) + ["X", "Y", "ref_X", "ref_Y"] + [nm for nm, _b, _d in extra["mov"] + extra["ref"]]
                  + ["aligned_idx", "window_id", "__plan_pos"])
         dtypes = [np.float64] * (len(self.cts) + 4) + [d for _n, _b, d in extra["mov"] + extra["ref"]] + [np.int64, np.int64, np.int64]
-        cid_r, cid_a = f"Ref_{self.cid}", f"Aligned_{self.cid}"
-        missing = [k for k in ("size", "ref_size", cid_r, cid_a) if k not in names]
-        host = {}
-        if missing:            # beside the device's gather (which was only enqueued)
-            final = acc.final_rows()
-            host = self.gather(final["a_row"].astype(np.int64), final["r_row"].astype(np.int64), None, None, None, None, None,
-                               only=set(missing))
+        missing = {"size", "ref_size", f"Ref_{self.cid}", f"Aligned_{self.cid}"} - set(names)
+        # beside the device's gather (which was only enqueued)
+        host = self.gather(acc.final_rows(), only=missing) if missing else {}
         with stage("table: wait for the device's columns"):
             acc.ctx.sync()
         with stage("table: the frame over the block"):
-            return self._frame_over(wide, flags, names, dtypes, host, n, with_plan_pos)
-
-    def _frame_over(self, wide, flags, names, dtypes, host, n, with_plan_pos):
-        cid_r, cid_a = f"Ref_{self.cid}", f"Aligned_{self.cid}"
-        dev = {nm: wide[q].view(dt) for q, (nm, dt) in enumerate(zip(names, dtypes))}
-        col = lambda k: dev[k] if k in dev else host[k]
-        out = {"aligned_idx": dev["aligned_idx"]}
-        for k in list(self.cts) + ["X", "Y", "ref_X", "ref_Y", "size", "ref_size", cid_r, cid_a]:
-            out[k] = col(k)
-        out["time_limit_reached"] = np.zeros(n, bool)
-        out["triangle_violation"], out["filtered_violation"] = flags[0].view(bool), flags[1].view(bool)
-        out["run_time"] = np.zeros(n)
-        out["window_id"] = dev["window_id"]
-        if with_plan_pos:
-            out["__plan_pos"] = dev["__plan_pos"]
-        return pd.DataFrame(out, copy=False)
+            cols = {nm: wide[q].view(dt) for q, (nm, dt) in enumerate(zip(names, dtypes))}
+            cols.update(host, triangle_violation=flags[0].view(bool), filtered_violation=flags[1].view(bool))
+            return _result_frame(cols, n, self.cts, self.cid, with_pos=with_plan_pos)
 
 
 def incumbent_of_prepared(prep, commonCT, with_ref_idx=True, ctx=None, use_device=True, mode=None):
@@ -345,22 +300,40 @@ def _match_table(a_df, r_df, ra, rr, commonCT, cid, aligned_idx, ref_idx, triang
     at rows `ra` / `rr` -- a window's own two frames at its own indices, or the CALLER's frames at section rows (the same values: a
     window's frames are rows of the caller's).  Plain indexing: a frame's column may be a strided view of its block, which np.take would
     first copy whole."""
-    out = {"aligned_idx": aligned_idx.astype(np.int64)}
-    if ref_idx is not None:
-        out["ref_idx"] = ref_idx.astype(np.int64)
+    cols = {"aligned_idx": aligned_idx.astype(np.int64), "ref_idx": None if ref_idx is None else ref_idx.astype(np.int64)}
     for ct in list(commonCT) + ["X", "Y"]:
-        out[ct] = a_df[ct].to_numpy()[ra]
+        cols[ct] = a_df[ct].to_numpy()[ra]
     for ct in ("X", "Y"):
-        out[f"ref_{ct}"] = r_df[ct].to_numpy()[rr]
-    out["size"] = a_df["size"].to_numpy()[ra] if "size" in a_df.columns else np.ones(len(ra), np.int64)       # src/same.py:934-940
-    out["ref_size"] = r_df["size"].to_numpy()[rr] if "size" in r_df.columns else np.ones(len(rr), np.int64)
-    out[f"Ref_{cid}"] = r_df[cid].to_numpy()[rr]
-    out[f"Aligned_{cid}"] = a_df[cid].to_numpy()[ra]
-    out["time_limit_reached"] = np.zeros(len(ra), bool)
-    out["triangle_violation"] = np.asarray(triangle_violation).astype(bool)
-    out["filtered_violation"] = np.asarray(filtered_violation).astype(bool)
-    out["run_time"] = np.zeros(len(ra))
-    return pd.DataFrame(out, copy=False)      # the columns are this function's own arrays: no consolidating copy
+        cols[f"ref_{ct}"] = r_df[ct].to_numpy()[rr]
+    cols["size"] = a_df["size"].to_numpy()[ra] if "size" in a_df.columns else None
+    cols["ref_size"] = r_df["size"].to_numpy()[rr] if "size" in r_df.columns else None
+    cols[f"Ref_{cid}"] = r_df[cid].to_numpy()[rr]
+    cols[f"Aligned_{cid}"] = a_df[cid].to_numpy()[ra]
+    cols["triangle_violation"] = np.asarray(triangle_violation).astype(bool)
+    cols["filtered_violation"] = np.asarray(filtered_violation).astype(bool)
+    return _result_frame(cols, len(ra), commonCT, cid, ref_idx is not None)
+
+
+def _result_frame(cols, n, cts, cid, with_ref_idx=False, with_pos=False):
+    """The result table of `n` rows over the arrays `cols` (by column name): the one statement of its column order (module text) and of
+    the columns that are constant without a solver.  No `size` / `ref_size` (absent or None): the frame has no sizes and every cell counts
+    1 (src/same.py:934-940).  No `window_id`: one window's table, which the caller stamps."""
+    size = lambda k: cols[k] if cols.get(k) is not None else np.ones(n, np.int64)
+    out = {"aligned_idx": cols["aligned_idx"]}
+    if with_ref_idx:
+        out["ref_idx"] = cols["ref_idx"]
+    for k in list(cts) + ["X", "Y", "ref_X", "ref_Y"]:
+        out[k] = cols[k]
+    out["size"], out["ref_size"] = size("size"), size("ref_size")
+    out[f"Ref_{cid}"], out[f"Aligned_{cid}"] = cols[f"Ref_{cid}"], cols[f"Aligned_{cid}"]
+    out["time_limit_reached"] = np.zeros(n, bool)
+    out["triangle_violation"], out["filtered_violation"] = cols["triangle_violation"], cols["filtered_violation"]
+    out["run_time"] = np.zeros(n)
+    if "window_id" in cols:
+        out["window_id"] = cols["window_id"]
+    if with_pos:
+        out["__plan_pos"] = cols["__plan_pos"]
+    return pd.DataFrame(out, copy=False)      # the columns are the caller's own arrays: no consolidating copy
 
 
 def _window_table(prep, commonCT, ai, ri, flip_node, pflag, with_ref_idx):
@@ -478,11 +451,13 @@ def sliding_window_incumbent(ref, moving, commonCT=None, outprefix=None, moving_
     return (table, [stats[pos] for pos in sorted(stats)]) if return_stats else table
 
 
-def _merged_rows(job, frames, builders, channel):
-    """The window merge on the device route's keys -> rows of the builders' table that the merged table keeps, in its order."""
+def _merged_rows(job, frames, rows, channel):
+    """The window merge on what the FINAL_RECORDs `rows` of the builders say of their cells -> the rows the merged table keeps, in its
+    order."""
     from . import merge as M
 
-    a_row, r_row, viol, wid, pos = _TableBuilder.keys(builders)
+    a_row, r_row, wid, pos = (rows[k].astype(np.int64) for k in ("a_row", "r_row", "wid", "pos"))
+    viol = (rows["flags"] & 1) != 0
     with stage("merge: cell ids of the rows"):
         (a_code, r_code), unique = frames.id_codes(job.optim_params["cell_id_col"])
         a_ids, r_ids = a_code[a_row], r_code[r_row]
@@ -553,7 +528,15 @@ def _device_route(job, frames, workers, with_ref_idx, triangulator, stats, merge
         [t.join() for t in threads]
         if errors:
             raise errors[0]
-    if accs is not None:
+    # the rows that stay, as FINAL_RECORDs: the builders' (the merge chooses among them on the host) or the accumulator's (the merge chose
+    # on the device; its columns may come from there too) -- then one way from records to the table
+    me, with_pos = builders[0], job.mine is not None and not merge
+    if accs is None:
+        rows, ref_idx = _TableBuilder.rows(builders)
+        if merge:
+            keep = _merged_rows(job, frames, rows, channel)
+            rows, ref_idx = rows[keep], ref_idx if ref_idx is None else ref_idx[keep]
+    else:
         calls0 = accs[0].ctx.stats()
         if merge:
             done = _merge_on_device(job, frames, accs, channel)
@@ -562,25 +545,18 @@ def _device_route(job, frames, workers, with_ref_idx, triangulator, stats, merge
 
             with stage("table rows (accumulated on the device, in plan order)"):
                 done = plain_accumulators(accs)
-        with_pos = job.mine is not None and not merge
-        with stage("table (columns of the rows that stay: by the device into page-locked memory, else on the gather threads)"):
-            if not done.n_final:
-                return pd.DataFrame()
-            me = builders[0]
-            if device_table:
-                table = me.table_from_device(frames, done, with_pos)     # the columns gathered on the device, into page-locked memory
-                if table is not None:
-                    # (the merge counted its own calls; what is new here: the rows laid end to end, the columns' launch and wait)
-                    _count_merge_calls(frames, accs[0].ctx, accs[0].ctx.stats() if merge else calls0, passes=0 if merge else 1)
-                    return table
-            final = done.final_rows()
-            flags = final["flags"]
-            return me.gather(final["a_row"].astype(np.int64), final["r_row"].astype(np.int64), final["cidx"].astype(np.int64), None,
-                             (flags & 2) != 0, (flags & 1) != 0, final["wid"].astype(np.int64),
-                             final["pos"].astype(np.int64) if with_pos else None)
-    select = _merged_rows(job, frames, builders, channel) if merge else None
+        if not done.n_final:
+            return pd.DataFrame()
+        if device_table:
+            with stage("table (columns of the rows that stay: by the device into page-locked memory)"):
+                table = me.table_from_device(frames, done, with_pos)
+            if table is not None:
+                # (the merge counted its own calls; what is new here: the rows laid end to end, the columns' launch and wait)
+                _count_merge_calls(frames, accs[0].ctx, accs[0].ctx.stats() if merge else calls0, passes=0 if merge else 1)
+                return table
+        rows, ref_idx = done.final_rows(), None
     with stage("table (columns gathered on the gather threads)"):
-        table = _TableBuilder.table(builders, select, plan_pos=False if merge else None)
+        table = me.gather(rows, ref_idx, with_pos)
     if job.all_matches:                      # rows of windows finished by an earlier run (resume)
         table = pd.concat(job.all_matches + ([table] if len(table) else []), ignore_index=True)
     return table

@@ -923,6 +923,37 @@ def test_incumbent_table_routes_agree():
             same_amd.sliding_window_incumbent(r_far, far, commonCT=cols, optim_params=dict(op), **kw)
 
 
+def test_incumbent_table_sources_agree(monkeypatch):
+    """The four sources of the incumbent's table side by side on one small job -- the device's columns (default), the accumulator's rows
+    with the host's gather (SAME_TABLE_COLUMNS=host), the builders' rows (window_local_indices=True, less its `ref_idx`) and the general
+    route's per-window tables -- un-merged and merged: the same frame, column list, dtypes and values.  The plan has 4 windows (a 2 x 2
+    grid), whose shared strips hold matched cells."""
+    import same_amd
+    from same_amd import synth
+
+    ref = synth.make_cells(6_000, 3, seed=40)
+    r_df, m_df = synth.to_frame(ref), synth.to_frame(synth.make_jittered(ref, seed=41))
+    m_df["size"] = np.where(np.arange(len(m_df)) % 3 == 0, 2, 1)
+    op = dict(radius=30, knn=6, window_size=700, overlap=200, min_cells_per_window=10)
+    cols = synth.type_columns(3)
+    run = lambda merge, **kw: same_amd.sliding_window_incumbent(r_df, m_df, commonCT=cols, optim_params=dict(op), merge=merge, **kw)
+    for merge in (False, True):
+        monkeypatch.delenv("SAME_TABLE_COLUMNS", raising=False)
+        first, stats = run(merge, _route="device", return_stats=True)
+        local = run(merge, _route="device", window_local_indices=True)
+        general = run(merge, _route="general")
+        monkeypatch.setenv("SAME_TABLE_COLUMNS", "host")
+        host = run(merge, _route="device")
+        assert len(stats) == 4 and first["window_id"].nunique() == 4 and len(first) > 3000
+        assert first["window_id"].dtype == np.int64 and first["size"].dtype == np.int64 and "ref_idx" in local.columns
+        x0 = int(min(r_df["X"].min(), m_df["X"].min())) + 500          # the second column of windows starts here: [x0, x0 + 200) is shared
+        assert ((first["X"] >= x0) & (first["X"] < x0 + 200)).sum() > 300
+        for name, other in (("host", host), ("local", local.drop(columns=["ref_idx"])), ("general", general)):
+            assert list(other.columns) == list(first.columns) and len(other) == len(first), (merge, name)
+            for c in first.columns:
+                assert other[c].dtype == first[c].dtype and np.array_equal(other[c].to_numpy(), first[c].to_numpy()), (merge, name, c)
+
+
 def test_resident_frames_serve_several_jobs(gp, tmp_path, monkeypatch):
     """`resident_frames`: the two frames uploaded and binned once, then jobs with other radii, penalties, window sizes and cost types over
     them -- each result equals the one-off call's; sliding_window_matching takes the same object; foreign frames are refused."""

@@ -144,6 +144,47 @@ def test_table_builder_makes_the_reference_table(float_columns, monkeypatch):
     assert list(sliced.columns) == list(got.columns) and all(sliced[c].dtype == got[c].dtype for c in got.columns) and sliced.equals(got)
 
 
+def test_table_builder_selects_rows_of_two_builders(monkeypatch):
+    """_TableBuilder.table over TWO builders (as two worker threads make them) with `ref_idx`, a `select` and the plan position: the rows
+    `select` names, in its order, of the per-window `_match_table` tables (central trim, window id, plan position) laid end to end --
+    every column, in order, with its dtype."""
+    from same_amd.incumbent import _match_table, _TableBuilder
+    from same_amd.windows import Section
+
+    ref, mov, cts = _frame(300, seed=3), _frame(400, seed=4), ["c0", "c1", "c2"]
+    mov["size"] = np.arange(400) % 3 + 1
+    job = types.SimpleNamespace(ref=ref, moving=mov, commonCT=cts, optim_params={"cell_id_col": "Cell_Num_Old"}, mine=None)
+    sections = (Section.from_frame(ref, cts), Section.from_frame(mov, cts))
+    rng = np.random.default_rng(11)
+    builders = [_TableBuilder(job, sections, with_ref_idx=True) for _ in range(2)]
+    assert _TableBuilder.table(builders, plan_pos=True).equals(pd.DataFrame())          # no window yet
+    tx0, tx1, ty0, ty1 = trim = (50.0, 450.0, 100.0, 500.0)
+    want = []
+    for pos in range(11):
+        dw, w = _fake_window(rng, 400, 300, pos, trim)
+        dw.axy = mov[["X", "Y"]].to_numpy(dtype=np.float64)[dw.rows_m]
+        ref_idx = np.where(dw.match_row >= 0, rng.integers(0, 250, 120), -1)
+        builders[0 if pos < 6 else 1].add(pos, w, dw, ref_idx)
+        x, y = dw.axy[:, 0], dw.axy[:, 1]
+        c = np.flatnonzero((dw.match_row >= 0) & (x >= tx0) & (x < tx1) & (y >= ty0) & (y < ty1))
+        t = _match_table(mov, ref, dw.rows_m[c], dw.match_row[c], cts, "Cell_Num_Old", c, ref_idx[c], dw.flip_flag[c], dw.point_flag[c])
+        t["window_id"] = np.full(len(c), w["window_id"], np.int64)
+        t["__plan_pos"] = np.full(len(c), pos, np.int64)
+        want.append(t)
+    want = pd.concat(want, ignore_index=True)
+    assert len(want) > 300 and want["ref_idx"].dtype == want["window_id"].dtype == want["__plan_pos"].dtype == np.int64
+    perm = np.random.default_rng(12).permutation(len(want))[:len(want) * 2 // 3]        # a strict subset, out of order
+    want = want.iloc[perm].reset_index(drop=True)
+    for slice_rows in (None, 37):
+        if slice_rows is not None:
+            monkeypatch.setattr(_TableBuilder, "SLICE", slice_rows)
+        got = _TableBuilder.table(builders, select=perm, plan_pos=True)
+        assert list(got.columns) == list(want.columns) and len(got) == len(perm)
+        for col in got.columns:
+            assert got[col].dtype == want[col].dtype and np.array_equal(got[col].to_numpy(), want[col].to_numpy()), (slice_rows, col)
+    assert _TableBuilder.table([_TableBuilder(job, sections, with_ref_idx=True)], plan_pos=True).equals(pd.DataFrame())
+
+
 def test_timing_double_installs_and_restores_gurobipy():
     """same_amd.bench_solver_double (bench.py's `api_path`, part b): a do-nothing stand-in for the gurobipy surface run_same touches --
     takes the MIP start as the incumbent, calls the lazy callback once, reports OPTIMAL; install / uninstall leave sys.modules as found."""

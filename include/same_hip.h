@@ -388,7 +388,7 @@ int same_first_candidate_dev(same_ctx *ctx, const int32_t *didx, int64_t rows, i
  *     fallback below): no filter, the filter arguments are ignored; SAME_TRIS_DEVICE the candidates same_window_delaunay left on the
  *     device for each window (every window must have been answered by it since it was staged): no host array, no upload -- the classes,
  *     the keep list and the same-type re-add are decided by the filter's own kernels, with the reference's arithmetic, and out_counts'
- *     near and ORDER TIES mean what they mean there.  NULL simplices and simplex_offsets go with SAME_TRIS_DEVICE and only with it ->
+ *     near and ORDER TIES mean what they mean there; SAME_TRIS_CALLER the triangles same_window_caller_tris left (below).  NULL simplices and simplex_offsets go with SAME_TRIS_DEVICE and only with it ->
  *     - filter_triangles_by_radius on the device (src/helpers.py:233-395: classes :300-330, the keep list, the same-type triangles
  *       added back so that every node keeps one :331-340 / :365-389, in the reference's order); the section's type_id codes play
  *       aligned_df["cell_type"].  Simplices must be distinct as vertex rows (Qhull's are): the re-add pass de-duplicates by triangle,
@@ -445,7 +445,10 @@ enum {
     SAME_WINDOW_SIGNS = 7,        /* int8[triangles]   (after same_window_filter_finish)                            */
     SAME_WINDOW_WEIGHTS = 8,      /* double[triangles] (after same_window_filter_finish)                            */
     SAME_WINDOW_MATCH = 9,        /* int32[kept]: matched reference index in the window or -1 (after finish)       */
-    SAME_WINDOW_TRIANGLES = 10    /* int32[triangles][3]: the kept triangles (after ..._filter_finish)           */
+    SAME_WINDOW_TRIANGLES = 10,   /* int32[triangles][3]: the kept triangles (after ..._filter_finish)           */
+    SAME_WINDOW_CALLER_TRIANGLES = 11, /* int32[selected][3]: the caller's triangles of the window over its kept cells AS STAGED,
+                                          in the caller's order (after same_window_caller_tris)                                  */
+    SAME_WINDOW_STAGED_PAIRS = 12 /* int32[pairs as staged][2]: SAME_WINDOW_PAIRS before same_window_caller_tris removed cells    */
 };
 int same_section_create(same_ctx *ctx, const double *xy, const double *types, int T, const double *size,
                         const int32_t *type_id /* may be NULL */, int64_t n, int cost_f32, same_section **out);
@@ -459,6 +462,7 @@ int same_window_fetch(same_window *window, int what, void *out, int64_t bytes);
 #define SAME_TRIS_SIMPLICES 0   /* host simplices, filtered on the device */
 #define SAME_TRIS_KEPT 1        /* host kept triangles in the reference's order */
 #define SAME_TRIS_DEVICE 2      /* the candidates same_window_delaunay left; simplices and simplex_offsets must be NULL */
+#define SAME_TRIS_CALLER 3      /* the triangles same_window_caller_tris left (a caller's own triangulation); NULL arrays as above */
 #define SAME_INCUMBENT_GREEDY 0
 #define SAME_INCUMBENT_ASSIGNMENT 1
 #define SAME_WINDOW_STATS 15    /* int64 words per window in out_stats */
@@ -497,6 +501,36 @@ int same_window_filter_finish_cap(same_window *const *windows, int n_windows, in
 int same_window_refinish_cap(same_window *window, const int32_t *match_pair, double no_match_penalty, int64_t refine_rounds_cap,
                              double delaunay_penalty, const same_window_capacity *capacity, int32_t *out_match_row,
                              uint8_t *out_point_flag, int64_t *out_stats);
+
+/* ---- a caller's own triangulation on the window path (csrc/window_caller.hip): src/same.py:425-435, :1016-1085 with the frames
+ * resident.  The reference remaps the caller's vertex ids to every window's rows, drops the triangles with a missing vertex, filters
+ * with remove_unconstrained_nodes=True, deletes the unconstrained nodes (no triangle of theirs passes the side and angle tests,
+ * src/helpers.py:323-325, :357-358) with their pairs and renumbers the rest.
+ *   same_caller_tris_create: the triangulation of `moving` as section ROWS, int32[n_tris][3] in the caller's order, uploaded once and
+ *     binned by the section's grid cell of each triangle's first corner (bin the section on the window grid first: the object is bound
+ *     to the grid the section has now).  Every row must lie in [0, rows of the section) -> else SAME_ERANGE before any device work.
+ *     Read-only afterwards: every context of the device may use it.  Destroy it before the section.
+ *   same_window_caller_tris: for each staged window of the batch (ONE wait): the triangles whose three rows are among the window's kept
+ *     aligned cells, as indices into them, in the caller's order and corner order (SAME_WINDOW_CALLER_TRIANGLES) -- only the triangles
+ *     binned in the cells the window's box covers are looked at; the node mask of the filter (radius, angle_enabled, cos_thr, near_tol,
+ *     ignore_same_type as for same_window_filter_finish); then the window WITHOUT its unconstrained nodes: kept rows, XY, sizes, kept
+ *     index, pairs and costs compacted, pair rows and triangle corners renumbered, triangles that name a removed node dropped (none of
+ *     them could be kept).  Every same_window_fetch array and count of the window is the smaller window's from then on
+ *     (SAME_WINDOW_STAGED_PAIRS: the pair list as staged); the reference side is NOT compacted again, and the reference limits of the
+ *     _cap calls are still read over the references the STAGED pair list names.  same_window_filter_finish follows with SAME_TRIS_CALLER.
+ *     out_counts[6 i ..] = {triangles selected, nodes removed, cosines within near_tol of cos_thr, kept cells left, pairs left,
+ *     triangles left}.  A window whose third count is not zero is left AS STAGED (kept cells and pairs: the staged numbers): the caller
+ *     filters its selected triangles on the host and calls again with removed != NULL -- the PREFILTERED form: removed[removed_offsets[i]
+ *     .. removed_offsets[i + 1]) holds one byte per kept cell as staged of window i, non-zero = unconstrained; no classification, the
+ *     third count is 0 -- and finishes with SAME_TRIS_KEPT and its own kept list (renumbered).  removed NULL <=> removed_offsets NULL.
+ *     A window without kept cells, or a triangulation without triangles, launches nothing over an empty grid.  SAME_EINVAL: a window
+ *     not staged, not staged over the triangulation's section, or staged before the section was binned again; bad offsets. */
+typedef struct same_caller_tris same_caller_tris;
+int same_caller_tris_create(same_ctx *ctx, const same_section *moving, const int32_t *tris, int64_t n_tris, same_caller_tris **out);
+void same_caller_tris_destroy(same_caller_tris *tris);
+int same_window_caller_tris(same_window *const *windows, int n_windows, const same_caller_tris *tris, const uint8_t *removed,
+                            const int64_t *removed_offsets, double radius, int angle_enabled, double cos_thr, double near_tol,
+                            int ignore_same_type, int64_t *out_counts);
 
 /* ---- a6 on the window path without the library call --------------------------------------------------------------------------
  * The reference triangulates every window's kept aligned cells with scipy.spatial.Delaunay (Qhull; src/same.py:1023), on the host

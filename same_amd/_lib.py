@@ -114,6 +114,9 @@ _PROTOTYPES = {
     "same_merge_dedup": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, ctypes.POINTER(c_i64)],
     "same_delaunay2d": [c_vp, c_i64, c_vp, c_i64, ctypes.POINTER(c_i64), c_dbl, ctypes.POINTER(c_dbl)],
     "same_window_delaunay": [c_vp, c_int, c_dbl, c_int, c_dbl, c_dbl, c_vp, c_vp],
+    "same_caller_tris_create": [c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(c_vp)],
+    "same_caller_tris_destroy": [c_vp],
+    "same_window_caller_tris": [c_vp, c_int, c_vp, c_vp, c_vp, c_dbl, c_int, c_dbl, c_dbl, c_int, c_vp],
     "same_sparse_assign": [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp],
     "same_sparse_assign_cap": [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_dbl, c_vp, c_vp],
     "same_refine_matching": [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_dbl, c_i64, c_vp, c_vp],
@@ -153,7 +156,7 @@ SAME_EINVAL, SAME_ENOMEM, SAME_EIO, SAME_ENODEV, SAME_ERANGE, SAME_EUNSURE = -22
 # why the device's triangulator refused a set (a mask; include/same_hip.h, same_window_delaunay)
 SAME_DD_FEW_POINTS, SAME_DD_NO_ANGLE, SAME_DD_NONFINITE, SAME_DD_IN_DOUBT, SAME_DD_OVERFLOW = 1, 2, 4, 8, 16
 # what same_window_filter_finish reads its triangles from, what it matches by, the int64 words of its stats record per window
-SAME_TRIS_SIMPLICES, SAME_TRIS_KEPT, SAME_TRIS_DEVICE = 0, 1, 2
+SAME_TRIS_SIMPLICES, SAME_TRIS_KEPT, SAME_TRIS_DEVICE, SAME_TRIS_CALLER = 0, 1, 2, 3
 SAME_INCUMBENT_GREEDY, SAME_INCUMBENT_ASSIGNMENT, SAME_INCUMBENT_TRANSPORT = 0, 1, 2
 SAME_WINDOW_STATS = 15
 SAME_WINDOW_STATS_CAP = 16       # the _cap calls: the 15 words, then sum_j max(0, count_j - 1) of the search's result
@@ -197,6 +200,7 @@ def load():
             L.same_knn_index_destroy.restype = None
             L.same_section_destroy.restype = None
             L.same_window_destroy.restype = None
+            L.same_caller_tris_destroy.restype = None
             if L.same_abi_version() != ABI_VERSION:
                 raise SameHipError(-22, "libsame_hip ABI version mismatch")
             _lib = L

@@ -44,6 +44,8 @@ struct RefineArgs {
     const double *rsize = nullptr;        // the window path's capacity: reference section sizes, at ref_rows[j] for reference j and
     const int32_t *ref_rows = nullptr;    // at ref_row[p] for pair p's; P pairs
     int64_t P = 0, max_matches = 1, multiplier = 0;   // multiplier 0 = None (the frame's largest size)
+    const int32_t *lim_row = nullptr;     // the frame the limits are read over when it is not the pair list's own: lim_P reference rows
+    int64_t lim_P = 0;                    // (a window whose unconstrained nodes went: the pair list as staged)
     // the work arrays (lay)
     int32_t *match = nullptr;             // [n] the search's matching (its result)
     int32_t *count = nullptr;             // [n_r] cells holding each reference

@@ -148,8 +148,10 @@ __global__ __launch_bounds__(LIM_NT) void refine_limit_kernel(Batch<RefineArgs> 
     if (!w.rsize) return;
     double mx = 0.0;
     bool meta = false;
-    for (int64_t p = threadIdx.x; p < w.P; p += LIM_NT) {
-        const double s = w.rsize[w.ref_row[p]];
+    const int32_t *__restrict__ frame = w.lim_row ? w.lim_row : w.ref_row;
+    const int64_t n_frame = w.lim_row ? w.lim_P : w.P;
+    for (int64_t p = threadIdx.x; p < n_frame; p += LIM_NT) {
+        const double s = w.rsize[frame[p]];
         meta = meta || s > 1.0;
         mx = fmax(mx, s);
     }

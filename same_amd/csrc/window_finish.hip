@@ -491,6 +491,8 @@ int prepare_finish(same_window *w, const int32_t *host_tris, int64_t cap_tr, con
             r.rsize = w->ref->size;
             r.ref_rows = w->rows_r;
             r.P = P;
+            r.lim_row = w->lim_row;
+            r.lim_P = w->lim_P;
             r.max_matches = mode.cap.max_matches;
             r.multiplier = mode.cap.multiplier;
         }
@@ -534,6 +536,8 @@ int launch_finish(same_ctx *ctx, same_window *const *ws, FinishPlan *const *ps, 
                 r.ref_row = w->jsec;
                 r.ref_rows = w->rows_r;
                 r.P = w->P;
+                r.lim_row = w->lim_row;
+                r.lim_P = w->lim_P;
                 r.n_r = w->n_r;
                 r.max_matches = c.max_matches;
                 r.multiplier = c.multiplier;
@@ -689,17 +693,18 @@ static int filter_finish(same_window *const *windows, int n_windows, int source,
     same_ctx *ctx = nullptr;
     SAME_TRY(check_batch(windows, n_windows, &ctx));
     SAME_TRY(check_mode(ctx, mode));
-    REQUIRE(ctx, source == SAME_TRIS_SIMPLICES || source == SAME_TRIS_KEPT || source == SAME_TRIS_DEVICE);
+    REQUIRE(ctx, source == SAME_TRIS_SIMPLICES || source == SAME_TRIS_KEPT || source == SAME_TRIS_DEVICE || source == SAME_TRIS_CALLER);
     // SAME_TRIS_DEVICE: every window's simplices are the ones same_window_delaunay left on the device for it (no host array; the offsets
-    // are those of its counts)
-    const bool on_device = source == SAME_TRIS_DEVICE;
+    // are those of its counts).  SAME_TRIS_CALLER: the caller's own triangles, as same_window_caller_tris left them over the window's cells
+    const bool from_caller = source == SAME_TRIS_CALLER;
+    const bool on_device = source == SAME_TRIS_DEVICE || from_caller;
     REQUIRE(ctx, on_device == !simplices && on_device == !simplex_offsets);
     std::vector<int64_t> dd_offsets;
     if (on_device) {
         dd_offsets.assign((size_t)n_windows + 1, 0);
         for (int i = 0; i < n_windows; ++i) {
-            REQUIRE(ctx, windows[i]->dd_ok && windows[i]->staged == 2);
-            dd_offsets[(size_t)i + 1] = dd_offsets[(size_t)i] + windows[i]->n_dd;
+            REQUIRE(ctx, (from_caller ? windows[i]->caller_ok : windows[i]->dd_ok) && windows[i]->staged == 2);
+            dd_offsets[(size_t)i + 1] = dd_offsets[(size_t)i] + (from_caller ? windows[i]->n_caller : windows[i]->n_dd);
         }
         simplex_offsets = dd_offsets.data();
     }
@@ -747,7 +752,7 @@ static int filter_finish(same_window *const *windows, int n_windows, int source,
         w->Tr = 0;
         if (w->n_ua == 0) continue;
         if (Tr && source != SAME_TRIS_KEPT) {
-            const int32_t *raw = on_device ? static_cast<const int32_t *>(w->dd_tris.p) : d_simplices + 3 * simplex_offsets[i];
+            const int32_t *raw = from_caller ? w->caller_out : on_device ? static_cast<const int32_t *>(w->dd_tris.p) : d_simplices + 3 * simplex_offsets[i];
             rc = prepare_filter(w, raw, Tr, ignore_same_type, ensure_min_triangle_per_node, &it.fplan);
             if (rc == SAME_OK) rc = prepare_finish(w, nullptr, Tr, it.fplan.counters + FC_TR, mode, &it.plan);
             if (rc == SAME_OK) {

@@ -136,6 +136,24 @@ struct CopyArgs {
     size_t bytes[2];
 };
 
+// One section's share of a window in window_rows_kernel (window_stage.hip): the candidates of the covered cells, merged ascending.  The
+// caller's triangulation (window_caller.hip) walks its triangles by cell through the same kernel: `order` then lists triangle numbers.
+struct RunDesc {
+    const int32_t *order;      // the section's rows by cell
+    const unsigned *starts;    // cell offsets into `order`
+    const double *xy;          // section XY (box test of the candidates)
+    int nx, cx0, ncx, cy0, ncy;   // covered cells: [cx0, cx0 + ncx) x [cy0, cy0 + ncy), ncx * ncy <= MAX_RUN_CELLS
+    int n_cand;                // rows in those cells (the host knows the cell offsets)
+    int aligned;               // the box is a union of cells: every candidate is inside
+    uint32_t *merged;          // out: the candidates ascending by row (| OUTSIDE where the box test fails)
+    unsigned long long *count; // out, aligned only: n_cand
+};
+struct RowsArgs {
+    RunDesc dm, dr;
+    unsigned blocks_m, blocks;     // blocks [0, blocks_m) walk the moving section's candidates, [blocks_m, blocks) the reference's
+    double bx0, bx1, by0, by1;
+};
+
 // covered cells of a box in a section's grid, and whether the box is exactly their union (section.hip)
 struct Cover {
     int cx0 = 0, ncx = 0, cy0 = 0, ncy = 0;
@@ -237,6 +255,38 @@ struct same_window {
     size_t host_bytes = 0;
     size_t host_finish_off = 0;   // the pinned block: [stage call's copy | finish call's copy | the filter's counters]
     size_t host_filter_off = 0;
+    // the caller's triangulation (window_caller.hip).  same_window_caller_tris leaves the window's triangles in `caller` and, unless a
+    // cosine sits at the threshold, the window WITHOUT its unconstrained nodes: the arrays above then point into `caller`, the stage
+    // call's own are kept in `st0` (a second call with the host's mask starts from them again)
+    double box[4] = {0.0, 0.0, 0.0, 0.0};
+    win::DevBuf caller;
+    int caller_sel = 0, caller_ok = 0;              // sel_tris valid; the window is the compacted one and caller_out its triangles
+    int64_t n_sel = 0, n_caller = 0;                // the window's triangles before / after the removal
+    int32_t *sel_tris = nullptr, *caller_out = nullptr;
+    struct Staged {
+        unsigned long long *counts = nullptr;
+        int32_t *ua = nullptr, *rows_ua = nullptr, *type_c = nullptr, *prow = nullptr, *pairs = nullptr, *jsec = nullptr;
+        double *axy_c = nullptr, *size_c = nullptr, *cost64 = nullptr;
+        int64_t n_ua = 0, P = 0;
+    } st0;
+    // the reference rows of the pair list BEFORE the removal: the frame the model's reference limits are read from is the prune's
+    // (src/same.py:1055-1085 does not compact the reference side again); null: the window's own pair list
+    const int32_t *lim_row = nullptr;
+    int64_t lim_P = 0;
+};
+
+// A caller's triangulation of a moving section, resident (same_caller_tris_create): section rows per corner, in the caller's order, and
+// the triangles binned by the section's grid cell of their FIRST corner (ascending inside a cell) -- a window reads the cells it covers.
+// Read-only after its creation: shared by the worker contexts of its device like a section.  Bound to the grid the section had then.
+struct same_caller_tris {
+    same_ctx *ctx = nullptr;
+    const same_section *mov = nullptr;
+    int64_t n_tris = 0, n_binned = 0;
+    int32_t *tris = nullptr;         // [n_tris][3]
+    win::BinGrid grid;
+    int32_t *order = nullptr;        // [n_binned] triangle numbers by cell
+    unsigned *starts = nullptr;      // [cells + 1]
+    std::vector<unsigned> h_starts;
 };
 
 namespace win {
@@ -246,6 +296,7 @@ int knn_index_for(same_ctx *ctx, const same_section *ref, double radius, std::sh
 Cover cover_of(const same_section *s, const double *box);
 // window_stage.hip
 int launch_copy_back(same_ctx *ctx, const CopyArgs *regions, int n_w);
+int launch_rows(same_ctx *ctx, const RowsArgs *jobs, int n_w);
 int launch_zero(same_ctx *ctx, const ZeroArgs *regions, int n_w);
 int check_batch(same_window *const *windows, int n_windows, same_ctx **out_ctx);
 

@@ -44,24 +44,9 @@ __global__ __launch_bounds__(256) void copy_back_kernel(Batch<CopyArgs> b) {
 }
 
 // ---- rows of a section inside a box, from the cells the box covers ---------------------------------------------------------
-struct RunDesc {               // one section's share of a window
-    const int32_t *order;      // the section's rows by cell
-    const unsigned *starts;    // cell offsets into `order`
-    const double *xy;          // section XY (box test of the candidates)
-    int nx, cx0, ncx, cy0, ncy;   // covered cells: [cx0, cx0 + ncx) x [cy0, cy0 + ncy), ncx * ncy <= MAX_RUN_CELLS
-    int n_cand;                // rows in those cells (the host knows the cell offsets)
-    int aligned;               // the box is a union of cells: every candidate is inside
-    uint32_t *merged;          // out: the candidates ascending by row (| OUTSIDE where the box test fails)
-    unsigned long long *count; // out, aligned only: n_cand
-};
-
+// (RunDesc, RowsArgs: window_internal.h)
 // One thread per candidate: its place in the ascending list = the number of candidates with a smaller row = the sum over the
 // covered cells of a lower bound in that cell's (ascending) run.  No sort, no scan; rows in different cells are distinct.
-struct RowsArgs {
-    RunDesc dm, dr;
-    unsigned blocks_m, blocks;     // blocks [0, blocks_m) walk the moving section's candidates, [blocks_m, blocks) the reference's
-    double bx0, bx1, by0, by1;
-};
 __global__ __launch_bounds__(256) void window_rows_kernel(Batch<RowsArgs> b) {
     __shared__ unsigned lo[MAX_RUN_CELLS], hi[MAX_RUN_CELLS], pref[MAX_RUN_CELLS + 1];
     const RowsArgs &wa = b.w[blockIdx.y];
@@ -365,7 +350,8 @@ void same_window_destroy(same_window *w) {
     if (!w) return;
     (void)hipSetDevice(w->ctx->device);
     (void)hipStreamSynchronize(w->ctx->stream);
-    for (DevBuf *b : {&w->stage, &w->filter, &w->finish, &w->tris, &w->big_mask, &w->full_m, &w->full_r, &w->dd_work, &w->dd_tris}) release(*b);
+    for (DevBuf *b : {&w->stage, &w->filter, &w->finish, &w->tris, &w->big_mask, &w->full_m, &w->full_r, &w->dd_work, &w->dd_tris, &w->caller})
+        release(*b);
     if (w->host) (void)hipHostFree(w->host);
     delete w;
 }
@@ -386,6 +372,18 @@ int launch_copy_back(same_ctx *ctx, const CopyArgs *regions, int n_w) {
     if (most == 0) return SAME_OK;
     const unsigned blocks = (unsigned)std::min<size_t>(64, (most + 4095) / 4096);
     SAME_LAUNCH(ctx, copy_back_kernel, dim3(blocks, (unsigned)n_w), dim3(256), 0, cb);
+    return SAME_OK;
+}
+
+// window_rows_kernel for a group of jobs made elsewhere (window_caller.hip: the caller's triangles of the covered cells, merged ascending)
+int launch_rows(same_ctx *ctx, const RowsArgs *jobs, int n_w) {
+    Batch<RowsArgs> rb{};
+    unsigned most = 0;
+    for (int q = 0; q < n_w; ++q) {
+        rb.w[q] = jobs[q];
+        most = std::max(most, jobs[q].blocks);
+    }
+    if (most) SAME_LAUNCH(ctx, window_rows_kernel, dim3(most, (unsigned)n_w), dim3(256), 0, rb);
     return SAME_OK;
 }
 
@@ -442,6 +440,10 @@ int prepare_stage(same_window *w, const same_section *mov, const same_section *r
     w->cost_f32 = mov->cost_f32;
     w->k = k;
     w->n_m = w->n_r = w->n_ua = w->P = w->Tr = 0;
+    w->caller_sel = w->caller_ok = 0;             // the stage call's arrays are the window's again
+    w->lim_row = nullptr;
+    w->lim_P = 0;
+    for (int q = 0; q < 4; ++q) w->box[q] = box[q];
     // the candidates: rows of the cells the box covers (their number is known here), or a mask over the whole section
     Cover cm = cover_of(mov, box), cr = cover_of(ref, box);
     int64_t cap_m = cm.n_cand, cap_r = cr.n_cand;
@@ -686,6 +688,8 @@ int same_window_fetch(same_window *w, int what, void *out, int64_t bytes) {
     case SAME_WINDOW_WEIGHTS: want = Tr * 8; dev = w->weight; REQUIRE(ctx, w->finished); break;
     case SAME_WINDOW_MATCH: want = n_ua * 4; dev = w->match_loc; REQUIRE(ctx, w->finished); break;
     case SAME_WINDOW_TRIANGLES: want = Tr * 12; dev = w->tris.p; REQUIRE(ctx, w->finished || w->filtered); break;
+    case SAME_WINDOW_CALLER_TRIANGLES: want = w->n_sel * 12; dev = w->sel_tris; REQUIRE(ctx, w->caller_sel); break;
+    case SAME_WINDOW_STAGED_PAIRS: want = (w->caller_ok ? w->st0.P : P) * 8; dev = w->caller_ok ? w->st0.pairs : w->pairs; break;
     default: REQUIRE(ctx, !"unknown same_window_fetch selector");
     }
     REQUIRE(ctx, bytes == want);

@@ -46,13 +46,21 @@ hip_refine="capacity" on top the stats carry `mip_gap` = (mip_objective - object
 from optimal.  The stats also carry `ref_extra_matches_start`, `transport_searches` and `fallback` (the certificate refused; the host solved the expanded
 graph).  hip_refine="local" does not go with it (that search holds every reference to one match).
 
+optim_params["hip_caller_delaunay"] = "device" (opt-in; without the key, None or "host" nothing changes) keeps a CALLER's triangulation
+-- MetaCell objects, `moving_delaunay=` arrays or frames, with or without `moving_delaunay_vertex_col` -- on the device route:
+the triangulation is uploaded once as rows of the moving section, and per batch the device selects and remaps every window's triangles
+in the caller's order, works out the filter's node mask and removes the unconstrained nodes with their pairs (src/same.py:1016-1085;
+csrc/window_caller.hip).  Table and stats are the general route's.  Inputs it refuses
+(window_api.caller_triangulation_refusal: ids not unique in the frame, two triangles with one vertex set, ids that are not integers,
+ignore_knn_if_matched) take the general route as before; `hip_delaunay` is irrelevant there (nothing is triangulated).
+
 Two routes produce the same table (tests/test_gpu_run_same.py::test_incumbent_table_routes_agree):
   device   both frames resident on the GPU, two library calls per window, the incumbent and the sweeps computed where the pairs are
            (csrc/window_stage.hip, csrc/window_finish.hip); the host triangulates, receives (match, flags) per window, keeps its matched
            central cells as `windows.FINAL_RECORD`s (what the device's accumulator holds of them) and gathers the table's columns ONCE at the end.  Windows are walked by `workers` threads with a context each.
   general  every window becomes a `PreparedInputs` (either pipeline of same_amd.api) and the incumbent + sweeps run through the
-           host-buffer entry points: caller-supplied triangulations (MetaCell inputs), the cell-type-priority filter, inputs the
-           sections cannot hold.
+           host-buffer entry points: caller-supplied triangulations (MetaCell inputs) without hip_caller_delaunay="device", the
+           cell-type-priority filter, inputs the sections cannot hold.
 """
 import os
 import threading
@@ -65,7 +73,8 @@ from ._trace import stage
 from .api import _Staged, prepare_same_inputs, ref_match_limits
 from .ops import MAX_REF_LIMIT          # noqa: F401  (the bound of every reference's match limit, "capacity" and "transport")
 from .window_api import _WindowJob, _walk_windows
-from .window_mode import INCUMBENTS, REFINE_ROUNDS, REFINES, WindowMode, incumbent_mode, refine_mode, transport_capacity  # noqa: F401
+from .window_mode import (INCUMBENTS, REFINE_ROUNDS, REFINES, WindowMode, caller_delaunay_route, incumbent_mode,  # noqa: F401
+                          refine_mode, transport_capacity)
 from .windows import FINAL_RECORD
 
 STAT_KEYS = ("pairs", "triangles", "checked", "flipped", "xy_violations", "area_flips", "matched")
@@ -385,10 +394,11 @@ def _device_stats(dw):
 
 def _device_ref_idx(dw):
     """index of every kept aligned cell's matched reference in the window's COMPACTED reference frame (src/utils.py:734-742), -1 = none"""
-    from .windows import _W_MATCH, _W_PAIRS, _W_ROWS_R
+    from .windows import _W_MATCH, _W_ROWS_R, _W_STAGED_PAIRS
 
     st = dw.state
-    pairs, n_box = st.fetch(_W_PAIRS), len(st.fetch(_W_ROWS_R))
+    # (the pair list as staged: the reference frame is the prune's even where a caller's triangulation removed cells and their pairs)
+    pairs, n_box = st.fetch(_W_STAGED_PAIRS), len(st.fetch(_W_ROWS_R))
     used = np.zeros(n_box, bool)
     used[pairs[:, 1]] = True
     m = st.fetch(_W_MATCH)
@@ -415,6 +425,13 @@ def sliding_window_incumbent(ref, moving, commonCT=None, outprefix=None, moving_
                      ignore_precomputed_triangulation, _shard, mode=mode)
     frames, own = job.device_frames(_pipeline, ctx=ctx)
     fast = frames is not None and not job.caller_triangulation and not job.optim_params["ignore_knn_if_matched"]
+    caller = None
+    if frames is not None and job.caller_triangulation and caller_delaunay_route(job.optim_params) == "device":
+        # the caller's triangulation resident beside the moving section -- unless the device route refuses these inputs
+        # (window_api.caller_triangulation_refusal): then the general route runs, as without the key
+        if not job.optim_params["ignore_knn_if_matched"]:
+            caller = frames.caller_tris(job.moving_delaunay, job.vertex_col)
+        fast = caller is not None
     if _route is not None:
         if _route == "device" and not fast:
             raise ValueError("the device route does not apply to these inputs")
@@ -424,11 +441,11 @@ def sliding_window_incumbent(ref, moving, commonCT=None, outprefix=None, moving_
         if merge and job.all_matches:
             raise ValueError("merge=True does not resume from an outprefix that already holds windows")
         if fast:
-            if triangulator is None:
+            if triangulator is None and caller is None:
                 from . import delaunay
 
                 triangulator = delaunay.triangulator_for(job.optim_params)   # optim_params["hip_delaunay"] / $SAME_DELAUNAY
-            table = _device_route(job, frames, workers, window_local_indices, triangulator, stats, merge, _merge_channel, batch)
+            table = _device_route(job, frames, workers, window_local_indices, triangulator, stats, merge, _merge_channel, batch, caller)
         else:
             table = _general_route(job, frames, window_local_indices, stats, ctx)
             if merge:
@@ -477,7 +494,7 @@ def _merged_rows(job, frames, rows, channel):
     return M.merged_part_rows(a_ids, r_ids, viol, wid, pos, seam, channel.rank, channel.tables)
 
 
-def _device_route(job, frames, workers, with_ref_idx, triangulator, stats, merge=False, channel=None, batch=None):
+def _device_route(job, frames, workers, with_ref_idx, triangulator, stats, merge=False, channel=None, batch=None, caller=None):
     n_workers = max(1, int(workers if workers is not None else _default_workers()))
     n_workers = min(n_workers, max(1, len(job.todo)))
     contexts = frames.worker_contexts(n_workers)
@@ -502,9 +519,11 @@ def _device_route(job, frames, workers, with_ref_idx, triangulator, stats, merge
             collector = lambda states, windows: accs[q].collect(states, [w["trim"] for w in windows], [w["window_id"] for w in windows],
                                                                 [pos_of[id(w)] for w in windows])
         for (pos, w), dw in zip(mine, frames.windows([w for _p, w in mine], ctx=contexts[q], triangulator=triangulator,
-                                                     collector=collector, batch=batch, mode=job.mode)):
+                                                     collector=collector, batch=batch, mode=job.mode, caller=caller)):
             if dw.error is not None:
                 raise dw.error
+            if dw.skipped:                   # every pair went with the unconstrained nodes: nothing to match (as the general route)
+                continue
             with stage("table rows (central trim)"):
                 if accs is None:
                     builders[q].add(pos, w, dw, _device_ref_idx(dw) if with_ref_idx else None)

@@ -96,6 +96,60 @@ def codes_of_ids(sorted_distinct_ids, ids):
     return pd.Index(sorted_distinct_ids).get_indexer(np.asarray(ids)).astype(np.int64)
 
 
+def caller_triangulation_rows(moving, moving_delaunay, vertex_col=None):
+    """A caller's triangulation of `moving` for the device route, once per job: -> (int32 (Tr, 3) ROWS of the frame, None), or (None,
+    why it stays on the general route).  The triangulation is normalised as `triangles._as_triangle_array` does; a vertex id is
+    `vertex_col`'s value of a row, or the row's index label (src/same.py:425-435: `__tri_vid`); triangles that name an id the frame does
+    not have are dropped (no window could keep them, src/same.py:262-290); the caller's order of triangles and of corners stays.
+    Refused: ids that are not unique in the frame (the reference's per-window dict keeps the last row of the WINDOW); two triangles with
+    the same vertex set (the device's re-add de-duplicates by triangle, the reference by vertex tuple); ids that are not integers."""
+    from .triangles import _as_triangle_array
+
+    def integral(a):
+        a = np.asarray(a)
+        if a.dtype.kind in "iu":
+            return a.astype(np.int64)
+        if a.dtype.kind == "f" and a.size == np.count_nonzero(np.isfinite(a) & (a == np.floor(a))) and (a.size == 0 or np.abs(a).max() < 2.0**62):
+            return a.astype(np.int64)
+        return None
+
+    if vertex_col is not None and vertex_col not in moving.columns:
+        return None, "aligned_delaunay_vertex_col missing"
+    frame = isinstance(moving_delaunay, pd.DataFrame)
+    raw = np.asarray(moving_delaunay.iloc[:, :3] if frame else moving_delaunay)
+    if raw.size and integral(raw) is None:
+        return None, "the triangulation's vertex ids are not integers"
+    tri = _as_triangle_array(moving_delaunay).astype(np.int64, copy=False).reshape(-1, 3)
+    ids = integral(moving.index.to_numpy() if vertex_col is None else moving[vertex_col].to_numpy())
+    if ids is None:
+        return None, "the frame's vertex ids are not integers"
+    n = len(ids)
+    order = np.argsort(ids, kind="stable")
+    by_id = ids[order]
+    if n > 1 and bool(np.any(by_id[1:] == by_id[:-1])):
+        return None, "the frame's vertex ids are not unique"
+    rows = np.zeros((0, 3), np.int64)
+    if len(tri) and n:
+        at = np.minimum(np.searchsorted(by_id, tri), n - 1)
+        known = by_id[at] == tri
+        rows = order[at][known.all(axis=1)].reshape(-1, 3)
+    if len(rows) > 1 and len(np.unique(np.sort(rows, axis=1), axis=0)) != len(rows):
+        return None, "two triangles have the same vertex set"
+    if len(rows) and (rows.min() < 0 or rows.max() >= n):                # (by construction; nothing is uploaded that was not looked at)
+        return None, "a vertex row outside the frame"
+    return np.ascontiguousarray(rows, dtype=np.int32), None
+
+
+def caller_triangulation_refusal(ref, moving, commonCT, op, moving_delaunay, vertex_col=None):
+    """Why a caller's triangulation does not take the device route of sliding_window_incumbent under
+    optim_params["hip_caller_delaunay"] = "device" (None: it does): a reason `_DeviceFrames.refusal` names, ignore_knn_if_matched (the
+    priority filter walks the pairs on the host), or one of `caller_triangulation_rows`."""
+    why = _DeviceFrames.refusal(ref, moving, commonCT, op, vertex_col)
+    if why is None and op["ignore_knn_if_matched"]:
+        why = "ignore_knn_if_matched"
+    return why if why is not None else caller_triangulation_rows(moving, moving_delaunay, vertex_col)[1]
+
+
 class _DeviceFrames:
     """The two frames of a window loop as sections resident on the device (windows.DeviceSection), binned on the grid on which every
     window box is a union of cells (windows.window_cell_grid).  `windows(plan)` runs the per-window device path over them."""
@@ -145,7 +199,22 @@ class _DeviceFrames:
             return "cell_type missing (priority filter)"
         return None
 
-    def windows(self, plan, triangulate=True, ctx=None, triangulator=None, fetch_triangles=False, collector=None, batch=None, mode=None):
+    def caller_tris(self, moving_delaunay, vertex_col):
+        """The caller's triangulation of the moving frame resident beside its section (windows.DeviceCallerTris), or None where
+        `caller_triangulation_rows` refuses it.  Made once per triangulation object and id column, kept until close(): an object of its
+        own, so what the sections mean to a job without a triangulation does not change; the worker contexts share it like a section."""
+        from .windows import DeviceCallerTris
+
+        known = self.__dict__.setdefault("_caller_tris", {})
+        key = (id(moving_delaunay), vertex_col)
+        if key not in known:
+            rows, _why = caller_triangulation_rows(self.moving, moving_delaunay, vertex_col)
+            # (the caller's object is held with the entry: its id names it for as long as the entry lives)
+            known[key] = (moving_delaunay, None if rows is None else DeviceCallerTris(self.dmov, rows, self.ctx))
+        return known[key][1]
+
+    def windows(self, plan, triangulate=True, ctx=None, triangulator=None, fetch_triangles=False, collector=None, batch=None, mode=None,
+                caller=None):
         from .windows import iter_device_windows
 
         op = self.op
@@ -153,7 +222,7 @@ class _DeviceFrames:
                                    dist_ct_coeff=op["dist_ct_coeff"], min_angle_deg=op.get("min_angle_deg", 15),
                                    ignore_same_type_triangles=op["ignore_same_type_triangles"], no_match_penalty=op["no_match_penalty"],
                                    ctx=self.ctx if ctx is None else ctx, triangulate=triangulate, triangulator=triangulator,
-                                   fetch_triangles=fetch_triangles, collector=collector, batch=batch, mode=mode)
+                                   fetch_triangles=fetch_triangles, collector=collector, batch=batch, mode=mode, caller=caller)
 
     def accumulators(self, contexts, cid):
         """One merge accumulator per worker context (kept with the frames: a pass re-uses the arrays of the last), and the sections' id
@@ -225,6 +294,9 @@ class _DeviceFrames:
         for held in self.__dict__.pop("_table_columns", {}).values():
             for _name, buf, _dt in held["mov"] + held["ref"]:
                 buf.free()
+        for _held, tris in self.__dict__.pop("_caller_tris", {}).values():      # before the section they are binned by
+            if tris is not None:
+                tris.close()
         for c in self._worker_ctx:
             c.close()
         self._worker_ctx = []

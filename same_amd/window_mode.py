@@ -12,6 +12,7 @@ from .params import init_gurobi_params, init_optim_params
 
 INCUMBENTS = ("greedy", "assignment", "transport")          # optim_params["hip_incumbent"]; "greedy" without the key
 REFINES = ("local", "capacity")               # optim_params["hip_refine"]; None without the key
+CALLER_DELAUNAY = (None, "host", "device")    # optim_params["hip_caller_delaunay"]; None without the key
 REFINE_ROUNDS = 32                             # optim_params["hip_refine_rounds"] without the key
 _CODES = dict(zip(INCUMBENTS, (_lib.SAME_INCUMBENT_GREEDY, _lib.SAME_INCUMBENT_ASSIGNMENT, _lib.SAME_INCUMBENT_TRANSPORT)))
 
@@ -55,6 +56,7 @@ class WindowMode:
         the checks of `incumbent_mode`, `refine_mode` and `transport_capacity`, in that order, over one completion of the params."""
         op = _Params.of(optim_params)
         incumbent, search, capacity = incumbent_mode(op, gurobi_params, moving), refine_mode(op), transport_capacity(op)
+        caller_delaunay_route(op)
         if search is None:
             return cls(incumbent, capacity=capacity)
         return cls(incumbent, op["hip_refine"], *search[:2], search[2] if op["hip_refine"] == "capacity" else capacity)
@@ -148,6 +150,15 @@ def incumbent_mode(optim_params, gurobi_params=None, moving=None):
             raise ValueError(f"hip_incumbent='assignment': a no-match cost no_match_penalty * size ({np.nanmax(worst):g}) is not below "
                              f"init_big_m / 2 ({big_m / 2:g}); the sparse problem would differ from the reference's big-M one")
     return mode
+
+
+def caller_delaunay_route(optim_params):
+    """optim_params["hip_caller_delaunay"] checked -> "host" (None or without the key: a caller's triangulation takes the general route
+    of sliding_window_incumbent, window by window on the host) | "device" (it stays on the device route: csrc/window_caller.hip)"""
+    route = (optim_params or {}).get("hip_caller_delaunay")
+    if not (route is None or isinstance(route, str)) or route not in CALLER_DELAUNAY:
+        raise ValueError(f"optim_params['hip_caller_delaunay'] must be None, 'host' or 'device', not {route!r}")
+    return "host" if route is None else route
 
 
 def _capacity_of(full, what):

@@ -341,6 +341,7 @@ def iter_window_arrays(ref, moving, plan, radius=250, knn=8, dist_ct_coeff=1.0, 
 # ---- the window path with the sections resident on the device (csrc/window_stage.hip, csrc/window_finish.hip) -------------
 
 _W_ALIGNED_XY, _W_ALIGNED_ROWS, _W_ROWS_M, _W_ROWS_R, _W_PAIRS, _W_COSTS, _W_KEPT, _W_SIGNS, _W_WEIGHTS, _W_MATCH, _W_TRIANGLES = range(11)
+_W_CALLER_TRIANGLES, _W_STAGED_PAIRS = 11, 12      # SAME_WINDOW_CALLER_TRIANGLES, SAME_WINDOW_STAGED_PAIRS
 
 
 def window_cell_grid(plan_or_grid, window_size, overlap):
@@ -431,21 +432,24 @@ class DeviceWindow:
         self.handle = h
         self.counts = (0, 0, 0, 0)
         self.n_triangles = 0
+        self.n_staged_pairs = self.n_selected = 0      # pairs as staged; the caller's triangles over the staged cells (caller_tris_windows)
         self.assignment = self.refine = None
 
     def stage(self, moving, ref, box, radius, knn, dist_ct_coeff):
         """-> (aligned rows in the box, reference rows in the box, aligned rows kept, pairs)"""
         return stage_windows([self], moving, ref, [box], radius, knn, dist_ct_coeff)[0]
 
-    # what -> (dtype, which count gives the length: 0 aligned in box, 1 refs in box, 2 kept, 3 pairs, 4 triangles, trailing width)
+    # what -> (dtype, which count gives the length: 0 aligned in box, 1 refs in box, 2 kept, 3 pairs, 4 triangles, 5 pairs as staged,
+    # 6 the caller's triangles selected; trailing width)
     _FETCH = {_W_ALIGNED_XY: (np.float64, 2, 2), _W_ALIGNED_ROWS: (np.int32, 2, 0), _W_ROWS_M: (np.int32, 0, 0),
               _W_ROWS_R: (np.int32, 1, 0),
               _W_PAIRS: (np.int32, 3, 2), _W_COSTS: (np.float64, 3, 0), _W_KEPT: (np.int32, 2, 0), _W_SIGNS: (np.int8, 4, 0),
-              _W_WEIGHTS: (np.float64, 4, 0), _W_MATCH: (np.int32, 2, 0), _W_TRIANGLES: (np.int32, 4, 3)}
+              _W_WEIGHTS: (np.float64, 4, 0), _W_MATCH: (np.int32, 2, 0), _W_TRIANGLES: (np.int32, 4, 3),
+              _W_CALLER_TRIANGLES: (np.int32, 6, 3), _W_STAGED_PAIRS: (np.int32, 5, 2)}
 
     def fetch(self, what):
         dtype, which, width = self._FETCH[what]
-        n = self.n_triangles if which == 4 else self.counts[which]
+        n = (self.n_triangles, self.n_staged_pairs, self.n_selected)[which - 4] if which >= 4 else self.counts[which]
         out = np.empty((n, width) if width else (n,), dtype)
         with self.ctx.lock:
             self.ctx.check(self.ctx.lib.same_window_fetch(self.handle, int(what), out.ctypes.data, out.nbytes), "same_window_fetch")
@@ -743,7 +747,66 @@ def stage_windows(states, moving, ref, boxes, radius, knn, dist_ct_coeff):
                                             float(dist_ct_coeff), counts.ctypes.data), "same_window_stage")
     for s, c in zip(states, counts.tolist()):
         s.counts, s.n_triangles = tuple(c), 0
+        s.n_staged_pairs, s.n_selected = c[3], 0
     return [s.counts for s in states]
+
+
+class DeviceCallerTris:
+    """A caller's triangulation of a moving section resident on the device (same_caller_tris_create, csrc/window_caller.hip): `rows`
+    int32 (Tr, 3) section rows in the caller's order (window_api.caller_triangulation_rows), uploaded once and binned by the grid the
+    section has NOW -- bin the section on the window grid first.  Read-only: the worker contexts of the device share it."""
+
+    def __init__(self, dsection, rows, ctx=None):
+        self.ctx = ctx = ops._ctx(ctx)
+        rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, 3)
+        self.n_triangles = len(rows)
+        h = ctypes.c_void_p()
+        with ctx.lock:
+            rc = ctx.lib.same_caller_tris_create(ctx.handle, dsection.handle, rows.ctypes.data if len(rows) else None, len(rows),
+                                                 ctypes.byref(h))
+            if rc != 0 and h.value:
+                ctx.lib.same_caller_tris_destroy(h)
+            ctx.check(rc, "same_caller_tris_create")
+        self.handle = h
+
+    def close(self):
+        if getattr(self, "handle", None) and self.ctx.handle:
+            with self.ctx.lock:
+                self.ctx.lib.same_caller_tris_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def caller_tris_windows(states, caller, radius, angle_enabled, cos_thr, near_tol, ignore_same_type, removed=None):
+    """same_window_caller_tris for a batch of staged windows of one context (one wait): the caller's triangles of every window over its
+    kept cells, the filter's node mask, and the window without its unconstrained nodes (src/same.py:1016-1085).  `removed`: per window a
+    uint8 mask over its kept cells AS STAGED (the prefiltered form: the host filtered).  -> [(selected, removed, near, kept cells left,
+    pairs left, triangles left) per window]; every state's counts are the smaller window's afterwards, unless its near is not 0."""
+    ctx, n = states[0].ctx, len(states)
+    counts = np.zeros((n, 6), np.int64)
+    flat = offsets = None
+    if removed is not None:
+        masks = [np.ascontiguousarray(m, dtype=np.uint8) for m in removed]
+        offsets = np.zeros(n + 1, np.int64)
+        np.cumsum([len(m) for m in masks], out=offsets[1:])
+        flat = np.concatenate(masks) if masks else np.zeros(0, np.uint8)
+        if len(flat) == 0:
+            flat = np.zeros(1, np.uint8)
+    with ctx.lock:
+        ctx.check(ctx.lib.same_window_caller_tris(_handles(states), n, caller.handle, _lib._ptr(flat), _lib._ptr(offsets), float(radius),
+                                                  int(angle_enabled), float(cos_thr), float(near_tol), int(bool(ignore_same_type)),
+                                                  counts.ctypes.data), "same_window_caller_tris")
+    out = []
+    for s, c in zip(states, counts.tolist()):
+        s.n_selected, s.n_triangles = c[0], 0
+        s.counts = (s.counts[0], s.counts[1], c[3], c[4])
+        out.append(tuple(c))
+    return out
 
 
 def _window_records(stats_words, mode):
@@ -752,11 +815,11 @@ def _window_records(stats_words, mode):
 
 
 def filter_finish_windows(states, simplices, radius, angle_enabled, cos_thr, near_tol, ignore_same_type, no_match_penalty,
-                          ensure_min_triangle_per_node=True, prefiltered=False, mode=None):
+                          ensure_min_triangle_per_node=True, prefiltered=False, mode=None, from_caller=False):
     """same_window_filter_finish for a batch (one wait for all of them): `simplices[i]` are window i's Delaunay simplices, or with
     `prefiltered` its kept triangles; `simplices=None` takes the candidates `triangulate_windows` left on the device for every window
-    (each state must have been answered since it was staged).  `mode`: a WindowMode -- the start, the search on it and the model's
-    reference capacities (None: the greedy start alone); one with a capacity goes through same_window_filter_finish_cap.
+    (each state must have been answered since it was staged), or with `from_caller` the triangles `caller_tris_windows` left.
+    `mode`: a WindowMode -- the start, the search on it and the model's reference capacities (None: the greedy start alone); one with a capacity goes through same_window_filter_finish_cap.
     -> [(kept, added back, near, match_row, flag byte, stats dict) per window]; a window with near != 0 has None for the last three.
     Every state's `order_ties` is set to the call's count of places where the answer hangs on the ORDER of the triangles or of their
     corners (include/same_hip.h; of consequence only when the simplices are not Qhull's own), its `assignment` and `refine` to the
@@ -764,7 +827,7 @@ def filter_finish_windows(states, simplices, radius, angle_enabled, cos_thr, nea
     mode = WindowMode.default() if mode is None else mode
     ctx, n = states[0].ctx, len(states)
     if simplices is None:
-        source, flat, offsets = _lib.SAME_TRIS_DEVICE, None, None
+        source, flat, offsets = _lib.SAME_TRIS_CALLER if from_caller else _lib.SAME_TRIS_DEVICE, None, None
     else:
         source = _lib.SAME_TRIS_KEPT if prefiltered else _lib.SAME_TRIS_SIMPLICES
         tris = [ops._tris(t) for t in simplices]
@@ -836,7 +899,8 @@ def _assignment_fallback(state, out, moving, no_match_penalty, mode, ref=None):
             mp = ops.sparse_assign_host(pairs, costs, unmatched, len(unmatched), out.counts[1])
             record = dict(objective=ops.assign_objective(mp, costs, unmatched), fallback=1)
         else:
-            limits = window_ref_limits(ref.size[state.fetch(_W_ROWS_R)], pairs, mode.capacity)
+            # (the limits' frame is the prune's: the references the pair list named as staged, whatever the caller's triangulation removed)
+            limits = window_ref_limits(ref.size[state.fetch(_W_ROWS_R)], state.fetch(_W_STAGED_PAIRS), mode.capacity)
             mp = ops.sparse_transport_host(pairs, costs, unmatched, len(unmatched), out.counts[1], limits, mode.capacity[2])
             obj, extra = ops.transport_objective(mp, pairs, costs, unmatched, out.counts[1], mode.capacity[2], with_extra=True)
             record = dict(objective=obj, ref_extra_matches_start=extra, fallback=1)
@@ -854,10 +918,12 @@ class DeviceWindowResult:
     box, kept, pairs); `state` is the live DeviceWindow until the generator is asked for the first window of the next batch (pairs,
     costs, signs ... through `state.fetch`).  `mode`: the WindowMode the window was finished under.  `assignment` (a start other than
     greedy only): {"objective", "fallback", "rounds"[, "ref_extra_matches_start"]}.  `refine` (with a search only): the search's record
-    of the window's final finish ({"rounds", "moves", "settled", "objective_start", "objective"[, "ref_extra_matches"]})."""
+    of the window's final finish ({"rounds", "moves", "settled", "objective_start", "objective"[, "ref_extra_matches"]}).
+    With a caller's triangulation: `removed` the number of unconstrained nodes that went (everything above describes the window without
+    them); `skipped` true for a window left without pairs, which contributes nothing (no error, nothing else set)."""
 
     __slots__ = ("window", "error", "rows_m", "axy", "triangles", "n_triangles", "match_row", "point_flag", "flip_flag", "stats",
-                 "counts", "state", "assignment", "refine", "mode")
+                 "counts", "state", "assignment", "refine", "mode", "skipped", "removed")
 
     def __init__(self, window, mode=None):
         self.window = window
@@ -897,7 +963,7 @@ class TriangulationCache(QhullTriangulator):
 
 def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dist_ct_coeff=1.0, min_angle_deg=15,
                         ignore_same_type_triangles=True, no_match_penalty=100.0, ctx=None, fetch_triangles=False, triangulator=None,
-                        triangulate=True, batch=None, collector=None, mode=None):
+                        triangulate=True, batch=None, collector=None, mode=None, caller=None):
     """The window path of `iter_window_arrays` + the greedy incumbent and the three sweeps, with both sections resident on the
     device (`dref`, `dmoving`: DeviceSections of `ref`, `moving`): per window the host only triangulates (Qhull helpers, windows
     ahead as before) and receives the match; the triangle filter runs on the device too, unless a cosine sits within 8 ulp of the
@@ -915,6 +981,13 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
     (api.sliding_window_matching with a caller's triangulation) and reads pairs / costs through `state.fetch`.
     `collector(states, windows)` is called once per finished batch with its windows' live states (the window merge's accumulator:
     MergeAccumulator.collect).
+    `caller`: a DeviceCallerTris of `dmoving` -- the triangulation source that needs no triangulator (`triangulator`, and with it
+    optim_params["hip_delaunay"], is irrelevant then: nothing is triangulated).  Right after a batch's stage call ONE more call selects
+    and remaps every window's triangles, works out the filter's node mask and leaves the window without its unconstrained nodes
+    (caller_tris_windows; src/same.py:1016-1085); rows_m, axy, counts and everything later describe that smaller window, and the finish
+    call filters the caller's triangles where they are.  A window left without pairs is yielded with `.skipped` (src/same.py's loop gets
+    an empty table from it); one with a cosine at the threshold has triangles AND mask re-decided on the host and goes on through the
+    prefiltered forms of both calls.
     `mode`: a WindowMode (None: the greedy start alone).  A window whose optimal start the device does not certify is solved again on
     the host (ops.sparse_assign_host, ops.sparse_transport_host) and finished again under that matching; every later finish of a window
     (that fallback, a re-finish with scipy's simplices) runs the mode's search again: `result.refine` holds the last one's counts."""
@@ -930,8 +1003,8 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
     angle_enabled, cos_thr = cos_threshold(min_angle_deg)
     near_tol = float(8 * np.spacing(abs(cos_thr))) if (angle_enabled and np.isfinite(cos_thr)) else 0.0
     tri = QHULL if triangulator is None else triangulator
-    depth = int(tri.lookahead())
-    if tri.warm:
+    depth = 0 if caller is not None else int(tri.lookahead())
+    if tri.warm and caller is None:
         qhull_pool.warm(min(depth, len(plan)))
     B = max(1, min(int(batch if batch is not None else os.environ.get("SAME_WINDOW_BATCH", "8")), WINDOW_BATCH_MAX, max(len(plan), 1)))
     if batch is None and depth > 0:
@@ -966,9 +1039,21 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
         except BaseException:
             free.extend(states)                       # a refused batch (SAME_EINVAL ...) must not take its states out of the pool
             raise
+        if caller is not None:
+            try:
+                with marked("caller's triangles: select + remap + node mask + second compaction (device)"):
+                    caller_front([(out, st) for out, st, c in zip(outs, states, counts) if c[3] != 0])
+                counts = [st.counts for st in states]
+            except BaseException:
+                free.extend(states)
+                raise
         staged = []
         for q, (out, state) in enumerate(zip(outs, states)):
             out.counts = counts[q]
+            if out.skipped:
+                free.append(state)
+                staged.append((out, None, None))
+                continue
             if out.counts[3] == 0:
                 free.append(state)
                 out.error = ValueError("No valid_pairs after KNN filtering. Increase radius and/or knn.")
@@ -977,7 +1062,7 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
             ticket = None
             try:
                 out.rows_m, out.axy = state.fetch(_W_ALIGNED_ROWS), state.fetch(_W_ALIGNED_XY)
-                if triangulate:
+                if triangulate and caller is None:
                     with marked("triangulate (hand-over; waits for a free helper)"):
                         ticket = tri.submit(out.axy, key=out.window.get("window_id"))
             except BaseException:
@@ -987,19 +1072,48 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
             staged.append((out, state, ticket))
         return staged
 
-    def finish_batch(group):
-        """filter + signs + incumbent + sweeps of the staged windows of `group`, by ONE library call (+ one per window whose filter met a
-        cosine at the threshold)"""
-        todo = [(out, state, ticket) for out, state, ticket in group if state is not None]
-        for out, state, _t in todo:
-            out.state, out.n_triangles = state, 0
-        if not triangulate or not todo:
+    def caller_front(pairs_of):
+        """the staged windows [(result, state)] that have pairs: their triangles from `caller`, their unconstrained nodes gone"""
+        if not pairs_of:
             return
-        states, tickets = [st for _o, st, _t in todo], [t for _o, _s, t in todo]
+        states = [st for _o, st in pairs_of]
+        filt = (radius, angle_enabled, cos_thr, near_tol, ignore_same_type_triangles)
+        got = caller_tris_windows(states, caller, *filt)
+        for q, (out, state) in enumerate(pairs_of):
+            if got[q][2]:
+                with marked("triangle filter (host: a cosine at the threshold)"):
+                    axy0, rows0, tris0 = state.fetch(_W_ALIGNED_XY), state.fetch(_W_ALIGNED_ROWS), state.fetch(_W_CALLER_TRIANGLES)
+                    tid = moving.type_id[rows0] if (ignore_same_type_triangles and moving.type_id is not None) else None
+                    kept, gone = filter_triangles_by_radius(axy0, tris0, radius, ignore_same_type_triangles=ignore_same_type_triangles,
+                                                            remove_unconstrained_nodes=True, min_angle_deg=min_angle_deg, verbose=False,
+                                                            ctx=ctx, _rows_as_array=True, _type_id=tid)
+                    mask = np.zeros(len(rows0), np.uint8)
+                    mask[sorted(gone)] = 1
+                    got[q] = caller_tris_windows([state], caller, *filt, removed=[mask])[0]
+                    kept = np.asarray(kept).reshape(-1, 3)
+                    kept = kept[(mask[kept] == 0).all(axis=1)] if len(kept) else kept        # src/same.py:1076-1078
+                    out.triangles = (np.cumsum(mask == 0) - 1)[kept].astype(np.int32).reshape(-1, 3)
+            out.removed = got[q][1]
+            out.skipped = got[q][4] == 0          # every node unconstrained, or the removed ones held every pair
+
+    def finish_callers(todo, states, args):
+        """the finish call over the caller's triangles, which are on the device (SAME_TRIS_CALLER); a window the host filtered
+        (caller_front) brings its kept list.  -> (result per window, no simplices)"""
+        with marked("filter + signs + incumbent + sweeps (device)"):
+            mine = [q for q, (o, _s, _t) in enumerate(todo) if o.triangles is None]
+            res = dict(zip(mine, filter_finish_windows([states[q] for q in mine], None, *args, mode=mode, from_caller=True) if mine else []))
+            for q, (o, st, _t) in enumerate(todo):
+                if o.triangles is not None:
+                    res[q] = (len(o.triangles), 0, 0) + tuple(st.finish(o.triangles, no_match_penalty, mode))
+        if any(r[2] for r in res.values()):        # (the node mask's kernel classifies the same corners with the same expressions)
+            raise RuntimeError("a cosine at the angle threshold that same_window_caller_tris did not report")
+        return res, [None] * len(todo)
+
+    def finish_triangulated(states, tickets, args):
+        """the finish call over the triangulator's answers -> (result per window, simplices per window)"""
         tri.before_finish(states, tickets, radius, angle_enabled, cos_thr)
         with marked("triangulate (wait for helper)"):
             tris = [ticket.result() for ticket in tickets]
-        args = (radius, angle_enabled, cos_thr, near_tol, ignore_same_type_triangles, no_match_penalty)
         with marked("filter + signs + incumbent + sweeps (device)"):
             # candidates the device made stay there (simplices None); every other window brings its simplices
             mine = [q for q, t in enumerate(tris) if t is None]
@@ -1015,6 +1129,19 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
                 with marked("order ties: the window again with Qhull's simplices"):
                     tris[q] = ticket.qhull()
                     res[q] = filter_finish_windows([state], [tris[q]], *args, mode=mode)[0]
+        return res, tris
+
+    def finish_batch(group):
+        """filter + signs + incumbent + sweeps of the staged windows of `group`, by ONE library call (+ one per window whose filter met a
+        cosine at the threshold)"""
+        todo = [(out, state, ticket) for out, state, ticket in group if state is not None]
+        for out, state, _t in todo:
+            out.state, out.n_triangles = state, 0
+        if not triangulate or not todo:
+            return
+        states, tickets = [st for _o, st, _t in todo], [t for _o, _s, t in todo]
+        args = (radius, angle_enabled, cos_thr, near_tol, ignore_same_type_triangles, no_match_penalty)
+        res, tris = finish_callers(todo, states, args) if caller is not None else finish_triangulated(states, tickets, args)
         for q, (out, state, _t) in enumerate(todo):
             _kept, _added, near, match_row, cell_flags, stats = res[q]
             if near:

@@ -448,7 +448,8 @@ enum {
     SAME_WINDOW_TRIANGLES = 10,   /* int32[triangles][3]: the kept triangles (after ..._filter_finish)           */
     SAME_WINDOW_CALLER_TRIANGLES = 11, /* int32[selected][3]: the caller's triangles of the window over its kept cells AS STAGED,
                                           in the caller's order (after same_window_caller_tris)                                  */
-    SAME_WINDOW_STAGED_PAIRS = 12 /* int32[pairs as staged][2]: SAME_WINDOW_PAIRS before same_window_caller_tris removed cells    */
+    SAME_WINDOW_STAGED_PAIRS = 12 /* int32[pairs as staged][2]: SAME_WINDOW_PAIRS before same_window_priority_pairs filtered the list
+                                     and same_window_caller_tris removed cells                                                  */
 };
 int same_section_create(same_ctx *ctx, const double *xy, const double *types, int T, const double *size,
                         const int32_t *type_id /* may be NULL */, int64_t n, int cost_f32, same_section **out);
@@ -531,6 +532,30 @@ void same_caller_tris_destroy(same_caller_tris *tris);
 int same_window_caller_tris(same_window *const *windows, int n_windows, const same_caller_tris *tris, const uint8_t *removed,
                             const int64_t *removed_offsets, double radius, int angle_enabled, double cos_thr, double near_tol,
                             int ignore_same_type, int64_t *out_counts);
+
+/* ---- the cell-type-priority prune on the window path (csrc/window_priority.hip): src/knn_utils.py:28-78, switched by
+ * optim_params["ignore_knn_if_matched"] at src/same.py:974-976, with the frames resident.  The reference re-sorts every aligned row's
+ * pruned list by distance (stable) and walks the rows in ascending order: a row whose nearest reference has its cell type and has not been
+ * claimed by an earlier row keeps that one pair and claims the reference; every other row keeps all its pairs.  Closed form: among the
+ * rows whose nearest reference j carries their label, the lowest row gets j.
+ *   same_section_set_label_codes: codes[row] of the section's cell type LABELS, int32[rows], made JOINTLY over the two sections of a job so
+ *     that equal non-negative codes <=> labels that compare equal (a label that equals nothing -- NaN -- gets a negative code).  A slot of
+ *     its own: same_section_set_codes (the window merge's id codes) is not touched.  Set it before the first same_window_priority_pairs call
+ *     over the section; setting it again waits for the device.  codes NULL only for a section without rows.
+ *   same_window_priority_pairs: for each staged window of the batch (ONE wait): d = sqrt(dx*dx + dy*dy) of every pair in fp64, each
+ *     operation rounded to nearest; the pair's stable rank in its row (#{q of the row: d_q < d_p, or d_q == d_p and q earlier}); rows whose
+ *     rank-0 reference has their label code bid for it, the lowest row wins; a winner keeps its nearest pair, every other row all its
+ *     pairs in rank order; pairs, their reference rows and costs are compacted into a second set of arrays.  SAME_WINDOW_PAIRS,
+ *     SAME_WINDOW_COSTS and the pair count are the filtered list's from then on; the kept aligned cells do not change (every one keeps a
+ *     pair), the reference side is NOT compacted again (src/knn_utils.py:78), SAME_WINDOW_STAGED_PAIRS stays the list as staged and the
+ *     reference limits of the _cap calls are still read over the references IT names -- also after a same_window_caller_tris that follows.
+ *     Call it right after same_window_stage, before same_window_delaunay / same_window_caller_tris / same_window_filter_finish.
+ *     out_counts[4 i ..] = {pairs staged, pairs left, rows that kept one pair, rows that kept all}.  A window without pairs launches
+ *     nothing over an empty grid (its counts are 0).  SAME_EINVAL before any device work: a window not staged, staged over sections
+ *     without label codes, staged before a section was binned again, or already filtered (by this call, same_window_caller_tris or
+ *     same_window_filter_finish). */
+int same_section_set_label_codes(same_section *section, const int32_t *codes);
+int same_window_priority_pairs(same_window *const *windows, int n_windows, int64_t *out_counts);
 
 /* ---- a6 on the window path without the library call --------------------------------------------------------------------------
  * The reference triangulates every window's kept aligned cells with scipy.spatial.Delaunay (Qhull; src/same.py:1023), on the host

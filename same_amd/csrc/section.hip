@@ -177,6 +177,7 @@ int bin_section(same_ctx *ctx, same_section *s, double x0, double y0, double cw,
     s->starts = starts;
     s->h_starts.swap(h_starts);
     s->n_binned = n_binned;
+    ++s->bins;
     return SAME_OK;
 }
 
@@ -320,6 +321,7 @@ void same_section_destroy(same_section *s) {
     if (s->size) (void)hipFree(s->size);
     if (s->type_id) (void)hipFree(s->type_id);
     if (s->id_codes) (void)hipFree(s->id_codes);
+    if (s->label_codes) (void)hipFree(s->label_codes);
     if (s->order) (void)hipFree(s->order);
     if (s->starts) (void)hipFree(s->starts);
     delete s;

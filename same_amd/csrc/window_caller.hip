@@ -213,8 +213,8 @@ int prepare_caller(same_window *w, const same_caller_tris *ct, bool use_type, Ca
     same_ctx *ctx = w->ctx;
     if (w->caller_ok) turn_to(w, w->st0);          // a second call (the host's mask) starts from the stage call's arrays again
     w->caller_ok = w->caller_sel = 0;
-    w->lim_row = nullptr;
-    w->lim_P = 0;
+    w->lim_row = w->prio_ok ? w->pr_jsec : nullptr;        // (a priority prune before this call: the frame stays the list as STAGED)
+    w->lim_P = w->prio_ok ? w->pr_P : 0;
     w->st0 = staged_of(w);
     const int64_t n0 = w->n_ua, P0 = w->P, cap_m = w->cap_m;
     // the candidates: the triangles binned in the cells the box covers (their number is known here), or every triangle of the job where
@@ -501,8 +501,8 @@ int same_window_caller_tris(same_window *const *windows, int n_windows, const sa
         turn_to(w, cp.next);
         w->n_caller = n_left;
         w->caller_ok = 1;
-        w->lim_row = w->st0.jsec;
-        w->lim_P = w->st0.P;
+        w->lim_row = w->prio_ok ? w->pr_jsec : w->st0.jsec;
+        w->lim_P = w->prio_ok ? w->pr_P : w->st0.P;
         w->dd_ok = 0;
         w->filtered = w->finished = 0;
         w->Tr = 0;

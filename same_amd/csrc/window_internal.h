@@ -31,7 +31,8 @@
 //       the lock is let go (hipFree waits for the device).
 //
 //   Nothing else of a section changes after same_section_create (xy, types, sizes, type codes, id codes are written once, before the
-//   handle is handed out; same_section_set_codes must precede the first collect call that reads the codes).
+//   handle is handed out; same_section_set_codes must precede the first collect call that reads the codes, same_section_set_label_codes
+//   the first same_window_priority_pairs call).
 //   same_section_destroy expects that no call is using the section (it waits for the device, not for threads).
 #pragma once
 #include <algorithm>
@@ -212,6 +213,9 @@ struct same_section {
     int32_t *type_id = nullptr;  // [n] codes of the cell type (equal type <=> equal code), or none
     int32_t *id_codes = nullptr; // [n] rank of the row's cell id among the frame's ids (same_section_set_codes), or none: a row's code is its number
     int64_t n_codes = 0;
+    int32_t *label_codes = nullptr; // [n] codes of the cell_type LABELS, joint over the two frames of a job (same_section_set_label_codes), or
+                                    // none: equal non-negative codes <=> labels that compare equal (the cell-type-priority prune)
+    unsigned long long bins = 0;    // how often the grid below was replaced (under grid_lock): a window remembers the numbers it was staged at
     // the grid of cells (same_section_bin)
     win::BinGrid grid;
     int32_t *order = nullptr;        // [n_binned] rows by cell, ascending inside a cell
@@ -273,6 +277,14 @@ struct same_window {
     // (src/same.py:1055-1085 does not compact the reference side again); null: the window's own pair list
     const int32_t *lim_row = nullptr;
     int64_t lim_P = 0;
+    // the cell-type-priority prune (window_priority.hip).  same_window_priority_pairs leaves the filtered pair list in `prio` and turns
+    // prow / pairs / jsec / cost64 to it; the list as staged stays where the stage call put it (pr_*: what SAME_WINDOW_STAGED_PAIRS and
+    // the reference limits go on reading).  bins_*: the sections' `bins` when the window was staged
+    win::DevBuf prio;
+    int prio_ok = 0;
+    const int32_t *pr_pairs = nullptr, *pr_jsec = nullptr;
+    int64_t pr_P = 0;
+    unsigned long long bins_m = 0, bins_r = 0;
 };
 
 // A caller's triangulation of a moving section, resident (same_caller_tris_create): section rows per corner, in the caller's order, and

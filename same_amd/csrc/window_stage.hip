@@ -350,7 +350,7 @@ void same_window_destroy(same_window *w) {
     if (!w) return;
     (void)hipSetDevice(w->ctx->device);
     (void)hipStreamSynchronize(w->ctx->stream);
-    for (DevBuf *b : {&w->stage, &w->filter, &w->finish, &w->tris, &w->big_mask, &w->full_m, &w->full_r, &w->dd_work, &w->dd_tris, &w->caller})
+    for (DevBuf *b : {&w->stage, &w->filter, &w->finish, &w->tris, &w->big_mask, &w->full_m, &w->full_r, &w->dd_work, &w->dd_tris, &w->caller, &w->prio})
         release(*b);
     if (w->host) (void)hipHostFree(w->host);
     delete w;
@@ -443,6 +443,11 @@ int prepare_stage(same_window *w, const same_section *mov, const same_section *r
     w->caller_sel = w->caller_ok = 0;             // the stage call's arrays are the window's again
     w->lim_row = nullptr;
     w->lim_P = 0;
+    w->prio_ok = 0;                               // ... and its pair list the only one
+    w->pr_pairs = w->pr_jsec = nullptr;
+    w->pr_P = 0;
+    w->bins_m = mov->bins;                        // (the caller holds both grid locks)
+    w->bins_r = ref->bins;
     for (int q = 0; q < 4; ++q) w->box[q] = box[q];
     // the candidates: rows of the cells the box covers (their number is known here), or a mask over the whole section
     Cover cm = cover_of(mov, box), cr = cover_of(ref, box);
@@ -689,7 +694,10 @@ int same_window_fetch(same_window *w, int what, void *out, int64_t bytes) {
     case SAME_WINDOW_MATCH: want = n_ua * 4; dev = w->match_loc; REQUIRE(ctx, w->finished); break;
     case SAME_WINDOW_TRIANGLES: want = Tr * 12; dev = w->tris.p; REQUIRE(ctx, w->finished || w->filtered); break;
     case SAME_WINDOW_CALLER_TRIANGLES: want = w->n_sel * 12; dev = w->sel_tris; REQUIRE(ctx, w->caller_sel); break;
-    case SAME_WINDOW_STAGED_PAIRS: want = (w->caller_ok ? w->st0.P : P) * 8; dev = w->caller_ok ? w->st0.pairs : w->pairs; break;
+    case SAME_WINDOW_STAGED_PAIRS:
+        want = (w->prio_ok ? w->pr_P : w->caller_ok ? w->st0.P : P) * 8;
+        dev = w->prio_ok ? w->pr_pairs : w->caller_ok ? w->st0.pairs : w->pairs;
+        break;
     default: REQUIRE(ctx, !"unknown same_window_fetch selector");
     }
     REQUIRE(ctx, bytes == want);

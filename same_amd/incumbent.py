@@ -52,7 +52,17 @@ the triangulation is uploaded once as rows of the moving section, and per batch 
 in the caller's order, works out the filter's node mask and removes the unconstrained nodes with their pairs (src/same.py:1016-1085;
 csrc/window_caller.hip).  Table and stats are the general route's.  Inputs it refuses
 (window_api.caller_triangulation_refusal: ids not unique in the frame, two triangles with one vertex set, ids that are not integers,
-ignore_knn_if_matched) take the general route as before; `hip_delaunay` is irrelevant there (nothing is triangulated).
+ignore_knn_if_matched without hip_priority_prune="device") take the general route as before; `hip_delaunay` is irrelevant there
+(nothing is triangulated).
+
+optim_params["hip_priority_prune"] = "device" (opt-in; without the key, None or "host" nothing changes, and without
+ignore_knn_if_matched the key means nothing) keeps a job with ignore_knn_if_matched=True -- the cell-type-priority prune,
+src/knn_utils.py:5-78 -- on the device route: the frames' `cell_type` labels are coded jointly and uploaded once, and per batch one call
+right after the stage call ranks every row's pairs by distance, lets the rows whose nearest reference has their label bid for it (the
+lowest row wins and keeps that one pair, every other row keeps all) and compacts the pair list (csrc/window_priority.hip).
+Everything behind it -- hip_incumbent, hip_refine, hip_delaunay, hip_caller_delaunay, merge=True, ranks -- sees the smaller list; the
+reference limits and `ref_idx` still read the list as staged.  Table and stats are the general route's; `pairs` is the filtered count
+and each window's stats gain `pairs_staged`, `priority_rows` (rows that kept one pair) and `keep_all_rows`.
 
 Two routes produce the same table (tests/test_gpu_run_same.py::test_incumbent_table_routes_agree):
   device   both frames resident on the GPU, two library calls per window, the incumbent and the sweeps computed where the pairs are
@@ -60,7 +70,7 @@ Two routes produce the same table (tests/test_gpu_run_same.py::test_incumbent_ta
            central cells as `windows.FINAL_RECORD`s (what the device's accumulator holds of them) and gathers the table's columns ONCE at the end.  Windows are walked by `workers` threads with a context each.
   general  every window becomes a `PreparedInputs` (either pipeline of same_amd.api) and the incumbent + sweeps run through the
            host-buffer entry points: caller-supplied triangulations (MetaCell inputs) without hip_caller_delaunay="device", the
-           cell-type-priority filter, inputs the sections cannot hold.
+           cell-type-priority filter without hip_priority_prune="device", inputs the sections cannot hold.
 """
 import os
 import threading
@@ -72,9 +82,9 @@ from . import ops
 from ._trace import stage
 from .api import _Staged, prepare_same_inputs, ref_match_limits
 from .ops import MAX_REF_LIMIT          # noqa: F401  (the bound of every reference's match limit, "capacity" and "transport")
-from .window_api import _WindowJob, _walk_windows
+from .window_api import _WindowJob, _walk_windows, _window_error
 from .window_mode import (INCUMBENTS, REFINE_ROUNDS, REFINES, WindowMode, caller_delaunay_route, incumbent_mode,  # noqa: F401
-                          refine_mode, transport_capacity)
+                          priority_prune_route, refine_mode, transport_capacity)
 from .windows import FINAL_RECORD
 
 STAT_KEYS = ("pairs", "triangles", "checked", "flipped", "xy_violations", "area_flips", "matched")
@@ -387,9 +397,12 @@ def _mode_stats(mode, start, search):
 def _device_stats(dw):
     """a window's stats record (STAT_KEYS) from what the device counted"""
     st = dw.stats
-    return {"pairs": dw.counts[3], "triangles": dw.n_triangles, "checked": st["checked"], "flipped": st["flipped"],
-            "xy_violations": st["xy_violations"], "area_flips": st["area_flips"], "matched": st["matched"],
-            **_mode_stats(dw.mode, dw.assignment, dw.refine)}
+    rec = {"pairs": dw.counts[3], "triangles": dw.n_triangles, "checked": st["checked"], "flipped": st["flipped"],
+           "xy_violations": st["xy_violations"], "area_flips": st["area_flips"], "matched": st["matched"],
+           **_mode_stats(dw.mode, dw.assignment, dw.refine)}
+    if dw.priority is not None:       # the priority prune ran on the device: `pairs` is what it left
+        rec["pairs_staged"], _left, rec["priority_rows"], rec["keep_all_rows"] = dw.priority
+    return rec
 
 
 def _device_ref_idx(dw):
@@ -424,12 +437,15 @@ def sliding_window_incumbent(ref, moving, commonCT=None, outprefix=None, moving_
     job = _WindowJob(ref, moving, commonCT, outprefix, moving_delaunay, moving_delaunay_vertex_col, optim_params, gurobi_params,
                      ignore_precomputed_triangulation, _shard, mode=mode)
     frames, own = job.device_frames(_pipeline, ctx=ctx)
-    fast = frames is not None and not job.caller_triangulation and not job.optim_params["ignore_knn_if_matched"]
+    # the cell-type-priority prune: on the host -- the general route -- unless optim_params["hip_priority_prune"] = "device"
+    priority = bool(job.optim_params["ignore_knn_if_matched"]) and priority_prune_route(job.optim_params) == "device"
+    host_prune = bool(job.optim_params["ignore_knn_if_matched"]) and not priority
+    fast = frames is not None and not job.caller_triangulation and not host_prune
     caller = None
     if frames is not None and job.caller_triangulation and caller_delaunay_route(job.optim_params) == "device":
         # the caller's triangulation resident beside the moving section -- unless the device route refuses these inputs
         # (window_api.caller_triangulation_refusal): then the general route runs, as without the key
-        if not job.optim_params["ignore_knn_if_matched"]:
+        if not host_prune:
             caller = frames.caller_tris(job.moving_delaunay, job.vertex_col)
         fast = caller is not None
     if _route is not None:
@@ -445,7 +461,8 @@ def sliding_window_incumbent(ref, moving, commonCT=None, outprefix=None, moving_
                 from . import delaunay
 
                 triangulator = delaunay.triangulator_for(job.optim_params)   # optim_params["hip_delaunay"] / $SAME_DELAUNAY
-            table = _device_route(job, frames, workers, window_local_indices, triangulator, stats, merge, _merge_channel, batch, caller)
+            table = _device_route(job, frames, workers, window_local_indices, triangulator, stats, merge, _merge_channel, batch, caller,
+                                  priority)
         else:
             table = _general_route(job, frames, window_local_indices, stats, ctx)
             if merge:
@@ -494,7 +511,8 @@ def _merged_rows(job, frames, rows, channel):
     return M.merged_part_rows(a_ids, r_ids, viol, wid, pos, seam, channel.rank, channel.tables)
 
 
-def _device_route(job, frames, workers, with_ref_idx, triangulator, stats, merge=False, channel=None, batch=None, caller=None):
+def _device_route(job, frames, workers, with_ref_idx, triangulator, stats, merge=False, channel=None, batch=None, caller=None,
+                  priority=False):
     n_workers = max(1, int(workers if workers is not None else _default_workers()))
     n_workers = min(n_workers, max(1, len(job.todo)))
     contexts = frames.worker_contexts(n_workers)
@@ -510,6 +528,8 @@ def _device_route(job, frames, workers, with_ref_idx, triangulator, stats, merge
     device_table = builders[0].device_columns_possible() and os.environ.get("SAME_TABLE_COLUMNS", "device") != "host"
     if not with_ref_idx and (merge or (device_table and not job.all_matches)):
         accs = _begin_accumulators(job, frames, contexts, cut, channel if merge else None)
+    if priority:                      # once, here: before a worker thread stages its first window (as the id codes above)
+        frames.label_codes_on_device()
     pos_of = {id(w): pos for pos, w in job.todo}
 
     def walk(q):
@@ -519,9 +539,9 @@ def _device_route(job, frames, workers, with_ref_idx, triangulator, stats, merge
             collector = lambda states, windows: accs[q].collect(states, [w["trim"] for w in windows], [w["window_id"] for w in windows],
                                                                 [pos_of[id(w)] for w in windows])
         for (pos, w), dw in zip(mine, frames.windows([w for _p, w in mine], ctx=contexts[q], triangulator=triangulator,
-                                                     collector=collector, batch=batch, mode=job.mode, caller=caller)):
+                                                     collector=collector, batch=batch, mode=job.mode, caller=caller, priority=priority)):
             if dw.error is not None:
-                raise dw.error
+                raise _window_error(dw, job.optim_params)      # (the priority prune's own failure for a window without pairs)
             if dw.skipped:                   # every pair went with the unconstrained nodes: nothing to match (as the general route)
                 continue
             with stage("table rows (central trim)"):

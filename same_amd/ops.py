@@ -598,3 +598,22 @@ def merge_dedup(viol, window_id, aligned_code, ref_code, ctx=None):
         ctx.check(ctx.lib.same_merge_dedup(ctx.handle, viol.ctypes.data, w.ctypes.data, a.ctypes.data, r.ctypes.data, n, out.ctypes.data,
                                            ctypes.byref(m)), "same_merge_dedup")
     return out[: m.value].copy()
+
+
+def section_set_label_codes(ctx, section_handle, codes, n_rows):
+    """same_section_set_label_codes: the joint cell-type label codes (eval_utils._label_codes) of a resident section's rows, in the slot
+    of their own the cell-type-priority prune reads (csrc/window_priority.hip)."""
+    c = as_c(codes, I32)
+    if len(c) != int(n_rows):
+        raise ValueError(f"one label code per section row: {len(c)} codes for {int(n_rows)} rows")
+    with ctx.lock:
+        ctx.check(ctx.lib.same_section_set_label_codes(section_handle, c.ctypes.data if len(c) else None), "same_section_set_label_codes")
+
+
+def window_priority_pairs(ctx, window_handles, n_windows):
+    """same_window_priority_pairs for a batch of staged windows of one context (one wait) -> int64 (n_windows, 4): per window {pairs
+    staged, pairs left, rows that kept one pair, rows that kept all}."""
+    counts = np.zeros((int(n_windows), 4), I64)
+    with ctx.lock:
+        ctx.check(ctx.lib.same_window_priority_pairs(window_handles, int(n_windows), counts.ctypes.data), "same_window_priority_pairs")
+    return counts

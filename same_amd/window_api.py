@@ -3,6 +3,7 @@
 Split from same_amd/api.py (run_same and prepare_same_inputs live there).  Two pipelines stand behind the same signature; which one
 runs, and on what, is said at the head of the code below and in DESIGN.md section 0."""
 import os
+import threading
 from typing import Any, Dict, Optional
 
 import numpy as np
@@ -142,10 +143,13 @@ def caller_triangulation_rows(moving, moving_delaunay, vertex_col=None):
 
 def caller_triangulation_refusal(ref, moving, commonCT, op, moving_delaunay, vertex_col=None):
     """Why a caller's triangulation does not take the device route of sliding_window_incumbent under
-    optim_params["hip_caller_delaunay"] = "device" (None: it does): a reason `_DeviceFrames.refusal` names, ignore_knn_if_matched (the
-    priority filter walks the pairs on the host), or one of `caller_triangulation_rows`."""
+    optim_params["hip_caller_delaunay"] = "device" (None: it does): a reason `_DeviceFrames.refusal` names, ignore_knn_if_matched
+    without optim_params["hip_priority_prune"] = "device" (the priority filter then runs on the host, window by window), or one of
+    `caller_triangulation_rows`."""
+    from .window_mode import priority_prune_route
+
     why = _DeviceFrames.refusal(ref, moving, commonCT, op, vertex_col)
-    if why is None and op["ignore_knn_if_matched"]:
+    if why is None and op["ignore_knn_if_matched"] and priority_prune_route(op) != "device":
         why = "ignore_knn_if_matched"
     return why if why is not None else caller_triangulation_rows(moving, moving_delaunay, vertex_col)[1]
 
@@ -163,6 +167,7 @@ class _DeviceFrames:
         self.ref_sec, self.mov_sec = Section.from_frame(ref, self.commonCT), Section.from_frame(moving, self.commonCT)
         self.dref = self.dmov = None
         self._worker_ctx = []            # contexts (= streams) of the worker threads beyond the first, kept with their window states
+        self._label_lock = threading.Lock()
         with stage("sections to the device + binning on the window grid"):
             self.dref = DeviceSection(self.ref_sec, self.cost_dtype, self.ctx)
             self.dmov = DeviceSection(self.mov_sec, self.cost_dtype, self.ctx)
@@ -213,16 +218,34 @@ class _DeviceFrames:
             known[key] = (moving_delaunay, None if rows is None else DeviceCallerTris(self.dmov, rows, self.ctx))
         return known[key][1]
 
+    def label_codes_on_device(self):
+        """The joint codes of the two frames' `cell_type` labels (eval_utils._label_codes: equal code <=> labels that compare equal; a
+        label that equals nothing is negative) in the sections' slot for them: what the cell-type-priority prune on the device compares
+        (windows.priority_windows).  Made and uploaded once per frames: the library wants the codes set before the first prune over a
+        section and frees the old ones when they are set again, so the device route calls this before its worker threads start."""
+        with self._label_lock:        # worker threads may all ask (`windows`): one uploads, before any of them prunes
+            if not self.__dict__.get("_label_codes_on_device"):
+                from .eval_utils import _label_codes
+
+                with stage("cell-type label codes to the device"):
+                    mov_code, ref_code = _label_codes(self.moving["cell_type"].to_numpy(), self.ref["cell_type"].to_numpy())
+                    self.dmov.set_label_codes(mov_code)
+                    self.dref.set_label_codes(ref_code)
+                self.__dict__["_label_codes_on_device"] = True
+
     def windows(self, plan, triangulate=True, ctx=None, triangulator=None, fetch_triangles=False, collector=None, batch=None, mode=None,
-                caller=None):
+                caller=None, priority=False):
         from .windows import iter_device_windows
 
         op = self.op
+        if priority:
+            self.label_codes_on_device()
         return iter_device_windows(self.ref_sec, self.mov_sec, self.dref, self.dmov, plan, radius=op["radius"], knn=op["knn"],
                                    dist_ct_coeff=op["dist_ct_coeff"], min_angle_deg=op.get("min_angle_deg", 15),
                                    ignore_same_type_triangles=op["ignore_same_type_triangles"], no_match_penalty=op["no_match_penalty"],
                                    ctx=self.ctx if ctx is None else ctx, triangulate=triangulate, triangulator=triangulator,
-                                   fetch_triangles=fetch_triangles, collector=collector, batch=batch, mode=mode, caller=caller)
+                                   fetch_triangles=fetch_triangles, collector=collector, batch=batch, mode=mode, caller=caller,
+                                   priority=priority)
 
     def accumulators(self, contexts, cid):
         """One merge accumulator per worker context (kept with the frames: a pass re-uses the arrays of the last), and the sections' id

@@ -13,6 +13,7 @@ from .params import init_gurobi_params, init_optim_params
 INCUMBENTS = ("greedy", "assignment", "transport")          # optim_params["hip_incumbent"]; "greedy" without the key
 REFINES = ("local", "capacity")               # optim_params["hip_refine"]; None without the key
 CALLER_DELAUNAY = (None, "host", "device")    # optim_params["hip_caller_delaunay"]; None without the key
+PRIORITY_PRUNE = (None, "host", "device")     # optim_params["hip_priority_prune"]; None without the key
 REFINE_ROUNDS = 32                             # optim_params["hip_refine_rounds"] without the key
 _CODES = dict(zip(INCUMBENTS, (_lib.SAME_INCUMBENT_GREEDY, _lib.SAME_INCUMBENT_ASSIGNMENT, _lib.SAME_INCUMBENT_TRANSPORT)))
 
@@ -57,6 +58,7 @@ class WindowMode:
         op = _Params.of(optim_params)
         incumbent, search, capacity = incumbent_mode(op, gurobi_params, moving), refine_mode(op), transport_capacity(op)
         caller_delaunay_route(op)
+        priority_prune_route(op)
         if search is None:
             return cls(incumbent, capacity=capacity)
         return cls(incumbent, op["hip_refine"], *search[:2], search[2] if op["hip_refine"] == "capacity" else capacity)
@@ -158,6 +160,16 @@ def caller_delaunay_route(optim_params):
     route = (optim_params or {}).get("hip_caller_delaunay")
     if not (route is None or isinstance(route, str)) or route not in CALLER_DELAUNAY:
         raise ValueError(f"optim_params['hip_caller_delaunay'] must be None, 'host' or 'device', not {route!r}")
+    return "host" if route is None else route
+
+
+def priority_prune_route(optim_params):
+    """optim_params["hip_priority_prune"] checked -> "host" (None or without the key: a job with ignore_knn_if_matched takes the general
+    route of sliding_window_incumbent, its pairs filtered window by window on the host) | "device" (it stays on the device route:
+    csrc/window_priority.hip).  Without ignore_knn_if_matched the key changes nothing."""
+    route = (optim_params or {}).get("hip_priority_prune")
+    if not (route is None or isinstance(route, str)) or route not in PRIORITY_PRUNE:
+        raise ValueError(f"optim_params['hip_priority_prune'] must be None, 'host' or 'device', not {route!r}")
     return "host" if route is None else route
 
 

@@ -402,6 +402,11 @@ class DeviceSection:
             self.ctx.check(self.ctx.lib.same_section_set_codes(self.handle, None if c is None else c.ctypes.data, int(n_codes)),
                            "same_section_set_codes")
 
+    def set_label_codes(self, codes):
+        """codes[row] = the row's cell-type label code, made jointly over the two sections of a job (eval_utils._label_codes): what the
+        cell-type-priority prune on the device compares (priority_windows).  A slot of its own, beside the merge's id codes."""
+        ops.section_set_label_codes(self.ctx, self.handle, codes, len(self.section.xy))
+
     def close(self):
         if getattr(self, "handle", None) and self.ctx.handle:        # a context that is already gone took its device memory along
             with self.ctx.lock:
@@ -434,6 +439,7 @@ class DeviceWindow:
         self.n_triangles = 0
         self.n_staged_pairs = self.n_selected = 0      # pairs as staged; the caller's triangles over the staged cells (caller_tris_windows)
         self.assignment = self.refine = None
+        self.priority = None       # priority_windows: (pairs staged, pairs left, rows that kept one pair, rows that kept all)
 
     def stage(self, moving, ref, box, radius, knn, dist_ct_coeff):
         """-> (aligned rows in the box, reference rows in the box, aligned rows kept, pairs)"""
@@ -747,8 +753,24 @@ def stage_windows(states, moving, ref, boxes, radius, knn, dist_ct_coeff):
                                             float(dist_ct_coeff), counts.ctypes.data), "same_window_stage")
     for s, c in zip(states, counts.tolist()):
         s.counts, s.n_triangles = tuple(c), 0
-        s.n_staged_pairs, s.n_selected = c[3], 0
+        s.n_staged_pairs, s.n_selected, s.priority = c[3], 0, None
     return [s.counts for s in states]
+
+
+def priority_windows(states):
+    """same_window_priority_pairs for a batch of staged windows of one context (one wait): the cell-type-priority prune of every window's
+    pair list (src/knn_utils.py:28-78; csrc/window_priority.hip).  -> [(pairs staged, pairs left, rows that kept one pair, rows that kept
+    all) per window]; every state's pair count -- and _W_PAIRS, _W_COSTS -- are the filtered list's afterwards, _W_STAGED_PAIRS stays the
+    list as staged.  The kept aligned cells do not change."""
+    ctx, n = states[0].ctx, len(states)
+    counts = ops.window_priority_pairs(ctx, _handles(states), n)
+    out = []
+    for s, c in zip(states, counts.tolist()):
+        if s.counts[3]:
+            s.counts = (s.counts[0], s.counts[1], s.counts[2], c[1])
+        s.priority = tuple(c)
+        out.append(s.priority)
+    return out
 
 
 class DeviceCallerTris:
@@ -920,10 +942,12 @@ class DeviceWindowResult:
     greedy only): {"objective", "fallback", "rounds"[, "ref_extra_matches_start"]}.  `refine` (with a search only): the search's record
     of the window's final finish ({"rounds", "moves", "settled", "objective_start", "objective"[, "ref_extra_matches"]}).
     With a caller's triangulation: `removed` the number of unconstrained nodes that went (everything above describes the window without
-    them); `skipped` true for a window left without pairs, which contributes nothing (no error, nothing else set)."""
+    them); `skipped` true for a window left without pairs, which contributes nothing (no error, nothing else set).
+    With the priority prune on the device: `priority` = (pairs staged, pairs left, rows that kept one pair, rows that kept all); `counts`
+    and everything later describe the filtered pair list."""
 
     __slots__ = ("window", "error", "rows_m", "axy", "triangles", "n_triangles", "match_row", "point_flag", "flip_flag", "stats",
-                 "counts", "state", "assignment", "refine", "mode", "skipped", "removed")
+                 "counts", "state", "assignment", "refine", "mode", "skipped", "removed", "priority")
 
     def __init__(self, window, mode=None):
         self.window = window
@@ -963,7 +987,7 @@ class TriangulationCache(QhullTriangulator):
 
 def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dist_ct_coeff=1.0, min_angle_deg=15,
                         ignore_same_type_triangles=True, no_match_penalty=100.0, ctx=None, fetch_triangles=False, triangulator=None,
-                        triangulate=True, batch=None, collector=None, mode=None, caller=None):
+                        triangulate=True, batch=None, collector=None, mode=None, caller=None, priority=False):
     """The window path of `iter_window_arrays` + the greedy incumbent and the three sweeps, with both sections resident on the
     device (`dref`, `dmoving`: DeviceSections of `ref`, `moving`): per window the host only triangulates (Qhull helpers, windows
     ahead as before) and receives the match; the triangle filter runs on the device too, unless a cosine sits within 8 ulp of the
@@ -988,6 +1012,11 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
     call filters the caller's triangles where they are.  A window left without pairs is yielded with `.skipped` (src/same.py's loop gets
     an empty table from it); one with a cosine at the threshold has triangles AND mask re-decided on the host and goes on through the
     prefiltered forms of both calls.
+    `priority`: the cell-type-priority prune (optim_params["ignore_knn_if_matched"], src/knn_utils.py:28-78) on the device: right after a
+    batch's stage call -- before anything is triangulated, before the caller's triangles are selected, as the reference filters its pairs
+    before it triangulates -- ONE more call filters every window's pair list (priority_windows); both sections need their label codes
+    (DeviceSection.set_label_codes).  `counts[3]`, the pairs and costs a state hands out and everything later are the filtered list's;
+    the pair list as staged stays fetchable (_W_STAGED_PAIRS) and stays the frame of the reference limits.
     `mode`: a WindowMode (None: the greedy start alone).  A window whose optimal start the device does not certify is solved again on
     the host (ops.sparse_assign_host, ops.sparse_transport_host) and finished again under that matching; every later finish of a window
     (that fallback, a re-finish with scipy's simplices) runs the mode's search again: `result.refine` holds the last one's counts."""
@@ -1039,6 +1068,16 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
         except BaseException:
             free.extend(states)                       # a refused batch (SAME_EINVAL ...) must not take its states out of the pool
             raise
+        if priority:
+            try:
+                with marked("cell-type-priority prune of the pair lists (device)"):
+                    priority_windows(states)
+                counts = [st.counts for st in states]
+                for out, st in zip(outs, states):
+                    out.priority = st.priority
+            except BaseException:
+                free.extend(states)
+                raise
         if caller is not None:
             try:
                 with marked("caller's triangles: select + remap + node mask + second compaction (device)"):

@@ -17,9 +17,9 @@ def device_rule(pairs, axy, rxy, code_m, code_r):
     dx, dy = axy[pairs[:, 0], 0] - rxy[pairs[:, 1], 0], axy[pairs[:, 0], 1] - rxy[pairs[:, 1], 1]
     d = np.sqrt(dx * dx + dy * dy)
     rank = np.empty(P, np.int64)
-    for a in range(len(rows)):                       # 1. the stable rank of every pair in its row
-        for p in range(prow[a], prow[a + 1]):
-            rank[p] = sum(1 for q in range(prow[a], prow[a + 1]) if d[q] < d[p] or (d[q] == d[p] and q < p))
+    for a in range(len(rows)):                       # 1. the stable rank of every pair in its row: #{q : d_q < d_p or (d_q == d_p and q < p)}
+        dr, q = d[prow[a]:prow[a + 1]], np.arange(prow[a + 1] - prow[a])
+        rank[prow[a]:prow[a + 1]] = ((dr[None, :] < dr[:, None]) | ((dr[None, :] == dr[:, None]) & (q[None, :] < q[:, None]))).sum(axis=1)
     claim = np.full(len(rxy), np.iinfo(np.int32).max, np.int64)
     near = np.empty(len(rows), np.int64)
     for a in range(len(rows)):                       # 2. the claims: min over the bidding rows

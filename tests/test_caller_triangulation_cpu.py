@@ -90,27 +90,12 @@ def device_front(rows_kept, job_rows, xy, type_id, pairs, radius, min_angle_deg,
     """csrc/window_caller.hip + the filter that follows, in numpy, for one window: `rows_kept` the ascending frame rows of its kept aligned
     cells, `job_rows` the job's triangles as frame rows (caller_triangulation_rows), `pairs` (P, 2) over the kept cells (rows ascending).
     -> (kept triangles renumbered, in the reference's order; removed nodes; renumbered pairs; cells left)"""
-    n = len(rows_kept)
-    # select + remap: all three rows among the kept cells; the caller's order, the caller's corners
-    at = np.minimum(np.searchsorted(rows_kept, job_rows), max(n - 1, 0))
-    inside = (rows_kept[at] == job_rows).all(axis=1) if n else np.zeros(len(job_rows), bool)
-    sel = at[inside]
-    # node mask: every triangle that passes the side and the angle test, before the same-type test
-    cls, _perim, _maxcos = oracle.tri_classify(xy, sel, radius, min_angle_deg, type_id if ignore_same_type else None)
-    valid = np.zeros(n, bool)
-    valid[sel[(cls == 0) | (cls == 3)].reshape(-1)] = True
-    # second compaction
-    new = np.cumsum(valid) - 1
-    left = sel[valid[sel].all(axis=1)] if len(sel) else sel
-    tris2 = new[left]
-    keep_pair = valid[pairs[:, 0]]
-    pairs2 = np.column_stack((new[pairs[keep_pair, 0]], pairs[keep_pair, 1]))
-    # the unchanged filter on the smaller window (no node of it is unconstrained any more)
-    frame = pd.DataFrame({"cell_type": type_id[valid]})
-    kept, gone = oracle.filter_triangles_by_radius(xy[valid], tris2, radius, aligned_df=frame, ignore_same_type_triangles=ignore_same_type,
-                                                   remove_unconstrained_nodes=True, min_angle_deg=min_angle_deg)
-    assert not gone
-    return np.asarray(kept, dtype=np.int64).reshape(-1, 3), np.flatnonzero(~valid), pairs2, int(valid.sum())
+    from caller_check import filtered_after, window_statement
+
+    _sel, valid, n_left, pairs2, _costs, tris2 = window_statement(rows_kept, job_rows, xy, type_id, pairs, np.zeros(len(pairs)), radius,
+                                                                  min_angle_deg, ignore_same_type, oracle)
+    kept = filtered_after(xy, type_id, valid, tris2, radius, min_angle_deg, ignore_same_type, oracle)
+    return kept, np.flatnonzero(~valid), pairs2, n_left
 
 
 def reference_flow(vertex_ids, caller_tris, xy, type_id, pairs, radius, min_angle_deg, ignore_same_type, oracle):

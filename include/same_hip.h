@@ -557,6 +557,23 @@ int same_window_caller_tris(same_window *const *windows, int n_windows, const sa
 int same_section_set_label_codes(same_section *section, const int32_t *codes);
 int same_window_priority_pairs(same_window *const *windows, int n_windows, int64_t *out_counts);
 
+/* ---- a staged window at a smaller k (csrc/window_knn_prefix.hip): what a parameter sweep over `knn` needs instead of a stage call per
+ * value.  The prune keeps an aligned row when any reference lies within the radius and orders a row's pairs by (squared distance,
+ * reference row) ascending, so the list a stage call at k <= k_staged leaves is, row by row, the first min(k, count) pairs of the list
+ * staged at k_staged: same kept aligned cells, same reference rows in the box, same costs.
+ *   same_window_knn_prefix: for each staged window of the batch (ONE wait; none when nothing is launched): every kept aligned row keeps
+ *     its first min(k, count) pairs, the pair offsets are rebuilt by an ordered scan, pairs, their reference rows and costs are COPIED
+ *     (a fetched cost is the staged cost of the same pair, bit for bit) into a second set of arrays, and the window is from then on the
+ *     one same_window_stage(..., k, ...) leaves: SAME_WINDOW_PAIRS, SAME_WINDOW_COSTS, SAME_WINDOW_STAGED_PAIRS, the pair count and the
+ *     frame of the _cap calls' reference limits are the shorter list's.  The aligned side (SAME_WINDOW_ALIGNED_*, SAME_WINDOW_KEPT,
+ *     SAME_WINDOW_ROWS_*) does not change, so what same_window_delaunay left for the window stays valid.  The list as staged stays where
+ *     the stage call put it: every call derives from IT, so values of k may come in any order, and k == k_staged turns the window back
+ *     to it without a launch.  same_window_priority_pairs and both finish calls run on the window as after a stage call; an earlier
+ *     priority prune or finish of the window no longer holds.  out_counts[4 i ..] as same_window_stage reports them.  A window without
+ *     pairs launches nothing.  SAME_EINVAL before anything changes: k < 1, k above the k a window was staged at, a window not staged, or
+ *     one same_window_caller_tris has compacted. */
+int same_window_knn_prefix(same_window *const *windows, int n_windows, int k, int64_t *out_counts);
+
 /* ---- a6 on the window path without the library call --------------------------------------------------------------------------
  * The reference triangulates every window's kept aligned cells with scipy.spatial.Delaunay (Qhull; src/same.py:1023), on the host
  * -- three quarters of a cfg 5 pass.  same_delaunay2d is this library's own triangulator (HOST code, no device, no context, safe to

@@ -119,6 +119,7 @@ _PROTOTYPES = {
     "same_window_caller_tris": [c_vp, c_int, c_vp, c_vp, c_vp, c_dbl, c_int, c_dbl, c_dbl, c_int, c_vp],
     "same_section_set_label_codes": [c_vp, c_vp],
     "same_window_priority_pairs": [c_vp, c_int, c_vp],
+    "same_window_knn_prefix": [c_vp, c_int, c_int, c_vp],
     "same_sparse_assign": [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp],
     "same_sparse_assign_cap": [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_dbl, c_vp, c_vp],
     "same_refine_matching": [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_dbl, c_i64, c_vp, c_vp],

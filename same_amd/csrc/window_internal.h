@@ -285,6 +285,16 @@ struct same_window {
     const int32_t *pr_pairs = nullptr, *pr_jsec = nullptr;
     int64_t pr_P = 0;
     unsigned long long bins_m = 0, bins_r = 0;
+    // the k-NN prefix (window_knn_prefix.hip).  same_window_knn_prefix leaves every row's first min(k, count) pairs in `kpre` and turns
+    // prow / pairs / jsec / cost64 to it: the window is then what a stage call at that k leaves, and `k` is that k.  sk: the list as the
+    // stage call put it (k_staged its k), which every prefix is derived from and a prefix at k_staged turns the window back to
+    win::DevBuf kpre;
+    int k_staged = 0;
+    struct StagedList {
+        int32_t *prow = nullptr, *pairs = nullptr, *jsec = nullptr;
+        double *cost64 = nullptr;
+        int64_t P = 0;
+    } sk;
 };
 
 // A caller's triangulation of a moving section, resident (same_caller_tris_create): section rows per corner, in the caller's order, and

@@ -1,0 +1,224 @@
+// window_knn_prefix.hip -- a staged window's pair list at a SMALLER k, derived from the list as staged instead of staged again
+// (same_window_knn_prefix).  The prune keeps an aligned row when any reference lies within the radius, whatever k is, and orders a row's
+// candidates by (squared distance, reference row) ascending -- a total order (knn.hip:1-13).  The list a stage call at k' <= k leaves is
+// therefore, row by row, the first min(k', count) pairs of the list staged at k: the same kept aligned cells, the same reference rows in
+// the box (a pair's reference number is its place among THOSE, window_stage.hip), the same costs.  Per batch of staged windows:
+//   row offsets    one ordered scan (scan.h) of min(k', count) over the kept rows gives the new pair offsets and the new pair count
+//   scatter        one thread per staged pair: a pair whose place in its row is below k' goes to new_prow[row] + place with its reference
+//                  number, its reference's section row and its cost -- copied, never recomputed -- into a SECOND set of arrays (the
+//                  window's `kpre` buffer); the window's pointers are turned to them.
+// The aligned side is untouched, so a triangulation held for the window stays valid.  The list as staged stays where the stage call put it
+// (same_window::sk): every prefix is derived from it, and a prefix at the staged k turns the window back to it without a launch.  The
+// window after the call is the one a stage call at k' leaves: what reads "the pair list as staged" (SAME_WINDOW_STAGED_PAIRS, the frame of
+// the reference limits, a priority prune that follows) reads the prefix; an earlier priority prune's result no longer holds.
+#include "window_internal.h"
+
+namespace {
+
+using namespace win;
+using scan::Pair;
+
+// per window of a launch
+struct PrefixArgs {
+    int64_t n, P0, cap;                // kept aligned cells, pairs as staged, pairs the prefix buffer holds (>= the prefix's count)
+    int k;
+    const int32_t *prow0, *pairs0, *jsec0;
+    const double *cost0;
+    unsigned long long *st, *counts;   // scan words; the window's count block: [3] pairs
+    int32_t *prow, *pairs, *jsec;
+    double *cost;
+};
+
+__device__ __forceinline__ unsigned prefix_keep(const PrefixArgs &w, int64_t a) {
+    const int32_t c = w.prow0[a + 1] - w.prow0[a];
+    return (unsigned)(c < 0 ? 0 : (c < w.k ? c : w.k));
+}
+
+// the rows' new pair offsets: scan of min(k, count)
+__global__ __launch_bounds__(scan::NT) void prefix_rows_kernel(Batch<PrefixArgs> b) {
+    __shared__ scan::Shared sh;
+    const PrefixArgs &w = b.w[blockIdx.y];
+    const int nb = (int)scan::blocks_for(w.n);
+    if ((int)blockIdx.x >= nb || w.n == 0) return;
+    const int64_t n = w.n;
+    auto val = [&](int64_t a) { return a < n ? Pair{1u, prefix_keep(w, a)} : Pair{0u, 0u}; };
+    Pair through;
+    const Pair off = scan::exclusive(w.st, (int)blockIdx.x, val, sh, &through);
+    const int64_t a = (int64_t)blockIdx.x * scan::NT + threadIdx.x;
+    if (a < n) w.prow[a] = (int32_t)off.p;
+    if ((int)blockIdx.x == nb - 1 && threadIdx.x == 0) {
+        w.prow[n] = (int32_t)through.p;
+        w.counts[3] = through.p;
+        w.counts[4] = 0;                          // (a priority prune's count: a freshly staged window has none)
+    }
+}
+
+__global__ __launch_bounds__(256) void prefix_scatter_kernel(Batch<PrefixArgs> b) {
+    const PrefixArgs &w = b.w[blockIdx.y];
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= w.P0) return;
+    const int32_t a = w.pairs0[2 * p];
+    if (a < 0 || a >= w.n) return;
+    const int64_t place = p - w.prow0[a];         // the pair's place in its row: the stage call wrote a row's pairs in the prune's order
+    if (place < 0 || place >= w.k) return;
+    const int64_t dst = (int64_t)w.prow[a] + place;
+    if (dst >= w.cap) return;                     // (the offsets are the scan of min(k, count): never taken)
+    w.pairs[2 * dst] = a;
+    w.pairs[2 * dst + 1] = w.pairs0[2 * p + 1];
+    w.jsec[dst] = w.jsec0[p];
+    w.cost[dst] = w.cost0[p];
+}
+
+struct PrefixPlan {
+    PrefixArgs a{};
+    ZeroArgs zero{};
+};
+
+// One window's `kpre` buffer laid out; no launch.
+int prepare_prefix(same_window *w, int k, PrefixPlan *pp) {
+    same_ctx *ctx = w->ctx;
+    const int64_t n = w->n_ua, P0 = w->sk.P, cap = std::min<int64_t>(P0, n * (int64_t)k);
+    PrefixArgs &a = pp->a;
+    a = PrefixArgs{};
+    size_t zero_bytes = 0;
+    auto lay = [&](Carver c) {
+        a.st = scan::arg(c.scan_words(n));          // zeroed head: the scan words
+        zero_bytes = c.off;
+        a.prow = c.take<int32_t>((size_t)n + 1);
+        a.pairs = c.take<int32_t>((size_t)cap * 2);
+        a.jsec = c.take<int32_t>((size_t)cap);
+        a.cost = c.take<double>((size_t)cap);
+        return c.off;
+    };
+    SAME_TRY(ensure(ctx, w->kpre, lay(Carver())));
+    lay(Carver(w->kpre.p));
+    pp->zero = ZeroArgs{{w->kpre.p, nullptr}, {zero_bytes, 0}};
+    a.n = n;
+    a.P0 = P0;
+    a.cap = cap;
+    a.k = k;
+    a.prow0 = w->sk.prow;
+    a.pairs0 = w->sk.pairs;
+    a.jsec0 = w->sk.jsec;
+    a.cost0 = w->sk.cost64;
+    a.counts = w->counts;
+    return SAME_OK;
+}
+
+int launch_prefix(same_ctx *ctx, PrefixPlan *const *pps, int n_w) {
+    Batch<PrefixArgs> b{};
+    ZeroArgs zr[SAME_LAUNCH_WINDOWS];
+    int64_t max_P = 0, max_n = 0;
+    for (int q = 0; q < n_w; ++q) {
+        b.w[q] = pps[q]->a;
+        zr[q] = pps[q]->zero;
+        max_P = std::max(max_P, pps[q]->a.P0);
+        max_n = std::max(max_n, pps[q]->a.n);
+    }
+    const unsigned nw = (unsigned)n_w;
+    SAME_TRY(launch_zero(ctx, zr, n_w));
+    SAME_LAUNCH(ctx, prefix_rows_kernel, dim3(scan::blocks_for(max_n), nw), dim3(scan::NT), 0, b);
+    SAME_LAUNCH(ctx, prefix_scatter_kernel, dim3(grid_for(max_P), nw), dim3(256), 0, b);
+    HIP_TRY(ctx, hipGetLastError());
+    return SAME_OK;
+}
+
+// the window's pair list is `prow` / `pairs` / `jsec` / `cost` with P pairs, as a stage call at k leaves it: nothing derived from an
+// earlier list holds any more
+void turn_to(same_window *w, int k, int32_t *prow, int32_t *pairs, int32_t *jsec, double *cost, int64_t P) {
+    w->prow = prow;
+    w->pairs = pairs;
+    w->jsec = jsec;
+    w->cost64 = cost;
+    w->P = P;
+    w->k = k;
+    w->prio_ok = 0;
+    w->pr_pairs = w->pr_jsec = nullptr;
+    w->pr_P = 0;
+    w->lim_row = nullptr;                         // the frame of the reference limits: the references THIS list names
+    w->lim_P = 0;
+    w->filtered = w->finished = 0;
+    w->Tr = 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int same_window_knn_prefix(same_window *const *windows, int n_windows, int k, int64_t *out_counts) {
+    same_ctx *ctx = nullptr;
+    SAME_TRY(check_batch(windows, n_windows, &ctx));
+    REQUIRE(ctx, out_counts && k >= 1);
+    for (int i = 0; i < n_windows; ++i) {
+        const same_window *w = windows[i];
+        REQUIRE(ctx, w->staged >= 1 && k <= w->k_staged);
+        REQUIRE(ctx, !w->caller_sel && !w->caller_ok);        // (a caller's triangulation compacts the aligned side: stage again)
+    }
+    SAME_TRY(same_use(ctx));
+    std::vector<PrefixPlan> plans((size_t)n_windows);
+    std::vector<int> live;
+    int rc = SAME_OK;
+    for (int i = 0; i < n_windows && rc == SAME_OK; ++i) {
+        same_window *w = windows[i];
+        // no pairs: every k leaves the same (empty) list; the staged k: the list as staged, no launch
+        if (w->staged != 2 || w->sk.P == 0 || w->n_ua == 0 || k == w->k_staged) continue;
+        rc = prepare_prefix(w, k, &plans[(size_t)i]);
+        if (rc == SAME_OK) live.push_back(i);
+    }
+    // ONE wait for the batch: per group of SAME_LAUNCH_WINDOWS windows the zeroing and the two kernels, then every window's count block
+    // straight into the head of its pinned block, where the stage call left the staged counts
+    for (size_t g = 0; g < live.size() && rc == SAME_OK; g += SAME_LAUNCH_WINDOWS) {
+        const int n_g = (int)std::min<size_t>(SAME_LAUNCH_WINDOWS, live.size() - g);
+        PrefixPlan *pps[SAME_LAUNCH_WINDOWS];
+        for (int q = 0; q < n_g; ++q) pps[q] = &plans[(size_t)live[g + (size_t)q]];
+        rc = launch_prefix(ctx, pps, n_g);
+        CopyArgs ca[SAME_LAUNCH_WINDOWS];
+        for (int q = 0; q < n_g && rc == SAME_OK; ++q) {
+            same_window *w = windows[live[g + (size_t)q]];
+            ca[q] = CopyArgs{};
+            if (w->host_dev) {
+                ca[q] = CopyArgs{{w->counts, nullptr}, {w->host_dev, nullptr}, {64, 0}};
+                continue;
+            }
+            hipError_t e = hipMemcpyAsync(w->host, w->counts, 64, hipMemcpyDeviceToHost, ctx->stream);
+            ++ctx->stats[SAME_STAT_COPIES];
+            if (e != hipSuccess) rc = same_fail(ctx, SAME_EIO, "k-NN prefix copy back", e);
+        }
+        if (rc == SAME_OK) rc = launch_copy_back(ctx, ca, n_g);
+    }
+    if (rc != SAME_OK) {
+        // nothing of a failed batch counts: windows of earlier groups have their count blocks overwritten already, so every window the
+        // call touched is no longer staged (as same_window_stage leaves a failed batch); what was enqueued is waited for first
+        (void)hipStreamSynchronize(ctx->stream);
+        for (int i : live) windows[i]->staged = 0;
+        return rc;
+    }
+    if (!live.empty()) SAME_WAIT(ctx);
+    for (int i : live) {
+        const same_window *w = windows[i];
+        const PrefixArgs &a = plans[(size_t)i].a;
+        const unsigned long long *tot = static_cast<const unsigned long long *>(w->host);
+        REQUIRE(ctx, (int64_t)tot[3] >= a.n && (int64_t)tot[3] <= a.cap && (int64_t)tot[2] == a.n);
+    }
+    size_t at = 0;
+    for (int i = 0; i < n_windows; ++i) {
+        same_window *w = windows[i];
+        const bool derived = at < live.size() && live[at] == i;
+        if (derived) {
+            const PrefixArgs &a = plans[(size_t)i].a;
+            turn_to(w, k, a.prow, a.pairs, a.jsec, a.cost, (int64_t) static_cast<const unsigned long long *>(w->host)[3]);
+            ++at;
+        } else {
+            turn_to(w, k, w->sk.prow, w->sk.pairs, w->sk.jsec, w->sk.cost64, w->sk.P);
+            static_cast<unsigned long long *>(w->host)[3] = (unsigned long long)w->sk.P;     // the count block's host copy: the list's
+        }
+        int64_t *counts = out_counts + 4 * i;
+        counts[0] = w->n_m;
+        counts[1] = w->n_r;
+        counts[2] = w->n_ua;
+        counts[3] = w->P;
+    }
+    return SAME_OK;
+}
+
+}  // extern "C"

@@ -350,7 +350,7 @@ void same_window_destroy(same_window *w) {
     if (!w) return;
     (void)hipSetDevice(w->ctx->device);
     (void)hipStreamSynchronize(w->ctx->stream);
-    for (DevBuf *b : {&w->stage, &w->filter, &w->finish, &w->tris, &w->big_mask, &w->full_m, &w->full_r, &w->dd_work, &w->dd_tris, &w->caller, &w->prio})
+    for (DevBuf *b : {&w->stage, &w->filter, &w->finish, &w->tris, &w->big_mask, &w->full_m, &w->full_r, &w->dd_work, &w->dd_tris, &w->caller, &w->prio, &w->kpre})
         release(*b);
     if (w->host) (void)hipHostFree(w->host);
     delete w;
@@ -446,6 +446,8 @@ int prepare_stage(same_window *w, const same_section *mov, const same_section *r
     w->prio_ok = 0;                               // ... and its pair list the only one
     w->pr_pairs = w->pr_jsec = nullptr;
     w->pr_P = 0;
+    w->k_staged = k;                              // ... at the k it was staged at (same_window_knn_prefix: w->k is the list's)
+    w->sk = same_window::StagedList{};
     w->bins_m = mov->bins;                        // (the caller holds both grid locks)
     w->bins_r = ref->bins;
     for (int q = 0; q < 4; ++q) w->box[q] = box[q];
@@ -497,6 +499,10 @@ int prepare_stage(same_window *w, const same_section *mov, const same_section *r
     w->host_filter_off = w->host_finish_off + ((finish_back_bytes(cap_m) + 255) & ~size_t(255));     // (n_ua <= cap_m)
     SAME_TRY(ensure_host(w, w->host_filter_off + 256));
     lay(Carver(w->stage.p));
+    w->sk.prow = w->prow;                         // the list as staged: what a k-NN prefix is derived from (window_knn_prefix.hip)
+    w->sk.pairs = w->pairs;
+    w->sk.jsec = w->jsec;
+    w->sk.cost64 = w->cost64;
     // aligned boxes: the merged list IS the row list; whole-section path: its own list is copied in
     w->rows_m = compact_m || !cm.use_runs ? rows_m : reinterpret_cast<int32_t *>(merged_m);
     w->rows_r = compact_r || !cr.use_runs ? rows_r : reinterpret_cast<int32_t *>(merged_r);
@@ -603,7 +609,7 @@ int collect_stage(same_window *w, const StagePlan &sp, int64_t *out_counts) {
     w->n_m = (int64_t)tot[0];
     w->n_r = (int64_t)tot[1];
     w->n_ua = (int64_t)tot[2];
-    w->P = (int64_t)tot[3];
+    w->P = w->sk.P = (int64_t)tot[3];
     REQUIRE(ctx, w->n_m <= w->cap_m && w->n_r <= w->cap_r && w->n_ua <= w->n_m && w->P <= (int64_t)sp.slots);
     out_counts[0] = w->n_m;
     out_counts[1] = w->n_r;

@@ -16,6 +16,10 @@ Same arguments as `sliding_window_matching`; the result has its columns wherever
 * `ref_idx` (index in the window's compacted reference frame) needs the window's pair list on the host and is only made on request
   (`window_local_indices=True`); `aligned_idx` is free.  `run_time` is 0.0, `time_limit_reached` False.
 
+Several parameter sets over the same frames -- a sweep of `knn`, of the penalties, of the start and the search -- are ONE pass of the
+windows through `same_amd.sliding_window_sweep` (sweep.py): every window is staged and triangulated once and finished once
+per set, and each set's table and stats are this function's.
+
 optim_params["hip_incumbent"] = "assignment" (opt-in; "greedy" is the default) takes each window's OPTIMAL one-to-one assignment
 instead: the reference's Hungarian start (src/init_helpers.py:135-175) on its sparse form, without `init_hungarian_max_n`, solved on the
 GPU (csrc/assign.hip).  It needs max_matches == 1 and every no-match cost below init_big_m / 2 (`incumbent_mode`).  With
@@ -567,6 +571,12 @@ def _device_route(job, frames, workers, with_ref_idx, triangulator, stats, merge
         [t.join() for t in threads]
         if errors:
             raise errors[0]
+    return _route_table(job, frames, builders, accs, merge, channel, device_table)
+
+
+def _route_table(job, frames, builders, accs, merge, channel, device_table):
+    """The device route's table once its windows are walked: from the builders' rows or from the accumulators' (None: the builders hold
+    them), merged or laid end to end."""
     # the rows that stay, as FINAL_RECORDs: the builders' (the merge chooses among them on the host) or the accumulator's (the merge chose
     # on the device; its columns may come from there too) -- then one way from records to the table
     me, with_pos = builders[0], job.mine is not None and not merge

@@ -234,7 +234,7 @@ class _DeviceFrames:
                 self.__dict__["_label_codes_on_device"] = True
 
     def windows(self, plan, triangulate=True, ctx=None, triangulator=None, fetch_triangles=False, collector=None, batch=None, mode=None,
-                caller=None, priority=False):
+                caller=None, priority=False, sets=None):
         from .windows import iter_device_windows
 
         op = self.op
@@ -245,7 +245,7 @@ class _DeviceFrames:
                                    ignore_same_type_triangles=op["ignore_same_type_triangles"], no_match_penalty=op["no_match_penalty"],
                                    ctx=self.ctx if ctx is None else ctx, triangulate=triangulate, triangulator=triangulator,
                                    fetch_triangles=fetch_triangles, collector=collector, batch=batch, mode=mode, caller=caller,
-                                   priority=priority)
+                                   priority=priority, sets=sets)
 
     def accumulators(self, contexts, cid):
         """One merge accumulator per worker context (kept with the frames: a pass re-uses the arrays of the last), and the sections' id

@@ -773,6 +773,22 @@ def priority_windows(states):
     return out
 
 
+def prefix_windows(states, k):
+    """same_window_knn_prefix for a batch of staged windows of one context (one wait): every window's pair list cut to each row's first
+    min(k, count) pairs (csrc/window_knn_prefix.hip) -- the window a stage call at `k` leaves, derived from the list as staged instead
+    of staged again.  k at most the knn the windows were staged at (that value turns them back to the staged list); values may come in
+    any order.  -> [counts per window]; every state's pair count -- and _W_PAIRS, _W_COSTS, _W_STAGED_PAIRS -- are the shorter list's
+    afterwards, an earlier priority prune's result is gone.  The kept aligned cells, and a triangulation made for them, do not change."""
+    ctx, n = states[0].ctx, len(states)
+    counts = np.zeros((n, 4), np.int64)
+    with ctx.lock:
+        ctx.check(ctx.lib.same_window_knn_prefix(_handles(states), n, int(k), counts.ctypes.data), "same_window_knn_prefix")
+    for s, c in zip(states, counts.tolist()):
+        s.counts, s.n_triangles = tuple(c), 0
+        s.n_staged_pairs, s.priority = c[3], None
+    return [s.counts for s in states]
+
+
 class DeviceCallerTris:
     """A caller's triangulation of a moving section resident on the device (same_caller_tris_create, csrc/window_caller.hip): `rows`
     int32 (Tr, 3) section rows in the caller's order (window_api.caller_triangulation_rows), uploaded once and binned by the grid the
@@ -944,10 +960,12 @@ class DeviceWindowResult:
     With a caller's triangulation: `removed` the number of unconstrained nodes that went (everything above describes the window without
     them); `skipped` true for a window left without pairs, which contributes nothing (no error, nothing else set).
     With the priority prune on the device: `priority` = (pairs staged, pairs left, rows that kept one pair, rows that kept all); `counts`
-    and everything later describe the filtered pair list."""
+    and everything later describe the filtered pair list.
+    With `sets` (a parameter sweep): `set` = the index of the parameter set this result was finished under; `mode`, `counts`, `priority`
+    and everything the finish call leaves are that set's, `rows_m` / `axy` are shared by the window's results."""
 
     __slots__ = ("window", "error", "rows_m", "axy", "triangles", "n_triangles", "match_row", "point_flag", "flip_flag", "stats",
-                 "counts", "state", "assignment", "refine", "mode", "skipped", "removed", "priority")
+                 "counts", "state", "assignment", "refine", "mode", "skipped", "removed", "priority", "set")
 
     def __init__(self, window, mode=None):
         self.window = window
@@ -987,7 +1005,7 @@ class TriangulationCache(QhullTriangulator):
 
 def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dist_ct_coeff=1.0, min_angle_deg=15,
                         ignore_same_type_triangles=True, no_match_penalty=100.0, ctx=None, fetch_triangles=False, triangulator=None,
-                        triangulate=True, batch=None, collector=None, mode=None, caller=None, priority=False):
+                        triangulate=True, batch=None, collector=None, mode=None, caller=None, priority=False, sets=None):
     """The window path of `iter_window_arrays` + the greedy incumbent and the three sweeps, with both sections resident on the
     device (`dref`, `dmoving`: DeviceSections of `ref`, `moving`): per window the host only triangulates (Qhull helpers, windows
     ahead as before) and receives the match; the triangle filter runs on the device too, unless a cosine sits within 8 ulp of the
@@ -1019,7 +1037,15 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
     the pair list as staged stays fetchable (_W_STAGED_PAIRS) and stays the frame of the reference limits.
     `mode`: a WindowMode (None: the greedy start alone).  A window whose optimal start the device does not certify is solved again on
     the host (ops.sparse_assign_host, ops.sparse_transport_host) and finished again under that matching; every later finish of a window
-    (that fallback, a re-finish with scipy's simplices) runs the mode's search again: `result.refine` holds the last one's counts."""
+    (that fallback, a re-finish with scipy's simplices) runs the mode's search again: `result.refine` holds the last one's counts.
+    `sets`: a parameter sweep over ONE pass -- a list of (knn, WindowMode, no_match_penalty) triples (then `knn`, `mode` and
+    `no_match_penalty` are not read).  Every batch is staged once at the largest knn and triangulated once, and finished once per set:
+    the sets are taken grouped by knn, largest first (a batch sees at most one prefix call per distinct value); per group a
+    `prefix_windows` call where its knn is not the current list's, then `priority_windows` if the job has the priority prune, then per
+    set of the group filter + finish under its mode and penalty.  One ticket per window serves every set: scipy's simplices, once a set's
+    order ties asked for them, are the ticket's answer for the sets after it.  Yields, per batch, one DeviceWindowResult per window for
+    the first set taken, then for the next ... (`result.set` says which); a result's `state` is live only until the next set's finish.
+    `collector(states, windows, set index)` is called per batch and set.  Not with `caller` or `triangulate=False`."""
     import os
     from collections import deque
 
@@ -1029,6 +1055,13 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
 
     ctx = ops._ctx(ctx)
     mode = WindowMode.default() if mode is None else mode
+    if sets is not None:
+        if caller is not None or not triangulate or not sets:
+            raise ValueError("sets: at least one, with windows triangulated by the route (no caller's triangulation)")
+        sets = [(int(k), WindowMode.default() if m is None else m, float(p)) for k, m, p in sets]
+        knn = max(k for k, _m, _p in sets)
+        # the sets grouped by knn, largest first (the first group is the list as staged)
+        set_groups = [(k, [q for q, st in enumerate(sets) if st[0] == k]) for k in sorted({st[0] for st in sets}, reverse=True)]
     angle_enabled, cos_thr = cos_threshold(min_angle_deg)
     near_tol = float(8 * np.spacing(abs(cos_thr))) if (angle_enabled and np.isfinite(cos_thr)) else 0.0
     tri = QHULL if triangulator is None else triangulator
@@ -1068,7 +1101,7 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
         except BaseException:
             free.extend(states)                       # a refused batch (SAME_EINVAL ...) must not take its states out of the pool
             raise
-        if priority:
+        if priority and sets is None:                 # (a sweep prunes per knn group, right before the group's finish calls)
             try:
                 with marked("cell-type-priority prune of the pair lists (device)"):
                     priority_windows(states)
@@ -1148,9 +1181,11 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
             raise RuntimeError("a cosine at the angle threshold that same_window_caller_tris did not report")
         return res, [None] * len(todo)
 
-    def finish_triangulated(states, tickets, args):
-        """the finish call over the triangulator's answers -> (result per window, simplices per window)"""
-        tri.before_finish(states, tickets, radius, angle_enabled, cos_thr)
+    def finish_triangulated(states, tickets, args, mode=mode, first=True):
+        """the finish call over the triangulator's answers -> (result per window, simplices per window); `first`: the batch's first
+        finish (the route's per-batch hook runs once; a ticket keeps its answer)"""
+        if first:
+            tri.before_finish(states, tickets, radius, angle_enabled, cos_thr)
         with marked("triangulate (wait for helper)"):
             tris = [ticket.result() for ticket in tickets]
         with marked("filter + signs + incumbent + sweeps (device)"):
@@ -1170,9 +1205,9 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
                     res[q] = filter_finish_windows([state], [tris[q]], *args, mode=mode)[0]
         return res, tris
 
-    def finish_batch(group):
+    def finish_batch(group, mode=mode, no_match_penalty=no_match_penalty, first=True, which=None):
         """filter + signs + incumbent + sweeps of the staged windows of `group`, by ONE library call (+ one per window whose filter met a
-        cosine at the threshold)"""
+        cosine at the threshold); `which`: the set of a sweep this finish is for (its mode and penalty; `first`: the batch's first)"""
         todo = [(out, state, ticket) for out, state, ticket in group if state is not None]
         for out, state, _t in todo:
             out.state, out.n_triangles = state, 0
@@ -1180,7 +1215,8 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
             return
         states, tickets = [st for _o, st, _t in todo], [t for _o, _s, t in todo]
         args = (radius, angle_enabled, cos_thr, near_tol, ignore_same_type_triangles, no_match_penalty)
-        res, tris = finish_callers(todo, states, args) if caller is not None else finish_triangulated(states, tickets, args)
+        res, tris = (finish_callers(todo, states, args) if caller is not None
+                     else finish_triangulated(states, tickets, args, mode, first))
         for q, (out, state, _t) in enumerate(todo):
             _kept, _added, near, match_row, cell_flags, stats = res[q]
             if near:
@@ -1206,7 +1242,35 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
                 out.triangles = state.fetch(_W_TRIANGLES)
         if collector is not None:
             with marked("central rows to the merge accumulator (device, enqueue only)"):
-                collector(states, [o.window for o, _s, _t in todo])
+                collector(states, [o.window for o, _s, _t in todo], *(() if which is None else (which,)))
+
+    def sweep_batch(group):
+        """the staged, submitted windows of `group` finished once per set -> yields the sets' results, group by group of equal knn"""
+        states = [state for _o, state, _t in group if state is not None]
+        current, first = knn, True
+        for k, members in set_groups:
+            if states and k != current:
+                with marked("pair lists cut to the set's knn (device)"):
+                    prefix_windows(states, k)
+                current = k
+            if states and priority:
+                with marked("cell-type-priority prune of the pair lists (device)"):
+                    priority_windows(states)
+            for which in members:
+                _k, set_mode, penalty = sets[which]
+                mine = []
+                for out, state, ticket in group:
+                    res = DeviceWindowResult(out.window, set_mode)
+                    res.set, res.error, res.skipped = which, out.error, out.skipped
+                    if state is not None:
+                        res.rows_m, res.axy, res.counts, res.priority = out.rows_m, out.axy, state.counts, state.priority
+                    else:
+                        res.counts = out.counts
+                    mine.append((res, state, ticket))
+                finish_batch(mine, set_mode, penalty, first, which)
+                first = False
+                for res, _state, _ticket in mine:
+                    yield res
 
     pending, live, nxt = deque(), [], 0
     try:
@@ -1219,6 +1283,9 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
             live = []
             group = [pending.popleft() for _ in range(min(B, len(pending)))]
             live = [state for _o, state, _t in group if state is not None]
+            if sets is not None:
+                yield from sweep_batch(group)
+                continue
             finish_batch(group)
             for out, _state, _ticket in group:
                 yield out

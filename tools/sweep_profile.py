@@ -1,0 +1,144 @@
+"""same_amd.sliding_window_sweep against the loop of stand-alone jobs it replaces (same_amd/sweep.py, csrc/window_knn_prefix.hip, DESIGN
+§5.12): BASELINE cfg 5's generator (bench_cfg5's parameters: windows 1200 / overlap 300, radius 25, fp32 costs) under the reference's two
+heart grids (examples/heart/run_parameter_sweep.sh) as six sets each -- knn in {1, 2, 4, 6, 8, 10} with hip_refine="local", and
+delaunay_penalty in {0, 1, 5, 10, 25, 50} at knn = 8 (hip_refine="local": the key is read by the search) -- on each triangulation route.
+The loop is the best the single-job function offers: six sliding_window_incumbent calls over ONE resident_frames object, in the same
+process and job as the sweep.  An untimed pass of each, then the best of --passes; every set's table must be the job's (checked, and said
+in the record).  Stage calls and tickets are counted where the binding makes them.  Then one more walk over the plan with the library's
+own timer around every batch's same_window_knn_prefix call: the GPU time a prefix costs per window.
+ONE JSON line, appended to --out (default profiles/sweep_profile.jsonl).
+Usage: python3 tools/sweep_profile.py [--cells 1000000] [--passes 3] [--workers N] [--routes qhull,native,device] [--out ...]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import same_amd                                          # noqa: E402
+from same_amd import synth                               # noqa: E402
+from same_amd import windows as W                        # noqa: E402
+
+GRIDS = {"knn": [{"knn": k, "hip_refine": "local"} for k in (1, 2, 4, 6, 8, 10)],
+         "delaunay_penalty": [{"knn": 8, "hip_refine": "local", "delaunay_penalty": p} for p in (0, 1, 5, 10, 25, 50)]}
+SEEN = {"stage": 0, "tickets": 0}
+
+
+def count_calls():
+    """stage calls of the binding, tickets asked of whichever triangulator a pass uses (a device ticket is one triangulation too)"""
+    from same_amd import delaunay
+
+    inner = W.stage_windows
+
+    def stage(*a, **k):
+        SEEN["stage"] += 1
+        return inner(*a, **k)
+
+    W.stage_windows = stage
+    for cls in (delaunay.QhullTriangulator, delaunay.NativeTriangulator, delaunay.DeviceTriangulator):
+        def submit(self, points, key=None, _inner=cls.submit):
+            SEEN["tickets"] += 1
+            return _inner(self, points, key)
+
+        cls.submit = submit
+
+
+def timed(run, passes):
+    """-> (result, best seconds of `passes` after an untimed pass, calls of one pass)"""
+    out = run()
+    best = float("inf")
+    for _ in range(passes):
+        SEEN.update(stage=0, tickets=0)
+        t0 = time.perf_counter()
+        out = run()
+        best = min(best, time.perf_counter() - t0)
+    return out, best, dict(SEEN)
+
+
+def identical(a, b):
+    if list(a.columns) != list(b.columns) or len(a) != len(b):
+        return False
+    return all(np.array_equal(a[c].to_numpy(), b[c].to_numpy()) for c in a.columns)
+
+
+def prefix_gpu_ms(r_df, m_df, cols, op, k_staged, k, batch=8):
+    """the plan walked once more, stage at k_staged + prefix at k only: GPU milliseconds inside same_window_knn_prefix, summed"""
+    from same_amd.window_api import _WindowJob
+
+    job = _WindowJob(r_df, m_df, cols, None, None, None, op, None, False, None)
+    frames, _own = job.device_frames("device")
+    states = []
+    try:
+        ctx, o = frames.ctx, job.optim_params
+        states = [W.DeviceWindow(ctx) for _ in range(batch)]
+        ms, windows = 0.0, 0
+        for rep in range(2):                     # the first walk grows the windows' buffers; the second is the one that counts
+            ms, windows = 0.0, 0
+            for at in range(0, len(job.plan), batch):
+                group = job.plan[at:at + batch]
+                W.stage_windows(states[:len(group)], frames.dmov, frames.dref, [w["box"] for w in group], abs(float(o["radius"])), k_staged,
+                                o["dist_ct_coeff"])
+                ctx.timer_start()
+                W.prefix_windows(states[:len(group)], k)
+                ms += ctx.timer_stop()
+                windows += len(group)
+        return ms, windows
+    finally:
+        for st in states:
+            st.close()
+        frames.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cells", type=int, default=1_000_000)
+    ap.add_argument("--passes", type=int, default=3)
+    ap.add_argument("--workers", type=int, default=None)
+    ap.add_argument("--routes", default="qhull,native,device")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sweep_profile.jsonl"))
+    args = ap.parse_args()
+
+    T = 8
+    ref = synth.make_cells(args.cells, T, seed=0)
+    mov = synth.make_jittered(ref, seed=1)
+    r_df, m_df = synth.to_frame(ref), synth.to_frame(mov)
+    cols = synth.type_columns(T)
+    base = dict(radius=25, knn=8, no_match_penalty=100, window_size=1200, overlap=300, min_cells_per_window=10, hip_cost_dtype="float32")
+    count_calls()
+    line = {"tool": "sweep_profile", "workload": "cfg5_generator_heart_grids", "cells": args.cells, "passes": args.passes,
+            "cpus": len(os.sched_getaffinity(0)), "sets_per_grid": 6, "routes": {}}
+    all_same = True
+    with same_amd.resident_frames(r_df, m_df) as frames:
+        for route in args.routes.split(","):
+            op = dict(base) if route == "qhull" else dict(base, hip_delaunay=route)
+            rec = {}
+            for grid, sets in GRIDS.items():
+                kw = dict(commonCT=cols, return_stats=True, workers=args.workers)
+                loop = lambda: [same_amd.sliding_window_incumbent(frames, m_df, optim_params={**op, **ps}, **kw) for ps in sets]
+                sweep = lambda: same_amd.sliding_window_sweep(frames, m_df, sets, optim_params=dict(op), **kw)
+                want, loop_s, loop_calls = timed(loop, args.passes)
+                got, sweep_s, sweep_calls = timed(sweep, args.passes)
+                same = all(identical(g[0], w[0]) and g[1] == w[1] for g, w in zip(got, want))
+                all_same = all_same and same
+                rec[grid] = {"windows": len(want[0][1]), "tables_identical": bool(same), "sweep_s": round(sweep_s, 4),
+                             "loop_s": round(loop_s, 4), "loop_over_sweep": round(loop_s / sweep_s, 2),
+                             "sweep_stage_calls": sweep_calls["stage"], "loop_stage_calls": loop_calls["stage"],
+                             "sweep_triangulations": sweep_calls["tickets"], "loop_triangulations": loop_calls["tickets"]}
+            line["routes"][route] = rec
+    ms, timed_windows = prefix_gpu_ms(r_df, m_df, cols, base, 10, 4)
+    line["prefix_gpu_ms_per_window"] = round(ms / max(timed_windows, 1), 4)
+    line["prefix_timed_windows"] = timed_windows
+    print(json.dumps(line), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write(json.dumps(line) + "\n")
+    if not all_same:
+        sys.exit("a sweep's table differs from the stand-alone job's")
+
+
+if __name__ == "__main__":
+    main()

@@ -18,7 +18,8 @@ Same arguments as `sliding_window_matching`; the result has its columns wherever
 
 Several parameter sets over the same frames -- a sweep of `knn`, of the penalties, of the start and the search -- are ONE pass of the
 windows through `same_amd.sliding_window_sweep` (sweep.py): every window is staged and triangulated once and finished once
-per set, and each set's table and stats are this function's.
+per set, and each set's table and stats are this function's -- made by this module's one device route (`_device_pass`), to which a
+single job is a sweep of one set.
 
 optim_params["hip_incumbent"] = "assignment" (opt-in; "greedy" is the default) takes each window's OPTIMAL one-to-one assignment
 instead: the reference's Hungarian start (src/init_helpers.py:135-175) on its sparse form, without `init_hungarian_max_n`, solved on the
@@ -89,7 +90,7 @@ from .ops import MAX_REF_LIMIT          # noqa: F401  (the bound of every refere
 from .window_api import _WindowJob, _walk_windows, _window_error
 from .window_mode import (INCUMBENTS, REFINE_ROUNDS, REFINES, WindowMode, caller_delaunay_route, incumbent_mode,  # noqa: F401
                           priority_prune_route, refine_mode, transport_capacity)
-from .windows import FINAL_RECORD
+from .windows import FINAL_RECORD, MergeAccumulator
 
 STAT_KEYS = ("pairs", "triangles", "checked", "flipped", "xy_violations", "area_flips", "matched")
 
@@ -465,8 +466,8 @@ def sliding_window_incumbent(ref, moving, commonCT=None, outprefix=None, moving_
                 from . import delaunay
 
                 triangulator = delaunay.triangulator_for(job.optim_params)   # optim_params["hip_delaunay"] / $SAME_DELAUNAY
-            table = _device_route(job, frames, workers, window_local_indices, triangulator, stats, merge, _merge_channel, batch, caller,
-                                  priority)
+            (table, stats), = _device_pass([job], frames, workers, window_local_indices, triangulator, merge, _merge_channel, batch,
+                                           caller, priority)
         else:
             table = _general_route(job, frames, window_local_indices, stats, ctx)
             if merge:
@@ -515,63 +516,84 @@ def _merged_rows(job, frames, rows, channel):
     return M.merged_part_rows(a_ids, r_ids, viol, wid, pos, seam, channel.rank, channel.tables)
 
 
-def _device_route(job, frames, workers, with_ref_idx, triangulator, stats, merge=False, channel=None, batch=None, caller=None,
-                  priority=False):
+def _device_pass(jobs, frames, workers, with_ref_idx, triangulator, merge=False, channel=None, batch=None, caller=None, priority=False):
+    """The device route: ONE walk of the windows for `jobs` -- _WindowJobs over the same frames, plan and share of the plan that differ
+    in sweep.SWEEP_KEYS only (`sliding_window_incumbent`: its one job; `sliding_window_sweep`: a job per parameter set).  Every job has
+    its own builders, accumulators and stats.  -> [(table, {plan position: stats record}) per job].  A caller's triangulation and a
+    merge channel go with a single job."""
+    if len(jobs) > 1 and (caller is not None or channel is not None):
+        raise ValueError("several jobs over one pass: not with a caller's triangulation or a merge channel")
+    job = jobs[0]                 # what the jobs share is read from the first
     n_workers = max(1, int(workers if workers is not None else _default_workers()))
     n_workers = min(n_workers, max(1, len(job.todo)))
     contexts = frames.worker_contexts(n_workers)
     sections = (frames.ref_sec, frames.mov_sec)
-    builders = [_TableBuilder(job, sections, with_ref_idx) for _ in range(n_workers)]
+    builders = [[_TableBuilder(j, sections, with_ref_idx) for _ in range(n_workers)] for j in jobs]
     lock = threading.Lock()
     # worker q walks a contiguous run of this process's windows
     cut = [len(job.todo) * q // n_workers for q in range(n_workers + 1)]
     # merge=True: the windows' matches stay where they are.  Every batch's central rows join the pass's accumulator on the device
     # (csrc/window_merge.hip); the merge runs there, and only what it could not decide alone comes to the host (`_merge_on_device`).
     # (window_local_indices needs every window's pair list on the host: the keys go through the builders then, `_merged_rows`.)
-    accs = None
-    device_table = builders[0].device_columns_possible() and os.environ.get("SAME_TABLE_COLUMNS", "device") != "host"
-    if not with_ref_idx and (merge or (device_table and not job.all_matches)):
-        accs = _begin_accumulators(job, frames, contexts, cut, channel if merge else None)
-    if priority:                      # once, here: before a worker thread stages its first window (as the id codes above)
-        frames.label_codes_on_device()
-    pos_of = {id(w): pos for pos, w in job.todo}
+    accs, extra = None, []
+    device_table = builders[0][0].device_columns_possible() and os.environ.get("SAME_TABLE_COLUMNS", "device") != "host"
+    stats = [{} for _ in jobs]
+    try:
+        if not with_ref_idx and (merge or (device_table and not job.all_matches)):
+            # job 0 takes the frames' own accumulators (which also puts the id codes on the device), every further job a set of its own
+            accs = [_begin_accumulators(job, frames, contexts, cut, channel if merge else None)]
+            for _j in jobs[1:]:
+                mine = [MergeAccumulator(c) for c in contexts]
+                extra.extend(mine)
+                for q, acc in enumerate(mine):
+                    acc.begin(sum(w["n_mov"] for _pos, w in job.todo[cut[q]:cut[q + 1]]))
+                accs.append(mine)
+        if priority:                      # once, here: before a worker thread stages its first window (as the id codes above)
+            frames.label_codes_on_device()
+        pos_of = {id(w): pos for pos, w in job.todo}
+        sets = [(j.optim_params["knn"], j.mode, j.optim_params["no_match_penalty"]) for j in jobs]
 
-    def walk(q):
-        mine = job.todo[cut[q]:cut[q + 1]]
-        collector = None
-        if accs is not None:
-            collector = lambda states, windows: accs[q].collect(states, [w["trim"] for w in windows], [w["window_id"] for w in windows],
-                                                                [pos_of[id(w)] for w in windows])
-        for (pos, w), dw in zip(mine, frames.windows([w for _p, w in mine], ctx=contexts[q], triangulator=triangulator,
-                                                     collector=collector, batch=batch, mode=job.mode, caller=caller, priority=priority)):
-            if dw.error is not None:
-                raise _window_error(dw, job.optim_params)      # (the priority prune's own failure for a window without pairs)
-            if dw.skipped:                   # every pair went with the unconstrained nodes: nothing to match (as the general route)
-                continue
-            with stage("table rows (central trim)"):
-                if accs is None:
-                    builders[q].add(pos, w, dw, _device_ref_idx(dw) if with_ref_idx else None)
-                rec = _device_stats(dw)
-            with lock:
-                stats[pos] = rec
+        def walk(q):
+            collector = None
+            if accs is not None:
+                collector = lambda states, windows, s: accs[s][q].collect(states, [w["trim"] for w in windows],
+                                                                          [w["window_id"] for w in windows],
+                                                                          [pos_of[id(w)] for w in windows])
+            for dw in frames.windows([w for _p, w in job.todo[cut[q]:cut[q + 1]]], ctx=contexts[q], triangulator=triangulator,
+                                     collector=collector, batch=batch, caller=caller, priority=priority, sets=sets):
+                s, pos = dw.set, pos_of[id(dw.window)]
+                if dw.error is not None:
+                    raise _window_error(dw, jobs[s].optim_params)      # (the priority prune's own failure for a window without pairs)
+                if dw.skipped:                   # every pair went with the unconstrained nodes: nothing to match (as the general route)
+                    continue
+                with stage("table rows (central trim)"):
+                    if accs is None:
+                        builders[s][q].add(pos, dw.window, dw, _device_ref_idx(dw) if with_ref_idx else None)
+                    rec = _device_stats(dw)
+                with lock:
+                    stats[s][pos] = rec
 
-    if n_workers == 1:
-        walk(0)
-    else:
-        errors = []
+        if n_workers == 1:
+            walk(0)
+        else:
+            errors = []
 
-        def guarded(q):
-            try:
-                walk(q)
-            except BaseException as e:   # noqa: BLE001 -- re-raised in the calling thread below
-                errors.append(e)
+            def guarded(q):
+                try:
+                    walk(q)
+                except BaseException as e:   # noqa: BLE001 -- re-raised in the calling thread below
+                    errors.append(e)
 
-        threads = [threading.Thread(target=guarded, args=(q,), name=f"same-windows-{q}") for q in range(n_workers)]
-        [t.start() for t in threads]
-        [t.join() for t in threads]
-        if errors:
-            raise errors[0]
-    return _route_table(job, frames, builders, accs, merge, channel, device_table)
+            threads = [threading.Thread(target=guarded, args=(q,), name=f"same-windows-{q}") for q in range(n_workers)]
+            [t.start() for t in threads]
+            [t.join() for t in threads]
+            if errors:
+                raise errors[0]
+        return [(_route_table(j, frames, builders[s], None if accs is None else accs[s], merge, channel, device_table), stats[s])
+                for s, j in enumerate(jobs)]
+    finally:
+        for acc in extra:
+            acc.close()
 
 
 def _route_table(job, frames, builders, accs, merge, channel, device_table):

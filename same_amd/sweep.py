@@ -11,12 +11,11 @@ As single jobs every point stages and triangulates every window again, although 
 
 So the sweep stages every window once at the largest `knn`, triangulates it once, and finishes it once per set
 (windows.iter_device_windows with `sets`).  `sliding_window_sweep(...)[i]` is `sliding_window_incumbent` under
-{**optim_params, **param_sets[i]}: table, dtypes, row order, stats."""
-import threading
-
-from .incumbent import (_TableBuilder, _begin_accumulators, _default_workers, _device_ref_idx, _device_stats, _route_table,
-                        sliding_window_incumbent)
-from .window_api import ResidentFrames, _WindowJob, _window_error
+{**optim_params, **param_sets[i]}: table, dtypes, row order, stats.  It is that function's own device route, too: a single job is a
+sweep of one set, and `incumbent._device_pass` walks the windows for either -- this module checks the sets, makes a job per set and
+shapes the result."""
+from .incumbent import _device_pass, sliding_window_incumbent
+from .window_api import ResidentFrames, _WindowJob
 from .window_mode import WindowMode, caller_delaunay_route, priority_prune_route
 
 # what a set may override: the keys that change neither a window's rows nor its triangulation
@@ -83,7 +82,8 @@ def sliding_window_sweep(ref, moving, param_sets, commonCT=None, *, optim_params
                 from . import delaunay
 
                 triangulator = delaunay.triangulator_for(op0)
-            return _sweep_device_route(jobs, frames, workers, window_local_indices, triangulator, merge, batch, priority, return_stats)
+            done = _device_pass(jobs, frames, workers, window_local_indices, triangulator, merge, None, batch, None, priority)
+            return [(table, [stats[pos] for pos in sorted(stats)]) if return_stats else table for table, stats in done]
     finally:
         if own and frames is not None:
             frames.close()
@@ -91,80 +91,3 @@ def sliding_window_sweep(ref, moving, param_sets, commonCT=None, *, optim_params
     return [sliding_window_incumbent(ref, moving, commonCT, optim_params=op, gurobi_params=gurobi_params, workers=workers,
                                      window_local_indices=window_local_indices, return_stats=return_stats, triangulator=triangulator,
                                      ctx=ctx, merge=merge, batch=batch) for op, _mode in checked]
-
-
-def _sweep_device_route(jobs, frames, workers, with_ref_idx, triangulator, merge, batch, priority, return_stats):
-    """incumbent._device_route for several jobs that differ in SWEEP_KEYS only (one plan, one share of it): the windows are walked once,
-    every set has its own builders, accumulators and stats, and its table is made by the single job's own tail (_route_table)."""
-    import os
-
-    from .windows import MergeAccumulator
-
-    job = jobs[0]
-    n_workers = max(1, int(workers if workers is not None else _default_workers()))
-    n_workers = min(n_workers, max(1, len(job.todo)))
-    contexts = frames.worker_contexts(n_workers)
-    sections = (frames.ref_sec, frames.mov_sec)
-    builders = [[_TableBuilder(j, sections, with_ref_idx) for _ in range(n_workers)] for j in jobs]
-    lock = threading.Lock()
-    cut = [len(job.todo) * q // n_workers for q in range(n_workers + 1)]
-    device_table = builders[0][0].device_columns_possible() and os.environ.get("SAME_TABLE_COLUMNS", "device") != "host"
-    accs, extra = None, []
-    stats = [{} for _ in jobs]
-    try:
-        if not with_ref_idx and (merge or device_table):
-            # set 0 takes the frames' own accumulators (which also puts the id codes on the device), every other set a set of its own
-            accs = [_begin_accumulators(job, frames, contexts, cut, None)]
-            for _j in jobs[1:]:
-                mine = [MergeAccumulator(c) for c in contexts]
-                extra.extend(mine)
-                for q, acc in enumerate(mine):
-                    acc.begin(sum(w["n_mov"] for _pos, w in job.todo[cut[q]:cut[q + 1]]))
-                accs.append(mine)
-        if priority:
-            frames.label_codes_on_device()
-        pos_of = {id(w): pos for pos, w in job.todo}
-        sets = [(j.optim_params["knn"], j.mode, j.optim_params["no_match_penalty"]) for j in jobs]
-
-        def walk(q):
-            mine = [w for _p, w in job.todo[cut[q]:cut[q + 1]]]
-            collector = None
-            if accs is not None:
-                collector = lambda states, windows, s: accs[s][q].collect(states, [w["trim"] for w in windows],
-                                                                          [w["window_id"] for w in windows],
-                                                                          [pos_of[id(w)] for w in windows])
-            for dw in frames.windows(mine, ctx=contexts[q], triangulator=triangulator, collector=collector, batch=batch,
-                                     priority=priority, sets=sets):
-                s, pos = dw.set, pos_of[id(dw.window)]
-                if dw.error is not None:
-                    raise _window_error(dw, jobs[s].optim_params)
-                if accs is None:
-                    builders[s][q].add(pos, dw.window, dw, _device_ref_idx(dw) if with_ref_idx else None)
-                rec = _device_stats(dw)
-                with lock:
-                    stats[s][pos] = rec
-
-        if n_workers == 1:
-            walk(0)
-        else:
-            errors = []
-
-            def guarded(q):
-                try:
-                    walk(q)
-                except BaseException as e:   # noqa: BLE001 -- re-raised in the calling thread below
-                    errors.append(e)
-
-            threads = [threading.Thread(target=guarded, args=(q,), name=f"same-sweep-{q}") for q in range(n_workers)]
-            [t.start() for t in threads]
-            [t.join() for t in threads]
-            if errors:
-                raise errors[0]
-        out = []
-        for s, j in enumerate(jobs):
-            table = _route_table(j, frames, builders[s], None if accs is None else accs[s], merge, None, device_table)
-            out.append((table, [stats[s][pos] for pos in sorted(stats[s])]) if return_stats else table)
-        return out
-    finally:
-        for acc in extra:
-            acc.close()

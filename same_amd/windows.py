@@ -361,31 +361,54 @@ def window_cell_grid(plan_or_grid, window_size, overlap):
     return float(xs[0]), float(ys[0]), cell
 
 
-class DeviceSection:
+class _DeviceHandle:
+    """The owner of one library object made on a context, stated once for the classes below: the create call (`_ENTRY[0]`; a create
+    that fails after it made something has that destroyed), `close()` through `_ENTRY[1]` and a `__del__` that cannot raise."""
+
+    _ENTRY = (None, None)        # the library's create and destroy entry points
+
+    def _create(self, ctx, *args):
+        """`handle` = what create(context, *args, &handle) makes on `ctx`, which becomes `self.ctx`"""
+        self.ctx = ctx = ops._ctx(ctx)
+        create, destroy = self._ENTRY
+        h = ctypes.c_void_p()
+        with ctx.lock:
+            rc = getattr(ctx.lib, create)(ctx.handle, *args, ctypes.byref(h))
+            if rc != 0 and h.value:
+                getattr(ctx.lib, destroy)(h)
+            ctx.check(rc, create)
+        self.handle = h
+
+    def close(self):
+        if getattr(self, "handle", None) and self.ctx.handle:        # a context that is already gone took its device memory along
+            with self.ctx.lock:
+                getattr(self.ctx.lib, self._ENTRY[1])(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceSection(_DeviceHandle):
     """A `Section`'s XY, type columns and sizes uploaded once (same_section_create) and binned into a grid of cells; every window
     reads them in place.  cost_dtype float32 keeps the cost operands as float (BASELINE cfg 5), float64 is the reference's
     arithmetic.  `bin(x0, y0, cell)` re-bins the rows on the window grid (window_cell_grid), on which a window's rows are
     whole cells: do it once, before the windows run."""
 
-    def __init__(self, section, cost_dtype=np.float64, ctx=None):
-        import ctypes
+    _ENTRY = ("same_section_create", "same_section_destroy")
 
-        self.ctx = ctx = ops._ctx(ctx)
+    def __init__(self, section, cost_dtype=np.float64, ctx=None):
         self.section = section
         self.cost_dtype = np.dtype(cost_dtype)
         if self.cost_dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
             raise ValueError(f"cost_dtype must be float64 or float32, not {self.cost_dtype}")
         size = np.ascontiguousarray(section.size, dtype=np.float64)
         tid = None if section.type_id is None else np.ascontiguousarray(section.type_id, dtype=np.int32)
-        h = ctypes.c_void_p()
-        with ctx.lock:
-            rc = ctx.lib.same_section_create(ctx.handle, section.xy.ctypes.data, section.types.ctypes.data, section.types.shape[1],
-                                             size.ctypes.data, None if tid is None else tid.ctypes.data, len(section.xy),
-                                             int(self.cost_dtype == np.dtype(np.float32)), ctypes.byref(h))
-            if rc != 0 and h.value:
-                ctx.lib.same_section_destroy(h)
-            ctx.check(rc, "same_section_create")
-        self.handle = h
+        self._create(ctx, section.xy.ctypes.data, section.types.ctypes.data, section.types.shape[1], size.ctypes.data,
+                     None if tid is None else tid.ctypes.data, len(section.xy), int(self.cost_dtype == np.dtype(np.float32)))
 
     def bin(self, x0, y0, cell_w, cell_h=None):
         with self.ctx.lock:
@@ -407,34 +430,15 @@ class DeviceSection:
         cell-type-priority prune on the device compares (priority_windows).  A slot of its own, beside the merge's id codes."""
         ops.section_set_label_codes(self.ctx, self.handle, codes, len(self.section.xy))
 
-    def close(self):
-        if getattr(self, "handle", None) and self.ctx.handle:        # a context that is already gone took its device memory along
-            with self.ctx.lock:
-                self.ctx.lib.same_section_destroy(self.handle)
-        self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DeviceWindow:
+class DeviceWindow(_DeviceHandle):
     """Device state of one window in flight (same_window): `stage` then `filter_finish` (or `finish` with triangles filtered by the
     caller), arrays of the state through `fetch`.  `stage_windows` / `filter_finish_windows` run a BATCH of windows per library call."""
 
-    def __init__(self, ctx=None):
-        import ctypes
+    _ENTRY = ("same_window_create", "same_window_destroy")
 
-        self.ctx = ctx = ops._ctx(ctx)
-        h = ctypes.c_void_p()
-        with ctx.lock:
-            rc = ctx.lib.same_window_create(ctx.handle, ctypes.byref(h))
-            if rc != 0 and h.value:
-                ctx.lib.same_window_destroy(h)
-            ctx.check(rc, "same_window_create")
-        self.handle = h
+    def __init__(self, ctx=None):
+        self._create(ctx)
         self.counts = (0, 0, 0, 0)
         self.n_triangles = 0
         self.n_staged_pairs = self.n_selected = 0      # pairs as staged; the caller's triangles over the staged cells (caller_tris_windows)
@@ -499,18 +503,6 @@ class DeviceWindow:
         self.refine = mode.records(stats, start=False)[1]
         return match_row, flag, dict(zip(self.STAT_NAMES, stats[:8].tolist()))
 
-    def close(self):
-        if getattr(self, "handle", None) and self.ctx.handle:
-            with self.ctx.lock:
-                self.ctx.lib.same_window_destroy(self.handle)
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # SAME_MERGE_REST
 REST_RECORD = np.dtype([("row", "<i4"), ("ac", "<i4"), ("rc", "<i4"), ("wid", "<i4"), ("pos", "<i4"), ("cidx", "<i4"), ("flags", "<u4")])
@@ -536,7 +528,6 @@ class _PinnedBlocks:
 
     def take(self, ctx, nbytes):
         """-> (ctypes char array over a pinned block of >= nbytes, address) or None"""
-        import ctypes
         import weakref
 
         self._release_surplus()
@@ -594,21 +585,14 @@ class _PinnedBlocks:
 PINNED_BLOCKS = _PinnedBlocks()
 
 
-class MergeAccumulator:
+class MergeAccumulator(_DeviceHandle):
     """The rows of one pass over a window plan on one context (same_merge_acc, csrc/window_merge.hip): `collect` appends the matched cells
     of the windows' central regions where they are -- on the device --, `resolve_accumulators` / `finish` run the window merge on them."""
 
-    def __init__(self, ctx=None):
-        import ctypes
+    _ENTRY = ("same_merge_acc_create", "same_merge_acc_destroy")
 
-        self.ctx = ctx = ops._ctx(ctx)
-        h = ctypes.c_void_p()
-        with ctx.lock:
-            rc = ctx.lib.same_merge_acc_create(ctx.handle, ctypes.byref(h))
-            if rc != 0 and h.value:
-                ctx.lib.same_merge_acc_destroy(h)
-            ctx.check(rc, "same_merge_acc_create")
-        self.handle = h
+    def __init__(self, ctx=None):
+        self._create(ctx)
 
     def begin(self, expected_rows, near=None, reach=0.0, all_seam=False):
         """A new pass.  near = (near_start int32[n_pos + 1], near_boxes float64[.., 4]): per plan position the central regions of OTHER
@@ -649,8 +633,6 @@ class MergeAccumulator:
     def finish(self, winner_rows, fetch=True):
         """The REST rows the host's matching kept (accumulator row numbers) -> the merged table's rows, aligned codes ascending: as
         FINAL_RECORDs, or (fetch=False) only their number -- they stay on the device for `columns`; `final_rows()` fetches them later."""
-        import ctypes
-
         ctx = self.ctx
         w = np.ascontiguousarray(winner_rows, dtype=np.int32)
         n = ctypes.c_int64(0)
@@ -672,8 +654,6 @@ class MergeAccumulator:
         columns (DeviceBuffers of 8-byte values per moving / reference row: ids, sizes), aligned_idx, window_id and plan position as int64,
         and the two flag columns.  -> (uint64 array (n_types + 4 + extras + 3, n_final), uint8 array (2, n_final)) over a pooled block,
         or None when no block is to be had (the caller gathers on the host)."""
-        import ctypes
-
         n8 = n_types + 4 + len(extra_moving) + len(extra_ref) + 3
         got = PINNED_BLOCKS.take(self.ctx, max(1, n8 * 8 * n_final + 2 * n_final)) if n_final else None
         if got is None:
@@ -690,24 +670,10 @@ class MergeAccumulator:
         flags = np.frombuffer(buf, dtype=np.uint8, count=2 * n_final, offset=n8 * 8 * n_final).reshape(2, n_final)
         return wide, flags
 
-    def close(self):
-        if getattr(self, "handle", None) and self.ctx.handle:
-            with self.ctx.lock:
-                self.ctx.lib.same_merge_acc_destroy(self.handle)
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def plain_accumulators(accs):
     """The pass is over and its table is wanted WITHOUT the merge: every accumulated row is a row of the table, windows in the order they
     were collected.  -> accs[0], holding the rows (`.n_final`, `.final_rows()`, `.columns(...)`)."""
-    import ctypes
-
     ctx = accs[0].ctx
     n = ctypes.c_int64(0)
     handles = (ctypes.c_void_p * len(accs))(*[a.handle.value for a in accs])
@@ -721,8 +687,6 @@ def resolve_accumulators(accs, dmoving, dref):
     """The pass is over: the accumulators of the worker contexts (in the order their runs of the plan have) -> ((rows, rows after the
     de-duplication, rest rows, rows final already), the REST rows as REST_RECORDs): what the device could not decide alone -- cells some
     window disagrees about, rows at a seam between ranks -- for merge.py's graph step; `accs[0].finish(winners)` completes the merge."""
-    import ctypes
-
     ctx = accs[0].ctx
     counts = np.zeros(4, np.int64)
     handles = (ctypes.c_void_p * len(accs))(*[a.handle.value for a in accs])
@@ -738,8 +702,6 @@ WINDOW_BATCH_MAX = 64      # SAME_WINDOW_BATCH_MAX
 
 
 def _handles(states):
-    import ctypes
-
     return (ctypes.c_void_p * len(states))(*[s.handle.value for s in states])
 
 
@@ -789,35 +751,17 @@ def prefix_windows(states, k):
     return [s.counts for s in states]
 
 
-class DeviceCallerTris:
+class DeviceCallerTris(_DeviceHandle):
     """A caller's triangulation of a moving section resident on the device (same_caller_tris_create, csrc/window_caller.hip): `rows`
     int32 (Tr, 3) section rows in the caller's order (window_api.caller_triangulation_rows), uploaded once and binned by the grid the
     section has NOW -- bin the section on the window grid first.  Read-only: the worker contexts of the device share it."""
 
+    _ENTRY = ("same_caller_tris_create", "same_caller_tris_destroy")
+
     def __init__(self, dsection, rows, ctx=None):
-        self.ctx = ctx = ops._ctx(ctx)
         rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, 3)
         self.n_triangles = len(rows)
-        h = ctypes.c_void_p()
-        with ctx.lock:
-            rc = ctx.lib.same_caller_tris_create(ctx.handle, dsection.handle, rows.ctypes.data if len(rows) else None, len(rows),
-                                                 ctypes.byref(h))
-            if rc != 0 and h.value:
-                ctx.lib.same_caller_tris_destroy(h)
-            ctx.check(rc, "same_caller_tris_create")
-        self.handle = h
-
-    def close(self):
-        if getattr(self, "handle", None) and self.ctx.handle:
-            with self.ctx.lock:
-                self.ctx.lib.same_caller_tris_destroy(self.handle)
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(ctx, dsection.handle, rows.ctypes.data if len(rows) else None, len(rows))
 
 
 def caller_tris_windows(states, caller, radius, angle_enabled, cos_thr, near_tol, ignore_same_type, removed=None):
@@ -974,6 +918,19 @@ class DeviceWindowResult:
         self.mode = mode
 
 
+class _StagedWindow:
+    """What a batch's stage step of `iter_device_windows` leaves of one window, shared by the window's results: `window`; `error` (no
+    pairs) or `skipped` / `removed` (a caller's triangulation); `rows_m`, `axy`; `triangles` a caller's, where the host filtered them;
+    `state` and `ticket` of a window that goes on to the finish calls, else None and `counts`, `priority` what the stage step left."""
+
+    __slots__ = ("window", "error", "skipped", "removed", "rows_m", "axy", "triangles", "counts", "priority", "state", "ticket")
+
+    def __init__(self, window):
+        self.window = window
+        for name in self.__slots__[1:]:
+            setattr(self, name, None)
+
+
 class TriangulationCache(QhullTriangulator):
     """Delaunay simplices remembered per window (a DIAGNOSTIC: bench.py's "what would a pass cost if the triangulations were free").
     `submit(points, key)` hands back the simplices of `key` when it has seen the window before, else asks the helper pool and keeps
@@ -1006,23 +963,34 @@ class TriangulationCache(QhullTriangulator):
 def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dist_ct_coeff=1.0, min_angle_deg=15,
                         ignore_same_type_triangles=True, no_match_penalty=100.0, ctx=None, fetch_triangles=False, triangulator=None,
                         triangulate=True, batch=None, collector=None, mode=None, caller=None, priority=False, sets=None):
-    """The window path of `iter_window_arrays` + the greedy incumbent and the three sweeps, with both sections resident on the
-    device (`dref`, `dmoving`: DeviceSections of `ref`, `moving`): per window the host only triangulates (Qhull helpers, windows
-    ahead as before) and receives the match; the triangle filter runs on the device too, unless a cosine sits within 8 ulp of the
-    angle threshold (then the host re-decides it with the reference's literal expression, as triangles.classify_triangles does).  Yields one
-    DeviceWindowResult per window in plan order; the numbers are those of the column pipeline
-    (tests/test_gpu_run_same.py::test_device_windows_equal_the_column_pipeline).  A window without pairs yields `.error`.
-    Windows go to the library in BATCHES of `batch` (default $SAME_WINDOW_BATCH, else 8): one stage call, and later one filter + finish
-    call, for up to that many windows -- one wait per call instead of one per window, and the device works on one window while the host
-    enqueues the next.  The states of a batch stay live (`result.state`) until the generator is asked for the first window of the next.
+    """The window path of `iter_window_arrays` + the incumbent and the three sweeps, with both sections resident on the device (`dref`,
+    `dmoving`: DeviceSections of `ref`, `moving`): per window the host only triangulates (Qhull helpers, windows ahead as before) and
+    receives the match; the triangle filter runs on the device too, unless a cosine sits within 8 ulp of the angle threshold (then the
+    host re-decides it with the reference's literal expression, as triangles.classify_triangles does).  The numbers are those of the
+    column pipeline (tests/test_gpu_run_same.py::test_device_windows_equal_the_column_pipeline).  A window without pairs yields `.error`.
+    What a window is finished under is a SET, a (knn, WindowMode, no_match_penalty) triple.  The plain form has one, (`knn`, `mode`,
+    `no_match_penalty`), and yields one DeviceWindowResult per window in plan order, `result.set` None.  `sets=[...]` is a parameter sweep
+    over ONE pass (then `knn`, `mode` and `no_match_penalty` are not read): every window is staged once, at the largest knn, and
+    triangulated once, and finished once per set; per batch the results come set by set in the order the sets are taken (below), one
+    per window each, `result.set` the set's index; `mode`, `counts`, `priority` and everything the finish call leaves are that set's,
+    `rows_m` / `axy` are shared by the window's results, and a result's `state` is live only until the next set's finish.  A list of one
+    set makes the calls of the plain form; more than one does not go with `caller` or `triangulate=False`.
+    Windows go to the library in BATCHES of `batch` (default $SAME_WINDOW_BATCH, else 8): one stage call, and later per set one filter +
+    finish call, for up to that many windows -- one wait per call instead of one per window, and the device works on one window while
+    the host enqueues the next.  The states of a batch stay live (`result.state`) until the generator is asked for the first window of
+    the next.  The sets of a batch are taken grouped by knn, largest first -- the first group's list is the list as staged; before
+    every other group ONE `prefix_windows` call cuts the pair lists to its knn (a batch sees at most one per distinct value) -- and
+    within a group in the order given.
     `triangulator`: the route, a delaunay.Triangulator (default: delaunay.QHULL, the Qhull helper pool).  It says how many windows to
     stage ahead and whether to start the helpers first; each window is submitted when it is staged, and the route's per-batch hook runs
-    right before the batch's filter + finish call.  A ticket's `.result()` is the simplices, or None for candidates the device made; one
-    whose `.native` is true after `.result()` brought simplices that are not scipy's own and has `.qhull()` for those (delaunay.py).
+    right before the batch's first filter + finish call.  A ticket's `.result()` is the simplices, or None for candidates the device
+    made; one whose `.native` is true after `.result()` brought simplices that are not scipy's own and has `.qhull()` for those
+    (delaunay.py).  One ticket per window serves every set: scipy's simplices, once a set's order ties asked for them, are the ticket's
+    answer for the sets after it.
     `triangulate=False` stops after the stage call (rows, prune, costs, compaction): the caller brings its own triangles
     (api.sliding_window_matching with a caller's triangulation) and reads pairs / costs through `state.fetch`.
-    `collector(states, windows)` is called once per finished batch with its windows' live states (the window merge's accumulator:
-    MergeAccumulator.collect).
+    `collector(states, windows)` -- with `sets`: `collector(states, windows, set index)` -- is called once per finished batch and set
+    with its windows' live states (the window merge's accumulator: MergeAccumulator.collect).
     `caller`: a DeviceCallerTris of `dmoving` -- the triangulation source that needs no triangulator (`triangulator`, and with it
     optim_params["hip_delaunay"], is irrelevant then: nothing is triangulated).  Right after a batch's stage call ONE more call selects
     and remaps every window's triangles, works out the filter's node mask and leaves the window without its unconstrained nodes
@@ -1032,21 +1000,13 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
     prefiltered forms of both calls.
     `priority`: the cell-type-priority prune (optim_params["ignore_knn_if_matched"], src/knn_utils.py:28-78) on the device: right after a
     batch's stage call -- before anything is triangulated, before the caller's triangles are selected, as the reference filters its pairs
-    before it triangulates -- ONE more call filters every window's pair list (priority_windows); both sections need their label codes
-    (DeviceSection.set_label_codes).  `counts[3]`, the pairs and costs a state hands out and everything later are the filtered list's;
-    the pair list as staged stays fetchable (_W_STAGED_PAIRS) and stays the frame of the reference limits.
-    `mode`: a WindowMode (None: the greedy start alone).  A window whose optimal start the device does not certify is solved again on
+    before it triangulates -- ONE more call filters every window's pair list (priority_windows), and one more after every prefix call,
+    which hands back an unpruned list; both sections need their label codes (DeviceSection.set_label_codes).  `counts[3]`, the pairs and
+    costs a state hands out and everything later are the filtered list's; the pair list as staged (or as cut) stays fetchable
+    (_W_STAGED_PAIRS) and stays the frame of the reference limits.
+    A set's WindowMode (None: the greedy start alone): a window whose optimal start the device does not certify is solved again on
     the host (ops.sparse_assign_host, ops.sparse_transport_host) and finished again under that matching; every later finish of a window
-    (that fallback, a re-finish with scipy's simplices) runs the mode's search again: `result.refine` holds the last one's counts.
-    `sets`: a parameter sweep over ONE pass -- a list of (knn, WindowMode, no_match_penalty) triples (then `knn`, `mode` and
-    `no_match_penalty` are not read).  Every batch is staged once at the largest knn and triangulated once, and finished once per set:
-    the sets are taken grouped by knn, largest first (a batch sees at most one prefix call per distinct value); per group a
-    `prefix_windows` call where its knn is not the current list's, then `priority_windows` if the job has the priority prune, then per
-    set of the group filter + finish under its mode and penalty.  One ticket per window serves every set: scipy's simplices, once a set's
-    order ties asked for them, are the ticket's answer for the sets after it.  Yields, per batch, one DeviceWindowResult per window for
-    the first set taken, then for the next ... (`result.set` says which); a result's `state` is live only until the next set's finish.
-    `collector(states, windows, set index)` is called per batch and set.  Not with `caller` or `triangulate=False`."""
-    import os
+    (that fallback, a re-finish with scipy's simplices) runs the mode's search again: `result.refine` holds the last one's counts."""
     from collections import deque
 
     from . import qhull_pool
@@ -1054,14 +1014,15 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
     from .triangles import cos_threshold, filter_triangles_by_radius
 
     ctx = ops._ctx(ctx)
-    mode = WindowMode.default() if mode is None else mode
-    if sets is not None:
-        if caller is not None or not triangulate or not sets:
-            raise ValueError("sets: at least one, with windows triangulated by the route (no caller's triangulation)")
-        sets = [(int(k), WindowMode.default() if m is None else m, float(p)) for k, m, p in sets]
-        knn = max(k for k, _m, _p in sets)
-        # the sets grouped by knn, largest first (the first group is the list as staged)
-        set_groups = [(k, [q for q, st in enumerate(sets) if st[0] == k]) for k in sorted({st[0] for st in sets}, reverse=True)]
+    # per set: (`result.set`, what the collector is told beside the states and the windows)
+    tags = [(None, ())] if sets is None else [(q, (q,)) for q in range(len(sets))]
+    sets = [(knn, mode, no_match_penalty)] if sets is None else [(int(k), m, float(p)) for k, m, p in sets]
+    if not sets or (len(sets) > 1 and (caller is not None or not triangulate)):
+        raise ValueError("sets: at least one; several only with windows triangulated by the route (no caller's triangulation)")
+    sets = [(k, WindowMode.default() if m is None else m, p) for k, m, p in sets]
+    knn = max(k for k, _m, _p in sets)
+    # the sets grouped by knn, largest first (the first group is the list as staged)
+    set_groups = [(k, [q for q, st in enumerate(sets) if st[0] == k]) for k in sorted({st[0] for st in sets}, reverse=True)]
     angle_enabled, cos_thr = cos_threshold(min_angle_deg)
     near_tol = float(8 * np.spacing(abs(cos_thr))) if (angle_enabled and np.isfinite(cos_thr)) else 0.0
     tri = QHULL if triangulator is None else triangulator
@@ -1088,12 +1049,12 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
         return free.pop() if free else DeviceWindow(ctx)
 
     def stage_batch(windows):
-        """-> [(result, state or None, ticket or None)] for `windows`, staged by ONE library call"""
-        outs = [DeviceWindowResult(w, mode) for w in windows]
+        """-> a _StagedWindow per window of `windows`, staged by ONE library call"""
+        staged = [_StagedWindow(w) for w in windows]
         if not prune_possible:
-            for out in outs:
-                out.error = ValueError("No valid_pairs after KNN filtering. Increase radius and/or knn.")
-            return [(out, None, None) for out in outs]
+            for rec in staged:
+                rec.error = ValueError("No valid_pairs after KNN filtering. Increase radius and/or knn.")
+            return staged
         states = [take_state() for _ in windows]
         try:
             with marked("subset + prune + costs + compaction (device)"):
@@ -1101,51 +1062,47 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
         except BaseException:
             free.extend(states)                       # a refused batch (SAME_EINVAL ...) must not take its states out of the pool
             raise
-        if priority and sets is None:                 # (a sweep prunes per knn group, right before the group's finish calls)
+        if priority:                                  # the list as staged is pruned here; a list cut later by its knn group (finish_sets)
             try:
                 with marked("cell-type-priority prune of the pair lists (device)"):
                     priority_windows(states)
                 counts = [st.counts for st in states]
-                for out, st in zip(outs, states):
-                    out.priority = st.priority
+                for rec, st in zip(staged, states):
+                    rec.priority = st.priority
             except BaseException:
                 free.extend(states)
                 raise
         if caller is not None:
             try:
                 with marked("caller's triangles: select + remap + node mask + second compaction (device)"):
-                    caller_front([(out, st) for out, st, c in zip(outs, states, counts) if c[3] != 0])
+                    caller_front([(rec, st) for rec, st, c in zip(staged, states, counts) if c[3] != 0])
                 counts = [st.counts for st in states]
             except BaseException:
                 free.extend(states)
                 raise
-        staged = []
-        for q, (out, state) in enumerate(zip(outs, states)):
-            out.counts = counts[q]
-            if out.skipped:
+        for q, (rec, state) in enumerate(zip(staged, states)):
+            rec.counts = counts[q]
+            if rec.skipped:
                 free.append(state)
-                staged.append((out, None, None))
                 continue
-            if out.counts[3] == 0:
+            if rec.counts[3] == 0:
                 free.append(state)
-                out.error = ValueError("No valid_pairs after KNN filtering. Increase radius and/or knn.")
-                staged.append((out, None, None))
+                rec.error = ValueError("No valid_pairs after KNN filtering. Increase radius and/or knn.")
                 continue
-            ticket = None
             try:
-                out.rows_m, out.axy = state.fetch(_W_ALIGNED_ROWS), state.fetch(_W_ALIGNED_XY)
+                rec.rows_m, rec.axy = state.fetch(_W_ALIGNED_ROWS), state.fetch(_W_ALIGNED_XY)
                 if triangulate and caller is None:
                     with marked("triangulate (hand-over; waits for a free helper)"):
-                        ticket = tri.submit(out.axy, key=out.window.get("window_id"))
+                        rec.ticket = tri.submit(rec.axy, key=rec.window.get("window_id"))
             except BaseException:
                 free.extend(st for st in states[q:])
-                free.extend(st for _o, st, _t in staged if st is not None)
+                free.extend(done.state for done in staged[:q] if done.state is not None)
                 raise
-            staged.append((out, state, ticket))
+            rec.state = state
         return staged
 
     def caller_front(pairs_of):
-        """the staged windows [(result, state)] that have pairs: their triangles from `caller`, their unconstrained nodes gone"""
+        """the staged windows [(record, state)] that have pairs: their triangles from `caller`, their unconstrained nodes gone"""
         if not pairs_of:
             return
         states = [st for _o, st in pairs_of]
@@ -1168,7 +1125,7 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
             out.removed = got[q][1]
             out.skipped = got[q][4] == 0          # every node unconstrained, or the removed ones held every pair
 
-    def finish_callers(todo, states, args):
+    def finish_callers(todo, states, args, no_match_penalty, mode):
         """the finish call over the caller's triangles, which are on the device (SAME_TRIS_CALLER); a window the host filtered
         (caller_front) brings its kept list.  -> (result per window, no simplices)"""
         with marked("filter + signs + incumbent + sweeps (device)"):
@@ -1181,7 +1138,7 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
             raise RuntimeError("a cosine at the angle threshold that same_window_caller_tris did not report")
         return res, [None] * len(todo)
 
-    def finish_triangulated(states, tickets, args, mode=mode, first=True):
+    def finish_triangulated(states, tickets, args, mode, first):
         """the finish call over the triangulator's answers -> (result per window, simplices per window); `first`: the batch's first
         finish (the route's per-batch hook runs once; a ticket keeps its answer)"""
         if first:
@@ -1205,17 +1162,26 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
                     res[q] = filter_finish_windows([state], [tris[q]], *args, mode=mode)[0]
         return res, tris
 
-    def finish_batch(group, mode=mode, no_match_penalty=no_match_penalty, first=True, which=None):
-        """filter + signs + incumbent + sweeps of the staged windows of `group`, by ONE library call (+ one per window whose filter met a
-        cosine at the threshold); `which`: the set of a sweep this finish is for (its mode and penalty; `first`: the batch's first)"""
-        todo = [(out, state, ticket) for out, state, ticket in group if state is not None]
-        for out, state, _t in todo:
-            out.state, out.n_triangles = state, 0
+    def finish_set(group, which, first):
+        """-> a DeviceWindowResult per staged window of `group` under set `which`: filter + signs + incumbent + sweeps of the windows
+        that have a state, by ONE library call (+ one per window whose filter met a cosine at the threshold); `first`: the batch's
+        first finish.  A result is the staged record + the state as the set's knn group left it + what the call leaves."""
+        _k, mode, no_match_penalty = sets[which]
+        outs = []
+        for rec in group:
+            out = DeviceWindowResult(rec.window, mode)
+            out.set, out.error, out.skipped, out.removed = tags[which][0], rec.error, rec.skipped, rec.removed
+            out.rows_m, out.axy, out.triangles, out.state = rec.rows_m, rec.axy, rec.triangles, rec.state
+            out.counts, out.priority = (rec.counts, rec.priority) if rec.state is None else (rec.state.counts, rec.state.priority)
+            outs.append(out)
+        todo = [(out, rec.state, rec.ticket) for out, rec in zip(outs, group) if rec.state is not None]
+        for out, _s, _t in todo:
+            out.n_triangles = 0
         if not triangulate or not todo:
-            return
+            return outs
         states, tickets = [st for _o, st, _t in todo], [t for _o, _s, t in todo]
         args = (radius, angle_enabled, cos_thr, near_tol, ignore_same_type_triangles, no_match_penalty)
-        res, tris = (finish_callers(todo, states, args) if caller is not None
+        res, tris = (finish_callers(todo, states, args, no_match_penalty, mode) if caller is not None
                      else finish_triangulated(states, tickets, args, mode, first))
         for q, (out, state, _t) in enumerate(todo):
             _kept, _added, near, match_row, cell_flags, stats = res[q]
@@ -1242,35 +1208,25 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
                 out.triangles = state.fetch(_W_TRIANGLES)
         if collector is not None:
             with marked("central rows to the merge accumulator (device, enqueue only)"):
-                collector(states, [o.window for o, _s, _t in todo], *(() if which is None else (which,)))
+                collector(states, [o.window for o, _s, _t in todo], *tags[which][1])
+        return outs
 
-    def sweep_batch(group):
-        """the staged, submitted windows of `group` finished once per set -> yields the sets' results, group by group of equal knn"""
-        states = [state for _o, state, _t in group if state is not None]
-        current, first = knn, True
+    def finish_sets(group):
+        """the staged windows of `group` finished once per set, knn group by knn group -> yields every set's results"""
+        states = [rec.state for rec in group if rec.state is not None]
+        current, pruned, first = knn, priority, True          # (stage_batch pruned the list as staged)
         for k, members in set_groups:
             if states and k != current:
                 with marked("pair lists cut to the set's knn (device)"):
                     prefix_windows(states, k)
-                current = k
-            if states and priority:
+                current, pruned = k, False
+            if states and priority and not pruned:
                 with marked("cell-type-priority prune of the pair lists (device)"):
                     priority_windows(states)
+                pruned = True
             for which in members:
-                _k, set_mode, penalty = sets[which]
-                mine = []
-                for out, state, ticket in group:
-                    res = DeviceWindowResult(out.window, set_mode)
-                    res.set, res.error, res.skipped = which, out.error, out.skipped
-                    if state is not None:
-                        res.rows_m, res.axy, res.counts, res.priority = out.rows_m, out.axy, state.counts, state.priority
-                    else:
-                        res.counts = out.counts
-                    mine.append((res, state, ticket))
-                finish_batch(mine, set_mode, penalty, first, which)
+                yield from finish_set(group, which, first)
                 first = False
-                for res, _state, _ticket in mine:
-                    yield res
 
     pending, live, nxt = deque(), [], 0
     try:
@@ -1282,15 +1238,10 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
             free.extend(live)                     # the caller has moved on: the previous batch's states go back to the pool
             live = []
             group = [pending.popleft() for _ in range(min(B, len(pending)))]
-            live = [state for _o, state, _t in group if state is not None]
-            if sets is not None:
-                yield from sweep_batch(group)
-                continue
-            finish_batch(group)
-            for out, _state, _ticket in group:
-                yield out
+            live = [rec.state for rec in group if rec.state is not None]
+            yield from finish_sets(group)
     finally:
-        free.extend(state for _o, state, _t in pending if state is not None)
+        free.extend(rec.state for rec in pending if rec.state is not None)
         free.extend(live)
         cache.extend(free)
         for extra in cache[want:]:            # a context keeps what one pass needs, not every state it ever had

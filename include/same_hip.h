@@ -525,13 +525,29 @@ int same_window_refinish_cap(same_window *window, const int32_t *match_pair, dou
  *     .. removed_offsets[i + 1]) holds one byte per kept cell as staged of window i, non-zero = unconstrained; no classification, the
  *     third count is 0 -- and finishes with SAME_TRIS_KEPT and its own kept list (renumbered).  removed NULL <=> removed_offsets NULL.
  *     A window without kept cells, or a triangulation without triangles, launches nothing over an empty grid.  SAME_EINVAL: a window
- *     not staged, not staged over the triangulation's section, or staged before the section was binned again; bad offsets. */
+ *     not staged, not staged over the triangulation's section, or staged before the section was binned again; bad offsets.
+ *   same_window_caller_pairs: the pair half of the second compaction again, for a sweep over knn.  Which rows a window keeps, which of the
+ *     caller's triangles are its own, the node mask and the renumbering do not depend on k; only the pair list behind the mask does.
+ *     After same_window_knn_prefix on a window same_window_caller_tris compacted (below: the window is as staged at the smaller k and
+ *     HOLDS the selection) -- and same_window_priority_pairs where the job prunes -- this call, for each window of the batch that holds
+ *     a selection (ONE wait; none when nothing is launched), pushes the window's current pair list through the held mask: pairs of
+ *     removed rows go, pair rows are renumbered, reference numbers, reference section rows and costs are copied bit for bit; the aligned
+ *     side and the triangles are NOT recomputed.  The window is from then on, array for array and count for count, the one
+ *     same_window_stage at that k [+ same_window_priority_pairs] + same_window_caller_tris leaves: every same_window_fetch array, the
+ *     frame of the _cap calls' reference limits (the list as staged at that k), SAME_WINDOW_CALLER_TRIANGLES; same_window_filter_finish
+ *     follows with SAME_TRIS_CALLER, or -- a window whose mask the host made (the prefiltered form) -- with SAME_TRIS_KEPT and the host's
+ *     kept list, as after same_window_caller_tris.  out_counts[6 i ..] as same_window_caller_tris reports them (the third is 0).  A
+ *     window without kept cells holds nothing and is passed over (its counts are 0).  SAME_EINVAL before anything changes, and for the
+ *     whole batch: a window with kept cells that holds no selection (never given same_window_caller_tris, left as staged by it, or not
+ *     cut by same_window_knn_prefix since), a window not staged, a window filtered or finished since its last prefix.  A batch that
+ *     fails later leaves its windows unstaged, as same_window_knn_prefix does. */
 typedef struct same_caller_tris same_caller_tris;
 int same_caller_tris_create(same_ctx *ctx, const same_section *moving, const int32_t *tris, int64_t n_tris, same_caller_tris **out);
 void same_caller_tris_destroy(same_caller_tris *tris);
 int same_window_caller_tris(same_window *const *windows, int n_windows, const same_caller_tris *tris, const uint8_t *removed,
                             const int64_t *removed_offsets, double radius, int angle_enabled, double cos_thr, double near_tol,
                             int ignore_same_type, int64_t *out_counts);
+int same_window_caller_pairs(same_window *const *windows, int n_windows, int64_t *out_counts);
 
 /* ---- the cell-type-priority prune on the window path (csrc/window_priority.hip): src/knn_utils.py:28-78, switched by
  * optim_params["ignore_knn_if_matched"] at src/same.py:974-976, with the frames resident.  The reference re-sorts every aligned row's
@@ -570,8 +586,12 @@ int same_window_priority_pairs(same_window *const *windows, int n_windows, int64
  *     the stage call put it: every call derives from IT, so values of k may come in any order, and k == k_staged turns the window back
  *     to it without a launch.  same_window_priority_pairs and both finish calls run on the window as after a stage call; an earlier
  *     priority prune or finish of the window no longer holds.  out_counts[4 i ..] as same_window_stage reports them.  A window without
- *     pairs launches nothing.  SAME_EINVAL before anything changes: k < 1, k above the k a window was staged at, a window not staged, or
- *     one same_window_caller_tris has compacted. */
+ *     pairs launches nothing.  A window same_window_caller_tris has compacted (either form of that call) is turned back to the arrays
+ *     of its stage call first -- the aligned side as staged, the staged counts, XY and rows -- and cut like any other: it is the window
+ *     a stage call at k leaves, and it HOLDS the caller's selection (node mask, renumbering, compacted aligned side, renumbered
+ *     triangles) for same_window_caller_pairs (above); same_window_priority_pairs may come between the two.  A same_window_caller_tris
+ *     call on such a window works from the cut list and replaces what is held; a stage call drops it.  SAME_EINVAL before anything
+ *     changes: k < 1, k above the k a window was staged at, a window not staged. */
 int same_window_knn_prefix(same_window *const *windows, int n_windows, int k, int64_t *out_counts);
 
 /* ---- a6 on the window path without the library call --------------------------------------------------------------------------

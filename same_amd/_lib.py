@@ -117,6 +117,7 @@ _PROTOTYPES = {
     "same_caller_tris_create": [c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(c_vp)],
     "same_caller_tris_destroy": [c_vp],
     "same_window_caller_tris": [c_vp, c_int, c_vp, c_vp, c_vp, c_dbl, c_int, c_dbl, c_dbl, c_int, c_vp],
+    "same_window_caller_pairs": [c_vp, c_int, c_vp],
     "same_section_set_label_codes": [c_vp, c_vp],
     "same_window_priority_pairs": [c_vp, c_int, c_vp],
     "same_window_knn_prefix": [c_vp, c_int, c_int, c_vp],

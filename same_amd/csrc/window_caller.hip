@@ -13,6 +13,17 @@
 // The compacted arrays live in the window's `caller` buffer and the window's pointers are turned to them: everything after this call --
 // the filter with the same-type re-add (which then meets no unconstrained node, :370), start, search, sweeps, collect -- is the
 // unchanged window path on the smaller window (same_window_filter_finish with SAME_TRIS_CALLER).  The REFERENCE side stays the prune's.
+// A parameter sweep over knn (same_window_caller_pairs).  Which rows a window keeps, which of the caller's triangles are its own, the node
+// mask and the renumbering do not depend on k: only the pair list behind the mask does, and the second compaction (whole rows of pairs
+// go) commutes with the k-NN prefix (every row is cut to its first min(k, count) pairs).  After same_window_knn_prefix turned the
+// compacted window back to the stage call's arrays -- the mask, the renumbering, the compacted aligned side and the renumbered
+// triangles stay in `caller`, held (same_window::Held) -- one call per batch pushes the window's CURRENT pair list through the held mask:
+//   row offsets    one ordered scan (scan.h) over the staged kept cells of valid[v] ? row count : 0 gives the new pair offsets and count
+//   scatter        one thread per pair of the current list: a pair of a row that stays goes to new_prow[newidx[row]] + place, its row
+//                  renumbered, its reference number, its reference's section row and its cost copied -- loads and stores run along
+//                  the pair index (the per-row loop of caller_cells_kernel, which also moves the aligned side, is not repeated)
+// into the pair arrays of `caller`, which were sized for the list as staged.  The window is then, array for array, the one a stage call
+// at k (+ the priority prune) + same_window_caller_tris leaves.
 #include "window_internal.h"
 
 namespace {
@@ -185,38 +196,21 @@ struct CallerPlan {
     ZeroArgs zero{};
     size_t back_bytes = 0;
     same_window::Staged next;          // the window's arrays once the removal counts
+    int64_t pair_cap = 0;              // pairs next's pair arrays hold
 };
-
-void turn_to(same_window *w, const same_window::Staged &s) {
-    w->counts = s.counts;
-    w->ua = s.ua;
-    w->rows_ua = s.rows_ua;
-    w->type_c = s.type_c;
-    w->prow = s.prow;
-    w->pairs = s.pairs;
-    w->jsec = s.jsec;
-    w->axy_c = s.axy_c;
-    w->size_c = s.size_c;
-    w->cost64 = s.cost64;
-    w->n_ua = s.n_ua;
-    w->P = s.P;
-}
-same_window::Staged staged_of(const same_window *w) {
-    same_window::Staged s;
-    s.counts = w->counts; s.ua = w->ua; s.rows_ua = w->rows_ua; s.type_c = w->type_c; s.prow = w->prow; s.pairs = w->pairs; s.jsec = w->jsec;
-    s.axy_c = w->axy_c; s.size_c = w->size_c; s.cost64 = w->cost64; s.n_ua = w->n_ua; s.P = w->P;
-    return s;
-}
 
 // One window's `caller` buffer laid out; no launch.  The caller holds the moving section's grid lock (shared).
 int prepare_caller(same_window *w, const same_caller_tris *ct, bool use_type, CallerPlan *cp) {
     same_ctx *ctx = w->ctx;
     if (w->caller_ok) turn_to(w, w->st0);          // a second call (the host's mask) starts from the stage call's arrays again
     w->caller_ok = w->caller_sel = 0;
+    w->held = same_window::Held{};                 // (a selection held for a k-NN prefix is overwritten: this call works from the list as it is)
     w->lim_row = w->prio_ok ? w->pr_jsec : nullptr;        // (a priority prune before this call: the frame stays the list as STAGED)
     w->lim_P = w->prio_ok ? w->pr_P : 0;
     w->st0 = staged_of(w);
     const int64_t n0 = w->n_ua, P0 = w->P, cap_m = w->cap_m;
+    // the pair arrays take the list as STAGED (>= any prefix of it, pruned or not): same_window_caller_pairs fills them again per knn
+    const int64_t pair_cap = cp->pair_cap = std::max(P0, w->sk.P);
     // the candidates: the triangles binned in the cells the box covers (their number is known here), or every triangle of the job where
     // the box covers more cells than a run takes (rare, as for the rows)
     const Cover cv = cover_of(w->mov, w->box);
@@ -256,9 +250,9 @@ int prepare_caller(same_window *w, const same_caller_tris *ct, bool use_type, Ca
         nx.type_c = c.take<int32_t>((size_t)n0);
         nx.size_c = c.take<double>((size_t)n0);
         nx.prow = c.take<int32_t>((size_t)n0 + 1);
-        nx.pairs = c.take<int32_t>((size_t)P0 * 2);
-        nx.jsec = c.take<int32_t>((size_t)P0);
-        nx.cost64 = c.take<double>((size_t)P0);
+        nx.pairs = c.take<int32_t>((size_t)pair_cap * 2);
+        nx.jsec = c.take<int32_t>((size_t)pair_cap);
+        nx.cost64 = c.take<double>((size_t)pair_cap);
         return c.off;
     };
     SAME_TRY(ensure(ctx, w->caller, lay(Carver())));
@@ -327,6 +321,108 @@ int launch_caller(same_ctx *ctx, CallerPlan *const *cps, int n_w, bool classify,
         if (max_cand) SAME_LAUNCH(ctx, caller_tris_kernel, dim3(scan::blocks_for(max_cand), nw), dim3(scan::NT), 0, b);
         SAME_LAUNCH(ctx, caller_counts_kernel, dim3(nw), dim3(64), 0, b);
     }
+    HIP_TRY(ctx, hipGetLastError());
+    return SAME_OK;
+}
+
+// ---- same_window_caller_pairs: the current pair list through the held mask ------------------------------------------------------------
+// per window of a launch
+struct PairsArgs {
+    int64_t n0, P0, cap;               // kept cells as staged, pairs of the current list, pairs the output arrays hold
+    const uint8_t *valid;
+    const int32_t *newidx, *prow0, *pairs0, *jsec0;
+    const double *cost0;
+    unsigned long long *st, *counts;   // scan words; the compacted window's count block: [3] pairs
+    int32_t *prow, *pairs, *jsec;
+    double *cost;
+};
+
+// the pair offsets of the rows that stay: scan of valid ? row count : 0
+__global__ __launch_bounds__(scan::NT) void caller_pair_rows_kernel(Batch<PairsArgs> b) {
+    __shared__ scan::Shared sh;
+    const PairsArgs &w = b.w[blockIdx.y];
+    const int nb = (int)scan::blocks_for(w.n0);
+    if ((int)blockIdx.x >= nb || w.n0 == 0) return;
+    const int64_t n = w.n0;
+    const uint8_t *__restrict__ valid = w.valid;
+    const int32_t *__restrict__ prow0 = w.prow0;
+    auto val = [&](int64_t v) {
+        if (v >= n || !valid[v]) return Pair{0u, 0u};
+        const int32_t c = prow0[v + 1] - prow0[v];
+        return Pair{1u, (unsigned)(c < 0 ? 0 : c)};
+    };
+    Pair through;
+    const Pair off = scan::exclusive(w.st, (int)blockIdx.x, val, sh, &through);
+    const int64_t v = (int64_t)blockIdx.x * scan::NT + threadIdx.x;
+    if (v < n && valid[v]) w.prow[off.a] = (int32_t)off.p;          // (off.a == newidx[v] < n0: prow holds n0 + 1)
+    if ((int)blockIdx.x == nb - 1 && threadIdx.x == 0) {
+        w.prow[through.a] = (int32_t)through.p;
+        w.counts[3] = through.p;
+    }
+}
+
+__global__ __launch_bounds__(256) void caller_pair_scatter_kernel(Batch<PairsArgs> b) {
+    const PairsArgs &w = b.w[blockIdx.y];
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= w.P0) return;
+    const int32_t v = w.pairs0[2 * p];
+    if (v < 0 || v >= w.n0) return;
+    const int32_t a = w.newidx[v];
+    if (a < 0 || a >= w.n0) return;               // the row went with its node
+    const int64_t place = p - w.prow0[v];         // the pair's place in its row: rows keep their order, and their pairs theirs
+    if (place < 0) return;
+    const int64_t dst = (int64_t)w.prow[a] + place;
+    if (dst >= w.cap) return;                     // (the offsets are the scan of the rows' counts, the list at most the staged one: never taken)
+    w.pairs[2 * dst] = a;
+    w.pairs[2 * dst + 1] = w.pairs0[2 * p + 1];
+    w.jsec[dst] = w.jsec0[p];
+    w.cost[dst] = w.cost0[p];
+}
+
+struct PairsPlan {
+    PairsArgs a{};
+    ZeroArgs zero{};
+};
+
+// no buffer is laid out: every pointer is one prepare_caller placed (same_window::Held), or the window's current list
+void prepare_pairs(const same_window *w, PairsPlan *pp) {
+    const same_window::Held &h = w->held;
+    PairsArgs &a = pp->a;
+    a = PairsArgs{};
+    a.n0 = w->n_ua;
+    a.P0 = w->P;
+    a.cap = h.cap;
+    a.valid = h.valid;
+    a.newidx = h.newidx;
+    a.prow0 = w->prow;
+    a.pairs0 = w->pairs;
+    a.jsec0 = w->jsec;
+    a.cost0 = w->cost64;
+    a.st = h.st;
+    a.counts = h.cs.counts;
+    a.prow = h.cs.prow;
+    a.pairs = h.cs.pairs;
+    a.jsec = h.cs.jsec;
+    a.cost = h.cs.cost64;
+    // the scan words again (scan::arg may have tagged the pointer: the words themselves start 8-byte aligned)
+    void *words = reinterpret_cast<void *>(reinterpret_cast<uintptr_t>(h.st) & ~uintptr_t(7));
+    pp->zero = ZeroArgs{{words, nullptr}, {scan::status_bytes(a.n0), 0}};
+}
+
+int launch_pairs(same_ctx *ctx, PairsPlan *const *pps, int n_w) {
+    Batch<PairsArgs> b{};
+    ZeroArgs zr[SAME_LAUNCH_WINDOWS];
+    int64_t max_P = 0, max_n = 0;
+    for (int q = 0; q < n_w; ++q) {
+        b.w[q] = pps[q]->a;
+        zr[q] = pps[q]->zero;
+        max_P = std::max(max_P, pps[q]->a.P0);
+        max_n = std::max(max_n, pps[q]->a.n0);
+    }
+    const unsigned nw = (unsigned)n_w;
+    SAME_TRY(launch_zero(ctx, zr, n_w));
+    SAME_LAUNCH(ctx, caller_pair_rows_kernel, dim3(scan::blocks_for(max_n), nw), dim3(scan::NT), 0, b);
+    SAME_LAUNCH(ctx, caller_pair_scatter_kernel, dim3(grid_for(max_P), nw), dim3(256), 0, b);
     HIP_TRY(ctx, hipGetLastError());
     return SAME_OK;
 }
@@ -501,6 +597,11 @@ int same_window_caller_tris(same_window *const *windows, int n_windows, const sa
         turn_to(w, cp.next);
         w->n_caller = n_left;
         w->caller_ok = 1;
+        w->held.valid = cp.a.valid;               // what a k-NN prefix holds on to (held.on stays 0: the window IS the compacted one)
+        w->held.newidx = cp.a.newidx;
+        w->held.st = cp.a.st_cell;
+        w->held.back_bytes = cp.back_bytes;
+        w->held.cap = cp.pair_cap;
         w->lim_row = w->prio_ok ? w->pr_jsec : w->st0.jsec;
         w->lim_P = w->prio_ok ? w->pr_P : w->st0.P;
         w->dd_ok = 0;
@@ -511,6 +612,87 @@ int same_window_caller_tris(same_window *const *windows, int n_windows, const sa
         counts[5] = n_left;
     }
     if (restored) SAME_WAIT(ctx);
+    return SAME_OK;
+}
+
+int same_window_caller_pairs(same_window *const *windows, int n_windows, int64_t *out_counts) {
+    same_ctx *ctx = nullptr;
+    SAME_TRY(check_batch(windows, n_windows, &ctx));
+    REQUIRE(ctx, out_counts);
+    for (int i = 0; i < n_windows; ++i) {
+        const same_window *w = windows[i];
+        REQUIRE(ctx, w->staged == 2 && !w->filtered && !w->finished && !w->caller_ok && !w->caller_sel);
+        // a held selection -- or a window without kept cells, which same_window_caller_tris had nothing to select for either
+        REQUIRE(ctx, w->held.on ? (w->n_ua > 0 && w->P <= w->held.cap && w->held.cs.n_ua <= w->n_ua) : w->n_ua == 0);
+    }
+    for (int q = 0; q < 6 * n_windows; ++q) out_counts[q] = 0;
+    SAME_TRY(same_use(ctx));
+    std::vector<PairsPlan> plans((size_t)n_windows);
+    std::vector<int> live;
+    for (int i = 0; i < n_windows; ++i)
+        if (windows[i]->held.on) {
+            prepare_pairs(windows[i], &plans[(size_t)i]);
+            live.push_back(i);
+        }
+    int rc = SAME_OK;
+    // ONE wait for the batch: per group of SAME_LAUNCH_WINDOWS windows the zeroing and the two kernels; then every window's counts, kept XY
+    // and kept rows -- the compacted window's, still in `caller` -- into its pinned block, where the prefix call put the staged ones
+    for (size_t g = 0; g < live.size() && rc == SAME_OK; g += SAME_LAUNCH_WINDOWS) {
+        const int n_g = (int)std::min<size_t>(SAME_LAUNCH_WINDOWS, live.size() - g);
+        PairsPlan *pps[SAME_LAUNCH_WINDOWS];
+        for (int q = 0; q < n_g; ++q) pps[q] = &plans[(size_t)live[g + (size_t)q]];
+        rc = launch_pairs(ctx, pps, n_g);
+        CopyArgs ca[SAME_LAUNCH_WINDOWS];
+        for (int q = 0; q < n_g && rc == SAME_OK; ++q) {
+            same_window *w = windows[live[g + (size_t)q]];
+            ca[q] = CopyArgs{};
+            if (w->host_dev) {
+                ca[q] = CopyArgs{{w->held.cs.counts, nullptr}, {w->host_dev, nullptr}, {w->held.back_bytes, 0}};
+                continue;
+            }
+            hipError_t e = hipMemcpyAsync(w->host, w->held.cs.counts, w->held.back_bytes, hipMemcpyDeviceToHost, ctx->stream);
+            ++ctx->stats[SAME_STAT_COPIES];
+            if (e != hipSuccess) rc = same_fail(ctx, SAME_EIO, "caller pairs copy back", e);
+        }
+        if (rc == SAME_OK) rc = launch_copy_back(ctx, ca, n_g);
+    }
+    if (rc != SAME_OK) {
+        // nothing of a failed batch counts: pinned blocks of earlier groups are overwritten already, so every window the call touched is
+        // no longer staged (as same_window_knn_prefix leaves a failed batch); what was enqueued is waited for first
+        (void)hipStreamSynchronize(ctx->stream);
+        for (int i : live) windows[i]->staged = 0;
+        return rc;
+    }
+    if (!live.empty()) SAME_WAIT(ctx);
+    for (int i : live) {
+        const same_window *w = windows[i];
+        const unsigned long long *tot = static_cast<const unsigned long long *>(w->host);
+        REQUIRE(ctx, (int64_t)tot[2] == w->held.cs.n_ua && (int64_t)tot[3] <= w->P && (int64_t)tot[3] <= w->held.cap &&
+                         (int64_t)tot[4] == w->n_caller && (int64_t)tot[7] == w->n_ua - w->held.cs.n_ua);
+    }
+    for (int i : live) {
+        same_window *w = windows[i];
+        const unsigned long long *tot = static_cast<const unsigned long long *>(w->host);
+        // as prepare_caller and the end of same_window_caller_tris leave it: st0 the list the removal started from, the limits' frame the
+        // priority prune's copy of the staged list where one ran, else that list
+        w->st0 = staged_of(w);
+        w->lim_row = w->prio_ok ? w->pr_jsec : w->st0.jsec;
+        w->lim_P = w->prio_ok ? w->pr_P : w->st0.P;
+        same_window::Staged cs = w->held.cs;
+        cs.P = (int64_t)tot[3];
+        turn_to(w, cs);
+        w->held.on = 0;
+        w->caller_sel = w->caller_ok = 1;
+        w->dd_ok = 0;
+        w->filtered = w->finished = 0;
+        w->Tr = 0;
+        int64_t *counts = out_counts + 6 * i;
+        counts[0] = w->n_sel;
+        counts[1] = w->st0.n_ua - cs.n_ua;
+        counts[3] = cs.n_ua;
+        counts[4] = cs.P;
+        counts[5] = w->n_caller;
+    }
     return SAME_OK;
 }
 

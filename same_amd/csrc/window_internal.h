@@ -261,7 +261,7 @@ struct same_window {
     size_t host_filter_off = 0;
     // the caller's triangulation (window_caller.hip).  same_window_caller_tris leaves the window's triangles in `caller` and, unless a
     // cosine sits at the threshold, the window WITHOUT its unconstrained nodes: the arrays above then point into `caller`, the stage
-    // call's own are kept in `st0` (a second call with the host's mask starts from them again)
+    // call's own are kept in `st0` (a second call with the host's mask starts from them again; a k-NN prefix turns the window back to them)
     double box[4] = {0.0, 0.0, 0.0, 0.0};
     win::DevBuf caller;
     int caller_sel = 0, caller_ok = 0;              // sel_tris valid; the window is the compacted one and caller_out its triangles
@@ -273,6 +273,20 @@ struct same_window {
         double *axy_c = nullptr, *size_c = nullptr, *cost64 = nullptr;
         int64_t n_ua = 0, P = 0;
     } st0;
+    // a k-NN prefix on the compacted window (window_knn_prefix.hip) turns it back to st0 and HOLDS the caller's work in `caller`: the node
+    // mask, the renumbering, the compacted aligned side (held.cs: ua, rows, XY, sizes, type codes; its counts block) and the renumbered
+    // triangles (caller_out, n_caller, n_sel stay).  same_window_caller_pairs pushes the window's current pair list through the mask
+    // into held.cs's pair arrays (room for `cap` pairs: the list as staged) and turns the window to held.cs again.  The pointers are
+    // those prepare_caller laid out -- kept, not laid out again
+    struct Held {
+        int on = 0;                                 // the window is as a stage call leaves it AND `caller` holds a selection for it
+        Staged cs;
+        const uint8_t *valid = nullptr;             // [st0.n_ua] the node mask
+        const int32_t *newidx = nullptr;            // [st0.n_ua] kept cell as staged -> kept cell left, or -1
+        unsigned long long *st = nullptr;           // the cell scan's words (a scan::arg)
+        size_t back_bytes = 0;                      // counts + kept XY + kept rows: what takes the stage block's place in the pinned block
+        int64_t cap = 0;
+    } held;
     // the reference rows of the pair list BEFORE the removal: the frame the model's reference limits are read from is the prune's
     // (src/same.py:1055-1085 does not compact the reference side again); null: the window's own pair list
     const int32_t *lim_row = nullptr;
@@ -312,6 +326,28 @@ struct same_caller_tris {
 };
 
 namespace win {
+
+// the window's arrays a caller's triangulation replaces (same_window::Staged): read off the window, put in their place
+inline same_window::Staged staged_of(const same_window *w) {
+    same_window::Staged s;
+    s.counts = w->counts; s.ua = w->ua; s.rows_ua = w->rows_ua; s.type_c = w->type_c; s.prow = w->prow; s.pairs = w->pairs; s.jsec = w->jsec;
+    s.axy_c = w->axy_c; s.size_c = w->size_c; s.cost64 = w->cost64; s.n_ua = w->n_ua; s.P = w->P;
+    return s;
+}
+inline void turn_to(same_window *w, const same_window::Staged &s) {
+    w->counts = s.counts;
+    w->ua = s.ua;
+    w->rows_ua = s.rows_ua;
+    w->type_c = s.type_c;
+    w->prow = s.prow;
+    w->pairs = s.pairs;
+    w->jsec = s.jsec;
+    w->axy_c = s.axy_c;
+    w->size_c = s.size_c;
+    w->cost64 = s.cost64;
+    w->n_ua = s.n_ua;
+    w->P = s.P;
+}
 
 // section.hip
 int knn_index_for(same_ctx *ctx, const same_section *ref, double radius, std::shared_ptr<same_knn_index> *out);

@@ -11,6 +11,13 @@
 // (same_window::sk): every prefix is derived from it, and a prefix at the staged k turns the window back to it without a launch.  The
 // window after the call is the one a stage call at k' leaves: what reads "the pair list as staged" (SAME_WINDOW_STAGED_PAIRS, the frame of
 // the reference limits, a priority prune that follows) reads the prefix; an earlier priority prune's result no longer holds.
+// A window same_window_caller_tris has compacted (either form of that call) is first turned back to the stage call's arrays (st0: the
+// aligned side as staged, its count block, and in the pinned block the staged counts, XY and rows again); the caller's work -- node mask,
+// renumbering, compacted aligned side, renumbered triangles -- stays in the window's `caller` buffer, HELD (same_window::Held), and
+// same_window_caller_pairs (window_caller.hip) pushes the cut list through the held mask.  The two steps are two calls, not one fused
+// kernel, because the staged prefix must exist as a list of its own: the frame of the _cap calls' reference limits,
+// SAME_WINDOW_STAGED_PAIRS and `ref_idx` are read over the pair list AS STAGED AT THAT k -- rows of removed nodes included -- not over
+// the compacted one, and a priority prune may come between the two.
 #include "window_internal.h"
 
 namespace {
@@ -152,9 +159,21 @@ int same_window_knn_prefix(same_window *const *windows, int n_windows, int k, in
     for (int i = 0; i < n_windows; ++i) {
         const same_window *w = windows[i];
         REQUIRE(ctx, w->staged >= 1 && k <= w->k_staged);
-        REQUIRE(ctx, !w->caller_sel && !w->caller_ok);        // (a caller's triangulation compacts the aligned side: stage again)
     }
     SAME_TRY(same_use(ctx));
+    // a compacted window: back to the stage call's arrays, the caller's work held.  Its pinned block holds the compacted counts, XY and
+    // rows: the staged ones take their place again below (`back`: what comes back per window)
+    std::vector<size_t> back((size_t)n_windows, 64);
+    for (int i = 0; i < n_windows; ++i) {
+        same_window *w = windows[i];
+        if (w->caller_ok) {
+            w->held.cs = staged_of(w);
+            win::turn_to(w, w->st0);
+            w->held.on = 1;
+            back[(size_t)i] = w->held.back_bytes;
+        }
+        w->caller_sel = w->caller_ok = 0;         // (selected but left as staged -- a cosine at the threshold -- : nothing is held)
+    }
     std::vector<PrefixPlan> plans((size_t)n_windows);
     std::vector<int> live;
     int rc = SAME_OK;
@@ -164,6 +183,14 @@ int same_window_knn_prefix(same_window *const *windows, int n_windows, int k, in
         if (w->staged != 2 || w->sk.P == 0 || w->n_ua == 0 || k == w->k_staged) continue;
         rc = prepare_prefix(w, k, &plans[(size_t)i]);
         if (rc == SAME_OK) live.push_back(i);
+    }
+    std::vector<int> turned;                      // turned back without a launch: only their pinned blocks are to restore
+    {
+        size_t at = 0;
+        for (int i = 0; i < n_windows && rc == SAME_OK; ++i) {
+            if (at < live.size() && live[at] == i) { ++at; continue; }
+            if (back[(size_t)i] > 64) turned.push_back(i);
+        }
     }
     // ONE wait for the batch: per group of SAME_LAUNCH_WINDOWS windows the zeroing and the two kernels, then every window's count block
     // straight into the head of its pinned block, where the stage call left the staged counts
@@ -177,23 +204,31 @@ int same_window_knn_prefix(same_window *const *windows, int n_windows, int k, in
             same_window *w = windows[live[g + (size_t)q]];
             ca[q] = CopyArgs{};
             if (w->host_dev) {
-                ca[q] = CopyArgs{{w->counts, nullptr}, {w->host_dev, nullptr}, {64, 0}};
+                ca[q] = CopyArgs{{w->counts, nullptr}, {w->host_dev, nullptr}, {back[(size_t)live[g + (size_t)q]], 0}};
                 continue;
             }
-            hipError_t e = hipMemcpyAsync(w->host, w->counts, 64, hipMemcpyDeviceToHost, ctx->stream);
+            hipError_t e = hipMemcpyAsync(w->host, w->counts, back[(size_t)live[g + (size_t)q]], hipMemcpyDeviceToHost, ctx->stream);
             ++ctx->stats[SAME_STAT_COPIES];
             if (e != hipSuccess) rc = same_fail(ctx, SAME_EIO, "k-NN prefix copy back", e);
         }
         if (rc == SAME_OK) rc = launch_copy_back(ctx, ca, n_g);
+    }
+    for (size_t g = 0; g < turned.size() && rc == SAME_OK; ++g) {
+        same_window *w = windows[turned[g]];
+        hipError_t e = hipMemcpyAsync(w->host, w->counts, back[(size_t)turned[g]], hipMemcpyDeviceToHost, ctx->stream);
+        ++ctx->stats[SAME_STAT_COPIES];
+        if (e != hipSuccess) rc = same_fail(ctx, SAME_EIO, "k-NN prefix copy back", e);
     }
     if (rc != SAME_OK) {
         // nothing of a failed batch counts: windows of earlier groups have their count blocks overwritten already, so every window the
         // call touched is no longer staged (as same_window_stage leaves a failed batch); what was enqueued is waited for first
         (void)hipStreamSynchronize(ctx->stream);
         for (int i : live) windows[i]->staged = 0;
+        for (int i = 0; i < n_windows; ++i)
+            if (back[(size_t)i] > 64) windows[i]->staged = 0;         // (turned back above: its pinned block may still be the compacted one)
         return rc;
     }
-    if (!live.empty()) SAME_WAIT(ctx);
+    if (!live.empty() || !turned.empty()) SAME_WAIT(ctx);
     for (int i : live) {
         const same_window *w = windows[i];
         const PrefixArgs &a = plans[(size_t)i].a;

@@ -441,6 +441,7 @@ int prepare_stage(same_window *w, const same_section *mov, const same_section *r
     w->k = k;
     w->n_m = w->n_r = w->n_ua = w->P = w->Tr = 0;
     w->caller_sel = w->caller_ok = 0;             // the stage call's arrays are the window's again
+    w->held = same_window::Held{};
     w->lim_row = nullptr;
     w->lim_P = 0;
     w->prio_ok = 0;                               // ... and its pair list the only one

@@ -519,10 +519,11 @@ def _merged_rows(job, frames, rows, channel):
 def _device_pass(jobs, frames, workers, with_ref_idx, triangulator, merge=False, channel=None, batch=None, caller=None, priority=False):
     """The device route: ONE walk of the windows for `jobs` -- _WindowJobs over the same frames, plan and share of the plan that differ
     in sweep.SWEEP_KEYS only (`sliding_window_incumbent`: its one job; `sliding_window_sweep`: a job per parameter set).  Every job has
-    its own builders, accumulators and stats.  -> [(table, {plan position: stats record}) per job].  A caller's triangulation and a
-    merge channel go with a single job."""
-    if len(jobs) > 1 and (caller is not None or channel is not None):
-        raise ValueError("several jobs over one pass: not with a caller's triangulation or a merge channel")
+    its own builders, accumulators and stats.  -> [(table, {plan position: stats record}) per job].  `caller`: the jobs' (one)
+    triangulation as a windows.DeviceCallerTris -- selected once per batch, whatever the number of jobs.  A merge channel goes with a
+    single job."""
+    if len(jobs) > 1 and channel is not None:
+        raise ValueError("several jobs over one pass: not with a merge channel")
     job = jobs[0]                 # what the jobs share is read from the first
     n_workers = max(1, int(workers if workers is not None else _default_workers()))
     n_workers = min(n_workers, max(1, len(job.todo)))

@@ -791,6 +791,24 @@ def caller_tris_windows(states, caller, radius, angle_enabled, cos_thr, near_tol
     return out
 
 
+def caller_pairs_windows(states):
+    """same_window_caller_pairs for a batch of windows of one context (one wait): every window `caller_tris_windows` compacted and
+    `prefix_windows` [+ `priority_windows`] has since cut gets its CURRENT pair list pushed through the node mask it holds
+    (csrc/window_caller.hip) -- the aligned side and the triangles are not made again.  -> [(selected, removed, 0, kept cells left, pairs
+    left, triangles left) per window], as caller_tris_windows reports them; every state's counts are the smaller window's afterwards:
+    the window is the one stage at that knn [+ prune] + caller_tris_windows leaves."""
+    ctx, n = states[0].ctx, len(states)
+    counts = np.zeros((n, 6), np.int64)
+    with ctx.lock:
+        ctx.check(ctx.lib.same_window_caller_pairs(_handles(states), n, counts.ctypes.data), "same_window_caller_pairs")
+    out = []
+    for s, c in zip(states, counts.tolist()):
+        s.n_selected, s.n_triangles = c[0], 0
+        s.counts = (s.counts[0], s.counts[1], c[3], c[4])
+        out.append(tuple(c))
+    return out
+
+
 def _window_records(stats_words, mode):
     """WindowMode.records of a FINISH call's stats words (a re-finish's are narrower: `mode.records(s, start=False)`)"""
     return mode.records(stats_words)
@@ -974,13 +992,17 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
     triangulated once, and finished once per set; per batch the results come set by set in the order the sets are taken (below), one
     per window each, `result.set` the set's index; `mode`, `counts`, `priority` and everything the finish call leaves are that set's,
     `rows_m` / `axy` are shared by the window's results, and a result's `state` is live only until the next set's finish.  A list of one
-    set makes the calls of the plain form; more than one does not go with `caller` or `triangulate=False`.
+    set makes the calls of the plain form; more than one does not go with `triangulate=False`, and with `caller` only when that is a
+    DeviceCallerTris: the caller's selection -- which triangles are the window's, the node mask, the window without its unconstrained
+    nodes -- does not depend on knn, so it is made ONCE per batch, at the largest knn, `removed`, `skipped` and a host-filtered window's
+    `triangles` serve every set, and after every prefix call (and the prune that follows it) ONE `caller_pairs_windows` call pushes the cut
+    pair lists through the node masks the windows hold.
     Windows go to the library in BATCHES of `batch` (default $SAME_WINDOW_BATCH, else 8): one stage call, and later per set one filter +
     finish call, for up to that many windows -- one wait per call instead of one per window, and the device works on one window while
     the host enqueues the next.  The states of a batch stay live (`result.state`) until the generator is asked for the first window of
     the next.  The sets of a batch are taken grouped by knn, largest first -- the first group's list is the list as staged; before
-    every other group ONE `prefix_windows` call cuts the pair lists to its knn (a batch sees at most one per distinct value) -- and
-    within a group in the order given.
+    every other group ONE `prefix_windows` call cuts the pair lists to its knn (a batch sees at most one per distinct value), then the
+    priority prune where it is on, then `caller_pairs_windows` where there is a `caller` -- and within a group in the order given.
     `triangulator`: the route, a delaunay.Triangulator (default: delaunay.QHULL, the Qhull helper pool).  It says how many windows to
     stage ahead and whether to start the helpers first; each window is submitted when it is staged, and the route's per-batch hook runs
     right before the batch's first filter + finish call.  A ticket's `.result()` is the simplices, or None for candidates the device
@@ -1017,8 +1039,8 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
     # per set: (`result.set`, what the collector is told beside the states and the windows)
     tags = [(None, ())] if sets is None else [(q, (q,)) for q in range(len(sets))]
     sets = [(knn, mode, no_match_penalty)] if sets is None else [(int(k), m, float(p)) for k, m, p in sets]
-    if not sets or (len(sets) > 1 and (caller is not None or not triangulate)):
-        raise ValueError("sets: at least one; several only with windows triangulated by the route (no caller's triangulation)")
+    if not sets or (len(sets) > 1 and ((caller is not None and not isinstance(caller, DeviceCallerTris)) or not triangulate)):
+        raise ValueError("sets: at least one; several only with windows triangulated by the route or by a DeviceCallerTris")
     sets = [(k, WindowMode.default() if m is None else m, p) for k, m, p in sets]
     knn = max(k for k, _m, _p in sets)
     # the sets grouped by knn, largest first (the first group is the list as staged)
@@ -1214,16 +1236,20 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
     def finish_sets(group):
         """the staged windows of `group` finished once per set, knn group by knn group -> yields every set's results"""
         states = [rec.state for rec in group if rec.state is not None]
-        current, pruned, first = knn, priority, True          # (stage_batch pruned the list as staged)
+        current, pruned, compacted, first = knn, priority, True, True     # (stage_batch pruned and compacted the list as staged)
         for k, members in set_groups:
             if states and k != current:
                 with marked("pair lists cut to the set's knn (device)"):
                     prefix_windows(states, k)
-                current, pruned = k, False
+                current, pruned, compacted = k, False, False
             if states and priority and not pruned:
                 with marked("cell-type-priority prune of the pair lists (device)"):
                     priority_windows(states)
                 pruned = True
+            if states and caller is not None and not compacted:
+                with marked("caller's triangles: the cut pair lists through the held node masks (device)"):
+                    caller_pairs_windows(states)
+                compacted = True
             for which in members:
                 yield from finish_set(group, which, first)
                 first = False

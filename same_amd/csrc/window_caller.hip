@@ -24,6 +24,7 @@
 //                  the pair index (the per-row loop of caller_cells_kernel, which also moves the aligned side, is not repeated)
 // into the pair arrays of `caller`, which were sized for the list as staged.  The window is then, array for array, the one a stage call
 // at k (+ the priority prune) + same_window_caller_tris leaves.
+// Both calls are batches of window_stage.hip's driver (window_internal.h); a failed batch of either leaves its live windows un-staged.
 #include "window_internal.h"
 
 namespace {
@@ -39,7 +40,7 @@ struct CallerArgs {
     int64_t n_cand;
     const int32_t *tris;               // the job's triangles [.][3], section rows
     const int32_t *rows0;              // kept aligned rows as staged, ascending
-    int64_t n0, P0;                    // kept cells, pairs as staged
+    int64_t n0;                        // kept cells as staged
     int32_t *tmp, *sel;                // [n_cand][3] remapped (first corner -1: not the window's); the window's triangles in order
     unsigned long long *st_sel, *st_cell, *st_tri, *dcount;     // scan words; [0] selected [1] removed [2] near
     // node mask
@@ -48,11 +49,12 @@ struct CallerArgs {
     uint8_t *valid;                    // [n0]
     // second compaction
     const unsigned long long *counts0;
-    const int32_t *ua0, *prow0, *pairs0, *jsec0;
-    const double *size0, *cost0;
+    const int32_t *ua0;
+    const double *size0;
+    PairList src, dst;                 // the window's list; the list without the removed nodes' rows, rows renumbered
     unsigned long long *counts;
-    int32_t *newidx, *ua, *rows, *type_c, *prow, *pairs, *jsec, *out;
-    double *axy, *size, *cost;
+    int32_t *newidx, *ua, *rows, *type_c, *out;
+    double *axy, *size;
 };
 
 __device__ __forceinline__ int32_t place_of(const int32_t *__restrict__ rows, int64_t n, int32_t row) {
@@ -124,7 +126,7 @@ __global__ __launch_bounds__(scan::NT) void caller_cells_kernel(Batch<CallerArgs
     if ((int)blockIdx.x >= nb || w.n0 == 0) return;
     const int64_t n = w.n0;
     const uint8_t *__restrict__ valid = w.valid;
-    const int32_t *__restrict__ prow0 = w.prow0;
+    const int32_t *__restrict__ prow0 = w.src.prow;
     auto val = [&](int64_t v) { return v < n && valid[v] ? Pair{1u, (unsigned)(prow0[v + 1] - prow0[v])} : Pair{0u, 0u}; };
     Pair through;
     const Pair off = scan::exclusive(w.st_cell, (int)blockIdx.x, val, sh, &through);
@@ -141,14 +143,9 @@ __global__ __launch_bounds__(scan::NT) void caller_cells_kernel(Batch<CallerArgs
             w.axy[2 * a + 1] = p.y;
             w.size[a] = w.size0[v];
             w.type_c[a] = w.type0 ? w.type0[v] : 0;
-            w.prow[a] = (int32_t)off.p;
+            w.dst.prow[a] = (int32_t)off.p;
             int64_t pp = off.p;
-            for (int32_t p0 = prow0[v]; p0 < prow0[v + 1]; ++p0, ++pp) {
-                w.pairs[2 * pp] = (int32_t)a;
-                w.pairs[2 * pp + 1] = w.pairs0[2 * (int64_t)p0 + 1];
-                w.jsec[pp] = w.jsec0[p0];
-                w.cost[pp] = w.cost0[p0];
-            }
+            for (int32_t p0 = prow0[v]; p0 < prow0[v + 1]; ++p0, ++pp) move_pair(w.dst, pp, (int32_t)a, w.src, p0);
         }
     }
     if ((int)blockIdx.x == nb - 1 && threadIdx.x == 0) {
@@ -156,7 +153,7 @@ __global__ __launch_bounds__(scan::NT) void caller_cells_kernel(Batch<CallerArgs
         w.counts[1] = w.counts0[1];
         w.counts[2] = through.a;
         w.counts[3] = through.p;
-        w.prow[through.a] = (int32_t)through.p;
+        w.dst.prow[through.a] = (int32_t)through.p;
         w.dcount[1] = (unsigned long long)n - through.a;
     }
 }
@@ -205,8 +202,6 @@ int prepare_caller(same_window *w, const same_caller_tris *ct, bool use_type, Ca
     if (w->caller_ok) turn_to(w, w->st0);          // a second call (the host's mask) starts from the stage call's arrays again
     w->caller_ok = w->caller_sel = 0;
     w->held = same_window::Held{};                 // (a selection held for a k-NN prefix is overwritten: this call works from the list as it is)
-    w->lim_row = w->prio_ok ? w->pr_jsec : nullptr;        // (a priority prune before this call: the frame stays the list as STAGED)
-    w->lim_P = w->prio_ok ? w->pr_P : 0;
     w->st0 = staged_of(w);
     const int64_t n0 = w->n_ua, P0 = w->P, cap_m = w->cap_m;
     // the pair arrays take the list as STAGED (>= any prefix of it, pruned or not): same_window_caller_pairs fills them again per knn
@@ -249,10 +244,10 @@ int prepare_caller(same_window *w, const same_caller_tris *ct, bool use_type, Ca
         nx.ua = c.take<int32_t>((size_t)n0);
         nx.type_c = c.take<int32_t>((size_t)n0);
         nx.size_c = c.take<double>((size_t)n0);
-        nx.prow = c.take<int32_t>((size_t)n0 + 1);
-        nx.pairs = c.take<int32_t>((size_t)pair_cap * 2);
-        nx.jsec = c.take<int32_t>((size_t)pair_cap);
-        nx.cost64 = c.take<double>((size_t)pair_cap);
+        nx.list.prow = c.take<int32_t>((size_t)n0 + 1);
+        nx.list.pairs = c.take<int32_t>((size_t)pair_cap * 2);
+        nx.list.jsec = c.take<int32_t>((size_t)pair_cap);
+        nx.list.cost64 = c.take<double>((size_t)pair_cap);
         return c.off;
     };
     SAME_TRY(ensure(ctx, w->caller, lay(Carver())));
@@ -271,26 +266,19 @@ int prepare_caller(same_window *w, const same_caller_tris *ct, bool use_type, Ca
     a.tris = ct->tris;
     a.rows0 = w->rows_ua;
     a.n0 = n0;
-    a.P0 = P0;
     a.axy0 = w->axy_c;
     a.type0 = use_type ? w->type_c : nullptr;
     a.counts0 = w->counts;
     a.ua0 = w->ua;
-    a.prow0 = w->prow;
-    a.pairs0 = w->pairs;
-    a.jsec0 = w->jsec;
     a.size0 = w->size_c;
-    a.cost0 = w->cost64;
+    a.src = list_of(w);
+    a.dst = nx.list;
     a.counts = nx.counts;
     a.ua = nx.ua;
     a.rows = nx.rows_ua;
     a.type_c = nx.type_c;
-    a.prow = nx.prow;
-    a.pairs = nx.pairs;
-    a.jsec = nx.jsec;
     a.axy = nx.axy_c;
     a.size = nx.size_c;
-    a.cost = nx.cost64;
     w->sel_tris = a.sel;
     w->caller_out = a.out;
     return SAME_OK;
@@ -328,24 +316,22 @@ int launch_caller(same_ctx *ctx, CallerPlan *const *cps, int n_w, bool classify,
 // ---- same_window_caller_pairs: the current pair list through the held mask ------------------------------------------------------------
 // per window of a launch
 struct PairsArgs {
-    int64_t n0, P0, cap;               // kept cells as staged, pairs of the current list, pairs the output arrays hold
+    int64_t n, cap;                    // kept cells as staged, pairs the output arrays hold
     const uint8_t *valid;
-    const int32_t *newidx, *prow0, *pairs0, *jsec0;
-    const double *cost0;
+    const int32_t *newidx;
+    PairList src, dst;                 // the window's current list; the compacted window's pair arrays (held.cs.list)
     unsigned long long *st, *counts;   // scan words; the compacted window's count block: [3] pairs
-    int32_t *prow, *pairs, *jsec;
-    double *cost;
 };
 
 // the pair offsets of the rows that stay: scan of valid ? row count : 0
 __global__ __launch_bounds__(scan::NT) void caller_pair_rows_kernel(Batch<PairsArgs> b) {
     __shared__ scan::Shared sh;
     const PairsArgs &w = b.w[blockIdx.y];
-    const int nb = (int)scan::blocks_for(w.n0);
-    if ((int)blockIdx.x >= nb || w.n0 == 0) return;
-    const int64_t n = w.n0;
+    const int nb = (int)scan::blocks_for(w.n);
+    if ((int)blockIdx.x >= nb || w.n == 0) return;
+    const int64_t n = w.n;
     const uint8_t *__restrict__ valid = w.valid;
-    const int32_t *__restrict__ prow0 = w.prow0;
+    const int32_t *__restrict__ prow0 = w.src.prow;
     auto val = [&](int64_t v) {
         if (v >= n || !valid[v]) return Pair{0u, 0u};
         const int32_t c = prow0[v + 1] - prow0[v];
@@ -354,75 +340,51 @@ __global__ __launch_bounds__(scan::NT) void caller_pair_rows_kernel(Batch<PairsA
     Pair through;
     const Pair off = scan::exclusive(w.st, (int)blockIdx.x, val, sh, &through);
     const int64_t v = (int64_t)blockIdx.x * scan::NT + threadIdx.x;
-    if (v < n && valid[v]) w.prow[off.a] = (int32_t)off.p;          // (off.a == newidx[v] < n0: prow holds n0 + 1)
-    if ((int)blockIdx.x == nb - 1 && threadIdx.x == 0) {
-        w.prow[through.a] = (int32_t)through.p;
-        w.counts[3] = through.p;
-    }
+    // (a row that stays: off.a == newidx[v] < n, and prow holds n + 1)
+    rows_tail(w.dst, w.counts, v < n && valid[v], off.a, off, (int)blockIdx.x == nb - 1, through.a, through);
 }
 
 __global__ __launch_bounds__(256) void caller_pair_scatter_kernel(Batch<PairsArgs> b) {
     const PairsArgs &w = b.w[blockIdx.y];
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= w.P0) return;
-    const int32_t v = w.pairs0[2 * p];
-    if (v < 0 || v >= w.n0) return;
+    if (p >= w.src.P) return;
+    const int32_t v = w.src.pairs[2 * p];
+    if (v < 0 || v >= w.n) return;
     const int32_t a = w.newidx[v];
-    if (a < 0 || a >= w.n0) return;               // the row went with its node
-    const int64_t place = p - w.prow0[v];         // the pair's place in its row: rows keep their order, and their pairs theirs
+    if (a < 0 || a >= w.n) return;                // the row went with its node
+    const int64_t place = p - w.src.prow[v];        // the pair's place in its row: rows keep their order, and their pairs theirs
     if (place < 0) return;
-    const int64_t dst = (int64_t)w.prow[a] + place;
+    const int64_t dst = (int64_t)w.dst.prow[a] + place;
     if (dst >= w.cap) return;                     // (the offsets are the scan of the rows' counts, the list at most the staged one: never taken)
-    w.pairs[2 * dst] = a;
-    w.pairs[2 * dst + 1] = w.pairs0[2 * p + 1];
-    w.jsec[dst] = w.jsec0[p];
-    w.cost[dst] = w.cost0[p];
+    move_pair(w.dst, dst, a, w.src, p);
 }
 
-struct PairsPlan {
-    PairsArgs a{};
-    ZeroArgs zero{};
-};
+using PairsPlan = ListPlan<PairsArgs>;
 
 // no buffer is laid out: every pointer is one prepare_caller placed (same_window::Held), or the window's current list
 void prepare_pairs(const same_window *w, PairsPlan *pp) {
     const same_window::Held &h = w->held;
     PairsArgs &a = pp->a;
     a = PairsArgs{};
-    a.n0 = w->n_ua;
-    a.P0 = w->P;
+    a.n = w->n_ua;
     a.cap = h.cap;
     a.valid = h.valid;
     a.newidx = h.newidx;
-    a.prow0 = w->prow;
-    a.pairs0 = w->pairs;
-    a.jsec0 = w->jsec;
-    a.cost0 = w->cost64;
+    a.src = list_of(w);
+    a.dst = h.cs.list;
     a.st = h.st;
     a.counts = h.cs.counts;
-    a.prow = h.cs.prow;
-    a.pairs = h.cs.pairs;
-    a.jsec = h.cs.jsec;
-    a.cost = h.cs.cost64;
     // the scan words again (scan::arg may have tagged the pointer: the words themselves start 8-byte aligned)
     void *words = reinterpret_cast<void *>(reinterpret_cast<uintptr_t>(h.st) & ~uintptr_t(7));
-    pp->zero = ZeroArgs{{words, nullptr}, {scan::status_bytes(a.n0), 0}};
+    pp->zero = ZeroArgs{{words, nullptr}, {scan::status_bytes(a.n), 0}};
 }
 
 int launch_pairs(same_ctx *ctx, PairsPlan *const *pps, int n_w) {
     Batch<PairsArgs> b{};
-    ZeroArgs zr[SAME_LAUNCH_WINDOWS];
-    int64_t max_P = 0, max_n = 0;
-    for (int q = 0; q < n_w; ++q) {
-        b.w[q] = pps[q]->a;
-        zr[q] = pps[q]->zero;
-        max_P = std::max(max_P, pps[q]->a.P0);
-        max_n = std::max(max_n, pps[q]->a.n0);
-    }
-    const unsigned nw = (unsigned)n_w;
-    SAME_TRY(launch_zero(ctx, zr, n_w));
-    SAME_LAUNCH(ctx, caller_pair_rows_kernel, dim3(scan::blocks_for(max_n), nw), dim3(scan::NT), 0, b);
-    SAME_LAUNCH(ctx, caller_pair_scatter_kernel, dim3(grid_for(max_P), nw), dim3(256), 0, b);
+    ListGrid g;
+    SAME_TRY(begin_group(ctx, pps, n_w, &b, &g));
+    SAME_LAUNCH(ctx, caller_pair_rows_kernel, dim3(scan::blocks_for(g.max_n), g.nw), dim3(scan::NT), 0, b);
+    SAME_LAUNCH(ctx, caller_pair_scatter_kernel, dim3(grid_for(g.max_P), g.nw), dim3(256), 0, b);
     HIP_TRY(ctx, hipGetLastError());
     return SAME_OK;
 }
@@ -532,42 +494,24 @@ int same_window_caller_tris(same_window *const *windows, int n_windows, const sa
             if (rc == SAME_OK) live.push_back(i);
         }
     }
-    // ONE wait for the batch: per group of SAME_LAUNCH_WINDOWS windows the zeroing, (the host's masks,) the kernels; then every window's
-    // counts, kept XY and kept rows straight into its pinned block, where the stage call left the staged ones
-    for (size_t g = 0; g < live.size() && rc == SAME_OK; g += SAME_LAUNCH_WINDOWS) {
-        const int n_g = (int)std::min<size_t>(SAME_LAUNCH_WINDOWS, live.size() - g);
-        CallerPlan *cps[SAME_LAUNCH_WINDOWS];
-        ZeroArgs zr[SAME_LAUNCH_WINDOWS];
-        for (int q = 0; q < n_g; ++q) {
-            cps[q] = &plans[(size_t)live[g + (size_t)q]];
-            zr[q] = cps[q]->zero;
-        }
-        rc = launch_zero(ctx, zr, n_g);
-        for (int q = 0; q < n_g && rc == SAME_OK && prefiltered; ++q) {
-            const int i = live[g + (size_t)q];
-            hipError_t e = hipMemcpyAsync(cps[q]->a.valid, stays.data() + removed_offsets[i], (size_t)cps[q]->a.n0, hipMemcpyHostToDevice, ctx->stream);
-            ++ctx->stats[SAME_STAT_COPIES];
-            if (e != hipSuccess) rc = same_fail(ctx, SAME_EIO, "node mask", e);
-        }
-        if (rc == SAME_OK) rc = launch_caller(ctx, cps, n_g, !prefiltered, radius, angle_enabled, cos_thr, near_tol);
-        CopyArgs ca[SAME_LAUNCH_WINDOWS];
-        for (int q = 0; q < n_g && rc == SAME_OK; ++q) {
-            same_window *w = windows[live[g + (size_t)q]];
-            ca[q] = CopyArgs{};
-            if (w->host_dev) {
-                ca[q] = CopyArgs{{cps[q]->next.counts, nullptr}, {w->host_dev, nullptr}, {cps[q]->back_bytes, 0}};
-                continue;
+    // ONE wait for the batch: per group the zeroing, (the host's masks,) the kernels; then every window's counts, kept XY and kept rows
+    // into the head of its pinned block, where the stage call left the staged ones
+    if (rc == SAME_OK)
+        rc = for_each_group(plans, live, [&](CallerPlan *const *cps, const int *at, int n_g) {
+            ZeroArgs zr[SAME_LAUNCH_WINDOWS];
+            for (int q = 0; q < n_g; ++q) zr[q] = cps[q]->zero;
+            SAME_TRY(launch_zero(ctx, zr, n_g));
+            for (int q = 0; q < n_g && prefiltered; ++q) {
+                hipError_t e = hipMemcpyAsync(cps[q]->a.valid, stays.data() + removed_offsets[at[q]], (size_t)cps[q]->a.n0, hipMemcpyHostToDevice, ctx->stream);
+                ++ctx->stats[SAME_STAT_COPIES];
+                if (e != hipSuccess) return same_fail(ctx, SAME_EIO, "node mask", e);
             }
-            hipError_t e = hipMemcpyAsync(w->host, cps[q]->next.counts, cps[q]->back_bytes, hipMemcpyDeviceToHost, ctx->stream);
-            ++ctx->stats[SAME_STAT_COPIES];
-            if (e != hipSuccess) rc = same_fail(ctx, SAME_EIO, "caller triangulation copy back", e);
-        }
-        if (rc == SAME_OK) rc = launch_copy_back(ctx, ca, n_g);
-    }
-    if (rc != SAME_OK) {
-        (void)hipStreamSynchronize(ctx->stream);
-        return rc;
-    }
+            SAME_TRY(launch_caller(ctx, cps, n_g, !prefiltered, radius, angle_enabled, cos_thr, near_tol));
+            Back back[SAME_LAUNCH_WINDOWS];
+            for (int q = 0; q < n_g; ++q) back[q] = Back{windows[at[q]], cps[q]->next.counts, cps[q]->back_bytes};
+            return copy_back_group(ctx, back, n_g, "caller triangulation copy back");
+        });
+    if (rc != SAME_OK) return fail_batch(ctx, windows, live, rc);
     if (!live.empty()) SAME_WAIT(ctx);
     bool restored = false;
     for (int i : live) {
@@ -576,7 +520,7 @@ int same_window_caller_tris(same_window *const *windows, int n_windows, const sa
         const unsigned long long *tot = static_cast<const unsigned long long *>(w->host);
         int64_t *counts = out_counts + 6 * i;
         const int64_t n_ua = (int64_t)tot[2], P = (int64_t)tot[3], n_left = (int64_t)tot[4], n_sel = (int64_t)tot[5], near = (int64_t)tot[6];
-        REQUIRE(ctx, n_ua <= w->st0.n_ua && P <= w->st0.P && n_left <= n_sel && n_sel <= cp.a.n_cand && (int64_t)tot[7] == w->st0.n_ua - n_ua);
+        REQUIRE(ctx, n_ua <= w->st0.n_ua && P <= w->st0.list.P && n_left <= n_sel && n_sel <= cp.a.n_cand && (int64_t)tot[7] == w->st0.n_ua - n_ua);
         w->n_sel = n_sel;
         w->caller_sel = 1;
         counts[0] = n_sel;
@@ -586,14 +530,15 @@ int same_window_caller_tris(same_window *const *windows, int n_windows, const sa
             // a cosine at the threshold: the mask is the host's to make.  The window stays as staged -- and its pinned block gets the
             // staged counts, XY and rows back (the second call starts from there)
             counts[3] = w->st0.n_ua;
-            counts[4] = w->st0.P;
+            counts[4] = w->st0.list.P;
             counts[5] = 0;
-            SAME_COPY(ctx, w->host, w->st0.counts, cp.back_bytes, hipMemcpyDeviceToHost);
+            const Back staged{w, w->st0.counts, cp.back_bytes};
+            SAME_TRY(copy_back_group(ctx, &staged, 1, "caller triangulation copy back", true));
             restored = true;
             continue;
         }
         cp.next.n_ua = n_ua;
-        cp.next.P = P;
+        cp.next.list.P = P;
         turn_to(w, cp.next);
         w->n_caller = n_left;
         w->caller_ok = 1;
@@ -602,8 +547,6 @@ int same_window_caller_tris(same_window *const *windows, int n_windows, const sa
         w->held.st = cp.a.st_cell;
         w->held.back_bytes = cp.back_bytes;
         w->held.cap = cp.pair_cap;
-        w->lim_row = w->prio_ok ? w->pr_jsec : w->st0.jsec;
-        w->lim_P = w->prio_ok ? w->pr_P : w->st0.P;
         w->dd_ok = 0;
         w->filtered = w->finished = 0;
         w->Tr = 0;
@@ -634,35 +577,15 @@ int same_window_caller_pairs(same_window *const *windows, int n_windows, int64_t
             prepare_pairs(windows[i], &plans[(size_t)i]);
             live.push_back(i);
         }
-    int rc = SAME_OK;
-    // ONE wait for the batch: per group of SAME_LAUNCH_WINDOWS windows the zeroing and the two kernels; then every window's counts, kept XY
-    // and kept rows -- the compacted window's, still in `caller` -- into its pinned block, where the prefix call put the staged ones
-    for (size_t g = 0; g < live.size() && rc == SAME_OK; g += SAME_LAUNCH_WINDOWS) {
-        const int n_g = (int)std::min<size_t>(SAME_LAUNCH_WINDOWS, live.size() - g);
-        PairsPlan *pps[SAME_LAUNCH_WINDOWS];
-        for (int q = 0; q < n_g; ++q) pps[q] = &plans[(size_t)live[g + (size_t)q]];
-        rc = launch_pairs(ctx, pps, n_g);
-        CopyArgs ca[SAME_LAUNCH_WINDOWS];
-        for (int q = 0; q < n_g && rc == SAME_OK; ++q) {
-            same_window *w = windows[live[g + (size_t)q]];
-            ca[q] = CopyArgs{};
-            if (w->host_dev) {
-                ca[q] = CopyArgs{{w->held.cs.counts, nullptr}, {w->host_dev, nullptr}, {w->held.back_bytes, 0}};
-                continue;
-            }
-            hipError_t e = hipMemcpyAsync(w->host, w->held.cs.counts, w->held.back_bytes, hipMemcpyDeviceToHost, ctx->stream);
-            ++ctx->stats[SAME_STAT_COPIES];
-            if (e != hipSuccess) rc = same_fail(ctx, SAME_EIO, "caller pairs copy back", e);
-        }
-        if (rc == SAME_OK) rc = launch_copy_back(ctx, ca, n_g);
-    }
-    if (rc != SAME_OK) {
-        // nothing of a failed batch counts: pinned blocks of earlier groups are overwritten already, so every window the call touched is
-        // no longer staged (as same_window_knn_prefix leaves a failed batch); what was enqueued is waited for first
-        (void)hipStreamSynchronize(ctx->stream);
-        for (int i : live) windows[i]->staged = 0;
-        return rc;
-    }
+    // ONE wait for the batch: per group the zeroing and the two kernels; then every window's counts, kept XY and kept rows -- the
+    // compacted window's, still in `caller` -- into the head of its pinned block, where the prefix call put the staged ones
+    const int rc = for_each_group(plans, live, [&](PairsPlan *const *pps, const int *at, int n_g) {
+        SAME_TRY(launch_pairs(ctx, pps, n_g));
+        Back back[SAME_LAUNCH_WINDOWS];
+        for (int q = 0; q < n_g; ++q) back[q] = Back{windows[at[q]], windows[at[q]]->held.cs.counts, windows[at[q]]->held.back_bytes};
+        return copy_back_group(ctx, back, n_g, "caller pairs copy back");
+    });
+    if (rc != SAME_OK) return fail_batch(ctx, windows, live, rc);
     if (!live.empty()) SAME_WAIT(ctx);
     for (int i : live) {
         const same_window *w = windows[i];
@@ -673,13 +596,10 @@ int same_window_caller_pairs(same_window *const *windows, int n_windows, int64_t
     for (int i : live) {
         same_window *w = windows[i];
         const unsigned long long *tot = static_cast<const unsigned long long *>(w->host);
-        // as prepare_caller and the end of same_window_caller_tris leave it: st0 the list the removal started from, the limits' frame the
-        // priority prune's copy of the staged list where one ran, else that list
+        // as prepare_caller and the end of same_window_caller_tris leave it: st0 the arrays the removal started from
         w->st0 = staged_of(w);
-        w->lim_row = w->prio_ok ? w->pr_jsec : w->st0.jsec;
-        w->lim_P = w->prio_ok ? w->pr_P : w->st0.P;
         same_window::Staged cs = w->held.cs;
-        cs.P = (int64_t)tot[3];
+        cs.list.P = (int64_t)tot[3];
         turn_to(w, cs);
         w->held.on = 0;
         w->caller_sel = w->caller_ok = 1;
@@ -690,7 +610,7 @@ int same_window_caller_pairs(same_window *const *windows, int n_windows, int64_t
         counts[0] = w->n_sel;
         counts[1] = w->st0.n_ua - cs.n_ua;
         counts[3] = cs.n_ua;
-        counts[4] = cs.P;
+        counts[4] = cs.list.P;
         counts[5] = w->n_caller;
     }
     return SAME_OK;

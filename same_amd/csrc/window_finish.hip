@@ -491,8 +491,8 @@ int prepare_finish(same_window *w, const int32_t *host_tris, int64_t cap_tr, con
             r.rsize = w->ref->size;
             r.ref_rows = w->rows_r;
             r.P = P;
-            r.lim_row = w->lim_row;
-            r.lim_P = w->lim_P;
+            r.lim_row = as_staged(w).jsec;
+            r.lim_P = as_staged(w).P;
             r.max_matches = mode.cap.max_matches;
             r.multiplier = mode.cap.multiplier;
         }
@@ -536,8 +536,8 @@ int launch_finish(same_ctx *ctx, same_window *const *ws, FinishPlan *const *ps, 
                 r.ref_row = w->jsec;
                 r.ref_rows = w->rows_r;
                 r.P = w->P;
-                r.lim_row = w->lim_row;
-                r.lim_P = w->lim_P;
+                r.lim_row = as_staged(w).jsec;
+                r.lim_P = as_staged(w).P;
                 r.n_r = w->n_r;
                 r.max_matches = c.max_matches;
                 r.multiplier = c.multiplier;

@@ -1,6 +1,7 @@
 // window_internal.h -- what the translation units of the device-resident window path share (section.hip, window_stage.hip,
-// window_finish.hip, window_merge.hip): the resident objects behind the opaque handles of include/same_hip.h part 4, the
-// per-launch argument blocks, the small host helpers.
+// window_finish.hip, window_merge.hip, window_caller.hip, window_priority.hip, window_knn_prefix.hip): the resident objects behind the
+// opaque handles of include/same_hip.h part 4, the per-launch argument blocks, a window's pair list (win::PairList) and the one
+// statement of which list is "the list as staged" (win::as_staged), the small host helpers and the batch driver of the window calls.
 //
 // The window path (src/same.py:507-593 with both sections RESIDENT on the device).  A section's columns are uploaded once
 // (same_section) and its rows are binned once into a grid of cells (same_section_bin: rows sorted by cell, ascending inside a cell)
@@ -198,6 +199,36 @@ inline size_t finish_back_bytes(int64_t n) {
     return b.back_bytes;
 }
 
+// A window's pair list: row a of the aligned side owns pairs [prow[a], prow[a + 1]); pair p is (pairs[2p] = aligned row, pairs[2p + 1] =
+// the reference's number in the window), jsec[p] that reference's SECTION row, cost64[p] its cost; P pairs.  The stage call makes one;
+// the priority prune, the k-NN prefix and the caller's removal each derive a second from one (source and destination of their kernels)
+// and turn the window to it (list_of / turn_to below).
+struct PairList {
+    int32_t *prow = nullptr, *pairs = nullptr, *jsec = nullptr;
+    double *cost64 = nullptr;
+    int64_t P = 0;
+};
+
+// pair p of `src` becomes pair `at` of `dst` under aligned row a: its reference number, that reference's section row and its cost are
+// copied, never recomputed
+__device__ __forceinline__ void move_pair(const PairList &dst, int64_t at, int32_t a, const PairList &src, int64_t p) {
+    dst.pairs[2 * at] = a;
+    dst.pairs[2 * at + 1] = src.pairs[2 * p + 1];
+    dst.jsec[at] = src.jsec[p];
+    dst.cost64[at] = src.cost64[p];
+}
+
+// the tail of a kernel that scans the rows' new pair counts (scan.h): the row's offset (where the thread has a row), and from the
+// last block's first thread the end of the last row and the window's pair count (counts[3]) -- the kernel adds its own count words
+__device__ __forceinline__ void rows_tail(const PairList &dst, unsigned long long *counts, bool has_row, int64_t row, scan::Pair off, bool last,
+                                          int64_t n_rows, scan::Pair through) {
+    if (has_row) dst.prow[row] = (int32_t)off.p;
+    if (last && threadIdx.x == 0) {
+        dst.prow[n_rows] = (int32_t)through.p;
+        counts[3] = through.p;
+    }
+}
+
 }  // namespace win
 
 struct same_section {
@@ -246,8 +277,8 @@ struct same_window {
     // stage block
     unsigned long long *counts = nullptr;           // [8], first words of the block the stage call copies back
     int32_t *rows_m = nullptr, *rows_r = nullptr, *idx = nullptr, *cnt = nullptr, *ua = nullptr, *rows_ua = nullptr, *type_c = nullptr,
-            *prow = nullptr, *pairs = nullptr, *jsec = nullptr;
-    double *axy_c = nullptr, *size_c = nullptr, *cost64 = nullptr;
+            *prow = nullptr, *pairs = nullptr, *jsec = nullptr;      // prow, pairs, jsec, cost64 and P: the window's CURRENT pair list
+    double *axy_c = nullptr, *size_c = nullptr, *cost64 = nullptr;  // (a win::PairList held loose: win::list_of reads it, win::turn_to sets it)
     // finish block
     int8_t *sign = nullptr;
     double *weight = nullptr;
@@ -260,8 +291,9 @@ struct same_window {
     size_t host_finish_off = 0;   // the pinned block: [stage call's copy | finish call's copy | the filter's counters]
     size_t host_filter_off = 0;
     // the caller's triangulation (window_caller.hip).  same_window_caller_tris leaves the window's triangles in `caller` and, unless a
-    // cosine sits at the threshold, the window WITHOUT its unconstrained nodes: the arrays above then point into `caller`, the stage
-    // call's own are kept in `st0` (a second call with the host's mask starts from them again; a k-NN prefix turns the window back to them)
+    // cosine sits at the threshold, the window WITHOUT its unconstrained nodes: the arrays above then point into `caller`, the ones the
+    // removal started from are kept in `st0` (a second call with the host's mask starts from them again; a k-NN prefix turns the window
+    // back to them)
     double box[4] = {0.0, 0.0, 0.0, 0.0};
     win::DevBuf caller;
     int caller_sel = 0, caller_ok = 0;              // sel_tris valid; the window is the compacted one and caller_out its triangles
@@ -269,9 +301,10 @@ struct same_window {
     int32_t *sel_tris = nullptr, *caller_out = nullptr;
     struct Staged {
         unsigned long long *counts = nullptr;
-        int32_t *ua = nullptr, *rows_ua = nullptr, *type_c = nullptr, *prow = nullptr, *pairs = nullptr, *jsec = nullptr;
-        double *axy_c = nullptr, *size_c = nullptr, *cost64 = nullptr;
-        int64_t n_ua = 0, P = 0;
+        int32_t *ua = nullptr, *rows_ua = nullptr, *type_c = nullptr;
+        double *axy_c = nullptr, *size_c = nullptr;
+        int64_t n_ua = 0;
+        win::PairList list;
     } st0;
     // a k-NN prefix on the compacted window (window_knn_prefix.hip) turns it back to st0 and HOLDS the caller's work in `caller`: the node
     // mask, the renumbering, the compacted aligned side (held.cs: ua, rows, XY, sizes, type codes; its counts block) and the renumbered
@@ -287,28 +320,19 @@ struct same_window {
         size_t back_bytes = 0;                      // counts + kept XY + kept rows: what takes the stage block's place in the pinned block
         int64_t cap = 0;
     } held;
-    // the reference rows of the pair list BEFORE the removal: the frame the model's reference limits are read from is the prune's
-    // (src/same.py:1055-1085 does not compact the reference side again); null: the window's own pair list
-    const int32_t *lim_row = nullptr;
-    int64_t lim_P = 0;
     // the cell-type-priority prune (window_priority.hip).  same_window_priority_pairs leaves the filtered pair list in `prio` and turns
-    // prow / pairs / jsec / cost64 to it; the list as staged stays where the stage call put it (pr_*: what SAME_WINDOW_STAGED_PAIRS and
-    // the reference limits go on reading).  bins_*: the sections' `bins` when the window was staged
+    // the window's list to it; the list it started from -- the list as staged -- stays where it is, kept in `pr` (win::as_staged).
+    // bins_*: the sections' `bins` when the window was staged
     win::DevBuf prio;
     int prio_ok = 0;
-    const int32_t *pr_pairs = nullptr, *pr_jsec = nullptr;
-    int64_t pr_P = 0;
+    win::PairList pr;
     unsigned long long bins_m = 0, bins_r = 0;
     // the k-NN prefix (window_knn_prefix.hip).  same_window_knn_prefix leaves every row's first min(k, count) pairs in `kpre` and turns
-    // prow / pairs / jsec / cost64 to it: the window is then what a stage call at that k leaves, and `k` is that k.  sk: the list as the
+    // the window's list to it: the window is then what a stage call at that k leaves, and `k` is that k.  sk: the list as the
     // stage call put it (k_staged its k), which every prefix is derived from and a prefix at k_staged turns the window back to
     win::DevBuf kpre;
     int k_staged = 0;
-    struct StagedList {
-        int32_t *prow = nullptr, *pairs = nullptr, *jsec = nullptr;
-        double *cost64 = nullptr;
-        int64_t P = 0;
-    } sk;
+    win::PairList sk;
 };
 
 // A caller's triangulation of a moving section, resident (same_caller_tris_create): section rows per corner, in the caller's order, and
@@ -327,11 +351,24 @@ struct same_caller_tris {
 
 namespace win {
 
+// the window's pair list (the loose fields prow / pairs / jsec / cost64 / P of same_window): read off the window, put in its place
+inline PairList list_of(const same_window *w) {
+    PairList l;
+    l.prow = w->prow; l.pairs = w->pairs; l.jsec = w->jsec; l.cost64 = w->cost64; l.P = w->P;
+    return l;
+}
+inline void turn_to(same_window *w, const PairList &l) {
+    w->prow = l.prow;
+    w->pairs = l.pairs;
+    w->jsec = l.jsec;
+    w->cost64 = l.cost64;
+    w->P = l.P;
+}
 // the window's arrays a caller's triangulation replaces (same_window::Staged): read off the window, put in their place
 inline same_window::Staged staged_of(const same_window *w) {
     same_window::Staged s;
-    s.counts = w->counts; s.ua = w->ua; s.rows_ua = w->rows_ua; s.type_c = w->type_c; s.prow = w->prow; s.pairs = w->pairs; s.jsec = w->jsec;
-    s.axy_c = w->axy_c; s.size_c = w->size_c; s.cost64 = w->cost64; s.n_ua = w->n_ua; s.P = w->P;
+    s.counts = w->counts; s.ua = w->ua; s.rows_ua = w->rows_ua; s.type_c = w->type_c;
+    s.axy_c = w->axy_c; s.size_c = w->size_c; s.n_ua = w->n_ua; s.list = list_of(w);
     return s;
 }
 inline void turn_to(same_window *w, const same_window::Staged &s) {
@@ -339,15 +376,16 @@ inline void turn_to(same_window *w, const same_window::Staged &s) {
     w->ua = s.ua;
     w->rows_ua = s.rows_ua;
     w->type_c = s.type_c;
-    w->prow = s.prow;
-    w->pairs = s.pairs;
-    w->jsec = s.jsec;
     w->axy_c = s.axy_c;
     w->size_c = s.size_c;
-    w->cost64 = s.cost64;
     w->n_ua = s.n_ua;
-    w->P = s.P;
+    turn_to(w, s.list);
 }
+// THE PAIR LIST AS STAGED: the list before the priority prune filtered it and before the caller's removal took the unconstrained nodes'
+// rows (in that order: the prune's source is the older one); the window's own list where neither ran.  A k-NN prefix IS a staged list
+// (it resets both).  It is what SAME_WINDOW_STAGED_PAIRS hands out, and its reference rows (jsec, P of them) are the frame the model's
+// reference limits are read over: the frame is the prune's, src/same.py:1055-1085 does not compact the reference side again.
+inline PairList as_staged(const same_window *w) { return w->prio_ok ? w->pr : w->caller_ok ? w->st0.list : list_of(w); }
 
 // section.hip
 int knn_index_for(same_ctx *ctx, const same_section *ref, double radius, std::shared_ptr<same_knn_index> *out);
@@ -357,5 +395,58 @@ int launch_copy_back(same_ctx *ctx, const CopyArgs *regions, int n_w);
 int launch_rows(same_ctx *ctx, const RowsArgs *jobs, int n_w);
 int launch_zero(same_ctx *ctx, const ZeroArgs *regions, int n_w);
 int check_batch(same_window *const *windows, int n_windows, same_ctx **out_ctx);
+
+// ---- the batch driver of the calls that work on staged windows (window_stage.hip) ------------------------------------------------------
+// A batch call prepares a plan per window (no launch), lists the windows that have work (`live`, indices into the batch), walks them in
+// groups of SAME_LAUNCH_WINDOWS -- per group its launches, then what each window hands back --, and waits ONCE.  A batch that fails
+// counts for nothing: fail_batch.
+struct Back {                // what one window hands back into the HEAD of its pinned block
+    same_window *w;
+    const void *src;
+    size_t bytes;
+};
+// a group's hand-backs enqueued: one launch_copy_back for the group, or -- for a window whose pinned block the device cannot address,
+// and for every window with `engine` -- one hipMemcpyAsync each (counted).  `what` names the call in the failure's text.
+int copy_back_group(same_ctx *ctx, const Back *back, int n_w, const char *what, bool engine = false);
+// what was enqueued is waited for; the listed windows of the batch are no longer staged (count blocks and pinned blocks of earlier groups
+// are overwritten already); -> rc
+int fail_batch(same_ctx *ctx, same_window *const *windows, const std::vector<int> &touched, int rc);
+// fn(plans of the group, their indices into the batch, how many) for every group of `live`, until one fails
+template <class Plan, class F>
+int for_each_group(std::vector<Plan> &plans, const std::vector<int> &live, F &&fn) {
+    int rc = SAME_OK;
+    for (size_t g = 0; g < live.size() && rc == SAME_OK; g += SAME_LAUNCH_WINDOWS) {
+        const int n_g = (int)std::min<size_t>(SAME_LAUNCH_WINDOWS, live.size() - g);
+        Plan *pps[SAME_LAUNCH_WINDOWS];
+        for (int q = 0; q < n_g; ++q) pps[q] = &plans[(size_t)live[g + (size_t)q]];
+        rc = fn(pps, live.data() + g, n_g);
+    }
+    return rc;
+}
+
+// The three calls that derive a pair list from a pair list (priority prune, k-NN prefix, caller pairs) plan alike: the kernels' argument
+// block -- `n` rows, the source list `src`, the destination `dst` -- and the head of the destination buffer to zero (the scan's words).
+template <class A>
+struct ListPlan {
+    A a{};
+    ZeroArgs zero{};
+};
+struct ListGrid {            // a group's launch shapes: blockIdx.y windows, the largest row count and source list
+    unsigned nw = 0;
+    int64_t max_n = 0, max_P = 0;
+};
+// a group's argument blocks by value, its shapes, its zeroing enqueued
+template <class A>
+int begin_group(same_ctx *ctx, ListPlan<A> *const *pps, int n_w, Batch<A> *b, ListGrid *g) {
+    ZeroArgs zr[SAME_LAUNCH_WINDOWS];
+    g->nw = (unsigned)n_w;
+    for (int q = 0; q < n_w; ++q) {
+        b->w[q] = pps[q]->a;
+        zr[q] = pps[q]->zero;
+        g->max_n = std::max(g->max_n, pps[q]->a.n);
+        g->max_P = std::max(g->max_P, pps[q]->a.src.P);
+    }
+    return launch_zero(ctx, zr, n_w);
+}
 
 }  // namespace win

@@ -9,8 +9,8 @@
 //                  window's `kpre` buffer); the window's pointers are turned to them.
 // The aligned side is untouched, so a triangulation held for the window stays valid.  The list as staged stays where the stage call put it
 // (same_window::sk): every prefix is derived from it, and a prefix at the staged k turns the window back to it without a launch.  The
-// window after the call is the one a stage call at k' leaves: what reads "the pair list as staged" (SAME_WINDOW_STAGED_PAIRS, the frame of
-// the reference limits, a priority prune that follows) reads the prefix; an earlier priority prune's result no longer holds.
+// window after the call is the one a stage call at k' leaves: what reads "the pair list as staged" (win::as_staged, a priority prune
+// that follows) reads the prefix; an earlier priority prune's result no longer holds.
 // A window same_window_caller_tris has compacted (either form of that call) is first turned back to the stage call's arrays (st0: the
 // aligned side as staged, its count block, and in the pinned block the staged counts, XY and rows again); the caller's work -- node mask,
 // renumbering, compacted aligned side, renumbered triangles -- stays in the window's `caller` buffer, HELD (same_window::Held), and
@@ -27,17 +27,14 @@ using scan::Pair;
 
 // per window of a launch
 struct PrefixArgs {
-    int64_t n, P0, cap;                // kept aligned cells, pairs as staged, pairs the prefix buffer holds (>= the prefix's count)
+    int64_t n, cap;                    // kept aligned cells, pairs the prefix buffer holds (>= the prefix's count)
     int k;
-    const int32_t *prow0, *pairs0, *jsec0;
-    const double *cost0;
+    PairList src, dst;                 // the list as staged; the prefix (the `kpre` buffer)
     unsigned long long *st, *counts;   // scan words; the window's count block: [3] pairs
-    int32_t *prow, *pairs, *jsec;
-    double *cost;
 };
 
 __device__ __forceinline__ unsigned prefix_keep(const PrefixArgs &w, int64_t a) {
-    const int32_t c = w.prow0[a + 1] - w.prow0[a];
+    const int32_t c = w.src.prow[a + 1] - w.src.prow[a];
     return (unsigned)(c < 0 ? 0 : (c < w.k ? c : w.k));
 }
 
@@ -52,34 +49,25 @@ __global__ __launch_bounds__(scan::NT) void prefix_rows_kernel(Batch<PrefixArgs>
     Pair through;
     const Pair off = scan::exclusive(w.st, (int)blockIdx.x, val, sh, &through);
     const int64_t a = (int64_t)blockIdx.x * scan::NT + threadIdx.x;
-    if (a < n) w.prow[a] = (int32_t)off.p;
-    if ((int)blockIdx.x == nb - 1 && threadIdx.x == 0) {
-        w.prow[n] = (int32_t)through.p;
-        w.counts[3] = through.p;
-        w.counts[4] = 0;                          // (a priority prune's count: a freshly staged window has none)
-    }
+    const bool last = (int)blockIdx.x == nb - 1;
+    rows_tail(w.dst, w.counts, a < n, a, off, last, n, through);
+    if (last && threadIdx.x == 0) w.counts[4] = 0;       // (a priority prune's count: a freshly staged window has none)
 }
 
 __global__ __launch_bounds__(256) void prefix_scatter_kernel(Batch<PrefixArgs> b) {
     const PrefixArgs &w = b.w[blockIdx.y];
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= w.P0) return;
-    const int32_t a = w.pairs0[2 * p];
+    if (p >= w.src.P) return;
+    const int32_t a = w.src.pairs[2 * p];
     if (a < 0 || a >= w.n) return;
-    const int64_t place = p - w.prow0[a];         // the pair's place in its row: the stage call wrote a row's pairs in the prune's order
+    const int64_t place = p - w.src.prow[a];        // the pair's place in its row: the stage call wrote a row's pairs in the prune's order
     if (place < 0 || place >= w.k) return;
-    const int64_t dst = (int64_t)w.prow[a] + place;
+    const int64_t dst = (int64_t)w.dst.prow[a] + place;
     if (dst >= w.cap) return;                     // (the offsets are the scan of min(k, count): never taken)
-    w.pairs[2 * dst] = a;
-    w.pairs[2 * dst + 1] = w.pairs0[2 * p + 1];
-    w.jsec[dst] = w.jsec0[p];
-    w.cost[dst] = w.cost0[p];
+    move_pair(w.dst, dst, a, w.src, p);
 }
 
-struct PrefixPlan {
-    PrefixArgs a{};
-    ZeroArgs zero{};
-};
+using PrefixPlan = ListPlan<PrefixArgs>;
 
 // One window's `kpre` buffer laid out; no launch.
 int prepare_prefix(same_window *w, int k, PrefixPlan *pp) {
@@ -91,59 +79,39 @@ int prepare_prefix(same_window *w, int k, PrefixPlan *pp) {
     auto lay = [&](Carver c) {
         a.st = scan::arg(c.scan_words(n));          // zeroed head: the scan words
         zero_bytes = c.off;
-        a.prow = c.take<int32_t>((size_t)n + 1);
-        a.pairs = c.take<int32_t>((size_t)cap * 2);
-        a.jsec = c.take<int32_t>((size_t)cap);
-        a.cost = c.take<double>((size_t)cap);
+        a.dst.prow = c.take<int32_t>((size_t)n + 1);
+        a.dst.pairs = c.take<int32_t>((size_t)cap * 2);
+        a.dst.jsec = c.take<int32_t>((size_t)cap);
+        a.dst.cost64 = c.take<double>((size_t)cap);
         return c.off;
     };
     SAME_TRY(ensure(ctx, w->kpre, lay(Carver())));
     lay(Carver(w->kpre.p));
     pp->zero = ZeroArgs{{w->kpre.p, nullptr}, {zero_bytes, 0}};
     a.n = n;
-    a.P0 = P0;
     a.cap = cap;
     a.k = k;
-    a.prow0 = w->sk.prow;
-    a.pairs0 = w->sk.pairs;
-    a.jsec0 = w->sk.jsec;
-    a.cost0 = w->sk.cost64;
+    a.src = w->sk;
     a.counts = w->counts;
     return SAME_OK;
 }
 
 int launch_prefix(same_ctx *ctx, PrefixPlan *const *pps, int n_w) {
     Batch<PrefixArgs> b{};
-    ZeroArgs zr[SAME_LAUNCH_WINDOWS];
-    int64_t max_P = 0, max_n = 0;
-    for (int q = 0; q < n_w; ++q) {
-        b.w[q] = pps[q]->a;
-        zr[q] = pps[q]->zero;
-        max_P = std::max(max_P, pps[q]->a.P0);
-        max_n = std::max(max_n, pps[q]->a.n);
-    }
-    const unsigned nw = (unsigned)n_w;
-    SAME_TRY(launch_zero(ctx, zr, n_w));
-    SAME_LAUNCH(ctx, prefix_rows_kernel, dim3(scan::blocks_for(max_n), nw), dim3(scan::NT), 0, b);
-    SAME_LAUNCH(ctx, prefix_scatter_kernel, dim3(grid_for(max_P), nw), dim3(256), 0, b);
+    ListGrid g;
+    SAME_TRY(begin_group(ctx, pps, n_w, &b, &g));
+    SAME_LAUNCH(ctx, prefix_rows_kernel, dim3(scan::blocks_for(g.max_n), g.nw), dim3(scan::NT), 0, b);
+    SAME_LAUNCH(ctx, prefix_scatter_kernel, dim3(grid_for(g.max_P), g.nw), dim3(256), 0, b);
     HIP_TRY(ctx, hipGetLastError());
     return SAME_OK;
 }
 
-// the window's pair list is `prow` / `pairs` / `jsec` / `cost` with P pairs, as a stage call at k leaves it: nothing derived from an
-// earlier list holds any more
-void turn_to(same_window *w, int k, int32_t *prow, int32_t *pairs, int32_t *jsec, double *cost, int64_t P) {
-    w->prow = prow;
-    w->pairs = pairs;
-    w->jsec = jsec;
-    w->cost64 = cost;
-    w->P = P;
+// the window's pair list is `l`, as a stage call at k leaves it: nothing derived from an earlier list holds any more (as_staged: `l`)
+void turn_to(same_window *w, int k, const PairList &l) {
+    win::turn_to(w, l);
     w->k = k;
     w->prio_ok = 0;
-    w->pr_pairs = w->pr_jsec = nullptr;
-    w->pr_P = 0;
-    w->lim_row = nullptr;                         // the frame of the reference limits: the references THIS list names
-    w->lim_P = 0;
+    w->pr = PairList{};
     w->filtered = w->finished = 0;
     w->Tr = 0;
 }
@@ -187,46 +155,28 @@ int same_window_knn_prefix(same_window *const *windows, int n_windows, int k, in
     std::vector<int> turned;                      // turned back without a launch: only their pinned blocks are to restore
     {
         size_t at = 0;
-        for (int i = 0; i < n_windows && rc == SAME_OK; ++i) {
+        for (int i = 0; i < n_windows; ++i) {
             if (at < live.size() && live[at] == i) { ++at; continue; }
             if (back[(size_t)i] > 64) turned.push_back(i);
         }
     }
-    // ONE wait for the batch: per group of SAME_LAUNCH_WINDOWS windows the zeroing and the two kernels, then every window's count block
-    // straight into the head of its pinned block, where the stage call left the staged counts
-    for (size_t g = 0; g < live.size() && rc == SAME_OK; g += SAME_LAUNCH_WINDOWS) {
-        const int n_g = (int)std::min<size_t>(SAME_LAUNCH_WINDOWS, live.size() - g);
-        PrefixPlan *pps[SAME_LAUNCH_WINDOWS];
-        for (int q = 0; q < n_g; ++q) pps[q] = &plans[(size_t)live[g + (size_t)q]];
-        rc = launch_prefix(ctx, pps, n_g);
-        CopyArgs ca[SAME_LAUNCH_WINDOWS];
-        for (int q = 0; q < n_g && rc == SAME_OK; ++q) {
-            same_window *w = windows[live[g + (size_t)q]];
-            ca[q] = CopyArgs{};
-            if (w->host_dev) {
-                ca[q] = CopyArgs{{w->counts, nullptr}, {w->host_dev, nullptr}, {back[(size_t)live[g + (size_t)q]], 0}};
-                continue;
-            }
-            hipError_t e = hipMemcpyAsync(w->host, w->counts, back[(size_t)live[g + (size_t)q]], hipMemcpyDeviceToHost, ctx->stream);
-            ++ctx->stats[SAME_STAT_COPIES];
-            if (e != hipSuccess) rc = same_fail(ctx, SAME_EIO, "k-NN prefix copy back", e);
-        }
-        if (rc == SAME_OK) rc = launch_copy_back(ctx, ca, n_g);
-    }
-    for (size_t g = 0; g < turned.size() && rc == SAME_OK; ++g) {
-        same_window *w = windows[turned[g]];
-        hipError_t e = hipMemcpyAsync(w->host, w->counts, back[(size_t)turned[g]], hipMemcpyDeviceToHost, ctx->stream);
-        ++ctx->stats[SAME_STAT_COPIES];
-        if (e != hipSuccess) rc = same_fail(ctx, SAME_EIO, "k-NN prefix copy back", e);
-    }
-    if (rc != SAME_OK) {
-        // nothing of a failed batch counts: windows of earlier groups have their count blocks overwritten already, so every window the
-        // call touched is no longer staged (as same_window_stage leaves a failed batch); what was enqueued is waited for first
-        (void)hipStreamSynchronize(ctx->stream);
-        for (int i : live) windows[i]->staged = 0;
-        for (int i = 0; i < n_windows; ++i)
-            if (back[(size_t)i] > 64) windows[i]->staged = 0;         // (turned back above: its pinned block may still be the compacted one)
-        return rc;
+    // ONE wait for the batch: per group the zeroing and the two kernels, then every window's count block (a window turned back: the
+    // staged counts, XY and rows) into the head of its pinned block; the windows turned back without a launch by a copy each
+    auto hand_back = [&](const int *at, int n_g, bool engine) {
+        Back bk[SAME_LAUNCH_WINDOWS];
+        for (int q = 0; q < n_g; ++q) bk[q] = Back{windows[at[q]], windows[at[q]]->counts, back[(size_t)at[q]]};
+        return copy_back_group(ctx, bk, n_g, "k-NN prefix copy back", engine);
+    };
+    if (rc == SAME_OK)
+        rc = for_each_group(plans, live, [&](PrefixPlan *const *pps, const int *at, int n_g) {
+            SAME_TRY(launch_prefix(ctx, pps, n_g));
+            return hand_back(at, n_g, false);
+        });
+    if (rc == SAME_OK) rc = for_each_group(plans, turned, [&](PrefixPlan *const *, const int *at, int n_g) { return hand_back(at, n_g, true); });
+    if (rc != SAME_OK) {                          // (a window turned back above: its pinned block may still be the compacted one)
+        std::vector<int> touched(live);
+        touched.insert(touched.end(), turned.begin(), turned.end());
+        return fail_batch(ctx, windows, touched, rc);
     }
     if (!live.empty() || !turned.empty()) SAME_WAIT(ctx);
     for (int i : live) {
@@ -240,11 +190,12 @@ int same_window_knn_prefix(same_window *const *windows, int n_windows, int k, in
         same_window *w = windows[i];
         const bool derived = at < live.size() && live[at] == i;
         if (derived) {
-            const PrefixArgs &a = plans[(size_t)i].a;
-            turn_to(w, k, a.prow, a.pairs, a.jsec, a.cost, (int64_t) static_cast<const unsigned long long *>(w->host)[3]);
+            PairList cut = plans[(size_t)i].a.dst;
+            cut.P = (int64_t) static_cast<const unsigned long long *>(w->host)[3];
+            turn_to(w, k, cut);
             ++at;
         } else {
-            turn_to(w, k, w->sk.prow, w->sk.pairs, w->sk.jsec, w->sk.cost64, w->sk.P);
+            turn_to(w, k, w->sk);
             static_cast<unsigned long long *>(w->host)[3] = (unsigned long long)w->sk.P;     // the count block's host copy: the list's
         }
         int64_t *counts = out_counts + 4 * i;

@@ -13,7 +13,8 @@
 //   scatter        one thread per pair: a kept pair goes to new_prow[row] + rank (a winner's nearest to new_prow[row]), with its reference
 //                  row and its cost, into a SECOND set of arrays (the window's `prio` buffer); the window's pointers are turned to them.
 // The aligned side is untouched (every kept cell keeps a pair) and the reference side is NOT compacted again (:78 returns the frames it
-// got): the pair list as staged stays where it is and stays what SAME_WINDOW_STAGED_PAIRS and the reference limits read.
+// got): the pair list as staged stays where it is and stays what win::as_staged answers (window_internal.h).  The batch is driven by
+// window_stage.hip's driver (window_internal.h).
 #include <climits>
 
 #include "window_internal.h"
@@ -26,14 +27,13 @@ using scan::Pair;
 
 // per window of a launch
 struct PrioArgs {
-    int64_t n, P0, n_r;                // kept aligned cells, pairs as staged, reference rows in the box
-    const int32_t *prow0, *pairs0, *jsec0, *rows_ua;
-    const double *cost0, *axy, *ref_xy;    // costs as staged; XY of the kept cells; XY of the reference SECTION
+    int64_t n, n_r;                    // kept aligned cells, reference rows in the box
+    PairList src, dst;                 // the list as staged; the filtered list (the `prio` buffer: room for src.P pairs)
+    const int32_t *rows_ua;
+    const double *axy, *ref_xy;        // XY of the kept cells; XY of the reference SECTION
     const int32_t *code_m, *code_r;    // label codes per section row
-    int32_t *claim, *near, *rank;      // [n_r] lowest bidding row; [n] the row's nearest reference in the window; [P0] stable rank in the row
+    int32_t *claim, *near, *rank;      // [n_r] lowest bidding row; [n] the row's nearest reference in the window; [src.P] stable rank in the row
     unsigned long long *st, *counts;   // scan words; the window's count block: [3] pairs left, [4] rows that kept one pair
-    int32_t *prow, *pairs, *jsec;
-    double *cost;
 };
 
 __global__ __launch_bounds__(256) void prio_init_kernel(Batch<PrioArgs> b) {
@@ -46,10 +46,10 @@ __global__ __launch_bounds__(256) void prio_init_kernel(Batch<PrioArgs> b) {
 __global__ __launch_bounds__(256) void prio_rank_kernel(Batch<PrioArgs> b) {
     const PrioArgs &w = b.w[blockIdx.y];
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= w.P0) return;
-    const int32_t a = w.pairs0[2 * p];
+    if (p >= w.src.P) return;
+    const int32_t a = w.src.pairs[2 * p];
     if (a < 0 || a >= w.n) return;
-    const int32_t *__restrict__ jsec0 = w.jsec0;
+    const int32_t *__restrict__ jsec0 = w.src.jsec;
     const double2_t m = ld2(w.axy, a);
     // correctly rounded by contract: the products and the sum are separate IEEE operations (-ffp-contract=off), and __builtin_sqrt is
     // llvm.sqrt.f64 without the `afn` flag (-fno-fast-math), which LLVM defines as the IEEE-754 square root -- round to nearest even
@@ -60,14 +60,14 @@ __global__ __launch_bounds__(256) void prio_rank_kernel(Batch<PrioArgs> b) {
     };
     const double d = dist(p);
     int32_t rank = 0;
-    for (int64_t q = w.prow0[a], e = w.prow0[a + 1]; q < e; ++q) {
+    for (int64_t q = w.src.prow[a], e = w.src.prow[a + 1]; q < e; ++q) {
         if (q == p) continue;
         const double dq = dist(q);
         rank += (dq < d || (dq == d && q < p)) ? 1 : 0;
     }
     w.rank[p] = rank;
     if (rank == 0) {
-        const int32_t j = w.pairs0[2 * p + 1];
+        const int32_t j = w.src.pairs[2 * p + 1];
         w.near[a] = j;
         const int32_t cm = w.code_m[w.rows_ua[a]], cr = w.code_r[jsec0[p]];
         if (cm == cr && cm >= 0 && j >= 0 && j < w.n_r) atomicMin(&w.claim[j], a);
@@ -86,7 +86,7 @@ __global__ __launch_bounds__(scan::NT) void prio_rows_kernel(Batch<PrioArgs> b) 
     const int nb = (int)scan::blocks_for(w.n);
     if ((int)blockIdx.x >= nb || w.n == 0) return;
     const int64_t n = w.n;
-    const int32_t *__restrict__ prow0 = w.prow0;
+    const int32_t *__restrict__ prow0 = w.src.prow;
     auto val = [&](int64_t a) {
         if (a >= n) return Pair{0u, 0u};
         const bool win = prio_wins(w, a);
@@ -95,35 +95,26 @@ __global__ __launch_bounds__(scan::NT) void prio_rows_kernel(Batch<PrioArgs> b) 
     Pair through;
     const Pair off = scan::exclusive(w.st, (int)blockIdx.x, val, sh, &through);
     const int64_t a = (int64_t)blockIdx.x * scan::NT + threadIdx.x;
-    if (a < n) w.prow[a] = (int32_t)off.p;
-    if ((int)blockIdx.x == nb - 1 && threadIdx.x == 0) {
-        w.prow[n] = (int32_t)through.p;
-        w.counts[3] = through.p;
-        w.counts[4] = through.a;
-    }
+    const bool last = (int)blockIdx.x == nb - 1;
+    rows_tail(w.dst, w.counts, a < n, a, off, last, n, through);
+    if (last && threadIdx.x == 0) w.counts[4] = through.a;
 }
 
 __global__ __launch_bounds__(256) void prio_scatter_kernel(Batch<PrioArgs> b) {
     const PrioArgs &w = b.w[blockIdx.y];
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= w.P0) return;
-    const int32_t a = w.pairs0[2 * p];
+    if (p >= w.src.P) return;
+    const int32_t a = w.src.pairs[2 * p];
     if (a < 0 || a >= w.n) return;
     const bool win = prio_wins(w, a);
     const int32_t r = w.rank[p];
     if (win && r != 0) return;
-    const int64_t dst = (int64_t)w.prow[a] + (win ? 0 : r);
-    if (dst >= w.P0) return;                      // (ranks are a permutation of the row's places: never taken)
-    w.pairs[2 * dst] = a;
-    w.pairs[2 * dst + 1] = w.pairs0[2 * p + 1];
-    w.jsec[dst] = w.jsec0[p];
-    w.cost[dst] = w.cost0[p];
+    const int64_t dst = (int64_t)w.dst.prow[a] + (win ? 0 : r);
+    if (dst >= w.src.P) return;                   // (ranks are a permutation of the row's places: never taken)
+    move_pair(w.dst, dst, a, w.src, p);
 }
 
-struct PrioPlan {
-    PrioArgs a{};
-    ZeroArgs zero{};
-};
+using PrioPlan = ListPlan<PrioArgs>;
 
 // One window's `prio` buffer laid out; no launch.
 int prepare_priority(same_window *w, PrioPlan *pp) {
@@ -138,23 +129,19 @@ int prepare_priority(same_window *w, PrioPlan *pp) {
         a.near = c.take<int32_t>((size_t)n);
         a.claim = c.take<int32_t>((size_t)n_r);
         a.rank = c.take<int32_t>((size_t)P0);
-        a.prow = c.take<int32_t>((size_t)n + 1);
-        a.pairs = c.take<int32_t>((size_t)P0 * 2);
-        a.jsec = c.take<int32_t>((size_t)P0);
-        a.cost = c.take<double>((size_t)P0);
+        a.dst.prow = c.take<int32_t>((size_t)n + 1);
+        a.dst.pairs = c.take<int32_t>((size_t)P0 * 2);
+        a.dst.jsec = c.take<int32_t>((size_t)P0);
+        a.dst.cost64 = c.take<double>((size_t)P0);
         return c.off;
     };
     SAME_TRY(ensure(ctx, w->prio, lay(Carver())));
     lay(Carver(w->prio.p));
     pp->zero = ZeroArgs{{w->prio.p, nullptr}, {zero_bytes, 0}};
     a.n = n;
-    a.P0 = P0;
     a.n_r = n_r;
-    a.prow0 = w->prow;
-    a.pairs0 = w->pairs;
-    a.jsec0 = w->jsec;
+    a.src = list_of(w);
     a.rows_ua = w->rows_ua;
-    a.cost0 = w->cost64;
     a.axy = w->axy_c;
     a.ref_xy = w->ref->xy;
     a.code_m = w->mov->label_codes;
@@ -165,21 +152,14 @@ int prepare_priority(same_window *w, PrioPlan *pp) {
 
 int launch_priority(same_ctx *ctx, PrioPlan *const *pps, int n_w) {
     Batch<PrioArgs> b{};
-    ZeroArgs zr[SAME_LAUNCH_WINDOWS];
-    int64_t max_P = 0, max_n = 0, max_r = 0;
-    for (int q = 0; q < n_w; ++q) {
-        b.w[q] = pps[q]->a;
-        zr[q] = pps[q]->zero;
-        max_P = std::max(max_P, pps[q]->a.P0);
-        max_n = std::max(max_n, pps[q]->a.n);
-        max_r = std::max(max_r, pps[q]->a.n_r);
-    }
-    const unsigned nw = (unsigned)n_w;
-    SAME_TRY(launch_zero(ctx, zr, n_w));
-    SAME_LAUNCH(ctx, prio_init_kernel, dim3(grid_for(std::max(max_r, max_n)), nw), dim3(256), 0, b);
-    SAME_LAUNCH(ctx, prio_rank_kernel, dim3(grid_for(max_P), nw), dim3(256), 0, b);
-    SAME_LAUNCH(ctx, prio_rows_kernel, dim3(scan::blocks_for(max_n), nw), dim3(scan::NT), 0, b);
-    SAME_LAUNCH(ctx, prio_scatter_kernel, dim3(grid_for(max_P), nw), dim3(256), 0, b);
+    ListGrid g;
+    SAME_TRY(begin_group(ctx, pps, n_w, &b, &g));
+    int64_t max_r = 0;
+    for (int q = 0; q < n_w; ++q) max_r = std::max(max_r, b.w[q].n_r);
+    SAME_LAUNCH(ctx, prio_init_kernel, dim3(grid_for(std::max(max_r, g.max_n)), g.nw), dim3(256), 0, b);
+    SAME_LAUNCH(ctx, prio_rank_kernel, dim3(grid_for(g.max_P), g.nw), dim3(256), 0, b);
+    SAME_LAUNCH(ctx, prio_rows_kernel, dim3(scan::blocks_for(g.max_n), g.nw), dim3(scan::NT), 0, b);
+    SAME_LAUNCH(ctx, prio_scatter_kernel, dim3(grid_for(g.max_P), g.nw), dim3(256), 0, b);
     HIP_TRY(ctx, hipGetLastError());
     return SAME_OK;
 }
@@ -233,54 +213,30 @@ int same_window_priority_pairs(same_window *const *windows, int n_windows, int64
         rc = prepare_priority(w, &plans[(size_t)i]);
         if (rc == SAME_OK) live.push_back(i);
     }
-    // ONE wait for the batch: per group of SAME_LAUNCH_WINDOWS windows the zeroing and the four kernels, then every window's count block
-    // straight into the head of its pinned block, where the stage call left the staged counts
-    for (size_t g = 0; g < live.size() && rc == SAME_OK; g += SAME_LAUNCH_WINDOWS) {
-        const int n_g = (int)std::min<size_t>(SAME_LAUNCH_WINDOWS, live.size() - g);
-        PrioPlan *pps[SAME_LAUNCH_WINDOWS];
-        for (int q = 0; q < n_g; ++q) pps[q] = &plans[(size_t)live[g + (size_t)q]];
-        rc = launch_priority(ctx, pps, n_g);
-        CopyArgs ca[SAME_LAUNCH_WINDOWS];
-        for (int q = 0; q < n_g && rc == SAME_OK; ++q) {
-            same_window *w = windows[live[g + (size_t)q]];
-            ca[q] = CopyArgs{};
-            if (w->host_dev) {
-                ca[q] = CopyArgs{{w->counts, nullptr}, {w->host_dev, nullptr}, {64, 0}};
-                continue;
-            }
-            hipError_t e = hipMemcpyAsync(w->host, w->counts, 64, hipMemcpyDeviceToHost, ctx->stream);
-            ++ctx->stats[SAME_STAT_COPIES];
-            if (e != hipSuccess) rc = same_fail(ctx, SAME_EIO, "priority prune copy back", e);
-        }
-        if (rc == SAME_OK) rc = launch_copy_back(ctx, ca, n_g);
-    }
-    if (rc != SAME_OK) {
-        // nothing of a failed batch counts: windows of earlier groups have their count blocks overwritten already, so every window the
-        // call touched is no longer staged (as same_window_stage leaves a failed batch); what was enqueued is waited for first
-        (void)hipStreamSynchronize(ctx->stream);
-        for (int i : live) windows[i]->staged = 0;
-        return rc;
-    }
+    // ONE wait for the batch: per group the zeroing and the four kernels, then every window's count block into the head of its pinned
+    // block, where the stage call left the staged counts
+    if (rc == SAME_OK)
+        rc = for_each_group(plans, live, [&](PrioPlan *const *pps, const int *at, int n_g) {
+            SAME_TRY(launch_priority(ctx, pps, n_g));
+            Back back[SAME_LAUNCH_WINDOWS];
+            for (int q = 0; q < n_g; ++q) back[q] = Back{windows[at[q]], windows[at[q]]->counts, 64};
+            return copy_back_group(ctx, back, n_g, "priority prune copy back");
+        });
+    if (rc != SAME_OK) return fail_batch(ctx, windows, live, rc);
     if (!live.empty()) SAME_WAIT(ctx);
     for (int i : live) {
         same_window *w = windows[i];
         const PrioArgs &a = plans[(size_t)i].a;
         const unsigned long long *tot = static_cast<const unsigned long long *>(w->host);
         const int64_t P = (int64_t)tot[3], one = (int64_t)tot[4];
-        REQUIRE(ctx, P >= a.n && P <= a.P0 && one >= 0 && one <= a.n && (int64_t)tot[2] == a.n);
-        w->pr_pairs = w->pairs;
-        w->pr_jsec = w->jsec;
-        w->pr_P = a.P0;
-        w->prow = a.prow;
-        w->pairs = a.pairs;
-        w->jsec = a.jsec;
-        w->cost64 = a.cost;
-        w->P = P;
+        REQUIRE(ctx, P >= a.n && P <= a.src.P && one >= 0 && one <= a.n && (int64_t)tot[2] == a.n);
+        PairList left = a.dst;
+        left.P = P;
+        w->pr = a.src;                            // the list as staged stays what as_staged() answers
+        turn_to(w, left);
         w->prio_ok = 1;
-        w->lim_row = w->pr_jsec;                  // the frame of the reference limits: the references the STAGED list names
-        w->lim_P = w->pr_P;
         int64_t *counts = out_counts + 4 * i;
-        counts[0] = a.P0;
+        counts[0] = a.src.P;
         counts[1] = P;
         counts[2] = one;
         counts[3] = a.n - one;

@@ -9,6 +9,9 @@
 // list of reference rows in the box -- what the reference's frames would index before src/utils.py:740-742 drops the unreferenced)
 // is only looked up for the pair list handed out and for the greedy rule's per-column state.  A window's numbers are those of
 // the column pipeline bit for bit (tests/test_gpu_run_same.py::test_device_windows_*).
+//
+// Also here, beside the launches every window call shares (launch_zero, launch_rows, launch_copy_back, check_batch): the batch driver of
+// the calls that work on staged windows (copy_back_group, fail_batch; window_internal.h states the protocol and the group walk).
 #include "window_internal.h"
 
 namespace {
@@ -401,6 +404,29 @@ int launch_zero(same_ctx *ctx, const ZeroArgs *regions, int n_w) {
     return SAME_OK;
 }
 
+// the batch driver (window_internal.h): the ONE place where a window's hand-back is a region of the group's launch or a copy of its own
+int copy_back_group(same_ctx *ctx, const Back *back, int n_w, const char *what, bool engine) {
+    CopyArgs ca[SAME_LAUNCH_WINDOWS];
+    for (int q = 0; q < n_w; ++q) {
+        same_window *w = back[q].w;
+        ca[q] = CopyArgs{};
+        if (w->host_dev && !engine) {
+            ca[q] = CopyArgs{{back[q].src, nullptr}, {w->host_dev, nullptr}, {back[q].bytes, 0}};
+            continue;
+        }
+        hipError_t e = hipMemcpyAsync(w->host, back[q].src, back[q].bytes, hipMemcpyDeviceToHost, ctx->stream);
+        ++ctx->stats[SAME_STAT_COPIES];
+        if (e != hipSuccess) return same_fail(ctx, SAME_EIO, what, e);
+    }
+    return launch_copy_back(ctx, ca, n_w);
+}
+
+int fail_batch(same_ctx *ctx, same_window *const *windows, const std::vector<int> &touched, int rc) {
+    (void)hipStreamSynchronize(ctx->stream);
+    for (int i : touched) windows[i]->staged = 0;
+    return rc;
+}
+
 // a batch call's windows: one context, no window twice
 int check_batch(same_window *const *windows, int n_windows, same_ctx **out_ctx) {
     if (!windows || n_windows < 1 || !windows[0]) return SAME_EINVAL;
@@ -442,13 +468,9 @@ int prepare_stage(same_window *w, const same_section *mov, const same_section *r
     w->n_m = w->n_r = w->n_ua = w->P = w->Tr = 0;
     w->caller_sel = w->caller_ok = 0;             // the stage call's arrays are the window's again
     w->held = same_window::Held{};
-    w->lim_row = nullptr;
-    w->lim_P = 0;
     w->prio_ok = 0;                               // ... and its pair list the only one
-    w->pr_pairs = w->pr_jsec = nullptr;
-    w->pr_P = 0;
+    w->pr = PairList{};
     w->k_staged = k;                              // ... at the k it was staged at (same_window_knn_prefix: w->k is the list's)
-    w->sk = same_window::StagedList{};
     w->bins_m = mov->bins;                        // (the caller holds both grid locks)
     w->bins_r = ref->bins;
     for (int q = 0; q < 4; ++q) w->box[q] = box[q];
@@ -500,10 +522,7 @@ int prepare_stage(same_window *w, const same_section *mov, const same_section *r
     w->host_filter_off = w->host_finish_off + ((finish_back_bytes(cap_m) + 255) & ~size_t(255));     // (n_ua <= cap_m)
     SAME_TRY(ensure_host(w, w->host_filter_off + 256));
     lay(Carver(w->stage.p));
-    w->sk.prow = w->prow;                         // the list as staged: what a k-NN prefix is derived from (window_knn_prefix.hip)
-    w->sk.pairs = w->pairs;
-    w->sk.jsec = w->jsec;
-    w->sk.cost64 = w->cost64;
+    w->sk = list_of(w);                           // the list as staged: what a k-NN prefix is derived from (window_knn_prefix.hip; P: collect_stage)
     // aligned boxes: the merged list IS the row list; whole-section path: its own list is copied in
     w->rows_m = compact_m || !cm.use_runs ? rows_m : reinterpret_cast<int32_t *>(merged_m);
     w->rows_r = compact_r || !cr.use_runs ? rows_r : reinterpret_cast<int32_t *>(merged_r);
@@ -638,40 +657,25 @@ int same_window_stage(same_window *const *windows, int n_windows, const same_sec
     // both sections' grids stay as they are until this call's kernels are enqueued (same_section_bin waits for this, then for the device)
     std::shared_lock<std::shared_mutex> grid_m(const_cast<same_section *>(mov)->grid_lock), grid_r;
     if (ref != mov) grid_r = std::shared_lock<std::shared_mutex>(const_cast<same_section *>(ref)->grid_lock);
-    // every window's buffer is laid out and zeroed, then the kernels run per group of SAME_LAUNCH_WINDOWS windows (one launch each for the
-    // whole group), then every window's copy back; ONE wait for the batch
+    // every window's buffer is laid out, then the kernels run per group of SAME_LAUNCH_WINDOWS windows (one launch each for the whole
+    // group) -- ALL groups' kernels first --, then per group what comes back per window: the four counts, then the kept aligned rows' XY
+    // and section rows at the capacity cap_m; ONE wait for the batch
     std::vector<StagePlan> plans((size_t)n_windows);
+    std::vector<int> live((size_t)n_windows);
     int rc = SAME_OK;
+    for (int i = 0; i < n_windows; ++i) live[(size_t)i] = i;
     for (int i = 0; i < n_windows && rc == SAME_OK; ++i) rc = prepare_stage(windows[i], mov, ref, boxes + 4 * i, k, &plans[(size_t)i]);
-    for (int g = 0; g < n_windows && rc == SAME_OK; g += SAME_LAUNCH_WINDOWS) {
-        StagePlan *sps[SAME_LAUNCH_WINDOWS];
-        const int n_g = std::min(SAME_LAUNCH_WINDOWS, n_windows - g);
-        for (int q = 0; q < n_g; ++q) sps[q] = &plans[(size_t)(g + q)];
-        rc = launch_stage(ctx, windows + g, sps, n_g, mov, ref, ix.get(), k, dist_ct_coeff);
-    }
-    // what comes back per window -- the four counts, then the kept aligned rows' XY and section rows at the capacity cap_m -- in one launch
-    // per group (straight into the pinned blocks), or one copy per window where a block is not device-addressable
-    for (int g = 0; g < n_windows && rc == SAME_OK; g += SAME_LAUNCH_WINDOWS) {
-        CopyArgs ca[SAME_LAUNCH_WINDOWS];
-        const int n_g = std::min(SAME_LAUNCH_WINDOWS, n_windows - g);
-        for (int q = 0; q < n_g && rc == SAME_OK; ++q) {
-            same_window *w = windows[g + q];
-            ca[q] = CopyArgs{};
-            if (w->host_dev) {
-                ca[q] = CopyArgs{{w->counts, nullptr}, {w->host_dev, nullptr}, {plans[(size_t)(g + q)].back_bytes, 0}};
-                continue;
-            }
-            hipError_t e = hipMemcpyAsync(w->host, w->counts, plans[(size_t)(g + q)].back_bytes, hipMemcpyDeviceToHost, ctx->stream);
-            ++ctx->stats[SAME_STAT_COPIES];
-            if (e != hipSuccess) rc = same_fail(ctx, SAME_EIO, "stage copy back", e);
-        }
-        if (rc == SAME_OK) rc = launch_copy_back(ctx, ca, n_g);
-    }
-    if (rc != SAME_OK) {                          // nothing of a failed batch counts; what was enqueued is waited for before returning
-        (void)hipStreamSynchronize(ctx->stream);
-        for (int i = 0; i < n_windows; ++i) windows[i]->staged = 0;
-        return rc;
-    }
+    if (rc == SAME_OK)
+        rc = for_each_group(plans, live, [&](StagePlan *const *sps, const int *at, int n_g) {
+            return launch_stage(ctx, windows + at[0], sps, n_g, mov, ref, ix.get(), k, dist_ct_coeff);
+        });
+    if (rc == SAME_OK)
+        rc = for_each_group(plans, live, [&](StagePlan *const *sps, const int *at, int n_g) {
+            Back back[SAME_LAUNCH_WINDOWS];
+            for (int q = 0; q < n_g; ++q) back[q] = Back{windows[at[q]], windows[at[q]]->counts, sps[q]->back_bytes};
+            return copy_back_group(ctx, back, n_g, "stage copy back");
+        });
+    if (rc != SAME_OK) return fail_batch(ctx, windows, live, rc);
     SAME_WAIT(ctx);
     for (int i = 0; i < n_windows; ++i) SAME_TRY(collect_stage(windows[i], plans[(size_t)i], out_counts + 4 * i));
     return SAME_OK;
@@ -701,10 +705,7 @@ int same_window_fetch(same_window *w, int what, void *out, int64_t bytes) {
     case SAME_WINDOW_MATCH: want = n_ua * 4; dev = w->match_loc; REQUIRE(ctx, w->finished); break;
     case SAME_WINDOW_TRIANGLES: want = Tr * 12; dev = w->tris.p; REQUIRE(ctx, w->finished || w->filtered); break;
     case SAME_WINDOW_CALLER_TRIANGLES: want = w->n_sel * 12; dev = w->sel_tris; REQUIRE(ctx, w->caller_sel); break;
-    case SAME_WINDOW_STAGED_PAIRS:
-        want = (w->prio_ok ? w->pr_P : w->caller_ok ? w->st0.P : P) * 8;
-        dev = w->prio_ok ? w->pr_pairs : w->caller_ok ? w->st0.pairs : w->pairs;
-        break;
+    case SAME_WINDOW_STAGED_PAIRS: want = as_staged(w).P * 8; dev = as_staged(w).pairs; break;
     default: REQUIRE(ctx, !"unknown same_window_fetch selector");
     }
     REQUIRE(ctx, bytes == want);

@@ -705,6 +705,26 @@ def _handles(states):
     return (ctypes.c_void_p * len(states))(*[s.handle.value for s in states])
 
 
+def _staged_anew(states, counts):
+    """the states of windows a call left as a stage call leaves them (same_window_stage; same_window_knn_prefix): their counts, a pair
+    list that is the list as staged, no triangles, no prune  -> [counts per window]"""
+    for s, c in zip(states, counts.tolist()):
+        s.counts, s.n_triangles = tuple(c), 0
+        s.n_staged_pairs, s.priority = c[3], None
+    return [s.counts for s in states]
+
+
+def _compacted(states, counts):
+    """the states of windows a call left without their unconstrained nodes (same_window_caller_tris; same_window_caller_pairs): the
+    triangles selected, the kept cells and pairs left  -> [the call's six counts per window]"""
+    out = []
+    for s, c in zip(states, counts.tolist()):
+        s.n_selected, s.n_triangles = c[0], 0
+        s.counts = (s.counts[0], s.counts[1], c[3], c[4])
+        out.append(tuple(c))
+    return out
+
+
 def stage_windows(states, moving, ref, boxes, radius, knn, dist_ct_coeff):
     """same_window_stage for a batch of windows of one context (one wait for all of them).  -> [counts per window]"""
     ctx, n = states[0].ctx, len(states)
@@ -713,10 +733,9 @@ def stage_windows(states, moving, ref, boxes, radius, knn, dist_ct_coeff):
     with ctx.lock:
         ctx.check(ctx.lib.same_window_stage(_handles(states), n, moving.handle, ref.handle, boxes.ctypes.data, float(radius), int(knn),
                                             float(dist_ct_coeff), counts.ctypes.data), "same_window_stage")
-    for s, c in zip(states, counts.tolist()):
-        s.counts, s.n_triangles = tuple(c), 0
-        s.n_staged_pairs, s.n_selected, s.priority = c[3], 0, None
-    return [s.counts for s in states]
+    for s in states:
+        s.n_selected = 0
+    return _staged_anew(states, counts)
 
 
 def priority_windows(states):
@@ -745,10 +764,7 @@ def prefix_windows(states, k):
     counts = np.zeros((n, 4), np.int64)
     with ctx.lock:
         ctx.check(ctx.lib.same_window_knn_prefix(_handles(states), n, int(k), counts.ctypes.data), "same_window_knn_prefix")
-    for s, c in zip(states, counts.tolist()):
-        s.counts, s.n_triangles = tuple(c), 0
-        s.n_staged_pairs, s.priority = c[3], None
-    return [s.counts for s in states]
+    return _staged_anew(states, counts)
 
 
 class DeviceCallerTris(_DeviceHandle):
@@ -783,12 +799,7 @@ def caller_tris_windows(states, caller, radius, angle_enabled, cos_thr, near_tol
         ctx.check(ctx.lib.same_window_caller_tris(_handles(states), n, caller.handle, _lib._ptr(flat), _lib._ptr(offsets), float(radius),
                                                   int(angle_enabled), float(cos_thr), float(near_tol), int(bool(ignore_same_type)),
                                                   counts.ctypes.data), "same_window_caller_tris")
-    out = []
-    for s, c in zip(states, counts.tolist()):
-        s.n_selected, s.n_triangles = c[0], 0
-        s.counts = (s.counts[0], s.counts[1], c[3], c[4])
-        out.append(tuple(c))
-    return out
+    return _compacted(states, counts)
 
 
 def caller_pairs_windows(states):
@@ -801,12 +812,7 @@ def caller_pairs_windows(states):
     counts = np.zeros((n, 6), np.int64)
     with ctx.lock:
         ctx.check(ctx.lib.same_window_caller_pairs(_handles(states), n, counts.ctypes.data), "same_window_caller_pairs")
-    out = []
-    for s, c in zip(states, counts.tolist()):
-        s.n_selected, s.n_triangles = c[0], 0
-        s.counts = (s.counts[0], s.counts[1], c[3], c[4])
-        out.append(tuple(c))
-    return out
+    return _compacted(states, counts)
 
 
 def _window_records(stats_words, mode):

@@ -594,6 +594,27 @@ int same_window_priority_pairs(same_window *const *windows, int n_windows, int64
  *     changes: k < 1, k above the k a window was staged at, a window not staged. */
 int same_window_knn_prefix(same_window *const *windows, int n_windows, int k, int64_t *out_counts);
 
+/* ---- staged windows priced again from another type matrix of the moving section (csrc/window_recost.hip): what a study over VARIANTS
+ * of the moving frame's type columns needs instead of a stage call (and a triangulation) per variant.  Rows, prune, compaction,
+ * reference numbers, triangle filter and priority prune do not read the type columns; the pair costs do.
+ *   same_types_layer: a resident copy of one (n, T) double matrix for the rows of an existing section -- and, in a float section, its
+ *     float copy, made once as same_section_create makes the section's own.  Created from a host pointer (row-major, the section's n and
+ *     T), destroyed on its own; it must not outlive its section.  Read-only: the contexts of its device share it.  Where a call takes a
+ *     layer, NULL means the section's own types.
+ *   same_window_recost: for each staged window of the batch (ONE wait; none when no window has pairs or was compacted): the costs of
+ *     the pair list AS STAGED are written again -- moving rows from `layer`, reference rows from `ref`, the stage call's expression in
+ *     the stage call's order, bit for bit what same_window_stage computes for a moving section created with the layer's matrix -- and
+ *     the window is from then on what same_window_knn_prefix at the staged k leaves: the staged list current, an earlier prefix,
+ *     priority prune or finish no longer holding, a caller's compaction turned back and HELD for same_window_caller_pairs.
+ *     `moving` / `ref` are the sections the windows were staged from, dist_ct_coeff the weight of the stage call's cost.
+ *     out_counts[4 i ..] as same_window_stage reports them.  SAME_EINVAL before anything changes: a window not staged or staged from
+ *     other sections, a layer of another section. */
+typedef struct same_types_layer same_types_layer;
+int same_types_layer_create(same_ctx *ctx, const same_section *section, const double *types, same_types_layer **out);
+void same_types_layer_destroy(same_types_layer *layer);
+int same_window_recost(same_window *const *windows, int n_windows, const same_section *moving, const same_section *ref,
+                       const same_types_layer *layer /* may be NULL */, double dist_ct_coeff, int64_t *out_counts);
+
 /* ---- a6 on the window path without the library call --------------------------------------------------------------------------
  * The reference triangulates every window's kept aligned cells with scipy.spatial.Delaunay (Qhull; src/same.py:1023), on the host
  * -- three quarters of a cfg 5 pass.  same_delaunay2d is this library's own triangulator (HOST code, no device, no context, safe to
@@ -761,6 +782,10 @@ int same_merge_acc_fetch(same_merge_acc *acc, int what, void *out, int64_t bytes
  * same_section_create. */
 int same_merge_acc_columns(same_merge_acc *acc, const same_section *moving, const same_section *ref, const void *const *extra_moving,
                            int n_extra_moving, const void *const *extra_ref, int n_extra_ref, void *out_host, int64_t n_final);
+/* ... with the moving section's type columns read from a types layer of it (NULL: the section's own -- the call above) */
+int same_merge_acc_columns_layer(same_merge_acc *acc, const same_section *moving, const same_types_layer *layer /* may be NULL */,
+                                 const same_section *ref, const void *const *extra_moving, int n_extra_moving, const void *const *extra_ref,
+                                 int n_extra_ref, void *out_host, int64_t n_final);
 int same_host_alloc(same_ctx *ctx, size_t bytes, void **out_ptr);
 int same_host_free(same_ctx *ctx, void *ptr);
 

@@ -121,6 +121,9 @@ _PROTOTYPES = {
     "same_section_set_label_codes": [c_vp, c_vp],
     "same_window_priority_pairs": [c_vp, c_int, c_vp],
     "same_window_knn_prefix": [c_vp, c_int, c_int, c_vp],
+    "same_types_layer_create": [c_vp, c_vp, c_vp, ctypes.POINTER(c_vp)],
+    "same_types_layer_destroy": [c_vp],
+    "same_window_recost": [c_vp, c_int, c_vp, c_vp, c_vp, c_dbl, c_vp],
     "same_sparse_assign": [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp],
     "same_sparse_assign_cap": [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_dbl, c_vp, c_vp],
     "same_refine_matching": [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_dbl, c_i64, c_vp, c_vp],
@@ -138,6 +141,7 @@ _PROTOTYPES = {
     "same_merge_acc_plain": [c_vp, c_int, ctypes.POINTER(c_i64)],
     "same_merge_acc_fetch": [c_vp, c_int, c_vp, c_i64],
     "same_merge_acc_columns": [c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_i64],
+    "same_merge_acc_columns_layer": [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_i64],
     "same_host_alloc": [c_vp, c_sz, ctypes.POINTER(c_vp)],
     "same_host_free": [c_vp, c_vp],
     "same_comm_unique_id": [c_vp],
@@ -205,6 +209,7 @@ def load():
             L.same_section_destroy.restype = None
             L.same_window_destroy.restype = None
             L.same_caller_tris_destroy.restype = None
+            L.same_types_layer_destroy.restype = None
             if L.same_abi_version() != ABI_VERSION:
                 raise SameHipError(-22, "libsame_hip ABI version mismatch")
             _lib = L

@@ -327,4 +327,43 @@ void same_section_destroy(same_section *s) {
     delete s;
 }
 
+// One more type matrix for the rows of `s` (window_internal.h, same_types_layer): the doubles and, in a float section, their float copy
+// made once, as same_section_create makes the section's own.
+int same_types_layer_create(same_ctx *ctx, const same_section *s, const double *types, same_types_layer **out) {
+    REQUIRE(ctx, ctx && out);
+    *out = nullptr;
+    REQUIRE(ctx, s && s->ctx->device == ctx->device && (s->n == 0 || s->T == 0 || types));
+    SAME_TRY(same_use(ctx));
+    same_types_layer *l = new (std::nothrow) same_types_layer();
+    if (!l) return SAME_ENOMEM;
+    l->ctx = ctx;
+    l->sec = s;
+    *out = l;                                     // freed by the caller's destroy on any failure below
+    const int64_t n = s->n;
+    const int T = s->T;
+    const size_t count = (size_t)std::max<int64_t>(n, 1) * (size_t)std::max(T, 1);
+    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&l->types64), count * sizeof(double)));
+    if (n && T) HIP_TRY(ctx, hipMemcpyAsync(l->types64, types, (size_t)n * T * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (!s->cost_f32) {
+        l->types_c = l->types64;
+    } else {
+        HIP_TRY(ctx, hipMalloc(&l->types_c, count * sizeof(float)));
+        if (n && T) {
+            hipLaunchKernelGGL(to_float_kernel, dim3(grid_for(n * T)), dim3(256), 0, ctx->stream, l->types64, n * T, static_cast<float *>(l->types_c));
+            HIP_TRY(ctx, hipGetLastError());
+        }
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return SAME_OK;
+}
+
+void same_types_layer_destroy(same_types_layer *l) {
+    if (!l) return;
+    (void)hipSetDevice(l->ctx->device);
+    (void)hipDeviceSynchronize();                 // windows of other contexts may still be reading the layer
+    if (l->types_c && l->types_c != l->types64) (void)hipFree(l->types_c);
+    if (l->types64) (void)hipFree(l->types64);
+    delete l;
+}
+
 }  // extern "C"

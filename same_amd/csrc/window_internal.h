@@ -1,5 +1,5 @@
 // window_internal.h -- what the translation units of the device-resident window path share (section.hip, window_stage.hip,
-// window_finish.hip, window_merge.hip, window_caller.hip, window_priority.hip, window_knn_prefix.hip): the resident objects behind the
+// window_finish.hip, window_merge.hip, window_caller.hip, window_priority.hip, window_knn_prefix.hip, window_recost.hip): the resident objects behind the
 // opaque handles of include/same_hip.h part 4, the per-launch argument blocks, a window's pair list (win::PairList) and the one
 // statement of which list is "the list as staged" (win::as_staged), the small host helpers and the batch driver of the window calls.
 //
@@ -264,6 +264,16 @@ struct same_section {
     std::shared_mutex grid_lock;
 };
 
+// A types layer of a section (same_types_layer_create, section.hip): one more (n, T) type matrix for the section's rows, resident like
+// the section's own -- the doubles as the caller gave them and, in a float section, their float copy.  Read-only after its creation; it
+// must not outlive its section.  Where a call takes a layer, NULL means the section's own types.
+struct same_types_layer {
+    same_ctx *ctx = nullptr;
+    const same_section *sec = nullptr;
+    void *types_c = nullptr;   // [n][T] in the section's cost type
+    double *types64 = nullptr; // [n][T] (== types_c for fp64 costs)
+};
+
 struct same_window {
     same_ctx *ctx = nullptr;
     const same_section *mov = nullptr, *ref = nullptr;
@@ -386,6 +396,33 @@ inline void turn_to(same_window *w, const same_window::Staged &s) {
 // (it resets both).  It is what SAME_WINDOW_STAGED_PAIRS hands out, and its reference rows (jsec, P of them) are the frame the model's
 // reference limits are read over: the frame is the prune's, src/same.py:1055-1085 does not compact the reference side again.
 inline PairList as_staged(const same_window *w) { return w->prio_ok ? w->pr : w->caller_ok ? w->st0.list : list_of(w); }
+
+// The two steps the calls share that leave a window "as a stage call at k leaves it" (the k-NN prefix, window_knn_prefix.hip; the recost,
+// window_recost.hip).
+// hold_caller: a window same_window_caller_tris compacted goes back to the stage call's arrays (st0), the caller's work HELD for
+// same_window_caller_pairs; -> the bytes of the pinned block's head the call has to bring back (64: the counts; a window turned back:
+// the staged counts, XY and rows again, its pinned block holds the compacted ones)
+inline size_t hold_caller(same_window *w) {
+    size_t back = 64;
+    if (w->caller_ok) {
+        w->held.cs = staged_of(w);
+        turn_to(w, w->st0);
+        w->held.on = 1;
+        back = w->held.back_bytes;
+    }
+    w->caller_sel = w->caller_ok = 0;             // (selected but left as staged -- a cosine at the threshold -- : nothing is held)
+    return back;
+}
+// staged_at: the window's pair list is `l`, as a stage call at k leaves it: nothing derived from an earlier list holds any more
+// (as_staged: `l`)
+inline void staged_at(same_window *w, int k, const PairList &l) {
+    turn_to(w, l);
+    w->k = k;
+    w->prio_ok = 0;
+    w->pr = PairList{};
+    w->filtered = w->finished = 0;
+    w->Tr = 0;
+}
 
 // section.hip
 int knn_index_for(same_ctx *ctx, const same_section *ref, double radius, std::shared_ptr<same_knn_index> *out);

@@ -106,16 +106,6 @@ int launch_prefix(same_ctx *ctx, PrefixPlan *const *pps, int n_w) {
     return SAME_OK;
 }
 
-// the window's pair list is `l`, as a stage call at k leaves it: nothing derived from an earlier list holds any more (as_staged: `l`)
-void turn_to(same_window *w, int k, const PairList &l) {
-    win::turn_to(w, l);
-    w->k = k;
-    w->prio_ok = 0;
-    w->pr = PairList{};
-    w->filtered = w->finished = 0;
-    w->Tr = 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -132,16 +122,7 @@ int same_window_knn_prefix(same_window *const *windows, int n_windows, int k, in
     // a compacted window: back to the stage call's arrays, the caller's work held.  Its pinned block holds the compacted counts, XY and
     // rows: the staged ones take their place again below (`back`: what comes back per window)
     std::vector<size_t> back((size_t)n_windows, 64);
-    for (int i = 0; i < n_windows; ++i) {
-        same_window *w = windows[i];
-        if (w->caller_ok) {
-            w->held.cs = staged_of(w);
-            win::turn_to(w, w->st0);
-            w->held.on = 1;
-            back[(size_t)i] = w->held.back_bytes;
-        }
-        w->caller_sel = w->caller_ok = 0;         // (selected but left as staged -- a cosine at the threshold -- : nothing is held)
-    }
+    for (int i = 0; i < n_windows; ++i) back[(size_t)i] = hold_caller(windows[i]);
     std::vector<PrefixPlan> plans((size_t)n_windows);
     std::vector<int> live;
     int rc = SAME_OK;
@@ -192,10 +173,10 @@ int same_window_knn_prefix(same_window *const *windows, int n_windows, int k, in
         if (derived) {
             PairList cut = plans[(size_t)i].a.dst;
             cut.P = (int64_t) static_cast<const unsigned long long *>(w->host)[3];
-            turn_to(w, k, cut);
+            staged_at(w, k, cut);
             ++at;
         } else {
-            turn_to(w, k, w->sk);
+            staged_at(w, k, w->sk);
             static_cast<unsigned long long *>(w->host)[3] = (unsigned long long)w->sk.P;     // the count block's host copy: the list's
         }
         int64_t *counts = out_counts + 4 * i;

@@ -645,10 +645,19 @@ int same_merge_acc_finish(same_merge_acc *a, const int32_t *winner_rows, int64_t
 
 int same_merge_acc_columns(same_merge_acc *a, const same_section *mov, const same_section *ref, const void *const *extra_mov, int n_extra_mov,
                            const void *const *extra_ref, int n_extra_ref, void *out_host, int64_t n_final) {
+    return same_merge_acc_columns_layer(a, mov, nullptr, ref, extra_mov, n_extra_mov, extra_ref, n_extra_ref, out_host, n_final);
+}
+
+// ... with the moving side's type block read from a types layer of `mov` (NULL: the section's own)
+int same_merge_acc_columns_layer(same_merge_acc *a, const same_section *mov, const same_types_layer *layer, const same_section *ref,
+                                 const void *const *extra_mov, int n_extra_mov, const void *const *extra_ref, int n_extra_ref, void *out_host,
+                                 int64_t n_final) {
     if (!a) return SAME_EINVAL;
     same_ctx *ctx = a->ctx;
+    REQUIRE(ctx, !layer || (mov && layer->sec == mov && layer->ctx->device == ctx->device));
+    const double *types64 = !mov ? nullptr : layer ? layer->types64 : mov->types64;
     REQUIRE(ctx, a->resolved == 2 && !a->loaded && mov && ref && n_final == a->n_final && (n_final == 0 || out_host));
-    REQUIRE(ctx, mov->ctx->device == ctx->device && ref->ctx->device == ctx->device && (mov->T == 0 || mov->types64));
+    REQUIRE(ctx, mov->ctx->device == ctx->device && ref->ctx->device == ctx->device && (mov->T == 0 || types64));
     REQUIRE(ctx, n_extra_mov >= 0 && n_extra_mov <= MAX_EXTRA_COLUMNS && n_extra_ref >= 0 && n_extra_ref <= MAX_EXTRA_COLUMNS);
     REQUIRE(ctx, (n_extra_mov == 0 || extra_mov) && (n_extra_ref == 0 || extra_ref));
     if (n_final == 0) return SAME_OK;
@@ -670,7 +679,7 @@ int same_merge_acc_columns(same_merge_acc *a, const same_section *mov, const sam
         REQUIRE(ctx, extra_ref[q]);
         ex.ref[q] = static_cast<const unsigned long long *>(extra_ref[q]);
     }
-    SAME_LAUNCH(ctx, table_columns_kernel, dim3(grid_for(n_final)), dim3(256), 0, static_cast<const FinalRec *>(a->out.p), n_final, mov->types64, mov->T,
+    SAME_LAUNCH(ctx, table_columns_kernel, dim3(grid_for(n_final)), dim3(256), 0, static_cast<const FinalRec *>(a->out.p), n_final, types64, mov->T,
                 mov->xy, ref->xy, ex, static_cast<unsigned long long *>(dev));
     HIP_TRY(ctx, hipGetLastError());
     return SAME_OK;

@@ -121,9 +121,18 @@ class _TableBuilder:
         # a frame's column may be a strided view of its block (a frame made from a 2-D array): np.take would copy such a source whole on
         # EVERY call, so the 1-D sources are made contiguous here, once per job (no copy where they already are)
         col = lambda df, c: np.ascontiguousarray(df[c].to_numpy())
-        plain_types = all(mov[c].dtype == f64 for c in self.cts) and len(set(self.cts)) == len(self.cts)
-        self.type_block = sections[1].types if plain_types else None
-        self.type_cols = None if self.type_block is not None else [col(mov, c) for c in self.cts]
+        distinct = len(set(self.cts)) == len(self.cts)
+        # a type-matrix variant of the moving frame (variants.py): the job's type columns are the variant's -- float64, column t under
+        # commonCT[t] (a name listed twice holds its last column) -- and on the device its layer's
+        variant, self.layer = getattr(job, "variant_types", None), getattr(job, "variant_layer", None)
+        if variant is None:
+            plain_types = all(mov[c].dtype == f64 for c in self.cts) and distinct
+            self.type_block = sections[1].types if plain_types else None
+            self.type_cols = None if self.type_block is not None else [col(mov, c) for c in self.cts]
+        else:
+            self.type_block = variant if distinct else None
+            self.type_cols = None if distinct else [np.ascontiguousarray(variant[:, len(self.cts) - 1 - self.cts[::-1].index(c)])
+                                                    for c in self.cts]
         both_xy = all(df[c].dtype == f64 for df in (ref, mov) for c in ("X", "Y"))
         self.mov_xy, self.ref_xy = (sections[1].xy, sections[0].xy) if both_xy else (None, None)
         self.xy_cols = None if both_xy else ([col(mov, c) for c in ("X", "Y")], [col(ref, c) for c in ("X", "Y")])
@@ -232,7 +241,7 @@ class _TableBuilder:
         with stage("table: page-locked block + the device's gather enqueued"):
             extra = frames.table_columns(self.cid)
             got = acc.columns(frames.dmov, frames.dref, n, len(self.cts), [b for _n, b, _d in extra["mov"]],
-                              [b for _n, b, _d in extra["ref"]])
+                              [b for _n, b, _d in extra["ref"]], layer=self.layer)
         if got is None:
             return None
         wide, flags = got
@@ -516,9 +525,13 @@ def _merged_rows(job, frames, rows, channel):
     return M.merged_part_rows(a_ids, r_ids, viol, wid, pos, seam, channel.rank, channel.tables)
 
 
-def _device_pass(jobs, frames, workers, with_ref_idx, triangulator, merge=False, channel=None, batch=None, caller=None, priority=False):
+def _device_pass(jobs, frames, workers, with_ref_idx, triangulator, merge=False, channel=None, batch=None, caller=None, priority=False,
+                 variants=None):
     """The device route: ONE walk of the windows for `jobs` -- _WindowJobs over the same frames, plan and share of the plan that differ
-    in sweep.SWEEP_KEYS only (`sliding_window_incumbent`: its one job; `sliding_window_sweep`: a job per parameter set).  Every job has
+    in sweep.SWEEP_KEYS only (`sliding_window_incumbent`: its one job; `sliding_window_sweep`: a job per parameter set) and in the
+    type-matrix variant of the moving frame they are priced from (`sliding_window_variants`: a job per (variant, set); `variants` the
+    variants' windows.DeviceTypesLayers, None for the frame's own types; a job names its variant by `job.variant`, an index into them,
+    and carries the matrix and the layer as `job.variant_types` / `job.variant_layer`).  Every job has
     its own builders, accumulators and stats.  -> [(table, {plan position: stats record}) per job].  `caller`: the jobs' (one)
     triangulation as a windows.DeviceCallerTris -- selected once per batch, whatever the number of jobs.  A merge channel goes with a
     single job."""
@@ -537,7 +550,8 @@ def _device_pass(jobs, frames, workers, with_ref_idx, triangulator, merge=False,
     # (csrc/window_merge.hip); the merge runs there, and only what it could not decide alone comes to the host (`_merge_on_device`).
     # (window_local_indices needs every window's pair list on the host: the keys go through the builders then, `_merged_rows`.)
     accs, extra = None, []
-    device_table = builders[0][0].device_columns_possible() and os.environ.get("SAME_TABLE_COLUMNS", "device") != "host"
+    # (every job's builder: a variant's type columns are float64 whatever the frame's own are)
+    device_table = all(b[0].device_columns_possible() for b in builders) and os.environ.get("SAME_TABLE_COLUMNS", "device") != "host"
     stats = [{} for _ in jobs]
     try:
         if not with_ref_idx and (merge or (device_table and not job.all_matches)):
@@ -552,7 +566,7 @@ def _device_pass(jobs, frames, workers, with_ref_idx, triangulator, merge=False,
         if priority:                      # once, here: before a worker thread stages its first window (as the id codes above)
             frames.label_codes_on_device()
         pos_of = {id(w): pos for pos, w in job.todo}
-        sets = [(j.optim_params["knn"], j.mode, j.optim_params["no_match_penalty"]) for j in jobs]
+        sets = [(j.optim_params["knn"], j.mode, j.optim_params["no_match_penalty"], getattr(j, "variant", 0)) for j in jobs]
 
         def walk(q):
             collector = None
@@ -561,7 +575,7 @@ def _device_pass(jobs, frames, workers, with_ref_idx, triangulator, merge=False,
                                                                           [w["window_id"] for w in windows],
                                                                           [pos_of[id(w)] for w in windows])
             for dw in frames.windows([w for _p, w in job.todo[cut[q]:cut[q + 1]]], ctx=contexts[q], triangulator=triangulator,
-                                     collector=collector, batch=batch, caller=caller, priority=priority, sets=sets):
+                                     collector=collector, batch=batch, caller=caller, priority=priority, sets=sets, variants=variants):
                 s, pos = dw.set, pos_of[id(dw.window)]
                 if dw.error is not None:
                     raise _window_error(dw, jobs[s].optim_params)      # (the priority prune's own failure for a window without pairs)

@@ -218,6 +218,19 @@ class _DeviceFrames:
             known[key] = (moving_delaunay, None if rows is None else DeviceCallerTris(self.dmov, rows, self.ctx))
         return known[key][1]
 
+    def types_layer(self, variant, types):
+        """A type-matrix variant of the moving frame resident beside its section (windows.DeviceTypesLayer): `types` the variant as a
+        float64 (rows, commonCT) matrix, `variant` the caller's object it was read from.  Uploaded once per object and kept until close()
+        -- with a `resident_frames` object for that object's life; the worker contexts share it like a section."""
+        from .windows import DeviceTypesLayer
+
+        known = self.__dict__.setdefault("_types_layers", {})
+        if id(variant) not in known:
+            # (the caller's object is held with the entry: its id names it for as long as the entry lives)
+            with stage("a type-matrix variant of the moving frame to the device"):
+                known[id(variant)] = (variant, DeviceTypesLayer(self.dmov, types, self.ctx))
+        return known[id(variant)][1]
+
     def label_codes_on_device(self):
         """The joint codes of the two frames' `cell_type` labels (eval_utils._label_codes: equal code <=> labels that compare equal; a
         label that equals nothing is negative) in the sections' slot for them: what the cell-type-priority prune on the device compares
@@ -234,7 +247,7 @@ class _DeviceFrames:
                 self.__dict__["_label_codes_on_device"] = True
 
     def windows(self, plan, triangulate=True, ctx=None, triangulator=None, fetch_triangles=False, collector=None, batch=None, mode=None,
-                caller=None, priority=False, sets=None):
+                caller=None, priority=False, sets=None, variants=None):
         from .windows import iter_device_windows
 
         op = self.op
@@ -245,7 +258,7 @@ class _DeviceFrames:
                                    ignore_same_type_triangles=op["ignore_same_type_triangles"], no_match_penalty=op["no_match_penalty"],
                                    ctx=self.ctx if ctx is None else ctx, triangulate=triangulate, triangulator=triangulator,
                                    fetch_triangles=fetch_triangles, collector=collector, batch=batch, mode=mode, caller=caller,
-                                   priority=priority, sets=sets)
+                                   priority=priority, sets=sets, variants=variants)
 
     def accumulators(self, contexts, cid):
         """One merge accumulator per worker context (kept with the frames: a pass re-uses the arrays of the last), and the sections' id
@@ -320,6 +333,8 @@ class _DeviceFrames:
         for _held, tris in self.__dict__.pop("_caller_tris", {}).values():      # before the section they are binned by
             if tris is not None:
                 tris.close()
+        for _held, layer in self.__dict__.pop("_types_layers", {}).values():   # before the section they belong to
+            layer.close()
         for c in self._worker_ctx:
             c.close()
         self._worker_ctx = []

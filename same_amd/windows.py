@@ -431,6 +431,23 @@ class DeviceSection(_DeviceHandle):
         ops.section_set_label_codes(self.ctx, self.handle, codes, len(self.section.xy))
 
 
+class DeviceTypesLayer(_DeviceHandle):
+    """One more (n, T) type matrix for the rows of a DeviceSection, resident beside it (same_types_layer_create): `types` float64, the
+    commonCT columns in commonCT order, one row per section row; in a float32 section the float copy is made once, as the section's own.
+    What `recost_windows` prices a staged window's pair list from and `MergeAccumulator.columns` reads a table's type columns from.
+    Read-only: the worker contexts of the device share it.  Close it BEFORE its section."""
+
+    _ENTRY = ("same_types_layer_create", "same_types_layer_destroy")
+
+    def __init__(self, dsection, types, ctx=None):
+        want = dsection.section.types.shape
+        self.types = types = np.ascontiguousarray(types, dtype=np.float64)
+        if types.shape != want:
+            raise ValueError(f"a types layer of this section is {want}, not {types.shape}")
+        self.dsection = dsection
+        self._create(ctx, dsection.handle, types.ctypes.data if types.size else None)
+
+
 class DeviceWindow(_DeviceHandle):
     """Device state of one window in flight (same_window): `stage` then `filter_finish` (or `finish` with triangles filtered by the
     caller), arrays of the state through `fetch`.  `stage_windows` / `filter_finish_windows` run a BATCH of windows per library call."""
@@ -648,9 +665,9 @@ class MergeAccumulator(_DeviceHandle):
             self.ctx.check(self.ctx.lib.same_merge_acc_fetch(self.handle, 1, out.ctypes.data, out.nbytes), "same_merge_acc_fetch")
         return out
 
-    def columns(self, dmoving, dref, n_final, n_types, extra_moving=(), extra_ref=()):
+    def columns(self, dmoving, dref, n_final, n_types, extra_moving=(), extra_ref=(), layer=None):
         """After finish(): the merged table's columns written by the device straight into page-locked host memory (enqueue only:
-        `ctx.sync()` before reading): the moving section's type columns, X, Y, the reference's X, Y, the caller's extra 8-byte device
+        `ctx.sync()` before reading): the moving section's type columns (`layer`: a DeviceTypesLayer of `dmoving` to read them from), X, Y, the reference's X, Y, the caller's extra 8-byte device
         columns (DeviceBuffers of 8-byte values per moving / reference row: ids, sizes), aligned_idx, window_id and plan position as int64,
         and the two flag columns.  -> (uint64 array (n_types + 4 + extras + 3, n_final), uint8 array (2, n_final)) over a pooled block,
         or None when no block is to be had (the caller gathers on the host)."""
@@ -663,9 +680,13 @@ class MergeAccumulator(_DeviceHandle):
         em = (ctypes.c_void_p * max(1, len(extra_moving)))(*[b.ptr for b in extra_moving])
         er = (ctypes.c_void_p * max(1, len(extra_ref)))(*[b.ptr for b in extra_ref])
         with ctx.lock:
-            ctx.check(ctx.lib.same_merge_acc_columns(self.handle, dmoving.handle, dref.handle, em, len(extra_moving), er, len(extra_ref),
-                                                     ptr,
-                                                     int(n_final)), "same_merge_acc_columns")
+            if layer is None:
+                ctx.check(ctx.lib.same_merge_acc_columns(self.handle, dmoving.handle, dref.handle, em, len(extra_moving), er,
+                                                         len(extra_ref), ptr, int(n_final)), "same_merge_acc_columns")
+            else:
+                ctx.check(ctx.lib.same_merge_acc_columns_layer(self.handle, dmoving.handle, layer.handle, dref.handle, em,
+                                                               len(extra_moving), er, len(extra_ref), ptr, int(n_final)),
+                          "same_merge_acc_columns_layer")
         wide = np.frombuffer(buf, dtype=np.uint64, count=n8 * n_final).reshape(n8, n_final)
         flags = np.frombuffer(buf, dtype=np.uint8, count=2 * n_final, offset=n8 * 8 * n_final).reshape(2, n_final)
         return wide, flags
@@ -764,6 +785,20 @@ def prefix_windows(states, k):
     counts = np.zeros((n, 4), np.int64)
     with ctx.lock:
         ctx.check(ctx.lib.same_window_knn_prefix(_handles(states), n, int(k), counts.ctypes.data), "same_window_knn_prefix")
+    return _staged_anew(states, counts)
+
+
+def recost_windows(states, dmoving, dref, layer, dist_ct_coeff):
+    """same_window_recost for a batch of staged windows of one context (one wait): the costs of every window's pair list AS STAGED written
+    again with the moving rows' types read from `layer` (a DeviceTypesLayer of `dmoving`; None: the section's own) -- bit for bit the
+    costs a stage call over a moving section made with that matrix computes (csrc/window_recost.hip).  `dmoving`, `dref`, `dist_ct_coeff`:
+    what the windows were staged with.  Every window is afterwards what `prefix_windows` at the staged knn leaves: the list as staged, no
+    priority prune, a caller's compaction turned back and held for `caller_pairs_windows`.  -> [counts per window]"""
+    ctx, n = states[0].ctx, len(states)
+    counts = np.zeros((n, 4), np.int64)
+    with ctx.lock:
+        ctx.check(ctx.lib.same_window_recost(_handles(states), n, dmoving.handle, dref.handle, None if layer is None else layer.handle,
+                                             float(dist_ct_coeff), counts.ctypes.data), "same_window_recost")
     return _staged_anew(states, counts)
 
 
@@ -930,10 +965,11 @@ class DeviceWindowResult:
     With the priority prune on the device: `priority` = (pairs staged, pairs left, rows that kept one pair, rows that kept all); `counts`
     and everything later describe the filtered pair list.
     With `sets` (a parameter sweep): `set` = the index of the parameter set this result was finished under; `mode`, `counts`, `priority`
-    and everything the finish call leaves are that set's, `rows_m` / `axy` are shared by the window's results."""
+    and everything the finish call leaves are that set's, `rows_m` / `axy` are shared by the window's results; `variant` = the index of
+    the set's type-matrix variant (`variants`; 0 without them)."""
 
     __slots__ = ("window", "error", "rows_m", "axy", "triangles", "n_triangles", "match_row", "point_flag", "flip_flag", "stats",
-                 "counts", "state", "assignment", "refine", "mode", "skipped", "removed", "priority", "set")
+                 "counts", "state", "assignment", "refine", "mode", "skipped", "removed", "priority", "set", "variant")
 
     def __init__(self, window, mode=None):
         self.window = window
@@ -986,7 +1022,7 @@ class TriangulationCache(QhullTriangulator):
 
 def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dist_ct_coeff=1.0, min_angle_deg=15,
                         ignore_same_type_triangles=True, no_match_penalty=100.0, ctx=None, fetch_triangles=False, triangulator=None,
-                        triangulate=True, batch=None, collector=None, mode=None, caller=None, priority=False, sets=None):
+                        triangulate=True, batch=None, collector=None, mode=None, caller=None, priority=False, sets=None, variants=None):
     """The window path of `iter_window_arrays` + the incumbent and the three sweeps, with both sections resident on the device (`dref`,
     `dmoving`: DeviceSections of `ref`, `moving`): per window the host only triangulates (Qhull helpers, windows ahead as before) and
     receives the match; the triangle filter runs on the device too, unless a cosine sits within 8 ulp of the angle threshold (then the
@@ -1032,6 +1068,14 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
     which hands back an unpruned list; both sections need their label codes (DeviceSection.set_label_codes).  `counts[3]`, the pairs and
     costs a state hands out and everything later are the filtered list's; the pair list as staged (or as cut) stays fetchable
     (_W_STAGED_PAIRS) and stays the frame of the reference limits.
+    `variants=[layer or None, ...]` (with `sets`): TYPE-MATRIX VARIANTS of the moving section over the same pass -- each a
+    DeviceTypesLayer of `dmoving`, or None for the section's own types -- and a set is then (knn, WindowMode, no_match_penalty, variant
+    index); a set of three values is of variant 0, and without `variants` there is the one variant None.  Only the pair costs read the type
+    columns, so staging, `tri.submit`, `caller_tris_windows` and the ticket per window happen once per batch whatever the number of
+    variants.  Per batch the variants are the outermost loop, None variants first (the list as staged is already theirs), the others in
+    the order given; before every other variant ONE `recost_windows` call prices the staged lists from its layer and leaves the windows
+    as `prefix_windows` at the staged knn does, and the knn groups of the variant's sets follow as above (prefix where k differs, then
+    the priority prune, then `caller_pairs_windows`).  `result.variant` carries the index (None in the plain form).
     A set's WindowMode (None: the greedy start alone): a window whose optimal start the device does not certify is solved again on
     the host (ops.sparse_assign_host, ops.sparse_transport_host) and finished again under that matching; every later finish of a window
     (that fallback, a re-finish with scipy's simplices) runs the mode's search again: `result.refine` holds the last one's counts."""
@@ -1044,13 +1088,22 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
     ctx = ops._ctx(ctx)
     # per set: (`result.set`, what the collector is told beside the states and the windows)
     tags = [(None, ())] if sets is None else [(q, (q,)) for q in range(len(sets))]
-    sets = [(knn, mode, no_match_penalty)] if sets is None else [(int(k), m, float(p)) for k, m, p in sets]
+    if variants is not None and (sets is None or len(variants) == 0):
+        raise ValueError("variants: at least one, and with sets that name them")
+    variants = [None] if variants is None else list(variants)
+    sets = [(knn, mode, no_match_penalty, 0)] if sets is None else [(int(st[0]), st[1], float(st[2]), int(st[3]) if len(st) > 3 else 0)
+                                                                     for st in sets]
     if not sets or (len(sets) > 1 and ((caller is not None and not isinstance(caller, DeviceCallerTris)) or not triangulate)):
         raise ValueError("sets: at least one; several only with windows triangulated by the route or by a DeviceCallerTris")
-    sets = [(k, WindowMode.default() if m is None else m, p) for k, m, p in sets]
-    knn = max(k for k, _m, _p in sets)
-    # the sets grouped by knn, largest first (the first group is the list as staged)
-    set_groups = [(k, [q for q, st in enumerate(sets) if st[0] == k]) for k in sorted({st[0] for st in sets}, reverse=True)]
+    if any(not 0 <= v < len(variants) for _k, _m, _p, v in sets):
+        raise ValueError("sets: a variant index outside `variants`")
+    sets = [(k, WindowMode.default() if m is None else m, p, v) for k, m, p, v in sets]
+    knn = max(st[0] for st in sets)
+    # the variants that have sets, None variants first (the list as staged is theirs); per variant its sets grouped by knn, largest first
+    # (the first group is the list as staged, or as priced again)
+    variant_order = sorted({st[3] for st in sets}, key=lambda v: (variants[v] is not None, v))
+    set_groups = {v: [(k, [q for q, st in enumerate(sets) if st[0] == k and st[3] == v])
+                      for k in sorted({st[0] for st in sets if st[3] == v}, reverse=True)] for v in variant_order}
     angle_enabled, cos_thr = cos_threshold(min_angle_deg)
     near_tol = float(8 * np.spacing(abs(cos_thr))) if (angle_enabled and np.isfinite(cos_thr)) else 0.0
     tri = QHULL if triangulator is None else triangulator
@@ -1194,11 +1247,12 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
         """-> a DeviceWindowResult per staged window of `group` under set `which`: filter + signs + incumbent + sweeps of the windows
         that have a state, by ONE library call (+ one per window whose filter met a cosine at the threshold); `first`: the batch's
         first finish.  A result is the staged record + the state as the set's knn group left it + what the call leaves."""
-        _k, mode, no_match_penalty = sets[which]
+        _k, mode, no_match_penalty, variant = sets[which]
         outs = []
         for rec in group:
             out = DeviceWindowResult(rec.window, mode)
             out.set, out.error, out.skipped, out.removed = tags[which][0], rec.error, rec.skipped, rec.removed
+            out.variant = None if tags[which][0] is None else variant
             out.rows_m, out.axy, out.triangles, out.state = rec.rows_m, rec.axy, rec.triangles, rec.state
             out.counts, out.priority = (rec.counts, rec.priority) if rec.state is None else (rec.state.counts, rec.state.priority)
             outs.append(out)
@@ -1243,22 +1297,27 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
         """the staged windows of `group` finished once per set, knn group by knn group -> yields every set's results"""
         states = [rec.state for rec in group if rec.state is not None]
         current, pruned, compacted, first = knn, priority, True, True     # (stage_batch pruned and compacted the list as staged)
-        for k, members in set_groups:
-            if states and k != current:
-                with marked("pair lists cut to the set's knn (device)"):
-                    prefix_windows(states, k)
-                current, pruned, compacted = k, False, False
-            if states and priority and not pruned:
-                with marked("cell-type-priority prune of the pair lists (device)"):
-                    priority_windows(states)
-                pruned = True
-            if states and caller is not None and not compacted:
-                with marked("caller's triangles: the cut pair lists through the held node masks (device)"):
-                    caller_pairs_windows(states)
-                compacted = True
-            for which in members:
-                yield from finish_set(group, which, first)
-                first = False
+        for v in variant_order:
+            if states and variants[v] is not None:
+                with marked("pair lists priced from the variant's type matrix (device)"):
+                    recost_windows(states, dmoving, dref, variants[v], dist_ct_coeff)
+                current, pruned, compacted = knn, False, False
+            for k, members in set_groups[v]:
+                if states and k != current:
+                    with marked("pair lists cut to the set's knn (device)"):
+                        prefix_windows(states, k)
+                    current, pruned, compacted = k, False, False
+                if states and priority and not pruned:
+                    with marked("cell-type-priority prune of the pair lists (device)"):
+                        priority_windows(states)
+                    pruned = True
+                if states and caller is not None and not compacted:
+                    with marked("caller's triangles: the cut pair lists through the held node masks (device)"):
+                        caller_pairs_windows(states)
+                    compacted = True
+                for which in members:
+                    yield from finish_set(group, which, first)
+                    first = False
 
     pending, live, nxt = deque(), [], 0
     try:

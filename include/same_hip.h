@@ -788,6 +788,27 @@ int same_merge_acc_columns_layer(same_merge_acc *acc, const same_section *moving
                                  int n_extra_ref, void *out_host, int64_t n_final);
 int same_host_alloc(same_ctx *ctx, size_t bytes, void **out_ptr);
 int same_host_free(same_ctx *ctx, void *ptr);
+/* A merged result reduced to the numbers it is read by (csrc/window_score.hip), without its table: after same_merge_acc_finish, on the
+ * final rows where they are.  `moving`, `ref`: the sections the pass ran over, both with label codes (same_section_set_label_codes: the
+ * joint codes of the frames' cell_type labels; a negative code equals nothing).  `tris`: the triangulation to score against as rows of
+ * `moving` (same_caller_tris_create), or NULL: no triangle counts.  out_counts[8]:
+ *   [0] final rows                      [1] rows whose moving cell's label code equals its matched reference cell's
+ *   [2] triangles resident in `tris`    [3] of them: all three corners matched (src/eval_utils.py:66-223, check_triangle_violations)
+ *   [4] of [3]: skipped, the three corners have one label (only with ignore_same_type)
+ *   [5] of [3]: flipped -- the signs of _signed_area on the moving XY and on the matched reference cells' XY differ, neither is 0
+ *   [6] of [5]: not skipped (the stats' triangles_flipped; percent_flipped is [6] of [3] - [4])
+ *   [7] final rows whose moving cell is a corner of a flipped triangle that is not skipped; with node_local: of at least min_flips
+ *       such triangles that are at least majority_threshold of the triangles not skipped it is a corner of
+ * What the call asks of the runtime for n final rows on the accumulator's context: n == 0 nothing; else one launch, and two more where
+ * `tris` holds a triangle; one copy (64 bytes back); ONE wait; no fill -- but the first call on an accumulator, and the first over a
+ * moving section of more rows than any before, lay the accumulator's work buffer (three words per moving row) and fill it, two fills.
+ * The call leaves that buffer as it found it, so the sets of a sweep follow each other without one.
+ * SAME_EINVAL (out_counts untouched): before same_merge_acc_finish, after same_merge_acc_plain or same_merge_acc_load (their rows may
+ * name a moving row twice), a section without label codes, `tris` made for another section.  SAME_ERANGE: a final row outside the
+ * sections (the pass ran over others). */
+int same_merge_acc_score(same_merge_acc *acc, const same_section *moving, const same_section *ref,
+                         const same_caller_tris *tris /* may be NULL: no triangle counts */, int ignore_same_type, int node_local,
+                         double majority_threshold, int64_t min_flips, int64_t *out_counts /* [8] */);
 
 /* ======================================================================================================================
  * part 4 -- COMM: one communicator per context, RCCL over xGMI

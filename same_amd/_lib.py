@@ -142,6 +142,7 @@ _PROTOTYPES = {
     "same_merge_acc_fetch": [c_vp, c_int, c_vp, c_i64],
     "same_merge_acc_columns": [c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_i64],
     "same_merge_acc_columns_layer": [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_i64],
+    "same_merge_acc_score": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_dbl, c_i64, c_vp],
     "same_host_alloc": [c_vp, c_sz, ctypes.POINTER(c_vp)],
     "same_host_free": [c_vp, c_vp],
     "same_comm_unique_id": [c_vp],

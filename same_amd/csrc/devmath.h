@@ -99,4 +99,17 @@ __device__ __forceinline__ double key_to_double(unsigned long long k) {
     return __longlong_as_double((long long)u);
 }
 
+// src/eval_utils.py:116-121 -- check_triangle_violations' _signed_area (not :73's form: other operations, other roundings)
+__device__ __forceinline__ double eval_area3(double2_t p1, double2_t p2, double2_t p3) {
+    return 0.5 * (p1.x * (p2.y - p3.y) + p2.x * (p3.y - p1.y) + p3.x * (p1.y - p2.y));
+}
+
+// src/eval_utils.py:160-166 -- its flip rule on the area before (the aligned XY) and after (the mapped XY): np.sign semantics incl. NaN
+// (a NaN sign compares unequal to everything, itself included).  One definition for match.hip's tri_flip_stats_kernel and
+// window_score.hip's triangle kernel.
+__device__ __forceinline__ bool eval_flipped(double before, double after) {
+    const int s0 = before != before ? 2 : (before > 0.0) - (before < 0.0), s1 = after != after ? 3 : (after > 0.0) - (after < 0.0);
+    return s0 != s1 && s0 != 0 && s1 != 0;
+}
+
 }  // namespace devmath

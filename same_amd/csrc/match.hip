@@ -11,6 +11,7 @@
 // the pairs with 64-bit atomicMin on a monotone key of the cost, then 32-bit atomicMin on the
 // pair index to break exact cost ties the way the stable sort does.
 #include "common.h"
+#include "devmath.h"
 
 #include <algorithm>
 
@@ -189,11 +190,8 @@ __global__ __launch_bounds__(256) void greedy_batch_kernel(GreedyBatch b, int s,
 }
 
 // ---- node-local flip statistics (src/eval_utils.py:66-223) -------------------------------------
-typedef double double2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ double2_t ld2(const double *xy, int64_t i) { return *reinterpret_cast<const double2_t *>(xy + 2 * i); }
-__device__ __forceinline__ double area3(double2_t p1, double2_t p2, double2_t p3) {  // _signed_area, eval_utils.py:116-121
-    return 0.5 * (p1.x * (p2.y - p3.y) + p2.x * (p3.y - p1.y) + p3.x * (p1.y - p2.y));
-}
+using devmath::double2_t;
+using devmath::ld2;
 
 // tri_flag: bit0 all three matched, bit1 same type (only when type_id given), bit2 flipped
 __global__ __launch_bounds__(256) void tri_flip_stats_kernel(
@@ -208,11 +206,9 @@ __global__ __launch_bounds__(256) void tri_flip_stats_kernel(
         f = 1;
         const bool same = type_id && type_id[a] == type_id[b] && type_id[b] == type_id[c];
         if (same) f |= 2;
-        const double sb = area3(ld2(axy, a), ld2(axy, b), ld2(axy, c));
-        const double sa = area3(ld2(mxy, a), ld2(mxy, b), ld2(mxy, c));
-        // np.sign semantics incl. NaN (a NaN sign compares unequal to everything, itself included): eval_utils.py:160-166
-        const int s0 = sb != sb ? 2 : (sb > 0.0) - (sb < 0.0), s1 = sa != sa ? 3 : (sa > 0.0) - (sa < 0.0);
-        const bool flipped = s0 != s1 && s0 != 0 && s1 != 0;
+        // the areas and the flip rule: devmath.h, shared with window_score.hip
+        const bool flipped = devmath::eval_flipped(devmath::eval_area3(ld2(axy, a), ld2(axy, b), ld2(axy, c)),
+                                                   devmath::eval_area3(ld2(mxy, a), ld2(mxy, b), ld2(mxy, c)));
         if (flipped) f |= 4;
         if (!same) {  // integer counters: order-independent
             atomicAdd(&node_tri[a], 1u); atomicAdd(&node_tri[b], 1u); atomicAdd(&node_tri[c], 1u);

@@ -1,5 +1,5 @@
 // window_internal.h -- what the translation units of the device-resident window path share (section.hip, window_stage.hip,
-// window_finish.hip, window_merge.hip, window_caller.hip, window_priority.hip, window_knn_prefix.hip, window_recost.hip): the resident objects behind the
+// window_finish.hip, window_merge.hip, window_score.hip, window_caller.hip, window_priority.hip, window_knn_prefix.hip, window_recost.hip): the resident objects behind the
 // opaque handles of include/same_hip.h part 4, the per-launch argument blocks, a window's pair list (win::PairList) and the one
 // statement of which list is "the list as staged" (win::as_staged), the small host helpers and the batch driver of the window calls.
 //
@@ -358,6 +358,73 @@ struct same_caller_tris {
     unsigned *starts = nullptr;      // [cells + 1]
     std::vector<unsigned> h_starts;
 };
+
+namespace win {
+
+// The score call's work buffer (window_score.hip), one per accumulator, laid for `rows` rows of the moving section.  BETWEEN calls every
+// word of it is in its idle state -- match_of -1, the node counters 0, the totals 0 -- filled ONCE when the buffer is laid; a call
+// leaves it so again itself (its last kernel resets what its first two wrote, per final row; its first kernel clears the totals' set
+// the NEXT call counts into), so a set costs no fill.
+constexpr int SCORE_TOTALS = 8;          // words of one set of totals; words [1] and [3 .. 7] are what out_counts[1], [3 .. 7] report
+struct ScoreWork {
+    int32_t *match_of = nullptr;                  // [rows] reference section row the moving row is matched to in the final rows, -1 = none
+    unsigned *node_tri = nullptr, *node_flip = nullptr;   // [rows] triangles not skipped the row is a corner of; the flipped ones of them
+    unsigned long long *totals = nullptr;         // [2][SCORE_TOTALS] two sets, used alternately (same_merge_acc::score_set)
+    size_t ones_bytes = 0, bytes = 0;             // match_of's share, from the buffer's start (filled 0xFF; the rest 0); the whole
+};
+inline void lay(ScoreWork &s, Carver &cv, int64_t rows) {
+    s.match_of = cv.take<int32_t>((size_t)rows);
+    s.ones_bytes = cv.off;
+    s.node_tri = cv.take<unsigned>((size_t)rows);
+    s.node_flip = cv.take<unsigned>((size_t)rows);
+    s.totals = cv.take<unsigned long long>(2 * SCORE_TOTALS);
+    s.bytes = cv.off;
+}
+
+}  // namespace win
+
+// The rows of one pass over a window plan on one context (window_merge.hip), and what window_score.hip reads of them.
+struct same_merge_acc {
+    same_ctx *ctx = nullptr;
+    // the rows (struct of arrays, capacity `cap`); `dcount[0]` rows so far (device), then the collect call's scratch words
+    int64_t cap = 0;
+    int32_t *a_row = nullptr, *r_row = nullptr, *wid = nullptr, *pos = nullptr, *cidx = nullptr;
+    uint8_t *flags = nullptr;
+    unsigned long long *dcount = nullptr;     // [0] rows, [1] pad, [2 .. 2 + SAME_LAUNCH_WINDOWS) per-window counts of the group in flight
+    int64_t bound = 0;                        // host: the rows collected since begin cannot exceed this (sum of the windows' kept cells)
+    // the seams of this rank's share of the plan (same_merge_acc_begin)
+    win::DevBuf near_start, near_boxes, scan_words;   // scan_words: the collect call's look-back words, one run per window of a group
+    int n_pos = 0, all_seam = 0;
+    double reach = 0.0;
+    // resolve / finish
+    win::DevBuf work, out;                    // out: the rest list, then (after finish / plain) the FinalRecs, n_final of them
+    int32_t *ac = nullptr, *rc = nullptr, *row_of = nullptr;
+    unsigned long long *counters = nullptr;   // in `work`: [0] survivors of the de-duplication, [1] rest rows, [2] final rows
+    int64_t n_codes_a = 0;
+    int64_t n_rows = 0, n_kept = 0, n_rest = 0, n_final = 0;
+    int resolved = 0;
+    int final_on_host = 0;                    // the final records have been copied to `host` (same_merge_acc_fetch does it on demand)
+    int merged = 0;                           // the final rows are a merge's (same_merge_acc_finish): at most one per moving row
+    int loaded = 0;                           // the rows came from the host (same_merge_acc_load): their "section rows" ARE the codes
+    int64_t loaded_codes_a = 0, loaded_codes_r = 0;
+    std::vector<char> host;                   // what the last resolve / finish brought back (fetched by same_merge_acc_fetch)
+    // same_merge_acc_score (window_score.hip)
+    win::DevBuf score;
+    win::ScoreWork sw;                        // laid over `score` for score_rows rows
+    int64_t score_rows = 0;                   // 0: not laid, or a call failed half way -- the next call lays and fills it again
+    int score_set = 0;                        // the totals' set the next call counts into
+};
+
+// what comes back: one record per row (include/same_hip.h)
+struct RestRec {
+    int32_t row, ac, rc, wid, pos, cidx;
+    uint32_t flags;               // bit 0 XY-order flag, bit 1 area-flip flag, bit 2 the row is at a seam
+};
+struct FinalRec {
+    int32_t a_row, r_row, cidx, wid, pos;
+    uint32_t flags;
+};
+static_assert(sizeof(RestRec) == SAME_MERGE_REST_BYTES && sizeof(FinalRec) == SAME_MERGE_FINAL_BYTES, "record layouts are part of the ABI");
 
 namespace win {
 

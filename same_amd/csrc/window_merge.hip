@@ -20,41 +20,7 @@
 // All integer / comparison work, exact by construction; a pass of 10^6 rows is ~25 MB of traffic: latency-bound, no roofline to speak of.
 #include "window_internal.h"
 
-struct same_merge_acc {
-    same_ctx *ctx = nullptr;
-    // the rows (struct of arrays, capacity `cap`); `dcount[0]` rows so far (device), then the collect call's scratch words
-    int64_t cap = 0;
-    int32_t *a_row = nullptr, *r_row = nullptr, *wid = nullptr, *pos = nullptr, *cidx = nullptr;
-    uint8_t *flags = nullptr;
-    unsigned long long *dcount = nullptr;     // [0] rows, [1] pad, [2 .. 2 + SAME_LAUNCH_WINDOWS) per-window counts of the group in flight
-    int64_t bound = 0;                        // host: the rows collected since begin cannot exceed this (sum of the windows' kept cells)
-    // the seams of this rank's share of the plan (same_merge_acc_begin)
-    win::DevBuf near_start, near_boxes, scan_words;   // scan_words: the collect call's look-back words, one run per window of a group
-    int n_pos = 0, all_seam = 0;
-    double reach = 0.0;
-    // resolve / finish
-    win::DevBuf work, out;
-    int32_t *ac = nullptr, *rc = nullptr, *row_of = nullptr;
-    unsigned long long *counters = nullptr;   // in `work`: [0] survivors of the de-duplication, [1] rest rows, [2] final rows
-    int64_t n_codes_a = 0;
-    int64_t n_rows = 0, n_kept = 0, n_rest = 0, n_final = 0;
-    int resolved = 0;
-    int final_on_host = 0;                    // the final records have been copied to `host` (same_merge_acc_fetch does it on demand)
-    int loaded = 0;                           // the rows came from the host (same_merge_acc_load): their "section rows" ARE the codes
-    int64_t loaded_codes_a = 0, loaded_codes_r = 0;
-    std::vector<char> host;                   // what the last resolve / finish brought back (fetched by same_merge_acc_fetch)
-};
-
-// what comes back: one record per row (include/same_hip.h)
-struct RestRec {
-    int32_t row, ac, rc, wid, pos, cidx;
-    uint32_t flags;               // bit 0 XY-order flag, bit 1 area-flip flag, bit 2 the row is at a seam
-};
-struct FinalRec {
-    int32_t a_row, r_row, cidx, wid, pos;
-    uint32_t flags;
-};
-static_assert(sizeof(RestRec) == SAME_MERGE_REST_BYTES && sizeof(FinalRec) == SAME_MERGE_FINAL_BYTES, "record layouts are part of the ABI");
+// (same_merge_acc and the two records that come back, RestRec and FinalRec: window_internal.h -- window_score.hip reads them too)
 
 namespace {
 
@@ -399,7 +365,7 @@ void same_merge_acc_destroy(same_merge_acc *a) {
     (void)hipStreamSynchronize(a->ctx->stream);
     free_rows(a);
     if (a->dcount) (void)hipFree(a->dcount);
-    for (DevBuf *b : {&a->near_start, &a->near_boxes, &a->scan_words, &a->work, &a->out}) release(*b);
+    for (DevBuf *b : {&a->near_start, &a->near_boxes, &a->scan_words, &a->work, &a->out, &a->score}) release(*b);
     delete a;
 }
 
@@ -604,6 +570,7 @@ int same_merge_acc_plain(same_merge_acc *const *accs, int n_accs, int64_t *out_n
     a->n_rows = a->n_kept = a->n_final = n;
     a->n_rest = 0;
     a->final_on_host = 0;
+    a->merged = 0;
     SAME_TRY(ensure(ctx, a->out, (size_t)std::max<int64_t>(n, 1) * sizeof(FinalRec)));
     if (n) SAME_LAUNCH(ctx, plain_kernel, dim3(grid_for(n)), dim3(256), 0, rows_of(a), n, static_cast<FinalRec *>(a->out.p));
     HIP_TRY(ctx, hipGetLastError());
@@ -638,6 +605,7 @@ int same_merge_acc_finish(same_merge_acc *a, const int32_t *winner_rows, int64_t
     REQUIRE(ctx, (int64_t)total <= a->n_kept);
     a->n_final = (int64_t)total;          // the records stay on the device until somebody asks for them (same_merge_acc_fetch, ..._columns)
     a->final_on_host = 0;
+    a->merged = 1;
     a->resolved = 2;
     *out_n_final = a->n_final;
     return SAME_OK;

@@ -526,7 +526,7 @@ def _merged_rows(job, frames, rows, channel):
 
 
 def _device_pass(jobs, frames, workers, with_ref_idx, triangulator, merge=False, channel=None, batch=None, caller=None, priority=False,
-                 variants=None):
+                 variants=None, score=None):
     """The device route: ONE walk of the windows for `jobs` -- _WindowJobs over the same frames, plan and share of the plan that differ
     in sweep.SWEEP_KEYS only (`sliding_window_incumbent`: its one job; `sliding_window_sweep`: a job per parameter set) and in the
     type-matrix variant of the moving frame they are priced from (`sliding_window_variants`: a job per (variant, set); `variants` the
@@ -534,9 +534,13 @@ def _device_pass(jobs, frames, workers, with_ref_idx, triangulator, merge=False,
     and carries the matrix and the layer as `job.variant_types` / `job.variant_layer`).  Every job has
     its own builders, accumulators and stats.  -> [(table, {plan position: stats record}) per job].  `caller`: the jobs' (one)
     triangulation as a windows.DeviceCallerTris -- selected once per batch, whatever the number of jobs.  A merge channel goes with a
-    single job."""
+    single job.  `score` (scores.DeviceScores; merge=True, no window-local indices, no channel): every job's merged rows are scored
+    where the merge left them and the record kept as `job.score_record`; with `score.tables` False the job's table is None -- never
+    made."""
     if len(jobs) > 1 and channel is not None:
         raise ValueError("several jobs over one pass: not with a merge channel")
+    if score is not None and (not merge or with_ref_idx or channel is not None):
+        raise ValueError("scores are read off the merged rows of one process: merge=True, no window-local indices, no merge channel")
     job = jobs[0]                 # what the jobs share is read from the first
     n_workers = max(1, int(workers if workers is not None else _default_workers()))
     n_workers = min(n_workers, max(1, len(job.todo)))
@@ -563,7 +567,7 @@ def _device_pass(jobs, frames, workers, with_ref_idx, triangulator, merge=False,
                 for q, acc in enumerate(mine):
                     acc.begin(sum(w["n_mov"] for _pos, w in job.todo[cut[q]:cut[q + 1]]))
                 accs.append(mine)
-        if priority:                      # once, here: before a worker thread stages its first window (as the id codes above)
+        if priority or score is not None:  # once, here: before a worker thread stages its first window (as the id codes above)
             frames.label_codes_on_device()
         pos_of = {id(w): pos for pos, w in job.todo}
         sets = [(j.optim_params["knn"], j.mode, j.optim_params["no_match_penalty"], getattr(j, "variant", 0)) for j in jobs]
@@ -604,16 +608,16 @@ def _device_pass(jobs, frames, workers, with_ref_idx, triangulator, merge=False,
             [t.join() for t in threads]
             if errors:
                 raise errors[0]
-        return [(_route_table(j, frames, builders[s], None if accs is None else accs[s], merge, channel, device_table), stats[s])
+        return [(_route_table(j, frames, builders[s], None if accs is None else accs[s], merge, channel, device_table, score), stats[s])
                 for s, j in enumerate(jobs)]
     finally:
         for acc in extra:
             acc.close()
 
 
-def _route_table(job, frames, builders, accs, merge, channel, device_table):
+def _route_table(job, frames, builders, accs, merge, channel, device_table, score=None):
     """The device route's table once its windows are walked: from the builders' rows or from the accumulators' (None: the builders hold
-    them), merged or laid end to end."""
+    them), merged or laid end to end.  `score`: see `_device_pass`."""
     # the rows that stay, as FINAL_RECORDs: the builders' (the merge chooses among them on the host) or the accumulator's (the merge chose
     # on the device; its columns may come from there too) -- then one way from records to the table
     me, with_pos = builders[0], job.mine is not None and not merge
@@ -631,6 +635,14 @@ def _route_table(job, frames, builders, accs, merge, channel, device_table):
 
             with stage("table rows (accumulated on the device, in plan order)"):
                 done = plain_accumulators(accs)
+        if score is not None:
+            # the merged rows are final in the accumulator: scored there; without tables that is all -- no columns, no frame
+            with stage("scores (counted on the device from the merged rows)"):
+                calls1 = accs[0].ctx.stats()
+                job.score_record = score.record(frames, done)
+                _count_merge_calls(frames, accs[0].ctx, calls1, passes=0)
+            if not score.tables:
+                return None
         if not done.n_final:
             return pd.DataFrame()
         if device_table:

@@ -1,0 +1,233 @@
+"""What a finished window run is read by, without its table: `sliding_window_scores`.
+
+The reference's figure notebooks (examples/heart/reproduce_figures.ipynb: Fig 3c, S4-S7) reduce every run to a few numbers:
+
+* the share of matched cells whose `cell_type` is that of the reference cell they were put on -- `check_alignment` at kNN=1 with the
+  matched cells placed ON their reference cells (SAME_X = ref_X), which asks of every row whether its own reference cell has its label;
+* `check_triangle_violations`' stats over the moving frame's whole triangulation under the merged matching, and the notebooks'
+  `violations` = 100 * triangles_flipped / total_triangles.
+
+A study -- a sweep of parameter sets, type-matrix variants of the moving frame, both -- is one pass of the windows (sweep.py,
+variants.py), and when a set's merge ends everything these numbers read is on the device: the merged rows as (moving section row,
+reference section row), both sections' XY, the triangulation as section rows, the joint `cell_type` codes.  `sliding_window_scores` counts
+there (csrc/window_score.hip, three short kernels per result) and with tables=False no table is ever made.
+
+`score_table` is the same record from a result TABLE with the functions the package already has: what the device record must equal,
+what inputs the device cannot score go through, and the tests' yardstick.  Both end in `record_from_counts`, the one place where counts
+become percentages."""
+import numbers
+import types
+
+import numpy as np
+import pandas as pd
+
+from .eval_utils import _label_codes, check_triangle_violations
+from .triangles import _as_triangle_array
+from .variants import _frames_of, sliding_window_variants
+
+# check_triangle_violations' own arguments and defaults (src/eval_utils.py:66-78)
+SCORE_PARAMS = {"ignore_same_type_triangles": True, "node_local": False, "majority_threshold": 0.5, "min_flips": 1}
+TRIANGLE_KEYS = ("total_triangles", "triangles_with_all_matched", "triangles_same_type_skipped", "triangles_flipped", "percent_flipped",
+                 "nodes_in_violating_triangles", "percent_nodes_violating", "violations")
+RECORD_KEYS = ("matched", "type_matches", "accuracy") + TRIANGLE_KEYS
+
+
+def checked_score_params(score_params):
+    """-> SCORE_PARAMS overridden by `score_params`; ValueError for a key that is none of them or a value of the wrong type"""
+    if score_params is not None and not isinstance(score_params, dict):
+        raise ValueError(f"score_params must be a dict over {tuple(SCORE_PARAMS)}, not {type(score_params).__name__}")
+    other = [k for k in (score_params or {}) if k not in SCORE_PARAMS]
+    if other:
+        raise ValueError(f"score_params has {other}: its keys are {tuple(SCORE_PARAMS)}")
+    p = {**SCORE_PARAMS, **(score_params or {})}
+    for k in ("ignore_same_type_triangles", "node_local"):
+        if not isinstance(p[k], (bool, np.bool_)):
+            raise ValueError(f"score_params[{k!r}] must be a bool, not {p[k]!r}")
+        p[k] = bool(p[k])
+    t = p["majority_threshold"]
+    if isinstance(t, (bool, np.bool_)) or not isinstance(t, numbers.Real) or t != t:
+        raise ValueError(f"score_params['majority_threshold'] must be a number, not {t!r}")
+    m = p["min_flips"]
+    if isinstance(m, (bool, np.bool_)) or not isinstance(m, numbers.Integral) or abs(int(m)) >= 2**62:
+        raise ValueError(f"score_params['min_flips'] must be an int, not {m!r}")
+    p["majority_threshold"], p["min_flips"] = float(t), int(m)
+    return p
+
+
+def record_from_counts(counts, score_params=None):
+    """The score record of the integer `counts` -- a dict: `matched` (rows of the merged table), `type_matches`, and where a triangulation
+    was scored against `total_triangles` (not None), `triangles_with_all_matched`, `triangles_same_type_skipped`, `triangles_flipped`
+    (among the triangles that are not skipped) and `nodes_in_violating_triangles` -- or in its place `node_triangles` / `node_flips`, per
+    row of the table the triangles not skipped its cell is a corner of and the flipped ones among them, which are then counted under
+    `score_params` by check_triangle_violations' rule (src/eval_utils.py:199-211): any flip, or with node_local at least min_flips flips
+    that are at least majority_threshold of the cell's triangles.
+    The percentages are eval_utils.check_triangle_violations' own expressions: percent_flipped = 100.0 * flipped / considered (0.0 with
+    none considered), percent_nodes_violating = 100.0 * (nodes / matched); accuracy = 100 * (type_matches / matched), the mean of
+    check_alignment's match column times 100; violations = 100 * flipped / total_triangles, the notebooks' column.  No rows, no
+    triangles: the quotient is NaN."""
+    p = checked_score_params(score_params)
+    over = lambda a, b: float(a) / float(b) if b else float("nan")
+    matched, type_matches = int(counts["matched"]), int(counts["type_matches"])
+    rec = {"matched": matched, "type_matches": type_matches, "accuracy": 100 * over(type_matches, matched)}
+    if counts.get("total_triangles") is None:
+        return rec
+    if "nodes_in_violating_triangles" in counts:
+        nodes = int(counts["nodes_in_violating_triangles"])
+    else:
+        n_tri, n_flip = np.asarray(counts["node_triangles"], np.int64), np.asarray(counts["node_flips"], np.int64)
+        if p["node_local"]:
+            with np.errstate(divide="ignore", invalid="ignore"):
+                nodes = int(np.count_nonzero((n_tri > 0) & (n_flip >= p["min_flips"]) & (n_flip / n_tri >= p["majority_threshold"])))
+        else:
+            nodes = int(np.count_nonzero(n_flip > 0))
+    total, all_matched = int(counts["total_triangles"]), int(counts["triangles_with_all_matched"])
+    same, flipped = int(counts["triangles_same_type_skipped"]), int(counts["triangles_flipped"])
+    considered = all_matched - same
+    rec.update(total_triangles=total, triangles_with_all_matched=all_matched, triangles_same_type_skipped=same, triangles_flipped=flipped,
+               percent_flipped=100.0 * flipped / considered if considered else 0.0, nodes_in_violating_triangles=nodes,
+               percent_nodes_violating=100.0 * over(nodes, matched), violations=over(100 * flipped, total))
+    return rec
+
+
+def _frame_rows(frame_ids, ids, what):
+    """rows of a frame named by `ids` through its id column `frame_ids` (an id that names several rows: the last, as the reference's
+    dicts keep it)"""
+    index = pd.Index(frame_ids)
+    rows = np.arange(len(index))
+    if not index.is_unique:
+        keep = ~index.duplicated(keep="last")
+        index, rows = index[keep], rows[keep]
+    at = index.get_indexer(np.asarray(ids))
+    if len(at) and at.min() < 0:
+        raise ValueError(f"the table names {what} ids the frame does not have")
+    return rows[at]
+
+
+def score_table(table, ref, moving, *, cell_id_col, score_delaunay=None, score_delaunay_vertex_col=None, score_params=None, ctx=None):
+    """The score record (`record_from_counts`) of a result table of `sliding_window_incumbent` / `_sweep` / `_variants` over the frames
+    `ref` and `moving` (MetaCell objects: their `.metacell_df`), with the functions the package already has.
+    The table's rows are mapped to frame rows through Aligned_<cell_id_col> / Ref_<cell_id_col>; `type_matches` compares the two frames'
+    `cell_type` at those rows (labels that compare equal; a missing label equals nothing).  With `score_delaunay` -- anything
+    `moving_delaunay` accepts, its vertex ids the moving frame's index labels or `score_delaunay_vertex_col`'s values -- the triangle keys
+    are `check_triangle_violations`' stats, called as the reference's notebook calls it: mapped_x_col="ref_X", mapped_y_col="ref_Y", the
+    table's `cell_type` assigned from the moving frame, and an object carrying the moving frame indexed by vertex id and the triangulation.
+    `score_params`: `checked_score_params`.  A frame without `cell_type` raises ValueError."""
+    p = checked_score_params(score_params)
+    ref, moving = getattr(ref, "metacell_df", ref), getattr(moving, "metacell_df", moving)
+    for df, name in ((ref, "ref"), (moving, "moving")):
+        if "cell_type" not in df.columns:
+            raise ValueError(f"scores compare cell types: the {name} frame has no 'cell_type' column")
+    n = len(table)
+    rows_m = _frame_rows(moving[cell_id_col].to_numpy(), table[f"Aligned_{cell_id_col}"].to_numpy(), "moving") if n else np.zeros(0, np.int64)
+    rows_r = _frame_rows(ref[cell_id_col].to_numpy(), table[f"Ref_{cell_id_col}"].to_numpy(), "reference") if n else np.zeros(0, np.int64)
+    mov_type = moving["cell_type"].to_numpy()[rows_m]
+    code_m, code_r = _label_codes(mov_type, ref["cell_type"].to_numpy()[rows_r])
+    counts = {"matched": n, "type_matches": int(np.count_nonzero((code_m >= 0) & (code_m == code_r)))}
+    if score_delaunay is not None:
+        tri = _as_triangle_array(score_delaunay)
+        if score_delaunay_vertex_col is not None and score_delaunay_vertex_col not in moving.columns:
+            raise ValueError(f"score_delaunay_vertex_col='{score_delaunay_vertex_col}' not in the moving frame")
+        vertex_ids = moving.index.to_numpy() if score_delaunay_vertex_col is None else moving[score_delaunay_vertex_col].to_numpy()
+        if not pd.Index(vertex_ids).is_unique:
+            raise ValueError("the moving frame's vertex ids are not unique: its triangulation names no definite cells")
+        counts.update(total_triangles=len(tri), triangles_with_all_matched=0, triangles_same_type_skipped=0, triangles_flipped=0,
+                      nodes_in_violating_triangles=0)
+        if n:
+            out = pd.DataFrame({"__vertex_id": vertex_ids[rows_m], f"Ref_{cell_id_col}": table[f"Ref_{cell_id_col}"].to_numpy(),
+                                "ref_X": table["ref_X"].to_numpy(), "ref_Y": table["ref_Y"].to_numpy(), "cell_type": mov_type})
+            frame = pd.DataFrame({"X": moving["X"].to_numpy(), "Y": moving["Y"].to_numpy()}, index=vertex_ids)
+            carrier = types.SimpleNamespace(metacell_df=frame, metacell_delaunay=tri)
+            _out, stats = check_triangle_violations(out, carrier, aligned_id_col="__vertex_id", ref_id_col=f"Ref_{cell_id_col}",
+                                                    mapped_x_col="ref_X", mapped_y_col="ref_Y", cell_type_col="cell_type", ctx=ctx, **p)
+            counts.update({k: int(stats[k]) for k in ("triangles_with_all_matched", "triangles_same_type_skipped", "triangles_flipped",
+                                                      "nodes_in_violating_triangles")})
+    return record_from_counts(counts, p)
+
+
+class DeviceScores:
+    """The score hook of `incumbent._device_pass`: what to score every job's merged rows against, and the call that does it."""
+
+    def __init__(self, score_delaunay, vertex_col, params, tables):
+        self.score_delaunay, self.vertex_col, self.params, self.tables = score_delaunay, vertex_col, params, bool(tables)
+        self.job = None          # the first job of the pass (sliding_window_variants tells): MetaCell unwrapping, cell_id_col, its triangulation
+        self.records = None      # [record per job, variants outermost] once the device scored them
+        self.tris, self.total = None, None
+
+    def triangulation(self, job):
+        """(the triangulation to score against, its vertex id column): `score_delaunay`, else the job's own caller triangulation"""
+        if self.score_delaunay is not None:
+            return self.score_delaunay, self.vertex_col
+        return (job.moving_delaunay, job.vertex_col) if job.caller_triangulation else (None, None)
+
+    def prepare(self, frames, job):
+        """Before the pass: the scoring triangulation resident beside the moving section (`frames.caller_tris`: the job's own object is the
+        copy its windows select from).  -> whether the device can score these inputs: not with cell ids that name several rows of a frame
+        (a merged row then names no definite cell), a `cell_type` with missing labels (the reference's same-type rule factorizes them
+        into one label, the joint codes make each equal nothing) or a triangulation `caller_triangulation_rows` refuses."""
+        if not frames.id_codes(job.optim_params["cell_id_col"])[1]:
+            return False
+        known = frames.__dict__                              # (asked once per frames: a resident_frames object serves many calls)
+        if "_labels_complete" not in known:
+            known["_labels_complete"] = not any(bool(pd.isna(df["cell_type"].to_numpy()).any()) for df in (job.ref, job.moving))
+        if not known["_labels_complete"]:
+            return False
+        tri, vertex_col = self.triangulation(job)
+        if tri is not None:
+            self.tris = frames.caller_tris(tri, vertex_col)
+            if self.tris is None:
+                return False
+            self.total = len(_as_triangle_array(tri))
+        return True
+
+    def record(self, frames, acc):
+        """the record of the merged rows `acc` holds after its finish (windows.MergeAccumulator.score)"""
+        p = self.params
+        c = acc.score(frames.dmov, frames.dref, self.tris, p["ignore_same_type_triangles"], p["node_local"], p["majority_threshold"],
+                      p["min_flips"]).tolist()
+        # (c[2], the triangles resident, leaves out those that name an id the frame lacks; total_triangles is the caller's own count)
+        return record_from_counts({"matched": c[0], "type_matches": c[1], "total_triangles": self.total, "triangles_with_all_matched": c[3],
+                                   "triangles_same_type_skipped": c[4], "triangles_flipped": c[6], "nodes_in_violating_triangles": c[7]}, p)
+
+
+def sliding_window_scores(ref, moving, commonCT=None, *, type_variants=None, param_sets=None, optim_params=None, gurobi_params=None,
+                          score_delaunay=None, score_delaunay_vertex_col=None, score_params=None, tables=False, workers=None,
+                          triangulator=None, ctx=None, batch=None, moving_delaunay=None, moving_delaunay_vertex_col=None):
+    """The score records of `sliding_window_variants(ref, moving, type_variants, commonCT, param_sets=param_sets, merge=True, ...)` over one
+    pass of the windows, counted on the device from every result's merged rows: -> a DataFrame with one row per (variant, set), variants
+    outermost, in the callers' order; with tables=True (scores, tables), `tables[v][s]` that call's tables.  `type_variants=None`: the
+    frame's own types alone; `param_sets=None`: one set, {}.  Without tables no table is made: no columns gathered, no frame built.
+    Columns: `variant`, `set` (indices into the callers' lists), then RECORD_KEYS -- `matched` (rows of the merged table), `type_matches`
+    (rows whose moving cell's `cell_type` compares equal to its matched reference cell's), `accuracy`, and `check_triangle_violations`'
+    stats with `violations` = 100 * triangles_flipped / total_triangles (`record_from_counts`).  The triangle columns are left out when
+    there is no triangulation to score against.
+    `score_delaunay`: the triangulation of the moving frame to score against -- anything `moving_delaunay` accepts, ids read through
+    `score_delaunay_vertex_col` --, used for scoring only; None: the job's own caller triangulation (a MetaCell object's, or
+    `moving_delaunay=`).  On plain frames: scipy.spatial.Delaunay(moving[["X", "Y"]]).simplices.  `score_params`: a dict over SCORE_PARAMS,
+    check_triangle_violations' arguments.  The other arguments are `sliding_window_variants`' and are checked by its checks; an unknown
+    `score_params` key, a value of the wrong type or a frame without `cell_type` raise ValueError before a job or a device is touched.
+    Every record equals `score_table` of its table.  Inputs the device cannot score -- whatever keeps the job off the shared device pass
+    (`sliding_window_sweep` lists it), and what `DeviceScores.prepare` names -- go through `score_table` on the tables: the same records,
+    nothing saved."""
+    params = checked_score_params(score_params)
+    _ref_arg, _moving_arg, ref_df, mov_df = _frames_of(ref, moving)
+    for df, name in ((ref_df, "ref"), (mov_df, "moving")):
+        if "cell_type" not in getattr(df, "columns", ()):
+            raise ValueError(f"scores compare cell types: the {name} frame has no 'cell_type' column")
+    if score_delaunay is not None:
+        _as_triangle_array(score_delaunay)                  # (its shape: the reference's ValueError)
+    hook = DeviceScores(score_delaunay, score_delaunay_vertex_col, params, tables)
+    results = sliding_window_variants(ref, moving, [None] if type_variants is None else type_variants, commonCT, param_sets=param_sets,
+                                      optim_params=optim_params, gurobi_params=gurobi_params, workers=workers, triangulator=triangulator,
+                                      ctx=ctx, merge=True, batch=batch, moving_delaunay=moving_delaunay,
+                                      moving_delaunay_vertex_col=moving_delaunay_vertex_col, _score=hook)
+    nested = [[r] if param_sets is None else list(r) for r in results]
+    records = hook.records
+    if records is None:                                     # not scored on the device: the host statement on every table
+        job = hook.job
+        tri, vertex_col = hook.triangulation(job)
+        records = [score_table(t, job.ref, job.moving, cell_id_col=job.optim_params["cell_id_col"], score_delaunay=tri,
+                               score_delaunay_vertex_col=vertex_col, score_params=params, ctx=ctx) for per_set in nested for t in per_set]
+    n_sets = len(nested[0])
+    rows = [{"variant": q // n_sets, "set": q % n_sets, **rec} for q, rec in enumerate(records)]
+    scores = pd.DataFrame(rows, columns=["variant", "set"] + [k for k in RECORD_KEYS if k in rows[0]])
+    return (scores, nested) if tables else scores

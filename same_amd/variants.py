@@ -88,7 +88,7 @@ def moving_variant(moving, commonCT, types):
 
 def sliding_window_variants(ref, moving, type_variants, commonCT=None, *, param_sets=None, optim_params=None, gurobi_params=None,
                             workers=None, window_local_indices=False, return_stats=False, triangulator=None, ctx=None, merge=False,
-                            batch=None, moving_delaunay=None, moving_delaunay_vertex_col=None):
+                            batch=None, moving_delaunay=None, moving_delaunay_vertex_col=None, _score=None):
     """`sliding_window_incumbent` -- with `param_sets`: `sliding_window_sweep` -- for every type-matrix variant of the moving frame over one
     pass of the windows.  -> [result per variant, in the order given]: a table (with return_stats: (table, [per-window stats dict in plan
     order])), or with `param_sets` the sweep's list of those per set.
@@ -105,7 +105,10 @@ def sliding_window_variants(ref, moving, type_variants, commonCT=None, *, param_
     Every window is staged once (at the sets' largest knn) and triangulated once; per batch and variant that is not None one call prices
     the staged pair lists again (windows.recost_windows).  Inputs that do not take the device route -- the ones `sliding_window_sweep`
     lists -- run variant by variant through `sliding_window_incumbent` / `sliding_window_sweep` on `moving_v`: the same results, nothing
-    shared.  (An `outprefix` and ranks are not offered here.)"""
+    shared.  (An `outprefix` and ranks are not offered here.)
+    `_score` (scores.sliding_window_scores' scores.DeviceScores): it is told the job (`_score.job`), and where the pass is shared and
+    `_score.prepare(frames, job)` agrees every result is scored on the device (`incumbent._device_pass`); a result is then None unless
+    `_score.tables`."""
     _checked_list(type_variants)
     ref_arg, moving_arg, ref_df, mov_df = _frames_of(ref, moving)
     cts = _common_types(ref_arg, moving_arg, ref_df, mov_df, commonCT)
@@ -117,6 +120,8 @@ def sliding_window_variants(ref, moving, type_variants, commonCT=None, *, param_
     new_job = lambda op, mode, **kw: _WindowJob(ref, moving, commonCT, None, moving_delaunay, moving_delaunay_vertex_col, op, gurobi_params,
                                                 False, None, mode=mode, **kw)
     job = new_job(*checked[0])
+    if _score is not None:
+        _score.job = job
     kw = {}
     if not isinstance(ref, ResidentFrames) and not isinstance(moving, ResidentFrames):
         # the jobs share window_size, overlap and min_cells: the first job's plan serves the others (this object holds nothing else)
@@ -138,6 +143,7 @@ def sliding_window_variants(ref, moving, type_variants, commonCT=None, *, param_
 
                 triangulator = delaunay.triangulator_for(op0)
             layers = [None if m is None else frames.types_layer(v, m) for v, m in zip(type_variants, mats)]
+            score = _score if _score is not None and _score.prepare(frames, job) else None
             jobs = []
             for v, m in enumerate(mats):            # a job per (variant, set), variants outermost
                 for s, (op, mode) in enumerate(checked):
@@ -145,7 +151,9 @@ def sliding_window_variants(ref, moving, type_variants, commonCT=None, *, param_
                     j.variant, j.variant_types, j.variant_layer = v, m, layers[v]
                     jobs.append(j)
             done = _device_pass(jobs, frames, workers, window_local_indices, triangulator, merge, None, batch, caller, priority,
-                                variants=layers)
+                                variants=layers, score=score)
+            if score is not None:
+                score.records = [j.score_record for j in jobs]
             res = [(table, [stats[pos] for pos in sorted(stats)]) if return_stats else table for table, stats in done]
             n_sets = len(checked)
             return [res[v * n_sets] if param_sets is None else res[v * n_sets:(v + 1) * n_sets] for v in range(len(mats))]

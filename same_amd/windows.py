@@ -665,6 +665,18 @@ class MergeAccumulator(_DeviceHandle):
             self.ctx.check(self.ctx.lib.same_merge_acc_fetch(self.handle, 1, out.ctypes.data, out.nbytes), "same_merge_acc_fetch")
         return out
 
+    def score(self, dmoving, dref, tris=None, ignore_same_type=True, node_local=False, majority_threshold=0.5, min_flips=1):
+        """After finish(): the merged rows reduced to same_merge_acc_score's eight counts (csrc/window_score.hip) -- final rows, rows whose
+        two label codes agree, triangles resident in `tris` (a DeviceCallerTris of `dmoving`; None: no triangle counts), all matched, same
+        type skipped, flipped, flipped among those not skipped, rows in a violating triangle -- as an int64 array.  Both sections carry
+        label codes (DeviceSection.set_label_codes).  One wait; no table is made."""
+        ctx, counts = self.ctx, np.zeros(8, np.int64)
+        with ctx.lock:
+            ctx.check(ctx.lib.same_merge_acc_score(self.handle, dmoving.handle, dref.handle, None if tris is None else tris.handle,
+                                                   int(bool(ignore_same_type)), int(bool(node_local)), float(majority_threshold),
+                                                   int(min_flips), counts.ctypes.data), "same_merge_acc_score")
+        return counts
+
     def columns(self, dmoving, dref, n_final, n_types, extra_moving=(), extra_ref=(), layer=None):
         """After finish(): the merged table's columns written by the device straight into page-locked host memory (enqueue only:
         `ctx.sync()` before reading): the moving section's type columns (`layer`: a DeviceTypesLayer of `dmoving` to read them from), X, Y, the reference's X, Y, the caller's extra 8-byte device

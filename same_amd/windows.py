@@ -7,10 +7,12 @@ batched device pass (csrc/sweep.hip window_count_kernel) instead of one pandas b
 per window; the sequential walk that decides merges is then pure host lookups."""
 import ctypes
 import os
+from collections import deque, namedtuple
 
 import numpy as np
 
 from . import _lib, ops
+from ._trace import stage as marked
 from .delaunay import QHULL, QhullTriangulator, Ticket
 from .window_mode import WindowMode
 
@@ -1032,6 +1034,188 @@ class TriangulationCache(QhullTriangulator):
         return simplices, False
 
 
+def batch_schedule(sets, layered, priority, caller):
+    """THE ORDER OF A BATCH'S CALLS in `iter_device_windows`, as data: the steps a batch makes after its front calls (the stage call,
+    [the priority prune], [`caller_tris_windows`], the tickets), a flat list of
+        ("recost", v)  ("prefix", k)  ("priority",)  ("caller_pairs",)  ("finish", set index)
+    -- `recost_windows` from variant v's layer, `prefix_windows` at k, `priority_windows`, `caller_pairs_windows`, and the filter +
+    finish call of one set.  `sets`: the sets, of which only the first entry (knn) and the last (variant index) are read; `layered[v]`:
+    variant v is a DeviceTypesLayer, not None (the section's own types); `priority`, `caller`: the prune is on, there is a caller's
+    triangulation.  Needs no device and no library.
+    The rule.  The front calls leave every window's pair list AT the staged knn (the largest of the sets), priced with the section's own
+    types, pruned and pushed through the caller's node masks.  The variants that have sets are the outermost loop, None variants first
+    -- that list is already theirs -- then by index.  A layered variant begins with ONE `recost`, which leaves the list at the staged
+    knn, unpruned and uncompacted.  Within a variant the distinct knn come largest first, and ONE `prefix` stands where a group's knn
+    is not the one the list is at (a batch sees at most one per variant and distinct value); it too hands back an unpruned,
+    uncompacted list.  After a `recost` or a `prefix` -- once for the two together -- comes `priority` where the prune is on, then
+    `caller_pairs` where there is a caller.  Then the group's finishes, in the order the sets were given.  So the first group of a
+    None variant at the staged knn has nothing before its finishes, and a list of one set is its finish alone."""
+    staged = max(st[0] for st in sets)
+    steps, at, anew = [], staged, False
+    for v in sorted({st[-1] for st in sets}, key=lambda v: (bool(layered[v]), v)):
+        if layered[v]:
+            steps.append(("recost", v))
+            at, anew = staged, True
+        for k in sorted({st[0] for st in sets if st[-1] == v}, reverse=True):
+            if k != at:
+                steps.append(("prefix", k))
+                at, anew = k, True
+            if anew:
+                steps += [("priority",)] * bool(priority) + [("caller_pairs",)] * bool(caller)
+                anew = False
+            steps += [("finish", q) for q, st in enumerate(sets) if st[0] == k and st[-1] == v]
+    return steps
+
+
+def _checked_walk_sets(sets, variants, knn, mode, no_match_penalty, caller, triangulate):
+    """`iter_device_windows`' sets and variants, checked and in one form -> ([(knn, WindowMode, no_match_penalty, variant index) per
+    set], [DeviceTypesLayer or None per variant], [(`result.set`, what the collector is told beside the states and the windows) per
+    set]).  The plain form (`sets` None) is the one set (`knn`, `mode`, `no_match_penalty`) of the one variant None; a set of three
+    values is of variant 0."""
+    tags = [(None, ())] if sets is None else [(q, (q,)) for q in range(len(sets))]
+    if variants is not None and (sets is None or len(variants) == 0):
+        raise ValueError("variants: at least one, and with sets that name them")
+    variants = [None] if variants is None else list(variants)
+    sets = [(knn, mode, no_match_penalty, 0)] if sets is None else [(int(st[0]), st[1], float(st[2]), int(st[3]) if len(st) > 3 else 0)
+                                                                     for st in sets]
+    if not sets or (len(sets) > 1 and ((caller is not None and not isinstance(caller, DeviceCallerTris)) or not triangulate)):
+        raise ValueError("sets: at least one; several only with windows triangulated by the route or by a DeviceCallerTris")
+    if any(not 0 <= v < len(variants) for _k, _m, _p, v in sets):
+        raise ValueError("sets: a variant index outside `variants`")
+    return [(k, WindowMode.default() if m is None else m, p, v) for k, m, p, v in sets], variants, tags
+
+
+class _WindowStates:
+    """The DeviceWindows of one pass of `iter_device_windows`, and how many windows go together.  Windows go to the library in batches
+    of `batch` (`size`; default $SAME_WINDOW_BATCH, else 8), at most `ahead_max` are staged and not yet finished ($SAME_WINDOW_AHEAD
+    beyond the route's `depth`).  `take(n)` hands out states -- the context's from earlier passes (`ctx._device_windows`) first, new
+    ones after --, `give(states)` takes them back for the next batch.  `all` holds every state of the pass once, handed out or not,
+    and `close()` leaves those with the context: whatever ended the pass -- a refused library call, a triangulator that raised, a
+    consumer that walked away -- a state is in the context's cache once or closed, and no call site has a failure path of its own."""
+
+    def __init__(self, ctx, n_windows, batch, depth):
+        B = max(1, min(int(batch if batch is not None else os.environ.get("SAME_WINDOW_BATCH", "8")), WINDOW_BATCH_MAX, max(n_windows, 1)))
+        if batch is None and depth > 0:
+            # a rank with three helpers (eight ranks on a 16-CPU host) gains nothing from collecting eight tickets at once
+            B = min(B, max(2, depth))
+        # windows staged and not yet finished: one per helper BEYOND the batch being finished (a batch's tickets are collected together,
+        # and nothing is handed over meanwhile: with only `depth` in flight, 12 helpers and batches of 8 ran 8 of 12 helpers -- 264
+        # against 431 windows/s for one thread of a rank that shares its host with another)
+        self.size, self.ahead_max = B, max(B, depth + int(os.environ.get("SAME_WINDOW_AHEAD", str(B))))
+        # window states (their device buffers, grown once) are kept with the context from one call to the next: a pass over a plan
+        # then makes no device allocation at all.  In use at once: the windows ahead + the batch being staged + the batch last yielded
+        self.ctx, self.cache = ctx, ctx.__dict__.setdefault("_device_windows", [])
+        self.want = min(self.ahead_max + 2 * B, max(n_windows, 1) + B)
+        self.all = [self.cache.pop() for _ in range(min(self.want, len(self.cache)))]       # every state of the pass, each once
+        self.free = list(self.all)
+
+    def take(self, n):
+        new = [DeviceWindow(self.ctx) for _ in range(n - len(self.free))]
+        self.all += new
+        self.free += new
+        at = len(self.free) - n
+        states, self.free[at:] = self.free[at:], []
+        return states
+
+    def give(self, states):
+        self.free.extend(states)
+
+    def close(self):
+        self.cache.extend(self.all)
+        for extra in self.cache[self.want:]:          # a context keeps what one pass needs, not every state it ever had
+            extra.close()
+        del self.cache[self.want:]
+
+
+# what the calls of one pass of `iter_device_windows` read beside their windows; `filt`: the triangle filter's arguments (radius,
+# angle_enabled, cos_thr, near_tol, ignore_same_type_triangles)
+_WalkPass = namedtuple("_WalkPass", "ctx moving tri caller filt min_angle_deg")
+
+
+def _host_filter(c, axy, rows, tris, **how):
+    """the triangle filter of a window with a cosine at the threshold, re-decided on the host with the reference's literal expression
+    (triangles.filter_triangles_by_radius over the aligned cells `axy`, section rows `rows`)"""
+    from .triangles import filter_triangles_by_radius
+
+    radius, _angle_enabled, _cos_thr, _near_tol, same_type = c.filt
+    tid = c.moving.type_id[rows] if (same_type and c.moving.type_id is not None) else None
+    return filter_triangles_by_radius(axy, tris, radius, ignore_same_type_triangles=same_type, min_angle_deg=c.min_angle_deg,
+                                      verbose=False, ctx=c.ctx, _rows_as_array=True, _type_id=tid, **how)
+
+
+def _caller_front(c, pairs_of):
+    """the staged windows [(record, state)] that have pairs: their triangles from `c.caller`, their unconstrained nodes gone"""
+    if not pairs_of:
+        return
+    got = caller_tris_windows([st for _o, st in pairs_of], c.caller, *c.filt)
+    for q, (out, state) in enumerate(pairs_of):
+        if got[q][2]:
+            with marked("triangle filter (host: a cosine at the threshold)"):
+                rows0 = state.fetch(_W_ALIGNED_ROWS)
+                kept, gone = _host_filter(c, state.fetch(_W_ALIGNED_XY), rows0, state.fetch(_W_CALLER_TRIANGLES),
+                                          remove_unconstrained_nodes=True)
+                mask = np.zeros(len(rows0), np.uint8)
+                mask[sorted(gone)] = 1
+                got[q] = caller_tris_windows([state], c.caller, *c.filt, removed=[mask])[0]
+                kept = np.asarray(kept).reshape(-1, 3)
+                kept = kept[(mask[kept] == 0).all(axis=1)] if len(kept) else kept        # src/same.py:1076-1078
+                out.triangles = (np.cumsum(mask == 0) - 1)[kept].astype(np.int32).reshape(-1, 3)
+        out.removed = got[q][1]
+        out.skipped = got[q][4] == 0          # every node unconstrained, or the removed ones held every pair
+
+
+def _finish_callers(c, todo, states, no_match_penalty, mode):
+    """the finish call over the caller's triangles, which are on the device (SAME_TRIS_CALLER); a window the host filtered
+    (_caller_front) brings its kept list.  -> (result per window, no simplices)"""
+    with marked("filter + signs + incumbent + sweeps (device)"):
+        mine = [q for q, (o, _s, _t) in enumerate(todo) if o.triangles is None]
+        res = dict(zip(mine, filter_finish_windows([states[q] for q in mine], None, *c.filt, no_match_penalty, mode=mode,
+                                                   from_caller=True) if mine else []))
+        for q, (o, st, _t) in enumerate(todo):
+            if o.triangles is not None:
+                res[q] = (len(o.triangles), 0, 0) + tuple(st.finish(o.triangles, no_match_penalty, mode))
+    if any(r[2] for r in res.values()):        # (the node mask's kernel classifies the same corners with the same expressions)
+        raise RuntimeError("a cosine at the angle threshold that same_window_caller_tris did not report")
+    return res, [None] * len(todo)
+
+
+def _finish_triangulated(c, states, tickets, no_match_penalty, mode, first):
+    """the finish call over the triangulator's answers -> (result per window, simplices per window); `first`: the batch's first
+    finish (the route's per-batch hook runs once; a ticket keeps its answer)"""
+    args = c.filt + (no_match_penalty,)
+    if first:
+        c.tri.before_finish(states, tickets, *c.filt[:3])
+    with marked("triangulate (wait for helper)"):
+        tris = [ticket.result() for ticket in tickets]
+    with marked("filter + signs + incumbent + sweeps (device)"):
+        # candidates the device made stay there (simplices None); every other window brings its simplices
+        mine = [q for q, t in enumerate(tris) if t is None]
+        theirs = [q for q, t in enumerate(tris) if t is not None]
+        res = dict(zip(mine, filter_finish_windows([states[q] for q in mine], None, *args, mode=mode) if mine else []))
+        res.update(zip(theirs, filter_finish_windows([states[q] for q in theirs], [tris[q] for q in theirs], *args, mode=mode)
+                       if theirs else []))
+    # simplices that are not Qhull's own (delaunay.py: the same triangles in another order): where the window's numbers hang on that
+    # order -- the device counted such places, or a cosine sits at the threshold and the host is about to re-decide the filter --
+    # the window is finished again with scipy's
+    for q, (state, ticket) in enumerate(zip(states, tickets)):
+        if ticket.native and (state.order_ties or res[q][2]):
+            with marked("order ties: the window again with Qhull's simplices"):
+                tris[q] = ticket.qhull()
+                res[q] = filter_finish_windows([state], [tris[q]], *args, mode=mode)[0]
+    return res, tris
+
+
+def _set_result(rec, mode, tag, variant):
+    """-> the DeviceWindowResult of the staged window `rec` under one set, before that set's finish call: the staged record + the state
+    as the set's knn group left it"""
+    out = DeviceWindowResult(rec.window, mode)
+    out.set, out.variant, out.error, out.skipped, out.removed = tag, variant, rec.error, rec.skipped, rec.removed
+    out.rows_m, out.axy, out.triangles, out.state = rec.rows_m, rec.axy, rec.triangles, rec.state
+    out.counts, out.priority = (rec.counts, rec.priority) if rec.state is None else (rec.state.counts, rec.state.priority)
+    out.n_triangles = None if rec.state is None else 0
+    return out
+
+
 def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dist_ct_coeff=1.0, min_angle_deg=15,
                         ignore_same_type_triangles=True, no_match_penalty=100.0, ctx=None, fetch_triangles=False, triangulator=None,
                         triangulate=True, batch=None, collector=None, mode=None, caller=None, priority=False, sets=None, variants=None):
@@ -1039,24 +1223,18 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
     `dmoving`: DeviceSections of `ref`, `moving`): per window the host only triangulates (Qhull helpers, windows ahead as before) and
     receives the match; the triangle filter runs on the device too, unless a cosine sits within 8 ulp of the angle threshold (then the
     host re-decides it with the reference's literal expression, as triangles.classify_triangles does).  The numbers are those of the
-    column pipeline (tests/test_gpu_run_same.py::test_device_windows_equal_the_column_pipeline).  A window without pairs yields `.error`.
-    What a window is finished under is a SET, a (knn, WindowMode, no_match_penalty) triple.  The plain form has one, (`knn`, `mode`,
-    `no_match_penalty`), and yields one DeviceWindowResult per window in plan order, `result.set` None.  `sets=[...]` is a parameter sweep
-    over ONE pass (then `knn`, `mode` and `no_match_penalty` are not read): every window is staged once, at the largest knn, and
-    triangulated once, and finished once per set; per batch the results come set by set in the order the sets are taken (below), one
-    per window each, `result.set` the set's index; `mode`, `counts`, `priority` and everything the finish call leaves are that set's,
-    `rows_m` / `axy` are shared by the window's results, and a result's `state` is live only until the next set's finish.  A list of one
-    set makes the calls of the plain form; more than one does not go with `triangulate=False`, and with `caller` only when that is a
-    DeviceCallerTris: the caller's selection -- which triangles are the window's, the node mask, the window without its unconstrained
-    nodes -- does not depend on knn, so it is made ONCE per batch, at the largest knn, `removed`, `skipped` and a host-filtered window's
-    `triangles` serve every set, and after every prefix call (and the prune that follows it) ONE `caller_pairs_windows` call pushes the cut
-    pair lists through the node masks the windows hold.
-    Windows go to the library in BATCHES of `batch` (default $SAME_WINDOW_BATCH, else 8): one stage call, and later per set one filter +
-    finish call, for up to that many windows -- one wait per call instead of one per window, and the device works on one window while
-    the host enqueues the next.  The states of a batch stay live (`result.state`) until the generator is asked for the first window of
-    the next.  The sets of a batch are taken grouped by knn, largest first -- the first group's list is the list as staged; before
-    every other group ONE `prefix_windows` call cuts the pair lists to its knn (a batch sees at most one per distinct value), then the
-    priority prune where it is on, then `caller_pairs_windows` where there is a `caller` -- and within a group in the order given.
+    column pipeline (tests/test_gpu_run_same.py::test_device_windows_equal_the_column_pipeline).
+    YIELDS DeviceWindowResults.  What a window is finished under is a SET, a (knn, WindowMode, no_match_penalty) triple.  The plain form
+    has one, (`knn`, `mode`, `no_match_penalty`), and yields one result per window in plan order, `result.set` and `result.variant` None;
+    a window without pairs yields `.error`.  `sets=[...]` is a parameter sweep over ONE pass (then `knn`, `mode` and `no_match_penalty`
+    are not read): every window is staged once, at the largest knn, triangulated once, and finished once per set.  Windows go to the
+    library in BATCHES (`batch`; _WindowStates); per batch the results come set by set in the order of `batch_schedule`'s finishes --
+    THE statement of which calls a batch makes and in which order -- one per window each, `result.set` the set's index; `mode`,
+    `counts`, `priority` and everything the finish call leaves are that set's, `rows_m` / `axy` are shared by the window's results.  A list
+    of one set makes the calls of the plain form; more than one does not go with `triangulate=False`, and with `caller` only when that
+    is a DeviceCallerTris (its selection does not depend on knn: it is made once per batch and serves every set).
+    `result.state` is the live DeviceWindow until the generator is asked for the first window of the next batch, and with several sets
+    only until the next set's finish.
     `triangulator`: the route, a delaunay.Triangulator (default: delaunay.QHULL, the Qhull helper pool).  It says how many windows to
     stage ahead and whether to start the helpers first; each window is submitted when it is staged, and the route's per-batch hook runs
     right before the batch's first filter + finish call.  A ticket's `.result()` is the simplices, or None for candidates the device
@@ -1068,224 +1246,99 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
     `collector(states, windows)` -- with `sets`: `collector(states, windows, set index)` -- is called once per finished batch and set
     with its windows' live states (the window merge's accumulator: MergeAccumulator.collect).
     `caller`: a DeviceCallerTris of `dmoving` -- the triangulation source that needs no triangulator (`triangulator`, and with it
-    optim_params["hip_delaunay"], is irrelevant then: nothing is triangulated).  Right after a batch's stage call ONE more call selects
-    and remaps every window's triangles, works out the filter's node mask and leaves the window without its unconstrained nodes
-    (caller_tris_windows; src/same.py:1016-1085); rows_m, axy, counts and everything later describe that smaller window, and the finish
-    call filters the caller's triangles where they are.  A window left without pairs is yielded with `.skipped` (src/same.py's loop gets
-    an empty table from it); one with a cosine at the threshold has triangles AND mask re-decided on the host and goes on through the
-    prefiltered forms of both calls.
+    optim_params["hip_delaunay"], is irrelevant then).  Right after a batch's stage call ONE more call selects and remaps every window's
+    triangles, works out the filter's node mask and leaves the window without its unconstrained nodes (caller_tris_windows;
+    src/same.py:1016-1085); rows_m, axy, counts and everything later describe that smaller window.  A window left without pairs is
+    yielded with `.skipped`; one with a cosine at the threshold has triangles AND mask re-decided on the host.
     `priority`: the cell-type-priority prune (optim_params["ignore_knn_if_matched"], src/knn_utils.py:28-78) on the device: right after a
-    batch's stage call -- before anything is triangulated, before the caller's triangles are selected, as the reference filters its pairs
-    before it triangulates -- ONE more call filters every window's pair list (priority_windows), and one more after every prefix call,
-    which hands back an unpruned list; both sections need their label codes (DeviceSection.set_label_codes).  `counts[3]`, the pairs and
-    costs a state hands out and everything later are the filtered list's; the pair list as staged (or as cut) stays fetchable
-    (_W_STAGED_PAIRS) and stays the frame of the reference limits.
+    batch's stage call -- before anything is triangulated or selected, as the reference filters its pairs before it triangulates --
+    ONE more call filters every window's pair list (priority_windows); both sections need their label codes
+    (DeviceSection.set_label_codes).  `counts[3]`, the pairs and costs a state hands out and everything later are the filtered list's;
+    the pair list as staged (or as cut) stays fetchable (_W_STAGED_PAIRS) and stays the frame of the reference limits.
     `variants=[layer or None, ...]` (with `sets`): TYPE-MATRIX VARIANTS of the moving section over the same pass -- each a
     DeviceTypesLayer of `dmoving`, or None for the section's own types -- and a set is then (knn, WindowMode, no_match_penalty, variant
-    index); a set of three values is of variant 0, and without `variants` there is the one variant None.  Only the pair costs read the type
-    columns, so staging, `tri.submit`, `caller_tris_windows` and the ticket per window happen once per batch whatever the number of
-    variants.  Per batch the variants are the outermost loop, None variants first (the list as staged is already theirs), the others in
-    the order given; before every other variant ONE `recost_windows` call prices the staged lists from its layer and leaves the windows
-    as `prefix_windows` at the staged knn does, and the knn groups of the variant's sets follow as above (prefix where k differs, then
-    the priority prune, then `caller_pairs_windows`).  `result.variant` carries the index (None in the plain form).
+    index); a set of three values is of variant 0.  Only the pair costs read the type columns, so staging, the tickets and the
+    caller's selection happen once per batch whatever the number of variants.  `result.variant` carries the index.
     A set's WindowMode (None: the greedy start alone): a window whose optimal start the device does not certify is solved again on
     the host (ops.sparse_assign_host, ops.sparse_transport_host) and finished again under that matching; every later finish of a window
     (that fallback, a re-finish with scipy's simplices) runs the mode's search again: `result.refine` holds the last one's counts."""
-    from collections import deque
-
     from . import qhull_pool
-    from ._trace import stage as marked
-    from .triangles import cos_threshold, filter_triangles_by_radius
+    from .triangles import cos_threshold
 
     ctx = ops._ctx(ctx)
-    # per set: (`result.set`, what the collector is told beside the states and the windows)
-    tags = [(None, ())] if sets is None else [(q, (q,)) for q in range(len(sets))]
-    if variants is not None and (sets is None or len(variants) == 0):
-        raise ValueError("variants: at least one, and with sets that name them")
-    variants = [None] if variants is None else list(variants)
-    sets = [(knn, mode, no_match_penalty, 0)] if sets is None else [(int(st[0]), st[1], float(st[2]), int(st[3]) if len(st) > 3 else 0)
-                                                                     for st in sets]
-    if not sets or (len(sets) > 1 and ((caller is not None and not isinstance(caller, DeviceCallerTris)) or not triangulate)):
-        raise ValueError("sets: at least one; several only with windows triangulated by the route or by a DeviceCallerTris")
-    if any(not 0 <= v < len(variants) for _k, _m, _p, v in sets):
-        raise ValueError("sets: a variant index outside `variants`")
-    sets = [(k, WindowMode.default() if m is None else m, p, v) for k, m, p, v in sets]
+    sets, variants, tags = _checked_walk_sets(sets, variants, knn, mode, no_match_penalty, caller, triangulate)
     knn = max(st[0] for st in sets)
-    # the variants that have sets, None variants first (the list as staged is theirs); per variant its sets grouped by knn, largest first
-    # (the first group is the list as staged, or as priced again)
-    variant_order = sorted({st[3] for st in sets}, key=lambda v: (variants[v] is not None, v))
-    set_groups = {v: [(k, [q for q, st in enumerate(sets) if st[0] == k and st[3] == v])
-                      for k in sorted({st[0] for st in sets if st[3] == v}, reverse=True)] for v in variant_order}
+    schedule = batch_schedule(sets, [layer is not None for layer in variants], priority, caller is not None)
     angle_enabled, cos_thr = cos_threshold(min_angle_deg)
     near_tol = float(8 * np.spacing(abs(cos_thr))) if (angle_enabled and np.isfinite(cos_thr)) else 0.0
     tri = QHULL if triangulator is None else triangulator
+    c = _WalkPass(ctx, moving, tri, caller, (radius, angle_enabled, cos_thr, near_tol, ignore_same_type_triangles), min_angle_deg)
     depth = 0 if caller is not None else int(tri.lookahead())
     if tri.warm and caller is None:
         qhull_pool.warm(min(depth, len(plan)))
-    B = max(1, min(int(batch if batch is not None else os.environ.get("SAME_WINDOW_BATCH", "8")), WINDOW_BATCH_MAX, max(len(plan), 1)))
-    if batch is None and depth > 0:
-        # a rank with three helpers (eight ranks on a 16-CPU host) gains nothing from collecting eight tickets at once
-        B = min(B, max(2, depth))
-    # windows staged and not yet finished: one per helper BEYOND the batch being finished (a batch's tickets are collected together, and
-    # nothing is handed over meanwhile: with only `depth` in flight, 12 helpers and batches of 8 ran 8 of 12 helpers -- 264 against 431
-    # windows/s for one thread of a rank that shares its host with another)
-    ahead_max = max(B, depth + int(os.environ.get("SAME_WINDOW_AHEAD", str(B))))
-    # window states (their device buffers, grown once) are kept with the context from one call to the next: a pass over a plan
-    # then makes no device allocation at all.  In use at once: the windows ahead + the batch being staged + the batch last yielded
-    cache = ctx.__dict__.setdefault("_device_windows", [])
-    want = min(ahead_max + 2 * B, max(len(plan), 1) + B)
-    free = [cache.pop() for _ in range(min(want, len(cache)))]
-    r = float(radius)
+    pool = _WindowStates(ctx, len(plan), batch, depth)
+    B, r = pool.size, float(radius)
     prune_possible = r == r and int(knn) > 0
-
-    def take_state():
-        return free.pop() if free else DeviceWindow(ctx)
+    # a schedule step that is no finish: its stage label and its call over the batch's live states
+    between = {"recost": ("pair lists priced from the variant's type matrix (device)",
+                          lambda states, v: recost_windows(states, dmoving, dref, variants[v], dist_ct_coeff)),
+               "prefix": ("pair lists cut to the set's knn (device)", lambda states, k: prefix_windows(states, k)),
+               "priority": ("cell-type-priority prune of the pair lists (device)", lambda states: priority_windows(states)),
+               "caller_pairs": ("caller's triangles: the cut pair lists through the held node masks (device)",
+                                lambda states: caller_pairs_windows(states))}
 
     def stage_batch(windows):
-        """-> a _StagedWindow per window of `windows`, staged by ONE library call"""
+        """-> a _StagedWindow per window of `windows`, staged by ONE library call.  No failure path of its own: a call that raises
+        ends the walk, whose `pool.close()` takes back the states handed out here"""
         staged = [_StagedWindow(w) for w in windows]
         if not prune_possible:
             for rec in staged:
                 rec.error = ValueError("No valid_pairs after KNN filtering. Increase radius and/or knn.")
             return staged
-        states = [take_state() for _ in windows]
-        try:
-            with marked("subset + prune + costs + compaction (device)"):
-                counts = stage_windows(states, dmoving, dref, [w["box"] for w in windows], abs(r), knn, dist_ct_coeff)
-        except BaseException:
-            free.extend(states)                       # a refused batch (SAME_EINVAL ...) must not take its states out of the pool
-            raise
-        if priority:                                  # the list as staged is pruned here; a list cut later by its knn group (finish_sets)
-            try:
-                with marked("cell-type-priority prune of the pair lists (device)"):
-                    priority_windows(states)
-                counts = [st.counts for st in states]
-                for rec, st in zip(staged, states):
-                    rec.priority = st.priority
-            except BaseException:
-                free.extend(states)
-                raise
+        states = pool.take(len(windows))
+        with marked("subset + prune + costs + compaction (device)"):
+            counts = stage_windows(states, dmoving, dref, [w["box"] for w in windows], abs(r), knn, dist_ct_coeff)
+        if priority:                                  # the list as staged is pruned here; a list cut or priced later, by `schedule`
+            with marked("cell-type-priority prune of the pair lists (device)"):
+                priority_windows(states)
+            counts = [st.counts for st in states]
         if caller is not None:
-            try:
-                with marked("caller's triangles: select + remap + node mask + second compaction (device)"):
-                    caller_front([(rec, st) for rec, st, c in zip(staged, states, counts) if c[3] != 0])
-                counts = [st.counts for st in states]
-            except BaseException:
-                free.extend(states)
-                raise
-        for q, (rec, state) in enumerate(zip(staged, states)):
-            rec.counts = counts[q]
+            with marked("caller's triangles: select + remap + node mask + second compaction (device)"):
+                _caller_front(c, [(rec, st) for rec, st, n in zip(staged, states, counts) if n[3] != 0])
+            counts = [st.counts for st in states]
+        for rec, state, n in zip(staged, states, counts):
+            rec.counts, rec.priority = n, state.priority          # (the prune's counts, or the None the stage call leaves)
             if rec.skipped:
-                free.append(state)
                 continue
             if rec.counts[3] == 0:
-                free.append(state)
                 rec.error = ValueError("No valid_pairs after KNN filtering. Increase radius and/or knn.")
                 continue
-            try:
-                rec.rows_m, rec.axy = state.fetch(_W_ALIGNED_ROWS), state.fetch(_W_ALIGNED_XY)
-                if triangulate and caller is None:
-                    with marked("triangulate (hand-over; waits for a free helper)"):
-                        rec.ticket = tri.submit(rec.axy, key=rec.window.get("window_id"))
-            except BaseException:
-                free.extend(st for st in states[q:])
-                free.extend(done.state for done in staged[:q] if done.state is not None)
-                raise
+            rec.rows_m, rec.axy = state.fetch(_W_ALIGNED_ROWS), state.fetch(_W_ALIGNED_XY)
+            if triangulate and caller is None:
+                with marked("triangulate (hand-over; waits for a free helper)"):
+                    rec.ticket = tri.submit(rec.axy, key=rec.window.get("window_id"))
             rec.state = state
+        pool.give(st for rec, st in zip(staged, states) if rec.state is None)      # skipped, or without pairs
         return staged
-
-    def caller_front(pairs_of):
-        """the staged windows [(record, state)] that have pairs: their triangles from `caller`, their unconstrained nodes gone"""
-        if not pairs_of:
-            return
-        states = [st for _o, st in pairs_of]
-        filt = (radius, angle_enabled, cos_thr, near_tol, ignore_same_type_triangles)
-        got = caller_tris_windows(states, caller, *filt)
-        for q, (out, state) in enumerate(pairs_of):
-            if got[q][2]:
-                with marked("triangle filter (host: a cosine at the threshold)"):
-                    axy0, rows0, tris0 = state.fetch(_W_ALIGNED_XY), state.fetch(_W_ALIGNED_ROWS), state.fetch(_W_CALLER_TRIANGLES)
-                    tid = moving.type_id[rows0] if (ignore_same_type_triangles and moving.type_id is not None) else None
-                    kept, gone = filter_triangles_by_radius(axy0, tris0, radius, ignore_same_type_triangles=ignore_same_type_triangles,
-                                                            remove_unconstrained_nodes=True, min_angle_deg=min_angle_deg, verbose=False,
-                                                            ctx=ctx, _rows_as_array=True, _type_id=tid)
-                    mask = np.zeros(len(rows0), np.uint8)
-                    mask[sorted(gone)] = 1
-                    got[q] = caller_tris_windows([state], caller, *filt, removed=[mask])[0]
-                    kept = np.asarray(kept).reshape(-1, 3)
-                    kept = kept[(mask[kept] == 0).all(axis=1)] if len(kept) else kept        # src/same.py:1076-1078
-                    out.triangles = (np.cumsum(mask == 0) - 1)[kept].astype(np.int32).reshape(-1, 3)
-            out.removed = got[q][1]
-            out.skipped = got[q][4] == 0          # every node unconstrained, or the removed ones held every pair
-
-    def finish_callers(todo, states, args, no_match_penalty, mode):
-        """the finish call over the caller's triangles, which are on the device (SAME_TRIS_CALLER); a window the host filtered
-        (caller_front) brings its kept list.  -> (result per window, no simplices)"""
-        with marked("filter + signs + incumbent + sweeps (device)"):
-            mine = [q for q, (o, _s, _t) in enumerate(todo) if o.triangles is None]
-            res = dict(zip(mine, filter_finish_windows([states[q] for q in mine], None, *args, mode=mode, from_caller=True) if mine else []))
-            for q, (o, st, _t) in enumerate(todo):
-                if o.triangles is not None:
-                    res[q] = (len(o.triangles), 0, 0) + tuple(st.finish(o.triangles, no_match_penalty, mode))
-        if any(r[2] for r in res.values()):        # (the node mask's kernel classifies the same corners with the same expressions)
-            raise RuntimeError("a cosine at the angle threshold that same_window_caller_tris did not report")
-        return res, [None] * len(todo)
-
-    def finish_triangulated(states, tickets, args, mode, first):
-        """the finish call over the triangulator's answers -> (result per window, simplices per window); `first`: the batch's first
-        finish (the route's per-batch hook runs once; a ticket keeps its answer)"""
-        if first:
-            tri.before_finish(states, tickets, radius, angle_enabled, cos_thr)
-        with marked("triangulate (wait for helper)"):
-            tris = [ticket.result() for ticket in tickets]
-        with marked("filter + signs + incumbent + sweeps (device)"):
-            # candidates the device made stay there (simplices None); every other window brings its simplices
-            mine = [q for q, t in enumerate(tris) if t is None]
-            theirs = [q for q, t in enumerate(tris) if t is not None]
-            res = dict(zip(mine, filter_finish_windows([states[q] for q in mine], None, *args, mode=mode) if mine else []))
-            res.update(zip(theirs, filter_finish_windows([states[q] for q in theirs], [tris[q] for q in theirs], *args, mode=mode)
-                           if theirs else []))
-        # simplices that are not Qhull's own (delaunay.py: the same triangles in another order): where the window's numbers hang on that
-        # order -- the device counted such places, or a cosine sits at the threshold and the host is about to re-decide the filter --
-        # the window is finished again with scipy's
-        for q, (state, ticket) in enumerate(zip(states, tickets)):
-            if ticket.native and (state.order_ties or res[q][2]):
-                with marked("order ties: the window again with Qhull's simplices"):
-                    tris[q] = ticket.qhull()
-                    res[q] = filter_finish_windows([state], [tris[q]], *args, mode=mode)[0]
-        return res, tris
 
     def finish_set(group, which, first):
         """-> a DeviceWindowResult per staged window of `group` under set `which`: filter + signs + incumbent + sweeps of the windows
         that have a state, by ONE library call (+ one per window whose filter met a cosine at the threshold); `first`: the batch's
-        first finish.  A result is the staged record + the state as the set's knn group left it + what the call leaves."""
+        first finish.  A result is _set_result's + what the call leaves."""
         _k, mode, no_match_penalty, variant = sets[which]
-        outs = []
-        for rec in group:
-            out = DeviceWindowResult(rec.window, mode)
-            out.set, out.error, out.skipped, out.removed = tags[which][0], rec.error, rec.skipped, rec.removed
-            out.variant = None if tags[which][0] is None else variant
-            out.rows_m, out.axy, out.triangles, out.state = rec.rows_m, rec.axy, rec.triangles, rec.state
-            out.counts, out.priority = (rec.counts, rec.priority) if rec.state is None else (rec.state.counts, rec.state.priority)
-            outs.append(out)
+        tag, told = tags[which]
+        outs = [_set_result(rec, mode, tag, None if tag is None else variant) for rec in group]
         todo = [(out, rec.state, rec.ticket) for out, rec in zip(outs, group) if rec.state is not None]
-        for out, _s, _t in todo:
-            out.n_triangles = 0
         if not triangulate or not todo:
             return outs
         states, tickets = [st for _o, st, _t in todo], [t for _o, _s, t in todo]
-        args = (radius, angle_enabled, cos_thr, near_tol, ignore_same_type_triangles, no_match_penalty)
-        res, tris = (finish_callers(todo, states, args, no_match_penalty, mode) if caller is not None
-                     else finish_triangulated(states, tickets, args, mode, first))
+        res, tris = (_finish_callers(c, todo, states, no_match_penalty, mode) if caller is not None
+                     else _finish_triangulated(c, states, tickets, no_match_penalty, mode, first))
         for q, (out, state, _t) in enumerate(todo):
             _kept, _added, near, match_row, cell_flags, stats = res[q]
             if near:
                 with marked("triangle filter (host: a cosine at the threshold)"):
-                    tid = moving.type_id[out.rows_m] if (ignore_same_type_triangles and moving.type_id is not None) else None
-                    out.triangles = filter_triangles_by_radius(out.axy, tris[q], radius,
-                                                               ignore_same_type_triangles=ignore_same_type_triangles,
-                                                               min_angle_deg=min_angle_deg, verbose=False, ctx=ctx, _rows_as_array=True,
-                                                               _type_id=tid)
+                    out.triangles = _host_filter(c, out.axy, out.rows_m, tris[q])
                 with marked("signs + incumbent + sweeps (device)"):
                     match_row, cell_flags, stats = state.finish(out.triangles, no_match_penalty, mode)
             if mode.incumbent != "greedy":
@@ -1302,51 +1355,33 @@ def iter_device_windows(ref, moving, dref, dmoving, plan, radius=250, knn=8, dis
                 out.triangles = state.fetch(_W_TRIANGLES)
         if collector is not None:
             with marked("central rows to the merge accumulator (device, enqueue only)"):
-                collector(states, [o.window for o, _s, _t in todo], *tags[which][1])
+                collector(states, [o.window for o, _s, _t in todo], *told)
         return outs
 
     def finish_sets(group):
-        """the staged windows of `group` finished once per set, knn group by knn group -> yields every set's results"""
+        """the staged windows of `group` taken through `schedule` -> yields every set's results; a batch without a live state makes
+        none of the calls between the finishes"""
         states = [rec.state for rec in group if rec.state is not None]
-        current, pruned, compacted, first = knn, priority, True, True     # (stage_batch pruned and compacted the list as staged)
-        for v in variant_order:
-            if states and variants[v] is not None:
-                with marked("pair lists priced from the variant's type matrix (device)"):
-                    recost_windows(states, dmoving, dref, variants[v], dist_ct_coeff)
-                current, pruned, compacted = knn, False, False
-            for k, members in set_groups[v]:
-                if states and k != current:
-                    with marked("pair lists cut to the set's knn (device)"):
-                        prefix_windows(states, k)
-                    current, pruned, compacted = k, False, False
-                if states and priority and not pruned:
-                    with marked("cell-type-priority prune of the pair lists (device)"):
-                        priority_windows(states)
-                    pruned = True
-                if states and caller is not None and not compacted:
-                    with marked("caller's triangles: the cut pair lists through the held node masks (device)"):
-                        caller_pairs_windows(states)
-                    compacted = True
-                for which in members:
-                    yield from finish_set(group, which, first)
-                    first = False
+        first = True
+        for kind, *arg in schedule:
+            if kind == "finish":
+                yield from finish_set(group, arg[0], first)
+                first = False
+            elif states:
+                label, call = between[kind]
+                with marked(label):
+                    call(states, *arg)
 
     pending, live, nxt = deque(), [], 0
     try:
         while nxt < len(plan) or pending:
-            while nxt < len(plan) and (not pending or len(pending) + min(B, len(plan) - nxt) <= ahead_max):
+            while nxt < len(plan) and (not pending or len(pending) + min(B, len(plan) - nxt) <= pool.ahead_max):
                 windows = plan[nxt:nxt + B]
                 nxt += len(windows)
                 pending.extend(stage_batch(windows))
-            free.extend(live)                     # the caller has moved on: the previous batch's states go back to the pool
-            live = []
+            pool.give(live)                       # the caller has moved on: the previous batch's states go back to the pool
             group = [pending.popleft() for _ in range(min(B, len(pending)))]
             live = [rec.state for rec in group if rec.state is not None]
             yield from finish_sets(group)
     finally:
-        free.extend(rec.state for rec in pending if rec.state is not None)
-        free.extend(live)
-        cache.extend(free)
-        for extra in cache[want:]:            # a context keeps what one pass needs, not every state it ever had
-            extra.close()
-        del cache[want:]
+        pool.close()

@@ -6,7 +6,9 @@ errored window, one batch is short.
 
 Pinned: the plain form's sequence (with and without the priority prune), the `sets` form's, and that a list of one set makes the plain
 form's calls.  With the priority prune a batch is pruned once right after its stage call -- over every staged window, the one without
-pairs included -- and once after every prefix call: two prunes per batch for two knn groups."""
+pairs included -- and once after every prefix call: two prunes per batch for two knn groups.  The `variants` form (a `recost_windows`
+stand-in beside the five) makes the steps of windows.batch_schedule batch by batch, and a batch without a live window makes its stage
+call alone."""
 import types
 
 import numpy as np
@@ -48,11 +50,18 @@ def walk(monkeypatch):
         for s, box in zip(states, boxes):
             kept = KEPT[int(box[0])]
             s.kept, s.counts, s.n_triangles = kept, (kept + 3, kept + 2, kept, kept * knn), 0
-            s.n_staged_pairs, s.priority = kept * knn, None
+            s.n_staged_pairs, s.priority, s.knn = kept * knn, None, knn
         return [s.counts for s in states]
+
+    def recost_windows(states, dmoving, dref, layer, dist_ct_coeff):
+        log.append(("recost", len(states), layer, None, None))
+        return cut(states, states[0].knn)             # the window as a prefix call at the staged knn leaves it
 
     def prefix_windows(states, k):
         log.append(("prefix", len(states), k, None, None))
+        return cut(states, k)
+
+    def cut(states, k):
         for s in states:
             s.counts, s.n_triangles = s.counts[:3] + (s.kept * k,), 0
             s.n_staged_pairs, s.priority = s.kept * k, None
@@ -83,15 +92,16 @@ def walk(monkeypatch):
             return delaunay.Ticket(self, points, simplices=np.array([[0, 1, 2]], np.int32), native=False)
 
     monkeypatch.setattr(W, "DeviceWindow", _State)
-    for stand_in in (stage_windows, prefix_windows, priority_windows, filter_finish_windows):
+    for stand_in in (stage_windows, recost_windows, prefix_windows, priority_windows, filter_finish_windows):
         monkeypatch.setattr(W, stand_in.__name__, stand_in)
 
-    def run(**kw):
+    def run(plan=PLAN, ctx=None, triangulator=None, take=list, **kw):
+        """`take`: what consumes the generator (tests/test_window_schedule_cpu.py abandons it)"""
         del log[:]
         collected = []
         kw.setdefault("collector", lambda *a: collected.append(a))
-        results = list(W.iter_device_windows(None, None, None, None, PLAN, ctx=types.SimpleNamespace(), batch=2, triangulator=Logging(),
-                                             **kw))
+        results = take(W.iter_device_windows(None, None, None, None, plan, ctx=types.SimpleNamespace() if ctx is None else ctx, batch=2,
+                                             triangulator=Logging() if triangulator is None else triangulator, **kw))
         return list(log), results, collected
 
     return run
@@ -190,3 +200,51 @@ def test_several_sets_go_with_the_routes_own_triangulation_only(walk):
         walk(sets=SETS, caller=object())
     with pytest.raises(ValueError):
         walk(sets=[])
+
+
+VARIANTS = ["layer 0", None, "layer 2"]          # (the walk hands a layer to recost_windows and reads nothing of it)
+VARIANT_SETS = [(8, None, 100.0, 0), (4, None, 100.0, 0), (8, SEARCH, 30.0, 1), (4, None, 100.0, 1), (4, None, 30.0, 2)]
+
+
+def test_variants(walk):
+    """5: per batch `stage 8`, the tickets, then the calls of windows.batch_schedule over the batch's live windows -- the None variant
+    first, `recost` before each layered one, `prefix` where k differs --; the results in the schedule's finish order, one per window
+    each, under their set's variant"""
+    steps = W.batch_schedule([(8, 0), (4, 0), (8, 1), (4, 1), (4, 2)], [True, False, True], False, False)
+    assert steps == [("finish", 2), ("prefix", 4), ("finish", 3), ("recost", 0), ("finish", 0), ("prefix", 4), ("finish", 1),
+                     ("recost", 2), ("prefix", 4), ("finish", 4)]
+
+    def call(n, kind, arg):
+        if kind == "finish":
+            _k, mode, penalty, _v = VARIANT_SETS[arg]
+            return ("finish", n, None, penalty, DEFAULT if mode is None else mode)
+        return (kind, n, VARIANTS[arg] if kind == "recost" else arg, None, None)
+
+    log, results, collected = walk(sets=VARIANT_SETS, variants=VARIANTS)
+    assert log == _batches(lambda staged, n, ids: [("stage", staged, 8, None, None)] + [("ticket", q) for q in ids]
+                           + [call(n, *step) for step in steps])
+    order = [(s, q) for batch in ((0, 1), (2, 3), (4,)) for s in (2, 3, 0, 1, 4) for q in batch]
+    assert [(r.set, r.window["window_id"]) for r in results] == order
+    for r in results:
+        k, _m, _p, v = VARIANT_SETS[r.set]
+        q = r.window["window_id"]
+        assert r.variant == v and (r.error is not None) == (q == 2)
+        if q != 2:
+            assert r.counts[3] == KEPT[q] * k == r.stats["pairs"] and len(r.match_row) == KEPT[q]
+    assert [a[2] for a in collected] == [2, 3, 0, 1, 4] * 3
+
+
+def test_a_batch_without_a_live_window_makes_its_stage_call_alone(walk, monkeypatch):
+    """6: windows 2 and 3 -- the second batch -- staged without pairs: `stage` and nothing else, no recost, prefix or prune over no
+    window, no finish; every set still yields an errored result for each of the two"""
+    monkeypatch.setitem(globals(), "KEPT", (4, 5, 0, 0, 8))
+    for priority in (False, True):
+        log, results, collected = walk(sets=VARIANT_SETS, variants=VARIANTS, priority=priority)
+        at = log.index(("stage", 2, 8, None, None), 1)
+        assert log[at + 1 + priority] == ("stage", 1, 8, None, None) and (not priority or log[at + 1] == ("priority", 2, None, None, None))
+        second = results[10:20]
+        assert [(r.set, r.window["window_id"]) for r in second] == [(s, q) for s in (2, 3, 0, 1, 4) for q in (2, 3)]
+        assert all(r.error is not None and r.state is None and r.match_row is None for r in second)
+        assert all(r.variant == VARIANT_SETS[r.set][3] and r.counts[3] == 0 for r in second)
+        assert sum(r.error is not None for r in results) == 10 and len(results) == 25
+        assert [[w["window_id"] for w in a[1]] for a in collected] == [[0, 1]] * 5 + [[4]] * 5

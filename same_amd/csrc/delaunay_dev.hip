@@ -502,7 +502,7 @@ int same_window_delaunay(same_window *const *windows, int n_windows, double radi
     same_ctx *ctx = nullptr;
     SAME_TRY(check_batch(windows, n_windows, &ctx));
     REQUIRE(ctx, out_status && out_n_tris && guard >= 0.0);
-    for (int i = 0; i < n_windows; ++i) REQUIRE(ctx, windows[i]->staged == 2 && windows[i]->n_ua < ((int64_t)1 << 30));
+    for (int i = 0; i < n_windows; ++i) REQUIRE(ctx, windows[i]->may_triangulate() && windows[i]->cur.n_ua < ((int64_t)1 << 30));
     SAME_TRY(same_use(ctx));
     const bool ok = settings_answerable(radius, angle_enabled, cos_thr);
     const Settings set{radius, cos_thr, guard};
@@ -513,12 +513,12 @@ int same_window_delaunay(same_window *const *windows, int n_windows, double radi
         same_window *w = windows[i];
         w->dd_ok = 0;
         w->n_dd = 0;
-        out_status[i] = !ok ? SAME_DD_NO_ANGLE : (w->n_ua < 3 ? SAME_DD_FEW_POINTS : 0);
+        out_status[i] = !ok ? SAME_DD_NO_ANGLE : (w->cur.n_ua < 3 ? SAME_DD_FEW_POINTS : 0);
         out_n_tris[i] = 0;
         if (out_status[i]) continue;
-        const int64_t n = w->n_ua, cap_out = 2 * n;
+        const int64_t n = w->cur.n_ua, cap_out = 2 * n;
         Job jb{};
-        jb.xy = w->axy_c;
+        jb.xy = w->cur.axy_c;
         jb.n = n;
         jb.cap_out = cap_out;
         size_t total = 0;
@@ -558,7 +558,7 @@ int same_window_delaunay(same_window *const *windows, int n_windows, double radi
         out_status[i] = (int32_t)(s[0] & 0x7fffffffu);
         if (out_status[i] == 0) {
             w->n_dd = (int64_t)s[1];
-            w->dd_ok = 1;
+            w->triangulated();
             out_n_tris[i] = w->n_dd;
         }
     }

@@ -10,20 +10,19 @@
 //   second compaction (src/same.py:1055-1085) the kept cells without the unconstrained ones -- rows, XY, sizes, type codes, kept index --
 //                    their pairs and costs, pair rows renumbered by the mask's prefix sum; the triangles without those that name a removed
 //                    node (none of them passes the tests: the filter that follows would drop them anyway), corners renumbered.
-// The compacted arrays live in the window's `caller` buffer and the window's pointers are turned to them: everything after this call --
-// the filter with the same-type re-add (which then meets no unconstrained node, :370), start, search, sweeps, collect -- is the
+// The compacted arrays live in the window's `caller` buffer and the window is turned to them (win::State::compacted): everything after
+// this call -- the filter with the same-type re-add (which then meets no unconstrained node, :370), start, search, sweeps, collect -- is the
 // unchanged window path on the smaller window (same_window_filter_finish with SAME_TRIS_CALLER).  The REFERENCE side stays the prune's.
 // A parameter sweep over knn (same_window_caller_pairs).  Which rows a window keeps, which of the caller's triangles are its own, the node
 // mask and the renumbering do not depend on k: only the pair list behind the mask does, and the second compaction (whole rows of pairs
 // go) commutes with the k-NN prefix (every row is cut to its first min(k, count) pairs).  After same_window_knn_prefix turned the
-// compacted window back to the stage call's arrays -- the mask, the renumbering, the compacted aligned side and the renumbered
-// triangles stay in `caller`, held (same_window::Held) -- one call per batch pushes the window's CURRENT pair list through the held mask:
+// compacted window back and HELD the caller's work (win::Held), one call per batch pushes the window's CURRENT pair list through the held mask:
 //   row offsets    one ordered scan (scan.h) over the staged kept cells of valid[v] ? row count : 0 gives the new pair offsets and count
 //   scatter        one thread per pair of the current list: a pair of a row that stays goes to new_prow[newidx[row]] + place, its row
 //                  renumbered, its reference number, its reference's section row and its cost copied -- loads and stores run along
 //                  the pair index (the per-row loop of caller_cells_kernel, which also moves the aligned side, is not repeated)
 // into the pair arrays of `caller`, which were sized for the list as staged.  The window is then, array for array, the one a stage call
-// at k (+ the priority prune) + same_window_caller_tris leaves.
+// at k (+ the priority prune) + same_window_caller_tris leaves.  What either call requires, leaves and invalidates: window_state.h's table.
 // Both calls are batches of window_stage.hip's driver (window_internal.h); a failed batch of either leaves its live windows un-staged.
 #include "window_internal.h"
 
@@ -192,18 +191,15 @@ struct CallerPlan {
     RowsArgs rows{};
     ZeroArgs zero{};
     size_t back_bytes = 0;
-    same_window::Staged next;          // the window's arrays once the removal counts
+    View next;                         // the window's view once the removal counts
     int64_t pair_cap = 0;              // pairs next's pair arrays hold
 };
 
 // One window's `caller` buffer laid out; no launch.  The caller holds the moving section's grid lock (shared).
 int prepare_caller(same_window *w, const same_caller_tris *ct, bool use_type, CallerPlan *cp) {
     same_ctx *ctx = w->ctx;
-    if (w->caller_ok) turn_to(w, w->st0);          // a second call (the host's mask) starts from the stage call's arrays again
-    w->caller_ok = w->caller_sel = 0;
-    w->held = same_window::Held{};                 // (a selection held for a k-NN prefix is overwritten: this call works from the list as it is)
-    w->st0 = staged_of(w);
-    const int64_t n0 = w->n_ua, P0 = w->P, cap_m = w->cap_m;
+    w->restart_caller();
+    const int64_t n0 = w->cur.n_ua, P0 = w->cur.list.P, cap_m = w->cap_m;
     // the pair arrays take the list as STAGED (>= any prefix of it, pruned or not): same_window_caller_pairs fills them again per knn
     const int64_t pair_cap = cp->pair_cap = std::max(P0, w->sk.P);
     // the candidates: the triangles binned in the cells the box covers (their number is known here), or every triangle of the job where
@@ -220,7 +216,7 @@ int prepare_caller(same_window *w, const same_caller_tris *ct, bool use_type, Ca
     CallerArgs &a = cp->a;
     a = CallerArgs{};
     uint32_t *merged = nullptr;
-    same_window::Staged &nx = cp->next;
+    View &nx = cp->next;
     size_t o_counts = 0;
     auto lay = [&](Carver c) {
         // zeroed head: scan words, the call's counters, the node mask
@@ -264,14 +260,14 @@ int prepare_caller(same_window *w, const same_caller_tris *ct, bool use_type, Ca
     a.cand = by_cells ? merged : nullptr;
     a.n_cand = n_cand;
     a.tris = ct->tris;
-    a.rows0 = w->rows_ua;
+    a.rows0 = w->cur.rows_ua;
     a.n0 = n0;
-    a.axy0 = w->axy_c;
-    a.type0 = use_type ? w->type_c : nullptr;
-    a.counts0 = w->counts;
-    a.ua0 = w->ua;
-    a.size0 = w->size_c;
-    a.src = list_of(w);
+    a.axy0 = w->cur.axy_c;
+    a.type0 = use_type ? w->cur.type_c : nullptr;
+    a.counts0 = w->cur.counts;
+    a.ua0 = w->cur.ua;
+    a.size0 = w->cur.size_c;
+    a.src = w->cur.list;
     a.dst = nx.list;
     a.counts = nx.counts;
     a.ua = nx.ua;
@@ -361,16 +357,16 @@ __global__ __launch_bounds__(256) void caller_pair_scatter_kernel(Batch<PairsArg
 
 using PairsPlan = ListPlan<PairsArgs>;
 
-// no buffer is laid out: every pointer is one prepare_caller placed (same_window::Held), or the window's current list
+// no buffer is laid out: every pointer is one prepare_caller placed (win::Held), or the window's current list
 void prepare_pairs(const same_window *w, PairsPlan *pp) {
-    const same_window::Held &h = w->held;
+    const Held &h = w->held;
     PairsArgs &a = pp->a;
     a = PairsArgs{};
-    a.n = w->n_ua;
+    a.n = w->cur.n_ua;
     a.cap = h.cap;
     a.valid = h.valid;
     a.newidx = h.newidx;
-    a.src = list_of(w);
+    a.src = w->cur.list;
     a.dst = h.cs.list;
     a.st = h.st;
     a.counts = h.cs.counts;
@@ -464,9 +460,9 @@ int same_window_caller_tris(same_window *const *windows, int n_windows, const sa
     REQUIRE(ctx, ct && out_counts && ct->ctx->device == ctx->device && !removed == !removed_offsets);
     for (int i = 0; i < n_windows; ++i) {
         const same_window *w = windows[i];
-        REQUIRE(ctx, w->staged == 2 && w->mov == ct->mov);
+        REQUIRE(ctx, w->may_select() && w->mov == ct->mov);
         if (removed) {
-            const int64_t n0 = w->caller_ok ? w->st0.n_ua : w->n_ua;
+            const int64_t n0 = w->caller_ok ? w->st0.n_ua : w->cur.n_ua;
             REQUIRE(ctx, (i > 0 || removed_offsets[0] == 0) && removed_offsets[i + 1] - removed_offsets[i] == n0);
         }
     }
@@ -488,7 +484,7 @@ int same_window_caller_tris(same_window *const *windows, int n_windows, const sa
         REQUIRE(ctx, g.x0 == h.x0 && g.y0 == h.y0 && g.cw == h.cw && g.ch == h.ch && g.nx == h.nx && g.ny == h.ny);
         for (int i = 0; i < n_windows && rc == SAME_OK; ++i) {
             same_window *w = windows[i];
-            if ((w->caller_ok ? w->st0.n_ua : w->n_ua) == 0) continue;     // no kept cell: nothing to select, nothing to remove
+            if ((w->caller_ok ? w->st0.n_ua : w->cur.n_ua) == 0) continue;     // no kept cell: nothing to select, nothing to remove
             const bool use_type = ignore_same_type && w->has_type;
             rc = prepare_caller(w, ct, use_type, &plans[(size_t)i]);
             if (rc == SAME_OK) live.push_back(i);
@@ -521,8 +517,7 @@ int same_window_caller_tris(same_window *const *windows, int n_windows, const sa
         int64_t *counts = out_counts + 6 * i;
         const int64_t n_ua = (int64_t)tot[2], P = (int64_t)tot[3], n_left = (int64_t)tot[4], n_sel = (int64_t)tot[5], near = (int64_t)tot[6];
         REQUIRE(ctx, n_ua <= w->st0.n_ua && P <= w->st0.list.P && n_left <= n_sel && n_sel <= cp.a.n_cand && (int64_t)tot[7] == w->st0.n_ua - n_ua);
-        w->n_sel = n_sel;
-        w->caller_sel = 1;
+        w->selected(n_sel);
         counts[0] = n_sel;
         counts[1] = (int64_t)tot[7];
         counts[2] = near;
@@ -539,17 +534,12 @@ int same_window_caller_tris(same_window *const *windows, int n_windows, const sa
         }
         cp.next.n_ua = n_ua;
         cp.next.list.P = P;
-        turn_to(w, cp.next);
-        w->n_caller = n_left;
-        w->caller_ok = 1;
+        w->compacted(cp.next, n_left);
         w->held.valid = cp.a.valid;               // what a k-NN prefix holds on to (held.on stays 0: the window IS the compacted one)
         w->held.newidx = cp.a.newidx;
         w->held.st = cp.a.st_cell;
         w->held.back_bytes = cp.back_bytes;
         w->held.cap = cp.pair_cap;
-        w->dd_ok = 0;
-        w->filtered = w->finished = 0;
-        w->Tr = 0;
         counts[3] = n_ua;
         counts[4] = P;
         counts[5] = n_left;
@@ -564,9 +554,9 @@ int same_window_caller_pairs(same_window *const *windows, int n_windows, int64_t
     REQUIRE(ctx, out_counts);
     for (int i = 0; i < n_windows; ++i) {
         const same_window *w = windows[i];
-        REQUIRE(ctx, w->staged == 2 && !w->filtered && !w->finished && !w->caller_ok && !w->caller_sel);
+        REQUIRE(ctx, w->may_push_pairs());
         // a held selection -- or a window without kept cells, which same_window_caller_tris had nothing to select for either
-        REQUIRE(ctx, w->held.on ? (w->n_ua > 0 && w->P <= w->held.cap && w->held.cs.n_ua <= w->n_ua) : w->n_ua == 0);
+        REQUIRE(ctx, w->held.on ? (w->cur.n_ua > 0 && w->cur.list.P <= w->held.cap && w->held.cs.n_ua <= w->cur.n_ua) : w->cur.n_ua == 0);
     }
     for (int q = 0; q < 6 * n_windows; ++q) out_counts[q] = 0;
     SAME_TRY(same_use(ctx));
@@ -590,22 +580,17 @@ int same_window_caller_pairs(same_window *const *windows, int n_windows, int64_t
     for (int i : live) {
         const same_window *w = windows[i];
         const unsigned long long *tot = static_cast<const unsigned long long *>(w->host);
-        REQUIRE(ctx, (int64_t)tot[2] == w->held.cs.n_ua && (int64_t)tot[3] <= w->P && (int64_t)tot[3] <= w->held.cap &&
-                         (int64_t)tot[4] == w->n_caller && (int64_t)tot[7] == w->n_ua - w->held.cs.n_ua);
+        REQUIRE(ctx, (int64_t)tot[2] == w->held.cs.n_ua && (int64_t)tot[3] <= w->cur.list.P && (int64_t)tot[3] <= w->held.cap &&
+                         (int64_t)tot[4] == w->n_caller && (int64_t)tot[7] == w->cur.n_ua - w->held.cs.n_ua);
     }
     for (int i : live) {
         same_window *w = windows[i];
         const unsigned long long *tot = static_cast<const unsigned long long *>(w->host);
         // as prepare_caller and the end of same_window_caller_tris leave it: st0 the arrays the removal started from
-        w->st0 = staged_of(w);
-        same_window::Staged cs = w->held.cs;
+        w->st0 = w->cur;
+        View cs = w->held.cs;
         cs.list.P = (int64_t)tot[3];
-        turn_to(w, cs);
-        w->held.on = 0;
-        w->caller_sel = w->caller_ok = 1;
-        w->dd_ok = 0;
-        w->filtered = w->finished = 0;
-        w->Tr = 0;
+        w->compacted(cs, w->n_caller);
         int64_t *counts = out_counts + 6 * i;
         counts[0] = w->n_sel;
         counts[1] = w->st0.n_ua - cs.n_ua;

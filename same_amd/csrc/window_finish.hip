@@ -301,15 +301,15 @@ struct FilterPlan {
 // of windows (launch_filter, and the zeroing with the finish buffers')
 int prepare_filter(same_window *w, const int32_t *d_simplices, int64_t Tr, int ignore_same_type, int ensure_min_triangle_per_node, FilterPlan *plan) {
     same_ctx *ctx = w->ctx;
-    const int64_t n = w->n_ua;
+    const int64_t n = w->cur.n_ua;
     const bool use_type = ignore_same_type && w->has_type;
     plan->readd = use_type && ensure_min_triangle_per_node;
     FilterArgs &a = plan->args;
-    a.xy = w->axy_c;
+    a.xy = w->cur.axy_c;
     a.raw = d_simplices;
     a.Tr = Tr;
     a.n = n;
-    a.type_id = use_type ? w->type_c : nullptr;
+    a.type_id = use_type ? w->cur.type_c : nullptr;
     auto lay = [&](Carver cv) {
         // zeroed head: scan words, counters, vertex marks, inverted minima
         a.st_keep = scan::arg(cv.scan_words(Tr));
@@ -414,10 +414,10 @@ int enqueue_tail(same_ctx *ctx, same_window *const *ws, FinishPlan *const *ps, i
     for (int q = 0; q < n_w; ++q) {
         same_window *w = ws[q];
         FinishPlan *p = ps[q];
-        const int64_t n = w->n_ua;
-        mb.w[q] = MatchRowsArgs{p->match_pair, p->refine ? p->rargs.match : p->match_pair, w->pairs, w->jsec, w->prow, p->gs.alive, p->gs.used, n, w->counts + 2, w->match_loc, p->match_row, p->pflag,
+        const int64_t n = w->cur.n_ua;
+        mb.w[q] = MatchRowsArgs{p->match_pair, p->refine ? p->rargs.match : p->match_pair, w->cur.list.pairs, w->cur.list.jsec, w->cur.list.prow, p->gs.alive, p->gs.used, n, w->cur.counts + 2, w->match_loc, p->match_row, p->pflag,
                                 p->counters};
-        sb.w[q] = SweepArgs{static_cast<const int32_t *>(w->tris.p), p->cap_tr, p->dTr, w->axy_c, w->size_c, w->ref->xy, p->match_row, w->sign, w->weight,
+        sb.w[q] = SweepArgs{static_cast<const int32_t *>(w->tris.p), p->cap_tr, p->dTr, w->cur.axy_c, w->cur.size_c, w->ref->xy, p->match_row, w->sign, w->weight,
                             p->pflag, p->counters};
         max_n = std::max(max_n, n);
         max_tr = std::max(max_tr, p->cap_tr);
@@ -433,7 +433,7 @@ int enqueue_tail(same_ctx *ctx, same_window *const *ws, FinishPlan *const *ps, i
 int prepare_finish(same_window *w, const int32_t *host_tris, int64_t cap_tr, const unsigned long long *dTr, const FinishMode &mode,
                    FinishPlan *p) {
     same_ctx *ctx = w->ctx;
-    const int64_t n = w->n_ua, P = w->P, n_ends = n + w->n_r;
+    const int64_t n = w->cur.n_ua, P = w->cur.list.P, n_ends = n + w->n_r;
     const size_t tt = (size_t)std::max<int64_t>(cap_tr, 1);
     p->mode = mode;
     p->cap_tr = cap_tr;
@@ -474,14 +474,14 @@ int prepare_finish(same_window *w, const int32_t *host_tris, int64_t cap_tr, con
     w->match_row = p->match_row;
     w->pflag = p->pflag;
     if (p->refine) {
-        r.prow = w->prow;
-        r.pairs = w->pairs;
-        r.cost = w->cost64;
-        r.size = w->size_c;
+        r.prow = w->cur.list.prow;
+        r.pairs = w->cur.list.pairs;
+        r.cost = w->cur.list.cost64;
+        r.size = w->cur.size_c;
         r.dp = mode.delaunay_penalty;
-        r.axy = w->axy_c;
+        r.axy = w->cur.axy_c;
         r.ref_xy = w->ref->xy;
-        r.ref_row = w->jsec;
+        r.ref_row = w->cur.list.jsec;
         r.tris = static_cast<const int32_t *>(w->tris.p);
         r.dTr = dTr;
         r.cap = mode.refine_cap;
@@ -491,8 +491,8 @@ int prepare_finish(same_window *w, const int32_t *host_tris, int64_t cap_tr, con
             r.rsize = w->ref->size;
             r.ref_rows = w->rows_r;
             r.P = P;
-            r.lim_row = as_staged(w).jsec;
-            r.lim_P = as_staged(w).P;
+            r.lim_row = w->as_staged().jsec;
+            r.lim_P = w->as_staged().P;
             r.max_matches = mode.cap.max_matches;
             r.multiplier = mode.cap.multiplier;
         }
@@ -533,11 +533,11 @@ int launch_finish(same_ctx *ctx, same_window *const *ws, FinishPlan *const *ps, 
                 rfn::RefineArgs &r = lim[q];
                 r = rfn::RefineArgs{};
                 r.rsize = w->ref->size;
-                r.ref_row = w->jsec;
+                r.ref_row = w->cur.list.jsec;
                 r.ref_rows = w->rows_r;
-                r.P = w->P;
-                r.lim_row = as_staged(w).jsec;
-                r.lim_P = as_staged(w).P;
+                r.P = w->cur.list.P;
+                r.lim_row = w->as_staged().jsec;
+                r.lim_P = w->as_staged().P;
                 r.n_r = w->n_r;
                 r.max_matches = c.max_matches;
                 r.multiplier = c.multiplier;
@@ -550,12 +550,12 @@ int launch_finish(same_ctx *ctx, same_window *const *ws, FinishPlan *const *ps, 
             FinishPlan *p = ps[q];
             asg::AssignArgs &a = jobs[q];
             a = p->aargs;                     // n, n_r and the work arrays (prepare_finish)
-            a.prow = w->prow;
-            a.pairs = w->pairs;
-            a.cost = w->cost64;
-            a.size = w->size_c;
+            a.prow = w->cur.list.prow;
+            a.pairs = w->cur.list.pairs;
+            a.cost = w->cur.list.cost64;
+            a.size = w->cur.size_c;
             a.penalty = no_match_penalty;
-            a.max_pops = asg::default_max_pops(w->n_ua, w->n_r, w->P, transport);
+            a.max_pops = asg::default_max_pops(w->cur.n_ua, w->n_r, w->cur.list.P, transport);
             a.alive = p->gs.alive;
             a.match_pair = p->match_pair;
             a.res = p->gs.sel;
@@ -570,15 +570,15 @@ int launch_finish(same_ctx *ctx, same_window *const *ws, FinishPlan *const *ps, 
     for (int q = 0; q < n_w; ++q) {
         same_window *w = ws[q];
         FinishPlan *p = ps[q];
-        pb.w[q] = PreferArgs{w->prow, w->cost64, w->size_c, w->counts + 2, p->gs.alive, p->match_pair, w->n_ua};
-        jobs[q].pairs = w->pairs;
-        jobs[q].costs = w->cost64;
-        jobs[q].P = w->P;
-        jobs[q].n_m = w->n_ua;
+        pb.w[q] = PreferArgs{w->cur.list.prow, w->cur.list.cost64, w->cur.size_c, w->cur.counts + 2, p->gs.alive, p->match_pair, w->cur.n_ua};
+        jobs[q].pairs = w->cur.list.pairs;
+        jobs[q].costs = w->cur.list.cost64;
+        jobs[q].P = w->cur.list.P;
+        jobs[q].n_m = w->cur.n_ua;
         jobs[q].n_r = w->n_r;
         jobs[q].st = p->gs;
         jobs[q].match_pair = p->match_pair;
-        max_n = std::max(max_n, w->n_ua);
+        max_n = std::max(max_n, w->cur.n_ua);
     }
     if (max_n) SAME_LAUNCH(ctx, row_prefer_kernel, dim3(grid_for(max_n), (unsigned)n_w), dim3(256), 0, pb, no_match_penalty);
     SAME_TRY(same_greedy_rounds_batch_core(ctx, jobs, n_w, 0, WINDOW_GREEDY_ROUNDS));
@@ -639,7 +639,7 @@ int settle(same_window *w, FinishPlan *p, bool fresh, int64_t *out_stats) {
 
 int read_finish(same_window *w, FinishPlan *p, int32_t *out_match_row, uint8_t *out_point_flag, int64_t *out_stats, int64_t *out_ties) {
     same_ctx *ctx = w->ctx;
-    const int64_t n = w->n_ua, P = w->P;
+    const int64_t n = w->cur.n_ua, P = w->cur.list.P;
     char *h = static_cast<char *>(w->host) + w->host_finish_off;
     const char *dsel = reinterpret_cast<const char *>(p->gs.sel);
     const unsigned long long *sel = reinterpret_cast<const unsigned long long *>(h);
@@ -662,7 +662,7 @@ int read_finish(same_window *w, FinishPlan *p, int32_t *out_match_row, uint8_t *
             for (;;) {
                 REQUIRE(ctx, rounds <= P + 1);
                 SAME_FILL(ctx, p->gs.sel, 0, (size_t)batch * 8);
-                SAME_TRY(same_greedy_rounds_core(ctx, w->pairs, w->cost64, P, nullptr, n, w->n_r, p->gs, p->match_pair, rounds, batch));
+                SAME_TRY(same_greedy_rounds_core(ctx, w->cur.list.pairs, w->cur.list.cost64, P, nullptr, n, w->n_r, p->gs, p->match_pair, rounds, batch));
                 SAME_COPY(ctx, h, dsel, (size_t)batch * 8, hipMemcpyDeviceToHost);
                 SAME_WAIT(ctx);
                 ++ctx->stats[SAME_STAT_GREEDY_READBACKS];
@@ -703,7 +703,7 @@ static int filter_finish(same_window *const *windows, int n_windows, int source,
     if (on_device) {
         dd_offsets.assign((size_t)n_windows + 1, 0);
         for (int i = 0; i < n_windows; ++i) {
-            REQUIRE(ctx, (from_caller ? windows[i]->caller_ok : windows[i]->dd_ok) && windows[i]->staged == 2);
+            REQUIRE(ctx, windows[i]->may_finish_from(from_caller ? FROM_CALLER : FROM_DEVICE));
             dd_offsets[(size_t)i + 1] = dd_offsets[(size_t)i] + (from_caller ? windows[i]->n_caller : windows[i]->n_dd);
         }
         simplex_offsets = dd_offsets.data();
@@ -712,8 +712,8 @@ static int filter_finish(same_window *const *windows, int n_windows, int source,
     int64_t n_cells = 0;
     for (int i = 0; i < n_windows; ++i) {
         const int64_t Tr = simplex_offsets[i + 1] - simplex_offsets[i];
-        REQUIRE(ctx, windows[i]->staged == 2 && Tr >= 0 && Tr < ((int64_t)1 << 31) - 512);
-        n_cells += windows[i]->n_ua;
+        REQUIRE(ctx, windows[i]->may_finish_from(FROM_HOST) && Tr >= 0 && Tr < ((int64_t)1 << 31) - 512);
+        n_cells += windows[i]->cur.n_ua;
     }
     REQUIRE(ctx, n_cells == 0 || (out_match_row && out_point_flag));
     for (int q = 0; q < 4 * n_windows; ++q) out_counts[q] = 0;
@@ -722,7 +722,7 @@ static int filter_finish(same_window *const *windows, int n_windows, int source,
     if (!on_device)     // (the device's own triangles index the window's kept cells by construction)
         for (int i = 0; i < n_windows; ++i)
             SAME_TRY(check_index_range(ctx, simplices + 3 * simplex_offsets[i], (simplex_offsets[i + 1] - simplex_offsets[i]) * 3, 0,
-                                       windows[i]->n_ua, "triangles"));
+                                       windows[i]->cur.n_ua, "triangles"));
     struct Item {
         FilterPlan fplan;
         FinishPlan plan;
@@ -748,9 +748,8 @@ static int filter_finish(same_window *const *windows, int n_windows, int source,
         Item &it = items[(size_t)i];
         const int32_t *tri = on_device ? nullptr : simplices + 3 * simplex_offsets[i];
         const int64_t Tr = simplex_offsets[i + 1] - simplex_offsets[i];
-        w->filtered = w->finished = 0;
-        w->Tr = 0;
-        if (w->n_ua == 0) continue;
+        w->results_void();
+        if (w->cur.n_ua == 0) continue;
         if (Tr && source != SAME_TRIS_KEPT) {
             const int32_t *raw = from_caller ? w->caller_out : on_device ? static_cast<const int32_t *>(w->dd_tris.p) : d_simplices + 3 * simplex_offsets[i];
             rc = prepare_filter(w, raw, Tr, ignore_same_type, ensure_min_triangle_per_node, &it.fplan);
@@ -796,7 +795,7 @@ static int filter_finish(same_window *const *windows, int n_windows, int source,
         for (int i = 0; i < n_windows && rc == SAME_OK; ++i) {
             same_window *w = windows[i];
             Item &it = items[(size_t)i];
-            if (w->n_ua != 0) {
+            if (w->cur.n_ua != 0) {
                 if (w->host_dev) {
                     ca[n_g++] = CopyArgs{{it.plan.gs.sel, it.filtered ? it.fplan.counters : nullptr},
                                          {w->host_dev + w->host_finish_off, w->host_dev + w->host_filter_off},
@@ -830,12 +829,12 @@ static int filter_finish(same_window *const *windows, int n_windows, int source,
         const int64_t Tr = simplex_offsets[i + 1] - simplex_offsets[i];
         int64_t *counts = out_counts + 4 * i, *stats = out_stats + mode.stride * i;
         if (!it.enqueued) {                 // no kept aligned cell: nothing to match, nothing to sweep
-            w->filtered = w->finished = 1;
+            w->finished_with(0);
             continue;
         }
         int32_t *const match_out = out_match_row + cell0;
         uint8_t *const flag_out = out_point_flag + cell0;
-        cell0 += w->n_ua;
+        cell0 += w->cur.n_ua;
         if (it.filtered) {
             // the filter's counters first (they are on the host since the batch's one wait): a window with a cosine at the threshold is
             // redone by the caller with SAME_TRIS_KEPT, so nothing of it is read back here (its stats stay 0) -- in particular no further greedy rounds
@@ -847,13 +846,11 @@ static int filter_finish(same_window *const *windows, int n_windows, int source,
             counts[2] = n_near;
             counts[3] = (int64_t)hf[FC_TIES];
             if (n_near) continue;
-            w->Tr = n_keep + n_add;
         } else {
             counts[0] = Tr;
-            w->Tr = Tr;
         }
         SAME_TRY(read_finish(w, &it.plan, match_out, flag_out, stats, counts + 3));
-        w->filtered = w->finished = 1;
+        w->finished_with(counts[0] + counts[1]);      // kept + added back (the caller's kept triangles: all of them)
     }
     return SAME_OK;
 }
@@ -864,15 +861,15 @@ static int refinish(same_window *window, const int32_t *match_pair, const Finish
     same_window *w = window;
     same_ctx *ctx = w->ctx;
     SAME_TRY(check_mode(ctx, mode));
-    REQUIRE(ctx, w->finished && w->staged == 2 && w->n_ua > 0 && match_pair && out_match_row && out_point_flag && out_stats);
-    for (int64_t i = 0; i < w->n_ua; ++i) REQUIRE(ctx, match_pair[i] >= -1 && match_pair[i] < w->P);
+    REQUIRE(ctx, w->has_results() && w->cur.n_ua > 0 && match_pair && out_match_row && out_point_flag && out_stats);
+    for (int64_t i = 0; i < w->cur.n_ua; ++i) REQUIRE(ctx, match_pair[i] >= -1 && match_pair[i] < w->cur.list.P);
     SAME_TRY(same_use(ctx));
     // the window's kept triangles are still the first w->Tr of its triangle buffer: lay the finish block out for exactly those
     FinishPlan p;
     SAME_TRY(prepare_finish(w, nullptr, w->Tr, nullptr, mode, &p));
     SAME_FILL(ctx, p.zero, 0, p.zero_bytes);
-    if (w->P) SAME_FILL(ctx, p.gs.alive, 0, (size_t)w->P);
-    SAME_COPY(ctx, p.match_pair, match_pair, (size_t)w->n_ua * 4, hipMemcpyHostToDevice);
+    if (w->cur.list.P) SAME_FILL(ctx, p.gs.alive, 0, (size_t)w->cur.list.P);
+    SAME_COPY(ctx, p.match_pair, match_pair, (size_t)w->cur.n_ua * 4, hipMemcpyHostToDevice);
     FinishPlan *pp = &p;
     SAME_TRY(enqueue_refine(ctx, &pp, 1));          // the local search again, from the caller's matching
     SAME_TRY(enqueue_tail(ctx, &w, &pp, 1));
@@ -883,8 +880,8 @@ static int refinish(same_window *window, const int32_t *match_pair, const Finish
     SAME_TRY(settle(w, &p, false, out_stats));
     const unsigned long long *cnt = reinterpret_cast<const unsigned long long *>(h + p.o_counters);
     for (int q = 0; q < 8; ++q) out_stats[q] = (int64_t)cnt[q];
-    memcpy(out_match_row, h + p.o_match_row, (size_t)w->n_ua * sizeof(int32_t));
-    memcpy(out_point_flag, h + p.o_pflag, (size_t)w->n_ua);
+    memcpy(out_match_row, h + p.o_match_row, (size_t)w->cur.n_ua * sizeof(int32_t));
+    memcpy(out_point_flag, h + p.o_pflag, (size_t)w->cur.n_ua);
     return SAME_OK;
 }
 

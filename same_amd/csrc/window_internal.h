@@ -1,7 +1,8 @@
 // window_internal.h -- what the translation units of the device-resident window path share (section.hip, window_stage.hip,
 // window_finish.hip, window_merge.hip, window_score.hip, window_caller.hip, window_priority.hip, window_knn_prefix.hip, window_recost.hip): the resident objects behind the
-// opaque handles of include/same_hip.h part 4, the per-launch argument blocks, a window's pair list (win::PairList) and the one
-// statement of which list is "the list as staged" (win::as_staged), the small host helpers and the batch driver of the window calls.
+// opaque handles of include/same_hip.h part 4, the per-launch argument blocks, the device side of a window's pair list, the window's
+// logical state (window_state.h: win::State, with the table of what each call requires, leaves and invalidates), the small host helpers
+// and the batch driver of the window calls.
 //
 // The window path (src/same.py:507-593 with both sections RESIDENT on the device).  A section's columns are uploaded once
 // (same_section) and its rows are binned once into a grid of cells (same_section_bin: rows sorted by cell, ascending inside a cell)
@@ -48,6 +49,7 @@
 #include "common.h"
 #include "devmath.h"
 #include "scan.h"
+#include "window_state.h"
 
 struct same_knn_index;
 extern "C" int same_knn_index_build(same_ctx *ctx, const double *drxy, int64_t n_r, double radius, same_knn_index **out);
@@ -199,16 +201,7 @@ inline size_t finish_back_bytes(int64_t n) {
     return b.back_bytes;
 }
 
-// A window's pair list: row a of the aligned side owns pairs [prow[a], prow[a + 1]); pair p is (pairs[2p] = aligned row, pairs[2p + 1] =
-// the reference's number in the window), jsec[p] that reference's SECTION row, cost64[p] its cost; P pairs.  The stage call makes one;
-// the priority prune, the k-NN prefix and the caller's removal each derive a second from one (source and destination of their kernels)
-// and turn the window to it (list_of / turn_to below).
-struct PairList {
-    int32_t *prow = nullptr, *pairs = nullptr, *jsec = nullptr;
-    double *cost64 = nullptr;
-    int64_t P = 0;
-};
-
+// (win::PairList, a window's pair list: window_state.h)
 // pair p of `src` becomes pair `at` of `dst` under aligned row a: its reference number, that reference's section row and its cost are
 // copied, never recomputed
 __device__ __forceinline__ void move_pair(const PairList &dst, int64_t at, int32_t a, const PairList &src, int64_t p) {
@@ -274,21 +267,19 @@ struct same_types_layer {
     double *types64 = nullptr; // [n][T] (== types_c for fp64 costs)
 };
 
-struct same_window {
+// A window: the buffers and the pinned block its calls work in, and -- the base -- its logical state (window_state.h: which arrays and
+// which list are the window's, what holds, and the table of what each call requires, leaves and invalidates).
+struct same_window : win::State {
     same_ctx *ctx = nullptr;
     const same_section *mov = nullptr, *ref = nullptr;
-    int cost_f32 = 0, k = 0, staged = 0, finished = 0, has_type = 0, filtered = 0;
+    int cost_f32 = 0, has_type = 0;
     int64_t cap_m = 0, cap_r = 0;                   // candidates of the covered cells: what the lists are sized for
-    int64_t n_m = 0, n_r = 0, n_ua = 0, P = 0, Tr = 0;
+    int64_t n_m = 0, n_r = 0;
     win::DevBuf stage, filter, finish, tris, big_mask, full_m, full_r;
     win::DevBuf dd_work, dd_tris;                   // the device's triangulation (delaunay_dev.hip): work buffer, candidate triangles
-    int64_t n_dd = 0;                               // candidate triangles in dd_tris ...
-    int dd_ok = 0;                                  // ... valid for the window as staged (same_window_delaunay answered it)
-    // stage block
-    unsigned long long *counts = nullptr;           // [8], first words of the block the stage call copies back
-    int32_t *rows_m = nullptr, *rows_r = nullptr, *idx = nullptr, *cnt = nullptr, *ua = nullptr, *rows_ua = nullptr, *type_c = nullptr,
-            *prow = nullptr, *pairs = nullptr, *jsec = nullptr;      // prow, pairs, jsec, cost64 and P: the window's CURRENT pair list
-    double *axy_c = nullptr, *size_c = nullptr, *cost64 = nullptr;  // (a win::PairList held loose: win::list_of reads it, win::turn_to sets it)
+    int64_t n_dd = 0;                               // candidate triangles in dd_tris (dd_ok)
+    // stage block (beside the stage view's arrays)
+    int32_t *rows_m = nullptr, *rows_r = nullptr, *idx = nullptr, *cnt = nullptr;
     // finish block
     int8_t *sign = nullptr;
     double *weight = nullptr;
@@ -300,50 +291,25 @@ struct same_window {
     size_t host_bytes = 0;
     size_t host_finish_off = 0;   // the pinned block: [stage call's copy | finish call's copy | the filter's counters]
     size_t host_filter_off = 0;
-    // the caller's triangulation (window_caller.hip).  same_window_caller_tris leaves the window's triangles in `caller` and, unless a
-    // cosine sits at the threshold, the window WITHOUT its unconstrained nodes: the arrays above then point into `caller`, the ones the
-    // removal started from are kept in `st0` (a second call with the host's mask starts from them again; a k-NN prefix turns the window
-    // back to them)
     double box[4] = {0.0, 0.0, 0.0, 0.0};
+    // the caller's triangulation (window_caller.hip): the window's triangles before / after the removal, the compacted view, the node
+    // mask and the renumbering
     win::DevBuf caller;
-    int caller_sel = 0, caller_ok = 0;              // sel_tris valid; the window is the compacted one and caller_out its triangles
-    int64_t n_sel = 0, n_caller = 0;                // the window's triangles before / after the removal
     int32_t *sel_tris = nullptr, *caller_out = nullptr;
-    struct Staged {
-        unsigned long long *counts = nullptr;
-        int32_t *ua = nullptr, *rows_ua = nullptr, *type_c = nullptr;
-        double *axy_c = nullptr, *size_c = nullptr;
-        int64_t n_ua = 0;
-        win::PairList list;
-    } st0;
-    // a k-NN prefix on the compacted window (window_knn_prefix.hip) turns it back to st0 and HOLDS the caller's work in `caller`: the node
-    // mask, the renumbering, the compacted aligned side (held.cs: ua, rows, XY, sizes, type codes; its counts block) and the renumbered
-    // triangles (caller_out, n_caller, n_sel stay).  same_window_caller_pairs pushes the window's current pair list through the mask
-    // into held.cs's pair arrays (room for `cap` pairs: the list as staged) and turns the window to held.cs again.  The pointers are
-    // those prepare_caller laid out -- kept, not laid out again
-    struct Held {
-        int on = 0;                                 // the window is as a stage call leaves it AND `caller` holds a selection for it
-        Staged cs;
-        const uint8_t *valid = nullptr;             // [st0.n_ua] the node mask
-        const int32_t *newidx = nullptr;            // [st0.n_ua] kept cell as staged -> kept cell left, or -1
-        unsigned long long *st = nullptr;           // the cell scan's words (a scan::arg)
-        size_t back_bytes = 0;                      // counts + kept XY + kept rows: what takes the stage block's place in the pinned block
-        int64_t cap = 0;
-    } held;
-    // the cell-type-priority prune (window_priority.hip).  same_window_priority_pairs leaves the filtered pair list in `prio` and turns
-    // the window's list to it; the list it started from -- the list as staged -- stays where it is, kept in `pr` (win::as_staged).
-    // bins_*: the sections' `bins` when the window was staged
-    win::DevBuf prio;
-    int prio_ok = 0;
-    win::PairList pr;
-    unsigned long long bins_m = 0, bins_r = 0;
-    // the k-NN prefix (window_knn_prefix.hip).  same_window_knn_prefix leaves every row's first min(k, count) pairs in `kpre` and turns
-    // the window's list to it: the window is then what a stage call at that k leaves, and `k` is that k.  sk: the list as the
-    // stage call put it (k_staged its k), which every prefix is derived from and a prefix at k_staged turns the window back to
-    win::DevBuf kpre;
-    int k_staged = 0;
-    win::PairList sk;
+    win::DevBuf prio;                               // the cell-type-priority prune's list (window_priority.hip)
+    unsigned long long bins_m = 0, bins_r = 0;      // the sections' `bins` when the window was staged
+    win::DevBuf kpre;                               // the k-NN prefix's list (window_knn_prefix.hip)
 };
+
+// what every call that leaves a window staged reports of it: aligned rows and reference rows in the box, kept aligned cells, pairs
+namespace win {
+inline void report_counts(const same_window *w, int64_t *out) {
+    out[0] = w->n_m;
+    out[1] = w->n_r;
+    out[2] = w->cur.n_ua;
+    out[3] = w->cur.list.P;
+}
+}  // namespace win
 
 // A caller's triangulation of a moving section, resident (same_caller_tris_create): section rows per corner, in the caller's order, and
 // the triangles binned by the section's grid cell of their FIRST corner (ascending inside a cell) -- a window reads the cells it covers.
@@ -428,69 +394,6 @@ static_assert(sizeof(RestRec) == SAME_MERGE_REST_BYTES && sizeof(FinalRec) == SA
 
 namespace win {
 
-// the window's pair list (the loose fields prow / pairs / jsec / cost64 / P of same_window): read off the window, put in its place
-inline PairList list_of(const same_window *w) {
-    PairList l;
-    l.prow = w->prow; l.pairs = w->pairs; l.jsec = w->jsec; l.cost64 = w->cost64; l.P = w->P;
-    return l;
-}
-inline void turn_to(same_window *w, const PairList &l) {
-    w->prow = l.prow;
-    w->pairs = l.pairs;
-    w->jsec = l.jsec;
-    w->cost64 = l.cost64;
-    w->P = l.P;
-}
-// the window's arrays a caller's triangulation replaces (same_window::Staged): read off the window, put in their place
-inline same_window::Staged staged_of(const same_window *w) {
-    same_window::Staged s;
-    s.counts = w->counts; s.ua = w->ua; s.rows_ua = w->rows_ua; s.type_c = w->type_c;
-    s.axy_c = w->axy_c; s.size_c = w->size_c; s.n_ua = w->n_ua; s.list = list_of(w);
-    return s;
-}
-inline void turn_to(same_window *w, const same_window::Staged &s) {
-    w->counts = s.counts;
-    w->ua = s.ua;
-    w->rows_ua = s.rows_ua;
-    w->type_c = s.type_c;
-    w->axy_c = s.axy_c;
-    w->size_c = s.size_c;
-    w->n_ua = s.n_ua;
-    turn_to(w, s.list);
-}
-// THE PAIR LIST AS STAGED: the list before the priority prune filtered it and before the caller's removal took the unconstrained nodes'
-// rows (in that order: the prune's source is the older one); the window's own list where neither ran.  A k-NN prefix IS a staged list
-// (it resets both).  It is what SAME_WINDOW_STAGED_PAIRS hands out, and its reference rows (jsec, P of them) are the frame the model's
-// reference limits are read over: the frame is the prune's, src/same.py:1055-1085 does not compact the reference side again.
-inline PairList as_staged(const same_window *w) { return w->prio_ok ? w->pr : w->caller_ok ? w->st0.list : list_of(w); }
-
-// The two steps the calls share that leave a window "as a stage call at k leaves it" (the k-NN prefix, window_knn_prefix.hip; the recost,
-// window_recost.hip).
-// hold_caller: a window same_window_caller_tris compacted goes back to the stage call's arrays (st0), the caller's work HELD for
-// same_window_caller_pairs; -> the bytes of the pinned block's head the call has to bring back (64: the counts; a window turned back:
-// the staged counts, XY and rows again, its pinned block holds the compacted ones)
-inline size_t hold_caller(same_window *w) {
-    size_t back = 64;
-    if (w->caller_ok) {
-        w->held.cs = staged_of(w);
-        turn_to(w, w->st0);
-        w->held.on = 1;
-        back = w->held.back_bytes;
-    }
-    w->caller_sel = w->caller_ok = 0;             // (selected but left as staged -- a cosine at the threshold -- : nothing is held)
-    return back;
-}
-// staged_at: the window's pair list is `l`, as a stage call at k leaves it: nothing derived from an earlier list holds any more
-// (as_staged: `l`)
-inline void staged_at(same_window *w, int k, const PairList &l) {
-    turn_to(w, l);
-    w->k = k;
-    w->prio_ok = 0;
-    w->pr = PairList{};
-    w->filtered = w->finished = 0;
-    w->Tr = 0;
-}
-
 // section.hip
 int knn_index_for(same_ctx *ctx, const same_section *ref, double radius, std::shared_ptr<same_knn_index> *out);
 Cover cover_of(const same_section *s, const double *box);
@@ -526,6 +429,61 @@ int for_each_group(std::vector<Plan> &plans, const std::vector<int> &live, F &&f
         rc = fn(pps, live.data() + g, n_g);
     }
     return rc;
+}
+
+// The two calls that leave windows "as a stage call at k leaves them" without staging them (k-NN prefix, recost) are this one batch:
+// every window's compaction by a caller's triangulation turned back and held; plan(w, &plan, &live) says whether the window needs a
+// launch and plans it; launch(plans, n) enqueues a group's kernels; every live window's count block -- a window turned back: the staged
+// counts, XY and rows, its pinned block holds the compacted ones -- goes into the head of its pinned block with the group's launch, a
+// window only turned back gets its by the copy engine; ONE wait, and only if anything was enqueued; derived(w, plan, &list) then checks
+// the counts that came back for a live window and names the list its kernels wrote (P: count word 3).  Every window ends staged_at k
+// (0: its own staged k) with that list, or the list as the stage call put it, and reports its four counts.
+template <class Plan, class PlanFn, class LaunchFn, class DerivedFn>
+int restage_batch(same_ctx *ctx, same_window *const *windows, int n_windows, int k, const char *what, int64_t *out_counts, PlanFn &&plan,
+                  LaunchFn &&launch, DerivedFn &&derived) {
+    std::vector<Plan> plans((size_t)n_windows);
+    std::vector<char> was_turned((size_t)n_windows), is_live((size_t)n_windows, 0);
+    for (int i = 0; i < n_windows; ++i) was_turned[(size_t)i] = windows[i]->hold_caller();
+    std::vector<int> live, turned;                // turned: turned back, no launch -- only their pinned blocks are to restore
+    int rc = SAME_OK;
+    for (int i = 0; i < n_windows && rc == SAME_OK; ++i) {
+        bool needs = false;
+        rc = plan(windows[i], &plans[(size_t)i], &needs);
+        if (rc == SAME_OK && needs) live.push_back(i), is_live[(size_t)i] = 1;
+    }
+    for (int i = 0; i < n_windows; ++i)
+        if (!is_live[(size_t)i] && was_turned[(size_t)i]) turned.push_back(i);
+    auto hand_back = [&](const int *at, int n_g, bool engine) {
+        Back bk[SAME_LAUNCH_WINDOWS];
+        for (int q = 0; q < n_g; ++q) {
+            same_window *w = windows[at[q]];
+            bk[q] = Back{w, w->cur.counts, was_turned[(size_t)at[q]] ? w->held.back_bytes : 64};
+        }
+        return copy_back_group(ctx, bk, n_g, what, engine);
+    };
+    if (rc == SAME_OK)
+        rc = for_each_group(plans, live, [&](Plan *const *pps, const int *at, int n_g) {
+            SAME_TRY(launch(pps, n_g));
+            return hand_back(at, n_g, false);
+        });
+    if (rc == SAME_OK) rc = for_each_group(plans, turned, [&](Plan *const *, const int *at, int n_g) { return hand_back(at, n_g, true); });
+    if (rc != SAME_OK) {                          // (a window turned back above: its pinned block may still be the compacted one)
+        live.insert(live.end(), turned.begin(), turned.end());
+        return fail_batch(ctx, windows, live, rc);
+    }
+    if (!live.empty() || !turned.empty()) SAME_WAIT(ctx);
+    std::vector<PairList> lists((size_t)n_windows);
+    for (int i : live) {
+        SAME_TRY(derived(windows[i], plans[(size_t)i], &lists[(size_t)i]));
+        lists[(size_t)i].P = (int64_t) static_cast<const unsigned long long *>(windows[i]->host)[3];
+    }
+    for (int i = 0; i < n_windows; ++i) {
+        same_window *w = windows[i];
+        w->staged_at(k ? k : w->k_staged, is_live[(size_t)i] ? lists[(size_t)i] : w->sk);
+        static_cast<unsigned long long *>(w->host)[3] = (unsigned long long)w->cur.list.P;     // the count block's host copy: the list's
+        report_counts(w, out_counts + 4 * i);
+    }
+    return SAME_OK;
 }
 
 // The three calls that derive a pair list from a pair list (priority prune, k-NN prefix, caller pairs) plan alike: the kernels' argument

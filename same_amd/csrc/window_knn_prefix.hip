@@ -8,16 +8,12 @@
 //                  number, its reference's section row and its cost -- copied, never recomputed -- into a SECOND set of arrays (the
 //                  window's `kpre` buffer); the window's pointers are turned to them.
 // The aligned side is untouched, so a triangulation held for the window stays valid.  The list as staged stays where the stage call put it
-// (same_window::sk): every prefix is derived from it, and a prefix at the staged k turns the window back to it without a launch.  The
-// window after the call is the one a stage call at k' leaves: what reads "the pair list as staged" (win::as_staged, a priority prune
-// that follows) reads the prefix; an earlier priority prune's result no longer holds.
-// A window same_window_caller_tris has compacted (either form of that call) is first turned back to the stage call's arrays (st0: the
-// aligned side as staged, its count block, and in the pinned block the staged counts, XY and rows again); the caller's work -- node mask,
-// renumbering, compacted aligned side, renumbered triangles -- stays in the window's `caller` buffer, HELD (same_window::Held), and
-// same_window_caller_pairs (window_caller.hip) pushes the cut list through the held mask.  The two steps are two calls, not one fused
-// kernel, because the staged prefix must exist as a list of its own: the frame of the _cap calls' reference limits,
-// SAME_WINDOW_STAGED_PAIRS and `ref_idx` are read over the pair list AS STAGED AT THAT k -- rows of removed nodes included -- not over
-// the compacted one, and a priority prune may come between the two.
+// (win::State::sk): every prefix is derived from it, and a prefix at the staged k turns the window back to it without a launch.  What the
+// call leaves and invalidates -- the window a stage call at k' leaves; a window same_window_caller_tris compacted turned back first, the
+// caller's work HELD for same_window_caller_pairs -- is the knn_prefix row of window_state.h's table.  Turning back and pushing the cut
+// list through the held mask are two calls, not one fused kernel, because the staged prefix must exist as a list of its own: the frame of
+// the _cap calls' reference limits, SAME_WINDOW_STAGED_PAIRS and `ref_idx` are read over the pair list AS STAGED AT THAT k -- rows of
+// removed nodes included -- not over the compacted one, and a priority prune may come between the two.
 #include "window_internal.h"
 
 namespace {
@@ -72,7 +68,7 @@ using PrefixPlan = ListPlan<PrefixArgs>;
 // One window's `kpre` buffer laid out; no launch.
 int prepare_prefix(same_window *w, int k, PrefixPlan *pp) {
     same_ctx *ctx = w->ctx;
-    const int64_t n = w->n_ua, P0 = w->sk.P, cap = std::min<int64_t>(P0, n * (int64_t)k);
+    const int64_t n = w->cur.n_ua, P0 = w->sk.P, cap = std::min<int64_t>(P0, n * (int64_t)k);
     PrefixArgs &a = pp->a;
     a = PrefixArgs{};
     size_t zero_bytes = 0;
@@ -92,7 +88,7 @@ int prepare_prefix(same_window *w, int k, PrefixPlan *pp) {
     a.cap = cap;
     a.k = k;
     a.src = w->sk;
-    a.counts = w->counts;
+    a.counts = w->cur.counts;
     return SAME_OK;
 }
 
@@ -116,76 +112,23 @@ int same_window_knn_prefix(same_window *const *windows, int n_windows, int k, in
     REQUIRE(ctx, out_counts && k >= 1);
     for (int i = 0; i < n_windows; ++i) {
         const same_window *w = windows[i];
-        REQUIRE(ctx, w->staged >= 1 && k <= w->k_staged);
+        REQUIRE(ctx, w->may_prefix(k));
     }
     SAME_TRY(same_use(ctx));
-    // a compacted window: back to the stage call's arrays, the caller's work held.  Its pinned block holds the compacted counts, XY and
-    // rows: the staged ones take their place again below (`back`: what comes back per window)
-    std::vector<size_t> back((size_t)n_windows, 64);
-    for (int i = 0; i < n_windows; ++i) back[(size_t)i] = hold_caller(windows[i]);
-    std::vector<PrefixPlan> plans((size_t)n_windows);
-    std::vector<int> live;
-    int rc = SAME_OK;
-    for (int i = 0; i < n_windows && rc == SAME_OK; ++i) {
-        same_window *w = windows[i];
-        // no pairs: every k leaves the same (empty) list; the staged k: the list as staged, no launch
-        if (w->staged != 2 || w->sk.P == 0 || w->n_ua == 0 || k == w->k_staged) continue;
-        rc = prepare_prefix(w, k, &plans[(size_t)i]);
-        if (rc == SAME_OK) live.push_back(i);
-    }
-    std::vector<int> turned;                      // turned back without a launch: only their pinned blocks are to restore
-    {
-        size_t at = 0;
-        for (int i = 0; i < n_windows; ++i) {
-            if (at < live.size() && live[at] == i) { ++at; continue; }
-            if (back[(size_t)i] > 64) turned.push_back(i);
-        }
-    }
-    // ONE wait for the batch: per group the zeroing and the two kernels, then every window's count block (a window turned back: the
-    // staged counts, XY and rows) into the head of its pinned block; the windows turned back without a launch by a copy each
-    auto hand_back = [&](const int *at, int n_g, bool engine) {
-        Back bk[SAME_LAUNCH_WINDOWS];
-        for (int q = 0; q < n_g; ++q) bk[q] = Back{windows[at[q]], windows[at[q]]->counts, back[(size_t)at[q]]};
-        return copy_back_group(ctx, bk, n_g, "k-NN prefix copy back", engine);
-    };
-    if (rc == SAME_OK)
-        rc = for_each_group(plans, live, [&](PrefixPlan *const *pps, const int *at, int n_g) {
-            SAME_TRY(launch_prefix(ctx, pps, n_g));
-            return hand_back(at, n_g, false);
+    return restage_batch<PrefixPlan>(
+        ctx, windows, n_windows, k, "k-NN prefix copy back", out_counts,
+        [&](same_window *w, PrefixPlan *pp, bool *needs) {
+            // no pairs: every k leaves the same (empty) list; the staged k: the list as staged, no launch
+            *needs = w->pairs_possible() && w->sk.P != 0 && w->cur.n_ua != 0 && k != w->k_staged;
+            return *needs ? prepare_prefix(w, k, pp) : SAME_OK;
+        },
+        [&](PrefixPlan *const *pps, int n_g) { return launch_prefix(ctx, pps, n_g); },
+        [&](const same_window *w, const PrefixPlan &pp, PairList *cut) {
+            const unsigned long long *tot = static_cast<const unsigned long long *>(w->host);
+            REQUIRE(ctx, (int64_t)tot[3] >= pp.a.n && (int64_t)tot[3] <= pp.a.cap && (int64_t)tot[2] == pp.a.n);
+            *cut = pp.a.dst;
+            return SAME_OK;
         });
-    if (rc == SAME_OK) rc = for_each_group(plans, turned, [&](PrefixPlan *const *, const int *at, int n_g) { return hand_back(at, n_g, true); });
-    if (rc != SAME_OK) {                          // (a window turned back above: its pinned block may still be the compacted one)
-        std::vector<int> touched(live);
-        touched.insert(touched.end(), turned.begin(), turned.end());
-        return fail_batch(ctx, windows, touched, rc);
-    }
-    if (!live.empty() || !turned.empty()) SAME_WAIT(ctx);
-    for (int i : live) {
-        const same_window *w = windows[i];
-        const PrefixArgs &a = plans[(size_t)i].a;
-        const unsigned long long *tot = static_cast<const unsigned long long *>(w->host);
-        REQUIRE(ctx, (int64_t)tot[3] >= a.n && (int64_t)tot[3] <= a.cap && (int64_t)tot[2] == a.n);
-    }
-    size_t at = 0;
-    for (int i = 0; i < n_windows; ++i) {
-        same_window *w = windows[i];
-        const bool derived = at < live.size() && live[at] == i;
-        if (derived) {
-            PairList cut = plans[(size_t)i].a.dst;
-            cut.P = (int64_t) static_cast<const unsigned long long *>(w->host)[3];
-            staged_at(w, k, cut);
-            ++at;
-        } else {
-            staged_at(w, k, w->sk);
-            static_cast<unsigned long long *>(w->host)[3] = (unsigned long long)w->sk.P;     // the count block's host copy: the list's
-        }
-        int64_t *counts = out_counts + 4 * i;
-        counts[0] = w->n_m;
-        counts[1] = w->n_r;
-        counts[2] = w->n_ua;
-        counts[3] = w->P;
-    }
-    return SAME_OK;
 }
 
 }  // extern "C"

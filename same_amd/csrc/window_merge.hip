@@ -437,8 +437,8 @@ int same_window_collect(same_window *const *windows, int n_windows, same_merge_a
     REQUIRE(ctx, a && a->ctx == ctx && trims && window_ids && plan_pos && !a->resolved);
     int64_t add = 0;
     for (int i = 0; i < n_windows; ++i) {
-        REQUIRE(ctx, windows[i]->finished && windows[i]->staged == 2 && window_ids[i] >= 0);
-        add += windows[i]->n_ua;
+        REQUIRE(ctx, windows[i]->has_results() && window_ids[i] >= 0);
+        add += windows[i]->cur.n_ua;
     }
     REQUIRE(ctx, a->bound + add < ((int64_t)1 << 30));
     SAME_TRY(same_use(ctx));
@@ -450,7 +450,7 @@ int same_window_collect(same_window *const *windows, int n_windows, same_merge_a
     }
     a->bound += add;
     int64_t most = 0;
-    for (int i = 0; i < n_windows; ++i) most = std::max(most, windows[i]->n_ua);
+    for (int i = 0; i < n_windows; ++i) most = std::max(most, windows[i]->cur.n_ua);
     const int64_t stride = (int64_t)(scan::status_bytes(most) / 8);          // look-back words of one window
     SAME_TRY(ensure(ctx, a->scan_words, (size_t)stride * 8 * SAME_LAUNCH_WINDOWS));
     unsigned long long *words = static_cast<unsigned long long *>(a->scan_words.p);
@@ -460,10 +460,10 @@ int same_window_collect(same_window *const *windows, int n_windows, same_merge_a
         int64_t most_g = 0;
         for (int i = g; i < n_windows && i < g + SAME_LAUNCH_WINDOWS; ++i) {
             const same_window *w = windows[i];
-            if (w->n_ua == 0) continue;
+            if (w->cur.n_ua == 0) continue;
             const double *t = trims + 4 * i;
-            b.w[n_g++] = CollectArgs{w->match_row, w->pflag, w->rows_ua, w->axy_c, w->n_ua, t[0], t[1], t[2], t[3], window_ids[i], plan_pos[i]};
-            most_g = std::max(most_g, w->n_ua);
+            b.w[n_g++] = CollectArgs{w->match_row, w->pflag, w->cur.rows_ua, w->cur.axy_c, w->cur.n_ua, t[0], t[1], t[2], t[3], window_ids[i], plan_pos[i]};
+            most_g = std::max(most_g, w->cur.n_ua);
         }
         if (!n_g) continue;
         const dim3 grid(scan::blocks_for(most_g), (unsigned)n_g);

@@ -13,7 +13,7 @@
 //   scatter        one thread per pair: a kept pair goes to new_prow[row] + rank (a winner's nearest to new_prow[row]), with its reference
 //                  row and its cost, into a SECOND set of arrays (the window's `prio` buffer); the window's pointers are turned to them.
 // The aligned side is untouched (every kept cell keeps a pair) and the reference side is NOT compacted again (:78 returns the frames it
-// got): the pair list as staged stays where it is and stays what win::as_staged answers (window_internal.h).  The batch is driven by
+// got): the pair list as staged stays where it is and stays what as_staged() answers (window_state.h).  The batch is driven by
 // window_stage.hip's driver (window_internal.h).
 #include <climits>
 
@@ -119,7 +119,7 @@ using PrioPlan = ListPlan<PrioArgs>;
 // One window's `prio` buffer laid out; no launch.
 int prepare_priority(same_window *w, PrioPlan *pp) {
     same_ctx *ctx = w->ctx;
-    const int64_t n = w->n_ua, P0 = w->P, n_r = w->n_r;
+    const int64_t n = w->cur.n_ua, P0 = w->cur.list.P, n_r = w->n_r;
     PrioArgs &a = pp->a;
     a = PrioArgs{};
     size_t zero_bytes = 0;
@@ -140,13 +140,13 @@ int prepare_priority(same_window *w, PrioPlan *pp) {
     pp->zero = ZeroArgs{{w->prio.p, nullptr}, {zero_bytes, 0}};
     a.n = n;
     a.n_r = n_r;
-    a.src = list_of(w);
-    a.rows_ua = w->rows_ua;
-    a.axy = w->axy_c;
+    a.src = w->cur.list;
+    a.rows_ua = w->cur.rows_ua;
+    a.axy = w->cur.axy_c;
     a.ref_xy = w->ref->xy;
     a.code_m = w->mov->label_codes;
     a.code_r = w->ref->label_codes;
-    a.counts = w->counts;
+    a.counts = w->cur.counts;
     return SAME_OK;
 }
 
@@ -192,9 +192,9 @@ int same_window_priority_pairs(same_window *const *windows, int n_windows, int64
     REQUIRE(ctx, out_counts);
     for (int i = 0; i < n_windows; ++i) {
         const same_window *w = windows[i];
-        REQUIRE(ctx, w->staged >= 1 && w->mov && w->ref);
+        REQUIRE(ctx, w->is_staged() && w->mov && w->ref);
         REQUIRE(ctx, w->mov->label_codes && w->ref->label_codes);
-        REQUIRE(ctx, !w->prio_ok && !w->caller_sel && !w->caller_ok && !w->filtered && !w->finished);
+        REQUIRE(ctx, w->may_prune());
         // the sections' grids as the window was staged over them (a shared hold each: same_section_bin swaps under the exclusive one)
         for (const same_section *sec : {w->mov, w->ref}) {
             same_section *s = const_cast<same_section *>(sec);
@@ -209,7 +209,7 @@ int same_window_priority_pairs(same_window *const *windows, int n_windows, int64
     int rc = SAME_OK;
     for (int i = 0; i < n_windows && rc == SAME_OK; ++i) {
         same_window *w = windows[i];
-        if (w->staged != 2 || w->P == 0 || w->n_ua == 0) continue;       // no pairs: nothing to rank, nothing launched
+        if (!w->pairs_possible() || w->cur.list.P == 0 || w->cur.n_ua == 0) continue;       // no pairs: nothing to rank, nothing launched
         rc = prepare_priority(w, &plans[(size_t)i]);
         if (rc == SAME_OK) live.push_back(i);
     }
@@ -219,7 +219,7 @@ int same_window_priority_pairs(same_window *const *windows, int n_windows, int64
         rc = for_each_group(plans, live, [&](PrioPlan *const *pps, const int *at, int n_g) {
             SAME_TRY(launch_priority(ctx, pps, n_g));
             Back back[SAME_LAUNCH_WINDOWS];
-            for (int q = 0; q < n_g; ++q) back[q] = Back{windows[at[q]], windows[at[q]]->counts, 64};
+            for (int q = 0; q < n_g; ++q) back[q] = Back{windows[at[q]], windows[at[q]]->cur.counts, 64};
             return copy_back_group(ctx, back, n_g, "priority prune copy back");
         });
     if (rc != SAME_OK) return fail_batch(ctx, windows, live, rc);
@@ -232,9 +232,7 @@ int same_window_priority_pairs(same_window *const *windows, int n_windows, int64
         REQUIRE(ctx, P >= a.n && P <= a.src.P && one >= 0 && one <= a.n && (int64_t)tot[2] == a.n);
         PairList left = a.dst;
         left.P = P;
-        w->pr = a.src;                            // the list as staged stays what as_staged() answers
-        turn_to(w, left);
-        w->prio_ok = 1;
+        w->pruned(a.src, left);
         int64_t *counts = out_counts + 4 * i;
         counts[0] = a.src.P;
         counts[1] = P;

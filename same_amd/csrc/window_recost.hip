@@ -2,7 +2,7 @@
 // Of everything a window is made of, only the pair costs read the type columns: the row lists, the radius / k prune, the compaction, the
 // reference numbers and the triangulation are geometry, the triangle filter and the priority prune read type CODES.  A study that changes
 // only the moving frame's type columns (a robustness run over noised types) therefore needs, per variant, not a stage call but the costs
-// of the list as staged (same_window::sk) written again -- with the moving rows read from a types layer (same_types_layer, section.hip)
+// of the list as staged (win::State::sk) written again -- with the moving rows read from a types layer (same_types_layer, section.hip)
 // and everything else where the stage call left it.
 //
 // The value is the stage call's, bit for bit (cost.hip, padded_cost_kernel / padded_cost_lds_kernel):
@@ -18,9 +18,8 @@
 // evaluate the same expression in the same order.
 // The pair count is read on the device (prow[kept cells]); the launch is sized by the host's copy of it.
 //
-// The call leaves every window in the state same_window_knn_prefix at the staged k leaves: the staged list current, no priority prune, a
-// caller's compaction turned back and HELD -- so the sequence of a knn group (prefix, prune, same_window_caller_pairs) runs on it
-// unchanged.  The slots of the stage call's padded candidate costs (the F values cost64 was widened from) are scratch of that call --
+// The call leaves every window in the state same_window_knn_prefix at the staged k leaves (window_state.h's table; the two calls are one
+// skeleton, win::restage_batch) -- so the sequence of a knn group (prefix, prune, same_window_caller_pairs) runs on it unchanged.  The slots of the stage call's padded candidate costs (the F values cost64 was widened from) are scratch of that call --
 // nothing reads them after its scatter -- and are not rewritten.
 #include "window_internal.h"
 
@@ -164,58 +163,26 @@ int same_window_recost(same_window *const *windows, int n_windows, const same_se
     REQUIRE(ctx, !layer || (layer->sec == mov && layer->ctx->device == ctx->device && (mov->T == 0 || mov->n == 0 || layer->types_c)));
     for (int i = 0; i < n_windows; ++i) {
         const same_window *w = windows[i];
-        REQUIRE(ctx, w->staged >= 1 && w->mov == mov && w->ref == ref);
+        REQUIRE(ctx, w->may_recost() && w->mov == mov && w->ref == ref);
     }
     SAME_TRY(same_use(ctx));
-    // a compacted window: back to the stage call's arrays, the caller's work held (as same_window_knn_prefix does)
-    std::vector<size_t> back((size_t)n_windows, 64);
-    for (int i = 0; i < n_windows; ++i) back[(size_t)i] = hold_caller(windows[i]);
-    std::vector<RecostPlan> plans((size_t)n_windows);
-    std::vector<int> live, turned;                // windows with pairs; windows without that were turned back (their pinned blocks to restore)
-    for (int i = 0; i < n_windows; ++i) {
-        same_window *w = windows[i];
-        if (w->staged != 2 || w->sk.P == 0 || w->n_ua == 0) {
-            if (back[(size_t)i] > 64) turned.push_back(i);
-            continue;
-        }
-        plans[(size_t)i].a = RecostArgs{w->n_ua, w->sk.P, w->rows_ua, w->sk, w->counts};
-        live.push_back(i);
-    }
     const void *types_c = layer ? layer->types_c : mov->types_c;
-    // ONE wait for the batch: per group the kernel, then every window's count block (a window turned back: the staged counts, XY and rows)
-    // into the head of its pinned block
-    auto hand_back = [&](const int *at, int n_g, bool engine) {
-        Back bk[SAME_LAUNCH_WINDOWS];
-        for (int q = 0; q < n_g; ++q) bk[q] = Back{windows[at[q]], windows[at[q]]->counts, back[(size_t)at[q]]};
-        return copy_back_group(ctx, bk, n_g, "recost copy back", engine);
-    };
-    int rc = for_each_group(plans, live, [&](RecostPlan *const *pps, const int *at, int n_g) {
-        SAME_TRY(mov->cost_f32 ? launch_recost<float>(ctx, pps, n_g, mov, ref, types_c, dist_ct_coeff)
-                               : launch_recost<double>(ctx, pps, n_g, mov, ref, types_c, dist_ct_coeff));
-        return hand_back(at, n_g, false);
-    });
-    if (rc == SAME_OK) rc = for_each_group(plans, turned, [&](RecostPlan *const *, const int *at, int n_g) { return hand_back(at, n_g, true); });
-    if (rc != SAME_OK) {
-        std::vector<int> touched(live);
-        touched.insert(touched.end(), turned.begin(), turned.end());
-        return fail_batch(ctx, windows, touched, rc);
-    }
-    if (!live.empty() || !turned.empty()) SAME_WAIT(ctx);
-    for (int i : live) {
-        const same_window *w = windows[i];
-        REQUIRE(ctx, (int64_t) static_cast<const unsigned long long *>(w->host)[3] == w->sk.P);
-    }
-    for (int i = 0; i < n_windows; ++i) {
-        same_window *w = windows[i];
-        staged_at(w, w->k_staged, w->sk);
-        static_cast<unsigned long long *>(w->host)[3] = (unsigned long long)w->sk.P;     // the count block's host copy: the list's
-        int64_t *counts = out_counts + 4 * i;
-        counts[0] = w->n_m;
-        counts[1] = w->n_r;
-        counts[2] = w->n_ua;
-        counts[3] = w->P;
-    }
-    return SAME_OK;
+    return restage_batch<RecostPlan>(
+        ctx, windows, n_windows, 0, "recost copy back", out_counts,
+        [&](same_window *w, RecostPlan *pp, bool *needs) {
+            *needs = w->pairs_possible() && w->sk.P != 0 && w->cur.n_ua != 0;
+            if (*needs) pp->a = RecostArgs{w->cur.n_ua, w->sk.P, w->cur.rows_ua, w->sk, w->cur.counts};
+            return SAME_OK;
+        },
+        [&](RecostPlan *const *pps, int n_g) {
+            return mov->cost_f32 ? launch_recost<float>(ctx, pps, n_g, mov, ref, types_c, dist_ct_coeff)
+                                 : launch_recost<double>(ctx, pps, n_g, mov, ref, types_c, dist_ct_coeff);
+        },
+        [&](const same_window *w, const RecostPlan &, PairList *list) {
+            REQUIRE(ctx, (int64_t) static_cast<const unsigned long long *>(w->host)[3] == w->sk.P);
+            *list = w->sk;
+            return SAME_OK;
+        });
 }
 
 }  // extern "C"

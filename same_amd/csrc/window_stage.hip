@@ -423,7 +423,7 @@ int copy_back_group(same_ctx *ctx, const Back *back, int n_w, const char *what, 
 
 int fail_batch(same_ctx *ctx, same_window *const *windows, const std::vector<int> &touched, int rc) {
     (void)hipStreamSynchronize(ctx->stream);
-    for (int i : touched) windows[i]->staged = 0;
+    for (int i : touched) windows[i]->staged = UNSTAGED;
     return rc;
 }
 
@@ -459,18 +459,11 @@ struct StagePlan {
 // (launch_stage).  The caller holds the sections' grid locks.
 int prepare_stage(same_window *w, const same_section *mov, const same_section *ref, const double *box, int k, StagePlan *sp) {
     same_ctx *ctx = w->ctx;
-    w->staged = w->finished = w->filtered = 0;
     w->mov = mov;
     w->ref = ref;
     w->has_type = mov->type_id != nullptr;
     w->cost_f32 = mov->cost_f32;
-    w->k = k;
-    w->n_m = w->n_r = w->n_ua = w->P = w->Tr = 0;
-    w->caller_sel = w->caller_ok = 0;             // the stage call's arrays are the window's again
-    w->held = same_window::Held{};
-    w->prio_ok = 0;                               // ... and its pair list the only one
-    w->pr = PairList{};
-    w->k_staged = k;                              // ... at the k it was staged at (same_window_knn_prefix: w->k is the list's)
+    w->n_m = w->n_r = 0;
     w->bins_m = mov->bins;                        // (the caller holds both grid locks)
     w->bins_r = ref->bins;
     for (int q = 0; q < 4; ++q) w->box[q] = box[q];
@@ -496,9 +489,9 @@ int prepare_stage(same_window *w, const same_section *mov, const same_section *r
         st_cm = scan::arg(cv.scan_words(cap_m));
         st_cr = scan::arg(cv.scan_words(cap_r));
         o_counts = cv.off;                  // counts, kept XY, kept rows: contiguous, they come back in one copy
-        w->counts = cv.pack<unsigned long long>(8);
-        w->axy_c = cv.pack<double>((size_t)cap_m * 2);
-        w->rows_ua = cv.pack<int32_t>((size_t)cap_m);
+        w->cur.counts = cv.pack<unsigned long long>(8);
+        w->cur.axy_c = cv.pack<double>((size_t)cap_m * 2);
+        w->cur.rows_ua = cv.pack<int32_t>((size_t)cap_m);
         back_bytes = cv.off - o_counts;
         merged_m = cv.take<uint32_t>((size_t)cap_m);
         merged_r = cv.take<uint32_t>((size_t)cap_r);
@@ -507,13 +500,13 @@ int prepare_stage(same_window *w, const same_section *mov, const same_section *r
         w->idx = cv.take<int32_t>(slots);
         w->cnt = cv.take<int32_t>((size_t)cap_m);
         cost = cv.take<char>(slots * cs);
-        w->ua = cv.take<int32_t>((size_t)cap_m);
-        w->type_c = cv.take<int32_t>((size_t)cap_m);
-        w->size_c = cv.take<double>((size_t)cap_m);
-        w->prow = cv.take<int32_t>(cm1);
-        w->pairs = cv.take<int32_t>(slots * 2);
-        w->jsec = cv.take<int32_t>(slots);
-        w->cost64 = cv.take<double>(slots);
+        w->cur.ua = cv.take<int32_t>((size_t)cap_m);
+        w->cur.type_c = cv.take<int32_t>((size_t)cap_m);
+        w->cur.size_c = cv.take<double>((size_t)cap_m);
+        w->cur.list.prow = cv.take<int32_t>(cm1);
+        w->cur.list.pairs = cv.take<int32_t>(slots * 2);
+        w->cur.list.jsec = cv.take<int32_t>(slots);
+        w->cur.list.cost64 = cv.take<double>(slots);
         return cv.off;
     };
     SAME_TRY(ensure(ctx, w->stage, lay(Carver())));
@@ -522,11 +515,11 @@ int prepare_stage(same_window *w, const same_section *mov, const same_section *r
     w->host_filter_off = w->host_finish_off + ((finish_back_bytes(cap_m) + 255) & ~size_t(255));     // (n_ua <= cap_m)
     SAME_TRY(ensure_host(w, w->host_filter_off + 256));
     lay(Carver(w->stage.p));
-    w->sk = list_of(w);                           // the list as staged: what a k-NN prefix is derived from (window_knn_prefix.hip; P: collect_stage)
+    w->sk = w->cur.list;                          // the list as staged: what a k-NN prefix is derived from (window_knn_prefix.hip; P: collect_stage)
     // aligned boxes: the merged list IS the row list; whole-section path: its own list is copied in
     w->rows_m = compact_m || !cm.use_runs ? rows_m : reinterpret_cast<int32_t *>(merged_m);
     w->rows_r = compact_r || !cr.use_runs ? rows_r : reinterpret_cast<int32_t *>(merged_r);
-    unsigned long long *dc = w->counts;
+    unsigned long long *dc = w->cur.counts;
 
     sp->zero = ZeroArgs{{w->stage.p, nullptr}, {o_counts + 64, 0}};       // scan words + counts, zeroed with the group's (launch_stage)
     sp->full_m = !cm.use_runs ? cap_m : 0;        // the whole-section path's list and count take their places after that
@@ -562,8 +555,8 @@ int prepare_stage(same_window *w, const same_section *mov, const same_section *r
         sp->knn.idx = w->idx; sp->knn.cnt = w->cnt;
         sp->cost.rows = w->rows_m; sp->cost.dn = dc; sp->cost.cap = cap_m; sp->cost.idx = w->idx; sp->cost.out = cost;
         sp->scatter = ScatterArgs{w->idx, cost, w->cnt, w->rows_m, w->rows_r, mov->xy, mov->size, mov->type_id,
-                                  st_scatter, dc, w->ua, w->rows_ua, w->type_c, w->prow, w->pairs,
-                                  w->jsec, w->axy_c, w->size_c, w->cost64, k, scan::blocks_for(cap_m)};
+                                  st_scatter, dc, w->cur.ua, w->cur.rows_ua, w->cur.type_c, w->cur.list.prow, w->cur.list.pairs,
+                                  w->cur.list.jsec, w->cur.axy_c, w->cur.size_c, w->cur.list.cost64, k, scan::blocks_for(cap_m)};
     } else {
         sp->knn.dn_m = dc; sp->knn.dn_r = dc + 1;     // a window without candidates still names its (zero) counts: its blocks read them and leave
         sp->cost.dn = dc;
@@ -601,11 +594,11 @@ int launch_stage(same_ctx *ctx, same_window *const *ws, StagePlan *const *sps, i
         same_window *w = ws[q];
         if (sps[q]->full_m) {
             SAME_COPY(ctx, w->rows_m, w->full_m.p, (size_t)sps[q]->full_m * 4, hipMemcpyDeviceToDevice);
-            SAME_LAUNCH(ctx, set_count_kernel, dim3(1), dim3(1), 0, w->counts, (unsigned long long)sps[q]->full_m);
+            SAME_LAUNCH(ctx, set_count_kernel, dim3(1), dim3(1), 0, w->cur.counts, (unsigned long long)sps[q]->full_m);
         }
         if (sps[q]->full_r) {
             SAME_COPY(ctx, w->rows_r, w->full_r.p, (size_t)sps[q]->full_r * 4, hipMemcpyDeviceToDevice);
-            SAME_LAUNCH(ctx, set_count_kernel, dim3(1), dim3(1), 0, w->counts + 1, (unsigned long long)sps[q]->full_r);
+            SAME_LAUNCH(ctx, set_count_kernel, dim3(1), dim3(1), 0, w->cur.counts + 1, (unsigned long long)sps[q]->full_r);
         }
     }
     if (max_rows) SAME_LAUNCH(ctx, window_rows_kernel, dim3(max_rows, nw), dim3(256), 0, rb);
@@ -628,14 +621,11 @@ int collect_stage(same_window *w, const StagePlan &sp, int64_t *out_counts) {
     const unsigned long long *tot = reinterpret_cast<const unsigned long long *>(w->host);
     w->n_m = (int64_t)tot[0];
     w->n_r = (int64_t)tot[1];
-    w->n_ua = (int64_t)tot[2];
-    w->P = w->sk.P = (int64_t)tot[3];
-    REQUIRE(ctx, w->n_m <= w->cap_m && w->n_r <= w->cap_r && w->n_ua <= w->n_m && w->P <= (int64_t)sp.slots);
-    out_counts[0] = w->n_m;
-    out_counts[1] = w->n_r;
-    out_counts[2] = w->n_ua;
-    out_counts[3] = w->P;
-    w->staged = (w->n_m && w->n_r) ? 2 : 1;      // no pairs possible: the caller raises what run_same raises (src/same.py:1003)
+    w->cur.n_ua = (int64_t)tot[2];
+    w->cur.list.P = w->sk.P = (int64_t)tot[3];
+    REQUIRE(ctx, w->n_m <= w->cap_m && w->n_r <= w->cap_r && w->cur.n_ua <= w->n_m && w->cur.list.P <= (int64_t)sp.slots);
+    report_counts(w, out_counts);
+    w->staged = (w->n_m && w->n_r) ? STAGED : STAGED_NO_PAIRS;      // no pairs possible: the caller raises what run_same raises (src/same.py:1003)
     return SAME_OK;
 }
 
@@ -651,7 +641,7 @@ int same_window_stage(same_window *const *windows, int n_windows, const same_sec
     REQUIRE(ctx, mov->T == ref->T && mov->cost_f32 == ref->cost_f32 && k >= 1 && k <= SAME_MAX_KNN && radius >= 0.0);
     SAME_TRY(same_use(ctx));
     for (int i = 0; i < 4 * n_windows; ++i) out_counts[i] = 0;
-    for (int i = 0; i < n_windows; ++i) windows[i]->staged = windows[i]->finished = windows[i]->filtered = windows[i]->dd_ok = 0;
+    for (int i = 0; i < n_windows; ++i) windows[i]->begin_stage(k);
     std::shared_ptr<same_knn_index> ix;           // held until this call's kernels have finished (both returns below wait first)
     SAME_TRY(knn_index_for(ctx, ref, radius, &ix));
     // both sections' grids stay as they are until this call's kernels are enqueued (same_section_bin waits for this, then for the device)
@@ -672,7 +662,7 @@ int same_window_stage(same_window *const *windows, int n_windows, const same_sec
     if (rc == SAME_OK)
         rc = for_each_group(plans, live, [&](StagePlan *const *sps, const int *at, int n_g) {
             Back back[SAME_LAUNCH_WINDOWS];
-            for (int q = 0; q < n_g; ++q) back[q] = Back{windows[at[q]], windows[at[q]]->counts, sps[q]->back_bytes};
+            for (int q = 0; q < n_g; ++q) back[q] = Back{windows[at[q]], windows[at[q]]->cur.counts, sps[q]->back_bytes};
             return copy_back_group(ctx, back, n_g, "stage copy back");
         });
     if (rc != SAME_OK) return fail_batch(ctx, windows, live, rc);
@@ -684,28 +674,28 @@ int same_window_stage(same_window *const *windows, int n_windows, const same_sec
 int same_window_fetch(same_window *w, int what, void *out, int64_t bytes) {
     if (!w) return SAME_EINVAL;
     same_ctx *ctx = w->ctx;
-    REQUIRE(ctx, w->staged >= 1 && bytes >= 0 && (bytes == 0 || out));
+    REQUIRE(ctx, w->is_staged() && bytes >= 0 && (bytes == 0 || out));
     SAME_TRY(same_use(ctx));
     const char *h = static_cast<const char *>(w->host);
     const void *dev = nullptr;
     const void *host = nullptr;
     int64_t want = 0;
-    const int64_t n_m = w->n_m, n_r = w->n_r, n_ua = w->n_ua, P = w->P, Tr = w->Tr;
-    const bool full = w->staged == 2;
+    const int64_t n_m = w->n_m, n_r = w->n_r, n_ua = w->cur.n_ua, P = w->cur.list.P, Tr = w->Tr;
+    const bool full = w->pairs_possible();
     switch (what) {
     case SAME_WINDOW_ALIGNED_XY: want = n_ua * 16; host = h + 64; REQUIRE(ctx, full || n_ua == 0); break;
     case SAME_WINDOW_ALIGNED_ROWS: want = n_ua * 4; host = h + 64 + (size_t)w->cap_m * 16; REQUIRE(ctx, full || n_ua == 0); break;
     case SAME_WINDOW_ROWS_M: want = n_m * 4; dev = w->rows_m; break;
     case SAME_WINDOW_ROWS_R: want = n_r * 4; dev = w->rows_r; break;
-    case SAME_WINDOW_PAIRS: want = P * 8; dev = w->pairs; break;
-    case SAME_WINDOW_COSTS: want = P * 8; dev = w->cost64; break;
-    case SAME_WINDOW_KEPT: want = n_ua * 4; dev = w->ua; break;
+    case SAME_WINDOW_PAIRS: want = P * 8; dev = w->cur.list.pairs; break;
+    case SAME_WINDOW_COSTS: want = P * 8; dev = w->cur.list.cost64; break;
+    case SAME_WINDOW_KEPT: want = n_ua * 4; dev = w->cur.ua; break;
     case SAME_WINDOW_SIGNS: want = Tr; dev = w->sign; REQUIRE(ctx, w->finished); break;
     case SAME_WINDOW_WEIGHTS: want = Tr * 8; dev = w->weight; REQUIRE(ctx, w->finished); break;
     case SAME_WINDOW_MATCH: want = n_ua * 4; dev = w->match_loc; REQUIRE(ctx, w->finished); break;
-    case SAME_WINDOW_TRIANGLES: want = Tr * 12; dev = w->tris.p; REQUIRE(ctx, w->finished || w->filtered); break;
+    case SAME_WINDOW_TRIANGLES: want = Tr * 12; dev = w->tris.p; REQUIRE(ctx, w->has_triangles()); break;
     case SAME_WINDOW_CALLER_TRIANGLES: want = w->n_sel * 12; dev = w->sel_tris; REQUIRE(ctx, w->caller_sel); break;
-    case SAME_WINDOW_STAGED_PAIRS: want = as_staged(w).P * 8; dev = as_staged(w).pairs; break;
+    case SAME_WINDOW_STAGED_PAIRS: want = w->as_staged().P * 8; dev = w->as_staged().pairs; break;
     default: REQUIRE(ctx, !"unknown same_window_fetch selector");
     }
     REQUIRE(ctx, bytes == want);

@@ -235,9 +235,14 @@ int same_check_alignment(same_ctx *ctx, const double *qxy, int64_t n_q, const in
  * same_collapse_candidates replaces the per-triangle work of one collapse iteration
  * (src/metacell_utils.py:233-260 validity, :393-431 candidate test and priority):
  * out_flag bit0 = valid (no edge > r_max, no corner angle < min_angle, as a cosine threshold),
- * bit1 = collapsible (valid, one cell type, size sum <= max_size); out_perim = priority;
- * out_total = size sum.  same_greedy_disjoint replaces the sort + vertex-disjoint scan of
- * :438-449 on items[M][3] with keys[M] (ties by item index), out_selected[M]. */
+ * bit1 = collapsible (valid, one cell type, not size sum > max_size: a NaN sum or max_size
+ * passes, as it does in the reference); out_perim = priority; out_total = size sum.  On NaN the
+ * validity rule is the reference's Python max(edge1, edge2, edge3) and min(angle1, angle2,
+ * angle3): the first operand stays unless a later one compares greater (less), so a leading NaN
+ * wins (the test then passes) and later NaNs are skipped.  same_greedy_disjoint replaces the
+ * sort + vertex-disjoint scan of :438-449 on items[M][3] with keys[M] (ties by item index; +0.0
+ * and -0.0 are one key), out_selected[M], out_rounds (may be NULL) = rounds that took an item.
+ * NaN keys are outside the contract: the reference's sort on them is not an order. */
 int same_collapse_candidates(same_ctx *ctx, const double *xy, int64_t n, const int32_t *tris,
                              int64_t Tr, int rmax_enabled, double r_max, int angle_enabled,
                              double cos_thr, const int32_t *type_id, const double *size,

@@ -18,6 +18,7 @@
 namespace {
 
 __device__ __forceinline__ unsigned long long cost_key(double v) {  // monotone u64 key of a double
+    v = v == 0.0 ? 0.0 : v;  // the two zeros are one key: the reference's sort finds them equal and keeps list order
     const unsigned long long u = (unsigned long long)__double_as_longlong(v);
     return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
 }
@@ -113,7 +114,8 @@ __global__ __launch_bounds__(256) void greedy_select_kernel(
 // -- float key in the high half, inverted pair index in the low half -- so a single atomicMax per end point finds the minimum cost
 // AND the first pair among equal costs: a round is two launches instead of three.  Same order, same matching as the generic rounds.
 __device__ __forceinline__ unsigned long long packed_key(double c, int64_t p) {
-    const unsigned u = __float_as_uint((float)c);
+    const float f = (float)c;
+    const unsigned u = __float_as_uint(f == 0.0f ? 0.0f : f);  // the two zeros are one key, as in cost_key
     const unsigned k = (u >> 31) ? ~u : (u | 0x80000000u);      // monotone key of the float
     return ((unsigned long long)(~k) << 32) | (unsigned long long)(~(unsigned)p);   // larger word = smaller (cost, index); never 0: p < 2^32 - 1
 }
@@ -226,7 +228,8 @@ __global__ __launch_bounds__(256) void tri_flip_stats_kernel(
 //   perimeter : |ab| + |bc| + |ca| with 1-D np.linalg.norm (= sqrt(ddot) = sqrt(fma(y,y,x*x)))
 // The angle rule is a cosine threshold as in tri.hip.  compute_angle here has no zero-length guard
 // (:236-238): a zero side gives cos = 0/0 = NaN; Python's min(angle1, angle2, angle3) keeps a NaN
-// that comes first and skips later ones, which is reproduced literally.
+// that comes first and skips later ones, which is reproduced literally -- and so is Python's
+// max(edge1, edge2, edge3) of the r_max rule, which a NaN corner reaches.
 __device__ __forceinline__ double nrm2(double x, double y) { return __builtin_sqrt(__builtin_fma(y, y, x * x)); }
 __device__ __forceinline__ double corner_cos_raw(double2_t p1, double2_t p2, double2_t p3) {  // corner at p2
     const double v1x = p1.x - p2.x, v1y = p1.y - p2.y, v2x = p3.x - p2.x, v2y = p3.y - p2.y;
@@ -247,8 +250,9 @@ __global__ __launch_bounds__(256) void collapse_candidates_kernel(
     bool valid = true;
     if (rmax_enabled) {  // is_triangle_valid, :247-252
         const double e1 = nrm2(p2.x - p1.x, p2.y - p1.y), e2 = nrm2(p3.x - p2.x, p3.y - p2.y), e3 = nrm2(p1.x - p3.x, p1.y - p3.y);
-        double mx = e1 > e2 ? e1 : e2;
-        mx = mx > e3 ? mx : e3;
+        double mx = e1;  // Python max(): the first stays unless a later one compares greater, so a leading NaN wins and later NaNs are skipped
+        if (e2 > mx) mx = e2;
+        if (e3 > mx) mx = e3;
         if (mx > r_max) valid = false;
     }
     if (valid && angle_enabled) {  // :255-260

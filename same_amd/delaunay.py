@@ -27,8 +27,9 @@ windows submitted, refused and re-finished, each window once.
 Every route is a `Triangulator` -- `QHULL` (the helper pool), windows.TriangulationCache, `NativeTriangulator`, `DeviceTriangulator`
 -- and hands out `Ticket`s; that protocol is all windows.iter_device_windows knows of them.  `triangulator_for(optim_params)` picks the
 route of a pass.  tests/test_delaunay_cpu.py (sets of triangles against scipy, fallbacks, tickets), tests/test_gpu_delaunay.py and
-tests/test_gpu_device_delaunay.py (tables of every route bit-identical; forced ties), tools/delaunay_margin.py (where Qhull itself
-stops being exact).
+tests/test_gpu_device_delaunay.py (tables of every route bit-identical; forced ties), tests/test_gpu_delaunay_library.py (the two
+device calls against their host statement, array equal, on hostile sets), tools/delaunay_margin.py (where Qhull itself stops being
+exact).
 """
 import os
 import threading

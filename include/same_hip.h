@@ -60,7 +60,7 @@ typedef struct same_sweep same_sweep; /* resident state of one lazy-constraint s
  * part 2  DEVICE-RESIDENT forms (operands already in HBM; enqueue     same_dense_cost_*_dev, same_knn_prune_dev, same_knn_index_*,
  *         only unless noted)                                          same_knn_prune_indexed_dev, same_padded_cost_*_dev, same_tri_*_dev,
  *                                                                     same_area_flip_dev, same_xyorder_sweep_dev, same_orient_*_dev, same_first_candidate_dev
- * part 3  WINDOW path, sections resident (BASELINE cfg 5)             same_section_*, same_window_*, same_merge_acc_*, same_delaunay2d (host),
+ * part 3  WINDOW path, sections resident (BASELINE cfg 5)             same_section_*, same_window_*, same_merge_acc_*, same_members_*, same_delaunay2d (host),
  *                                                                     same_delaunay_filtered
  * part 4  COMM: RCCL collectives between the ranks' contexts          same_comm_*, same_allgather_dev*, same_allreduce_dev
  * Every declaration cites the reference lines it replaces (file:line into the reference tree).
@@ -814,6 +814,42 @@ int same_host_free(same_ctx *ctx, void *ptr);
 int same_merge_acc_score(same_merge_acc *acc, const same_section *moving, const same_section *ref,
                          const same_caller_tris *tris /* may be NULL: no triangle counts */, int ignore_same_type, int node_local,
                          double majority_threshold, int64_t min_flips, int64_t *out_counts /* [8] */);
+/* A merged MetaCell result unpacked to cells (csrc/window_unpack.hip; src/metacell_utils.py:564-766, unpack_metacell_matches with
+ * metacells on both sides), without its table: after same_merge_acc_finish, on the final rows where they are and in their order.
+ *   same_members_create: the members of `section`'s rows as CSR -- row i owns members [off[i], off[i+1]); per member its XY (the
+ *   ORIGINAL cell's, float64) and its label code (joint codes of the two original frames' labels; a negative code equals nothing).
+ *   Uploaded once on the section's context, resident on its device, read-only and shared by the worker contexts like same_caller_tris;
+ *   destroy it before its section.  SAME_EINVAL unless off[0] == 0, off is non-decreasing, off[n_rows] == m < 2^31 and no row has more
+ *   than SAME_ASSIGN_MAX_MEMBERS members.
+ *   same_merge_acc_unpack: a final row (a, r) with na moving and nr reference members yields na pairs, in the moving row's member order:
+ *   member i with reference member i % nr (SAME_UNPACK_DISTRIBUTE; XY is not read), or with the one the optimal assignment of
+ *   cdist(moving XY, reference XY) gives it, the reference columns tiled ceil(na / nr) times when na > nr and mapped back by % nr
+ *   (SAME_UNPACK_NEAREST) -- solved by the very device function same_batched_assign's kernel runs (csrc/assign_solve.h), so ties
+ *   resolve as scipy's linear_sum_assignment resolves them.  A moving row without members yields no pairs.  out_counts[4]:
+ *     [0] final rows      [1] pairs (the sum of na)      [2] pairs whose two member codes are equal and non-negative
+ *     [3] the largest member count met on either side of a final row
+ *   out_ref_member (may be NULL: counts only), `capacity` entries: entry q = the flat index into `ref`'s CSR of the reference member
+ *   pair q got; pair q's moving member is off[a] + i, pairs in the order of the final rows.  capacity < [1]: SAME_EINVAL with out_counts
+ *   FILLED and out_ref_member untouched -- size the array and ask again.
+ * What the call asks of the runtime for n final rows on the accumulator's context: n == 0 nothing; else one launch (sizes and their
+ * scan), one copy (64 bytes back) and one wait -- and where there is a pair: one launch more per started budget (64 MiB) of the
+ * rows' solver slices (DISTRIBUTE has no slices: one launch), a second copy (64 bytes) and a second wait; with out_ref_member a third
+ * copy (the entries) and a third wait.  No fill -- but the first call on an accumulator, and the first over more final rows than any
+ * before, lay the accumulator's work buffer (two words per final row and the scan's words) and fill its head, one fill.  The call
+ * leaves that buffer as it found it, so the sets of a sweep follow each other without one.  The solver's slices live in a buffer of the
+ * accumulator bounded by the budget plus one largest slice, whatever the section's size.
+ * SAME_EINVAL (outputs untouched): before same_merge_acc_finish, after same_merge_acc_plain or same_merge_acc_load, an unknown
+ * strategy, members made for a section other than the one the pass ran over, under NEAREST n final rows times the largest possible
+ * slice (in 128-byte units) beyond 2^31.  SAME_ERANGE (outputs untouched): a final row pairs a non-empty moving list with an empty
+ * reference list; under NEAREST a cost matrix is infeasible (non-finite member XY: same_batched_assign's rule). */
+typedef struct same_members same_members;
+int  same_members_create(const same_section *section, const int64_t *off /* n_rows + 1 */, const double *member_xy /* 2 * m */,
+                         const int32_t *member_code /* m */, int64_t m, same_members **out);
+void same_members_destroy(same_members *members);
+#define SAME_UNPACK_DISTRIBUTE 0
+#define SAME_UNPACK_NEAREST    1
+int same_merge_acc_unpack(same_merge_acc *acc, const same_members *moving, const same_members *ref, int strategy,
+                          int64_t *out_counts /* [4] */, int64_t *out_ref_member /* may be NULL */, int64_t capacity);
 
 /* ======================================================================================================================
  * part 4 -- COMM: one communicator per context, RCCL over xGMI

@@ -1,5 +1,5 @@
 // window_internal.h -- what the translation units of the device-resident window path share (section.hip, window_stage.hip,
-// window_finish.hip, window_merge.hip, window_score.hip, window_caller.hip, window_priority.hip, window_knn_prefix.hip, window_recost.hip): the resident objects behind the
+// window_finish.hip, window_merge.hip, window_score.hip, window_unpack.hip, window_caller.hip, window_priority.hip, window_knn_prefix.hip, window_recost.hip): the resident objects behind the
 // opaque handles of include/same_hip.h part 4, the per-launch argument blocks, the device side of a window's pair list, the window's
 // logical state (window_state.h: win::State, with the table of what each call requires, leaves and invalidates), the small host helpers
 // and the batch driver of the window calls.
@@ -325,7 +325,41 @@ struct same_caller_tris {
     std::vector<unsigned> h_starts;
 };
 
+// The members of a section's rows (same_members_create, window_unpack.hip): CSR over the rows, per member the original cell's XY and its
+// joint label code.  Read-only after its creation: shared by the worker contexts of its device like a section; it must not outlive it.
+struct same_members {
+    same_ctx *ctx = nullptr;
+    const same_section *sec = nullptr;
+    int64_t n_rows = 0, m = 0;
+    int64_t max_count = 0;           // the longest list (host: bounds a solver slice)
+    int64_t *off = nullptr;          // [n_rows + 1]
+    double *xy = nullptr;            // [m][2]
+    int32_t *code = nullptr;         // [m]
+};
+
 namespace win {
+
+// The unpack call's work buffer (window_unpack.hip), one per accumulator, laid for `rows` final rows.  BETWEEN calls the scan's look-back
+// words and the totals of BOTH sets are zero -- filled ONCE when the buffer is laid; a call counts into one set and its first kernel
+// clears the other, which the next call counts into, so a set costs no fill.  The offsets are written before they are read.
+constexpr int UNPACK_TOTALS = 8;         // words of one set of totals (window_unpack.hip names them)
+struct UnpackWork {
+    unsigned long long *status[2] = {nullptr, nullptr};   // the scan's look-back words, two sets
+    unsigned long long *totals = nullptr;                 // [2][UNPACK_TOTALS]
+    unsigned *pair_off = nullptr, *work_off = nullptr;    // [rows] the row's first pair; its solver slice, in units of UNPACK_UNIT words
+    size_t status_words = 0, zero_bytes = 0, bytes = 0;   // words of one set; the share that is zero between calls; the whole
+};
+constexpr int64_t UNPACK_UNIT = 16;      // words of 8 bytes a solver slice is a multiple of: offsets scan in 31 bits, slices start on 128 bytes
+inline void lay(UnpackWork &u, Carver &cv, int64_t rows) {
+    u.status_words = scan::status_bytes(rows) / 8;
+    u.status[0] = cv.scan_words(rows);
+    u.status[1] = cv.scan_words(rows);
+    u.totals = cv.take<unsigned long long>(2 * UNPACK_TOTALS);
+    u.zero_bytes = cv.off;
+    u.pair_off = cv.take<unsigned>((size_t)rows);
+    u.work_off = cv.take<unsigned>((size_t)rows);
+    u.bytes = cv.off;
+}
 
 // The score call's work buffer (window_score.hip), one per accumulator, laid for `rows` rows of the moving section.  BETWEEN calls every
 // word of it is in its idle state -- match_of -1, the node counters 0, the totals 0 -- filled ONCE when the buffer is laid; a call
@@ -379,6 +413,12 @@ struct same_merge_acc {
     win::ScoreWork sw;                        // laid over `score` for score_rows rows
     int64_t score_rows = 0;                   // 0: not laid, or a call failed half way -- the next call lays and fills it again
     int score_set = 0;                        // the totals' set the next call counts into
+    // same_merge_acc_unpack (window_unpack.hip)
+    const same_section *pass_mov = nullptr, *pass_ref = nullptr;   // the sections the pass ran over (same_merge_acc_resolve; null: loaded rows)
+    win::DevBuf unpack, unpack_slices, unpack_pairs;   // the work buffer; the solver's slices (bounded); the pairs' reference members
+    win::UnpackWork uw;                       // laid over `unpack` for unpack_rows final rows
+    int64_t unpack_rows = 0;                  // 0: not laid, or a call failed half way -- the next call lays and fills it again
+    int unpack_set = 0;                       // the set (look-back words, totals) the next call counts into
 };
 
 // what comes back: one record per row (include/same_hip.h)

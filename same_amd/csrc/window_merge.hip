@@ -365,7 +365,7 @@ void same_merge_acc_destroy(same_merge_acc *a) {
     (void)hipStreamSynchronize(a->ctx->stream);
     free_rows(a);
     if (a->dcount) (void)hipFree(a->dcount);
-    for (DevBuf *b : {&a->near_start, &a->near_boxes, &a->scan_words, &a->work, &a->out, &a->score}) release(*b);
+    for (DevBuf *b : {&a->near_start, &a->near_boxes, &a->scan_words, &a->work, &a->out, &a->score, &a->unpack, &a->unpack_slices, &a->unpack_pairs}) release(*b);
     delete a;
 }
 
@@ -492,6 +492,8 @@ int same_merge_acc_resolve(same_merge_acc *const *accs, int n_accs, const same_s
     SAME_TRY(lay_end_to_end(accs, n_accs, &n));
     for (int q = 0; q < n_accs; ++q) accs[q]->resolved = 1;
     a->n_rows = n;
+    a->pass_mov = loaded ? nullptr : mov;          // (what same_merge_acc_unpack holds its members against)
+    a->pass_ref = loaded ? nullptr : ref;
     a->n_codes_a = loaded ? a->loaded_codes_a : (mov->id_codes ? mov->n_codes : mov->n);
     const int64_t n_codes_a = std::max<int64_t>(a->n_codes_a, 1),
                   n_codes_r = std::max<int64_t>(loaded ? a->loaded_codes_r : (ref->id_codes ? ref->n_codes : ref->n), 1);

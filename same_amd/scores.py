@@ -12,6 +12,12 @@ variants.py), and when a set's merge ends everything these numbers read is on th
 reference section row), both sections' XY, the triangulation as section rows, the joint `cell_type` codes.  `sliding_window_scores` counts
 there (csrc/window_score.hip, three short kernels per result) and with tables=False no table is ever made.
 
+With MetaCell objects on both sides a study is read at CELL level (examples/luad/reproduce_figures.ipynb cell 12, examples/tongue cell 15):
+the metacell matches are unpacked to cells (`unpack_metacell_matches`, strategy 'nearest' / 'distribute'), both sides' labels mapped on
+and the pairs and their label agreement counted.  `unpack=` adds those numbers to every record, counted where the merged rows are
+(csrc/window_unpack.hip); `score_unpacked` is the same from a result table -- the notebook cell with the functions the package
+already has.
+
 `score_table` is the same record from a result TABLE with the functions the package already has: what the device record must equal,
 what inputs the device cannot score go through, and the tests' yardstick.  Both end in `record_from_counts`, the one place where counts
 become percentages."""
@@ -21,7 +27,9 @@ import types
 import numpy as np
 import pandas as pd
 
+from . import _lib
 from .eval_utils import _label_codes, check_triangle_violations
+from .metacell_utils import unpack_metacell_matches
 from .triangles import _as_triangle_array
 from .variants import _frames_of, sliding_window_variants
 
@@ -30,6 +38,11 @@ SCORE_PARAMS = {"ignore_same_type_triangles": True, "node_local": False, "majori
 TRIANGLE_KEYS = ("total_triangles", "triangles_with_all_matched", "triangles_same_type_skipped", "triangles_flipped", "percent_flipped",
                  "nodes_in_violating_triangles", "percent_nodes_violating", "violations")
 RECORD_KEYS = ("matched", "type_matches", "accuracy") + TRIANGLE_KEYS
+# the cell-level keys of `unpack=`: rows of the unpacked table, those whose two cells' labels compare equal, their share times 100
+UNPACK_KEYS = ("cells_matched", "cell_type_matches", "cell_accuracy")
+UNPACK_STRATEGIES = ("distribute", "nearest")
+# the longest member list the product unpacks on the device: one lane solves a row in O(n^3) (the library takes SAME_ASSIGN_MAX_MEMBERS)
+UNPACK_DEVICE_MAX = 64
 
 
 def checked_score_params(score_params):
@@ -144,11 +157,57 @@ def score_table(table, ref, moving, *, cell_id_col, score_delaunay=None, score_d
     return record_from_counts(counts, p)
 
 
+def unpack_record(cells_matched, cell_type_matches):
+    """the cell-level keys from their two counts: cell_accuracy = (cell_type_matches / cells_matched) * 100 -- the notebooks'
+    `celltype_match.mean() * 100` --, NaN with no pairs"""
+    n, k = int(cells_matched), int(cell_type_matches)
+    return {"cells_matched": n, "cell_type_matches": k, "cell_accuracy": (k / n) * 100 if n else float("nan")}
+
+
+def checked_unpack(unpack, ref, moving):
+    """ValueError unless `unpack` is None or a strategy and, with a strategy, `ref` and `moving` are MetaCell-like objects: `metacell_df`
+    with a `members` column of lists, `original_df`, `original_idx_col`"""
+    if unpack is None:
+        return
+    if not isinstance(unpack, str) or unpack not in UNPACK_STRATEGIES:
+        raise ValueError(f"unpack must be None or one of {UNPACK_STRATEGIES}, not {unpack!r}")
+    for obj, name in ((ref, "ref"), (moving, "moving")):
+        lacking = [f for f in ("metacell_df", "original_df", "original_idx_col") if not hasattr(obj, f)]
+        if lacking:
+            raise ValueError(f"unpack={unpack!r} reads MetaCell objects on both sides: {name} has no {lacking}")
+        frame = obj.metacell_df
+        if "members" not in getattr(frame, "columns", ()) or not all(isinstance(m, list) for m in frame["members"].tolist()):
+            raise ValueError(f"unpack={unpack!r}: {name}.metacell_df has no 'members' column of lists")
+
+
+def score_unpacked(table, ref_mc, moving_mc, strategy):
+    """The cell-level record of a result table over the MetaCell objects `ref_mc` and `moving_mc`, as the reference's notebooks make it
+    (examples/luad/reproduce_figures.ipynb cell 12): `unpack_metacell_matches(table, moving_mc.metacell_df, ref_mc.metacell_df,
+    aligned_df=moving_mc.original_df, ref_df=ref_mc.original_df, strategy=strategy, ...)`, both sides' labels mapped on through the
+    objects' `original_idx_col`, `celltype_match` = the two labels compare equal.  -> ({cells_matched: len of the unpacked table,
+    cell_type_matches: celltype_match.sum(), cell_accuracy: (cell_type_matches / cells_matched) * 100}, the unpacked table with
+    Aligned_cell_id and Ref_cell_id).  What `sliding_window_scores(unpack=strategy)` must equal, and what it falls back to."""
+    if not len(table):
+        return unpack_record(0, 0), pd.DataFrame([])
+    cells = unpack_metacell_matches(table, moving_mc.metacell_df, ref_mc.metacell_df, aligned_df=moving_mc.original_df,
+                                    ref_df=ref_mc.original_df, strategy=strategy, aligned_original_idx_col=moving_mc.original_idx_col,
+                                    ref_original_idx_col=ref_mc.original_idx_col, x_col=moving_mc.x_col, y_col=moving_mc.y_col)
+    if not len(cells):
+        return unpack_record(0, 0), cells
+    label = lambda mc: mc.original_df.set_index(mc.original_idx_col)[mc.cell_type_col]
+    aligned_ct, ref_ct = cells["Aligned_cell_id"].map(label(moving_mc)), cells["Ref_cell_id"].map(label(ref_mc))
+    celltype_match = aligned_ct == ref_ct
+    return unpack_record(len(cells), int(celltype_match.sum())), cells
+
+
 class DeviceScores:
     """The score hook of `incumbent._device_pass`: what to score every job's merged rows against, and the call that does it."""
 
-    def __init__(self, score_delaunay, vertex_col, params, tables):
+    def __init__(self, score_delaunay, vertex_col, params, tables, unpack=None, ref_mc=None, moving_mc=None):
         self.score_delaunay, self.vertex_col, self.params, self.tables = score_delaunay, vertex_col, params, bool(tables)
+        self.unpack, self.ref_mc, self.moving_mc = unpack, ref_mc, moving_mc      # the strategy (None: metacell level only), the two objects
+        self.members = None      # (moving, reference) windows.DeviceMembers once `prepare` agreed
+        self.cell_tables = []    # with tables: the unpacked table per job, in the jobs' order
         self.job = None          # the first job of the pass (sliding_window_variants tells): MetaCell unwrapping, cell_id_col, its triangulation
         self.records = None      # [record per job, variants outermost] once the device scored them
         self.tris, self.total = None, None
@@ -177,7 +236,32 @@ class DeviceScores:
             if self.tris is None:
                 return False
             self.total = len(_as_triangle_array(tri))
+        if self.unpack is not None:
+            self.members = self.device_members(frames, job)
+            if self.members is None:
+                return False
         return True
+
+    def device_members(self, frames, job):
+        """(moving, reference) member lists resident beside the sections, or None where the device does not unpack these objects (the
+        whole call then goes through `score_unpacked` on the tables): a table that does not name metacells by `metacell_id`; metacell ids
+        that are not 0 .. n-1 in row order (the reference indexes `members` with .iloc[id]); coordinate columns that differ between the
+        objects; what `window_api.member_layout` refuses; a reference row without members; a list longer than UNPACK_DEVICE_MAX; an
+        original label that is missing (pandas' == makes it equal nothing, the joint codes make None equal None)."""
+        mov, ref = self.moving_mc, self.ref_mc
+        if job.optim_params["cell_id_col"] != "metacell_id" or (mov.x_col, mov.y_col) != (ref.x_col, ref.y_col):
+            return None
+        for mc in (mov, ref):
+            ids = mc.metacell_df[mc.metacell_idx_col].to_numpy() if mc.metacell_idx_col in mc.metacell_df.columns else None
+            if mc.metacell_idx_col != "metacell_id" or ids is None or ids.dtype.kind not in "iu" or not np.array_equal(ids, np.arange(len(ids))):
+                return None
+            if bool(pd.isna(mc.original_df[mc.cell_type_col].to_numpy()).any()):
+                return None
+            counts = np.fromiter((len(m) for m in mc.metacell_df["members"].tolist()), np.int64, len(mc.metacell_df))
+            if len(counts) and (counts.max() > UNPACK_DEVICE_MAX or (mc is ref and counts.min() == 0)):
+                return None
+        made = frames.members(mov, "moving", ref), frames.members(ref, "ref", mov)
+        return None if made[0] is None or made[1] is None else made
 
     def record(self, frames, acc):
         """the record of the merged rows `acc` holds after its finish (windows.MergeAccumulator.score)"""
@@ -185,13 +269,36 @@ class DeviceScores:
         c = acc.score(frames.dmov, frames.dref, self.tris, p["ignore_same_type_triangles"], p["node_local"], p["majority_threshold"],
                       p["min_flips"]).tolist()
         # (c[2], the triangles resident, leaves out those that name an id the frame lacks; total_triangles is the caller's own count)
-        return record_from_counts({"matched": c[0], "type_matches": c[1], "total_triangles": self.total, "triangles_with_all_matched": c[3],
-                                   "triangles_same_type_skipped": c[4], "triangles_flipped": c[6], "nodes_in_violating_triangles": c[7]}, p)
+        rec = record_from_counts({"matched": c[0], "type_matches": c[1], "total_triangles": self.total, "triangles_with_all_matched": c[3],
+                                  "triangles_same_type_skipped": c[4], "triangles_flipped": c[6], "nodes_in_violating_triangles": c[7]}, p)
+        if self.unpack is not None:
+            rec.update(self.unpacked(acc))
+        return rec
+
+    def unpacked(self, acc):
+        """the cell-level keys of the merged rows `acc` holds (windows.MergeAccumulator.unpack); with tables the unpacked table joins
+        `cell_tables`: the moving rows' members in their order, each with the reference member the device gave it"""
+        mm, rm = self.members
+        try:
+            got = acc.unpack(mm, rm, self.unpack, pairs=self.tables)
+        except _lib.SameHipError as e:
+            if e.code == _lib.SAME_ERANGE and self.unpack == "nearest":
+                raise ValueError("cost matrix is infeasible") from e
+            raise
+        counts, ref_member = got if self.tables else (got, None)
+        if self.tables:
+            a = acc.final_rows()["a_row"].astype(np.int64)
+            n_a = mm.off[a + 1] - mm.off[a]
+            within = np.arange(int(n_a.sum()), dtype=np.int64) - np.repeat(np.cumsum(n_a) - n_a, n_a)
+            mov_member = np.repeat(mm.off[a], n_a) + within
+            self.cell_tables.append(pd.DataFrame({"Aligned_cell_id": mm.ids[mov_member], "Ref_cell_id": rm.ids[ref_member]})
+                                    if len(mov_member) else pd.DataFrame([]))
+        return unpack_record(counts[1], counts[2])
 
 
 def sliding_window_scores(ref, moving, commonCT=None, *, type_variants=None, param_sets=None, optim_params=None, gurobi_params=None,
                           score_delaunay=None, score_delaunay_vertex_col=None, score_params=None, tables=False, workers=None,
-                          triangulator=None, ctx=None, batch=None, moving_delaunay=None, moving_delaunay_vertex_col=None):
+                          triangulator=None, ctx=None, batch=None, moving_delaunay=None, moving_delaunay_vertex_col=None, unpack=None):
     """The score records of `sliding_window_variants(ref, moving, type_variants, commonCT, param_sets=param_sets, merge=True, ...)` over one
     pass of the windows, counted on the device from every result's merged rows: -> a DataFrame with one row per (variant, set), variants
     outermost, in the callers' order; with tables=True (scores, tables), `tables[v][s]` that call's tables.  `type_variants=None`: the
@@ -205,17 +312,26 @@ def sliding_window_scores(ref, moving, commonCT=None, *, type_variants=None, par
     `moving_delaunay=`).  On plain frames: scipy.spatial.Delaunay(moving[["X", "Y"]]).simplices.  `score_params`: a dict over SCORE_PARAMS,
     check_triangle_violations' arguments.  The other arguments are `sliding_window_variants`' and are checked by its checks; an unknown
     `score_params` key, a value of the wrong type or a frame without `cell_type` raise ValueError before a job or a device is touched.
+    `unpack` ("distribute" / "nearest"; `ref` and `moving` MetaCell objects): every record gains UNPACK_KEYS -- `cells_matched`, the rows of
+    `unpack_metacell_matches` of the result under that strategy, `cell_type_matches`, those whose two cells' labels compare equal, and
+    `cell_accuracy` (`unpack_record`) --, counted on the device from the merged rows and the objects' member lists resident beside the
+    sections (csrc/window_unpack.hip); with tables=True -> (scores, tables, cell_tables), `cell_tables[v][s]` that unpacked table.  Every
+    record and table equals `score_unpacked` of its table, which is also what objects the device does not unpack go through
+    (`DeviceScores.device_members` names them).  An unknown `unpack`, or objects without `metacell_df` / `original_df` /
+    `original_idx_col` / a `members` column of lists, raise ValueError first; non-finite member coordinates under "nearest" raise
+    ValueError("cost matrix is infeasible") as `unpack_metacell_matches` does.
     Every record equals `score_table` of its table.  Inputs the device cannot score -- whatever keeps the job off the shared device pass
     (`sliding_window_sweep` lists it), and what `DeviceScores.prepare` names -- go through `score_table` on the tables: the same records,
     nothing saved."""
     params = checked_score_params(score_params)
-    _ref_arg, _moving_arg, ref_df, mov_df = _frames_of(ref, moving)
+    ref_arg, moving_arg, ref_df, mov_df = _frames_of(ref, moving)
+    checked_unpack(unpack, ref_arg, moving_arg)
     for df, name in ((ref_df, "ref"), (mov_df, "moving")):
         if "cell_type" not in getattr(df, "columns", ()):
             raise ValueError(f"scores compare cell types: the {name} frame has no 'cell_type' column")
     if score_delaunay is not None:
         _as_triangle_array(score_delaunay)                  # (its shape: the reference's ValueError)
-    hook = DeviceScores(score_delaunay, score_delaunay_vertex_col, params, tables)
+    hook = DeviceScores(score_delaunay, score_delaunay_vertex_col, params, tables, unpack, ref_arg, moving_arg)
     results = sliding_window_variants(ref, moving, [None] if type_variants is None else type_variants, commonCT, param_sets=param_sets,
                                       optim_params=optim_params, gurobi_params=gurobi_params, workers=workers, triangulator=triangulator,
                                       ctx=ctx, merge=True, batch=batch, moving_delaunay=moving_delaunay,
@@ -227,7 +343,13 @@ def sliding_window_scores(ref, moving, commonCT=None, *, type_variants=None, par
         tri, vertex_col = hook.triangulation(job)
         records = [score_table(t, job.ref, job.moving, cell_id_col=job.optim_params["cell_id_col"], score_delaunay=tri,
                                score_delaunay_vertex_col=vertex_col, score_params=params, ctx=ctx) for per_set in nested for t in per_set]
+        if unpack is not None:
+            cells = [score_unpacked(t, ref_arg, moving_arg, unpack) for per_set in nested for t in per_set]
+            records = [{**rec, **cell_rec} for rec, (cell_rec, _t) in zip(records, cells)]
+            hook.cell_tables = [t for _rec, t in cells]
     n_sets = len(nested[0])
     rows = [{"variant": q // n_sets, "set": q % n_sets, **rec} for q, rec in enumerate(records)]
-    scores = pd.DataFrame(rows, columns=["variant", "set"] + [k for k in RECORD_KEYS if k in rows[0]])
+    scores = pd.DataFrame(rows, columns=["variant", "set"] + [k for k in RECORD_KEYS + UNPACK_KEYS if k in rows[0]])
+    if tables and unpack is not None:
+        return scores, nested, [hook.cell_tables[q:q + n_sets] for q in range(0, len(records), n_sets)]
     return (scores, nested) if tables else scores

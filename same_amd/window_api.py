@@ -141,6 +141,25 @@ def caller_triangulation_rows(moving, moving_delaunay, vertex_col=None):
     return np.ascontiguousarray(rows, dtype=np.int32), None
 
 
+def member_layout(mc):
+    """The member lists of a MetaCell object as the device reads them: -> (int64 CSR offsets over the rows of `mc.metacell_df`, the
+    members' ids in CSR order, their rows in `mc.original_df`, None), or (None, None, None, why the lists stay on the host): ids that
+    are not integers, ids `mc.original_df[mc.original_idx_col]` repeats, a member id it does not have."""
+    lists = mc.metacell_df["members"].tolist()
+    off = np.zeros(len(lists) + 1, np.int64)
+    np.cumsum([len(m) for m in lists], out=off[1:])
+    ids = np.asarray([x for m in lists for x in m]) if off[-1] else np.zeros(0, np.int64)
+    if ids.dtype.kind not in "iu" or ids.ndim != 1:
+        return None, None, None, "member ids are not integers"
+    index = pd.Index(mc.original_df[mc.original_idx_col].to_numpy())
+    if not index.is_unique:
+        return None, None, None, "the original frame repeats a cell id"
+    rows = index.get_indexer(ids)
+    if len(rows) and rows.min() < 0:
+        return None, None, None, "a member id the original frame does not have"
+    return off, ids.astype(np.int64), rows.astype(np.int64), None
+
+
 def caller_triangulation_refusal(ref, moving, commonCT, op, moving_delaunay, vertex_col=None):
     """Why a caller's triangulation does not take the device route of sliding_window_incumbent under
     optim_params["hip_caller_delaunay"] = "device" (None: it does): a reason `_DeviceFrames.refusal` names, ignore_knn_if_matched
@@ -216,6 +235,30 @@ class _DeviceFrames:
             rows, _why = caller_triangulation_rows(self.moving, moving_delaunay, vertex_col)
             # (the caller's object is held with the entry: its id names it for as long as the entry lives)
             known[key] = (moving_delaunay, None if rows is None else DeviceCallerTris(self.dmov, rows, self.ctx))
+        return known[key][1]
+
+    def members(self, mc, side, other):
+        """The members of MetaCell object `mc`'s rows resident beside its section (windows.DeviceMembers) -- `side` "moving" or "ref",
+        `other` the object of the other side: the CSR of `mc.metacell_df["members"]`, per member its cell's XY in `mc.original_df`
+        (float64) and its code among the joint codes of the two objects' original `cell_type_col` labels (eval_utils._label_codes).
+        None where `member_layout` refuses the lists.  Made once per pair of objects and kept until close() -- the objects are held with
+        the entry, as `caller_tris` holds its triangulation; `.ids` is the members' ids in CSR order."""
+        from .eval_utils import _label_codes
+        from .windows import DeviceMembers
+
+        known = self.__dict__.setdefault("_members", {})
+        key = (id(mc), id(other), side)
+        if key not in known:
+            off, ids, rows, _why = member_layout(mc)
+            made = None
+            if off is not None and len(off) == len(self.moving if side == "moving" else self.ref) + 1:
+                mov_mc, ref_mc = (mc, other) if side == "moving" else (other, mc)
+                codes = _label_codes(mov_mc.original_df[mov_mc.cell_type_col].to_numpy(), ref_mc.original_df[ref_mc.cell_type_col].to_numpy())
+                xy = mc.original_df[[mc.x_col, mc.y_col]].to_numpy(dtype=np.float64)
+                with stage("member lists to the device"):
+                    made = DeviceMembers(self.dmov if side == "moving" else self.dref, off, xy[rows], codes[0 if side == "moving" else 1][rows])
+                made.ids = ids
+            known[key] = ((mc, other), made)
         return known[key][1]
 
     def types_layer(self, variant, types):
@@ -335,6 +378,9 @@ class _DeviceFrames:
                 tris.close()
         for _held, layer in self.__dict__.pop("_types_layers", {}).values():   # before the section they belong to
             layer.close()
+        for _held, members in self.__dict__.pop("_members", {}).values():      # before the section whose rows they list
+            if members is not None:
+                members.close()
         for c in self._worker_ctx:
             c.close()
         self._worker_ctx = []

@@ -679,6 +679,22 @@ class MergeAccumulator(_DeviceHandle):
                                                    int(min_flips), counts.ctypes.data), "same_merge_acc_score")
         return counts
 
+    def unpack(self, mov_members, ref_members, strategy, pairs=False):
+        """After finish(): the merged metacell rows unpacked to cells (same_merge_acc_unpack, csrc/window_unpack.hip) under `strategy`
+        ("distribute" / "nearest"; `mov_members`, `ref_members`: DeviceMembers of the sections the pass ran over) -> the int64 counts
+        (final rows, pairs, pairs whose two label codes agree, largest member count met); with `pairs` (counts, per pair the flat index
+        of its reference member in `ref_members`' CSR) -- the pairs in the order of the final rows and of each moving row's members.
+        A merge names a moving row once, so the moving side's member count bounds the pairs: one call."""
+        if strategy not in UNPACK_STRATEGIES:
+            raise ValueError(f"strategy must be one of {tuple(UNPACK_STRATEGIES)}, not {strategy!r}")
+        ctx, counts = self.ctx, np.zeros(4, np.int64)
+        out = np.empty(mov_members.n_members, np.int64) if pairs else None
+        with ctx.lock:
+            ctx.check(ctx.lib.same_merge_acc_unpack(self.handle, mov_members.handle, ref_members.handle, UNPACK_STRATEGIES[strategy],
+                                                    counts.ctypes.data, None if out is None else out.ctypes.data, 0 if out is None else len(out)),
+                      "same_merge_acc_unpack")
+        return (counts, out[:int(counts[1])]) if pairs else counts
+
     def columns(self, dmoving, dref, n_final, n_types, extra_moving=(), extra_ref=(), layer=None):
         """After finish(): the merged table's columns written by the device straight into page-locked host memory (enqueue only:
         `ctx.sync()` before reading): the moving section's type columns (`layer`: a DeviceTypesLayer of `dmoving` to read them from), X, Y, the reference's X, Y, the caller's extra 8-byte device
@@ -827,6 +843,36 @@ class DeviceCallerTris(_DeviceHandle):
         rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1, 3)
         self.n_triangles = len(rows)
         self._create(ctx, dsection.handle, rows.ctypes.data if len(rows) else None, len(rows))
+
+
+class DeviceMembers(_DeviceHandle):
+    """The members of a section's rows resident on the device (same_members_create, csrc/window_unpack.hip): `off` int64 (rows + 1) CSR
+    offsets, `xy` float64 (m, 2) the members' ORIGINAL cells' coordinates, `codes` int32 (m) their joint label codes (negative: equals
+    nothing).  Made on the section's context; read-only: the worker contexts of the device share it.  Close it before its section."""
+
+    _ENTRY = (None, "same_members_destroy")
+
+    def __init__(self, dsection, off, xy, codes):
+        self.off = np.ascontiguousarray(off, dtype=np.int64)
+        xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        codes = np.ascontiguousarray(codes, dtype=np.int32)
+        if len(xy) != len(codes):
+            raise ValueError(f"{len(xy)} member coordinates, {len(codes)} member codes")
+        if len(self.off) != len(dsection.section.xy) + 1:       # (the library reads off[rows]: nothing it was not given)
+            raise ValueError(f"{len(self.off)} offsets for a section of {len(dsection.section.xy)} rows")
+        self.n_members = len(codes)
+        self.ctx = ctx = dsection.ctx
+        h = ctypes.c_void_p()
+        with ctx.lock:
+            rc = ctx.lib.same_members_create(dsection.handle, self.off.ctypes.data, xy.ctypes.data if len(xy) else None,
+                                             codes.ctypes.data if len(codes) else None, len(codes), ctypes.byref(h))
+            if rc != 0 and h.value:
+                ctx.lib.same_members_destroy(h)
+            ctx.check(rc, "same_members_create")
+        self.handle = h
+
+
+UNPACK_STRATEGIES = {"distribute": _lib.SAME_UNPACK_DISTRIBUTE, "nearest": _lib.SAME_UNPACK_NEAREST}
 
 
 def caller_tris_windows(states, caller, radius, angle_enabled, cos_thr, near_tol, ignore_same_type, removed=None):

@@ -375,6 +375,10 @@ int same_merge_acc_begin(same_merge_acc *a, int64_t expected_rows, int n_pos, co
     same_ctx *ctx = a->ctx;
     REQUIRE(ctx, expected_rows >= 0 && expected_rows < ((int64_t)1 << 30) && n_pos >= 0 && reach >= 0.0 && reach - reach == 0.0);
     REQUIRE(ctx, !near_start || n_pos == 0 || near_boxes || near_start[n_pos] == 0);
+    if (near_start && n_pos > 0) {                // (before the pass so far is touched: a refused begin leaves it as it was)
+        REQUIRE(ctx, near_start[0] == 0);
+        for (int q = 0; q < n_pos; ++q) REQUIRE(ctx, near_start[q + 1] >= near_start[q]);
+    }
     SAME_TRY(same_use(ctx));
     a->resolved = 0;
     a->loaded = 0;
@@ -386,8 +390,6 @@ int same_merge_acc_begin(same_merge_acc *a, int64_t expected_rows, int n_pos, co
     SAME_FILL(ctx, a->dcount, 0, (2 + SAME_LAUNCH_WINDOWS) * sizeof(unsigned long long));
     SAME_TRY(reserve_rows(a, expected_rows, 0));
     if (near_start && n_pos > 0) {
-        REQUIRE(ctx, near_start[0] == 0);
-        for (int q = 0; q < n_pos; ++q) REQUIRE(ctx, near_start[q + 1] >= near_start[q]);
         const int64_t n_boxes = near_start[n_pos];
         SAME_TRY(ensure(ctx, a->near_start, (size_t)(n_pos + 1) * sizeof(int32_t)));
         SAME_TRY(ensure(ctx, a->near_boxes, (size_t)std::max<int64_t>(n_boxes, 1) * 4 * sizeof(double)));
@@ -481,7 +483,7 @@ int same_merge_acc_resolve(same_merge_acc *const *accs, int n_accs, const same_s
     same_ctx *ctx = a->ctx;
     REQUIRE(ctx, n_accs <= 64 && out_counts);
     const bool loaded = a->loaded != 0;           // rows that came from the host carry their codes: no sections, one accumulator
-    REQUIRE(ctx, loaded ? n_accs == 1 : (mov && ref && mov->ctx->device == ctx->device && ref->ctx->device == ctx->device));
+    REQUIRE(ctx, loaded ? (n_accs == 1 && !mov && !ref) : (mov && ref && mov->ctx->device == ctx->device && ref->ctx->device == ctx->device));
     for (int q = 0; q < n_accs; ++q) {
         REQUIRE(ctx, accs[q] && accs[q]->ctx->device == ctx->device && !accs[q]->resolved);
         for (int p = 0; p < q; ++p) REQUIRE(ctx, accs[p] != accs[q]);

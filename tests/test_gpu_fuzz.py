@@ -532,7 +532,7 @@ def test_scans_hold_when_no_block_ever_sees_a_predecessor():
            "tests/test_gpu_run_same.py::test_window_rows_do_not_depend_on_the_section_grid",
            "tests/test_gpu_parity.py::test_sharded_sweeps_rccl_single_rank_and_block_forms",
            "tests/test_host_rows.py::test_merge_dedup_on_device",
-           "tests/test_gpu_merge.py", "tests/test_gpu_fuzz.py::test_fuzz_window_merge_routes_agree",
+           "tests/test_gpu_merge.py", "tests/test_gpu_merge_library.py", "tests/test_gpu_fuzz.py::test_fuzz_window_merge_routes_agree",
            "tests/test_gpu_window_front_calls.py::test_caller_scan_edges", "tests/test_gpu_window_front_calls.py::test_priority_scan_edges"]
     res = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-k", "not scans_hold"] + sel, cwd=root, env=env,
                          capture_output=True, text=True, timeout=1500)

@@ -814,6 +814,49 @@ int same_host_free(same_ctx *ctx, void *ptr);
 int same_merge_acc_score(same_merge_acc *acc, const same_section *moving, const same_section *ref,
                          const same_caller_tris *tris /* may be NULL: no triangle counts */, int ignore_same_type, int node_local,
                          double majority_threshold, int64_t min_flips, int64_t *out_counts /* [8] */);
+/* The same result broken down three ways (csrc/window_score_detail.hip): by label pair, by group of the moving rows, by the rank of the
+ * moving cell's label among its matched reference cell's type columns -- binned where same_merge_acc_score totals.
+ *   same_score_detail_create: what to bin by, uploaded once on `moving`'s context, resident on its device, read-only and shared by the
+ *   worker contexts like same_caller_tris; destroy it before its section.  group_of[row] in [0, n_groups) is the moving row's group, a
+ *   negative value: the row is in no group; NULL: every row in group 0.  col_of_label[code] is the type column (of the sections' T) the
+ *   label with that joint code names, or -1; NULL: no label names a column (as n_labels entries of -1).  Checked on the host before
+ *   anything is uploaded: SAME_EINVAL for n_labels < 0 or > SAME_SCORE_MAX_LABELS, n_groups < 1 or > SAME_SCORE_MAX_GROUPS; SAME_ERANGE
+ *   for a group_of value >= n_groups or a col_of_label value outside [-1, T).
+ *   same_merge_acc_score_detail: arguments as same_merge_acc_score's, and `detail`, made for `moving`.  With L = n_labels, G = n_groups,
+ *   R = SAME_SCORE_RANKS, `out` holds out_words >= L*L + 1 + (G+1)*8 + 2*(R+1) + 1 words (SAME_SCORE_DETAIL_WORDS), in this order:
+ *     confusion [L*L]   out[cm*L + cr]: final rows whose moving label code is cm and whose matched reference cell's is cr;
+ *     unlabelled [1]    the final rows in no cell: a code that is negative or >= L on either side;
+ *     groups [(G+1)*8]  bin g < G is group g, bin G is "cross".  A bin's eight words are out_counts[0 .. 7] of same_merge_acc_score
+ *                       restricted to the bin: [0] final rows (a row is in its moving row's group; without one, in the cross bin)
+ *                       [1] of them, the two label codes agree  [2] triangles resident (a triangle is in group g iff its three corners
+ *                       carry g, else in the cross bin)  [3] all corners matched  [4] skipped, same type  [5] flipped  [6] flipped and
+ *                       not skipped  [7] final rows whose moving cell is violating under the any-flip / node-local rule -- counted
+ *                       over the triangles that are WITHIN a group and not skipped: a node is counted in its own group, the cross
+ *                       bin's word stays 0.  Over all bins words [0 .. 6] sum to same_merge_acc_score's counts;
+ *     ranks [2*(R+1)]   for final row (a, r): c = col_of_label[code of a], v = ref types[r][c] (the float64 matrix the section was made
+ *                       from), strict = #{t != c: types[r][t] > v}, weak = #{t != c: types[r][t] >= v}; first the histogram of
+ *                       min(strict, R), then that of min(weak, R);
+ *     untyped [1]       the final rows in no rank bin: a moving code that is negative or >= L, c < 0, a NaN in the reference type row.
+ * What the call asks of the runtime for n final rows on the accumulator's context: n == 0 and no triangle resident: nothing (out is zeros); else one launch, and two more where `tris` holds a triangle; one copy (the words of `out` and one more); ONE
+ * wait; no fill -- but a call that lays the accumulator's score work buffer (same_merge_acc_score: the first, and the first over more
+ * moving rows) fills it, two fills, and one that lays the bins' buffer (the first, and the first with more words than any before)
+ * fills that, one fill.  The call leaves the score work buffer as it found it and the bins' buffer clear for the next call: score and
+ * detail calls alternate on one accumulator without a fill.
+ * SAME_EINVAL / SAME_ERANGE as same_merge_acc_score, `out` untouched; SAME_EINVAL also for a `detail` made for another section,
+ * sections whose T differ where a label names a column, and out_words too small. */
+#define SAME_SCORE_MAX_LABELS 64
+#define SAME_SCORE_MAX_GROUPS 256
+#define SAME_SCORE_RANKS 16
+#define SAME_SCORE_DETAIL_WORDS(L, G) ((int64_t)(L) * (L) + 1 + ((int64_t)(G) + 1) * 8 + 2 * (SAME_SCORE_RANKS + 1) + 1)
+typedef struct same_score_detail same_score_detail;
+int  same_score_detail_create(const same_section *moving, const int32_t *group_of /* [rows] or NULL: every row in group 0 */, int n_groups,
+                              int n_labels, const int32_t *col_of_label /* [n_labels] or NULL: no rank counts */,
+                              same_score_detail **out);
+void same_score_detail_destroy(same_score_detail *detail);
+int  same_merge_acc_score_detail(same_merge_acc *acc, const same_section *moving, const same_section *ref,
+                                 const same_caller_tris *tris /* may be NULL */, const same_score_detail *detail,
+                                 int ignore_same_type, int node_local, double majority_threshold, int64_t min_flips,
+                                 int64_t *out, int64_t out_words);
 /* A merged MetaCell result unpacked to cells (csrc/window_unpack.hip; src/metacell_utils.py:564-766, unpack_metacell_matches with
  * metacells on both sides), without its table: after same_merge_acc_finish, on the final rows where they are and in their order.
  *   same_members_create: the members of `section`'s rows as CSR -- row i owns members [off[i], off[i+1]); per member its XY (the

@@ -143,6 +143,9 @@ _PROTOTYPES = {
     "same_merge_acc_columns": [c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_i64],
     "same_merge_acc_columns_layer": [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_i64],
     "same_merge_acc_score": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_dbl, c_i64, c_vp],
+    "same_score_detail_create": [c_vp, c_vp, c_int, c_int, c_vp, ctypes.POINTER(c_vp)],
+    "same_score_detail_destroy": [c_vp],
+    "same_merge_acc_score_detail": [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_dbl, c_i64, c_vp, c_i64],
     "same_members_create": [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(c_vp)],
     "same_members_destroy": [c_vp],
     "same_merge_acc_unpack": [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_i64],
@@ -172,6 +175,7 @@ SAME_TRIS_SIMPLICES, SAME_TRIS_KEPT, SAME_TRIS_DEVICE, SAME_TRIS_CALLER = 0, 1, 
 SAME_INCUMBENT_GREEDY, SAME_INCUMBENT_ASSIGNMENT, SAME_INCUMBENT_TRANSPORT = 0, 1, 2
 SAME_WINDOW_STATS = 15
 SAME_UNPACK_DISTRIBUTE, SAME_UNPACK_NEAREST = 0, 1     # same_merge_acc_unpack's strategies
+SAME_SCORE_MAX_LABELS, SAME_SCORE_MAX_GROUPS, SAME_SCORE_RANKS = 64, 256, 16     # same_merge_acc_score_detail's caps and rank bins
 SAME_WINDOW_STATS_CAP = 16       # the _cap calls: the 15 words, then sum_j max(0, count_j - 1) of the search's result
 SAME_WINDOW_STATS_TRANSPORT = 17  # SAME_INCUMBENT_TRANSPORT: the 16 words, then sum_j max(0, count_j - 1) of the start
 
@@ -216,6 +220,7 @@ def load():
             L.same_caller_tris_destroy.restype = None
             L.same_types_layer_destroy.restype = None
             L.same_members_destroy.restype = None
+            L.same_score_detail_destroy.restype = None
             if L.same_abi_version() != ABI_VERSION:
                 raise SameHipError(-22, "libsame_hip ABI version mismatch")
             _lib = L

@@ -1,5 +1,5 @@
 // window_internal.h -- what the translation units of the device-resident window path share (section.hip, window_stage.hip,
-// window_finish.hip, window_merge.hip, window_score.hip, window_unpack.hip, window_caller.hip, window_priority.hip, window_knn_prefix.hip, window_recost.hip): the resident objects behind the
+// window_finish.hip, window_merge.hip, window_score.hip, window_score_detail.hip, window_unpack.hip, window_caller.hip, window_priority.hip, window_knn_prefix.hip, window_recost.hip): the resident objects behind the
 // opaque handles of include/same_hip.h part 4, the per-launch argument blocks, the device side of a window's pair list, the window's
 // logical state (window_state.h: win::State, with the table of what each call requires, leaves and invalidates), the small host helpers
 // and the batch driver of the window calls.
@@ -381,7 +381,48 @@ inline void lay(ScoreWork &s, Carver &cv, int64_t rows) {
     s.bytes = cv.off;
 }
 
+// The detail call's bins (window_score_detail.hip), one buffer per accumulator: two sets of `cap` words, used alternately.  A set holds
+// what include/same_hip.h states of same_merge_acc_score_detail's `out`, in its order -- the confusion matrix, `unlabelled`, the groups'
+// records, the two rank histograms, `untyped` -- and one word more, the final rows outside the sections.  BETWEEN calls every word of
+// both sets is zero -- filled ONCE when the buffer is laid; a call counts into one set and its first kernel clears what the call before
+// it counted into the other (same_merge_acc::detail_dirty words), so a set costs no fill.
+constexpr int DETAIL_GROUP_WORDS = 8;    // words of a group's record, in the order of same_merge_acc_score's out_counts
+struct DetailWork {
+    unsigned long long *bins = nullptr;           // [2][cap]
+    int64_t cap = 0;
+    size_t bytes = 0;
+};
+inline void lay(DetailWork &d, Carver &cv, int64_t cap) {
+    d.cap = cap;
+    d.bins = cv.take<unsigned long long>((size_t)(2 * cap));
+    d.bytes = cv.off;
+}
+// where a set's parts start for L labels, G groups and R = SAME_SCORE_RANKS: the one statement of the layout, host and device
+struct DetailLayout {
+    int L = 0, G = 0;
+    __host__ __device__ int64_t confusion() const { return 0; }
+    __host__ __device__ int64_t unlabelled() const { return (int64_t)L * L; }
+    __host__ __device__ int64_t groups() const { return unlabelled() + 1; }
+    __host__ __device__ int64_t strict() const { return groups() + (int64_t)(G + 1) * DETAIL_GROUP_WORDS; }
+    __host__ __device__ int64_t weak() const { return strict() + SAME_SCORE_RANKS + 1; }
+    __host__ __device__ int64_t untyped() const { return weak() + SAME_SCORE_RANKS + 1; }
+    __host__ __device__ int64_t out_words() const { return untyped() + 1; }       // what the caller's `out` holds
+    __host__ __device__ int64_t bad() const { return out_words(); }               // final rows outside the sections
+    __host__ __device__ int64_t words() const { return out_words() + 1; }
+};
+
 }  // namespace win
+
+// What same_merge_acc_score_detail bins by, resident (same_score_detail_create, window_score_detail.hip): per row of the moving section
+// its group, per label code the commonCT column the label names.  Read-only after its creation: shared by the worker contexts of its
+// device like a same_caller_tris; it must not outlive its section.
+struct same_score_detail {
+    same_ctx *ctx = nullptr;
+    const same_section *mov = nullptr;
+    int n_groups = 1, n_labels = 0;
+    int32_t *group_of = nullptr;     // [mov->n] in [0, n_groups), negative: no group; null: every row in group 0
+    int32_t *col_of_label = nullptr; // [n_labels] in [-1, mov->T); null: no label names a column
+};
 
 // The rows of one pass over a window plan on one context (window_merge.hip), and what window_score.hip reads of them.
 struct same_merge_acc {
@@ -413,6 +454,11 @@ struct same_merge_acc {
     win::ScoreWork sw;                        // laid over `score` for score_rows rows
     int64_t score_rows = 0;                   // 0: not laid, or a call failed half way -- the next call lays and fills it again
     int score_set = 0;                        // the totals' set the next call counts into
+    // same_merge_acc_score_detail (window_score_detail.hip): it works in `sw` too, under the score call's protocol
+    win::DevBuf detail;
+    win::DetailWork dw;                       // laid over `detail`; dw.cap == 0: not laid, or a call failed half way
+    int detail_set = 0;                       // the bins' set the next call counts into
+    int64_t detail_dirty = 0;                 // words of the OTHER set the call before counted into: the next call's first kernel clears them
     // same_merge_acc_unpack (window_unpack.hip)
     const same_section *pass_mov = nullptr, *pass_ref = nullptr;   // the sections the pass ran over (same_merge_acc_resolve; null: loaded rows)
     win::DevBuf unpack, unpack_slices, unpack_pairs;   // the work buffer; the solver's slices (bounded); the pairs' reference members
@@ -420,6 +466,26 @@ struct same_merge_acc {
     int64_t unpack_rows = 0;                  // 0: not laid, or a call failed half way -- the next call lays and fills it again
     int unpack_set = 0;                       // the set (look-back words, totals) the next call counts into
 };
+
+namespace win {
+// the accumulator's ScoreWork laid for at least `rows` rows of a moving section: laid for too few (or never, or a call failed half way)
+// it is laid again and filled ONCE, two fills -- what the score call and the detail call both begin with
+inline int ensure_score_work(same_ctx *ctx, same_merge_acc *a, int64_t rows) {
+    if (a->score_rows >= rows && a->score.p) return SAME_OK;
+    a->score_rows = 0;
+    ScoreWork probe;
+    Carver measure;
+    lay(probe, measure, rows);
+    SAME_TRY(ensure(ctx, a->score, probe.bytes));
+    Carver place(a->score.p);
+    lay(a->sw, place, rows);
+    SAME_FILL(ctx, a->score.p, 0xFF, a->sw.ones_bytes);
+    SAME_FILL(ctx, static_cast<char *>(a->score.p) + a->sw.ones_bytes, 0, a->sw.bytes - a->sw.ones_bytes);
+    a->score_set = 0;
+    a->score_rows = rows;
+    return SAME_OK;
+}
+}  // namespace win
 
 // what comes back: one record per row (include/same_hip.h)
 struct RestRec {

@@ -136,20 +136,7 @@ extern "C" int same_merge_acc_score(same_merge_acc *a, const same_section *mov, 
     const int64_t n = a->n_final, Tr = tris ? tris->n_tris : 0;
     unsigned long long h[SCORE_TOTALS] = {};
     if (n > 0) {
-        const int64_t rows = std::max<int64_t>(mov->n, 1);
-        if (a->score_rows < rows || !a->score.p) {            // laid for too few rows (or never, or a call failed): lay it, fill it ONCE
-            a->score_rows = 0;
-            ScoreWork probe;
-            Carver measure;
-            lay(probe, measure, rows);
-            SAME_TRY(ensure(ctx, a->score, probe.bytes));
-            Carver place(a->score.p);
-            lay(a->sw, place, rows);
-            SAME_FILL(ctx, a->score.p, 0xFF, a->sw.ones_bytes);
-            SAME_FILL(ctx, static_cast<char *>(a->score.p) + a->sw.ones_bytes, 0, a->sw.bytes - a->sw.ones_bytes);
-            a->score_set = 0;
-            a->score_rows = rows;
-        }
+        SAME_TRY(ensure_score_work(ctx, a, std::max<int64_t>(mov->n, 1)));   // laid for too few rows (or never, or a call failed): laid, filled ONCE
         const ScoreWork &sw = a->sw;
         const int64_t laid = a->score_rows;
         a->score_rows = 0;                                    // until the call is through: what fails half way leaves the buffer in doubt

@@ -18,6 +18,9 @@ and the pairs and their label agreement counted.  `unpack=` adds those numbers t
 (csrc/window_unpack.hip); `score_unpacked` is the same from a result table -- the notebook cell with the functions the package
 already has.
 
+score_details.py breaks every record down by group of the moving rows, by label pair and by type rank over the same pass: its
+`DetailSpec` rides on the hook below, which then makes the detail call beside the score call (csrc/window_score_detail.hip).
+
 `score_table` is the same record from a result TABLE with the functions the package already has: what the device record must equal,
 what inputs the device cannot score go through, and the tests' yardstick.  Both end in `record_from_counts`, the one place where counts
 become percentages."""
@@ -203,8 +206,10 @@ def score_unpacked(table, ref_mc, moving_mc, strategy):
 class DeviceScores:
     """The score hook of `incumbent._device_pass`: what to score every job's merged rows against, and the call that does it."""
 
-    def __init__(self, score_delaunay, vertex_col, params, tables, unpack=None, ref_mc=None, moving_mc=None):
+    def __init__(self, score_delaunay, vertex_col, params, tables, unpack=None, ref_mc=None, moving_mc=None, detail=None):
         self.score_delaunay, self.vertex_col, self.params, self.tables = score_delaunay, vertex_col, params, bool(tables)
+        # what to break every record down by (score_details.DetailSpec; None: totals only); its resident object once `prepare` agreed
+        self.detail, self.detail_dev = detail, None
         self.unpack, self.ref_mc, self.moving_mc = unpack, ref_mc, moving_mc      # the strategy (None: metacell level only), the two objects
         self.members = None      # (moving, reference) windows.DeviceMembers once `prepare` agreed
         self.cell_tables = []    # with tables: the unpacked table per job, in the jobs' order
@@ -240,6 +245,10 @@ class DeviceScores:
             self.members = self.device_members(frames, job)
             if self.members is None:
                 return False
+        if self.detail is not None:
+            self.detail_dev = self.detail.resident(frames)
+            if self.detail_dev is None:
+                return False
         return True
 
     def device_members(self, frames, job):
@@ -273,6 +282,10 @@ class DeviceScores:
                                   "triangles_same_type_skipped": c[4], "triangles_flipped": c[6], "nodes_in_violating_triangles": c[7]}, p)
         if self.unpack is not None:
             rec.update(self.unpacked(acc))
+        if self.detail_dev is not None:
+            # the detail call beside the score call: the same rows, triangles and rule, binned (csrc/window_score_detail.hip)
+            rec["_detail"] = acc.score_detail(frames.dmov, frames.dref, self.tris, self.detail_dev, p["ignore_same_type_triangles"],
+                                              p["node_local"], p["majority_threshold"], p["min_flips"])
         return rec
 
     def unpacked(self, acc):
@@ -323,6 +336,23 @@ def sliding_window_scores(ref, moving, commonCT=None, *, type_variants=None, par
     Every record equals `score_table` of its table.  Inputs the device cannot score -- whatever keeps the job off the shared device pass
     (`sliding_window_sweep` lists it), and what `DeviceScores.prepare` names -- go through `score_table` on the tables: the same records,
     nothing saved."""
+    scores, nested, hook = _scored_study(ref, moving, commonCT, type_variants=type_variants, param_sets=param_sets, optim_params=optim_params,
+                                         gurobi_params=gurobi_params, score_delaunay=score_delaunay,
+                                         score_delaunay_vertex_col=score_delaunay_vertex_col, score_params=score_params, tables=tables,
+                                         workers=workers, triangulator=triangulator, ctx=ctx, batch=batch, moving_delaunay=moving_delaunay,
+                                         moving_delaunay_vertex_col=moving_delaunay_vertex_col, unpack=unpack)
+    if tables and unpack is not None:
+        n_sets = len(nested[0])
+        return scores, nested, [hook.cell_tables[q:q + n_sets] for q in range(0, len(scores), n_sets)]
+    return (scores, nested) if tables else scores
+
+
+def _scored_study(ref, moving, commonCT, *, type_variants, param_sets, optim_params, gurobi_params, score_delaunay,
+                  score_delaunay_vertex_col, score_params, tables, workers, triangulator, ctx, batch, moving_delaunay,
+                  moving_delaunay_vertex_col, unpack, detail=None):
+    """`sliding_window_scores`' pass -> (its scores frame, the results per variant and set -- tables, or None where the device scored
+    and none was asked for --, the hook: `hook.records` is None where the host scored the tables).  With `detail`
+    (score_details.DetailSpec) every record of the device carries the detail call's words under "_detail"."""
     params = checked_score_params(score_params)
     ref_arg, moving_arg, ref_df, mov_df = _frames_of(ref, moving)
     checked_unpack(unpack, ref_arg, moving_arg)
@@ -331,7 +361,7 @@ def sliding_window_scores(ref, moving, commonCT=None, *, type_variants=None, par
             raise ValueError(f"scores compare cell types: the {name} frame has no 'cell_type' column")
     if score_delaunay is not None:
         _as_triangle_array(score_delaunay)                  # (its shape: the reference's ValueError)
-    hook = DeviceScores(score_delaunay, score_delaunay_vertex_col, params, tables, unpack, ref_arg, moving_arg)
+    hook = DeviceScores(score_delaunay, score_delaunay_vertex_col, params, tables, unpack, ref_arg, moving_arg, detail)
     results = sliding_window_variants(ref, moving, [None] if type_variants is None else type_variants, commonCT, param_sets=param_sets,
                                       optim_params=optim_params, gurobi_params=gurobi_params, workers=workers, triangulator=triangulator,
                                       ctx=ctx, merge=True, batch=batch, moving_delaunay=moving_delaunay,
@@ -350,6 +380,4 @@ def sliding_window_scores(ref, moving, commonCT=None, *, type_variants=None, par
     n_sets = len(nested[0])
     rows = [{"variant": q // n_sets, "set": q % n_sets, **rec} for q, rec in enumerate(records)]
     scores = pd.DataFrame(rows, columns=["variant", "set"] + [k for k in RECORD_KEYS + UNPACK_KEYS if k in rows[0]])
-    if tables and unpack is not None:
-        return scores, nested, [hook.cell_tables[q:q + n_sets] for q in range(0, len(records), n_sets)]
-    return (scores, nested) if tables else scores
+    return scores, nested, hook

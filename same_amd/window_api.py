@@ -261,6 +261,21 @@ class _DeviceFrames:
             known[key] = ((mc, other), made)
         return known[key][1]
 
+    def score_detail(self, group_of, n_groups, n_labels, col_of_label):
+        """What a study's scores are broken down by, resident beside the moving section (windows.DeviceScoreDetail): `group_of` the
+        moving rows' group codes (None: one group), `col_of_label` the joint label codes' type columns (None: no rank counts).  Made
+        once per (group codes, column map) -- keyed by their values -- and kept until close(), as `caller_tris` and `members` are."""
+        from .windows import DeviceScoreDetail
+
+        g = None if group_of is None else np.ascontiguousarray(group_of, dtype=np.int32)
+        c = None if col_of_label is None else np.ascontiguousarray(col_of_label, dtype=np.int32)
+        known = self.__dict__.setdefault("_score_details", {})
+        key = (None if g is None else g.tobytes(), int(n_groups), int(n_labels), None if c is None else c.tobytes())
+        if key not in known:
+            with stage("score groups and label columns to the device"):
+                known[key] = DeviceScoreDetail(self.dmov, g, n_groups, n_labels, c)
+        return known[key]
+
     def types_layer(self, variant, types):
         """A type-matrix variant of the moving frame resident beside its section (windows.DeviceTypesLayer): `types` the variant as a
         float64 (rows, commonCT) matrix, `variant` the caller's object it was read from.  Uploaded once per object and kept until close()
@@ -381,6 +396,8 @@ class _DeviceFrames:
         for _held, members in self.__dict__.pop("_members", {}).values():      # before the section whose rows they list
             if members is not None:
                 members.close()
+        for detail in self.__dict__.pop("_score_details", {}).values():        # before the section whose rows they group
+            detail.close()
         for c in self._worker_ctx:
             c.close()
         self._worker_ctx = []

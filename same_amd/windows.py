@@ -679,6 +679,19 @@ class MergeAccumulator(_DeviceHandle):
                                                    int(min_flips), counts.ctypes.data), "same_merge_acc_score")
         return counts
 
+    def score_detail(self, dmoving, dref, tris, detail, ignore_same_type=True, node_local=False, majority_threshold=0.5, min_flips=1):
+        """After finish(): the merged rows binned by same_merge_acc_score_detail (csrc/window_score_detail.hip) under `detail`, a
+        DeviceScoreDetail of `dmoving`; the other arguments are `score`'s.  -> the call's int64 words cut by `detail.split`: a dict of
+        `confusion` (L, L), `unlabelled`, `groups` (G + 1, 8: `score`'s eight counts per group, the last row the cross bin),
+        `strict` and `weak` (SCORE_RANKS + 1 each) and `untyped`.  One wait; leaves the accumulator as `score` does."""
+        ctx, out = self.ctx, np.zeros(detail.n_words, np.int64)
+        with ctx.lock:
+            ctx.check(ctx.lib.same_merge_acc_score_detail(self.handle, dmoving.handle, dref.handle, None if tris is None else tris.handle,
+                                                          detail.handle, int(bool(ignore_same_type)), int(bool(node_local)),
+                                                          float(majority_threshold), int(min_flips), out.ctypes.data, len(out)),
+                      "same_merge_acc_score_detail")
+        return detail.split(out)
+
     def unpack(self, mov_members, ref_members, strategy, pairs=False):
         """After finish(): the merged metacell rows unpacked to cells (same_merge_acc_unpack, csrc/window_unpack.hip) under `strategy`
         ("distribute" / "nearest"; `mov_members`, `ref_members`: DeviceMembers of the sections the pass ran over) -> the int64 counts
@@ -870,6 +883,56 @@ class DeviceMembers(_DeviceHandle):
                 ctx.lib.same_members_destroy(h)
             ctx.check(rc, "same_members_create")
         self.handle = h
+
+
+SCORE_RANKS = _lib.SAME_SCORE_RANKS
+
+
+def score_detail_words(n_labels, n_groups):
+    """int64 words of same_merge_acc_score_detail's `out` (SAME_SCORE_DETAIL_WORDS)"""
+    return n_labels * n_labels + 1 + (n_groups + 1) * 8 + 2 * (SCORE_RANKS + 1) + 1
+
+
+def split_score_detail(out, n_labels, n_groups):
+    """the words of same_merge_acc_score_detail's `out` by name, in the order include/same_hip.h states"""
+    L, G, R = int(n_labels), int(n_groups), SCORE_RANKS
+    out = np.asarray(out, np.int64)
+    assert len(out) >= score_detail_words(L, G)
+    at = np.cumsum([0, L * L, 1, (G + 1) * 8, R + 1, R + 1, 1])
+    part = lambda q: out[at[q]:at[q + 1]]
+    return {"confusion": part(0).reshape(L, L), "unlabelled": int(part(1)[0]), "groups": part(2).reshape(G + 1, 8), "strict": part(3),
+            "weak": part(4), "untyped": int(part(5)[0])}
+
+
+class DeviceScoreDetail(_DeviceHandle):
+    """What same_merge_acc_score_detail bins by, resident beside a moving section (same_score_detail_create,
+    csrc/window_score_detail.hip): `group_of` int32 per section row (negative: no group; None: every row in group 0) over `n_groups`
+    groups, `col_of_label` int32 per joint label code, the type column the label names or -1 (None: no rank counts), `n_labels` codes.
+    Made on the section's context; read-only: the worker contexts of the device share it.  Close it before its section."""
+
+    _ENTRY = (None, "same_score_detail_destroy")
+
+    def __init__(self, dsection, group_of, n_groups, n_labels, col_of_label):
+        g = None if group_of is None else np.ascontiguousarray(group_of, dtype=np.int32)
+        c = None if col_of_label is None else np.ascontiguousarray(col_of_label, dtype=np.int32)
+        if g is not None and g.shape != (len(dsection.section.xy),):        # (the library reads one entry per row: nothing it was not given)
+            raise ValueError(f"group_of has shape {g.shape} for a section of {len(dsection.section.xy)} rows")
+        if c is not None and c.shape != (max(int(n_labels), 0),):
+            raise ValueError(f"col_of_label has shape {c.shape} for {n_labels} labels")
+        self.n_groups, self.n_labels = int(n_groups), int(n_labels)
+        self.ctx = ctx = dsection.ctx
+        h = ctypes.c_void_p()
+        with ctx.lock:
+            rc = ctx.lib.same_score_detail_create(dsection.handle, None if g is None or not len(g) else g.ctypes.data, self.n_groups,
+                                                  self.n_labels, None if c is None or not len(c) else c.ctypes.data, ctypes.byref(h))
+            if rc != 0 and h.value:
+                ctx.lib.same_score_detail_destroy(h)
+            ctx.check(rc, "same_score_detail_create")
+        self.handle = h
+        self.n_words = score_detail_words(self.n_labels, self.n_groups)
+
+    def split(self, out):
+        return split_score_detail(out, self.n_labels, self.n_groups)
 
 
 UNPACK_STRATEGIES = {"distribute": _lib.SAME_UNPACK_DISTRIBUTE, "nearest": _lib.SAME_UNPACK_NEAREST}

@@ -1,8 +1,8 @@
 // window_internal.h -- what the translation units of the device-resident window path share (section.hip, window_stage.hip,
 // window_finish.hip, window_merge.hip, window_score.hip, window_score_detail.hip, window_unpack.hip, window_caller.hip, window_priority.hip, window_knn_prefix.hip, window_recost.hip): the resident objects behind the
 // opaque handles of include/same_hip.h part 4, the per-launch argument blocks, the device side of a window's pair list, the window's
-// logical state (window_state.h: win::State, with the table of what each call requires, leaves and invalidates), the small host helpers
-// and the batch driver of the window calls.
+// logical state (window_state.h: win::State, with the table of what each call requires, leaves and invalidates), the protocol of the merged
+// rows' reader calls (work_sets.h: win::WorkSets), the small host helpers and the batch driver of the window calls.
 //
 // The window path (src/same.py:507-593 with both sections RESIDENT on the device).  A section's columns are uploaded once
 // (same_section) and its rows are binned once into a grid of cells (same_section_bin: rows sorted by cell, ascending inside a cell)
@@ -50,6 +50,7 @@
 #include "devmath.h"
 #include "scan.h"
 #include "window_state.h"
+#include "work_sets.h"
 
 struct same_knn_index;
 extern "C" int same_knn_index_build(same_ctx *ctx, const double *drxy, int64_t n_r, double radius, same_knn_index **out);
@@ -108,6 +109,17 @@ struct Carver {
     }
     unsigned long long *scan_words(int64_t n) { return take<unsigned long long>(scan::status_bytes(n) / 8); }   // status_bytes: 16-byte units
 };
+// `w` laid over `buf` for n (a lay(Work &, Carver &, int64_t) says how): measured, the buffer ensured, the pointers placed
+template <class Work>
+int lay_over(same_ctx *ctx, DevBuf &buf, Work &w, int64_t n) {
+    Work probe;
+    Carver measure;
+    lay(probe, measure, n);
+    SAME_TRY(ensure(ctx, buf, probe.bytes));
+    Carver place(buf.p);
+    lay(w, place, n);
+    return SAME_OK;
+}
 
 inline unsigned grid_for(int64_t n) { return (unsigned)ceil_div(n > 0 ? n : 1, 256); }
 
@@ -339,9 +351,10 @@ struct same_members {
 
 namespace win {
 
-// The unpack call's work buffer (window_unpack.hip), one per accumulator, laid for `rows` final rows.  BETWEEN calls the scan's look-back
-// words and the totals of BOTH sets are zero -- filled ONCE when the buffer is laid; a call counts into one set and its first kernel
-// clears the other, which the next call counts into, so a set costs no fill.  The offsets are written before they are read.
+// The work buffers of the merged rows' reader calls, one of each per accumulator, under the protocol of work_sets.h.
+//
+// The unpack call's (window_unpack.hip), laid for `rows` final rows.  Idle: the scan's look-back words and the totals of BOTH sets zero;
+// unpack_size_kernel clears the other set's.  The offsets are written before they are read.
 constexpr int UNPACK_TOTALS = 8;         // words of one set of totals (window_unpack.hip names them)
 struct UnpackWork {
     unsigned long long *status[2] = {nullptr, nullptr};   // the scan's look-back words, two sets
@@ -361,15 +374,13 @@ inline void lay(UnpackWork &u, Carver &cv, int64_t rows) {
     u.bytes = cv.off;
 }
 
-// The score call's work buffer (window_score.hip), one per accumulator, laid for `rows` rows of the moving section.  BETWEEN calls every
-// word of it is in its idle state -- match_of -1, the node counters 0, the totals 0 -- filled ONCE when the buffer is laid; a call
-// leaves it so again itself (its last kernel resets what its first two wrote, per final row; its first kernel clears the totals' set
-// the NEXT call counts into), so a set costs no fill.
+// The score call's (window_score.hip), laid for `rows` rows of the moving section.  Idle: match_of -1, the node counters 0, the totals 0;
+// the nodes kernel resets what the two kernels before it wrote, per final row, and score_rows_kernel clears the other set of totals.
 constexpr int SCORE_TOTALS = 8;          // words of one set of totals; words [1] and [3 .. 7] are what out_counts[1], [3 .. 7] report
 struct ScoreWork {
     int32_t *match_of = nullptr;                  // [rows] reference section row the moving row is matched to in the final rows, -1 = none
     unsigned *node_tri = nullptr, *node_flip = nullptr;   // [rows] triangles not skipped the row is a corner of; the flipped ones of them
-    unsigned long long *totals = nullptr;         // [2][SCORE_TOTALS] two sets, used alternately (same_merge_acc::score_set)
+    unsigned long long *totals = nullptr;         // [2][SCORE_TOTALS] two sets
     size_t ones_bytes = 0, bytes = 0;             // match_of's share, from the buffer's start (filled 0xFF; the rest 0); the whole
 };
 inline void lay(ScoreWork &s, Carver &cv, int64_t rows) {
@@ -381,11 +392,10 @@ inline void lay(ScoreWork &s, Carver &cv, int64_t rows) {
     s.bytes = cv.off;
 }
 
-// The detail call's bins (window_score_detail.hip), one buffer per accumulator: two sets of `cap` words, used alternately.  A set holds
-// what include/same_hip.h states of same_merge_acc_score_detail's `out`, in its order -- the confusion matrix, `unlabelled`, the groups'
-// records, the two rank histograms, `untyped` -- and one word more, the final rows outside the sections.  BETWEEN calls every word of
-// both sets is zero -- filled ONCE when the buffer is laid; a call counts into one set and its first kernel clears what the call before
-// it counted into the other (same_merge_acc::detail_dirty words), so a set costs no fill.
+// The detail call's bins (window_score_detail.hip): two sets of `cap` words.  A set holds what include/same_hip.h states of
+// same_merge_acc_score_detail's `out`, in its order -- the confusion matrix, `unlabelled`, the groups' records, the two rank histograms,
+// `untyped` -- and one word more, the final rows outside the sections.  Idle: every word of both sets zero; detail_rows_kernel clears
+// what the call before counted into the other set (WorkSets::dirty words).
 constexpr int DETAIL_GROUP_WORDS = 8;    // words of a group's record, in the order of same_merge_acc_score's out_counts
 struct DetailWork {
     unsigned long long *bins = nullptr;           // [2][cap]
@@ -451,38 +461,40 @@ struct same_merge_acc {
     std::vector<char> host;                   // what the last resolve / finish brought back (fetched by same_merge_acc_fetch)
     // same_merge_acc_score (window_score.hip)
     win::DevBuf score;
-    win::ScoreWork sw;                        // laid over `score` for score_rows rows
-    int64_t score_rows = 0;                   // 0: not laid, or a call failed half way -- the next call lays and fills it again
-    int score_set = 0;                        // the totals' set the next call counts into
-    // same_merge_acc_score_detail (window_score_detail.hip): it works in `sw` too, under the score call's protocol
+    win::ScoreWork sw;                        // laid over `score`
+    win::WorkSets score_sets;                 // ... for so many rows of the moving section
+    // same_merge_acc_score_detail (window_score_detail.hip): it works in `sw` too (never in its totals: score_sets does not flip)
     win::DevBuf detail;
-    win::DetailWork dw;                       // laid over `detail`; dw.cap == 0: not laid, or a call failed half way
-    int detail_set = 0;                       // the bins' set the next call counts into
-    int64_t detail_dirty = 0;                 // words of the OTHER set the call before counted into: the next call's first kernel clears them
+    win::DetailWork dw;                       // laid over `detail`
+    win::WorkSets detail_sets;                // ... for so many words a set
     // same_merge_acc_unpack (window_unpack.hip)
     const same_section *pass_mov = nullptr, *pass_ref = nullptr;   // the sections the pass ran over (same_merge_acc_resolve; null: loaded rows)
     win::DevBuf unpack, unpack_slices, unpack_pairs;   // the work buffer; the solver's slices (bounded); the pairs' reference members
-    win::UnpackWork uw;                       // laid over `unpack` for unpack_rows final rows
-    int64_t unpack_rows = 0;                  // 0: not laid, or a call failed half way -- the next call lays and fills it again
-    int unpack_set = 0;                       // the set (look-back words, totals) the next call counts into
+    win::UnpackWork uw;                       // laid over `unpack`
+    win::WorkSets unpack_sets;                // ... for so many final rows; a set: look-back words and totals
 };
 
 namespace win {
-// the accumulator's ScoreWork laid for at least `rows` rows of a moving section: laid for too few (or never, or a call failed half way)
-// it is laid again and filled ONCE, two fills -- what the score call and the detail call both begin with
+// the accumulator holds a merge's final rows on the device: what the three reader calls require of it
+inline bool has_merged_rows(const same_merge_acc *a) { return a->resolved == 2 && a->merged && !a->loaded; }
+// what the score call and the detail call require alike (refusals come before any device call)
+inline int require_score_args(same_ctx *ctx, const same_merge_acc *a, const same_section *mov, const same_section *ref,
+                              const same_caller_tris *tris, double majority_threshold) {
+    REQUIRE(ctx, has_merged_rows(a));
+    REQUIRE(ctx, mov && ref && mov->ctx->device == ctx->device && ref->ctx->device == ctx->device);
+    REQUIRE(ctx, mov->label_codes && ref->label_codes);
+    REQUIRE(ctx, !tris || (tris->mov == mov && tris->ctx->device == ctx->device));
+    REQUIRE(ctx, majority_threshold == majority_threshold);
+    return SAME_OK;
+}
+// ... and both begin with: the accumulator's ScoreWork laid for at least `rows` rows of the moving section, two fills where it is laid
 inline int ensure_score_work(same_ctx *ctx, same_merge_acc *a, int64_t rows) {
-    if (a->score_rows >= rows && a->score.p) return SAME_OK;
-    a->score_rows = 0;
-    ScoreWork probe;
-    Carver measure;
-    lay(probe, measure, rows);
-    SAME_TRY(ensure(ctx, a->score, probe.bytes));
-    Carver place(a->score.p);
-    lay(a->sw, place, rows);
+    if (a->score_sets.fits(rows)) return SAME_OK;
+    InDoubt laying(a->score_sets);
+    SAME_TRY(lay_over(ctx, a->score, a->sw, rows));
     SAME_FILL(ctx, a->score.p, 0xFF, a->sw.ones_bytes);
     SAME_FILL(ctx, static_cast<char *>(a->score.p) + a->sw.ones_bytes, 0, a->sw.bytes - a->sw.ones_bytes);
-    a->score_set = 0;
-    a->score_rows = rows;
+    a->score_sets.laid_anew(rows);
     return SAME_OK;
 }
 }  // namespace win
@@ -499,6 +511,53 @@ struct FinalRec {
 static_assert(sizeof(RestRec) == SAME_MERGE_REST_BYTES && sizeof(FinalRec) == SAME_MERGE_FINAL_BYTES, "record layouts are part of the ABI");
 
 namespace win {
+
+// ---- check_triangle_violations' rule (src/eval_utils.py:66-223) over a merge's final rows, as the device states it ---------------------
+// Each decision of it ONCE, for the kernels of window_score.hip, window_score_detail.hip and window_unpack.hip; how a kernel adds up what
+// these answer (ballots, LDS bins) stays its own.  (match.hip's tri_flip_stats_kernel serves the host-buffer call: another matched mask,
+// another same-type test.)
+__device__ __forceinline__ bool row_in(int32_t row, int64_t n) { return (unsigned long long)(long long)row < (unsigned long long)n; }
+// a final row is FOLLOWED where both its rows lie inside their sections (rows of other sections: counted, never followed)
+__device__ __forceinline__ bool followed(const FinalRec &row, int64_t n_mov, int64_t n_ref) {
+    return row_in(row.a_row, n_mov) && row_in(row.r_row, n_ref);
+}
+// do two joint label codes agree: a negative code equals nothing
+__device__ __forceinline__ bool labels_agree(int32_t a, int32_t b) { return a >= 0 && a == b; }
+
+// a resident triangle (a, b, c: rows of the moving section): all three corners matched?  then, under ignore_same, the same-type rule on
+// the moving codes, and the flip rule on the moving XY and the matched reference XY (devmath.h: eval_area3, eval_flipped).  A triangle
+// that is not all matched loads neither codes nor XY.  (Filled in place: returned by value the three flags travel packed, in VGPRs.)
+struct TriVerdict {
+    bool all = false, same = false, flipped = false;
+};
+__device__ __forceinline__ void tri_verdict(TriVerdict &v, int32_t a, int32_t b, int32_t c, const int32_t *match_of, const int32_t *code_m,
+                                            int ignore_same, const double *mov_xy, const double *ref_xy) {
+    using namespace devmath;
+    const int32_t ma = match_of[a], mb = match_of[b], mc = match_of[c];
+    v.all = ma >= 0 && mb >= 0 && mc >= 0;
+    if (!v.all) return;
+    if (ignore_same) {
+        const int32_t ca = code_m[a];
+        v.same = labels_agree(ca, code_m[b]) && labels_agree(ca, code_m[c]);
+    }
+    v.flipped = eval_flipped(eval_area3(ld2(mov_xy, a), ld2(mov_xy, b), ld2(mov_xy, c)),
+                             eval_area3(ld2(ref_xy, ma), ld2(ref_xy, mb), ld2(ref_xy, mc)));
+}
+// the corners' counters of a triangle that is not skipped
+__device__ __forceinline__ void count_corners(int32_t a, int32_t b, int32_t c, bool flipped, unsigned *node_tri, unsigned *node_flip) {
+    atomicAdd(&node_tri[a], 1u); atomicAdd(&node_tri[b], 1u); atomicAdd(&node_tri[c], 1u);
+    if (flipped) { atomicAdd(&node_flip[a], 1u); atomicAdd(&node_flip[b], 1u); atomicAdd(&node_flip[c], 1u); }
+}
+// src/eval_utils.py:199-211: any flip, or at least min_flips flips that are at least the threshold's share of the node's triangles
+__device__ __forceinline__ bool node_violating(unsigned n_tri, unsigned n_flip, int node_local, double majority_threshold, int64_t min_flips) {
+    return node_local ? (n_tri > 0 && (int64_t)n_flip >= min_flips && (double)n_flip / (double)n_tri >= majority_threshold) : n_flip > 0;
+}
+// moving row a's three words back to idle: a merge's final rows name a moving row once, nobody else reads or resets them
+__device__ __forceinline__ void reset_idle(int32_t a, int32_t *match_of, unsigned *node_tri, unsigned *node_flip) {
+    match_of[a] = -1;
+    node_tri[a] = 0u;
+    node_flip[a] = 0u;
+}
 
 // section.hip
 int knn_index_for(same_ctx *ctx, const same_section *ref, double radius, std::shared_ptr<same_knn_index> *out);

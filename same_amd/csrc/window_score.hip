@@ -9,19 +9,18 @@
 //
 //   score_rows_kernel    per final row: match_of[moving row] = reference row; do the two label codes agree (a negative code equals nothing)
 //   score_tris_kernel    per resident triangle: all three corners matched?  the same-type rule on the moving codes; the flip rule of
-//                        check_triangle_violations on the moving XY and the matched reference XY (devmath.h: eval_area3, eval_flipped --
-//                        match.hip's tri_flip_stats_kernel runs the same two functions); the corners' counters over the triangles that
-//                        are not skipped
+//                        check_triangle_violations on the moving XY and the matched reference XY; the corners' counters over the
+//                        triangles that are not skipped
 //   score_nodes_kernel   per final row: is the row's node violating (any flip, or the node-local majority rule); the row's match_of and
 //                        counters go back to their idle state (win::ScoreWork, window_internal.h)
 //
+// What a row, a triangle and a node ARE under the rule is window_internal.h's (the rule's section); these kernels add it up.
 // Every count is an integer: a block counts with wave ballots, adds its waves' counts in LDS and issues ONE 64-bit atomic per total it
 // has something for; the per-node counters are 32-bit integer atomics.  No float is ever added, so the counts do not depend on the order.
 #include "window_internal.h"
 
 namespace {
 
-using namespace devmath;
 using namespace win;
 
 constexpr int NT = 256;
@@ -46,8 +45,6 @@ __device__ __forceinline__ void block_totals(const bool (&flag)[K], const int (&
     }
 }
 
-__device__ __forceinline__ bool row_in(int32_t row, int64_t n) { return (unsigned long long)(long long)row < (unsigned long long)n; }
-
 // match_of null: no triangles to score, nothing reads it
 __global__ __launch_bounds__(NT) void score_rows_kernel(const FinalRec *__restrict__ rows, int64_t n, int64_t n_mov, int64_t n_ref,
                                                         const int32_t *__restrict__ code_m, const int32_t *__restrict__ code_r,
@@ -58,11 +55,10 @@ __global__ __launch_bounds__(NT) void score_rows_kernel(const FinalRec *__restri
     bool bad = false, agree = false;
     if (i < n) {
         const int32_t a = rows[i].a_row, r = rows[i].r_row;
-        bad = !row_in(a, n_mov) || !row_in(r, n_ref);         // (rows of other sections: counted, never followed)
+        bad = !followed(rows[i], n_mov, n_ref);
         if (!bad) {
             if (match_of) match_of[a] = r;
-            const int32_t c = code_m[a];
-            agree = c >= 0 && c == code_r[r];
+            agree = labels_agree(code_m[a], code_r[r]);
         }
     }
     const bool flag[2] = {bad, agree};
@@ -75,25 +71,13 @@ __global__ __launch_bounds__(NT) void score_tris_kernel(const int32_t *__restric
                                                         const double *__restrict__ ref_xy, unsigned *__restrict__ node_tri,
                                                         unsigned *__restrict__ node_flip, unsigned long long *__restrict__ totals) {
     const int64_t t = (int64_t)blockIdx.x * NT + threadIdx.x;
-    bool all = false, same = false, flipped = false;
+    TriVerdict v;
     if (t < Tr) {
         const int32_t a = tris[3 * t], b = tris[3 * t + 1], c = tris[3 * t + 2];        // rows of the moving section (same_caller_tris_create)
-        const int32_t ma = match_of[a], mb = match_of[b], mc = match_of[c];
-        all = ma >= 0 && mb >= 0 && mc >= 0;
-        if (all) {
-            if (ignore_same) {
-                const int32_t ca = code_m[a];
-                same = ca >= 0 && ca == code_m[b] && ca == code_m[c];
-            }
-            flipped = eval_flipped(eval_area3(ld2(mov_xy, a), ld2(mov_xy, b), ld2(mov_xy, c)),
-                                   eval_area3(ld2(ref_xy, ma), ld2(ref_xy, mb), ld2(ref_xy, mc)));
-            if (!same) {
-                atomicAdd(&node_tri[a], 1u); atomicAdd(&node_tri[b], 1u); atomicAdd(&node_tri[c], 1u);
-                if (flipped) { atomicAdd(&node_flip[a], 1u); atomicAdd(&node_flip[b], 1u); atomicAdd(&node_flip[c], 1u); }
-            }
-        }
+        tri_verdict(v, a, b, c, match_of, code_m, ignore_same, mov_xy, ref_xy);
+        if (v.all && !v.same) count_corners(a, b, c, v.flipped, node_tri, node_flip);
     }
-    const bool flag[4] = {all, same, flipped, flipped && !same};
+    const bool flag[4] = {v.all, v.same, v.flipped, v.flipped && !v.same};
     const int word[4] = {T_ALL, T_SAME, T_FLIP, T_FLIP_CONSIDERED};
     block_totals<4>(flag, word, totals);
 }
@@ -106,14 +90,9 @@ __global__ __launch_bounds__(NT) void score_nodes_kernel(const FinalRec *__restr
     bool violating = false;
     if (i < n) {
         const int32_t a = rows[i].a_row;
-        if (row_in(a, n_mov) && row_in(rows[i].r_row, n_ref)) {          // (the rows score_rows_kernel followed)
-            const unsigned n_tri = node_tri[a], n_flip = node_flip[a];
-            // src/eval_utils.py:199-211: any flip, or at least min_flips flips that are at least the threshold's share of the node's triangles
-            violating = node_local ? (n_tri > 0 && (int64_t)n_flip >= min_flips && (double)n_flip / (double)n_tri >= majority_threshold)
-                                   : n_flip > 0;
-            match_of[a] = -1;          // a merge's final rows name a moving row once: nobody else reads or resets these three words
-            node_tri[a] = 0u;
-            node_flip[a] = 0u;
+        if (followed(rows[i], n_mov, n_ref)) {
+            violating = node_violating(node_tri[a], node_flip[a], node_local, majority_threshold, min_flips);
+            reset_idle(a, match_of, node_tri, node_flip);
         }
     }
     const bool flag[1] = {violating};
@@ -127,20 +106,16 @@ extern "C" int same_merge_acc_score(same_merge_acc *a, const same_section *mov, 
                                     int ignore_same_type, int node_local, double majority_threshold, int64_t min_flips, int64_t *out_counts) {
     if (!a) return SAME_EINVAL;
     same_ctx *ctx = a->ctx;
-    REQUIRE(ctx, out_counts && a->resolved == 2 && a->merged && !a->loaded);
-    REQUIRE(ctx, mov && ref && mov->ctx->device == ctx->device && ref->ctx->device == ctx->device);
-    REQUIRE(ctx, mov->label_codes && ref->label_codes);
-    REQUIRE(ctx, !tris || (tris->mov == mov && tris->ctx->device == ctx->device));
-    REQUIRE(ctx, majority_threshold == majority_threshold);
+    REQUIRE(ctx, out_counts);
+    SAME_TRY(require_score_args(ctx, a, mov, ref, tris, majority_threshold));
     SAME_TRY(same_use(ctx));
     const int64_t n = a->n_final, Tr = tris ? tris->n_tris : 0;
     unsigned long long h[SCORE_TOTALS] = {};
     if (n > 0) {
-        SAME_TRY(ensure_score_work(ctx, a, std::max<int64_t>(mov->n, 1)));   // laid for too few rows (or never, or a call failed): laid, filled ONCE
+        SAME_TRY(ensure_score_work(ctx, a, std::max<int64_t>(mov->n, 1)));
         const ScoreWork &sw = a->sw;
-        const int64_t laid = a->score_rows;
-        a->score_rows = 0;                                    // until the call is through: what fails half way leaves the buffer in doubt
-        unsigned long long *totals = sw.totals + (size_t)a->score_set * SCORE_TOTALS, *next = sw.totals + (size_t)(a->score_set ^ 1) * SCORE_TOTALS;
+        InDoubt doubt(a->score_sets);
+        unsigned long long *totals = sw.totals + (size_t)a->score_sets.set * SCORE_TOTALS, *next = sw.totals + (size_t)(a->score_sets.set ^ 1) * SCORE_TOTALS;
         const FinalRec *fin = static_cast<const FinalRec *>(a->out.p);
         SAME_LAUNCH(ctx, score_rows_kernel, dim3(grid_for(n)), dim3(NT), 0, fin, n, mov->n, ref->n, mov->label_codes, ref->label_codes,
                     Tr > 0 ? sw.match_of : nullptr, totals, next);
@@ -153,20 +128,15 @@ extern "C" int same_merge_acc_score(same_merge_acc *a, const same_section *mov, 
         HIP_TRY(ctx, hipGetLastError());
         SAME_COPY(ctx, h, totals, sizeof h, hipMemcpyDeviceToHost);
         SAME_WAIT(ctx);
-        a->score_set ^= 1;
-        a->score_rows = laid;
+        doubt.sound();
+        a->score_sets.flip();
         if (h[T_BAD]) {
             ctx->err = "same_merge_acc_score: final rows outside the sections (the accumulator's pass ran over other sections)";
             return SAME_ERANGE;
         }
     }
+    for (int q = 0; q < SCORE_TOTALS; ++q) out_counts[q] = (int64_t)h[q];     // a set's words [1] and [3 .. 7] are out_counts' own
     out_counts[0] = n;
-    out_counts[1] = (int64_t)h[T_TYPE];
     out_counts[2] = Tr;
-    out_counts[3] = (int64_t)h[T_ALL];
-    out_counts[4] = (int64_t)h[T_SAME];
-    out_counts[5] = (int64_t)h[T_FLIP];
-    out_counts[6] = (int64_t)h[T_FLIP_CONSIDERED];
-    out_counts[7] = (int64_t)h[T_NODES];
     return SAME_OK;
 }

@@ -20,7 +20,6 @@
 
 namespace {
 
-using namespace devmath;
 using namespace win;
 
 constexpr int NT = 256;
@@ -30,8 +29,6 @@ constexpr int R = SAME_SCORE_RANKS;
 enum { W_ROWS = 0, W_TYPE = 1, W_TRIS = 2, W_ALL = 3, W_SAME = 4, W_FLIP = 5, W_FLIP_CONSIDERED = 6, W_NODES = 7 };
 
 unsigned blocks_for(int64_t n) { return (unsigned)std::min<int64_t>(ceil_div(n > 0 ? n : 1, NT), MAX_BLOCKS); }
-
-__device__ __forceinline__ bool row_in(int32_t row, int64_t n) { return (unsigned long long)(long long)row < (unsigned long long)n; }
 
 extern __shared__ unsigned lds_bins[];
 
@@ -69,7 +66,7 @@ __global__ __launch_bounds__(NT) void detail_rows_kernel(const FinalRec *__restr
     clear_lds(words);
     for (int64_t i = first; i < n; i += stride) {
         const int32_t a = rows[i].a_row, r = rows[i].r_row;
-        if (!row_in(a, n_mov) || !row_in(r, n_ref)) {        // (rows of other sections: counted, never followed)
+        if (!followed(rows[i], n_mov, n_ref)) {
             atomicAdd(&lds_bins[o_bad], 1u);
             continue;
         }
@@ -79,7 +76,7 @@ __global__ __launch_bounds__(NT) void detail_rows_kernel(const FinalRec *__restr
         atomicAdd(&lds_bins[lm && lr ? cm * L + cr : o_unl], 1u);
         const int g = group_at(group_of, a, G);
         atomicAdd(&lds_bins[o_grp + 2 * g], 1u);
-        if (cm >= 0 && cm == cr) atomicAdd(&lds_bins[o_grp + 2 * g + 1], 1u);
+        if (labels_agree(cm, cr)) atomicAdd(&lds_bins[o_grp + 2 * g + 1], 1u);
         const int c = lm && col_of_label ? col_of_label[cm] : -1;
         bool typed = c >= 0 && c < T;
         if (typed) {
@@ -126,23 +123,14 @@ __global__ __launch_bounds__(NT) void detail_tris_kernel(const int32_t *__restri
         const int g = ga == group_at(group_of, b, G) && ga == group_at(group_of, c, G) ? ga : G;
         unsigned *mine = lds_bins + 5 * g;
         atomicAdd(&mine[0], 1u);
-        const int32_t ma = match_of[a], mb = match_of[b], mc = match_of[c];
-        if (ma < 0 || mb < 0 || mc < 0) continue;
+        TriVerdict v;
+        tri_verdict(v, a, b, c, match_of, code_m, ignore_same, mov_xy, ref_xy);
+        if (!v.all) continue;
         atomicAdd(&mine[1], 1u);
-        bool same = false;
-        if (ignore_same) {
-            const int32_t ca = code_m[a];
-            same = ca >= 0 && ca == code_m[b] && ca == code_m[c];
-        }
-        const bool flipped = eval_flipped(eval_area3(ld2(mov_xy, a), ld2(mov_xy, b), ld2(mov_xy, c)),
-                                          eval_area3(ld2(ref_xy, ma), ld2(ref_xy, mb), ld2(ref_xy, mc)));
-        if (same) atomicAdd(&mine[2], 1u);
-        if (flipped) atomicAdd(&mine[3], 1u);
-        if (flipped && !same) atomicAdd(&mine[4], 1u);
-        if (!same && g < G) {                     // within a group and not skipped: the corners' counters
-            atomicAdd(&node_tri[a], 1u); atomicAdd(&node_tri[b], 1u); atomicAdd(&node_tri[c], 1u);
-            if (flipped) { atomicAdd(&node_flip[a], 1u); atomicAdd(&node_flip[b], 1u); atomicAdd(&node_flip[c], 1u); }
-        }
+        if (v.same) atomicAdd(&mine[2], 1u);
+        if (v.flipped) atomicAdd(&mine[3], 1u);
+        if (v.flipped && !v.same) atomicAdd(&mine[4], 1u);
+        if (!v.same && g < G) count_corners(a, b, c, v.flipped, node_tri, node_flip);       // within a group and not skipped
     }
     flush_lds(words, bins, [=](int i) -> int64_t { return lay.groups() + (int64_t)(i / 5) * DETAIL_GROUP_WORDS + W_TRIS + i % 5; });
 }
@@ -158,15 +146,10 @@ __global__ __launch_bounds__(NT) void detail_nodes_kernel(const FinalRec *__rest
     const int64_t stride = (int64_t)gridDim.x * NT;
     for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < n; i += stride) {
         const int32_t a = rows[i].a_row;
-        if (!row_in(a, n_mov) || !row_in(rows[i].r_row, n_ref)) continue;          // (the rows detail_rows_kernel followed)
-        const unsigned n_tri = node_tri[a], n_flip = node_flip[a];
-        // src/eval_utils.py:199-211: any flip, or at least min_flips flips that are at least the threshold's share of the node's triangles
-        const bool violating = node_local ? (n_tri > 0 && (int64_t)n_flip >= min_flips && (double)n_flip / (double)n_tri >= majority_threshold)
-                                          : n_flip > 0;
-        if (violating) atomicAdd(&lds_bins[group_at(group_of, a, G)], 1u);
-        match_of[a] = -1;          // a merge's final rows name a moving row once: nobody else reads or resets these three words
-        node_tri[a] = 0u;
-        node_flip[a] = 0u;
+        if (!followed(rows[i], n_mov, n_ref)) continue;
+        if (node_violating(node_tri[a], node_flip[a], node_local, majority_threshold, min_flips))
+            atomicAdd(&lds_bins[group_at(group_of, a, G)], 1u);
+        reset_idle(a, match_of, node_tri, node_flip);
     }
     flush_lds(words, bins, [=](int i) -> int64_t { return lay.groups() + (int64_t)i * DETAIL_GROUP_WORDS + W_NODES; });
 }
@@ -227,13 +210,10 @@ int same_merge_acc_score_detail(same_merge_acc *a, const same_section *mov, cons
                                 int64_t min_flips, int64_t *out, int64_t out_words) {
     if (!a) return SAME_EINVAL;
     same_ctx *ctx = a->ctx;
-    REQUIRE(ctx, out && a->resolved == 2 && a->merged && !a->loaded);
-    REQUIRE(ctx, mov && ref && mov->ctx->device == ctx->device && ref->ctx->device == ctx->device);
-    REQUIRE(ctx, mov->label_codes && ref->label_codes);
-    REQUIRE(ctx, !tris || (tris->mov == mov && tris->ctx->device == ctx->device));
+    REQUIRE(ctx, out);
+    SAME_TRY(require_score_args(ctx, a, mov, ref, tris, majority_threshold));
     REQUIRE(ctx, detail && detail->mov == mov && detail->ctx->device == ctx->device);
     REQUIRE(ctx, !detail->col_of_label || (ref->T == mov->T && ref->types64));
-    REQUIRE(ctx, majority_threshold == majority_threshold);
     DetailLayout lay;
     lay.L = detail->n_labels;
     lay.G = detail->n_groups;
@@ -243,28 +223,21 @@ int same_merge_acc_score_detail(same_merge_acc *a, const same_section *mov, cons
     std::vector<unsigned long long> h((size_t)words, 0ull);
     if (n > 0 || Tr > 0) {
         SAME_TRY(ensure_score_work(ctx, a, std::max<int64_t>(mov->n, 1)));
-        if (a->dw.cap < words || !a->detail.p) {          // laid for too few words (or never, or a call failed): lay it, fill it ONCE
-            a->dw.cap = 0;
-            DetailWork probe;
-            Carver measure;
-            win::lay(probe, measure, words);
-            SAME_TRY(ensure(ctx, a->detail, probe.bytes));
-            Carver place(a->detail.p);
-            win::lay(a->dw, place, words);
+        WorkSets &ds = a->detail_sets;
+        if (!ds.fits(words)) {
+            InDoubt laying(ds);
+            SAME_TRY(lay_over(ctx, a->detail, a->dw, words));
             SAME_FILL(ctx, a->detail.p, 0, a->dw.bytes);
-            a->detail_set = 0;
-            a->detail_dirty = 0;
+            ds.laid_anew(words);
         }
         const ScoreWork &sw = a->sw;
-        const int64_t laid = a->score_rows, cap = a->dw.cap;
-        a->score_rows = 0;                                // until the call is through: what fails half way leaves both buffers in doubt
-        a->dw.cap = 0;
-        unsigned long long *bins = a->dw.bins + (size_t)a->detail_set * cap, *next = a->dw.bins + (size_t)(a->detail_set ^ 1) * cap;
+        InDoubt doubt_score(a->score_sets), doubt(ds);        // the call works in both buffers
+        unsigned long long *bins = a->dw.bins + (size_t)ds.set * a->dw.cap, *next = a->dw.bins + (size_t)(ds.set ^ 1) * a->dw.cap;
         const FinalRec *fin = static_cast<const FinalRec *>(a->out.p);
         const size_t lds_rows = (size_t)(lay.L * lay.L + 1 + 2 * (lay.G + 1) + 2 * (R + 1) + 2) * sizeof(unsigned);
-        SAME_LAUNCH(ctx, detail_rows_kernel, dim3(blocks_for(std::max(n, a->detail_dirty))), dim3(NT), lds_rows, fin, n, mov->n, ref->n,
+        SAME_LAUNCH(ctx, detail_rows_kernel, dim3(blocks_for(std::max(n, ds.dirty))), dim3(NT), lds_rows, fin, n, mov->n, ref->n,
                     mov->label_codes, ref->label_codes, detail->group_of, detail->col_of_label, ref->types64, mov->T, lay,
-                    Tr > 0 ? sw.match_of : nullptr, bins, next, a->detail_dirty);
+                    Tr > 0 ? sw.match_of : nullptr, bins, next, ds.dirty);
         if (Tr > 0) {
             SAME_LAUNCH(ctx, detail_tris_kernel, dim3(blocks_for(Tr)), dim3(NT), (size_t)(5 * (lay.G + 1)) * sizeof(unsigned), tris->tris, Tr,
                         sw.match_of, mov->label_codes, detail->group_of, ignore_same_type ? 1 : 0, mov->xy, ref->xy, lay, sw.node_tri,
@@ -276,10 +249,9 @@ int same_merge_acc_score_detail(same_merge_acc *a, const same_section *mov, cons
         HIP_TRY(ctx, hipGetLastError());
         SAME_COPY(ctx, h.data(), bins, (size_t)words * sizeof(unsigned long long), hipMemcpyDeviceToHost);
         SAME_WAIT(ctx);
-        a->detail_set ^= 1;
-        a->detail_dirty = words;
-        a->score_rows = laid;
-        a->dw.cap = cap;
+        doubt_score.sound();
+        doubt.sound();
+        ds.flip(words);
         if (h[(size_t)lay.bad()]) {
             ctx->err = "same_merge_acc_score_detail: final rows outside the sections (the accumulator's pass ran over other sections)";
             return SAME_ERANGE;

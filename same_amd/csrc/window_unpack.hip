@@ -45,7 +45,7 @@ struct RowLists {
 __device__ __forceinline__ RowLists lists_of(const FinalRec &row, const Lists &l) {
     RowLists out;
     const int32_t a = row.a_row, r = row.r_row;
-    out.inside = (unsigned long long)(long long)a < (unsigned long long)l.n_mov && (unsigned long long)(long long)r < (unsigned long long)l.n_ref;
+    out.inside = followed(row, l.n_mov, l.n_ref);
     if (out.inside) {
         out.a0 = l.moff[a];
         out.r0 = l.roff[r];
@@ -128,8 +128,7 @@ __global__ __launch_bounds__(NT) void unpack_solve_kernel(const FinalRec *__rest
             if (!infeasible)
                 for (int k = 0; k < q.na; ++k) {
                     const int64_t member = q.r0 + (nearest ? col4row[k] : k) % q.nr;
-                    const int32_t c = mcode[q.a0 + k];
-                    agree += c >= 0 && c == rcode[member] ? 1u : 0u;
+                    agree += labels_agree(mcode[q.a0 + k], rcode[member]) ? 1u : 0u;
                     if (out_ref) out_ref[first + k] = member;
                 }
         }
@@ -209,7 +208,7 @@ int same_merge_acc_unpack(same_merge_acc *a, const same_members *mov, const same
                           int64_t *out_ref_member, int64_t capacity) {
     if (!a) return SAME_EINVAL;
     same_ctx *ctx = a->ctx;
-    REQUIRE(ctx, out_counts && a->resolved == 2 && a->merged && !a->loaded);
+    REQUIRE(ctx, out_counts && has_merged_rows(a));
     REQUIRE(ctx, strategy == SAME_UNPACK_DISTRIBUTE || strategy == SAME_UNPACK_NEAREST);
     REQUIRE(ctx, mov && ref && mov->ctx->device == ctx->device && ref->ctx->device == ctx->device);
     REQUIRE(ctx, mov->sec == a->pass_mov && ref->sec == a->pass_ref);
@@ -222,22 +221,16 @@ int same_merge_acc_unpack(same_merge_acc *a, const same_members *mov, const same
         // the largest slice any row of these members can ask for; the scan adds the rows' units in 31 bits
         const int64_t unit_max = slice_units(std::max<int64_t>(mov->max_count, 1), std::max<int64_t>(mov->max_count + ref->max_count, 1));
         REQUIRE(ctx, !nearest || n * unit_max < ((int64_t)1 << 31));
-        if (a->unpack_rows < n || !a->unpack.p) {             // laid for too few rows (or never, or a call failed): lay it, fill it ONCE
-            a->unpack_rows = 0;
-            UnpackWork probe;
-            Carver measure;
-            lay(probe, measure, n);
-            SAME_TRY(ensure(ctx, a->unpack, probe.bytes));
-            Carver place(a->unpack.p);
-            lay(a->uw, place, n);
+        WorkSets &us = a->unpack_sets;
+        if (!us.fits(n)) {
+            InDoubt laying(us);
+            SAME_TRY(lay_over(ctx, a->unpack, a->uw, n));
             SAME_FILL(ctx, a->unpack.p, 0, a->uw.zero_bytes);
-            a->unpack_set = 0;
-            a->unpack_rows = n;
+            us.laid_anew(n);
         }
         const UnpackWork &uw = a->uw;
-        const int64_t laid = a->unpack_rows;
-        a->unpack_rows = 0;                                   // until the call is through: what fails half way leaves the buffer in doubt
-        const int set = a->unpack_set;
+        InDoubt doubt(us);
+        const int set = us.set;
         unsigned long long *totals = uw.totals + (size_t)set * UNPACK_TOTALS, *next = uw.totals + (size_t)(set ^ 1) * UNPACK_TOTALS;
         const FinalRec *fin = static_cast<const FinalRec *>(a->out.p);
         const Lists l{mov->off, ref->off, mov->n_rows, ref->n_rows};
@@ -246,8 +239,8 @@ int same_merge_acc_unpack(same_merge_acc *a, const same_members *mov, const same
         HIP_TRY(ctx, hipGetLastError());
         SAME_COPY(ctx, h, totals, sizeof h, hipMemcpyDeviceToHost);
         SAME_WAIT(ctx);
-        a->unpack_set ^= 1;                                   // the other set is clear; this one the next call's first kernel clears
-        a->unpack_rows = laid;
+        doubt.sound();
+        us.flip();                                            // the call's one flip: the phases below work on in the set it counted into
         if (h[T_FLAGS] & F_OUTSIDE) {
             ctx->err = "same_merge_acc_unpack: final rows outside the members' sections";
             return SAME_ERANGE;
@@ -271,23 +264,23 @@ int same_merge_acc_unpack(same_merge_acc *a, const same_members *mov, const same
                 SAME_TRY(ensure(ctx, a->unpack_pairs, (size_t)pairs * sizeof(int64_t)));
                 dref = static_cast<int64_t *>(a->unpack_pairs.p);
             }
-            a->unpack_rows = 0;
+            InDoubt solving(us);
             for (int64_t c = 0; c < chunks; ++c)
                 SAME_LAUNCH(ctx, unpack_solve_kernel, dim3(grid_for(n)), dim3(NT), 0, fin, n, l, nearest, mov->xy, ref->xy, mov->code, ref->code,
                             uw.pair_off, uw.work_off, c * budget, budget, slices, dref, totals);
             HIP_TRY(ctx, hipGetLastError());
             SAME_COPY(ctx, h, totals, sizeof h, hipMemcpyDeviceToHost);
             SAME_WAIT(ctx);
-            a->unpack_rows = laid;
+            solving.sound();
             if (h[T_FLAGS] & F_INFEASIBLE) {
                 ctx->err = "same_merge_acc_unpack: a cost matrix is infeasible (non-finite coordinates)";
                 return SAME_ERANGE;
             }
             if (write) {
-                a->unpack_rows = 0;
+                InDoubt copying(us);
                 SAME_COPY(ctx, out_ref_member, dref, (size_t)pairs * sizeof(int64_t), hipMemcpyDeviceToHost);
                 SAME_WAIT(ctx);
-                a->unpack_rows = laid;
+                copying.sound();
             }
         }
         out_counts[0] = n;

@@ -26,7 +26,7 @@ import pandas as pd
 
 from . import _lib
 from .eval_utils import _label_codes, check_triangle_violations
-from .scores import (RECORD_KEYS, _frame_rows, _scored_study, checked_score_params, record_from_counts, score_table)
+from .scores import (RECORD_KEYS, _frame_rows, _scored_study, checked_score_params, counts_from_words, record_from_counts, score_table)
 from .triangles import _as_triangle_array
 from .variants import _common_types, _frames_of
 
@@ -282,9 +282,7 @@ class DetailSpec:
         """the device's words of one result (`record["_detail"]`, windows.split_score_detail) as `_frames_of_counts` reads them;
         `total`: the caller's triangle count, None without a triangulation"""
         d = record["_detail"]
-        word = lambda w: {"matched": int(w[0]), "type_matches": int(w[1]), "total_triangles": None if total is None else int(w[2]),
-                          "triangles_with_all_matched": int(w[3]), "triangles_same_type_skipped": int(w[4]), "triangles_flipped": int(w[6]),
-                          "nodes_in_violating_triangles": int(w[7])}
+        word = lambda w: counts_from_words(w, None if total is None else int(w[2]))      # (a group's triangles: the resident ones in it)
         out = {"matched": int(record["matched"]), "confusion": d["confusion"], "unlabelled": d["unlabelled"]}
         if self.group_names is not None:
             n_groups = len(self.group_names)

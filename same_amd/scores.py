@@ -105,6 +105,14 @@ def record_from_counts(counts, score_params=None):
     return rec
 
 
+def counts_from_words(w, total):
+    """The library's eight count words -- same_merge_acc_score's out_counts, a group's record of the detail call -- under
+    `record_from_counts`' keys.  Word 6, not word 5, is `triangles_flipped` (the flipped among the triangles not skipped); `total` is
+    total_triangles (None: no triangulation was scored) -- word 2 leaves out the triangles that name an id the frame lacks."""
+    return {"matched": int(w[0]), "type_matches": int(w[1]), "total_triangles": total, "triangles_with_all_matched": int(w[3]),
+            "triangles_same_type_skipped": int(w[4]), "triangles_flipped": int(w[6]), "nodes_in_violating_triangles": int(w[7])}
+
+
 def _frame_rows(frame_ids, ids, what):
     """rows of a frame named by `ids` through its id column `frame_ids` (an id that names several rows: the last, as the reference's
     dicts keep it)"""
@@ -276,10 +284,8 @@ class DeviceScores:
         """the record of the merged rows `acc` holds after its finish (windows.MergeAccumulator.score)"""
         p = self.params
         c = acc.score(frames.dmov, frames.dref, self.tris, p["ignore_same_type_triangles"], p["node_local"], p["majority_threshold"],
-                      p["min_flips"]).tolist()
-        # (c[2], the triangles resident, leaves out those that name an id the frame lacks; total_triangles is the caller's own count)
-        rec = record_from_counts({"matched": c[0], "type_matches": c[1], "total_triangles": self.total, "triangles_with_all_matched": c[3],
-                                  "triangles_same_type_skipped": c[4], "triangles_flipped": c[6], "nodes_in_violating_triangles": c[7]}, p)
+                      p["min_flips"])
+        rec = record_from_counts(counts_from_words(c, self.total), p)             # (total_triangles: the caller's own count)
         if self.unpack is not None:
             rec.update(self.unpacked(acc))
         if self.detail_dev is not None:

@@ -61,7 +61,7 @@ typedef struct same_sweep same_sweep; /* resident state of one lazy-constraint s
  *         only unless noted)                                          same_knn_prune_indexed_dev, same_padded_cost_*_dev, same_tri_*_dev,
  *                                                                     same_area_flip_dev, same_xyorder_sweep_dev, same_orient_*_dev, same_first_candidate_dev
  * part 3  WINDOW path, sections resident (BASELINE cfg 5)             same_section_*, same_window_*, same_merge_acc_*, same_members_*, same_delaunay2d (host),
- *                                                                     same_delaunay_filtered
+ *                                                                     same_delaunay_filtered, same_unpack_detail_*
  * part 4  COMM: RCCL collectives between the ranks' contexts          same_comm_*, same_allgather_dev*, same_allreduce_dev
  * Every declaration cites the reference lines it replaces (file:line into the reference tree).
  * Measurement hooks and opt-in controls that are NOT the path -- runtime-call counters, timers, the spread allocator, the fixed-point
@@ -893,6 +893,50 @@ void same_members_destroy(same_members *members);
 #define SAME_UNPACK_NEAREST    1
 int same_merge_acc_unpack(same_merge_acc *acc, const same_members *moving, const same_members *ref, int strategy,
                           int64_t *out_counts /* [4] */, int64_t *out_ref_member /* may be NULL */, int64_t capacity);
+/* The unpacked pairs broken down three ways (csrc/window_unpack_detail.hip): by label pair, by group of the moving row, by the rank of
+ * the moving CELL's label among the type columns of the reference CELL it was put on (examples/luad/reproduce_figures.ipynb cell 13) --
+ * binned on the device behind same_merge_acc_unpack's own phases; no pair comes to the host.
+ *   same_unpack_detail_create: what cell pairs are binned by, uploaded once on `ref_members`' context, resident on its device, read-only
+ *   and shared by the worker contexts like same_members; destroy it before its members.  n_labels: the number of CELL-level joint label
+ *   codes, the codes the members were uploaded with.  col_of_label[code] is the type column (of T) the label names, or -1; NULL: no
+ *   label names a column.  ref_member_types: one float64 type row of T columns per reference member, in CSR order; NULL: no type rows.
+ *   Checked on the host before anything is uploaded: SAME_EINVAL for n_labels < 0 or > SAME_SCORE_MAX_LABELS, T < 0, col_of_label given
+ *   without ref_member_types or with T == 0; SAME_ERANGE for a col_of_label value outside [-1, T).  A failure after these checks (an
+ *   allocation, a copy) can leave *out set: destroy a non-null *out whatever the call returned.
+ *   same_merge_acc_unpack_detail: `moving`, `ref`, `strategy` as same_merge_acc_unpack's; `detail` made for `ref`; `groups` (may be NULL:
+ *   one group, 0) a same_score_detail of the moving members' section, of which only group_of and n_groups are read.  With L = n_labels,
+ *   G = groups' n_groups (1 without groups) and R = SAME_SCORE_RANKS, `out` holds out_words >= 4 + L*L + 1 + (G+1)*2 + 2*(R+1) + 1 words
+ *   (SAME_UNPACK_DETAIL_WORDS), in this order:
+ *     counts [4]        exactly same_merge_acc_unpack's out_counts for the same arguments;
+ *     confusion [L*L]   out[4 + cm*L + cr]: the pairs whose moving member's code is cm and whose reference member's code is cr;
+ *     unlabelled [1]    the pairs in no cell: a code that is negative or >= L on either side;
+ *     groups [(G+1)*2]  per bin (pairs, pairs whose two codes are equal and non-negative).  A pair is in the group of its final row's
+ *                       moving section row (group_of[a_row]); bin G takes the pairs whose moving row has no group;
+ *     ranks [2*(R+1)]   for the pair (moving member i, reference member j): c = col_of_label[code of i], v = ref_member_types[j][c],
+ *                       strict = #{t != c: types[j][t] > v}, weak = #{t != c: types[j][t] >= v}, float64 comparisons (the rule of
+ *                       same_merge_acc_score_detail's ranks); first the histogram of min(strict, R), then that of min(weak, R);
+ *     untyped [1]       the pairs in no rank bin: a moving code that is negative or >= L, c < 0, no type rows, a NaN anywhere in the
+ *                       reference member's type row.
+ *   confusion + unlabelled, the groups' pairs, and weak + untyped each sum to counts[1]; the groups' agreeing pairs sum to counts[2].
+ * What the call asks of the runtime for n final rows on the accumulator's context: n == 0 nothing (out is zeros); without a pair what
+ * same_merge_acc_unpack asks (one launch, one copy, one wait); else exactly ONE launch more than same_merge_acc_unpack for the same
+ * rows -- the sizes' launch, one launch per started budget of solver slices, the bins' launch --, THREE copies (64 bytes after the sizes;
+ * 64 bytes and the words of `out` behind its counts after the bins) and TWO waits, the sizes' and the last.  No fill -- but a call that
+ * lays the accumulator's unpack work buffer (same_merge_acc_unpack: the first, and the first over more final rows) fills its head, one
+ * fill, and one that lays the bins' buffer (the first, and the first with more words than any before) fills that, one fill.  Both
+ * buffers are left clear for the next call: both unpack calls, same_merge_acc_score and same_merge_acc_score_detail alternate on one
+ * accumulator without a fill.
+ * SAME_EINVAL / SAME_ERANGE as same_merge_acc_unpack, `out` untouched -- under NEAREST an infeasible row's pairs are never read, its
+ * entries are marked on the device; SAME_EINVAL also for a `detail` made for other reference members, `groups` made for another section
+ * than the moving members', and out_words too small. */
+#define SAME_UNPACK_DETAIL_WORDS(L, G) (4 + (int64_t)(L) * (L) + 1 + ((int64_t)(G) + 1) * 2 + 2 * (SAME_SCORE_RANKS + 1) + 1)
+typedef struct same_unpack_detail same_unpack_detail;
+int  same_unpack_detail_create(const same_members *ref_members, int n_labels, const int32_t *col_of_label /* [n_labels] or NULL */,
+                               const double *ref_member_types /* [m][T] or NULL */, int T, same_unpack_detail **out);
+void same_unpack_detail_destroy(same_unpack_detail *detail);
+int  same_merge_acc_unpack_detail(same_merge_acc *acc, const same_members *moving, const same_members *ref, int strategy,
+                                  const same_unpack_detail *detail, const same_score_detail *groups /* may be NULL: one group */,
+                                  int64_t *out, int64_t out_words);
 
 /* ======================================================================================================================
  * part 4 -- COMM: one communicator per context, RCCL over xGMI

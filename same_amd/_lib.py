@@ -149,6 +149,9 @@ _PROTOTYPES = {
     "same_members_create": [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(c_vp)],
     "same_members_destroy": [c_vp],
     "same_merge_acc_unpack": [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_i64],
+    "same_unpack_detail_create": [c_vp, c_int, c_vp, c_vp, c_int, ctypes.POINTER(c_vp)],
+    "same_unpack_detail_destroy": [c_vp],
+    "same_merge_acc_unpack_detail": [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_i64],
     "same_host_alloc": [c_vp, c_sz, ctypes.POINTER(c_vp)],
     "same_host_free": [c_vp, c_vp],
     "same_comm_unique_id": [c_vp],
@@ -221,6 +224,7 @@ def load():
             L.same_types_layer_destroy.restype = None
             L.same_members_destroy.restype = None
             L.same_score_detail_destroy.restype = None
+            L.same_unpack_detail_destroy.restype = None
             if L.same_abi_version() != ABI_VERSION:
                 raise SameHipError(-22, "libsame_hip ABI version mismatch")
             _lib = L

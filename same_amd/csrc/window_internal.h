@@ -1,5 +1,5 @@
 // window_internal.h -- what the translation units of the device-resident window path share (section.hip, window_stage.hip,
-// window_finish.hip, window_merge.hip, window_score.hip, window_score_detail.hip, window_unpack.hip, window_caller.hip, window_priority.hip, window_knn_prefix.hip, window_recost.hip): the resident objects behind the
+// window_finish.hip, window_merge.hip, window_score.hip, window_score_detail.hip, window_unpack.hip, window_unpack_detail.hip, window_caller.hip, window_priority.hip, window_knn_prefix.hip, window_recost.hip): the resident objects behind the
 // opaque handles of include/same_hip.h part 4, the per-launch argument blocks, the device side of a window's pair list, the window's
 // logical state (window_state.h: win::State, with the table of what each call requires, leaves and invalidates), the protocol of the merged
 // rows' reader calls (work_sets.h: win::WorkSets), the small host helpers and the batch driver of the window calls.
@@ -434,6 +434,17 @@ struct same_score_detail {
     int32_t *col_of_label = nullptr; // [n_labels] in [-1, mov->T); null: no label names a column
 };
 
+// What same_merge_acc_unpack_detail bins cell pairs by, resident (same_unpack_detail_create, window_unpack_detail.hip): per cell-level
+// label code the type column the label names, per reference member its type row.  Read-only after its creation: shared by the worker
+// contexts of its device like its members; it must not outlive them.
+struct same_unpack_detail {
+    same_ctx *ctx = nullptr;
+    const same_members *ref = nullptr;
+    int n_labels = 0, T = 0;
+    int32_t *col_of_label = nullptr; // [n_labels] in [-1, T); null: no label names a column
+    double *types = nullptr;         // [ref->m][T] in CSR order; null: no type rows
+};
+
 // The rows of one pass over a window plan on one context (window_merge.hip), and what window_score.hip reads of them.
 struct same_merge_acc {
     same_ctx *ctx = nullptr;
@@ -472,6 +483,10 @@ struct same_merge_acc {
     win::DevBuf unpack, unpack_slices, unpack_pairs;   // the work buffer; the solver's slices (bounded); the pairs' reference members
     win::UnpackWork uw;                       // laid over `unpack`
     win::WorkSets unpack_sets;                // ... for so many final rows; a set: look-back words and totals
+    // same_merge_acc_unpack_detail (window_unpack_detail.hip): it runs same_merge_acc_unpack's phases in `uw`, and bins the pairs in
+    win::DevBuf unpack_bins;                  // (released by same_merge_acc_destroy with the buffers above: a DevBuf added here joins its list)
+    win::DetailWork ubw;                      // laid over `unpack_bins`: two sets of so many words
+    win::WorkSets unpack_bin_sets;            // ... for so many words a set
 };
 
 namespace win {
@@ -524,6 +539,28 @@ __device__ __forceinline__ bool followed(const FinalRec &row, int64_t n_mov, int
 // do two joint label codes agree: a negative code equals nothing
 __device__ __forceinline__ bool labels_agree(int32_t a, int32_t b) { return a >= 0 && a == b; }
 
+// the bin of a moving row under `group_of` over G groups (null: every row in group 0): its group, or G -- the bin of the rows without one
+__device__ __forceinline__ int group_at(const int32_t *__restrict__ group_of, int64_t row, int G) {
+    const int32_t g = group_of ? group_of[row] : 0;
+    return g >= 0 && g < G ? g : G;               // (create refused g >= G)
+}
+// the rank of type column c in a reference type row of T float64 columns: with v = row[c], how many OTHER columns hold a value > v
+// (strict) and how many one >= v (weak) -> whether the row ranks at all: a NaN anywhere in it ranks nothing
+__device__ __forceinline__ bool type_rank(const double *__restrict__ row, int T, int c, int &strict, int &weak) {
+    const double v = row[c];
+    strict = weak = 0;
+    bool nan = v != v;
+    for (int t = 0; t < T; ++t) {
+        const double x = row[t];
+        nan |= x != x;
+        if (t != c) {
+            strict += x > v ? 1 : 0;
+            weak += x >= v ? 1 : 0;
+        }
+    }
+    return !nan;
+}
+
 // a resident triangle (a, b, c: rows of the moving section): all three corners matched?  then, under ignore_same, the same-type rule on
 // the moving codes, and the flip rule on the moving XY and the matched reference XY (devmath.h: eval_area3, eval_flipped).  A triangle
 // that is not all matched loads neither codes nor XY.  (Filled in place: returned by value the three flags travel packed, in VGPRs.)
@@ -558,6 +595,25 @@ __device__ __forceinline__ void reset_idle(int32_t a, int32_t *match_of, unsigne
     node_tri[a] = 0u;
     node_flip[a] = 0u;
 }
+
+// window_unpack.hip: the phases of same_merge_acc_unpack, once, for the calls that unpack -- sizes and their scan, the wait for them,
+// the solve launches, the call's last wait.  A PairReader rides between the last solve launch and that wait: the pairs then stay on the
+// device (reference member int64 and flat moving member int32 per pair, -1 for the pairs of an infeasible row) and nothing of them is
+// copied to the host.
+struct DevicePairs {
+    const int64_t *ref_member = nullptr;     // [pairs] flat index into the reference members' CSR, -1: the row was infeasible
+    const int32_t *mov_member = nullptr;     // [pairs] flat index into the moving members' CSR, -1 likewise
+    int64_t pairs = 0;
+};
+struct PairReader {
+    WorkSets *sets = nullptr;                // the protocol of the reader's own buffer: in doubt whenever the unpack buffer is
+    int64_t counted = 0;                     // words of its set the reader's kernel counted into (enqueue says): the flip's argument
+    virtual int lay(same_ctx *ctx) = 0;                               // before the first enqueue: its buffer laid (and filled, if anew)
+    virtual int enqueue(same_ctx *ctx, const DevicePairs &p) = 0;     // its launch and its copy back, behind the last solve launch
+    virtual ~PairReader() = default;
+};
+int unpack_run(same_merge_acc *a, const same_members *mov, const same_members *ref, int strategy, int64_t *out_counts,
+               int64_t *out_ref_member, int64_t capacity, PairReader *reader);
 
 // section.hip
 int knn_index_for(same_ctx *ctx, const same_section *ref, double radius, std::shared_ptr<same_knn_index> *out);

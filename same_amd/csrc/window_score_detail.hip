@@ -46,11 +46,6 @@ __device__ __forceinline__ void flush_lds(int words, unsigned long long *__restr
     }
 }
 
-__device__ __forceinline__ int group_at(const int32_t *__restrict__ group_of, int32_t row, int G) {
-    const int32_t g = group_of ? group_of[row] : 0;
-    return g >= 0 && g < G ? g : G;               // (create refused g >= G)
-}
-
 // LDS: [L*L confusion | unlabelled | (G+1) x (rows, type matches) | strict[R+1] | weak[R+1] | untyped | bad]
 __global__ __launch_bounds__(NT) void detail_rows_kernel(const FinalRec *__restrict__ rows, int64_t n, int64_t n_mov, int64_t n_ref,
                                                          const int32_t *__restrict__ code_m, const int32_t *__restrict__ code_r,
@@ -80,19 +75,8 @@ __global__ __launch_bounds__(NT) void detail_rows_kernel(const FinalRec *__restr
         const int c = lm && col_of_label ? col_of_label[cm] : -1;
         bool typed = c >= 0 && c < T;
         if (typed) {
-            const double *__restrict__ row = types_r + (int64_t)r * T;
-            const double v = row[c];
-            int strict = 0, weak = 0;
-            bool nan = v != v;
-            for (int t = 0; t < T; ++t) {
-                const double x = row[t];
-                nan |= x != x;
-                if (t != c) {
-                    strict += x > v ? 1 : 0;
-                    weak += x >= v ? 1 : 0;
-                }
-            }
-            typed = !nan;
+            int strict, weak;
+            typed = type_rank(types_r + (int64_t)r * T, T, c, strict, weak);
             if (typed) {
                 atomicAdd(&lds_bins[o_strict + (strict < R ? strict : R)], 1u);
                 atomicAdd(&lds_bins[o_weak + (weak < R ? weak : R)], 1u);

@@ -18,6 +18,10 @@
 //
 // The slices' buffer is bounded: rows whose slices start in [c * budget, (c + 1) * budget) are one launch of the solve kernel, and the
 // buffer holds a budget plus one largest slice -- it does not grow with the section.  Every count is an integer.
+//
+// The phases are stated once, in win::unpack_run: same_merge_acc_unpack is that function, and same_merge_acc_unpack_detail
+// (window_unpack_detail.hip) is that function with a win::PairReader -- the pairs then stay on the device, with their moving members
+// beside them, and the reader's one kernel bins them between the last solve launch and the call's last wait.
 #include "assign_solve.h"
 #include "window_internal.h"
 
@@ -104,13 +108,15 @@ __global__ __launch_bounds__(NT) void unpack_size_kernel(const FinalRec *__restr
     }
 }
 
-// rows whose slice starts in [lo, lo + span) units (DISTRIBUTE: every row, no slices); out_ref null: only the count
+// rows whose slice starts in [lo, lo + span) units (DISTRIBUTE: every row, no slices); out_ref null: only the count; out_mov (with
+// out_ref, for a reader of the pairs on the device): the pair's flat moving member too, and -1 in both for the pairs of an infeasible row
 __global__ __launch_bounds__(NT) void unpack_solve_kernel(const FinalRec *__restrict__ rows, int64_t n, Lists l, int nearest,
                                                           const double *__restrict__ mxy, const double *__restrict__ rxy,
                                                           const int32_t *__restrict__ mcode, const int32_t *__restrict__ rcode,
                                                           const unsigned *__restrict__ pair_off, const unsigned *__restrict__ work_off,
                                                           int64_t lo, int64_t span, double *__restrict__ slices,
-                                                          int64_t *__restrict__ out_ref, unsigned long long *__restrict__ totals) {
+                                                          int64_t *__restrict__ out_ref, int32_t *__restrict__ out_mov,
+                                                          unsigned long long *__restrict__ totals) {
     __shared__ unsigned part[NT / 64];
     const int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x;
     unsigned agree = 0u;
@@ -130,6 +136,12 @@ __global__ __launch_bounds__(NT) void unpack_solve_kernel(const FinalRec *__rest
                     const int64_t member = q.r0 + (nearest ? col4row[k] : k) % q.nr;
                     agree += labels_agree(mcode[q.a0 + k], rcode[member]) ? 1u : 0u;
                     if (out_ref) out_ref[first + k] = member;
+                    if (out_mov) out_mov[first + k] = (int32_t)(q.a0 + k);
+                }
+            else if (out_mov)                      // a reader of the pairs on the device skips them: nothing of this row is a pair
+                for (int k = 0; k < q.na; ++k) {
+                    out_ref[first + k] = -1;
+                    out_mov[first + k] = -1;
                 }
         }
     }
@@ -206,6 +218,17 @@ void same_members_destroy(same_members *mb) {
 
 int same_merge_acc_unpack(same_merge_acc *a, const same_members *mov, const same_members *ref, int strategy, int64_t *out_counts,
                           int64_t *out_ref_member, int64_t capacity) {
+    return win::unpack_run(a, mov, ref, strategy, out_counts, out_ref_member, capacity, nullptr);
+}
+
+}  // extern "C"
+
+namespace win {
+
+// The calls that unpack (same_merge_acc_unpack: reader null; same_merge_acc_unpack_detail: its bins kernel the reader) -- every phase
+// stated here alone.  With a reader nothing is written through out_ref_member and out_counts is written only by a call that succeeds.
+int unpack_run(same_merge_acc *a, const same_members *mov, const same_members *ref, int strategy, int64_t *out_counts,
+               int64_t *out_ref_member, int64_t capacity, PairReader *reader) {
     if (!a) return SAME_EINVAL;
     same_ctx *ctx = a->ctx;
     REQUIRE(ctx, out_counts && has_merged_rows(a));
@@ -213,6 +236,7 @@ int same_merge_acc_unpack(same_merge_acc *a, const same_members *mov, const same
     REQUIRE(ctx, mov && ref && mov->ctx->device == ctx->device && ref->ctx->device == ctx->device);
     REQUIRE(ctx, mov->sec == a->pass_mov && ref->sec == a->pass_ref);
     REQUIRE(ctx, !out_ref_member || capacity >= 0);
+    REQUIRE(ctx, !reader || !out_ref_member);
     SAME_TRY(same_use(ctx));
     const int nearest = strategy == SAME_UNPACK_NEAREST;
     const int64_t n = a->n_final;
@@ -228,8 +252,11 @@ int same_merge_acc_unpack(same_merge_acc *a, const same_members *mov, const same
             SAME_FILL(ctx, a->unpack.p, 0, a->uw.zero_bytes);
             us.laid_anew(n);
         }
+        if (reader) SAME_TRY(reader->lay(ctx));
+        WorkSets nobody;
+        WorkSets &rs = reader ? *reader->sets : nobody;       // the reader's buffer is in doubt whenever this one is
         const UnpackWork &uw = a->uw;
-        InDoubt doubt(us);
+        InDoubt doubt(us), doubt_reader(rs);
         const int set = us.set;
         unsigned long long *totals = uw.totals + (size_t)set * UNPACK_TOTALS, *next = uw.totals + (size_t)(set ^ 1) * UNPACK_TOTALS;
         const FinalRec *fin = static_cast<const FinalRec *>(a->out.p);
@@ -240,6 +267,7 @@ int same_merge_acc_unpack(same_merge_acc *a, const same_members *mov, const same
         SAME_COPY(ctx, h, totals, sizeof h, hipMemcpyDeviceToHost);
         SAME_WAIT(ctx);
         doubt.sound();
+        doubt_reader.sound();
         us.flip();                                            // the call's one flip: the phases below work on in the set it counted into
         if (h[T_FLAGS] & F_OUTSIDE) {
             ctx->err = "same_merge_acc_unpack: final rows outside the members' sections";
@@ -256,22 +284,28 @@ int same_merge_acc_unpack(same_merge_acc *a, const same_members *mov, const same
             const int64_t budget = budget_units(), chunks = nearest ? std::max<int64_t>((units + budget - 1) / budget, 1) : 1;
             double *slices = nullptr;
             int64_t *dref = nullptr;
+            int32_t *dmov = nullptr;
             if (nearest) {
                 SAME_TRY(ensure(ctx, a->unpack_slices, (size_t)(chunks > 1 ? budget + unit_max : units) * UNPACK_UNIT * 8));
                 slices = static_cast<double *>(a->unpack_slices.p);
             }
-            if (write) {
-                SAME_TRY(ensure(ctx, a->unpack_pairs, (size_t)pairs * sizeof(int64_t)));
+            if (write || reader) {
+                // [pairs] int64 reference members, then -- for a reader -- [pairs] int32 moving members
+                SAME_TRY(ensure(ctx, a->unpack_pairs, (size_t)pairs * (sizeof(int64_t) + (reader ? sizeof(int32_t) : 0))));
                 dref = static_cast<int64_t *>(a->unpack_pairs.p);
+                if (reader) dmov = reinterpret_cast<int32_t *>(dref + pairs);
             }
-            InDoubt solving(us);
+            InDoubt solving(us), solving_reader(rs);
             for (int64_t c = 0; c < chunks; ++c)
                 SAME_LAUNCH(ctx, unpack_solve_kernel, dim3(grid_for(n)), dim3(NT), 0, fin, n, l, nearest, mov->xy, ref->xy, mov->code, ref->code,
-                            uw.pair_off, uw.work_off, c * budget, budget, slices, dref, totals);
+                            uw.pair_off, uw.work_off, c * budget, budget, slices, dref, dmov, totals);
             HIP_TRY(ctx, hipGetLastError());
+            if (reader) SAME_TRY(reader->enqueue(ctx, DevicePairs{dref, dmov, pairs}));
             SAME_COPY(ctx, h, totals, sizeof h, hipMemcpyDeviceToHost);
             SAME_WAIT(ctx);
             solving.sound();
+            solving_reader.sound();
+            if (reader) rs.flip(reader->counted);             // (whatever the answer: the next call clears what this one counted)
             if (h[T_FLAGS] & F_INFEASIBLE) {
                 ctx->err = "same_merge_acc_unpack: a cost matrix is infeasible (non-finite coordinates)";
                 return SAME_ERANGE;
@@ -297,4 +331,4 @@ int same_merge_acc_unpack(same_merge_acc *a, const same_members *mov, const same
     return SAME_OK;
 }
 
-}  // extern "C"
+}  // namespace win

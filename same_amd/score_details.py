@@ -14,8 +14,11 @@ result TABLE with the functions the package already has: what the device must eq
 `top_k_counts` is the host statement of the rank rule; it works on any list of pairs, so the cell-level top-k of an unpacked table is
 one call of it on `cell_tables`.
 
-Not counted on the device: cell-level (`unpack=`) confusion and rank counts.  They need the members' type rows resident and a change to
-the unpack kernel; `top_k_counts` on the unpacked table gives them on the host."""
+With MetaCell objects and `unpack=` the same three readings are made at CELL level as well: the notebook's FigS19 asks
+of every unpacked cell pair whether the moving cell's label is among the k largest type columns of the reference CELL it was put on --
+another number than the metacell rows' rank count, a metacell's type row being a mean over its members.  The pairs are binned where the
+unpack call makes them (csrc/window_unpack_detail.hip: the reference members' type rows resident, one kernel behind the solve kernel);
+`score_unpacked_details` is the host statement per table, and what the device refuses goes through it."""
 import collections
 import collections.abc
 import numbers
@@ -26,14 +29,23 @@ import pandas as pd
 
 from . import _lib
 from .eval_utils import _label_codes, check_triangle_violations
-from .scores import (RECORD_KEYS, _frame_rows, _scored_study, checked_score_params, counts_from_words, record_from_counts, score_table)
+from .scores import (RECORD_KEYS, UNPACK_KEYS, _frame_rows, _scored_study, checked_score_params, checked_unpack, counts_from_words,
+                     record_from_counts, score_table, score_unpacked, unpack_record)
 from .triangles import _as_triangle_array
 from .variants import _common_types, _frames_of
 
 ScoreDetails = collections.namedtuple("ScoreDetails", "scores confusion groups cross top_k")
+CellDetails = collections.namedtuple("CellDetails", "cell_confusion cell_groups cell_cross cell_top_k")
+CellScoreDetails = collections.namedtuple("CellScoreDetails", ScoreDetails._fields + CellDetails._fields)
 MAX_TOP_K = _lib.SAME_SCORE_RANKS
 # the cross record: RECORD_KEYS without the node counts (a node is counted in its own group)
 CROSS_KEYS = tuple(k for k in RECORD_KEYS if k not in ("nodes_in_violating_triangles", "percent_nodes_violating"))
+
+
+class _NoMetaCellObjects(ValueError, TypeError):
+    """`sliding_window_score_details(unpack=...)` over something that is no MetaCell object.  Callers are told ValueError, as for every
+    refusal; it is a TypeError too only because the call raised that for `unpack` over plain frames before it had the keyword
+    (tests/test_score_details_cpu.py still asserts it).  Private: to become a plain ValueError once that assertion is retired."""
 
 
 # ---- arguments ---------------------------------------------------------------------------------------------------------------------------
@@ -259,6 +271,84 @@ def score_table_details(table, ref, moving, *, cell_id_col, commonCT, group_by=N
     return ScoreDetails(scores, *_frames_of_counts(counts, labels, group_names, ks, p))
 
 
+# ---- at cell level: the unpacked pairs ---------------------------------------------------------------------------------------------------
+def _cell_frames_of_counts(counts, labels, group_names, ks):
+    """One table's `CellDetails` from its integer counts: `pairs`; `confusion` (L, L) over the cell-level labels; `groups` a (pairs,
+    agreeing pairs) per group and `cross` one for the rest (None: no groups asked for); `ranks` top_k_counts' dict (None: no top_k)"""
+    over = lambda a, b: float(a) / float(b) if b else float("nan")
+    confusion = pd.DataFrame(np.asarray(counts["confusion"], np.int64).reshape(len(labels), len(labels)),
+                             index=pd.Index(labels, dtype=object, name="moving_label"), columns=pd.Index(labels, dtype=object))
+    groups = cross = top = None
+    if group_names is not None:
+        groups = pd.DataFrame([{"group": name, **unpack_record(*c)} for name, c in zip(group_names, counts["groups"])],
+                              columns=("group",) + UNPACK_KEYS)
+        cross = pd.DataFrame([unpack_record(*counts["cross"])], columns=UNPACK_KEYS)
+    if ks:
+        ranks, pairs = counts["ranks"], int(counts["pairs"])
+        row = {"typed_rows": ranks["typed_rows"]}
+        for k in ks:
+            row.update({f"top{k}_matches": ranks[f"top{k}_matches"], f"top{k}_tied": ranks[f"top{k}_tied"],
+                        f"top{k}_accuracy": 100 * over(ranks[f"top{k}_matches"], pairs)})
+        top = pd.DataFrame([row])
+    return CellDetails(confusion, groups, cross, top)
+
+
+def score_unpacked_details(table, ref_mc, moving_mc, strategy, *, commonCT, group_by=None, top_k=None, cells=None):
+    """`CellDetails` of ONE result table over the MetaCell objects `ref_mc` and `moving_mc`, with the functions the package already has
+    -- what `sliding_window_score_details(unpack=strategy)` must equal per table, without the `variant` and `set` columns, and what it
+    falls back to.  The pairs are `score_unpacked`'s unpacked table (examples/luad/reproduce_figures.ipynb cell 12), which lists them in
+    the order of the table's rows and of each moving row's members:
+      cell_confusion  rows the moving cells' labels, one int64 column per reference cell label, labels in the order of the joint codes
+                      of the two objects' `original_df[cell_type_col]` (`joint_labels`); np.bincount over the codes;
+      cell_groups     one row per group of `group_by` -- a column of `moving_mc.metacell_df` or an array of its length; a pair is in its
+                      metacell row's group, np.repeat of the row's group over its member count --: `group` and UNPACK_KEYS;
+      cell_cross      one row: UNPACK_KEYS over the pairs of rows without a group;
+      cell_top_k      one row: `top_k_counts` of (the moving cell's label, `ref_mc.original_df[commonCT]` at the row of Ref_cell_id) --
+                      the notebook's cell 13 --, and `top{k}_accuracy` = 100 * matches / cells_matched.
+    `cell_groups` and `cell_cross` are None without `group_by`, `cell_top_k` is None without `top_k`.  `cells`: `score_unpacked`'s unpacked
+    table of `table` under `strategy` where the caller has it already (it is not made again)."""
+    ks = checked_top_k(top_k)
+    columns = list(commonCT)
+    group_codes, group_names = checked_groups(group_by, moving_mc.metacell_df)
+    if cells is None:
+        _record, cells = score_unpacked(table, ref_mc, moving_mc, strategy)
+    n = len(cells)
+    mov_labels, ref_labels = (mc.original_df[mc.cell_type_col].to_numpy() for mc in (moving_mc, ref_mc))
+    code_m, code_r, labels = joint_labels(mov_labels, ref_labels)
+    L = len(labels)
+    rows_of = lambda mc, ids, what: _frame_rows(mc.original_df[mc.original_idx_col].to_numpy(), ids.to_numpy(), what)
+    rows_m = rows_of(moving_mc, cells["Aligned_cell_id"], "moving") if n else np.zeros(0, np.int64)
+    rows_r = rows_of(ref_mc, cells["Ref_cell_id"], "reference") if n else np.zeros(0, np.int64)
+    cm, cr = code_m[rows_m].astype(np.int64), code_r[rows_r].astype(np.int64)
+    in_cell = (cm >= 0) & (cr >= 0)
+    agree = (cm >= 0) & (cm == cr)
+    counts = {"pairs": n, "confusion": np.bincount(cm[in_cell] * L + cr[in_cell], minlength=L * L).astype(np.int64),
+              "unlabelled": int(n - in_cell.sum())}
+    if group_codes is not None:
+        lists = moving_mc.metacell_df["members"].tolist()
+        a_ids = table["Aligned_metacell_id"].to_numpy().astype(np.int64) if n else np.zeros(0, np.int64)
+        pair_group = np.repeat(group_codes[a_ids], [len(lists[a]) for a in a_ids.tolist()]) if n else np.zeros(0, np.int32)
+        assert len(pair_group) == n
+        counts["groups"] = [(int(np.count_nonzero(pair_group == g)), int(np.count_nonzero(agree & (pair_group == g))))
+                            for g in range(len(group_names))]
+        counts["cross"] = (int(np.count_nonzero(pair_group < 0)), int(np.count_nonzero(agree & (pair_group < 0))))
+    if ks:
+        types = ref_mc.original_df[columns].to_numpy(dtype=np.float64)[rows_r] if n else np.zeros((0, len(columns)))
+        counts["ranks"] = top_k_counts(mov_labels[rows_m], types, columns, ks)
+    return _cell_frames_of_counts(counts, labels, group_names, ks)
+
+
+def _cell_counts_of_words(d, group_names, ks):
+    """the device's words of one result (windows.split_unpack_detail) as `_cell_frames_of_counts` reads them"""
+    out = {"pairs": int(d["counts"][1]), "confusion": d["confusion"], "unlabelled": d["unlabelled"]}
+    if group_names is not None:
+        out["groups"] = [tuple(int(x) for x in w) for w in d["groups"][:len(group_names)]]
+        out["cross"] = tuple(int(x) for x in d["groups"][len(group_names):].sum(axis=0))     # (no group at all: as DetailSpec.counts)
+    if ks:
+        out["ranks"] = _top_k_from_histograms(d["strict"], d["weak"], ks)
+    return out
+
+
 # ---- on the device -------------------------------------------------------------------------------------------------------------------------
 class DetailSpec:
     """What `scores.DeviceScores` breaks every record down by: the moving rows' group codes and names (None: no groups), the ks."""
@@ -300,7 +390,7 @@ class DetailSpec:
 def sliding_window_score_details(ref, moving, commonCT=None, *, group_by=None, top_k=None, type_variants=None, param_sets=None,
                                  optim_params=None, gurobi_params=None, score_delaunay=None, score_delaunay_vertex_col=None,
                                  score_params=None, workers=None, triangulator=None, ctx=None, batch=None, moving_delaunay=None,
-                                 moving_delaunay_vertex_col=None):
+                                 moving_delaunay_vertex_col=None, unpack=None):
     """`sliding_window_scores` with every record broken down three ways, over the same one pass of the windows and still without a table:
     -> `ScoreDetails`
       scores     exactly `sliding_window_scores`' frame for the same arguments;
@@ -314,16 +404,34 @@ def sliding_window_score_details(ref, moving, commonCT=None, *, group_by=None, t
                  `top{k}_accuracy` = 100 * matches / matched.
     `group_by`: a column of the moving frame (a MetaCell object's `metacell_df`) or an array of its length; missing values mean no
     group; groups in pd.factorize order; None: `groups` and `cross` are None.  `top_k`: a set of ints in 1..16, the ranks are read from
-    the reference frame's commonCT columns; None: `top_k` is None.  The other keywords are `sliding_window_scores`' but for `tables` and
-    `unpack`; a `group_by` that is neither, a `top_k` outside the range and what `sliding_window_scores` refuses raise ValueError before
-    a job or a device is touched.
+    the reference frame's commonCT columns; None: `top_k` is None.  The other keywords are `sliding_window_scores`' but for `tables`;
+    a `group_by` that is neither, a `top_k` outside the range and what `sliding_window_scores` refuses raise ValueError before a job or
+    a device is touched.
     Counted on the device from every result's merged rows (csrc/window_score_detail.hip: the detail call beside the score call).  What
     `scores.DeviceScores.prepare` refuses, and more labels or groups than the library's caps (64, 256), go through
-    `score_table_details` on the tables: the same frames, nothing saved.  Cell-level (`unpack=`) confusion and rank counts are not
-    offered here: `top_k_counts` on an unpacked table gives them on the host."""
+    `score_table_details` on the tables: the same frames, nothing saved.
+    `unpack` ("distribute" / "nearest"; `ref` and `moving` MetaCell objects, `checked_unpack`'s rules): -> `CellScoreDetails`, the five
+    fields above -- `scores` with UNPACK_KEYS, as `sliding_window_scores(unpack=)` gives them -- and the same readings of the unpacked
+    CELL pairs (examples/luad/reproduce_figures.ipynb cells 12, 13):
+      cell_confusion  indexed by (variant, set, moving_label) over the cell-level labels (`joint_labels` of the two objects'
+                      `original_df[cell_type_col]`), one int64 column per reference cell label;
+      cell_groups     one row per (variant, set, group): `group` and UNPACK_KEYS over the pairs whose metacell row is in the group;
+      cell_cross      one row per (variant, set): UNPACK_KEYS over the pairs of rows without a group;
+      cell_top_k      one row per (variant, set): `typed_rows`, `top{k}_matches`, `top{k}_tied` over (the moving cell's label, the type
+                      row `ref.original_df[commonCT]` of the reference cell it was put on) and `top{k}_accuracy` = 100 * matches /
+                      cells_matched; with `top_k`, a commonCT column `ref.original_df` lacks raises ValueError first.
+    The group and top-k frames are None without `group_by` / `top_k`.  On the device ONE call per result takes the unpack call's place
+    and bins the pairs where they are made (csrc/window_unpack_detail.hip); objects `DeviceScores.device_members` refuses, more than 64
+    cell labels and whatever keeps the job off the shared pass go through `score_unpacked_details` on every table: the same frames."""
     params = checked_score_params(score_params)
     ks = checked_top_k(top_k)
     ref_arg, moving_arg, ref_df, mov_df = _frames_of(ref, moving)
+    checked_unpack(unpack, ref_arg, moving_arg, no_objects=_NoMetaCellObjects)
+    if unpack is not None and ks:
+        cell_cts = _common_types(ref_arg, moving_arg, ref_df, mov_df, commonCT)
+        lacking = [c for c in cell_cts if c not in ref_arg.original_df.columns]
+        if lacking:
+            raise ValueError(f"top_k with unpack={unpack!r} ranks the reference cells' type columns: ref.original_df has no {lacking}")
     group_codes, group_names = checked_groups(group_by, mov_df)
     group_values = mov_df[group_by].to_numpy() if isinstance(group_by, str) else group_by       # (the host route's frames may be copies)
     spec = DetailSpec(group_codes, group_names, ks)
@@ -331,7 +439,7 @@ def sliding_window_score_details(ref, moving, commonCT=None, *, group_by=None, t
                                          gurobi_params=gurobi_params, score_delaunay=score_delaunay,
                                          score_delaunay_vertex_col=score_delaunay_vertex_col, score_params=params, tables=False,
                                          workers=workers, triangulator=triangulator, ctx=ctx, batch=batch, moving_delaunay=moving_delaunay,
-                                         moving_delaunay_vertex_col=moving_delaunay_vertex_col, unpack=None, detail=spec)
+                                         moving_delaunay_vertex_col=moving_delaunay_vertex_col, unpack=unpack, detail=spec)
     n_sets = len(nested[0])
     job = hook.job
     if hook.records is not None:
@@ -344,4 +452,14 @@ def sliding_window_score_details(ref, moving, commonCT=None, *, group_by=None, t
                                          group_by=group_values, top_k=ks or None, score_delaunay=tri,
                                          score_delaunay_vertex_col=vertex_col, score_params=params, ctx=ctx)[1:]
                      for per_set in nested for t in per_set]
-    return ScoreDetails(scores, *_stacked(per_table, n_sets))
+    if unpack is None:
+        return ScoreDetails(scores, *_stacked(per_table, n_sets))
+    if hook.records is not None:
+        cells = [_cell_frames_of_counts(_cell_counts_of_words(rec["_cell_detail"], group_names, ks), hook.cell_dev.labels, group_names, ks)
+                 for rec in hook.records]
+    else:                                               # the host statement on every table
+        cts = _common_types(ref_arg, moving_arg, ref_df, mov_df, commonCT)
+        tables = [t for per_set in nested for t in per_set]             # (hook.cell_tables: `_scored_study` unpacked every table already)
+        cells = [score_unpacked_details(t, ref_arg, moving_arg, unpack, commonCT=cts, group_by=group_values, top_k=ks or None, cells=c)
+                 for t, c in zip(tables, hook.cell_tables)]
+    return CellScoreDetails(scores, *_stacked(per_table, n_sets), *_stacked(cells, n_sets))

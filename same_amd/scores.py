@@ -175,9 +175,9 @@ def unpack_record(cells_matched, cell_type_matches):
     return {"cells_matched": n, "cell_type_matches": k, "cell_accuracy": (k / n) * 100 if n else float("nan")}
 
 
-def checked_unpack(unpack, ref, moving):
+def checked_unpack(unpack, ref, moving, no_objects=ValueError):
     """ValueError unless `unpack` is None or a strategy and, with a strategy, `ref` and `moving` are MetaCell-like objects: `metacell_df`
-    with a `members` column of lists, `original_df`, `original_idx_col`"""
+    with a `members` column of lists, `original_df`, `original_idx_col` (`no_objects`: the ValueError raised for an object without them)"""
     if unpack is None:
         return
     if not isinstance(unpack, str) or unpack not in UNPACK_STRATEGIES:
@@ -185,7 +185,7 @@ def checked_unpack(unpack, ref, moving):
     for obj, name in ((ref, "ref"), (moving, "moving")):
         lacking = [f for f in ("metacell_df", "original_df", "original_idx_col") if not hasattr(obj, f)]
         if lacking:
-            raise ValueError(f"unpack={unpack!r} reads MetaCell objects on both sides: {name} has no {lacking}")
+            raise no_objects(f"unpack={unpack!r} reads MetaCell objects on both sides: {name} has no {lacking}")
         frame = obj.metacell_df
         if "members" not in getattr(frame, "columns", ()) or not all(isinstance(m, list) for m in frame["members"].tolist()):
             raise ValueError(f"unpack={unpack!r}: {name}.metacell_df has no 'members' column of lists")
@@ -220,6 +220,7 @@ class DeviceScores:
         self.detail, self.detail_dev = detail, None
         self.unpack, self.ref_mc, self.moving_mc = unpack, ref_mc, moving_mc      # the strategy (None: metacell level only), the two objects
         self.members = None      # (moving, reference) windows.DeviceMembers once `prepare` agreed
+        self.cell_dev = None     # with `unpack` and `detail`: what the cell pairs are binned by (windows.DeviceUnpackDetail) once `prepare` agreed
         self.cell_tables = []    # with tables: the unpacked table per job, in the jobs' order
         self.job = None          # the first job of the pass (sliding_window_variants tells): MetaCell unwrapping, cell_id_col, its triangulation
         self.records = None      # [record per job, variants outermost] once the device scored them
@@ -257,6 +258,11 @@ class DeviceScores:
             self.detail_dev = self.detail.resident(frames)
             if self.detail_dev is None:
                 return False
+            if self.unpack is not None:
+                # the cell pairs binned too (csrc/window_unpack_detail.hip): the cell-level labels' columns, the reference members' type rows
+                self.cell_dev = frames.unpack_detail(self.ref_mc, self.moving_mc, frames.commonCT, self.detail.ks)
+                if self.cell_dev is None:
+                    return False
         return True
 
     def device_members(self, frames, job):
@@ -286,7 +292,12 @@ class DeviceScores:
         c = acc.score(frames.dmov, frames.dref, self.tris, p["ignore_same_type_triangles"], p["node_local"], p["majority_threshold"],
                       p["min_flips"])
         rec = record_from_counts(counts_from_words(c, self.total), p)             # (total_triangles: the caller's own count)
-        if self.unpack is not None:
+        if self.cell_dev is not None:
+            # ONE call in the unpack call's place: its counts are the record's cell keys, its bins the cell-level breakdown
+            rec["_cell_detail"] = d = self._infeasible_as_the_reference(
+                lambda: acc.unpack_detail(*self.members, self.unpack, self.cell_dev, self.detail_dev))
+            rec.update(unpack_record(d["counts"][1], d["counts"][2]))
+        elif self.unpack is not None:
             rec.update(self.unpacked(acc))
         if self.detail_dev is not None:
             # the detail call beside the score call: the same rows, triangles and rule, binned (csrc/window_score_detail.hip)
@@ -294,16 +305,20 @@ class DeviceScores:
                                               p["node_local"], p["majority_threshold"], p["min_flips"])
         return rec
 
-    def unpacked(self, acc):
-        """the cell-level keys of the merged rows `acc` holds (windows.MergeAccumulator.unpack); with tables the unpacked table joins
-        `cell_tables`: the moving rows' members in their order, each with the reference member the device gave it"""
-        mm, rm = self.members
+    def _infeasible_as_the_reference(self, call):
+        """call(), an unpack call of the library: non-finite member coordinates under "nearest" raise as `unpack_metacell_matches` does"""
         try:
-            got = acc.unpack(mm, rm, self.unpack, pairs=self.tables)
+            return call()
         except _lib.SameHipError as e:
             if e.code == _lib.SAME_ERANGE and self.unpack == "nearest":
                 raise ValueError("cost matrix is infeasible") from e
             raise
+
+    def unpacked(self, acc):
+        """the cell-level keys of the merged rows `acc` holds (windows.MergeAccumulator.unpack); with tables the unpacked table joins
+        `cell_tables`: the moving rows' members in their order, each with the reference member the device gave it"""
+        mm, rm = self.members
+        got = self._infeasible_as_the_reference(lambda: acc.unpack(mm, rm, self.unpack, pairs=self.tables))
         counts, ref_member = got if self.tables else (got, None)
         if self.tables:
             a = acc.final_rows()["a_row"].astype(np.int64)

@@ -257,8 +257,35 @@ class _DeviceFrames:
                 xy = mc.original_df[[mc.x_col, mc.y_col]].to_numpy(dtype=np.float64)
                 with stage("member lists to the device"):
                     made = DeviceMembers(self.dmov if side == "moving" else self.dref, off, xy[rows], codes[0 if side == "moving" else 1][rows])
-                made.ids = ids
+                made.ids, made.rows = ids, rows
             known[key] = ((mc, other), made)
+        return known[key][1]
+
+    def unpack_detail(self, ref_mc, mov_mc, commonCT, ks):
+        """What a study's cell pairs are binned by, resident beside the reference members (windows.DeviceUnpackDetail): the cell-level
+        labels -- `score_details.joint_labels` of the two objects' `original_df[cell_type_col]`, the codes `members` uploads --, with
+        `ks` their columns among `commonCT` (`label_columns`) and one type row per reference member, `ref_mc.original_df[commonCT]` as
+        float64 at `member_layout`'s rows.  `.labels`: the labels in their codes' order.  None for more than SAME_SCORE_MAX_LABELS cell
+        labels, and where `members` refuses the lists.  Made once per pair of objects and kept until close(), like `members`."""
+        from ._lib import SAME_SCORE_MAX_LABELS
+        from .score_details import joint_labels, label_columns
+        from .windows import DeviceUnpackDetail
+
+        known = self.__dict__.setdefault("_unpack_details", {})
+        key = (id(ref_mc), id(mov_mc), tuple(commonCT), bool(ks))
+        if key not in known:
+            made, ref_members = None, self.members(ref_mc, "ref", mov_mc)
+            _cm, _cr, labels = joint_labels(mov_mc.original_df[mov_mc.cell_type_col].to_numpy(),
+                                            ref_mc.original_df[ref_mc.cell_type_col].to_numpy())
+            if ref_members is not None and len(labels) <= SAME_SCORE_MAX_LABELS:
+                cols = types = None
+                if ks:
+                    cols = label_columns(labels, commonCT)
+                    types = ref_mc.original_df[list(commonCT)].to_numpy(dtype=np.float64)[ref_members.rows]
+                with stage("cell labels' columns and member type rows to the device"):
+                    made = DeviceUnpackDetail(ref_members, len(labels), cols, types)
+                made.labels = labels
+            known[key] = ((ref_mc, mov_mc), made)
         return known[key][1]
 
     def score_detail(self, group_of, n_groups, n_labels, col_of_label):
@@ -393,6 +420,9 @@ class _DeviceFrames:
                 tris.close()
         for _held, layer in self.__dict__.pop("_types_layers", {}).values():   # before the section they belong to
             layer.close()
+        for _held, detail in self.__dict__.pop("_unpack_details", {}).values():   # before the members whose type rows they hold
+            if detail is not None:
+                detail.close()
         for _held, members in self.__dict__.pop("_members", {}).values():      # before the section whose rows they list
             if members is not None:
                 members.close()

@@ -708,6 +708,23 @@ class MergeAccumulator(_DeviceHandle):
                       "same_merge_acc_unpack")
         return (counts, out[:int(counts[1])]) if pairs else counts
 
+    def unpack_detail(self, mov_members, ref_members, strategy, detail, groups=None):
+        """After finish(): `unpack`'s pairs binned where they are made (same_merge_acc_unpack_detail, csrc/window_unpack_detail.hip) under
+        `detail`, a DeviceUnpackDetail of `ref_members`, and `groups`, a DeviceScoreDetail of the moving section whose group codes a pair
+        takes from its moving row (None: one group).  -> the call's int64 words by name (`split_unpack_detail`): `counts` -- `unpack`'s
+        four --, `confusion` (L, L) over the cell-level label codes, `unlabelled`, `groups` (G + 1, 2: pairs and pairs whose codes agree,
+        the last row the pairs of rows without a group), `strict` and `weak` (SCORE_RANKS + 1 each) and `untyped`.  Two waits; no pair
+        comes to the host."""
+        if strategy not in UNPACK_STRATEGIES:
+            raise ValueError(f"strategy must be one of {tuple(UNPACK_STRATEGIES)}, not {strategy!r}")
+        n_groups = 1 if groups is None else groups.n_groups
+        ctx, out = self.ctx, np.zeros(unpack_detail_words(detail.n_labels, n_groups), np.int64)
+        with ctx.lock:
+            ctx.check(ctx.lib.same_merge_acc_unpack_detail(self.handle, mov_members.handle, ref_members.handle, UNPACK_STRATEGIES[strategy],
+                                                           detail.handle, None if groups is None else groups.handle, out.ctypes.data,
+                                                           len(out)), "same_merge_acc_unpack_detail")
+        return split_unpack_detail(out, detail.n_labels, n_groups)
+
     def columns(self, dmoving, dref, n_final, n_types, extra_moving=(), extra_ref=(), layer=None):
         """After finish(): the merged table's columns written by the device straight into page-locked host memory (enqueue only:
         `ctx.sync()` before reading): the moving section's type columns (`layer`: a DeviceTypesLayer of `dmoving` to read them from), X, Y, the reference's X, Y, the caller's extra 8-byte device
@@ -936,6 +953,50 @@ class DeviceScoreDetail(_DeviceHandle):
 
 
 UNPACK_STRATEGIES = {"distribute": _lib.SAME_UNPACK_DISTRIBUTE, "nearest": _lib.SAME_UNPACK_NEAREST}
+
+
+def unpack_detail_words(n_labels, n_groups):
+    """int64 words of same_merge_acc_unpack_detail's `out` (SAME_UNPACK_DETAIL_WORDS)"""
+    return 4 + n_labels * n_labels + 1 + (n_groups + 1) * 2 + 2 * (SCORE_RANKS + 1) + 1
+
+
+def split_unpack_detail(out, n_labels, n_groups):
+    """the words of same_merge_acc_unpack_detail's `out` by name, in the order include/same_hip.h states"""
+    L, G, R = int(n_labels), int(n_groups), SCORE_RANKS
+    out = np.asarray(out, np.int64)
+    assert len(out) >= unpack_detail_words(L, G)
+    at = np.cumsum([0, 4, L * L, 1, (G + 1) * 2, R + 1, R + 1, 1])
+    part = lambda q: out[at[q]:at[q + 1]]
+    return {"counts": part(0), "confusion": part(1).reshape(L, L), "unlabelled": int(part(2)[0]), "groups": part(3).reshape(G + 1, 2),
+            "strict": part(4), "weak": part(5), "untyped": int(part(6)[0])}
+
+
+class DeviceUnpackDetail(_DeviceHandle):
+    """What same_merge_acc_unpack_detail bins cell pairs by, resident beside the reference members (same_unpack_detail_create,
+    csrc/window_unpack_detail.hip): `n_labels` cell-level joint label codes -- the codes the members were uploaded with --,
+    `col_of_label` int32 per code, the type column the label names or -1 (None: no rank counts), `member_types` float64 (members, T),
+    one type row per reference member in CSR order (None: none).  Made on the members' context; read-only: the worker contexts of the
+    device share it.  Close it before its members."""
+
+    _ENTRY = (None, "same_unpack_detail_destroy")
+
+    def __init__(self, ref_members, n_labels, col_of_label, member_types):
+        c = None if col_of_label is None else np.ascontiguousarray(col_of_label, dtype=np.int32)
+        t = None if member_types is None else np.ascontiguousarray(member_types, dtype=np.float64)
+        if c is not None and c.shape != (max(int(n_labels), 0),):            # (the library reads one entry per label: nothing it was not given)
+            raise ValueError(f"col_of_label has shape {c.shape} for {n_labels} labels")
+        if t is not None and (t.ndim != 2 or len(t) != ref_members.n_members):
+            raise ValueError(f"member_types has shape {t.shape} for {ref_members.n_members} reference members")
+        self.n_labels, self.n_types = int(n_labels), 0 if t is None else t.shape[1]
+        self.ctx = ctx = ref_members.ctx
+        h = ctypes.c_void_p()
+        with ctx.lock:
+            rc = ctx.lib.same_unpack_detail_create(ref_members.handle, self.n_labels, None if c is None or not len(c) else c.ctypes.data,
+                                                   None if t is None else t.ctypes.data, self.n_types, ctypes.byref(h))
+            if rc != 0 and h.value:
+                ctx.lib.same_unpack_detail_destroy(h)
+            ctx.check(rc, "same_unpack_detail_create")
+        self.handle = h
 
 
 def caller_tris_windows(states, caller, radius, angle_enabled, cos_thr, near_tol, ignore_same_type, removed=None):

@@ -857,6 +857,61 @@ int  same_merge_acc_score_detail(same_merge_acc *acc, const same_section *moving
                                  const same_caller_tris *tris /* may be NULL */, const same_score_detail *detail,
                                  int ignore_same_type, int node_local, double majority_threshold, int64_t min_flips,
                                  int64_t *out, int64_t out_words);
+/* The same result per CELL (csrc/window_score_map.hip): same_merge_acc_score's counts and, per row of the moving section, one 16-byte
+ * mark -- what the reference's notebooks plot per cell (in_violating_triangle, correct / incorrect, in the top k, on the ground truth).
+ *   The mark of moving row i:
+ *     ref_row      the reference section row the final rows put it on, -1: none (a final row outside the sections leaves its moving
+ *                  row unmatched, as it leaves the counts);
+ *     node_tri     the resident triangles not skipped the row is a corner of; node_flip: the flipped ones of them;
+ *     flags        SAME_MARK_MATCHED 1; TYPE_MATCH 2: the two label codes agree (out_counts[1]'s rule); CONSIDERED 4: node_tri > 0;
+ *                  VIOLATING 8: the any-flip / node-local rule of out_counts[7]; TRUTH_KNOWN 16: the map holds a truth row >= 0 for
+ *                  the row; ON_TRUTH 32: matched and ref_row equals it; RANKED 64: the two rank bytes hold ranks;
+ *     rank_strict, rank_weak   same_merge_acc_score_detail's strict and weak of (the row's label's column, the matched reference
+ *                  row's type row), saturated at 254; 255 where the row is not ranked: unmatched, the label names no column, a NaN
+ *                  in the type row, no `detail` or one without col_of_label.
+ *   An unmatched row's mark is {-1, 0, 0, TRUTH_KNOWN or 0, 255, 255, 0}.
+ *   same_score_map_create: what the marks are read against and folded into, made on `ctx` for the two sections, resident on its device
+ *   and shared by the worker contexts of that device (at most 32 calling contexts); destroy it before its sections.  truth_row[i]
+ *   (host, mov->n entries, may be NULL: every row unknown): the reference section row that is moving row i's true or baseline match,
+ *   -1 unknown; SAME_EINVAL for a value < -1 or >= the reference section's rows, checked before anything is uploaded.  with_tally:
+ *   the map holds tally[mov->n][4] (uint32, zero at first) -- per moving row in how many results folded in so far it was matched,
+ *   type-matched, violating, on its truth row -- and every same_merge_acc_score_map call adds its result to it.
+ *   same_score_map_tally: the tally copied out (out_tally: mov->n * 4 words, may be NULL; SAME_EINVAL when given for a map without a
+ *   tally) and the number of results folded in since the creation or the last reset (out_results, may be NULL).  One copy, one wait.
+ *   same_score_map_reset: tally and result count back to zero (one fill, one wait).
+ *   same_merge_acc_score_map: arguments as same_merge_acc_score's; `detail` (may be NULL: no ranks) a same_score_detail of `moving`,
+ *   of which only col_of_label and n_labels are read; `map` made for these two sections.  out_counts[10]: [0 .. 7] exactly
+ *   same_merge_acc_score's for the same arguments, [8] matched rows whose truth is known, [9] of them: on it.  out_marks (may be NULL:
+ *   counts and tally only): mov->n marks; any host memory, page-locked memory (same_host_alloc) takes them by DMA.
+ * What the call asks of the runtime on the accumulator's context, whatever the number of final rows: the score call's rows launch, its
+ * triangles launch where `tris` holds a triangle, one launch over the moving rows -- THREE launches, two without a triangle --; one
+ * copy (80 bytes back) and with out_marks a second (the marks, from a device buffer of the map); ONE wait; no fill -- but the call that
+ * lays the accumulator's score work buffer (same_merge_acc_score: the first, and the first over more moving rows) fills it, two fills.
+ * The totals are counted in the map, two sets per calling context of which each call clears the other's, so the accumulator's score
+ * work buffer is left as it was found and its own totals are not touched: map, score and detail calls alternate on one accumulator
+ * without a fill.  Sections without a row and an accumulator without a final row: nothing.
+ * SAME_EINVAL / SAME_ERANGE as same_merge_acc_score, out_counts untouched; SAME_EINVAL also for a `map` made for other sections or on
+ * another device, a `detail` made for another section, sections whose T differ where a label names a column.  After SAME_ERANGE
+ * out_marks is undefined and the tally holds the refused result's rows inside the sections: reset it. */
+#define SAME_MARK_MATCHED     1
+#define SAME_MARK_TYPE_MATCH  2
+#define SAME_MARK_CONSIDERED  4
+#define SAME_MARK_VIOLATING   8
+#define SAME_MARK_TRUTH_KNOWN 16
+#define SAME_MARK_ON_TRUTH    32
+#define SAME_MARK_RANKED      64
+typedef struct { int32_t ref_row; uint32_t node_tri, node_flip; uint8_t flags, rank_strict, rank_weak, reserved; } same_cell_mark;
+typedef struct same_score_map same_score_map;
+int  same_score_map_create(same_ctx *ctx, const same_section *moving, const same_section *ref,
+                           const int32_t *truth_row /* host, [moving rows], -1 unknown; may be NULL */, int with_tally,
+                           same_score_map **out);
+void same_score_map_destroy(same_score_map *map);
+int  same_score_map_tally(same_score_map *map, uint32_t *out_tally /* [moving rows][4], may be NULL */, int64_t *out_results);
+int  same_score_map_reset(same_score_map *map);
+int  same_merge_acc_score_map(same_merge_acc *acc, const same_section *moving, const same_section *ref,
+                              const same_caller_tris *tris /* may be NULL */, const same_score_detail *detail /* may be NULL: no ranks */,
+                              same_score_map *map, int ignore_same_type, int node_local, double majority_threshold, int64_t min_flips,
+                              same_cell_mark *out_marks /* [moving rows], may be NULL */, int64_t *out_counts /* [10] */);
 /* A merged MetaCell result unpacked to cells (csrc/window_unpack.hip; src/metacell_utils.py:564-766, unpack_metacell_matches with
  * metacells on both sides), without its table: after same_merge_acc_finish, on the final rows where they are and in their order.
  *   same_members_create: the members of `section`'s rows as CSR -- row i owns members [off[i], off[i+1]); per member its XY (the

@@ -146,6 +146,11 @@ _PROTOTYPES = {
     "same_score_detail_create": [c_vp, c_vp, c_int, c_int, c_vp, ctypes.POINTER(c_vp)],
     "same_score_detail_destroy": [c_vp],
     "same_merge_acc_score_detail": [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_dbl, c_i64, c_vp, c_i64],
+    "same_score_map_create": [c_vp, c_vp, c_vp, c_vp, c_int, ctypes.POINTER(c_vp)],
+    "same_score_map_destroy": [c_vp],
+    "same_score_map_tally": [c_vp, c_vp, ctypes.POINTER(c_i64)],
+    "same_score_map_reset": [c_vp],
+    "same_merge_acc_score_map": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_dbl, c_i64, c_vp, c_vp],
     "same_members_create": [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(c_vp)],
     "same_members_destroy": [c_vp],
     "same_merge_acc_unpack": [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_i64],
@@ -179,6 +184,9 @@ SAME_INCUMBENT_GREEDY, SAME_INCUMBENT_ASSIGNMENT, SAME_INCUMBENT_TRANSPORT = 0, 
 SAME_WINDOW_STATS = 15
 SAME_UNPACK_DISTRIBUTE, SAME_UNPACK_NEAREST = 0, 1     # same_merge_acc_unpack's strategies
 SAME_SCORE_MAX_LABELS, SAME_SCORE_MAX_GROUPS, SAME_SCORE_RANKS = 64, 256, 16     # same_merge_acc_score_detail's caps and rank bins
+# same_cell_mark's flag bits (same_merge_acc_score_map) and the rank byte of a row that is not ranked
+SAME_MARK_MATCHED, SAME_MARK_TYPE_MATCH, SAME_MARK_CONSIDERED, SAME_MARK_VIOLATING = 1, 2, 4, 8
+SAME_MARK_TRUTH_KNOWN, SAME_MARK_ON_TRUTH, SAME_MARK_RANKED, SAME_MARK_UNRANKED = 16, 32, 64, 255
 SAME_WINDOW_STATS_CAP = 16       # the _cap calls: the 15 words, then sum_j max(0, count_j - 1) of the search's result
 SAME_WINDOW_STATS_TRANSPORT = 17  # SAME_INCUMBENT_TRANSPORT: the 16 words, then sum_j max(0, count_j - 1) of the start
 
@@ -224,6 +232,7 @@ def load():
             L.same_types_layer_destroy.restype = None
             L.same_members_destroy.restype = None
             L.same_score_detail_destroy.restype = None
+            L.same_score_map_destroy.restype = None
             L.same_unpack_detail_destroy.restype = None
             if L.same_abi_version() != ABI_VERSION:
                 raise SameHipError(-22, "libsame_hip ABI version mismatch")

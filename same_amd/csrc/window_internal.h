@@ -1,5 +1,5 @@
 // window_internal.h -- what the translation units of the device-resident window path share (section.hip, window_stage.hip,
-// window_finish.hip, window_merge.hip, window_score.hip, window_score_detail.hip, window_unpack.hip, window_unpack_detail.hip, window_caller.hip, window_priority.hip, window_knn_prefix.hip, window_recost.hip): the resident objects behind the
+// window_finish.hip, window_merge.hip, window_score.hip, window_score_detail.hip, window_score_map.hip, window_unpack.hip, window_unpack_detail.hip, window_caller.hip, window_priority.hip, window_knn_prefix.hip, window_recost.hip): the resident objects behind the
 // opaque handles of include/same_hip.h part 4, the per-launch argument blocks, the device side of a window's pair list, the window's
 // logical state (window_state.h: win::State, with the table of what each call requires, leaves and invalidates), the protocol of the merged
 // rows' reader calls (work_sets.h: win::WorkSets), the small host helpers and the batch driver of the window calls.
@@ -445,6 +445,31 @@ struct same_unpack_detail {
     double *types = nullptr;         // [ref->m][T] in CSR order; null: no type rows
 };
 
+// What same_merge_acc_score_map keeps beside the counts, resident (same_score_map_create, window_score_map.hip): per row of the moving
+// section its truth row and -- with a tally -- four counters over the results folded in so far; and what a map call works in that is not
+// the accumulator's: per calling context a slot of two sets of totals (the score call's eight words and the two truth totals, under the
+// protocol of work_sets.h) and the device buffer the marks are written to before their copy.  The truth rows are read-only and the tally
+// is only added to, so the worker contexts of the device share a map; a slot belongs to ONE context, which one thread uses at a time.
+namespace win {
+constexpr int MAP_TOTALS = 10;           // words of one set: [0 .. 7] the score call's set, [8] matched rows with a known truth, [9] those on it
+constexpr int MAP_SLOTS = 32;            // calling contexts a map serves
+struct MapSlot {
+    const same_ctx *owner = nullptr;
+    WorkSets sets;                       // laid: 1 while both sets are idle
+    DevBuf marks;                        // [mov->n] same_cell_mark
+};
+}  // namespace win
+struct same_score_map {
+    same_ctx *ctx = nullptr;
+    const same_section *mov = nullptr, *ref = nullptr;
+    int32_t *truth_row = nullptr;        // [mov->n] reference section row, -1 unknown; null: every row unknown
+    unsigned *tally = nullptr;           // [mov->n][4] matched_in, type_match_in, violating_in, on_truth_in; null: no tally
+    unsigned long long *totals = nullptr;   // [MAP_SLOTS][2][MAP_TOTALS]
+    int64_t results = 0;                 // map calls folded into the tally since the last reset (under `lock`)
+    std::mutex lock;                     // guards `slots`' owners and `results`; never held across device work
+    win::MapSlot slots[win::MAP_SLOTS];
+};
+
 // The rows of one pass over a window plan on one context (window_merge.hip), and what window_score.hip reads of them.
 struct same_merge_acc {
     same_ctx *ctx = nullptr;
@@ -595,6 +620,35 @@ __device__ __forceinline__ void reset_idle(int32_t a, int32_t *match_of, unsigne
     node_tri[a] = 0u;
     node_flip[a] = 0u;
 }
+
+// words of a set of score totals (SCORE_TOTALS of them) -- in a namespace of their own, which window_score.hip and window_score_map.hip
+// open: window_unpack.hip names the words of ITS totals T_... too, and win::unpack_run would read these in their place
+namespace score_totals {
+enum { T_BAD = 0, T_TYPE = 1, T_ALL = 3, T_SAME = 4, T_FLIP = 5, T_FLIP_CONSIDERED = 6, T_NODES = 7 };
+}
+constexpr int SCORE_NT = 256;            // threads of a block of the score kernels
+// how many threads of the block hold flag[k] -> totals[word[k]].  Every thread of the block calls it (wave64: four ballots' counts meet
+// in LDS), thread k adds total k -- one atomic per block and total, none where the block counted nothing.
+template <int K>
+__device__ __forceinline__ void block_totals(const bool (&flag)[K], const int (&word)[K], unsigned long long *__restrict__ totals) {
+    __shared__ unsigned part[K][SCORE_NT / 64];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const unsigned long long bal = __ballot(flag[k]);
+        if ((threadIdx.x & 63) == 0) part[k][threadIdx.x >> 6] = (unsigned)__builtin_popcountll(bal);
+    }
+    __syncthreads();
+    if (threadIdx.x < K) {
+        unsigned n = 0;
+        for (int q = 0; q < SCORE_NT / 64; ++q) n += part[threadIdx.x][q];
+        if (n) atomicAdd(&totals[word[threadIdx.x]], (unsigned long long)n);
+    }
+}
+// window_score.hip: the rows and triangles phases of same_merge_acc_score, once, for the calls that score -- enqueued into the
+// accumulator's ScoreWork (laid by the caller), counting into `totals` and clearing SCORE_TOTALS words of `next`.  match_of is written
+// where there is a triangle or `keep_match` says a later kernel reads it; the caller's last kernel returns the rows' words to idle.
+int score_phases(same_ctx *ctx, same_merge_acc *a, const same_section *mov, const same_section *ref, const same_caller_tris *tris,
+                 int ignore_same_type, bool keep_match, unsigned long long *totals, unsigned long long *next);
 
 // window_unpack.hip: the phases of same_merge_acc_unpack, once, for the calls that unpack -- sizes and their scan, the wait for them,
 // the solve launches, the call's last wait.  A PairReader rides between the last solve launch and that wait: the pairs then stay on the

@@ -22,28 +22,10 @@
 namespace {
 
 using namespace win;
+using namespace win::score_totals;
 
-constexpr int NT = 256;
-// words of a set of totals (win::SCORE_TOTALS of them)
-enum { T_BAD = 0, T_TYPE = 1, T_ALL = 3, T_SAME = 4, T_FLIP = 5, T_FLIP_CONSIDERED = 6, T_NODES = 7 };
-
-// how many threads of the block hold flag[k] -> totals[word[k]].  Every thread of the block calls it (wave64: four ballots' counts meet
-// in LDS), thread k adds total k -- one atomic per block and total, none where the block counted nothing.
-template <int K>
-__device__ __forceinline__ void block_totals(const bool (&flag)[K], const int (&word)[K], unsigned long long *__restrict__ totals) {
-    __shared__ unsigned part[K][NT / 64];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const unsigned long long bal = __ballot(flag[k]);
-        if ((threadIdx.x & 63) == 0) part[k][threadIdx.x >> 6] = (unsigned)__builtin_popcountll(bal);
-    }
-    __syncthreads();
-    if (threadIdx.x < K) {
-        unsigned n = 0;
-        for (int q = 0; q < NT / 64; ++q) n += part[threadIdx.x][q];
-        if (n) atomicAdd(&totals[word[threadIdx.x]], (unsigned long long)n);
-    }
-}
+constexpr int NT = SCORE_NT;
+// (the totals' words and block_totals: window_internal.h, shared with window_score_map.hip)
 
 // match_of null: no triangles to score, nothing reads it
 __global__ __launch_bounds__(NT) void score_rows_kernel(const FinalRec *__restrict__ rows, int64_t n, int64_t n_mov, int64_t n_ref,
@@ -102,6 +84,19 @@ __global__ __launch_bounds__(NT) void score_nodes_kernel(const FinalRec *__restr
 
 }  // namespace
 
+int win::score_phases(same_ctx *ctx, same_merge_acc *a, const same_section *mov, const same_section *ref, const same_caller_tris *tris,
+                      int ignore_same_type, bool keep_match, unsigned long long *totals, unsigned long long *next) {
+    const int64_t n = a->n_final, Tr = tris ? tris->n_tris : 0;
+    const ScoreWork &sw = a->sw;
+    const FinalRec *fin = static_cast<const FinalRec *>(a->out.p);
+    SAME_LAUNCH(ctx, score_rows_kernel, dim3(grid_for(n)), dim3(NT), 0, fin, n, mov->n, ref->n, mov->label_codes, ref->label_codes,
+                Tr > 0 || keep_match ? sw.match_of : nullptr, totals, next);
+    if (Tr > 0)
+        SAME_LAUNCH(ctx, score_tris_kernel, dim3(grid_for(Tr)), dim3(NT), 0, tris->tris, Tr, sw.match_of, mov->label_codes,
+                    ignore_same_type ? 1 : 0, mov->xy, ref->xy, sw.node_tri, sw.node_flip, totals);
+    return SAME_OK;
+}
+
 extern "C" int same_merge_acc_score(same_merge_acc *a, const same_section *mov, const same_section *ref, const same_caller_tris *tris,
                                     int ignore_same_type, int node_local, double majority_threshold, int64_t min_flips, int64_t *out_counts) {
     if (!a) return SAME_EINVAL;
@@ -117,11 +112,8 @@ extern "C" int same_merge_acc_score(same_merge_acc *a, const same_section *mov, 
         InDoubt doubt(a->score_sets);
         unsigned long long *totals = sw.totals + (size_t)a->score_sets.set * SCORE_TOTALS, *next = sw.totals + (size_t)(a->score_sets.set ^ 1) * SCORE_TOTALS;
         const FinalRec *fin = static_cast<const FinalRec *>(a->out.p);
-        SAME_LAUNCH(ctx, score_rows_kernel, dim3(grid_for(n)), dim3(NT), 0, fin, n, mov->n, ref->n, mov->label_codes, ref->label_codes,
-                    Tr > 0 ? sw.match_of : nullptr, totals, next);
+        SAME_TRY(score_phases(ctx, a, mov, ref, tris, ignore_same_type, false, totals, next));
         if (Tr > 0) {
-            SAME_LAUNCH(ctx, score_tris_kernel, dim3(grid_for(Tr)), dim3(NT), 0, tris->tris, Tr, sw.match_of, mov->label_codes,
-                        ignore_same_type ? 1 : 0, mov->xy, ref->xy, sw.node_tri, sw.node_flip, totals);
             SAME_LAUNCH(ctx, score_nodes_kernel, dim3(grid_for(n)), dim3(NT), 0, fin, n, mov->n, ref->n, node_local ? 1 : 0, majority_threshold,
                         min_flips, sw.match_of, sw.node_tri, sw.node_flip, totals);
         }

@@ -305,6 +305,9 @@ class DeviceScores:
                                               p["node_local"], p["majority_threshold"], p["min_flips"])
         return rec
 
+    def finished(self, frames):
+        """after the pass's last record, while the frames are still resident (a hook that keeps something on the device reads it here)"""
+
     def _infeasible_as_the_reference(self, call):
         """call(), an unpack call of the library: non-finite member coordinates under "nearest" raise as `unpack_metacell_matches` does"""
         try:
@@ -370,10 +373,11 @@ def sliding_window_scores(ref, moving, commonCT=None, *, type_variants=None, par
 
 def _scored_study(ref, moving, commonCT, *, type_variants, param_sets, optim_params, gurobi_params, score_delaunay,
                   score_delaunay_vertex_col, score_params, tables, workers, triangulator, ctx, batch, moving_delaunay,
-                  moving_delaunay_vertex_col, unpack, detail=None):
+                  moving_delaunay_vertex_col, unpack, detail=None, hook=None):
     """`sliding_window_scores`' pass -> (its scores frame, the results per variant and set -- tables, or None where the device scored
     and none was asked for --, the hook: `hook.records` is None where the host scored the tables).  With `detail`
-    (score_details.DetailSpec) every record of the device carries the detail call's words under "_detail"."""
+    (score_details.DetailSpec) every record of the device carries the detail call's words under "_detail".  `hook`: a DeviceScores
+    variant made by the caller to ride on the pass in the plain one's place (score_maps.MapScores)."""
     params = checked_score_params(score_params)
     ref_arg, moving_arg, ref_df, mov_df = _frames_of(ref, moving)
     checked_unpack(unpack, ref_arg, moving_arg)
@@ -382,7 +386,8 @@ def _scored_study(ref, moving, commonCT, *, type_variants, param_sets, optim_par
             raise ValueError(f"scores compare cell types: the {name} frame has no 'cell_type' column")
     if score_delaunay is not None:
         _as_triangle_array(score_delaunay)                  # (its shape: the reference's ValueError)
-    hook = DeviceScores(score_delaunay, score_delaunay_vertex_col, params, tables, unpack, ref_arg, moving_arg, detail)
+    if hook is None:
+        hook = DeviceScores(score_delaunay, score_delaunay_vertex_col, params, tables, unpack, ref_arg, moving_arg, detail)
     results = sliding_window_variants(ref, moving, [None] if type_variants is None else type_variants, commonCT, param_sets=param_sets,
                                       optim_params=optim_params, gurobi_params=gurobi_params, workers=workers, triangulator=triangulator,
                                       ctx=ctx, merge=True, batch=batch, moving_delaunay=moving_delaunay,

@@ -108,7 +108,7 @@ def sliding_window_variants(ref, moving, type_variants, commonCT=None, *, param_
     shared.  (An `outprefix` and ranks are not offered here.)
     `_score` (scores.sliding_window_scores' scores.DeviceScores): it is told the job (`_score.job`), and where the pass is shared and
     `_score.prepare(frames, job)` agrees every result is scored on the device (`incumbent._device_pass`); a result is then None unless
-    `_score.tables`."""
+    `_score.tables`.  After the last record `_score.finished(frames)` is called while the frames are still resident."""
     _checked_list(type_variants)
     ref_arg, moving_arg, ref_df, mov_df = _frames_of(ref, moving)
     cts = _common_types(ref_arg, moving_arg, ref_df, mov_df, commonCT)
@@ -154,6 +154,7 @@ def sliding_window_variants(ref, moving, type_variants, commonCT=None, *, param_
                                 variants=layers, score=score)
             if score is not None:
                 score.records = [j.score_record for j in jobs]
+                score.finished(frames)
             res = [(table, [stats[pos] for pos in sorted(stats)]) if return_stats else table for table, stats in done]
             n_sets = len(checked)
             return [res[v * n_sets] if param_sets is None else res[v * n_sets:(v + 1) * n_sets] for v in range(len(mats))]

@@ -303,6 +303,17 @@ class _DeviceFrames:
                 known[key] = DeviceScoreDetail(self.dmov, g, n_groups, n_labels, c)
         return known[key]
 
+    def score_map(self, truth_row, tally):
+        """A study's per-cell map resident beside the sections (windows.DeviceScoreMap): `truth_row` the moving rows' true reference
+        rows (None: none known), `tally` whether results are folded into per-cell counters.  One per call -- its tally is a study's
+        own --, kept until close() or until the study closes it."""
+        from .windows import DeviceScoreMap
+
+        with stage("truth rows and the per-cell tally to the device"):
+            made = DeviceScoreMap(self.dmov, self.dref, truth_row, tally, self.ctx)
+        self.__dict__.setdefault("_score_maps", []).append(made)
+        return made
+
     def types_layer(self, variant, types):
         """A type-matrix variant of the moving frame resident beside its section (windows.DeviceTypesLayer): `types` the variant as a
         float64 (rows, commonCT) matrix, `variant` the caller's object it was read from.  Uploaded once per object and kept until close()
@@ -426,6 +437,8 @@ class _DeviceFrames:
         for _held, members in self.__dict__.pop("_members", {}).values():      # before the section whose rows they list
             if members is not None:
                 members.close()
+        for made in self.__dict__.pop("_score_maps", []):                      # before the sections they were made for
+            made.close()
         for detail in self.__dict__.pop("_score_details", {}).values():        # before the section whose rows they group
             detail.close()
         for c in self._worker_ctx:

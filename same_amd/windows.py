@@ -692,6 +692,27 @@ class MergeAccumulator(_DeviceHandle):
                       "same_merge_acc_score_detail")
         return detail.split(out)
 
+    def score_map(self, dmoving, dref, tris, detail, score_map, ignore_same_type=True, node_local=False, majority_threshold=0.5,
+                  min_flips=1, marks=True):
+        """After finish(): `score`'s counts and, per row of the moving section, its mark (same_merge_acc_score_map,
+        csrc/window_score_map.hip) -- folded into `score_map`, a DeviceScoreMap of the two sections, whose truth rows the marks are read
+        against.  `detail`: a DeviceScoreDetail of `dmoving` whose label columns rank the rows (None: no ranks); the other arguments are
+        `score`'s.  -> (ten int64 counts: `score`'s eight, matched rows with a known truth, those on it; the marks as a CELL_MARK array
+        over a pooled page-locked block, or None with marks=False).  One wait; leaves the accumulator as `score` does."""
+        ctx, counts = self.ctx, np.zeros(10, np.int64)
+        n = len(dmoving.section.xy)
+        out = None
+        if marks:
+            got = PINNED_BLOCKS.take(ctx, max(1, n * CELL_MARK.itemsize))
+            out = np.empty(n, CELL_MARK) if got is None else np.frombuffer(got[0], dtype=CELL_MARK, count=n)
+        with ctx.lock:
+            ctx.check(ctx.lib.same_merge_acc_score_map(self.handle, dmoving.handle, dref.handle, None if tris is None else tris.handle,
+                                                       None if detail is None else detail.handle, score_map.handle,
+                                                       int(bool(ignore_same_type)), int(bool(node_local)), float(majority_threshold),
+                                                       int(min_flips), None if out is None or not n else out.ctypes.data,
+                                                       counts.ctypes.data), "same_merge_acc_score_map")
+        return counts, out
+
     def unpack(self, mov_members, ref_members, strategy, pairs=False):
         """After finish(): the merged metacell rows unpacked to cells (same_merge_acc_unpack, csrc/window_unpack.hip) under `strategy`
         ("distribute" / "nearest"; `mov_members`, `ref_members`: DeviceMembers of the sections the pass ran over) -> the int64 counts
@@ -950,6 +971,46 @@ class DeviceScoreDetail(_DeviceHandle):
 
     def split(self, out):
         return split_score_detail(out, self.n_labels, self.n_groups)
+
+
+# same_cell_mark (include/same_hip.h): one record per row of the moving section
+CELL_MARK = np.dtype([("ref_row", np.int32), ("node_tri", np.uint32), ("node_flip", np.uint32), ("flags", np.uint8),
+                      ("rank_strict", np.uint8), ("rank_weak", np.uint8), ("reserved", np.uint8)])
+assert CELL_MARK.itemsize == 16
+TALLY_COLUMNS = ("matched_in", "type_match_in", "violating_in", "on_truth_in")
+
+
+class DeviceScoreMap(_DeviceHandle):
+    """What same_merge_acc_score_map reads its marks against and folds them into, resident beside the two sections
+    (same_score_map_create, csrc/window_score_map.hip): `truth_row` int32 per moving section row, the reference section row that is its
+    true or baseline match, -1 unknown (None: every row unknown); with `tally` four uint32 counters per moving row over the results
+    folded in.  The worker contexts of the device share it.  Close it before its sections."""
+
+    _ENTRY = ("same_score_map_create", "same_score_map_destroy")
+
+    def __init__(self, dmoving, dref, truth_row=None, tally=True, ctx=None):
+        t = None if truth_row is None else np.ascontiguousarray(truth_row, dtype=np.int32)
+        self.n_rows = len(dmoving.section.xy)
+        if t is not None and t.shape != (self.n_rows,):             # (the library reads one entry per row: nothing it was not given)
+            raise ValueError(f"truth_row has shape {t.shape} for a moving section of {self.n_rows} rows")
+        self.has_tally = bool(tally)
+        self._create(dmoving.ctx if ctx is None else ctx, dmoving.handle, dref.handle, None if t is None or not len(t) else t.ctypes.data,
+                     int(self.has_tally))
+
+    def tally(self):
+        """-> (uint32 (rows, 4) over TALLY_COLUMNS, or None for a map without a tally; the results folded in since the creation or the
+        last `reset`)"""
+        ctx = self.ctx
+        out = np.zeros((self.n_rows, 4), np.uint32) if self.has_tally else None
+        n = ctypes.c_int64(0)
+        with ctx.lock:
+            ctx.check(ctx.lib.same_score_map_tally(self.handle, None if out is None or not len(out) else out.ctypes.data, ctypes.byref(n)),
+                      "same_score_map_tally")
+        return out, n.value
+
+    def reset(self):
+        with self.ctx.lock:
+            self.ctx.check(self.ctx.lib.same_score_map_reset(self.handle), "same_score_map_reset")
 
 
 UNPACK_STRATEGIES = {"distribute": _lib.SAME_UNPACK_DISTRIBUTE, "nearest": _lib.SAME_UNPACK_NEAREST}

@@ -912,6 +912,68 @@ int  same_merge_acc_score_map(same_merge_acc *acc, const same_section *moving, c
                               const same_caller_tris *tris /* may be NULL */, const same_score_detail *detail /* may be NULL: no ranks */,
                               same_score_map *map, int ignore_same_type, int node_local, double majority_threshold, int64_t min_flips,
                               same_cell_mark *out_marks /* [moving rows], may be NULL */, int64_t *out_counts /* [10] */);
+/* The same result read as FEATURE SUMS (csrc/window_score_feature.hip): the matched pairs put two feature matrices side by side, and the
+ * reference's notebooks read them as means -- per group of the moving rows (examples/luad/reproduce_figures.ipynb cells 16-22, the
+ * matrixplot by annotation) and per bin of the distance to the nearest pair of a marked zone (cdist(...).min(axis=1), pd.cut).
+ *   FIXED-POINT COLUMNS.  A feature column c is quantised once on the host: with m = max |x| over the column and p = frexp(m)'s exponent,
+ *   e_c = 30 - p (0 for an all-zero column) and q = rint(ldexp(x, e_c)) as int32, |q| <= 2^30.  The device sums the int32 values in int64:
+ *   exact, the same from run to run and under every grid shape.  mean = ldexp((double)sum / n, -e_c); against the true mean it errs by
+ *   at most 2^(-e_c-1) + 3 * 2^-53 * |mean|.  A column's step is 2^-e_c, which is 2^-30 of the power of two above its largest
+ *   magnitude; a value is rounded by at most half of it, 2^-31 of that power of two.
+ *   same_score_features_create: what to sum, uploaded once on `moving`'s context, resident on its device, read-only and shared by the
+ *   worker contexts like same_caller_tris; destroy it before its sections.  mov_q[moving rows][F_m], ref_q[ref rows][F_r]: row-major
+ *   int32, host memory (NULL where the side has no column or no row).  F = F_m + F_r.  group_of, n_groups: exactly
+ *   same_score_detail_create's.  Checked on the host before anything is uploaded: SAME_EINVAL for F_m < 0, F_r < 0, F < 1,
+ *   F > SAME_FEATURE_MAX_COLUMNS, a matrix missing where its side has columns and rows, n_groups < 1 or > SAME_SCORE_MAX_GROUPS;
+ *   SAME_ERANGE for a |q| > 2^30 or a group_of value >= n_groups.
+ *   same_feature_zone_create: the zone and the subset of a distance reading, made on `feats`' context for its sections and resident
+ *   like it; destroy it before `feats`.  mov_flags[moving rows], ref_flags[ref rows]: uint8, bit 0 "zone side", bit 1 "subset side";
+ *   NULL: every bit set.  A final row (a, r) is a ZONE pair iff mov_flags[a] & ref_flags[r] & 1, a SUBSET pair iff
+ *   mov_flags[a] & ref_flags[r] & 2.  d2_edges[n_edges]: thresholds on the SQUARED distance, non-decreasing, +inf allowed; with
+ *   B = n_edges - 1, bin b < B holds d2_edges[b] < d2 <= d2_edges[b+1] (pd.cut's right-closed rule).  SAME_EINVAL for n_edges < 2 or
+ *   > SAME_FEATURE_MAX_EDGES, a NaN edge, a decreasing pair of edges.
+ *   same_merge_acc_score_features: after same_merge_acc_finish, on the final rows where they are.  With G = n_groups, `out` holds
+ *   out_words >= SAME_FEATURE_WORDS(G, F, B) int64 words (B = 0 without `zone`), in this order:
+ *     counts [4]           final rows; those whose moving row has a group; zone pairs; subset pairs (both 0 without `zone`);
+ *     rows [G+1]           final rows per group, bin G: the rows without a group;
+ *     sums [(G+1)*F]       per bin, the sum over its final rows (a, r) of mov_q[a][0 .. F_m) and then of ref_q[r][0 .. F_r);
+ *     with `zone` also
+ *     bin_rows [B+1]       subset pairs per distance bin, bin B: the subset pairs in no bin;
+ *     bin_sums [(B+1)*F]   as sums, over the subset pairs.
+ *   A pair's position is its reference row's XY.  For a subset pair d2 = min over ALL zone pairs of dx*dx + dy*dy, in fp64 without
+ *   contraction (a pair that is both: 0); with no zone pair every d2 is NaN and every subset pair is in bin B.  The minimum does not
+ *   depend on the order of the zone pairs.  out_d2 (moving rows doubles, may be NULL): the d2 of the row's subset pair, NaN otherwise.
+ * What the call asks of the runtime on the accumulator's context.  Without `zone`: no final row: nothing (out is zeros); else ONE
+ * launch, one copy (the words of `out` and one more), ONE wait.  With `zone` and a final row: FOUR launches (the sums by group and
+ * the flag kernel; after the first wait the walk and the sums by bin), two copies (32 bytes before the first wait, the words of
+ * `out` and one more before the second) and with out_d2 a third, TWO waits; where there is a zone pair the grid of the zone pairs is
+ * built between the two waits by knn.hip's build (grid.h: a bounding-box reduction with its 32-byte read-back and a wait, one fill
+ * and three launches of its own, which the context's counters do not count).  No fill -- but the call that
+ * lays the sums' buffer (the first, and the first with more words than any before) fills it, one fill, and with `zone` the call that
+ * lays the zone work buffer (the first, and the first over more final rows or moving rows) fills it, one fill.  The call leaves
+ * both clear for the next call and touches no other buffer of the accumulator: score, detail, map and feature calls alternate on
+ * one accumulator without a fill.
+ * SAME_EINVAL (`out`, out_d2 untouched): what same_merge_acc_score refuses -- before same_merge_acc_finish, after same_merge_acc_plain or
+ * same_merge_acc_load, a section without label codes --, `feats` made for other sections or on another device, `zone` made for
+ * another `feats`, out_words too small.  SAME_ERANGE (`out`, out_d2 untouched): a final row outside the
+ * sections (the pass ran over others); with `zone`, a zone or subset pair whose reference XY is not finite (`out` untouched). */
+#define SAME_FEATURE_MAX_COLUMNS 4096
+#define SAME_FEATURE_MAX_EDGES 65
+#define SAME_FEATURE_WORDS(G, F, B) (4 + ((int64_t)(G) + 1) * (1 + (int64_t)(F)) + ((B) > 0 ? ((int64_t)(B) + 1) * (1 + (int64_t)(F)) : 0))
+typedef struct same_score_features same_score_features;
+typedef struct same_feature_zone same_feature_zone;
+int  same_score_features_create(const same_section *moving, const same_section *ref, const int32_t *mov_q /* host, [moving rows][F_m] */,
+                                int F_m, const int32_t *ref_q /* host, [ref rows][F_r] */, int F_r,
+                                const int32_t *group_of /* [moving rows] or NULL: every row in group 0 */, int n_groups,
+                                same_score_features **out);
+void same_score_features_destroy(same_score_features *feats);
+int  same_feature_zone_create(const same_score_features *feats, const uint8_t *mov_flags /* [moving rows] or NULL */,
+                              const uint8_t *ref_flags /* [ref rows] or NULL */, const double *d2_edges, int n_edges,
+                              same_feature_zone **out);
+void same_feature_zone_destroy(same_feature_zone *zone);
+int  same_merge_acc_score_features(same_merge_acc *acc, const same_section *moving, const same_section *ref,
+                                   const same_score_features *feats, const same_feature_zone *zone /* may be NULL */, int64_t *out,
+                                   int64_t out_words, double *out_d2 /* [moving rows], may be NULL */);
 /* A merged MetaCell result unpacked to cells (csrc/window_unpack.hip; src/metacell_utils.py:564-766, unpack_metacell_matches with
  * metacells on both sides), without its table: after same_merge_acc_finish, on the final rows where they are and in their order.
  *   same_members_create: the members of `section`'s rows as CSR -- row i owns members [off[i], off[i+1]); per member its XY (the

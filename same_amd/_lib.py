@@ -151,6 +151,11 @@ _PROTOTYPES = {
     "same_score_map_tally": [c_vp, c_vp, ctypes.POINTER(c_i64)],
     "same_score_map_reset": [c_vp],
     "same_merge_acc_score_map": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_dbl, c_i64, c_vp, c_vp],
+    "same_score_features_create": [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, ctypes.POINTER(c_vp)],
+    "same_score_features_destroy": [c_vp],
+    "same_feature_zone_create": [c_vp, c_vp, c_vp, c_vp, c_int, ctypes.POINTER(c_vp)],
+    "same_feature_zone_destroy": [c_vp],
+    "same_merge_acc_score_features": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
     "same_members_create": [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(c_vp)],
     "same_members_destroy": [c_vp],
     "same_merge_acc_unpack": [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_i64],
@@ -187,6 +192,7 @@ SAME_SCORE_MAX_LABELS, SAME_SCORE_MAX_GROUPS, SAME_SCORE_RANKS = 64, 256, 16    
 # same_cell_mark's flag bits (same_merge_acc_score_map) and the rank byte of a row that is not ranked
 SAME_MARK_MATCHED, SAME_MARK_TYPE_MATCH, SAME_MARK_CONSIDERED, SAME_MARK_VIOLATING = 1, 2, 4, 8
 SAME_MARK_TRUTH_KNOWN, SAME_MARK_ON_TRUTH, SAME_MARK_RANKED, SAME_MARK_UNRANKED = 16, 32, 64, 255
+SAME_FEATURE_MAX_COLUMNS, SAME_FEATURE_MAX_EDGES = 4096, 65     # same_score_features_create's and same_feature_zone_create's caps
 SAME_WINDOW_STATS_CAP = 16       # the _cap calls: the 15 words, then sum_j max(0, count_j - 1) of the search's result
 SAME_WINDOW_STATS_TRANSPORT = 17  # SAME_INCUMBENT_TRANSPORT: the 16 words, then sum_j max(0, count_j - 1) of the start
 
@@ -233,6 +239,8 @@ def load():
             L.same_members_destroy.restype = None
             L.same_score_detail_destroy.restype = None
             L.same_score_map_destroy.restype = None
+            L.same_score_features_destroy.restype = None
+            L.same_feature_zone_destroy.restype = None
             L.same_unpack_detail_destroy.restype = None
             if L.same_abi_version() != ABI_VERSION:
                 raise SameHipError(-22, "libsame_hip ABI version mismatch")

@@ -1,5 +1,5 @@
 // window_internal.h -- what the translation units of the device-resident window path share (section.hip, window_stage.hip,
-// window_finish.hip, window_merge.hip, window_score.hip, window_score_detail.hip, window_score_map.hip, window_unpack.hip, window_unpack_detail.hip, window_caller.hip, window_priority.hip, window_knn_prefix.hip, window_recost.hip): the resident objects behind the
+// window_finish.hip, window_merge.hip, window_score.hip, window_score_detail.hip, window_score_map.hip, window_score_feature.hip, window_unpack.hip, window_unpack_detail.hip, window_caller.hip, window_priority.hip, window_knn_prefix.hip, window_recost.hip): the resident objects behind the
 // opaque handles of include/same_hip.h part 4, the per-launch argument blocks, the device side of a window's pair list, the window's
 // logical state (window_state.h: win::State, with the table of what each call requires, leaves and invalidates), the protocol of the merged
 // rows' reader calls (work_sets.h: win::WorkSets), the small host helpers and the batch driver of the window calls.
@@ -512,6 +512,11 @@ struct same_merge_acc {
     win::DevBuf unpack_bins;                  // (released by same_merge_acc_destroy with the buffers above: a DevBuf added here joins its list)
     win::DetailWork ubw;                      // laid over `unpack_bins`: two sets of so many words
     win::WorkSets unpack_bin_sets;            // ... for so many words a set
+    // same_merge_acc_score_features (window_score_feature.hip): the sums, and what a call with a zone works in (that file lays it)
+    win::DevBuf feature, zone;
+    win::DetailWork fw;                       // laid over `feature`: two sets of so many words
+    win::WorkSets feature_sets;               // ... for so many words a set
+    win::WorkSets zone_sets;                  // `zone`: for so many final rows and moving rows; a set: look-back words and totals
 };
 
 namespace win {

@@ -1,5 +1,5 @@
-// work_sets.h -- the protocol of a reader call's work buffer (same_merge_acc_score, _score_detail, _score_map, _unpack: window_internal.h lays
-// the buffers).  Plain C++ (no HIP, nothing dereferenced): tests/native/work_sets_test.cpp walks it alone.
+// work_sets.h -- the protocol of a reader call's work buffer (same_merge_acc_score, _score_detail, _score_map, _score_features, _unpack:
+// window_internal.h lays the buffers).  Plain C++ (no HIP, nothing dereferenced): tests/native/work_sets_test.cpp walks it alone.
 //
 // THE PROTOCOL.  A buffer is laid ONCE for a size and filled ONCE into its idle state; it holds two sets of the words a call counts into,
 // used alternately: a call counts into one set and its first kernel clears the other, which the next call counts into, so a set costs no

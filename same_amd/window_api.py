@@ -314,6 +314,22 @@ class _DeviceFrames:
         self.__dict__.setdefault("_score_maps", []).append(made)
         return made
 
+    def score_features(self, mov_q, ref_q, group_of, n_groups, zone=None):
+        """A study's fixed-point feature columns resident beside the sections (windows.DeviceScoreFeatures) and, with `zone` =
+        (moving flags, reference flags, squared-distance edges), its distance reading (windows.DeviceFeatureZone; else None).  One pair
+        per call -- the matrices are a study's own --, kept until close() or until the study closes them.  -> (features, zone)"""
+        from .windows import DeviceFeatureZone, DeviceScoreFeatures
+
+        held = self.__dict__.setdefault("_score_features", [])
+        with stage("feature columns, groups and zone masks to the device"):
+            feats = DeviceScoreFeatures(self.dmov, self.dref, mov_q, ref_q, group_of, n_groups)
+            held.append(feats)
+            made = None
+            if zone is not None:
+                made = DeviceFeatureZone(feats, *zone)
+                held.append(made)
+        return feats, made
+
     def types_layer(self, variant, types):
         """A type-matrix variant of the moving frame resident beside its section (windows.DeviceTypesLayer): `types` the variant as a
         float64 (rows, commonCT) matrix, `variant` the caller's object it was read from.  Uploaded once per object and kept until close()
@@ -438,6 +454,8 @@ class _DeviceFrames:
             if members is not None:
                 members.close()
         for made in self.__dict__.pop("_score_maps", []):                      # before the sections they were made for
+            made.close()
+        for made in reversed(self.__dict__.pop("_score_features", [])):        # a zone before its features, both before the sections
             made.close()
         for detail in self.__dict__.pop("_score_details", {}).values():        # before the section whose rows they group
             detail.close()

@@ -713,6 +713,23 @@ class MergeAccumulator(_DeviceHandle):
                                                        counts.ctypes.data), "same_merge_acc_score_map")
         return counts, out
 
+    def score_features(self, dmoving, dref, features, zone=None, d2=False):
+        """After finish(): the merged rows read as feature sums (same_merge_acc_score_features, csrc/window_score_feature.hip) under
+        `features`, a DeviceScoreFeatures of the two sections, and `zone`, a DeviceFeatureZone of it (None: no distance reading).
+        -> (the call's int64 words cut by `split_score_features`: `counts`, `rows`, `sums` and with a zone `bin_rows`, `bin_sums`; with
+        `d2` and a zone the float64 squared distance to the zone per moving row, NaN where the row has no subset pair, else None).
+        Touches none of the other reader calls' buffers."""
+        ctx = self.ctx
+        B = 0 if zone is None else zone.n_bins
+        out = np.zeros(score_feature_words(features.n_groups, features.n_columns, B), np.int64)
+        dist = np.empty(features.n_rows, np.float64) if d2 and zone is not None else None
+        with ctx.lock:
+            ctx.check(ctx.lib.same_merge_acc_score_features(self.handle, dmoving.handle, dref.handle, features.handle,
+                                                            None if zone is None else zone.handle, out.ctypes.data, len(out),
+                                                            None if dist is None or not len(dist) else dist.ctypes.data),
+                      "same_merge_acc_score_features")
+        return split_score_features(out, features.n_groups, features.n_columns, B), dist
+
     def unpack(self, mov_members, ref_members, strategy, pairs=False):
         """After finish(): the merged metacell rows unpacked to cells (same_merge_acc_unpack, csrc/window_unpack.hip) under `strategy`
         ("distribute" / "nearest"; `mov_members`, `ref_members`: DeviceMembers of the sections the pass ran over) -> the int64 counts
@@ -1011,6 +1028,84 @@ class DeviceScoreMap(_DeviceHandle):
     def reset(self):
         with self.ctx.lock:
             self.ctx.check(self.ctx.lib.same_score_map_reset(self.handle), "same_score_map_reset")
+
+
+def score_feature_words(n_groups, n_columns, n_bins=0):
+    """int64 words of same_merge_acc_score_features' `out` (SAME_FEATURE_WORDS); n_bins: the zone's distance bins, 0 without a zone"""
+    return 4 + (n_groups + 1) * (1 + n_columns) + ((n_bins + 1) * (1 + n_columns) if n_bins > 0 else 0)
+
+
+def split_score_features(out, n_groups, n_columns, n_bins=0):
+    """the words of same_merge_acc_score_features' `out` by name, in the order include/same_hip.h states: `counts` (4), `rows` (G + 1),
+    `sums` (G + 1, F) and with a zone `bin_rows` (B + 1), `bin_sums` (B + 1, F)"""
+    G, F, B = int(n_groups), int(n_columns), int(n_bins)
+    out = np.asarray(out, np.int64)
+    assert len(out) >= score_feature_words(G, F, B)
+    at = np.cumsum([0, 4, G + 1, (G + 1) * F] + ([B + 1, (B + 1) * F] if B > 0 else []))
+    part = lambda q: out[at[q]:at[q + 1]]
+    got = {"counts": part(0), "rows": part(1), "sums": part(2).reshape(G + 1, F)}
+    if B > 0:
+        got.update(bin_rows=part(3), bin_sums=part(4).reshape(B + 1, F))
+    return got
+
+
+class DeviceScoreFeatures(_DeviceHandle):
+    """What same_merge_acc_score_features sums, resident beside the two sections (same_score_features_create,
+    csrc/window_score_feature.hip): `mov_q` int32 (moving rows, F_m) and `ref_q` int32 (reference rows, F_r), the fixed-point feature
+    columns (|q| <= 2**30; None: the side has no column), `group_of` / `n_groups` as DeviceScoreDetail's.  Made on the moving section's
+    context; read-only: the worker contexts of the device share it.  Close it before its sections."""
+
+    _ENTRY = (None, "same_score_features_destroy")
+
+    def __init__(self, dmoving, dref, mov_q, ref_q, group_of, n_groups):
+        n_m, n_r = len(dmoving.section.xy), len(dref.section.xy)
+        side = lambda q, n: np.zeros((n, 0), np.int32) if q is None else np.ascontiguousarray(q, dtype=np.int32)
+        mq, rq = side(mov_q, n_m), side(ref_q, n_r)
+        for q, n, name in ((mq, n_m, "mov_q"), (rq, n_r, "ref_q")):       # (the library reads rows x columns: nothing it was not given)
+            if q.ndim != 2 or q.shape[0] != n:
+                raise ValueError(f"{name} has shape {q.shape} for a section of {n} rows")
+        g = None if group_of is None else np.ascontiguousarray(group_of, dtype=np.int32)
+        if g is not None and g.shape != (n_m,):
+            raise ValueError(f"group_of has shape {g.shape} for a section of {n_m} rows")
+        self.F_m, self.F_r, self.n_groups = mq.shape[1], rq.shape[1], int(n_groups)
+        self.n_columns, self.n_rows, self.n_ref_rows = self.F_m + self.F_r, n_m, n_r
+        self.ctx = ctx = dmoving.ctx
+        h = ctypes.c_void_p()
+        with ctx.lock:
+            rc = ctx.lib.same_score_features_create(dmoving.handle, dref.handle, mq.ctypes.data if mq.size else None, self.F_m,
+                                                    rq.ctypes.data if rq.size else None, self.F_r,
+                                                    None if g is None or not len(g) else g.ctypes.data, self.n_groups, ctypes.byref(h))
+            if rc != 0 and h.value:
+                ctx.lib.same_score_features_destroy(h)
+            ctx.check(rc, "same_score_features_create")
+        self.handle = h
+
+
+class DeviceFeatureZone(_DeviceHandle):
+    """The zone and the subset of a distance reading, resident beside a DeviceScoreFeatures (same_feature_zone_create): `mov_flags`,
+    `ref_flags` uint8 per section row, bit 0 "zone side", bit 1 "subset side" (None: every bit set); `d2_edges` the thresholds on the
+    SQUARED distance, non-decreasing, 2 .. 65 of them.  Close it before its features."""
+
+    _ENTRY = (None, "same_feature_zone_destroy")
+
+    def __init__(self, features, mov_flags, ref_flags, d2_edges):
+        flags = lambda f: None if f is None else np.ascontiguousarray(f, dtype=np.uint8)
+        mf, rf = flags(mov_flags), flags(ref_flags)
+        for f, n, name in ((mf, features.n_rows, "mov_flags"), (rf, features.n_ref_rows, "ref_flags")):
+            if f is not None and f.shape != (n,):                         # (the library reads one entry per row: nothing it was not given)
+                raise ValueError(f"{name} has shape {f.shape} for a section of {n} rows")
+        e = np.ascontiguousarray(d2_edges, dtype=np.float64).reshape(-1)
+        self.features, self.n_bins = features, len(e) - 1
+        self.ctx = ctx = features.ctx
+        h = ctypes.c_void_p()
+        with ctx.lock:
+            rc = ctx.lib.same_feature_zone_create(features.handle, None if mf is None or not len(mf) else mf.ctypes.data,
+                                                  None if rf is None or not len(rf) else rf.ctypes.data, e.ctypes.data if len(e) else None,
+                                                  len(e), ctypes.byref(h))
+            if rc != 0 and h.value:
+                ctx.lib.same_feature_zone_destroy(h)
+            ctx.check(rc, "same_feature_zone_create")
+        self.handle = h
 
 
 UNPACK_STRATEGIES = {"distribute": _lib.SAME_UNPACK_DISTRIBUTE, "nearest": _lib.SAME_UNPACK_NEAREST}

@@ -1054,6 +1054,64 @@ void same_unpack_detail_destroy(same_unpack_detail *detail);
 int  same_merge_acc_unpack_detail(same_merge_acc *acc, const same_members *moving, const same_members *ref, int strategy,
                                   const same_unpack_detail *detail, const same_score_detail *groups /* may be NULL: one group */,
                                   int64_t *out, int64_t out_words);
+/* The unpacked pairs read as FEATURE SUMS (csrc/window_unpack_feature.hip): same_merge_acc_score_features' reading at cell level -- what
+ * examples/luad/reproduce_figures.ipynb cells 16-22 compute, which gather the two modalities' rows of every CELL pair of cell 12's
+ * unpacked matches.  The pairs stay on the device behind same_merge_acc_unpack's own phases; the kernels are the section call's
+ * (csrc/feature_kernels.h), reading a cell pair where that call reads a final row.
+ *   same_unpack_features_create: one int32 fixed-point row per MEMBER, in CSR order -- mov_q[moving members][F_m], ref_q[reference
+ *   members][F_r]; the quantisation is same_score_features_create's, word for word.  member_group[moving members]: the group of the
+ *   moving CELL, negative: the cell has no group; NULL: every cell in group 0.  Uploaded once on `moving`'s context, resident on its
+ *   device, read-only and shared by the worker contexts like same_members; destroy it before the members.  Checked on the host before
+ *   anything is uploaded: SAME_EINVAL for the shapes same_score_features_create refuses (over member counts) and for members on
+ *   different devices; SAME_ERANGE for a |q| > 2^30 or a group >= n_groups.  Caps: SAME_FEATURE_MAX_COLUMNS, SAME_SCORE_MAX_GROUPS.
+ *   same_unpack_zone_create: exactly same_feature_zone_create's rules, per member: mov_flags[moving members], ref_flags[reference
+ *   members], bit 0 "zone side", bit 1 "subset side", NULL: every bit set; a pair (i, j) is a ZONE pair iff mov_flags[i] & ref_flags[j]
+ *   & 1, a SUBSET pair iff ... & 2; d2_edges cut the SQUARED distance right-closed; 2 to SAME_FEATURE_MAX_EDGES edges.  Destroy it
+ *   before `feats`.
+ *   same_merge_acc_unpack_features: `moving`, `ref`, `strategy` as same_merge_acc_unpack's.  With G = n_groups, F = F_m + F_r and
+ *   B = n_edges - 1 (0 without `zone`), `out` holds out_words >= SAME_UNPACK_FEATURE_WORDS(G, F, B) = 4 + SAME_FEATURE_WORDS(G, F, B)
+ *   int64 words:
+ *     [0 .. 4)   exactly same_merge_acc_unpack's out_counts for the same arguments;
+ *     [4 ..)     same_merge_acc_score_features' `out`, with "final row" read as "cell pair": counts [4] (pairs; those whose moving cell
+ *                has a group; zone pairs; subset pairs), rows [G+1], sums [(G+1)*F], and with `zone` bin_rows [B+1], bin_sums [(B+1)*F].
+ *   A pair's bin is its moving member's group, its position its REFERENCE MEMBER's XY (same_members').  d2: the fp64 minimum over all
+ *   zone pairs of dx*dx + dy*dy, without contraction (a pair that is both: 0); with no zone pair every d2 is NaN and every subset pair
+ *   is in bin B.  out_d2 (may be NULL) and out_ref_member (may be NULL), `capacity` entries each, are indexed by PAIR, in
+ *   same_merge_acc_unpack's pair order -- which keeps the call defined where hostile final rows name a moving row twice: the d2 of a
+ *   subset pair, NaN otherwise (all NaN without `zone`); the flat reference member.  capacity < out[1] with either array given:
+ *   SAME_EINVAL with out[0 .. 4) FILLED, the rest of `out` and the arrays untouched.
+ * What the call asks of the runtime for n final rows on the accumulator's context: n == 0 nothing (out is zeros); without a pair what
+ * same_merge_acc_unpack asks.  Else, without `zone`: exactly ONE launch more than same_merge_acc_unpack for the same rows (the sums by
+ * group), THREE copies (64 bytes after the sizes; 64 bytes and the words of `out` and one more before the last wait) and with
+ * out_ref_member a fourth, TWO waits -- the sizes' and the last: no wait of its own.  With `zone`: FOUR launches more (the sums by group,
+ * the flag kernel; after the reader's wait the walk and the sums by bin), one copy more (32 bytes) and ONE wait more, taken INSIDE the
+ * reader between the flag kernel and the grid build -- the host must know the zone pairs' count and box first --, with out_d2 one copy
+ * more; where there is a zone pair grid.h's build runs behind that wait as in same_merge_acc_score_features (its own read-back, wait,
+ * fill and three launches, which the context's counters do not count).  No fill -- but a call that lays the unpack work buffer fills
+ * its head, one that lays the sums' buffer (the first, and the first with more words) fills it, and with `zone` one that lays the
+ * zone work buffer (the first, and the first over more pairs) fills its head: one fill each.  Every buffer is left as it was found:
+ * score, detail, map, feature, both unpack calls and this call alternate on one accumulator without a fill, and a call that failed
+ * between an enqueue and its wait leaves the buffers it worked in marked not laid, so the next call lays them again.
+ * SAME_EINVAL / SAME_ERANGE as same_merge_acc_unpack, outputs untouched; SAME_EINVAL also for `feats` made for other members or on
+ * another device, `zone` made for other `feats`, out_words too small, an array given with capacity < 0; SAME_ERANGE (outputs
+ * untouched) with `zone` for a zone or subset pair whose reference member XY is not finite -- found by the flag kernel, before
+ * anything is binned by it. */
+#define SAME_UNPACK_FEATURE_WORDS(G, F, B) (4 + SAME_FEATURE_WORDS(G, F, B))
+typedef struct same_unpack_features same_unpack_features;
+typedef struct same_unpack_zone same_unpack_zone;
+int  same_unpack_features_create(const same_members *moving, const same_members *ref, const int32_t *mov_q /* host, [moving members][F_m] */,
+                                 int F_m, const int32_t *ref_q /* host, [ref members][F_r] */, int F_r,
+                                 const int32_t *member_group /* [moving members] or NULL: every cell in group 0 */, int n_groups,
+                                 same_unpack_features **out);
+void same_unpack_features_destroy(same_unpack_features *feats);
+int  same_unpack_zone_create(const same_unpack_features *feats, const uint8_t *mov_member_flags /* [moving members] or NULL */,
+                             const uint8_t *ref_member_flags /* [ref members] or NULL */, const double *d2_edges, int n_edges,
+                             same_unpack_zone **out);
+void same_unpack_zone_destroy(same_unpack_zone *zone);
+int  same_merge_acc_unpack_features(same_merge_acc *acc, const same_members *moving, const same_members *ref, int strategy,
+                                    const same_unpack_features *feats, const same_unpack_zone *zone /* may be NULL */, int64_t *out,
+                                    int64_t out_words, double *out_d2 /* [capacity], may be NULL */,
+                                    int64_t *out_ref_member /* [capacity], may be NULL */, int64_t capacity);
 
 /* ======================================================================================================================
  * part 4 -- COMM: one communicator per context, RCCL over xGMI

@@ -162,6 +162,11 @@ _PROTOTYPES = {
     "same_unpack_detail_create": [c_vp, c_int, c_vp, c_vp, c_int, ctypes.POINTER(c_vp)],
     "same_unpack_detail_destroy": [c_vp],
     "same_merge_acc_unpack_detail": [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_i64],
+    "same_unpack_features_create": [c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, ctypes.POINTER(c_vp)],
+    "same_unpack_features_destroy": [c_vp],
+    "same_unpack_zone_create": [c_vp, c_vp, c_vp, c_vp, c_int, ctypes.POINTER(c_vp)],
+    "same_unpack_zone_destroy": [c_vp],
+    "same_merge_acc_unpack_features": [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64],
     "same_host_alloc": [c_vp, c_sz, ctypes.POINTER(c_vp)],
     "same_host_free": [c_vp, c_vp],
     "same_comm_unique_id": [c_vp],
@@ -242,6 +247,8 @@ def load():
             L.same_score_features_destroy.restype = None
             L.same_feature_zone_destroy.restype = None
             L.same_unpack_detail_destroy.restype = None
+            L.same_unpack_features_destroy.restype = None
+            L.same_unpack_zone_destroy.restype = None
             if L.same_abi_version() != ABI_VERSION:
                 raise SameHipError(-22, "libsame_hip ABI version mismatch")
             _lib = L

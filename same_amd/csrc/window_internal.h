@@ -1,5 +1,5 @@
 // window_internal.h -- what the translation units of the device-resident window path share (section.hip, window_stage.hip,
-// window_finish.hip, window_merge.hip, window_score.hip, window_score_detail.hip, window_score_map.hip, window_score_feature.hip, window_unpack.hip, window_unpack_detail.hip, window_caller.hip, window_priority.hip, window_knn_prefix.hip, window_recost.hip): the resident objects behind the
+// window_finish.hip, window_merge.hip, window_score.hip, window_score_detail.hip, window_score_map.hip, window_score_feature.hip, window_unpack.hip, window_unpack_detail.hip, window_unpack_feature.hip, window_caller.hip, window_priority.hip, window_knn_prefix.hip, window_recost.hip): the resident objects behind the
 // opaque handles of include/same_hip.h part 4, the per-launch argument blocks, the device side of a window's pair list, the window's
 // logical state (window_state.h: win::State, with the table of what each call requires, leaves and invalidates), the protocol of the merged
 // rows' reader calls (work_sets.h: win::WorkSets), the small host helpers and the batch driver of the window calls.
@@ -517,6 +517,11 @@ struct same_merge_acc {
     win::DetailWork fw;                       // laid over `feature`: two sets of so many words
     win::WorkSets feature_sets;               // ... for so many words a set
     win::WorkSets zone_sets;                  // `zone`: for so many final rows and moving rows; a set: look-back words and totals
+    // same_merge_acc_unpack_features (window_unpack_feature.hip): it runs same_merge_acc_unpack's phases in `uw`; its sums and zone work
+    win::DevBuf unpack_feature, unpack_zone;
+    win::DetailWork ufw;                      // laid over `unpack_feature`: two sets of so many words
+    win::WorkSets unpack_feature_sets;        // ... for so many words a set
+    win::WorkSets unpack_zone_sets;           // `unpack_zone`: for so many pairs; a set: look-back words and totals
 };
 
 namespace win {

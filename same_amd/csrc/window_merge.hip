@@ -366,7 +366,7 @@ void same_merge_acc_destroy(same_merge_acc *a) {
     free_rows(a);
     if (a->dcount) (void)hipFree(a->dcount);
     for (DevBuf *b : {&a->near_start, &a->near_boxes, &a->scan_words, &a->work, &a->out, &a->score, &a->detail, &a->unpack, &a->unpack_slices, &a->unpack_pairs,
-                      &a->unpack_bins, &a->feature, &a->zone})
+                      &a->unpack_bins, &a->feature, &a->zone, &a->unpack_feature, &a->unpack_zone})
         release(*b);
     delete a;
 }

@@ -1,4 +1,4 @@
-"""A study read as FEATURE MEANS of its matched pairs: `sliding_window_score_features`.
+"""A study read as FEATURE MEANS of its matched pairs: `sliding_window_score_features` (at cell level, `unpack=`: §5.20).
 
 Every study the reference's notebooks report ends the same way: the matches put two modalities' feature matrices side by side and the
 result is read as means.  examples/luad/reproduce_figures.ipynb cells 16-22 gather the PCF rows and the Xenium rows of every matched
@@ -20,15 +20,22 @@ value is rounded to a multiple of `resolution` = 2**-e, which is 2**-30 of the p
 error of at most 2**-31 of it).
 
 `score_table_features` is the same reading of a result TABLE with numpy: what the device must equal, and what inputs the device
-refuses go through."""
+refuses go through.
+
+AT CELL LEVEL (`unpack=`).  The LUAD notebook never reads metacell pairs: cell 12 unpacks the metacell matches to cells and everything
+after it is built on the cell pairs -- a metacell has no PCF or Xenium row, and its annotation is not a cell's.  With `unpack=` the
+features, groups and masks are per ORIGINAL cell of the two MetaCell objects, reordered once into the member lists' CSR order, and one
+call per result in the unpack call's place sums them over the cell pairs where the unpack phases make them
+(csrc/window_unpack_feature.hip).  `score_unpacked_features` is its host statement, built from `score_unpacked`'s table and the same
+numpy sums."""
 import collections
 
 import numpy as np
 import pandas as pd
 
 from . import _lib
-from .score_details import checked_groups
-from .scores import DeviceScores, _frame_rows, _scored_study, checked_score_params
+from .score_details import _NoMetaCellObjects, checked_groups
+from .scores import DeviceScores, _frame_rows, _scored_study, checked_score_params, checked_unpack, score_unpacked, unpack_record
 from .variants import _frames_of
 
 ScoreFeatures = collections.namedtuple("ScoreFeatures", "scores rows means sums resolution zones pairs")
@@ -161,7 +168,7 @@ class FeatureSpec:
     """What a study sums, checked and quantised once for the device route and the host statement: the two fixed-point matrices (None: the
     side has no column), their exponents and names, the moving rows' group codes and names, the zone's flags, thresholds and labels."""
 
-    def __init__(self, ref_df, mov_df, moving_features, ref_features, group_by, zones):
+    def __init__(self, ref_df, mov_df, moving_features, ref_features, group_by, zones, xy_cols=("X", "Y"), default_group="cell_type"):
         if moving_features is None and ref_features is None:
             raise ValueError("pass moving_features, ref_features or both: there is no feature to read")
         mov_x, mov_names = checked_features(moving_features, mov_df, "moving")
@@ -173,18 +180,18 @@ class FeatureSpec:
         self.ref_q, e_r = quantize_features(ref_x) if ref_x is not None else (None, np.zeros(0, np.int32))
         self.e = np.concatenate((e_m, e_r)).astype(np.int32)
         if group_by is None:
-            if "cell_type" not in mov_df.columns:
-                raise ValueError("group_by=None groups by the moving frame's 'cell_type': it has no such column")
-            group_by = "cell_type"
+            if default_group not in mov_df.columns:
+                raise ValueError(f"group_by=None groups by the moving frame's '{default_group}': it has no such column")
+            group_by = default_group
         self.group_codes, self.group_names = checked_groups(group_by, mov_df)
         self.n_groups = max(len(self.group_names), 1)
         self.zone = checked_zones(zones, len(ref_df), len(mov_df))
         self.ref_xy_finite = True
         if self.zone is not None:
-            for c in ("X", "Y"):
+            for c in xy_cols:
                 if c not in ref_df.columns:
                     raise ValueError(f"zones measure distances between reference cells: the ref frame has no '{c}' column")
-            self.ref_xy_finite = bool(np.isfinite(ref_df[["X", "Y"]].to_numpy(dtype=np.float64)).all())
+            self.ref_xy_finite = bool(np.isfinite(ref_df[list(xy_cols)].to_numpy(dtype=np.float64)).all())
         self.n_mov, self.n_ref = len(mov_df), len(ref_df)
 
     @property
@@ -317,15 +324,59 @@ def score_table_features(table, ref, moving, *, cell_id_col, moving_features=Non
     return TableFeatures(rows, means, sums, spec.resolution(), zone, pairs)
 
 
+def unpack_spec(ref_mc, moving_mc, moving_features, ref_features, group_by, zones):
+    """the FeatureSpec of a cell-level reading: everything per row of the two objects' `original_df` -- features, the moving cells'
+    groups (None: their `cell_type_col`), the masks; positions are the reference cells' `x_col`, `y_col`"""
+    return FeatureSpec(ref_mc.original_df, moving_mc.original_df, moving_features, ref_features, group_by, zones,
+                       xy_cols=(ref_mc.x_col, ref_mc.y_col), default_group=moving_mc.cell_type_col)
+
+
+def _cell_frames(spec, ref_mc, moving_mc, rows_m, rows_r, words, d2, per_pair):
+    """both routes' one statement of a cell-level result's frames and dtypes: `words` and the pairs' rows in the two `original_df`s"""
+    rows, means, sums, zone = spec.frames(words)
+    pairs = None
+    if per_pair:
+        pairs = spec.pair_frame(pd.Index(moving_mc.original_df[moving_mc.original_idx_col].to_numpy(), name=moving_mc.original_idx_col),
+                                ref_mc.original_df[ref_mc.original_idx_col].to_numpy(), rows_m, rows_r, d2)
+    return TableFeatures(rows, means, sums, spec.resolution(), zone, pairs)
+
+
+def score_unpacked_features(table, ref_mc, moving_mc, strategy, *, moving_features=None, ref_features=None, group_by=None, zones=None,
+                            per_pair=False, _spec=None):
+    """The cell-level feature reading of ONE result table over the MetaCell objects `ref_mc` and `moving_mc`, with numpy -- what
+    `sliding_window_score_features(..., unpack=strategy)`'s frames of that result must equal, bit for bit, and what serves everything
+    the device refuses: `score_unpacked`'s cell pairs (examples/luad/reproduce_figures.ipynb cell 12), then `score_table_features`'
+    sums over them -- the same quantisation of the ORIGINAL cells' columns, the same `means_from_sums`, `nearest_zone_d2` over the
+    reference cells' own coordinates (cell 20), the bins of `pd.cut` (cells 21-22).  -> `TableFeatures`: `rows` count cell pairs per
+    group of the moving CELL (`group_by`: a column of `moving_mc.original_df` or an array over its rows; None: its `cell_type_col`);
+    `pairs` (per_pair) is indexed by the moving cell id and carries `ref_id`, the reference cell id, and with `zones`
+    `distance_to_zone`.  `moving_features` / `ref_features`: a DataFrame on the object's `original_df` index, an (n_cells, F) array or
+    a list of `original_df` column names; the masks of `zones` are per cell."""
+    checked_unpack(strategy, ref_mc, moving_mc)
+    if strategy is None:
+        raise ValueError("strategy must be 'nearest' or 'distribute'")
+    spec = _spec if _spec is not None else unpack_spec(ref_mc, moving_mc, moving_features, ref_features, group_by, zones)
+    _rec, cells = score_unpacked(table, ref_mc, moving_mc, strategy)
+    if len(cells):
+        rows_m = _frame_rows(moving_mc.original_df[moving_mc.original_idx_col].to_numpy(), cells["Aligned_cell_id"].to_numpy(), "moving")
+        rows_r = _frame_rows(ref_mc.original_df[ref_mc.original_idx_col].to_numpy(), cells["Ref_cell_id"].to_numpy(), "reference")
+    else:
+        rows_m = rows_r = np.zeros(0, np.int64)
+    ref_xy = ref_mc.original_df[[ref_mc.x_col, ref_mc.y_col]].to_numpy(dtype=np.float64) if spec.zone is not None else None
+    words, d2 = host_words(spec, rows_m, rows_r, ref_xy)
+    return _cell_frames(spec, ref_mc, moving_mc, rows_m, rows_r, words, d2, per_pair)
+
+
 # ---- on the device -------------------------------------------------------------------------------------------------------------------------
 class FeatureScores(DeviceScores):
     """`scores.DeviceScores` whose `record` makes the feature call beside the score call (windows.MergeAccumulator.score_features):
     the words of every result (`words`, in the jobs' order) and with per_pair its rows and squared distances (`pairs`)."""
 
-    def __init__(self, score_delaunay, vertex_col, params, spec, per_pair):
-        super().__init__(score_delaunay, vertex_col, params, tables=False)
+    def __init__(self, score_delaunay, vertex_col, params, spec, per_pair, unpack=None, ref_mc=None, moving_mc=None):
+        super().__init__(score_delaunay, vertex_col, params, tables=False, unpack=unpack, ref_mc=ref_mc, moving_mc=moving_mc)
         self.spec, self.per_pair = spec, bool(per_pair)
-        self.feats = self.zone = None        # windows.DeviceScoreFeatures, windows.DeviceFeatureZone once `prepare` agreed
+        # windows.DeviceScoreFeatures, windows.DeviceFeatureZone (with `unpack`: DeviceUnpackFeatures, DeviceUnpackZone) once `prepare` agreed
+        self.feats = self.zone = None
         self.words, self.pairs = [], []
 
     def prepare(self, frames, job):
@@ -334,11 +385,41 @@ class FeatureScores(DeviceScores):
         if not self.spec.device_ok or not super().prepare(frames, job):
             return False
         s = self.spec
+        if self.unpack is not None:
+            # per original cell -> the member lists' CSR order, once (`prepare` made the members: `.rows` are their rows of original_df)
+            mm, rm = self.members
+            at = lambda x, rows: None if x is None else x[rows]
+            zone = None if s.zone is None else (s.zone[0][mm.rows], s.zone[1][rm.rows], s.zone[2])
+            self.feats, self.zone = frames.unpack_features(mm, rm, at(s.mov_q, mm.rows), at(s.ref_q, rm.rows), s.group_codes[mm.rows],
+                                                           s.n_groups, zone)
+            return True
         self.feats, self.zone = frames.score_features(s.mov_q, s.ref_q, s.group_codes, s.n_groups, None if s.zone is None else s.zone[:3])
         return True
 
+    def unpacked(self, acc):
+        """`DeviceScores.unpacked` by ONE call in the unpack call's place (windows.MergeAccumulator.unpack_features): its counts are the
+        record's cell keys, its words the result's sums; with per_pair the pairs' rows in the two `original_df`s and d2 per moving cell"""
+        mm, rm = self.members
+        counts, words, d2, ref_member = self._infeasible_as_the_reference(
+            lambda: acc.unpack_features(mm, rm, self.unpack, self.feats, self.zone, d2=self.per_pair and self.zone is not None,
+                                        pairs=self.per_pair))
+        self.words.append(words)
+        if self.per_pair:
+            a = acc.final_rows()["a_row"].astype(np.int64) if acc.n_final else np.zeros(0, np.int64)
+            n_a = mm.off[a + 1] - mm.off[a]
+            within = np.arange(int(n_a.sum()), dtype=np.int64) - np.repeat(np.cumsum(n_a) - n_a, n_a)
+            rows_m, rows_r = mm.rows[np.repeat(mm.off[a], n_a) + within], rm.rows[ref_member]
+            d2_cell = None
+            if d2 is not None:
+                d2_cell = np.full(self.spec.n_mov, np.nan)
+                d2_cell[rows_m] = d2
+            self.pairs.append((rows_m, rows_r, d2_cell))
+        return unpack_record(counts[1], counts[2])
+
     def record(self, frames, acc):
         rec = super().record(frames, acc)
+        if self.unpack is not None:          # (`unpacked` made the call)
+            return rec
         words, d2 = acc.score_features(frames.dmov, frames.dref, self.feats, self.zone, d2=self.per_pair)
         self.words.append(words)
         if self.per_pair:
@@ -348,7 +429,7 @@ class FeatureScores(DeviceScores):
 
     def finished(self, frames):
         """the resident objects closed with the study: the zone before its features"""
-        held = frames.__dict__.get("_score_features", [])
+        held = frames.__dict__.get("_score_features" if self.unpack is None else "_unpack_features", [])
         for made in (self.zone, self.feats):
             if made is not None:
                 if made in held:
@@ -360,7 +441,7 @@ class FeatureScores(DeviceScores):
 def sliding_window_score_features(ref, moving, commonCT=None, *, moving_features=None, ref_features=None, group_by=None, zones=None,
                                   per_pair=False, type_variants=None, param_sets=None, optim_params=None, gurobi_params=None,
                                   score_delaunay=None, score_delaunay_vertex_col=None, score_params=None, workers=None, triangulator=None,
-                                  ctx=None, batch=None, moving_delaunay=None, moving_delaunay_vertex_col=None):
+                                  ctx=None, batch=None, moving_delaunay=None, moving_delaunay_vertex_col=None, unpack=None):
     """`sliding_window_scores` with every result read as feature means of its matched pairs as well, over the same one pass of the
     windows and without a table: -> `ScoreFeatures`
       scores      `sliding_window_scores`' frame for the same arguments;
@@ -370,36 +451,61 @@ def sliding_window_score_features(ref, moving, commonCT=None, *, moving_features
       zones       with `zones`: `zones[v][s]` that result's `ZoneReading` per distance bin; else None;
       pairs       with per_pair: `pairs[v][s]`, indexed like the moving frame: `ref_id` and with `zones` `distance_to_zone`; else None.
     `moving_features`, `ref_features`: a DataFrame on the frame's index, an (n, F) array or a list of the frame's own column names, of
-    any float or integer dtype; at least one side.  MetaCell objects are read at metacell level: the features are per row of their
-    `metacell_df`.  `group_by`: `score_details.checked_groups`'; None: the moving frame's `cell_type`.  `zones`: `FeatureZones(
+    any float or integer dtype; at least one side.  Without `unpack` MetaCell objects are read at metacell level: the features are per
+    row of their `metacell_df`.  `group_by`: `score_details.checked_groups`'; None: the moving frame's `cell_type`.  `zones`: `FeatureZones(
     zone_moving, zone_ref, subset_moving, subset_ref, edges, labels=None)` -- four boolean masks per row (None: all), `edges` the
-    distances as given to `pd.cut`.  The other keywords are `sliding_window_scores`' but for `tables` and `unpack`.  A value that is not
+    distances as given to `pd.cut`.  The other keywords are `sliding_window_scores`' but for `tables`.  A value that is not
     finite, a wrong length, a mask of the wrong length, edges that decrease and what `sliding_window_scores` refuses raise ValueError
     before a job or a device is touched.
     A column with one huge outlier loses its small values: see `resolution`.
     On the device one call per result beside the score call sums the fixed-point columns where the merged rows are
     (csrc/window_score_feature.hip).  What `scores.DeviceScores.prepare` refuses, more columns or groups than the library's caps (4096,
     256), a job off the shared pass and non-finite reference XY with `zones` go through `score_table_features` on the tables: the same
-    frames, nothing saved."""
+    frames, nothing saved.
+    `unpack` ("nearest" / "distribute"; `ref` and `moving` MetaCell objects, `scores.checked_unpack`): the reading at CELL level, as
+    examples/luad/reproduce_figures.ipynb cells 12-22 make it.  `moving_features` and `ref_features` are then per ORIGINAL cell -- a
+    DataFrame on the object's `original_df` index, an (n_cells, F) array or a list of `original_df` column names --, `group_by` is per
+    moving cell (None: the cells' `cell_type_col`) and the masks of `zones` are per cell; a pair's position is its reference CELL's
+    coordinates.  The rows are reordered into the member lists' CSR order once, before the upload.  Every frame counts cell pairs;
+    `scores` carries `cells_matched`, `cell_type_matches` and `cell_accuracy`; `pairs[v][s]` is indexed by the moving cell id and
+    carries `ref_id`, the reference cell id, and `distance_to_zone`.  One call per result in the unpack call's place sums where the
+    unpack phases make the pairs (csrc/window_unpack_feature.hip); every frame equals `score_unpacked_features` of its table, which
+    also serves what the device refuses: whatever `score_unpacked` serves, columns or groups over the caps, non-finite reference cell
+    coordinates with `zones`, a job off the shared pass."""
     params = checked_score_params(score_params)
     ref_arg, moving_arg, ref_df, mov_df = _frames_of(ref, moving)
     for df, name in ((ref_df, "ref"), (mov_df, "moving")):
         if not isinstance(df, pd.DataFrame):
             raise ValueError(f"the {name} frame is no DataFrame")
-    spec = FeatureSpec(ref_df, mov_df, moving_features, ref_features, group_by, zones)
-    hook = FeatureScores(score_delaunay, score_delaunay_vertex_col, params, spec, per_pair)
+    # (over plain frames: a ValueError that is a TypeError too, as the call raised for `unpack` before it had the keyword --
+    # tests/test_score_features_cpu.py still asserts it; score_details does the same)
+    checked_unpack(unpack, ref_arg, moving_arg, no_objects=_NoMetaCellObjects)
+    if unpack is None:
+        spec = FeatureSpec(ref_df, mov_df, moving_features, ref_features, group_by, zones)
+    else:
+        spec = unpack_spec(ref_arg, moving_arg, moving_features, ref_features, group_by, zones)
+    hook = FeatureScores(score_delaunay, score_delaunay_vertex_col, params, spec, per_pair, unpack, ref_arg, moving_arg)
     scores, nested, hook = _scored_study(ref, moving, commonCT, type_variants=type_variants, param_sets=param_sets, optim_params=optim_params,
                                          gurobi_params=gurobi_params, score_delaunay=score_delaunay,
                                          score_delaunay_vertex_col=score_delaunay_vertex_col, score_params=params, tables=False,
                                          workers=workers, triangulator=triangulator, ctx=ctx, batch=batch, moving_delaunay=moving_delaunay,
-                                         moving_delaunay_vertex_col=moving_delaunay_vertex_col, unpack=None, hook=hook)
+                                         moving_delaunay_vertex_col=moving_delaunay_vertex_col, unpack=unpack, hook=hook)
     n_sets = len(nested[0])
     job = hook.job
     cid = job.optim_params["cell_id_col"]
-    if hook.records is not None:
+    if hook.records is not None and unpack is not None:
+        rows_of = lambda q: hook.pairs[q] if per_pair else (None, None, None)       # (rows in the two original_df, d2 per moving cell)
+        got = [_cell_frames(spec, ref_arg, moving_arg, rows_of(q)[0], rows_of(q)[1], w, rows_of(q)[2], per_pair) for q, w in enumerate(hook.words)]
+        flat = [(g.rows, g.means, g.sums, g.zones) for g in got]
+        pairs = [g.pairs for g in got] if per_pair else None
+    elif hook.records is not None:
         flat = [spec.frames(w) for w in hook.words]
         pairs = [spec.pair_frame(job.moving.index, job.ref[cid].to_numpy(), *p) for p in hook.pairs] if per_pair else None
-    else:                                               # not read on the device: the host statement on every table
+    elif unpack is not None:                            # not read on the device: the host statement on every table
+        got = [score_unpacked_features(t, ref_arg, moving_arg, unpack, per_pair=per_pair, _spec=spec) for per_set in nested for t in per_set]
+        flat = [(g.rows, g.means, g.sums, g.zones) for g in got]
+        pairs = [g.pairs for g in got] if per_pair else None
+    else:
         got = [score_table_features(t, job.ref, job.moving, cell_id_col=cid, per_pair=per_pair, _spec=spec) for per_set in nested for t in per_set]
         flat = [(g.rows, g.means, g.sums, g.zones) for g in got]
         pairs = [g.pairs for g in got] if per_pair else None

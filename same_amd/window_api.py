@@ -330,6 +330,23 @@ class _DeviceFrames:
                 held.append(made)
         return feats, made
 
+    def unpack_features(self, mov_members, ref_members, mov_q, ref_q, member_group, n_groups, zone=None):
+        """`score_features` at cell level: one fixed-point row per MEMBER in CSR order and the moving cells' groups resident beside the
+        two member lists (windows.DeviceUnpackFeatures) and, with `zone` = (moving member flags, reference member flags,
+        squared-distance edges), the distance reading (windows.DeviceUnpackZone; else None).  One pair per call, kept until close() or
+        until the study closes them.  -> (features, zone)"""
+        from .windows import DeviceUnpackFeatures, DeviceUnpackZone
+
+        held = self.__dict__.setdefault("_unpack_features", [])
+        with stage("member feature columns, groups and zone masks to the device"):
+            feats = DeviceUnpackFeatures(mov_members, ref_members, mov_q, ref_q, member_group, n_groups)
+            held.append(feats)
+            made = None
+            if zone is not None:
+                made = DeviceUnpackZone(feats, *zone)
+                held.append(made)
+        return feats, made
+
     def types_layer(self, variant, types):
         """A type-matrix variant of the moving frame resident beside its section (windows.DeviceTypesLayer): `types` the variant as a
         float64 (rows, commonCT) matrix, `variant` the caller's object it was read from.  Uploaded once per object and kept until close()
@@ -450,6 +467,8 @@ class _DeviceFrames:
         for _held, detail in self.__dict__.pop("_unpack_details", {}).values():   # before the members whose type rows they hold
             if detail is not None:
                 detail.close()
+        for made in reversed(self.__dict__.pop("_unpack_features", [])):       # a zone before its features, both before their members
+            made.close()
         for _held, members in self.__dict__.pop("_members", {}).values():      # before the section whose rows they list
             if members is not None:
                 members.close()

@@ -763,6 +763,31 @@ class MergeAccumulator(_DeviceHandle):
                                                            len(out)), "same_merge_acc_unpack_detail")
         return split_unpack_detail(out, detail.n_labels, n_groups)
 
+    def unpack_features(self, mov_members, ref_members, strategy, features, zone=None, d2=False, pairs=False):
+        """After finish(): `unpack`'s pairs read as feature sums where they are made (same_merge_acc_unpack_features,
+        csrc/window_unpack_feature.hip) under `features`, a DeviceUnpackFeatures of the two member lists, and `zone`, a DeviceUnpackZone
+        of it (None: no distance reading).  -> (`unpack`'s four int64 counts; the feature words cut by `split_score_features`, "final
+        row" read as "cell pair"; with `d2` the float64 squared distance to the zone per PAIR, NaN where it is no subset pair, else
+        None; with `pairs` per pair the flat index of its reference member, else None) -- the pairs in `unpack`'s order.  A merge names
+        a moving row once, so the moving side's member count bounds the pairs: one call."""
+        if strategy not in UNPACK_STRATEGIES:
+            raise ValueError(f"strategy must be one of {tuple(UNPACK_STRATEGIES)}, not {strategy!r}")
+        ctx = self.ctx
+        B = 0 if zone is None else zone.n_bins
+        out = np.zeros(4 + score_feature_words(features.n_groups, features.n_columns, B), np.int64)
+        cap = mov_members.n_members
+        dist = np.empty(cap, np.float64) if d2 else None
+        ref_member = np.empty(cap, np.int64) if pairs else None
+        with ctx.lock:
+            ctx.check(ctx.lib.same_merge_acc_unpack_features(self.handle, mov_members.handle, ref_members.handle, UNPACK_STRATEGIES[strategy],
+                                                             features.handle, None if zone is None else zone.handle, out.ctypes.data, len(out),
+                                                             None if dist is None else dist.ctypes.data,
+                                                             None if ref_member is None else ref_member.ctypes.data, cap),
+                      "same_merge_acc_unpack_features")
+        n = int(out[1])
+        return (out[:4], split_score_features(out[4:], features.n_groups, features.n_columns, B), None if dist is None else dist[:n],
+                None if ref_member is None else ref_member[:n])
+
     def columns(self, dmoving, dref, n_final, n_types, extra_moving=(), extra_ref=(), layer=None):
         """After finish(): the merged table's columns written by the device straight into page-locked host memory (enqueue only:
         `ctx.sync()` before reading): the moving section's type columns (`layer`: a DeviceTypesLayer of `dmoving` to read them from), X, Y, the reference's X, Y, the caller's extra 8-byte device
@@ -1125,6 +1150,66 @@ def split_unpack_detail(out, n_labels, n_groups):
     part = lambda q: out[at[q]:at[q + 1]]
     return {"counts": part(0), "confusion": part(1).reshape(L, L), "unlabelled": int(part(2)[0]), "groups": part(3).reshape(G + 1, 2),
             "strict": part(4), "weak": part(5), "untyped": int(part(6)[0])}
+
+
+class DeviceUnpackFeatures(_DeviceHandle):
+    """What same_merge_acc_unpack_features sums, resident beside the two member lists (same_unpack_features_create,
+    csrc/window_unpack_feature.hip): `mov_q` int32 (moving members, F_m) and `ref_q` int32 (reference members, F_r), one fixed-point
+    feature row per MEMBER in CSR order (|q| <= 2**30; None: the side has no column); `member_group` int32 per moving member, the group
+    of the moving CELL (negative: none; None: every cell in group 0) over `n_groups` groups.  Made on the moving members' context;
+    read-only: the worker contexts of the device share it.  Close it before its members."""
+
+    _ENTRY = (None, "same_unpack_features_destroy")
+
+    def __init__(self, mov_members, ref_members, mov_q, ref_q, member_group, n_groups):
+        n_m, n_r = mov_members.n_members, ref_members.n_members
+        side = lambda q, n: np.zeros((n, 0), np.int32) if q is None else np.ascontiguousarray(q, dtype=np.int32)
+        mq, rq = side(mov_q, n_m), side(ref_q, n_r)
+        for q, n, name in ((mq, n_m, "mov_q"), (rq, n_r, "ref_q")):       # (the library reads members x columns: nothing it was not given)
+            if q.ndim != 2 or q.shape[0] != n:
+                raise ValueError(f"{name} has shape {q.shape} for {n} members")
+        g = None if member_group is None else np.ascontiguousarray(member_group, dtype=np.int32)
+        if g is not None and g.shape != (n_m,):
+            raise ValueError(f"member_group has shape {g.shape} for {n_m} moving members")
+        self.F_m, self.F_r, self.n_groups = mq.shape[1], rq.shape[1], int(n_groups)
+        self.n_columns, self.n_rows, self.n_ref_rows = self.F_m + self.F_r, n_m, n_r
+        self.ctx = ctx = mov_members.ctx
+        h = ctypes.c_void_p()
+        with ctx.lock:
+            rc = ctx.lib.same_unpack_features_create(mov_members.handle, ref_members.handle, mq.ctypes.data if mq.size else None, self.F_m,
+                                                     rq.ctypes.data if rq.size else None, self.F_r,
+                                                     None if g is None or not len(g) else g.ctypes.data, self.n_groups, ctypes.byref(h))
+            if rc != 0 and h.value:
+                ctx.lib.same_unpack_features_destroy(h)
+            ctx.check(rc, "same_unpack_features_create")
+        self.handle = h
+
+
+class DeviceUnpackZone(_DeviceHandle):
+    """The zone and the subset of a cell-level distance reading, resident beside a DeviceUnpackFeatures (same_unpack_zone_create):
+    `mov_flags`, `ref_flags` uint8 per MEMBER, bit 0 "zone side", bit 1 "subset side" (None: every bit set); `d2_edges` the thresholds
+    on the SQUARED distance, non-decreasing, 2 .. 65 of them.  Close it before its features."""
+
+    _ENTRY = (None, "same_unpack_zone_destroy")
+
+    def __init__(self, features, mov_flags, ref_flags, d2_edges):
+        flags = lambda f: None if f is None else np.ascontiguousarray(f, dtype=np.uint8)
+        mf, rf = flags(mov_flags), flags(ref_flags)
+        for f, n, name in ((mf, features.n_rows, "mov_flags"), (rf, features.n_ref_rows, "ref_flags")):
+            if f is not None and f.shape != (n,):                         # (the library reads one entry per member: nothing it was not given)
+                raise ValueError(f"{name} has shape {f.shape} for {n} members")
+        e = np.ascontiguousarray(d2_edges, dtype=np.float64).reshape(-1)
+        self.features, self.n_bins = features, len(e) - 1
+        self.ctx = ctx = features.ctx
+        h = ctypes.c_void_p()
+        with ctx.lock:
+            rc = ctx.lib.same_unpack_zone_create(features.handle, None if mf is None or not len(mf) else mf.ctypes.data,
+                                                 None if rf is None or not len(rf) else rf.ctypes.data, e.ctypes.data if len(e) else None,
+                                                 len(e), ctypes.byref(h))
+            if rc != 0 and h.value:
+                ctx.lib.same_unpack_zone_destroy(h)
+            ctx.check(rc, "same_unpack_zone_create")
+        self.handle = h
 
 
 class DeviceUnpackDetail(_DeviceHandle):

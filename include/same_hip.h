@@ -61,7 +61,7 @@ typedef struct same_sweep same_sweep; /* resident state of one lazy-constraint s
  *         only unless noted)                                          same_knn_prune_indexed_dev, same_padded_cost_*_dev, same_tri_*_dev,
  *                                                                     same_area_flip_dev, same_xyorder_sweep_dev, same_orient_*_dev, same_first_candidate_dev
  * part 3  WINDOW path, sections resident (BASELINE cfg 5)             same_section_*, same_window_*, same_merge_acc_*, same_members_*, same_delaunay2d (host),
- *                                                                     same_delaunay_filtered, same_unpack_detail_*
+ *                                                                     same_delaunay_filtered, same_unpack_detail_*, same_unpack_map_*
  * part 4  COMM: RCCL collectives between the ranks' contexts          same_comm_*, same_allgather_dev*, same_allreduce_dev
  * Every declaration cites the reference lines it replaces (file:line into the reference tree).
  * Measurement hooks and opt-in controls that are NOT the path -- runtime-call counters, timers, the spread allocator, the fixed-point
@@ -1112,6 +1112,63 @@ int  same_merge_acc_unpack_features(same_merge_acc *acc, const same_members *mov
                                     const same_unpack_features *feats, const same_unpack_zone *zone /* may be NULL */, int64_t *out,
                                     int64_t out_words, double *out_d2 /* [capacity], may be NULL */,
                                     int64_t *out_ref_member /* [capacity], may be NULL */, int64_t capacity);
+/* The unpacked pairs per moving CELL (csrc/window_unpack_map.hip): same_merge_acc_score_map's reading at cell level -- what
+ * examples/tongue/reproduce_figures.ipynb cells 15-16 and examples/luad cells 12-13 plot, every cell coloured by what the reference CELL
+ * it was put on says of it.  The pairs stay on the device behind same_merge_acc_unpack's own phases; one 16-byte mark per moving member.
+ *   The mark of moving member i (a flat index into `moving`'s CSR):
+ *     ref_member   the flat index into `ref`'s CSR of the reference member the unpack gave it: exactly entry out_ref_member[pair] of
+ *                  same_merge_acc_unpack for the same arguments;
+ *     ref_row      the reference section row that owns that member;
+ *     pair         the pair's index in same_merge_acc_unpack's pair order;
+ *     flags        the SAME_MARK_* bits: MATCHED 1; TYPE_MATCH 2: the two member codes are equal and non-negative (out_counts[2]'s
+ *                  rule); TRUTH_KNOWN 16: the map holds a truth member >= 0 for i; ON_TRUTH 32: matched and ref_member equals it;
+ *                  RANKED 64: the two rank bytes hold ranks.  CONSIDERED and VIOLATING are never set: triangles are a metacell-level
+ *                  reading;
+ *     rank_strict, rank_weak   same_merge_acc_unpack_detail's strict and weak of (col_of_label[code of i], the reference MEMBER's type
+ *                  row), saturated at 254 as same_cell_mark's; 255 with RANKED clear where the member is not ranked: unmatched, no
+ *                  `detail` or one without col_of_label or type rows, a code that is negative or >= n_labels, a label that names no
+ *                  column, a NaN anywhere in the type row.
+ *   An unmatched member's mark is {-1, -1, -1, TRUTH_KNOWN or 0, 255, 255, 0}: no final row names its moving row (or the row has no
+ *   pair, which a non-empty list on a named row cannot).  A merge's final rows name a moving row at most once, so a member has at most
+ *   one pair; the call relies on that, as same_merge_acc_score_map does.
+ *   out_counts[6]: [0 .. 3] exactly same_merge_acc_unpack's for the same arguments; [4] the matched members whose truth is known, [5]
+ *   those of them that are on it.  The marks with MATCHED number [1], those with TYPE_MATCH [2].
+ *   same_unpack_map_create: what the marks are read against and folded into, made on `moving`'s context for these two member objects,
+ *   resident on its device and shared by the worker contexts of that device like same_score_map (at most 32 calling contexts); destroy
+ *   it before the members.  truth_member[i] (host, one per moving member, may be NULL: every member unknown): the flat reference member
+ *   that is member i's true or baseline partner, -1 unknown; SAME_EINVAL for a value < -1 or >= the reference members' count, checked on
+ *   the host before anything is uploaded.  with_tally: the map holds tally[moving members][3] (uint32, zero at first) -- per member in
+ *   how many results folded in so far it was matched, type-matched, on its truth -- added to by 32-bit atomics, results of one study may
+ *   be folded in from several worker contexts.
+ *   same_unpack_map_tally, same_unpack_map_reset: same_score_map_tally's and same_score_map_reset's rules (out_tally: members * 3
+ *   words, may be NULL, SAME_EINVAL when given for a map without a tally; one copy and one wait -- one fill and one wait).
+ *   same_merge_acc_unpack_map: `moving`, `ref`, `strategy` as same_merge_acc_unpack's; `detail` (may be NULL: no ranks) made for `ref`;
+ *   `map` made for these members.  out_marks (may be NULL: counts and tally only): one mark per moving member, any host memory, written
+ *   by the host from a page-locked block of the map and only by a call that succeeds.
+ * What the call asks of the runtime on the accumulator's context: without a pair -- no final row, or none whose moving row has a member
+ * -- what same_merge_acc_unpack asks and nothing more: out_counts[4], [5] are zero, out_marks is written on the host as the unmatched
+ * marks (the map keeps the truth members for the TRUTH_KNOWN bit), the result count goes up by one.  Else same_merge_acc_unpack's own
+ * budget for the same rows and beyond it: TWO launches (pair_of by pair, the marks by member), one copy of the totals (16 bytes) and with
+ * out_marks one copy of the marks, from a device buffer of the map; no wait beyond same_merge_acc_unpack's second, the call's last -- so
+ * THREE copies (four with out_marks) and TWO waits.  No fill -- but a call that lays the accumulator's unpack work buffer fills its
+ * head, one fill, and a calling context's first call on a map (and the first after a call that failed half way) lays its slot: two
+ * fills (pair_of to -1, the slot's totals to zero).  The totals are counted in the map, two sets per calling context of which each
+ * call clears the other's (work_sets.h), and pair_of is returned to -1 member by member: every buffer is left as it was found, so the
+ * unpack, unpack-detail, unpack-feature, score, detail, map, feature calls and this call alternate on one accumulator without a fill.
+ * SAME_EINVAL / SAME_ERANGE as same_merge_acc_unpack, out_counts and out_marks untouched; SAME_EINVAL also for a `map` made for other
+ * members or on another device and a `detail` made for other reference members.  After SAME_ERANGE the tally may hold part of the
+ * refused result: reset it. */
+typedef struct { int32_t ref_member, ref_row, pair; uint8_t flags, rank_strict, rank_weak, reserved; } same_member_mark;   /* 16 bytes */
+typedef struct same_unpack_map same_unpack_map;
+int  same_unpack_map_create(const same_members *moving, const same_members *ref,
+                            const int32_t *truth_member /* host, [moving members], -1 unknown; may be NULL */, int with_tally,
+                            same_unpack_map **out);
+void same_unpack_map_destroy(same_unpack_map *map);
+int  same_unpack_map_tally(same_unpack_map *map, uint32_t *out_tally /* [moving members][3], may be NULL */, int64_t *out_results);
+int  same_unpack_map_reset(same_unpack_map *map);
+int  same_merge_acc_unpack_map(same_merge_acc *acc, const same_members *moving, const same_members *ref, int strategy,
+                               const same_unpack_detail *detail /* may be NULL: no ranks */, same_unpack_map *map,
+                               same_member_mark *out_marks /* [moving members], may be NULL */, int64_t *out_counts /* [6] */);
 
 /* ======================================================================================================================
  * part 4 -- COMM: one communicator per context, RCCL over xGMI

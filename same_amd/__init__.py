@@ -24,7 +24,7 @@ from .variants import sliding_window_variants  # noqa: F401
 from .scores import record_from_counts, score_table, score_unpacked, sliding_window_scores  # noqa: F401
 from .score_details import (CellDetails, CellScoreDetails, ScoreDetails, score_table_details, score_unpacked_details,  # noqa: F401
                             sliding_window_score_details, top_k_counts)
-from .score_maps import ScoreMaps, score_table_maps, sliding_window_score_maps  # noqa: F401
+from .score_maps import CellScoreMaps, ScoreMaps, score_table_maps, score_unpacked_maps, sliding_window_score_maps  # noqa: F401
 from .score_features import (FeatureZones, ScoreFeatures, score_table_features, score_unpacked_features,  # noqa: F401
                              sliding_window_score_features, standard_scale_var)
 from .windows import window_plan  # noqa: F401
@@ -34,7 +34,7 @@ from .eval_utils import check_alignment, check_triangle_violations  # noqa: F401
 
 __version__ = "0.1.0"
 __all__ = [
-    "init_gurobi_params", "init_optim_params", "sliding_window_matching", "sliding_window_incumbent", "sliding_window_sweep", "sliding_window_variants", "sliding_window_scores", "sliding_window_score_details", "sliding_window_score_maps", "score_table_maps", "ScoreMaps", "sliding_window_score_features", "score_table_features", "score_unpacked_features", "ScoreFeatures", "FeatureZones", "standard_scale_var", "score_table_details", "top_k_counts", "ScoreDetails", "CellScoreDetails", "CellDetails", "score_unpacked_details", "score_table", "score_unpacked", "record_from_counts", "run_same", "prepare_same_inputs",
+    "init_gurobi_params", "init_optim_params", "sliding_window_matching", "sliding_window_incumbent", "sliding_window_sweep", "sliding_window_variants", "sliding_window_scores", "sliding_window_score_details", "sliding_window_score_maps", "score_table_maps", "score_unpacked_maps", "ScoreMaps", "CellScoreMaps", "sliding_window_score_features", "score_table_features", "score_unpacked_features", "ScoreFeatures", "FeatureZones", "standard_scale_var", "score_table_details", "top_k_counts", "ScoreDetails", "CellScoreDetails", "CellDetails", "score_unpacked_details", "score_table", "score_unpacked", "record_from_counts", "run_same", "prepare_same_inputs",
     "find_knn_within_radius", "find_knn_with_cell_type_priority", "pair_costs", "dense_cost_matrix",
     "filter_triangles_by_radius", "precompute_triangle_info", "triangle_weights_and_signs",
     "LazyOrientationSweep", "verify_spatial_preservation", "print_violation_report", "triangle_area_flips",

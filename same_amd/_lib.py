@@ -167,6 +167,11 @@ _PROTOTYPES = {
     "same_unpack_zone_create": [c_vp, c_vp, c_vp, c_vp, c_int, ctypes.POINTER(c_vp)],
     "same_unpack_zone_destroy": [c_vp],
     "same_merge_acc_unpack_features": [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64],
+    "same_unpack_map_create": [c_vp, c_vp, c_vp, c_int, ctypes.POINTER(c_vp)],
+    "same_unpack_map_destroy": [c_vp],
+    "same_unpack_map_tally": [c_vp, c_vp, ctypes.POINTER(c_i64)],
+    "same_unpack_map_reset": [c_vp],
+    "same_merge_acc_unpack_map": [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp],
     "same_host_alloc": [c_vp, c_sz, ctypes.POINTER(c_vp)],
     "same_host_free": [c_vp, c_vp],
     "same_comm_unique_id": [c_vp],
@@ -249,6 +254,7 @@ def load():
             L.same_unpack_detail_destroy.restype = None
             L.same_unpack_features_destroy.restype = None
             L.same_unpack_zone_destroy.restype = None
+            L.same_unpack_map_destroy.restype = None
             if L.same_abi_version() != ABI_VERSION:
                 raise SameHipError(-22, "libsame_hip ABI version mismatch")
             _lib = L

@@ -1,5 +1,5 @@
 // window_internal.h -- what the translation units of the device-resident window path share (section.hip, window_stage.hip,
-// window_finish.hip, window_merge.hip, window_score.hip, window_score_detail.hip, window_score_map.hip, window_score_feature.hip, window_unpack.hip, window_unpack_detail.hip, window_unpack_feature.hip, window_caller.hip, window_priority.hip, window_knn_prefix.hip, window_recost.hip): the resident objects behind the
+// window_finish.hip, window_merge.hip, window_score.hip, window_score_detail.hip, window_score_map.hip, window_score_feature.hip, window_unpack.hip, window_unpack_detail.hip, window_unpack_feature.hip, window_unpack_map.hip, window_caller.hip, window_priority.hip, window_knn_prefix.hip, window_recost.hip): the resident objects behind the
 // opaque handles of include/same_hip.h part 4, the per-launch argument blocks, the device side of a window's pair list, the window's
 // logical state (window_state.h: win::State, with the table of what each call requires, leaves and invalidates), the protocol of the merged
 // rows' reader calls (work_sets.h: win::WorkSets), the small host helpers and the batch driver of the window calls.
@@ -470,6 +470,34 @@ struct same_score_map {
     win::MapSlot slots[win::MAP_SLOTS];
 };
 
+// What same_merge_acc_unpack_map keeps beside the counts, resident (same_unpack_map_create, window_unpack_map.hip): per moving MEMBER its
+// truth member (on the device and, for the marks of a result without a pair, on the host) and -- with a tally -- three counters over the
+// results folded in so far; and what a call works in that is not the accumulator's: per calling context a slot of pair_of (the member's
+// pair, idle -1), two sets of the two truth totals (work_sets.h), the device buffer of the marks and the page-locked block they are copied
+// into.  Shared by the worker contexts of the device as same_score_map is; a slot belongs to ONE context.
+namespace win {
+constexpr int UNPACK_MAP_TOTALS = 2;     // words of one set: matched members with a known truth, those on it
+struct UnpackMapSlot {
+    const same_ctx *owner = nullptr;
+    WorkSets sets;                       // laid: the members pair_of is laid for while it is idle and both sets are zero
+    DevBuf pair_of;                      // [mov->m] int32
+    DevBuf marks;                        // [mov->m] same_member_mark
+    void *host_marks = nullptr;          // page-locked, [mov->m] same_member_mark: where the marks' copy lands
+    size_t host_bytes = 0;
+};
+}  // namespace win
+struct same_unpack_map {
+    same_ctx *ctx = nullptr;
+    const same_members *mov = nullptr, *ref = nullptr;
+    int32_t *truth = nullptr;            // [mov->m] flat reference member, -1 unknown; null: every member unknown
+    std::vector<int32_t> h_truth;        // the same on the host (empty: every member unknown)
+    unsigned *tally = nullptr;           // [mov->m][3] matched_in, type_match_in, on_truth_in; null: no tally
+    unsigned long long *totals = nullptr;   // [MAP_SLOTS][2][UNPACK_MAP_TOTALS]
+    int64_t results = 0;                 // calls folded in since the last reset (under `lock`)
+    std::mutex lock;                     // guards `slots`' owners and `results`; never held across device work
+    win::UnpackMapSlot slots[win::MAP_SLOTS];
+};
+
 // The rows of one pass over a window plan on one context (window_merge.hip), and what window_score.hip reads of them.
 struct same_merge_acc {
     same_ctx *ctx = nullptr;
@@ -578,6 +606,15 @@ __device__ __forceinline__ bool labels_agree(int32_t a, int32_t b) { return a >=
 __device__ __forceinline__ int group_at(const int32_t *__restrict__ group_of, int64_t row, int G) {
     const int32_t g = group_of ? group_of[row] : 0;
     return g >= 0 && g < G ? g : G;               // (create refused g >= G)
+}
+// the row of the CSR `off` (n_rows + 1 offsets) that owns member i: the last row whose list starts at or before i and ends behind it
+__device__ __forceinline__ int64_t row_of_member(const int64_t *__restrict__ off, int64_t n_rows, int64_t i) {
+    int64_t lo = 0, hi = n_rows;                  // off[lo] <= i < off[hi]
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (off[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
 }
 // the rank of type column c in a reference type row of T float64 columns: with v = row[c], how many OTHER columns hold a value > v
 // (strict) and how many one >= v (weak) -> whether the row ranks at all: a NaN anywhere in it ranks nothing

@@ -36,16 +36,6 @@ __host__ __device__ inline int64_t bin_words(int L, int G) { return (int64_t)L *
 
 extern __shared__ unsigned lds_bins[];
 
-// the row of the CSR `off` (n_rows + 1 offsets) that owns member i: the last row whose list starts at or before i and ends behind it
-__device__ __forceinline__ int64_t row_of_member(const int64_t *__restrict__ off, int64_t n_rows, int64_t i) {
-    int64_t lo = 0, hi = n_rows;                  // off[lo] <= i < off[hi]
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // LDS and a set alike: [L*L confusion | unlabelled | (G+1) x (pairs, codes agree) | strict[R+1] | weak[R+1] | untyped]
 __global__ __launch_bounds__(NT) void unpack_bins_kernel(const int64_t *__restrict__ pair_ref, const int32_t *__restrict__ pair_mov,
                                                          int64_t pairs, const int64_t *__restrict__ moff, int64_t n_mov, int64_t m_mov,

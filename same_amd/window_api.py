@@ -314,6 +314,18 @@ class _DeviceFrames:
         self.__dict__.setdefault("_score_maps", []).append(made)
         return made
 
+    def unpack_map(self, mov_members, ref_members, truth_member, tally):
+        """`score_map` at cell level: a study's per-CELL map resident beside the two member lists (windows.DeviceUnpackMap):
+        `truth_member` the moving members' true reference members, flat into `ref_members`' CSR (None: none known), `tally` whether
+        results are folded into per-member counters.  One per call -- its tally is a study's own --, kept until close() or until the
+        study closes it."""
+        from .windows import DeviceUnpackMap
+
+        with stage("truth members and the per-member tally to the device"):
+            made = DeviceUnpackMap(mov_members, ref_members, truth_member, tally)
+        self.__dict__.setdefault("_unpack_maps", []).append(made)
+        return made
+
     def score_features(self, mov_q, ref_q, group_of, n_groups, zone=None):
         """A study's fixed-point feature columns resident beside the sections (windows.DeviceScoreFeatures) and, with `zone` =
         (moving flags, reference flags, squared-distance edges), its distance reading (windows.DeviceFeatureZone; else None).  One pair
@@ -467,6 +479,8 @@ class _DeviceFrames:
         for _held, detail in self.__dict__.pop("_unpack_details", {}).values():   # before the members whose type rows they hold
             if detail is not None:
                 detail.close()
+        for made in self.__dict__.pop("_unpack_maps", []):                     # before the members they were made for
+            made.close()
         for made in reversed(self.__dict__.pop("_unpack_features", [])):       # a zone before its features, both before their members
             made.close()
         for _held, members in self.__dict__.pop("_members", {}).values():      # before the section whose rows they list

@@ -788,6 +788,25 @@ class MergeAccumulator(_DeviceHandle):
         return (out[:4], split_score_features(out[4:], features.n_groups, features.n_columns, B), None if dist is None else dist[:n],
                 None if ref_member is None else ref_member[:n])
 
+    def unpack_map(self, mov_members, ref_members, strategy, detail, unpack_map, marks=True):
+        """After finish(): `unpack`'s counts and, per moving MEMBER, its mark (same_merge_acc_unpack_map, csrc/window_unpack_map.hip) --
+        folded into `unpack_map`, a DeviceUnpackMap of the two member lists, whose truth members the marks are read against.  `detail`: a
+        DeviceUnpackDetail of `ref_members` whose label columns and type rows rank the members (None: no ranks).  -> (six int64 counts:
+        `unpack`'s four, matched members with a known truth, those on it; the marks as a MEMBER_MARK array, or None with marks=False).
+        The device's copy of the marks lands in a page-locked block of the map; the array is written from it once the call succeeded.
+        No wait beyond `unpack`'s; leaves the accumulator as `unpack` does."""
+        if strategy not in UNPACK_STRATEGIES:
+            raise ValueError(f"strategy must be one of {tuple(UNPACK_STRATEGIES)}, not {strategy!r}")
+        ctx, counts = self.ctx, np.zeros(6, np.int64)
+        n = mov_members.n_members
+        out = np.empty(n, MEMBER_MARK) if marks else None
+        with ctx.lock:
+            ctx.check(ctx.lib.same_merge_acc_unpack_map(self.handle, mov_members.handle, ref_members.handle, UNPACK_STRATEGIES[strategy],
+                                                        None if detail is None else detail.handle, unpack_map.handle,
+                                                        None if out is None or not n else out.ctypes.data, counts.ctypes.data),
+                      "same_merge_acc_unpack_map")
+        return counts, out
+
     def columns(self, dmoving, dref, n_final, n_types, extra_moving=(), extra_ref=(), layer=None):
         """After finish(): the merged table's columns written by the device straight into page-locked host memory (enqueue only:
         `ctx.sync()` before reading): the moving section's type columns (`layer`: a DeviceTypesLayer of `dmoving` to read them from), X, Y, the reference's X, Y, the caller's extra 8-byte device
@@ -1238,6 +1257,54 @@ class DeviceUnpackDetail(_DeviceHandle):
                 ctx.lib.same_unpack_detail_destroy(h)
             ctx.check(rc, "same_unpack_detail_create")
         self.handle = h
+
+
+# same_member_mark (include/same_hip.h): one record per moving member
+MEMBER_MARK = np.dtype([("ref_member", np.int32), ("ref_row", np.int32), ("pair", np.int32), ("flags", np.uint8),
+                        ("rank_strict", np.uint8), ("rank_weak", np.uint8), ("reserved", np.uint8)])
+assert MEMBER_MARK.itemsize == 16
+MEMBER_TALLY_COLUMNS = ("matched_in", "type_match_in", "on_truth_in")
+
+
+class DeviceUnpackMap(_DeviceHandle):
+    """What same_merge_acc_unpack_map reads its marks against and folds them into, resident beside the two member lists
+    (same_unpack_map_create, csrc/window_unpack_map.hip): `truth_member` int32 per moving member, the flat reference member that is its
+    true or baseline partner, -1 unknown (None: every member unknown); with `with_tally` three uint32 counters per moving member over
+    the results folded in.  Made on the moving members' context; the worker contexts of the device share it.  Close it before its
+    members."""
+
+    _ENTRY = (None, "same_unpack_map_destroy")
+
+    def __init__(self, moving_members, ref_members, truth_member=None, with_tally=True):
+        t = None if truth_member is None else np.ascontiguousarray(truth_member, dtype=np.int32)
+        self.n_members = moving_members.n_members
+        if t is not None and t.shape != (self.n_members,):          # (the library reads one entry per member: nothing it was not given)
+            raise ValueError(f"truth_member has shape {t.shape} for {self.n_members} moving members")
+        self.has_tally = bool(with_tally)
+        self.ctx = ctx = moving_members.ctx
+        h = ctypes.c_void_p()
+        with ctx.lock:
+            rc = ctx.lib.same_unpack_map_create(moving_members.handle, ref_members.handle, None if t is None or not len(t) else t.ctypes.data,
+                                                int(self.has_tally), ctypes.byref(h))
+            if rc != 0 and h.value:
+                ctx.lib.same_unpack_map_destroy(h)
+            ctx.check(rc, "same_unpack_map_create")
+        self.handle = h
+
+    def tally(self):
+        """-> (uint32 (members, 3) over MEMBER_TALLY_COLUMNS, or None for a map without a tally; the results folded in since the creation
+        or the last `reset`)"""
+        ctx = self.ctx
+        out = np.zeros((self.n_members, 3), np.uint32) if self.has_tally else None
+        n = ctypes.c_int64(0)
+        with ctx.lock:
+            ctx.check(ctx.lib.same_unpack_map_tally(self.handle, None if out is None or not len(out) else out.ctypes.data, ctypes.byref(n)),
+                      "same_unpack_map_tally")
+        return out, n.value
+
+    def reset(self):
+        with self.ctx.lock:
+            self.ctx.check(self.ctx.lib.same_unpack_map_reset(self.handle), "same_unpack_map_reset")
 
 
 def caller_tris_windows(states, caller, radius, angle_enabled, cos_thr, near_tol, ignore_same_type, removed=None):
